@@ -42,6 +42,27 @@ def kernel_source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_MAX_VOXELS = 1 << 21      # --dump-outputs: 2 M voxels x (4 float32 fields + 1 float64 index) = 48 MiB at most
+
+
+def dump_outputs(out_dir, cm, n_out):
+    """--dump-outputs: what the caller of the timed path receives for its last step — the voxel centroids of that frame,
+    cm_result_copy of the context that ran it — as DIR/{x,y,z,intensity}.npy (float32) and DIR/n_out.npy (float64).
+    Above DUMP_MAX_VOXELS voxels a fixed sample (PCG64(0), ascending) is written instead, its indices as DIR/index.npy."""
+    import numpy as np
+    n_out = int(n_out)
+    out = cm.result(n_out)
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None
+    if n_out > DUMP_MAX_VOXELS:
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n_out, DUMP_MAX_VOXELS, replace=False))
+        np.save(os.path.join(out_dir, "index.npy"), idx.astype(np.float64))
+    for name in ("x", "y", "z", "intensity"):
+        a = out[name] if idx is None else out[name][idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    np.save(os.path.join(out_dir, "n_out.npy"), np.array([n_out], dtype=np.float64))
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -74,7 +95,13 @@ def parse():
                          "(SURVEY 8f rank 2; off for the headline metric)")
     ap.add_argument("--inflight", type=int, default=3,
                     help="frames in flight per GPU (independent frames on separate HIP streams/contexts)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's voxel centroids as DIR/<name>.npy (rank 0; at most "
+                         "48 MiB, a fixed sample of a larger result) to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main_fused(args):
@@ -159,6 +186,8 @@ def main_fused(args):
     else:
         worst = {k: acc[k] / args.steps for k in acc}
     n_out = int(res.n_out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cm, n_out)
     ms = 1e3 * elapsed / args.steps
     # per GPU: the rank reads its own points once and writes the whole fused cloud once (SURVEY.md 8d's accounting
     # applied to what one GPU does); the exchange is reported beside it, in ms and in table bytes
@@ -350,6 +379,8 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     n_out = int(res.n_out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cms[(args.steps - 1) % inflight], n_out)    # the context run_steps waited on last
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
