@@ -23,6 +23,9 @@ BAD_ARG, HIP_ERROR, NO_DEVICE, CAPACITY, INTERNAL = -1, -2, -3, -4, -5
 FLAG_PROFILE, FLAG_LATEST_WINS, FLAG_OCCUPANCY = 0x1, 0x2, 0x4
 # cm_result.path_flags (CM_PATH_*)
 PATH_LDS_RANK, PATH_BUCKET, PATH_PREDICTED, PATH_REDONE, PATH_PACKED, PATH_SPLIT, PATH_QUANTILE = 1, 2, 4, 8, 16, 32, 64
+PATH_MOTION = 128
+# per-point time field types of cm_set_sensor_time_field (CM_TIME_*)
+TIME_NONE, TIME_F32_S, TIME_U32_NS = 0, 1, 2
 
 # Every symbol include/cloudmerge.h declares (tests/test_capi_symbols.py checks both directions).
 SYMBOLS = [
@@ -35,6 +38,7 @@ SYMBOLS = [
     "cm_set_ground_removal", "cm_ground_copy", "cm_ground_planes",
     "cm_submit_cloud_async", "cm_result_copy_async", "cm_sync", "cm_get_frame_stats",
     "cm_result_publish_async", "cm_publish_wait", "cm_host_register", "cm_host_unregister",
+    "cm_set_sensor_time_field", "cm_set_ego_motion",
 ]
 MAX_ZONES = 8
 
@@ -94,6 +98,25 @@ def make_ground_params(zones_per_sensor, max_iterations=1000, distance_threshold
         for k, (x0, ln, zm) in enumerate(zs):
             g.zones[s][k] = Zone(x0, ln, zm)
     return g
+
+
+class Motion(C.Structure):
+    """cm_motion: ego twist in the common frame, the reference instant and the header stamp of every slot's cloud."""
+    _fields_ = [("v", C.c_float * 3), ("w", C.c_float * 3), ("t_ref_ns", C.c_int64), ("stamp_ns", C.c_int64 * MAX_SENSORS)]
+
+
+def make_motion(v, w, t_ref_ns, stamp_ns):
+    """stamp_ns: one stamp per sensor slot (a sequence, or a dict slot -> stamp); slots not named get t_ref_ns."""
+    m = Motion()
+    m.v = (C.c_float * 3)(*[float(x) for x in v])
+    m.w = (C.c_float * 3)(*[float(x) for x in w])
+    m.t_ref_ns = int(t_ref_ns)
+    items = stamp_ns.items() if isinstance(stamp_ns, dict) else enumerate(stamp_ns)
+    st = [int(t_ref_ns)] * MAX_SENSORS
+    for s, t in items:
+        st[int(s)] = int(t)
+    m.stamp_ns = (C.c_int64 * MAX_SENSORS)(*st)
+    return m
 
 
 class FrameStats(C.Structure):
@@ -174,6 +197,8 @@ def load():
     L.cm_ground_planes.argtypes = [vp, C.POINTER(GroundPlane), u32]
     L.cm_host_alloc.argtypes = [C.POINTER(vp), C.c_size_t]
     L.cm_host_free.argtypes = [vp]
+    L.cm_set_sensor_time_field.argtypes = [vp, u32, u32, u32]
+    L.cm_set_ego_motion.argtypes = [vp, C.POINTER(Motion)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -427,6 +452,15 @@ class CloudMerger:
         st = self._lib.cm_merge_tables(self._ctx, ptrs, cnts, n, C.byref(make_params(params)), C.byref(res))
         self._check(st, "cm_merge_tables", ok=(OK, EMPTY_INPUT))
         return res
+
+    # ---- ego-motion compensation (cm_set_ego_motion) ----
+    def set_time_field(self, sensor, offset, type_):
+        """Per-point time field of a sensor's clouds: byte offset and TIME_NONE / TIME_F32_S / TIME_U32_NS."""
+        self._check(self._lib.cm_set_sensor_time_field(self._ctx, int(sensor), int(offset), int(type_)), "cm_set_sensor_time_field")
+
+    def set_ego_motion(self, motion):
+        """motion: Motion (make_motion) or None to switch compensation off."""
+        self._check(self._lib.cm_set_ego_motion(self._ctx, C.byref(motion) if motion is not None else None), "cm_set_ego_motion")
 
     def stage_times(self):
         t = StageTimes()

@@ -57,6 +57,7 @@ struct Slot {
     uint64_t bytes_h2d = 0;              // payload bytes of the staged cloud that crossed PCIe (0: device submit)
     uint64_t active_bytes_h2d = 0;
     uint64_t gen = 0, active_gen = 0;    // accepted submits so far; the one `active` came from
+    uint32_t time_off = 0, time_type = CM_TIME_NONE;   // per-point time field (cm_set_sensor_time_field)
 };
 
 }  // namespace
@@ -200,6 +201,13 @@ struct cm_ctx {
     uint32_t* h_tile_kept = nullptr;     // writes them straight into pinned host memory (d_tile_kept is its device view)
     uint64_t bytes_d2h = 0;              // result / merged / ground bytes copied to the host since the frame was enqueued
 
+    // ego-motion compensation (cm_kernels_motion.hip): k_motion writes the frame's compensated points here, at their padded
+    // indices, and the descriptor points at them; they live as long as the frame's by-products (until the next enqueue)
+    bool motion_on = false;
+    cm_motion motion;
+    void* motion_buf = nullptr;          // cap_padded x 16 B, allocated by the first cm_set_ego_motion
+    bool last_motion = false;            // the frame enqueued last was compensated (CM_PATH_MOTION)
+
     std::vector<hipEvent_t> prof_ev;
     std::vector<std::string> prof_names;
     size_t prof_used = 0;
@@ -300,7 +308,7 @@ void free_all(cm_ctx* c) {
     F(c->seg_counts); F(c->seg_tile_counts); F(c->seg_groups); F(c->grp); F(c->partials); F(c->out_key); F(c->out_cnt); F(c->merged_total); F(c->out); F(c->merged); F(c->partial); F(c->table_entries); F(c->mask); F(c->sorted_pts); F(c->rows); F(c->d_state_o);
     F(c->stage32); F(c->out32); F(c->rec_a); F(c->rec_b); F(c->dig); F(c->tile_state); F(c->wave_cnt); F(c->records);
     F(c->spl[0]); F(c->spl[1]); F(c->qcnt); F(c->qtot); F(c->qbofs); F(c->qbid); F(c->qbig);
-    F(c->out_other); F(c->out32_other);
+    F(c->out_other); F(c->out32_other); F(c->motion_buf);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
     F(c->d_ground); F(c->d_state_g); F(c->gmask); F(c->zone_off); F(c->d_planes); F(c->hyp0); F(c->valid0); F(c->counts0); F(c->chunk_sums); F(c->bmask); F(c->zcode);
@@ -389,8 +397,12 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
     for (uint32_t s = 0; s < c->max_sensors; ++s) {
         Slot& sl = c->slots[s];
         if (!sl.has_data) continue;
-        const uint64_t nb = static_cast<uint64_t>(base) + round_up(sl.fresh ? sl.staged.n : sl.active.n, CM_TILE);
+        const SlotCloud& sc = sl.fresh ? sl.staged : sl.active;
+        const uint64_t nb = static_cast<uint64_t>(base) + round_up(sc.n, CM_TILE);
         if (nb > c->cap_padded) return fail(c, CM_CAPACITY, "frame exceeds cm_limits.max_points_total");
+        if (c->motion_on && sl.time_type != CM_TIME_NONE && sc.n && static_cast<uint64_t>(sl.time_off) + 4u > sc.step)
+            return fail(c, CM_BAD_ARG, "sensor " + std::to_string(s) + ": time field at byte " + std::to_string(sl.time_off) +
+                                           " does not fit point_step " + std::to_string(sc.step));
         base = static_cast<uint32_t>(nb);
     }
     base = 0;
@@ -433,6 +445,40 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
     f.n_sensors = k;
     f.n_padded = base;
     f.n_tiles = base / CM_TILE;
+    if (consume) c->last_motion = false;
+    if (consume && c->motion_on && f.n_padded) {
+        // Ego-motion compensation: one pre-pass over the raw clouds writes the compensated points at their padded indices,
+        // then every sensor of the descriptor reads those — 16-byte records, identity matrix — and each route runs unchanged.
+        const cm_motion& mo = c->motion;
+        CmMotionDev md;
+        std::memset(&md, 0, sizeof md);
+        md.n_sensors = k;
+        for (uint32_t j = 0; j < k; ++j) {
+            md.s[j] = f.s[j];
+            const Slot& sl = c->slots[f.s[j].slot];
+            md.time_off[j] = sl.time_off;
+            md.time_type[j] = sl.time_type;
+            // (the difference of the stamps in 64 bits, wrapping rather than overflowing, then fp64 seconds rounded to fp32)
+            const int64_t d = static_cast<int64_t>(static_cast<uint64_t>(mo.stamp_ns[f.s[j].slot]) - static_cast<uint64_t>(mo.t_ref_ns));
+            md.dt0[j] = static_cast<float>(static_cast<double>(d) * 1e-9);
+        }
+        for (int a = 0; a < 3; ++a) { md.v[a] = mo.v[a]; md.w[a] = mo.w[a]; }
+        md.k[0] = mo.w[1] * mo.v[2] - mo.w[2] * mo.v[1];       // k = w x v (fp32, no contraction: built with -ffp-contract=off)
+        md.k[1] = mo.w[2] * mo.v[0] - mo.w[0] * mo.v[2];
+        md.k[2] = mo.w[0] * mo.v[1] - mo.w[1] * mo.v[0];
+        prof_mark(c, "k_motion");
+        cmk_motion(c->stream, md, c->motion_buf, f.n_padded);
+        static const float identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+        for (uint32_t j = 0; j < k; ++j) {
+            CmSensorDev& d = f.s[j];
+            d.data = static_cast<const unsigned char*>(c->motion_buf) + static_cast<size_t>(d.base) * 16;
+            d.point_step = 16;
+            d.off_x = 0; d.off_y = 4; d.off_z = 8; d.off_i = 12;
+            d.layout = CM_LAYOUT_XYZI16;
+            std::memcpy(d.m, identity, sizeof d.m);
+        }
+        c->last_motion = true;
+    }
     f.crop_enable = p->crop_enable ? 1u : 0u;
     for (int a = 0; a < 3; ++a) {
         f.crop_min[a] = p->crop_min[a];
@@ -779,7 +825,10 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode = 0, const float* bounds = n
         gm_o = 1;
     }
 
+    if (mode == 1 && c->motion_on) return fail(c, CM_BAD_ARG, "ego-motion compensation is not combined with partial tables (cm_set_ego_motion(NULL) first)");
+
     std::vector<std::unique_lock<std::mutex>> locks;
+    c->prof_used = 0;                                // (k_motion, when compensation is on, is the frame's first stage)
     const int bf = build_frame(c, p, true, locks);
     if (bf != CM_OK) return bf;
     CmFrameDev& f = c->frame;
@@ -793,7 +842,6 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode = 0, const float* bounds = n
     }
     c->have_result = false;
     c->out_is_merged = false;
-    c->prof_used = 0;
     c->last_mode = mode;
     c->bytes_d2h = 0;
     if (c->pub_pending[0]) {
@@ -1280,7 +1328,7 @@ int wait_frame(cm_ctx* c, cm_result* res) {
         r.sort_passes = h.n_passes;
         r.path_flags = (c->lds_rank ? 1u : 0u) | (c->last_v2 ? 2u : 0u) | (c->last_predicted ? 4u : 0u) | (redone ? 8u : 0u) |
                        ((c->last_v2 && c->last_packed) ? 16u : 0u) | ((c->last_v2 && c->last_k3) ? 32u : 0u) |
-                       ((c->last_v2 && c->last_quant) ? 64u : 0u);
+                       ((c->last_v2 && c->last_quant) ? 64u : 0u) | (c->last_motion ? CM_PATH_MOTION : 0u);
         if (c->last_predicted && h.status == CM_OK) {
             // The device sorted by cells of the predicted box (same order); the grid PCL itself would
             // report comes from the cloud's exact bounds, which the frame also produced (A.4 steps 2, 4).
@@ -1817,6 +1865,7 @@ int cm_local_bounds(cm_ctx* c, const cm_params* p, float min_xyz[3], float max_x
     std::lock_guard<std::mutex> lk(c->merge_mu);
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->pending) return fail(c, CM_BAD_ARG, "previous frame not waited for (cm_wait)");
+    if (c->motion_on) return fail(c, CM_BAD_ARG, "ego-motion compensation is not combined with cm_local_bounds (cm_set_ego_motion(NULL) first)");
     for (int a = 0; a < 3; ++a)
         if (!(p->leaf[a] > 0.0f)) return fail(c, CM_BAD_ARG, "leaf must be > 0");
     std::vector<std::unique_lock<std::mutex>> locks;
@@ -1993,6 +2042,35 @@ int cm_merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_
     c->out_is_merged = false;
     if (res) *res = r;
     return r.status;
+}
+
+int cm_set_sensor_time_field(cm_ctx* c, uint32_t sensor, uint32_t offset, uint32_t type) {
+    if (!c) return CM_BAD_ARG;
+    if (sensor >= c->max_sensors) return fail(c, CM_BAD_ARG, "sensor index out of range");
+    if (type != CM_TIME_NONE && type != CM_TIME_F32_S && type != CM_TIME_U32_NS) return fail(c, CM_BAD_ARG, "unknown time field type");
+    std::lock_guard<std::mutex> lk(c->slots[sensor].mu);
+    c->slots[sensor].time_off = offset;
+    c->slots[sensor].time_type = type;
+    return CM_OK;
+}
+
+int cm_set_ego_motion(cm_ctx* c, const cm_motion* m) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (!m) { c->motion_on = false; return CM_OK; }
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(m->v[a]) || !std::isfinite(m->w[a])) return fail(c, CM_BAD_ARG, "ego velocity must be finite");
+    if (!c->motion_buf) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (hipMalloc(&c->motion_buf, static_cast<size_t>(c->cap_padded) * 16) != hipSuccess) {
+            c->motion_buf = nullptr;
+            (void)hipGetLastError();
+            return fail(c, CM_HIP_ERROR, "could not allocate the compensated clouds' buffer");
+        }
+    }
+    c->motion = *m;
+    c->motion_on = true;
+    return CM_OK;
 }
 
 int cm_get_stage_times(cm_ctx* c, cm_stage_times* out) {

@@ -176,3 +176,19 @@ struct CmFrameState {
                                 // what the stage left behind (half-sorted keys, unwritten records) must not be indexed with
 
 #define CM_ROW_TABLE_CAP (1u << 22)   // rows (y,z cell pairs) of the outlier stage's candidate grid
+
+// Ego-motion compensation (cm_kernels_motion.hip): the raw sensor descriptors of the frame plus, per sensor, its time field
+// and the offset of its header stamp from the reference instant; the twist. Passed by value to k_motion.
+#define CM_MOTION_ITEMS 8         // points per thread of k_motion: CM_BLOCK * 8 = 2048 per workgroup, two to a tile
+#define CM_DEV_TIME_NONE 0u       // == CM_TIME_NONE / CM_TIME_F32_S / CM_TIME_U32_NS
+#define CM_DEV_TIME_F32_S 1u
+#define CM_DEV_TIME_U32_NS 2u
+struct CmMotionDev {
+    CmSensorDev s[CM_DEV_MAX_SENSORS];
+    uint32_t time_off[CM_DEV_MAX_SENSORS];
+    uint32_t time_type[CM_DEV_MAX_SENSORS];
+    float dt0[CM_DEV_MAX_SENSORS];   // (float)((double)(stamp - t_ref) * 1e-9), seconds
+    float v[3], w[3];
+    float k[3];                      // w x v, fp32 on the host
+    uint32_t n_sensors;
+};

@@ -118,3 +118,8 @@ void cmkg_planes(hipStream_t s, const CmFrameDev* fd, const CmGroundDev* gd, con
                  const uint32_t* keys_sorted, const uint32_t* vals_sorted, void* band_pts, uint32_t* zone_off,
                  void* hyp0, uint32_t* valid0, uint32_t* counts0, double* chunk_sums, CmGroundPlaneDev* planes,
                  unsigned char* keep_mask, unsigned char* ground_mask, uint32_t n_padded);
+
+// ---- ego-motion compensation (cm_kernels_motion.hip) -------------------------------------------
+// Every point of the frame's clouds (md: raw descriptors) transformed by its sensor's matrix and moved to the reference
+// instant; written as 16-byte x,y,z,intensity records at the point's padded index into `out` (n_padded x 16 bytes).
+void cmk_motion(hipStream_t s, const CmMotionDev& md, void* out, uint32_t n_padded);

@@ -2,6 +2,7 @@
 #include "merger_node.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -135,6 +136,16 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             ok = ok && sidx < c.sensors.size() && c.ground.n_zones[sidx] < CM_MAX_ZONES;
             if (ok) c.ground.zones[sidx][c.ground.n_zones[sidx]++] = z;
         }
+        else if (key == "motion_compensation") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.motion_compensation = v == 1; }
+        else if (key == "time_field") {
+            std::string name, type;
+            uint32_t off = 0;
+            ok = static_cast<bool>(is >> name >> off >> type) && (type == "f32" || type == "u32ns");
+            size_t sidx = c.sensors.size();
+            for (size_t q = 0; q < c.sensors.size(); ++q) if (c.sensors[q].name == name) sidx = q;
+            ok = ok && sidx < c.sensors.size();
+            if (ok) c.time_field[sidx] = NodeConfig::TimeField{off, type == "f32" ? CM_TIME_F32_S : CM_TIME_U32_NS};
+        }
         else if (key == "max_points_total") ok = static_cast<bool>(is >> c.max_points_total);
         else if (key == "device") ok = static_cast<bool>(is >> c.device);
         else ok = false;
@@ -177,6 +188,14 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
             ctx_ = nullptr;
         }
     }
+    for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s) {
+        const int ts = cm_set_sensor_time_field(ctx_, static_cast<uint32_t>(s), cfg_.time_field[s].offset, cfg_.time_field[s].type);
+        if (ts != CM_OK) {
+            error_ = std::string("cm_set_sensor_time_field: ") + cm_last_error(ctx_);
+            cm_destroy(ctx_);
+            ctx_ = nullptr;
+        }
+    }
     clock_ = [] {
         return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(
             std::chrono::system_clock::now().time_since_epoch()).count());
@@ -187,6 +206,45 @@ CloudMergerNode::~CloudMergerNode() {
     if (ctx_) (void)cm_sync(ctx_);
     for (void* p : pipe_registered_) if (p) (void)cm_host_unregister(p);
     if (ctx_) cm_destroy(ctx_);
+}
+
+int CloudMergerNode::set_ego_twist(const float v[3], const float w[3]) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(v[a]) || !std::isfinite(w[a])) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(twist_mu_);
+    for (int a = 0; a < 3; ++a) { twist_v_[a] = v[a]; twist_w_[a] = w[a]; }
+    return CM_OK;
+}
+
+// Enqueues the tick's frame (wait: and waits for it, into *r). With motion_compensation the stamps of the clouds the frame
+// will read, the reference stamp and the twist go to the context first — under every slot's lock, so that no callback
+// replaces a cloud between the stamps being read and the frame taking the clouds over.
+int CloudMergerNode::enqueue_frame(bool wait, cm_result* r) {
+    if (!cfg_.motion_compensation)
+        return wait ? cm_merge_voxelize(ctx_, &cfg_.params, r) : cm_merge_voxelize_async(ctx_, &cfg_.params);
+    int eq;
+    {
+        std::vector<std::unique_lock<std::mutex>> locks;
+        for (auto& m : slot_mu_) locks.emplace_back(m);
+        cm_motion mo{};
+        {
+            std::lock_guard<std::mutex> lk(twist_mu_);
+            for (int a = 0; a < 3; ++a) { mo.v[a] = twist_v_[a]; mo.w[a] = twist_w_[a]; }
+        }
+        const uint64_t newest = newest_stamp();
+        const uint64_t t_ref = (cfg_.stamp_from_inputs && newest) ? newest : clock_();
+        mo.t_ref_ns = static_cast<int64_t>(t_ref);
+        for (size_t s = 0; s < stamp_ns_.size(); ++s) mo.stamp_ns[s] = static_cast<int64_t>(stamp_ns_[s].load());
+        const int ms = cm_set_ego_motion(ctx_, &mo);
+        if (ms != CM_OK) return ms;
+        eq = cm_merge_voxelize_async(ctx_, &cfg_.params);
+        if (eq == CM_OK) motion_t_ref_ = t_ref;
+    }
+    if (eq != CM_OK || !wait) {
+        if (wait && r) { *r = cm_result{}; r->status = eq; }
+        return eq;
+    }
+    return cm_wait(ctx_, r);
 }
 
 uint64_t CloudMergerNode::newest_stamp() const {
@@ -220,7 +278,7 @@ int CloudMergerNode::spin_once_pipelined(cm_result* res) {
     auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(now() - t0).count(); };
     auto t0 = now();
     const uint64_t stamp_enq = newest_stamp();                          // (of the clouds this fuse reads: a callback may deliver the next ones before the wait)
-    const int eq = cm_merge_voxelize_async(ctx_, &cfg_.params);        // fusePointclouds + voxelgrid, enqueued
+    const int eq = enqueue_frame(false, nullptr);                       // fusePointclouds + voxelgrid, enqueued
     if (eq == CM_OK) enq_stamp_ = stamp_enq;
     const double t_enq = since(t0); t0 = now();
     flush_published();                                                  // frame n - 1 goes out while frame n runs
@@ -247,7 +305,7 @@ int CloudMergerNode::spin_once_deferred(cm_result* res) {
         if (st_prev < 0) return st_prev;
     }
     const uint64_t stamp_enq = newest_stamp();
-    const int eq = cm_merge_voxelize_async(ctx_, &cfg_.params);        // frame n: enqueued, not waited for
+    const int eq = enqueue_frame(false, nullptr);                       // frame n: enqueued, not waited for
     if (eq == CM_OK) { frame_pending_ = true; enq_stamp_ = stamp_enq; }
     else if (eq != CM_NOT_READY) { set_error(cm_last_error(ctx_)); return eq; }
     return eq;                                                          // CM_OK: a frame was fused this tick; CM_NOT_READY: none (:575)
@@ -297,7 +355,7 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
         if (cs != CM_OK) { set_error(cm_last_error(ctx_)); return cs; }
     }
     msg.header.seq = seq_++;
-    msg.header.stamp_ns = (cfg_.stamp_from_inputs && enq_stamp_) ? enq_stamp_ : clock_();
+    msg.header.stamp_ns = cfg_.motion_compensation ? motion_t_ref_ : (cfg_.stamp_from_inputs && enq_stamp_) ? enq_stamp_ : clock_();
     msg.header.frame_id = cfg_.base_frame;
     pipe_in_flight_ = true;
     pipe_cur_ ^= 1;
@@ -364,7 +422,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     }
     if (cfg_.pipelined_publish && !cfg_.ground_enable) return (cfg_.deferred_wait && !cfg_.max_stamp_spread_ns) ? spin_once_deferred(res) : spin_once_pipelined(res);   // (the stamp gate above reads what the last frame consumed: known only once it was waited for)
     cm_result r{};
-    const int st = cm_merge_voxelize(ctx_, &cfg_.params, &r);      // fusePointclouds + voxelgrid
+    const int st = enqueue_frame(true, &r);                         // fusePointclouds + voxelgrid
     if (res) *res = r;
     if (st == CM_NOT_READY) return st;                              // :575 — nothing fused this tick
     if (st < 0) { set_error(cm_last_error(ctx_)); return st; }
@@ -394,7 +452,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     msg.header.seq = seq_++;
     uint64_t newest = 0;
     for (const auto& t : stamp_ns_) newest = std::max(newest, t.load());
-    msg.header.stamp_ns = (cfg_.stamp_from_inputs && newest) ? newest : clock_();
+    msg.header.stamp_ns = cfg_.motion_compensation ? motion_t_ref_ : (cfg_.stamp_from_inputs && newest) ? newest : clock_();
     msg.header.frame_id = cfg_.base_frame;
     if (cfg_.ground_enable && publish_ && st != CM_EMPTY_INPUT) {
         // publishPointcloud's other two legs (:203-213): the fused no-ground and ground clouds

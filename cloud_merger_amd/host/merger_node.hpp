@@ -65,6 +65,14 @@ struct NodeConfig {
     cm_ground_params ground{};
     std::string no_ground_topic = "/points_no_ground";   // :516
     std::string ground_topic = "/points_ground";          // :517
+    // Ego-motion compensation (deskew) before the merge (cm_set_ego_motion; an extension, the reference has none). Off by
+    // default. On: every frame moves each sensor's points from the instant they were measured — the cloud's header stamp
+    // plus the point's own time field, when the sensor has one — into the vehicle frame at the stamp the frame is published
+    // with, by the twist set_ego_twist() last gave. That stamp is then fixed when the frame is enqueued (the newest input
+    // stamp with stamp_from_inputs, else the clock at that moment).
+    bool motion_compensation = false;
+    struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
+    TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
 
 // Loads a node description from a text file (an N-sensor configuration instead
@@ -75,6 +83,8 @@ struct NodeConfig {
 //   max_points_total <n> | device <n> | max_stamp_spread_ms <v>
 //   ground <max_iterations> <distance_threshold> <probability> | zone <sensor_name> <x_min> <x_length> <z_max_ground>
 //   ground_outlier <radius> <min_neighbors>   (removeGround's outlierRemoval on every slab's band points, :119)
+//   motion_compensation <0|1> | time_field <sensor_name> <byte_offset> <f32|u32ns>   (ego-motion compensation; f32: seconds,
+//   u32ns: nanoseconds, relative to the cloud's header stamp)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
@@ -117,6 +127,11 @@ public:
     // *accepted (optional): false when the slot still held an unconsumed cloud and this one was dropped (:330) — the
     // call still returns CM_OK like the reference's callback; a lossless replay waits and offers the cloud again.
     int on_cloud(size_t sensor, const PointCloud2& msg, bool* accepted = nullptr);
+
+    // Ego twist for motion_compensation: linear (m/s) and angular (rad/s) velocity of the vehicle in the base frame, taken
+    // as constant over a frame. Callable from any thread; the next fused frame uses it. Returns a cm_status (CM_BAD_ARG: not
+    // finite).
+    int set_ego_twist(const float v[3], const float w[3]);
 
     void set_publisher(Publisher p) { publish_ = std::move(p); }
     void set_clock(Clock c) { clock_ = std::move(c); }
@@ -168,6 +183,11 @@ private:
     // one lock per sensor: a callback's submit + bookkeeping and the loop thread's drop of that sensor's cloud (approximate
     // time synchronisation) exclude each other, so a cloud accepted in between is neither marked consumed nor loses its stamp
     std::vector<std::mutex> slot_mu_;
+    // ego-motion compensation: the twist, and the stamp the frame enqueued last is expressed at (and published with)
+    std::mutex twist_mu_;
+    float twist_v_[3] = {0, 0, 0}, twist_w_[3] = {0, 0, 0};
+    uint64_t motion_t_ref_ = 0;
+    int enqueue_frame(bool wait, cm_result* r);   // cm_merge_voxelize(_async), with the motion of the frame set under the slot locks
 };
 
 }  // namespace cloudmerge

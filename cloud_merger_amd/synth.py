@@ -220,3 +220,82 @@ def velodyne_frame(frame, sensor, rings=32, azimuths=3750):
     xyz = (d * r[:, None]).astype(np.float32)
     inten = rng.uniform(0, 255, len(d)).astype(np.float32)
     return xyz, inten
+
+
+def _rot(axis_angle) -> np.ndarray:
+    """Rodrigues: rotation matrix of an axis-angle vector (float64)."""
+    a = np.asarray(axis_angle, np.float64)
+    th = np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    if th < 1e-12:
+        return np.eye(3) + K
+    return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+
+
+def se3_exp(v, w, dt):
+    """exp(dt (v, w)) for a constant body twist, per element of dt: (R (n,3,3), t (n,3)), float64 (Rodrigues + V matrix)."""
+    dt = np.asarray(dt, np.float64).reshape(-1)
+    v, w = np.asarray(v, np.float64), np.asarray(w, np.float64)
+    phi = dt[:, None] * w[None, :]
+    th = np.linalg.norm(phi, axis=1)
+    K = np.zeros((len(dt), 3, 3))
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0] = -phi[:, 2], phi[:, 1], phi[:, 2]
+    K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -phi[:, 0], -phi[:, 1], phi[:, 0]
+    K2 = K @ K
+    small = th < 1e-8
+    ths = np.where(small, 1.0, th)
+    a = np.where(small, 1.0 - th ** 2 / 6, np.sin(ths) / ths)
+    b = np.where(small, 0.5 - th ** 2 / 24, (1 - np.cos(ths)) / ths ** 2)
+    c = np.where(small, 1.0 / 6 - th ** 2 / 120, (ths - np.sin(ths)) / ths ** 3)
+    eye = np.eye(3)[None]
+    R = eye + a[:, None, None] * K + b[:, None, None] * K2
+    V = eye + b[:, None, None] * K + c[:, None, None] * K2
+    t = np.einsum("nij,nj->ni", V, dt[:, None] * v[None, :])
+    return R, t
+
+
+def moving_scene(n_sensors=4, rings=16, azimuths=2000, v=(15.0, 0.5, 0.0), w=(0.0, 0.0, 0.3), t_ref_ns=1_000_000_000_000,
+                 stamp_spread_ns=50_000_000, sweep_s=0.1, seed=7):
+    """A static scene (ground plane z = -1.8 and four walls: x = +-30, y = +-12, in the vehicle frame at t_ref) seen by
+    n_sensors spinning lidars on a vehicle that moves with the constant body twist (v, w). Sensor s is mounted by a yaw
+    and an offset; its sweep starts at its header stamp (t_ref + a draw in +-stamp_spread_ns) and lasts sweep_s seconds,
+    the azimuth turning with the point's time. Every point is cast from where the sensor was at its own instant.
+    Returns a list of dicts: xyz (n,3 f32, sensor frame, as measured), tau (n, f32 seconds after the stamp),
+    intensity (n, f32), q_xyzw / t_xyz (the mount), m (3x4 f64 mount matrix), stamp_ns (int), truth (n,3 f64: the points
+    in the vehicle frame at t_ref)."""
+    rng = _rng(seed)
+    v, w = np.asarray(v, np.float64), np.asarray(w, np.float64)
+    out = []
+    for s in range(n_sensors):
+        yaw = 2 * np.pi * s / n_sensors + rng.uniform(-0.2, 0.2)
+        mount_t = np.array([1.5 * np.cos(yaw), 0.8 * np.sin(yaw), 0.3 + 0.1 * s])
+        Rm = _rot([0.0, 0.0, yaw])
+        stamp = int(t_ref_ns + int(rng.integers(-stamp_spread_ns, stamp_spread_ns + 1)))
+        n = rings * azimuths
+        tau = np.repeat(np.linspace(0.0, sweep_s, azimuths, endpoint=False)[None, :], rings, 0).reshape(-1)
+        az = (-np.pi + 2 * np.pi * tau / sweep_s + rng.uniform(0, 2 * np.pi / azimuths))
+        el = np.repeat(np.deg2rad(np.linspace(-20.0, 10.0, rings))[:, None], azimuths, 1).reshape(-1)
+        d_s = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)   # ray, sensor frame
+        dt = (stamp - t_ref_ns) * 1e-9 + tau.astype(np.float32).astype(np.float64)
+        Rb, tb = se3_exp(v, w, dt)                                   # vehicle pose at the point's instant (frame at t_ref)
+        Rw = Rb @ Rm[None]                                           # sensor pose
+        o = np.einsum("nij,j->ni", Rb, mount_t) + tb
+        u = np.einsum("nij,nj->ni", Rw, d_s)
+        rmax = np.full(n, 60.0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cand = [np.where(u[:, 2] < -1e-6, (-1.8 - o[:, 2]) / u[:, 2], np.inf)]
+            for ax, c in ((0, 30.0), (0, -30.0), (1, 12.0), (1, -12.0)):
+                tt = (c - o[:, ax]) / u[:, ax]
+                cand.append(np.where(tt > 0, tt, np.inf))
+        r = np.minimum(np.min(np.stack(cand, 1), axis=1), rmax)
+        P = o + r[:, None] * u                                       # hit point, vehicle frame at t_ref
+        # as measured: the hit point in the sensor frame of the point's instant (+ 5 mm range noise)
+        r_meas = r + rng.normal(0, 0.005, n)
+        xyz = (d_s * r_meas[:, None]).astype(np.float32)
+        truth = o + r_meas[:, None] * u
+        inten = rng.uniform(0, 255, n).astype(np.float32)
+        q = yaw_quaternion(yaw)
+        m = np.concatenate([Rm, mount_t[:, None]], 1)
+        out.append(dict(xyz=xyz, tau=tau.astype(np.float32), intensity=inten, q_xyzw=q, t_xyz=mount_t, m=m,
+                        stamp_ns=stamp, truth=truth, hit=P))
+    return out

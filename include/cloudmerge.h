@@ -124,6 +124,8 @@ typedef struct cm_result {
                                   first attempt measured (CM_PATH_BUCKET | CM_PATH_PREDICTED stay set); after a bucket too large
                                   for LDS, or more survivors of the crop than the last frame promised, on the general path */
 
+#define CM_PATH_MOTION 128u    /* the frame's points were motion-compensated (cm_set_ego_motion) before anything else read them */
+
 #define CM_MAX_STAGES 48
 typedef struct cm_stage_times {
     uint32_t n_stages;
@@ -297,6 +299,35 @@ CM_API int cm_set_ground_removal(cm_ctx* ctx, const cm_ground_params* g);
 CM_API int cm_ground_copy(cm_ctx* ctx, void* host_dst, uint64_t capacity_points, uint64_t* n_points);
 /* Planes of the last frame, indexed [sensor * CM_MAX_ZONES + zone]; capacity in entries. */
 CM_API int cm_ground_planes(cm_ctx* ctx, cm_ground_plane* planes, uint32_t capacity);
+
+/* ---- ego-motion compensation (deskew) before the merge (an extension: the reference has none) ----------------------
+ * The merger otherwise fuses clouds as if every point were measured at one instant. With a twist set, every point of
+ * sensor slot s measured at t = stamp_ns[s] + tau (tau: the point's own time field, 0 without one) is moved from the
+ * vehicle frame of that instant into the vehicle frame at t_ref_ns, by the second-order expansion of exp(dt xi) for a
+ * constant body twist xi = (v, w), dt = t - t_ref:
+ *     q = M_s p,  c = w x q,  e = w x c,  k = w x v,  h = dt^2 / 2
+ *     out = q + (dt (c + v) + h (e + k))      fp32, round-to-nearest, no contraction, in this order
+ * It runs as one pre-pass (k_motion) over all clouds of the frame, before the transform's consumers: the voxel grid, the
+ * outlier and ground stages, cm_merged_copy, the CM_GRID_OVERFLOW fallback and a redo inside cm_wait all see the
+ * compensated points. A point with a non-finite coordinate or time stays non-finite and is dropped as before.
+ * Not combined with cm_local_bounds / cm_merge_partial (fused cloud across GPUs): they return CM_BAD_ARG while set. */
+#define CM_TIME_NONE   0u   /* no per-point time: every point of the cloud is at its header stamp */
+#define CM_TIME_F32_S  1u   /* float32 seconds relative to the header stamp (velodyne "time") */
+#define CM_TIME_U32_NS 2u   /* uint32 nanoseconds relative to the header stamp (ouster "t") */
+typedef struct cm_motion {
+    float v[3];                        /* ego linear velocity, m/s, in the common frame */
+    float w[3];                        /* ego angular velocity, rad/s, in the common frame */
+    int64_t t_ref_ns;                  /* the instant the merged cloud is expressed at (the published stamp) */
+    int64_t stamp_ns[CM_MAX_SENSORS];  /* header stamp of the cloud each sensor slot contributes (a stale one: its own) */
+} cm_motion;
+/* Per-point time field of a sensor's clouds: byte offset and CM_TIME_* type. Persistent per sensor, like the transform;
+ * checked against each cloud's point_step when a frame is built (offset + 4 > point_step: that frame returns CM_BAD_ARG,
+ * cm_last_error names the sensor, and the clouds stay fresh). */
+CM_API int cm_set_sensor_time_field(cm_ctx* ctx, uint32_t sensor, uint32_t offset, uint32_t type);
+/* The twist and stamps of the next frames; NULL switches compensation off. Takes effect with the next merge. Non-finite
+ * v or w: CM_BAD_ARG. The compensated clouds' buffer (16 B per point of capacity) is allocated by the first non-NULL
+ * call; if that fails the call returns CM_HIP_ERROR and compensation stays off. */
+CM_API int cm_set_ego_motion(cm_ctx* ctx, const cm_motion* m);
 
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
