@@ -39,6 +39,7 @@ SYMBOLS = [
     "cm_submit_cloud_async", "cm_result_copy_async", "cm_sync", "cm_get_frame_stats",
     "cm_result_publish_async", "cm_publish_wait", "cm_host_register", "cm_host_unregister",
     "cm_set_sensor_time_field", "cm_set_ego_motion",
+    "cm_result_voxel_cov", "cm_result_voxel_cov_device",
 ]
 MAX_ZONES = 8
 
@@ -116,6 +117,35 @@ def make_motion(v, w, t_ref_ns, stamp_ns):
     for s, t in items:
         st[int(s)] = int(t)
     m.stamp_ns = (C.c_int64 * MAX_SENSORS)(*st)
+    return m
+
+
+# per-voxel covariance (cm_result_voxel_cov): cm_voxel_cov.flags
+COV_VALID, COV_INFLATED = 1, 2
+
+
+class CovParams(C.Structure):
+    _fields_ = [("min_points", C.c_uint32), ("eig_mult", C.c_float)]
+
+
+class VoxelCov(C.Structure):
+    """cm_voxel_cov (80 bytes): cov / icov hold (0,0) (1,0) (2,0) (1,1) (2,1) (2,2)."""
+    _fields_ = [("mean", C.c_float * 3), ("count", C.c_uint32), ("cov", C.c_float * 6), ("icov", C.c_float * 6),
+                ("evals", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+VOXEL_COV_DTYPE = np.dtype([("mean", "<f4", (3,)), ("count", "<u4"), ("cov", "<f4", (6,)), ("icov", "<f4", (6,)),
+                            ("evals", "<f4", (3,)), ("flags", "<u4")])
+assert VOXEL_COV_DTYPE.itemsize == C.sizeof(VoxelCov) == 80
+
+
+def sym6_to_3x3(a):
+    """(..., 6) lower-triangle entries in cm_voxel_cov order -> (..., 3, 3) symmetric matrices."""
+    a = np.asarray(a)
+    m = np.empty(a.shape[:-1] + (3, 3), dtype=a.dtype)
+    for q, (i, j) in enumerate(((0, 0), (1, 0), (2, 0), (1, 1), (2, 1), (2, 2))):
+        m[..., i, j] = a[..., q]
+        m[..., j, i] = a[..., q]
     return m
 
 
@@ -199,6 +229,8 @@ def load():
     L.cm_host_free.argtypes = [vp]
     L.cm_set_sensor_time_field.argtypes = [vp, u32, u32, u32]
     L.cm_set_ego_motion.argtypes = [vp, C.POINTER(Motion)]
+    L.cm_result_voxel_cov.argtypes = [vp, C.POINTER(CovParams), vp, u64]
+    L.cm_result_voxel_cov_device.argtypes = [vp, C.POINTER(CovParams), C.POINTER(vp), C.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -461,6 +493,24 @@ class CloudMerger:
     def set_ego_motion(self, motion):
         """motion: Motion (make_motion) or None to switch compensation off."""
         self._check(self._lib.cm_set_ego_motion(self._ctx, C.byref(motion) if motion is not None else None), "cm_set_ego_motion")
+
+    # ---- per-voxel covariance of the last result (cm_result_voxel_cov) ----
+    def voxel_covariance(self, n_out, min_points=6, eig_mult=0.01):
+        """(n_out,) VOXEL_COV_DTYPE array: entry k belongs to result record k (pcl::VoxelGridCovariance's statistics)."""
+        n_out = int(n_out)
+        out = np.zeros(n_out, dtype=VOXEL_COV_DTYPE)
+        p = CovParams(int(min_points), float(eig_mult))
+        self._check(self._lib.cm_result_voxel_cov(self._ctx, C.byref(p), out.ctypes.data if n_out else None, n_out),
+                    "cm_result_voxel_cov")
+        return out
+
+    def voxel_covariance_device(self, min_points=6, eig_mult=0.01):
+        """(device pointer, entries) of the same table, owned by the context and valid until the next merge."""
+        ptr, n = C.c_void_p(), C.c_uint64()
+        p = CovParams(int(min_points), float(eig_mult))
+        self._check(self._lib.cm_result_voxel_cov_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)),
+                    "cm_result_voxel_cov_device")
+        return ptr.value, n.value
 
     def stage_times(self):
         t = StageTimes()

@@ -208,6 +208,18 @@ struct cm_ctx {
     void* motion_buf = nullptr;          // cap_padded x 16 B, allocated by the first cm_set_ego_motion
     bool last_motion = false;            // the frame enqueued last was compensated (CM_PATH_MOTION)
 
+    // per-voxel covariance of the result (cm_kernels_cov.hip), on request after a frame: buffers of its own — no frame reads
+    // them — allocated by the first request and grown with the frames. (The merged records go to `merged`, which
+    // cm_merged_copy fills with the same bytes and which no frame reads either.)
+    uint32_t cov_cap_slots = 0;          // words of each keys / vals buffer
+    uint32_t *cov_keys_a = nullptr, *cov_keys_b = nullptr, *cov_vals_a = nullptr, *cov_vals_b = nullptr;
+    uint32_t *cov_hist = nullptr, *cov_grp = nullptr;    // (cov_cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
+    uint32_t* cov_tile_counts = nullptr; // cap_tiles words: cmk_merged's per-tile offsets
+    uint32_t* cov_words = nullptr;       // [0] merged records, [1] error word of k_cov_reduce, [2..257] digit totals (k_gscan)
+    CmFrameState* cov_state = nullptr;   // the sort's state record
+    void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
+    uint64_t cov_cap_entries = 0;
+
     std::vector<hipEvent_t> prof_ev;
     std::vector<std::string> prof_names;
     size_t prof_used = 0;
@@ -309,6 +321,8 @@ void free_all(cm_ctx* c) {
     F(c->stage32); F(c->out32); F(c->rec_a); F(c->rec_b); F(c->dig); F(c->tile_state); F(c->wave_cnt); F(c->records);
     F(c->spl[0]); F(c->spl[1]); F(c->qcnt); F(c->qtot); F(c->qbofs); F(c->qbid); F(c->qbig);
     F(c->out_other); F(c->out32_other); F(c->motion_buf);
+    F(c->cov_keys_a); F(c->cov_keys_b); F(c->cov_vals_a); F(c->cov_vals_b); F(c->cov_hist); F(c->cov_grp);
+    F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
     F(c->d_ground); F(c->d_state_g); F(c->gmask); F(c->zone_off); F(c->d_planes); F(c->hyp0); F(c->valid0); F(c->counts0); F(c->chunk_sums); F(c->bmask); F(c->zcode);
@@ -1780,6 +1794,133 @@ int cm_merged_copy(cm_ctx* c, void* host_dst, uint64_t capacity, uint64_t* n_poi
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->bytes_d2h += static_cast<uint64_t>(total) * 16;
     }
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_voxel_cov) == 80 && sizeof(CmVoxelCovDev) == sizeof(cm_voxel_cov), "cm_voxel_cov is 80 bytes");
+static_assert(CM_COV_VALID == CM_COV_VALID_DEV && CM_COV_INFLATED == CM_COV_INFLATED_DEV, "flags mirror the header");
+
+namespace {
+
+// The per-voxel covariance table of the last result into c->cov_entries (cm_kernels_cov.hip). Caller holds merge_mu.
+// Launches on the context's stream, reads what the frame left (descriptor, mask, out_key / out_cnt, cell grid) and writes
+// only the cov_* buffers and `merged`: nothing a later frame reads.
+// The refusals of cm_result_voxel_cov*: CM_OK when a table can be computed with *q.
+int voxel_cov_check(cm_ctx* c, const cm_cov_params* p, cm_cov_params* q) {
+    if (!(c->flags & CM_FLAG_OCCUPANCY)) return fail(c, CM_BAD_ARG, "context created without CM_FLAG_OCCUPANCY");
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->have_result) return fail(c, CM_BAD_ARG, "no result");
+    if (c->last_mode != 0) return fail(c, CM_BAD_ARG, "the last result is a partial or merged table (cm_merge_partial / cm_merge_tables)");
+    if (c->result.status != CM_OK) return fail(c, CM_BAD_ARG, std::string("last frame has no voxel grid (") + k_status_names(c->result.status) + ")");
+    *q = p ? *p : cm_cov_params{6u, 0.01f};
+    if (q->min_points < 3) return fail(c, CM_BAD_ARG, "min_points must be at least 3");
+    if (!(q->eig_mult >= 0.0f && q->eig_mult <= 1.0f)) return fail(c, CM_BAD_ARG, "eig_mult must lie in [0, 1]");
+    return CM_OK;
+}
+
+int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
+    const uint64_t n_out = c->result.n_out;
+    if (n_out == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
+    if (n_out > c->cov_cap_entries) {
+        if (c->cov_entries) { (void)hipFree(c->cov_entries); c->cov_entries = nullptr; c->cov_cap_entries = 0; }
+        if (!A(&c->cov_entries, n_out * sizeof(cm_voxel_cov))) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance table");
+        c->cov_cap_entries = n_out;
+    }
+    const CmFrameDev& f = c->frame;
+    const uint32_t nt = f.n_tiles, n_slots = f.n_padded;
+    const uint32_t n_groups = (nt + CM_GROUP - 1) / CM_GROUP, gw = n_groups * CM_RADIX;
+    if (n_slots > c->cov_cap_slots) {
+        uint32_t** bufs[] = {&c->cov_keys_a, &c->cov_keys_b, &c->cov_vals_a, &c->cov_vals_b, &c->cov_hist, &c->cov_grp};
+        for (uint32_t** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
+        c->cov_cap_slots = 0;
+        const size_t tiles = n_slots / CM_TILE, groups = (tiles + CM_GROUP - 1) / CM_GROUP;
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(bufs[k]), static_cast<size_t>(n_slots) * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->cov_hist), tiles * CM_RADIX * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->cov_grp), CM_MAX_PASSES * groups * CM_RADIX * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's buffers");
+        c->cov_cap_slots = n_slots;
+    }
+    if (!c->cov_state) {
+        bool ok = A(reinterpret_cast<void**>(&c->cov_state), sizeof(CmFrameState)) &&
+                  A(reinterpret_cast<void**>(&c->cov_tile_counts), static_cast<size_t>(c->cap_tiles) * 4) &&
+                  A(reinterpret_cast<void**>(&c->cov_words), (2 + CM_RADIX) * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's state");
+    }
+    if (!c->merged) HIP_TRY(c, hipMalloc(&c->merged, static_cast<size_t>(c->cap_padded) * 16));
+    hipStream_t st = c->stream;
+    // the kept points in (sensor, point) order, as cm_merged_copy returns them
+    cmk_merged(st, c->d_frame, c->cov_tile_counts, c->cov_words, c->merged, nt, c->frame_mask);
+    // (voxel number, record index) pairs, sorted by voxel number: as many 8-bit passes as the numbers need
+    uint32_t bits = 1;
+    while (bits < 32 && ((n_out - 1) >> bits)) ++bits;
+    const uint32_t passes = (bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    CmCovGridDev g;
+    for (int a = 0; a < 3; ++a) {
+        g.inv[a] = f.inv_leaf[a];
+        g.min_b[a] = c->cell_min_b[a];
+        g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
+    }
+    HIP_TRY(c, hipMemsetAsync(c->cov_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->cov_words + 1, 0, 4, st));
+    cmk_cov_keys(st, c->merged, c->cov_words, g, c->out_key, static_cast<uint32_t>(n_out), passes, c->cov_state, c->cov_keys_a,
+                 c->cov_hist, c->cov_grp, nt);
+    const bool big = n_groups > CM_DIRECT_GROUPS;
+    uint32_t* totals = c->cov_words + 2;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const bool even = (pass & 1u) == 0;
+        const uint32_t* kin = even ? c->cov_keys_a : c->cov_keys_b;
+        const uint32_t* vin = even ? c->cov_vals_a : c->cov_vals_b;
+        uint32_t* kout = even ? c->cov_keys_b : c->cov_keys_a;
+        uint32_t* vout = even ? c->cov_vals_b : c->cov_vals_a;
+        uint32_t* grp = c->cov_grp + static_cast<size_t>(pass) * gw;
+        if (pass > 0) cmk_hist(st, c->cov_state, kin, c->cov_hist, grp, pass, nt);
+        if (big) cmk_gscan(st, c->cov_state, grp, totals, pass, n_groups);
+        // ballot ranking whatever the context's probe found: stable by construction, the sums' order depends on it
+        cmk_scatter(st, c->cov_state, kin, vin, kout, vout, c->cov_hist, grp, big ? totals : nullptr, pass, nt, n_groups,
+                    n_slots, false);
+    }
+    cmk_cov_reduce(st, c->merged, c->cov_state, c->cov_keys_a, c->cov_vals_a, c->cov_keys_b, c->cov_vals_b, c->out_cnt,
+                   static_cast<uint32_t>(n_out), q.min_points, q.eig_mult, c->cov_entries, c->cov_words + 1);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t err = 0;
+    HIP_TRY(c, hipMemcpyAsync(&err, c->cov_words + 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (err) return fail(c, CM_INTERNAL, "covariance: a voxel's points did not match its count in the result");
+    return CM_OK;
+}
+
+}  // namespace
+
+int cm_result_voxel_cov(cm_ctx* c, const cm_cov_params* p, cm_voxel_cov* host_dst, uint64_t capacity) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_cov_params q;
+    int e = voxel_cov_check(c, p, &q);
+    if (e != CM_OK) return e;
+    if (c->result.n_out > capacity) return fail(c, CM_CAPACITY, "destination too small");
+    if (c->result.n_out && !host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    e = voxel_cov(c, q);
+    if (e != CM_OK) return e;
+    const uint64_t n = c->result.n_out;
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->cov_entries, n * sizeof(cm_voxel_cov), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_voxel_cov);
+    return CM_OK;
+}
+
+int cm_result_voxel_cov_device(cm_ctx* c, const cm_cov_params* p, const void** dev_ptr, uint64_t* n) {
+    if (!c || !dev_ptr || !n) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_cov_params q;
+    int e = voxel_cov_check(c, p, &q);
+    if (e == CM_OK) e = voxel_cov(c, q);
+    if (e != CM_OK) return e;
+    *dev_ptr = c->cov_entries;
+    *n = c->result.n_out;
     return CM_OK;
 }
 

@@ -192,3 +192,21 @@ struct CmMotionDev {
     float k[3];                      // w x v, fp32 on the host
     uint32_t n_sensors;
 };
+
+// Per-voxel covariance (cm_kernels_cov.hip): the grid the result's keys (out_key) are linear indices in — cm_ctx's cell grid
+// and the frame's fp32 1 / leaf — passed by value to k_cov_keys; and one table entry (== cm_voxel_cov, 80 bytes).
+struct CmCovGridDev {
+    float inv[3];
+    int32_t min_b[3];
+    uint32_t div_b[3];
+};
+#define CM_COV_VALID_DEV 1u       // == CM_COV_VALID / CM_COV_INFLATED
+#define CM_COV_INFLATED_DEV 2u
+struct CmVoxelCovDev {
+    float mean[3];
+    uint32_t count;
+    float cov[6];
+    float icov[6];
+    float evals[3];
+    uint32_t flags;
+};

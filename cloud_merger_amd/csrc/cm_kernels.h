@@ -123,3 +123,14 @@ void cmkg_planes(hipStream_t s, const CmFrameDev* fd, const CmGroundDev* gd, con
 // Every point of the frame's clouds (md: raw descriptors) transformed by its sensor's matrix and moved to the reference
 // instant; written as 16-byte x,y,z,intensity records at the point's padded index into `out` (n_padded x 16 bytes).
 void cmk_motion(hipStream_t s, const CmMotionDev& md, void* out, uint32_t n_padded);
+
+// ---- per-voxel covariance of the last result (cm_kernels_cov.hip) --------------------------------
+// recs / total: the frame's kept points as cmk_merged leaves them; keys: n_tiles * CM_TILE words; hist: n_tiles rows; grp: the
+// pass-0 group rows (zeroed). Leaves in st what the radix kernels read (status, n_passes).
+void cmk_cov_keys(hipStream_t s, const void* recs, const uint32_t* total, const CmCovGridDev& g, const uint32_t* out_key,
+                  uint32_t n_out, uint32_t n_passes, CmFrameState* st, uint32_t* keys, uint32_t* hist, uint32_t* grp,
+                  uint32_t n_tiles);
+// One cm_voxel_cov per voxel into out (n_out x 80 B); a run that does not match out_cnt sets *err.
+void cmk_cov_reduce(hipStream_t s, const void* recs, const CmFrameState* st_sort, const uint32_t* keys_a, const uint32_t* vals_a,
+                    const uint32_t* keys_b, const uint32_t* vals_b, const uint32_t* out_cnt, uint32_t n_out, uint32_t min_points,
+                    float eig_mult, void* out, uint32_t* err);

@@ -189,36 +189,6 @@ __device__ __forceinline__ bool plane_inlier(float a, float b, float c, float d,
     return fabsf(__fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(a, p.x), __fmul_rn(b, p.y)), __fmul_rn(c, p.z)), d)) < thr;
 }
 
-__device__ void jacobi3(double a[3][3], double v[3][3]) {
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) v[i][j] = (i == j) ? 1.0 : 0.0;
-    const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2};
-    for (int sweep = 0; sweep < 12; ++sweep)
-        for (int r = 0; r < 3; ++r) {
-            const int p = P[r], q = Q[r];
-            const double apq = a[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            const double theta = __ddiv_rn(__dsub_rn(a[q][q], a[p][p]), __dmul_rn(2.0, apq));
-            const double t = __ddiv_rn(theta >= 0.0 ? 1.0 : -1.0,
-                                       __dadd_rn(fabs(theta), __dsqrt_rn(__dadd_rn(__dmul_rn(theta, theta), 1.0))));
-            const double c = __ddiv_rn(1.0, __dsqrt_rn(__dadd_rn(__dmul_rn(t, t), 1.0))), s = __dmul_rn(t, c);
-            for (int k = 0; k < 3; ++k) {
-                const double akp = a[k][p], akq = a[k][q];
-                a[k][p] = __dsub_rn(__dmul_rn(c, akp), __dmul_rn(s, akq));
-                a[k][q] = __dadd_rn(__dmul_rn(s, akp), __dmul_rn(c, akq));
-            }
-            for (int k = 0; k < 3; ++k) {
-                const double apk = a[p][k], aqk = a[q][k];
-                a[p][k] = __dsub_rn(__dmul_rn(c, apk), __dmul_rn(s, aqk));
-                a[q][k] = __dadd_rn(__dmul_rn(s, apk), __dmul_rn(c, aqk));
-            }
-            for (int k = 0; k < 3; ++k) {
-                const double vkp = v[k][p], vkq = v[k][q];
-                v[k][p] = __dsub_rn(__dmul_rn(c, vkp), __dmul_rn(s, vkq));
-                v[k][q] = __dadd_rn(__dmul_rn(s, vkp), __dmul_rn(c, vkq));
-            }
-        }
-}
-
 __global__ __launch_bounds__(256) void kg_ransac(const CmGroundDev* __restrict__ gd,
                                                  const CmFrameState* __restrict__ st,
                                                  const float4* __restrict__ band_pts,

@@ -329,6 +329,39 @@ CM_API int cm_set_sensor_time_field(cm_ctx* ctx, uint32_t sensor, uint32_t offse
  * call; if that fails the call returns CM_HIP_ERROR and compensation stays off. */
 CM_API int cm_set_ego_motion(cm_ctx* ctx, const cm_motion* m);
 
+/* ---- per-voxel covariance (NDT voxel statistics; an extension: the reference has none) ---------------------------
+ * pcl::VoxelGridCovariance's statistics for every voxel of the last frame's result, computed on request after the frame
+ * (DESIGN.md §12). Entry k belongs to cm_result_copy record k. With p_1..p_n the voxel's points in (sensor, point) order
+ * (the order of cm_merged_copy), fp64, round-to-nearest, no contraction, sums taken one point after the other from 0:
+ *     s_i = sum double(p_i),  S_ij = sum double(p_i) double(p_j),  m_i = s_i / n
+ *     C_ij = ((S_ij - 2 (s_i m_j)) / n + m_i m_j) ((n - 1.0) / n)      i >= j, mirrored
+ * The factor (n - 1) / n is PCL's (VoxelGridCovariance), not the textbook n / (n - 1). lambda_0 <= lambda_1 <= lambda_2 are the
+ * eigenvalues of C. Valid: n >= min_points, lambda_0 >= 0, lambda_1 >= 0, lambda_2 > 0 and a finite inverse. Inflation
+ * (Magnusson eq. 6.11): with mu = eig_mult lambda_2, lambda_0 < mu raises lambda_0 (and lambda_1 if below) to mu and C is rebuilt
+ * as V diag(lambda) V^T (CM_COV_INFLATED). Outputs are rounded to fp32. Voxels below min_points keep an entry (count and mean
+ * only, flags 0) so that the table lines up with the result; PCL leaves them out.
+ * Refused with CM_BAD_ARG (cm_last_error says why): a context without CM_FLAG_OCCUPANCY, no result or a frame in flight, a
+ * last status other than CM_OK, a result of cm_merge_partial / cm_merge_tables, min_points < 3, eig_mult outside [0, 1].
+ * The table lives as long as the result (until the next merge); no later frame depends on whether it was asked for. */
+typedef struct cm_cov_params {
+    uint32_t min_points;               /* PCL's default 6, floor 3 */
+    float eig_mult;                    /* PCL's default 0.01 */
+} cm_cov_params;                       /* NULL: {6, 0.01f} */
+#define CM_COV_VALID    1u
+#define CM_COV_INFLATED 2u
+typedef struct cm_voxel_cov {          /* 80 bytes */
+    float mean[3];
+    uint32_t count;
+    float cov[6];                      /* (0,0) (1,0) (2,0) (1,1) (2,1) (2,2) of C, after inflation; zero below min_points */
+    float icov[6];                     /* same order; zero unless valid */
+    float evals[3];                    /* ascending, after inflation; zero unless valid */
+    uint32_t flags;                    /* CM_COV_* */
+} cm_voxel_cov;
+/* The table copied to the host: capacity in entries (fewer than the result's voxels: CM_CAPACITY). */
+CM_API int cm_result_voxel_cov(cm_ctx* ctx, const cm_cov_params* p, cm_voxel_cov* host_dst, uint64_t capacity);
+/* The same table left in device memory owned by the context: *n entries of 80 bytes at *dev_ptr. */
+CM_API int cm_result_voxel_cov_device(cm_ctx* ctx, const cm_cov_params* p, const void** dev_ptr, uint64_t* n);
+
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
 CM_API int cm_host_free(void* ptr);
