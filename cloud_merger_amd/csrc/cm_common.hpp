@@ -64,6 +64,32 @@ __device__ __forceinline__ bool finite_f32(float v) {
     return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u;
 }
 
+// A voxel's centroid value: its point sum divided by the count, correctly rounded (A.4 step 6). pcl's accumulator starts
+// at +0.0f, so its sum is never -0.0f; a sum formed from the first point on (a -0.0f coordinate or intensity) is moved
+// to +0.0f by the same addition of +0.0f.
+__device__ __forceinline__ float centroid_div(float s, float c) {
+    return __fdiv_rn(__fadd_rn(s, 0.0f), c);
+}
+
+// (out of line: the fallback below is taken by no ordinary sum, and four inlined copies per record cost the finishes)
+__device__ __attribute__((noinline)) float centroid_div_slow(float s, float c) {
+    return centroid_div(s, c);
+}
+
+// The same from rc = RN(1/c) (a count below 2^16), without a division: quotient estimate, exact residual by FMA, one
+// correction — the correctly rounded s / c whenever that is a normal number. Below 2^-126 the correction can round an
+// exact tie to the odd neighbour (c = 6: 9 ulps / 6 = 1.5 ulps gives 1 ulp, not 2; tests/test_division_emulation.py),
+// so lanes whose quotient is not normal (zero included) divide instead: a branch no ordinary sum takes. inf / NaN sums
+// pass through unchanged.
+__device__ __forceinline__ float centroid_div_rc(float s, float c, float rc) {
+    const float q = __fmul_rn(s, rc);
+    if (!finite_f32(q)) return q;
+    const float r = __fmaf_rn(-q, c, s);
+    const float q2 = __fmaf_rn(r, rc, q);
+    if (!(fabsf(q2) >= 0x1p-126f)) return centroid_div_slow(s, c);
+    return q2;
+}
+
 // PassThrough x3 (closed box) + "non-finite points vanish" (A.2, A.3).
 __device__ __forceinline__ bool point_valid(float x, float y, float z, uint32_t crop,
                                             const float* __restrict__ cmin, const float* __restrict__ cmax) {

@@ -829,8 +829,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_seg_reduce(const CmFrameDev* __res
             if (MODE == SEG_CENTROIDS) {
                 const float c = static_cast<float>(a.c);
                 float4 o;
-                o.x = __fdiv_rn(a.x, c); o.y = __fdiv_rn(a.y, c);
-                o.z = __fdiv_rn(a.z, c); o.w = __fdiv_rn(a.i, c);
+                o.x = centroid_div(a.x, c); o.y = centroid_div(a.y, c);
+                o.z = centroid_div(a.z, c); o.w = centroid_div(a.i, c);
                 out[slot] = o;
                 if (out_key) { out_key[slot] = ak; out_cnt[slot] = a.c; }
             } else {                                   // cm_partial_entry: key, count, sx, sy | sz, si, 0, 0
@@ -915,7 +915,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_table_finish(const float4* __restr
         if (write && keep) {
             const uint32_t cnt = __float_as_uint(lo.y);
             const float c = static_cast<float>(cnt);
-            out[slot + ex] = make_float4(__fdiv_rn(lo.z, c), __fdiv_rn(lo.w, c), __fdiv_rn(hi.x, c), __fdiv_rn(hi.y, c));
+            out[slot + ex] = make_float4(centroid_div(lo.z, c), centroid_div(lo.w, c), centroid_div(hi.x, c), centroid_div(hi.y, c));
             if (out_key) { out_key[slot + ex] = __float_as_uint(lo.x); out_cnt[slot + ex] = cnt; }
         }
         slot += tot;

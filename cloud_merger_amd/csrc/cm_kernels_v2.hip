@@ -63,16 +63,6 @@ __device__ __forceinline__ uint32_t block_sum_w(uint32_t v, uint32_t* lds) {
     return tot;
 }
 
-// x / c for a point count c (an integer below 2^16) given rc = RN(1/c): quotient estimate, exact
-// residual by FMA, one correction — the correctly rounded x / c that pcl::VoxelGrid's float division
-// gives (A.4 step 6) whenever x / c is a normal number; inf / NaN sums pass through unchanged.
-__device__ __forceinline__ float div_by_count(float x, float c, float rc) {
-    const float q = __fmul_rn(x, rc);
-    const float r = __fmaf_rn(-q, c, x);
-    const float q2 = __fmaf_rn(r, rc, q);
-    return finite_f32(q) ? q2 : q;
-}
-
 __device__ __forceinline__ uint32_t sensor_of_slot(const CmFrameDev* __restrict__ fd, uint32_t first) {
     uint32_t s = 0;
     for (uint32_t q = 1; q < fd->n_sensors; ++q) s += (first >= fd->s[q].base) ? 1u : 0u;
@@ -1128,8 +1118,8 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
             const float c = static_cast<float>(acc[j].c);
             const float rc = __frcp_rn(c);                  // RN(1/c), shared by the four quotients
             float4 o;
-            o.x = div_by_count(acc[j].x, c, rc); o.y = div_by_count(acc[j].y, c, rc);
-            o.z = div_by_count(acc[j].z, c, rc); o.w = div_by_count(acc[j].i, c, rc);
+            o.x = centroid_div_rc(acc[j].x, c, rc); o.y = centroid_div_rc(acc[j].y, c, rc);
+            o.z = centroid_div_rc(acc[j].z, c, rc); o.w = centroid_div_rc(acc[j].i, c, rc);
             out[slot] = o;
             if (out_key) { out_key[slot] = sk[si[vstart[j]]]; out_cnt[slot] = acc[j].c; }
             ++slot;

@@ -31,13 +31,6 @@
 
 namespace {
 
-__device__ __forceinline__ float div_by_count3(float x, float c, float rc) {   // see div_by_count (cm_kernels_v2.hip)
-    const float q = __fmul_rn(x, rc);
-    const float r = __fmaf_rn(-q, c, x);
-    const float q2 = __fmaf_rn(r, rc, q);
-    return finite_f32(q) ? q2 : q;
-}
-
 // Sum of a float over the wave in a fixed order (the DPP ladder of wave_incl_scan_u32: rows of 16, then across rows),
 // the same in every lane. Deterministic; NOT the sequential order — used for long runs only (see the long-run jobs).
 __device__ __forceinline__ float wave_sum_f32_fixed(float v) {
@@ -730,8 +723,8 @@ __global__ __launch_bounds__(256) void k3_compact(const CmFrameState* __restrict
             const uint32_t cn = stage_cnt[src + q];
             const float c = static_cast<float>(cn);
             const float rc = __frcp_rn(c);                      // RN(1/c), shared by the four quotients
-            out[prefix + q] = make_float4(div_by_count3(sm.x, c, rc), div_by_count3(sm.y, c, rc), div_by_count3(sm.z, c, rc),
-                                          div_by_count3(sm.w, c, rc));
+            out[prefix + q] = make_float4(centroid_div_rc(sm.x, c, rc), centroid_div_rc(sm.y, c, rc), centroid_div_rc(sm.z, c, rc),
+                                          centroid_div_rc(sm.w, c, rc));
             if (out_key) { out_key[prefix + q] = stage_key[src + q]; out_cnt[prefix + q] = cn; }
         }
     }
