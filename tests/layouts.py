@@ -1,0 +1,122 @@
+"""A catalogue of PointCloud2 wire layouts: the same fp32 values written into records of every shape the loaders of
+cm_common.hpp meet. `xyzi16` and `pcl32` take the fast loaders (XYZI16, PCL32); every other layout is close to one of
+them without being it (a permuted or missing field, an odd offset, a decoy where a fast loader would look) and must take
+the generic one.
+
+Every byte of a record that is not one of the four fields holds a per-point decoy: finite floats of 1e4 m to 1e5 m with a
+random sign at the 4-byte slots, 0xFF elsewhere, random values in the extra fields (ring, tag, line, reflectivity, range).
+A loader that reads a wrong offset then gets values that differ from every field, and the result changes. Layouts with a
+per-point time field report its offset and type (capi.TIME_*); the field holds the caller's times, or a decoy without them.
+
+No GPU and no oracle here: the CPU test (tests/test_oracle_cross.py) and the GPU tests (tests/test_layouts.py) use it."""
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+
+from cloud_merger_amd.types import SensorCloud, XYZI_DTYPE
+
+TIME_NONE, TIME_F32_S, TIME_U32_NS = 0, 1, 2          # capi.TIME_* (not imported: this module loads no library)
+
+
+@dataclass(frozen=True)
+class Layout:
+    step: int
+    off: Tuple[int, int, int, Optional[int]]          # x, y, z, intensity (None: no intensity field)
+    fast: str                                         # the loader build_frame must pick: "XYZI16", "PCL32" or "GENERIC"
+    extra: Tuple[Tuple[int, str], ...] = ()           # (offset, numpy dtype) of the extra fields
+    time: Optional[Tuple[int, int]] = None            # (offset, TIME_*) of the per-point time field
+
+
+LAYOUTS = {
+    "xyzi16": Layout(16, (0, 4, 8, 12), "XYZI16"),
+    "pcl32": Layout(32, (0, 4, 8, 16), "PCL32"),
+    "pcl32_i12": Layout(32, (0, 4, 8, 12), "GENERIC"),                       # the PCL32 image, intensity in the pad
+    "zyx_i16": Layout(16, (8, 4, 0, 12), "GENERIC"),
+    "i_first16": Layout(16, (4, 8, 12, 0), "GENERIC"),
+    "xyz_pad16": Layout(16, (0, 4, 8, None), "GENERIC"),                     # the pad at 12 is a decoy, not intensity
+    "xyz12": Layout(12, (0, 4, 8, None), "GENERIC"),
+    "velo22": Layout(22, (0, 4, 8, 12), "GENERIC", ((16, "<u2"),), (18, TIME_F32_S)),
+    "livox18": Layout(18, (0, 4, 8, 12), "GENERIC", ((16, "u1"), (17, "u1"))),
+    "odd17": Layout(17, (1, 5, 9, 13), "GENERIC"),
+    "tail": Layout(19, (2, 6, 10, 15), "GENERIC"),                           # intensity ends the record
+    "ouster48": Layout(48, (0, 4, 8, 16), "GENERIC",
+                       ((20, "<u4"), (24, "<u2"), (26, "<u2"), (32, "<u4")), (20, TIME_U32_NS)),
+}
+# the time-field variants of odd17 and livox18: the time sits at an odd offset
+TIMED = {
+    "odd17_t": Layout(21, (1, 5, 9, 13), "GENERIC", (), (17, TIME_F32_S)),
+    "livox18_t": Layout(23, (0, 4, 8, 12), "GENERIC", ((16, "u1"), (17, "u1")), (19, TIME_U32_NS)),
+}
+ALL = {**LAYOUTS, **TIMED}
+NO_INTENSITY = tuple(k for k, v in ALL.items() if v.off[3] is None)
+
+
+def _put(raw, off, values):
+    """write the bytes of `values` (one scalar per record) at byte `off` of every record"""
+    if not len(raw):
+        return
+    b = np.ascontiguousarray(values).view(np.uint8).reshape(len(raw), -1)
+    raw[:, off:off + b.shape[1]] = b
+
+
+def repack(xyz, intensity, name, rng, tau=None, **kw) -> SensorCloud:
+    """(n,3) float32 xyz and (n,) float32 intensity (None: zeros) as a SensorCloud in layout `name`; the float bits are
+    copied, NaN payloads and signed zeros included. tau: per-point times for the time field (float32 seconds or uint32
+    nanoseconds, per the layout's type); without it the field holds a decoy. kw: q_xyzw, t_xyz, is_dense."""
+    lay = ALL[name]
+    xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
+    n = len(xyz)
+    raw = np.full((n, lay.step), 0xFF, np.uint8)
+    used = set()
+    fields = [(o, 4) for o in lay.off if o is not None] + [(o, np.dtype(t).itemsize) for o, t in lay.extra]
+    if lay.time is not None:
+        fields.append((lay.time[0], 4))
+    for o, w in fields:
+        used |= set(range(o, o + w))
+    for o in range(0, lay.step - 3, 4):                   # finite far-away floats in the free 4-byte slots
+        if not used & set(range(o, o + 4)):
+            _put(raw, o, (rng.uniform(1e4, 1e5, n) * rng.choice([-1.0, 1.0], n)).astype("<f4"))
+    for o, t in lay.extra:
+        info = np.iinfo(np.dtype(t))
+        _put(raw, o, rng.integers(0, int(info.max) + 1, n, dtype=np.int64).astype(t))
+    if lay.time is not None:
+        off, kind = lay.time
+        if tau is not None:
+            _put(raw, off, np.asarray(tau, "<f4" if kind == TIME_F32_S else "<u4"))
+        elif kind == TIME_F32_S:
+            _put(raw, off, rng.uniform(-1e5, -1e4, n).astype("<f4"))
+        else:
+            _put(raw, off, rng.integers(0, 2**32, n, dtype=np.int64).astype("<u4"))
+    for a in range(3):
+        _put(raw, lay.off[a], xyz[:, a])
+    if lay.off[3] is not None:
+        inten = np.zeros(n, "<f4") if intensity is None else np.ascontiguousarray(intensity, dtype="<f4")
+        _put(raw, lay.off[3], inten)
+    return SensorCloud(data=raw, n=n, point_step=lay.step, off_x=lay.off[0], off_y=lay.off[1], off_z=lay.off[2],
+                       off_i=lay.off[3], **kw)
+
+
+def relayout(cloud: SensorCloud, name, rng, tau=None) -> SensorCloud:
+    """an XYZI16 SensorCloud in layout `name`, transform and is_dense kept"""
+    d = cloud.data
+    xyz = np.stack([d["x"], d["y"], d["z"]], axis=1)
+    return repack(xyz, d["intensity"], name, rng, tau=tau, q_xyzw=cloud.q_xyzw, t_xyz=cloud.t_xyz,
+                  is_dense=cloud.is_dense)
+
+
+def unpack(cloud: SensorCloud) -> np.ndarray:
+    """the XYZI16 records a cloud holds (intensity 0 without the field): the inverse of repack, bit for bit"""
+    raw = np.ascontiguousarray(cloud.data).view(np.uint8).reshape(cloud.n, cloud.point_step)
+    a = np.zeros(cloud.n, dtype=XYZI_DTYPE)
+    for f, o in zip(("x", "y", "z", "intensity"), (cloud.off_x, cloud.off_y, cloud.off_z, cloud.off_i)):
+        if o is not None:
+            a[f] = np.ascontiguousarray(raw[:, o:o + 4]).view("<f4").reshape(-1)
+    return a
+
+
+def zero_intensity(cloud: SensorCloud) -> SensorCloud:
+    """an XYZI16 SensorCloud with intensity 0: what a layout without the field must give"""
+    d = cloud.data.copy()
+    d["intensity"] = 0
+    return SensorCloud(data=d, n=cloud.n, q_xyzw=cloud.q_xyzw, t_xyz=cloud.t_xyz, is_dense=cloud.is_dense)

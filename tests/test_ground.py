@@ -18,13 +18,13 @@ FRONT = [(30.0, 30.0, 2.5), (19.0, 11.0, 2.0), (4.0, 15.0, 1.5), (-4.0, 8.0, 0.3
 GP = dict(max_iterations=1000, threshold=0.3, probability=0.99, optimize=True, z_keep_max=3.0, seed=12345)
 
 
-def scene(rng, n, tilt=0.01, ground_sigma=0.03, obj_frac=0.25):
-    """Tilted noisy ground + boxes above it, vehicle frame."""
+def scene(rng, n, tilt=0.01, ground_sigma=0.03, obj_frac=0.25, obj_z=(0.6, 2.9)):
+    """Tilted noisy ground + boxes above it (obj_z: their height range), vehicle frame."""
     ng = int(n * (1 - obj_frac))
     gx, gy = rng.uniform(-15, 60, ng), rng.uniform(-5, 5, ng)
     g = np.stack([gx, gy, -0.05 + tilt * gx + 0.02 * gy + ground_sigma * rng.standard_normal(ng)], 1)
     no = n - ng
-    o = np.stack([rng.uniform(-15, 60, no), rng.uniform(-5, 5, no), rng.uniform(0.6, 2.9, no)], 1)
+    o = np.stack([rng.uniform(-15, 60, no), rng.uniform(-5, 5, no), rng.uniform(*obj_z, no)], 1)
     xyz = np.concatenate([g, o]).astype(np.float32)
     return xyz[rng.permutation(n)]
 
@@ -138,6 +138,39 @@ def test_sample_planes_without_refit_are_bit_exact():
                     got = np.array(g["planes"][s * 8 + k].plane, np.float32)
                     assert same_bits(got, np.array(pl.plane, np.float32)), (iters, s, k, got, pl.plane)
     assert n_planes >= 60
+
+
+# 90 % of the points are clutter inside every slab's band (z from -0.45 to 0.25, the ground at about -0.05 + 0.01 x):
+# with a 1.5 cm threshold few samples are all ground, the stopping rule asks for thousands of hypotheses and every slab
+# runs to max_iterations. kg_ransac scores hypotheses 32 and later itself (kg_score0 only the first 32).
+def clutter_scene(seed, n_sensors=2, n=70_001):
+    rng = np.random.default_rng(seed)
+    return [xyzi_cloud(scene(rng, n, obj_frac=0.9, obj_z=(-0.45, 0.25)), rng.uniform(0, 255, n)) for _ in range(n_sensors)]
+
+
+def test_cluttered_bands_run_past_the_first_round():
+    sensors = clutter_scene(37)
+    params = MergeParams(leaf=(0.1,) * 3, min_points_per_voxel=2, **ROI)
+    gp = dict(GP, threshold=0.015, max_iterations=1000)
+    g, planes = check(sensors, [FRONT] * len(sensors), params, gp)
+    iters = [pl.iterations for pls in planes for pl in pls if pl is not None and pl.found]
+    assert sum(it > 32 for it in iters) >= 2, iters
+    assert len(g["ground"]) > 0
+
+
+def test_cluttered_sample_planes_without_refit_are_bit_exact():
+    sensors = clutter_scene(38)
+    params = MergeParams(leaf=(0.1,) * 3, min_points_per_voxel=0, **ROI)
+    gp = dict(GP, optimize=False, threshold=0.02, max_iterations=150, seed=7)
+    g, planes = check(sensors, [FRONT] * len(sensors), params, gp)
+    n_long = 0
+    for s, pls in enumerate(planes):
+        for k, pl in enumerate(pls):
+            assert pl is not None and pl.found
+            n_long += pl.iterations > 32
+            got = np.array(g["planes"][s * 8 + k].plane, np.float32)
+            assert same_bits(got, np.array(pl.plane, np.float32)), (s, k, got, pl.plane)
+    assert n_long >= 2
 
 
 def test_empty_frame_after_a_ground_frame_reports_no_planes():

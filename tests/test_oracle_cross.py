@@ -5,6 +5,7 @@ import pytest
 
 from cloud_merger_amd import synth
 from oracle import np_oracle, oracle
+from tests import layouts as wl
 from tests.util import assert_centroids_close, same_bits, xyzi_of
 
 
@@ -52,17 +53,61 @@ def test_config3_scaled_crop():
     assert 0 < rep.n_merged < rep.n_in
 
 
-@pytest.mark.parametrize("layout", ["pcl32", "velo22", "xyz12"])
+@pytest.mark.parametrize("layout", list(wl.ALL))
 def test_wire_layouts_agree(layout):
+    """every layout of tests/layouts.py (decoys in every byte that is not a field) gives the oracle the bytes xyzi16
+    gives it; without an intensity field, the bytes xyzi16 with intensity 0 gives"""
     base, params = synth.config2(n_per_sensor=10_000, min_pts=0, layout="xyzi16")
-    other, _ = synth.config2(n_per_sensor=10_000, min_pts=0, layout=layout)
+    rng = np.random.default_rng(sum(map(ord, layout)))
+    others = [[wl.relayout(s, layout, rng) for s in base]]
+    if layout in ("pcl32", "velo22", "xyz12"):                    # synth.pack's own images of these
+        others.append(synth.config2(n_per_sensor=10_000, min_pts=0, layout=layout)[0])
+    for s, o in zip(base, others[0]):
+        want = s.data if layout not in wl.NO_INTENSITY else wl.zero_intensity(s).data
+        assert o.point_step == wl.ALL[layout].step and o.data.nbytes == o.n * o.point_step
+        assert wl.unpack(o).tobytes() == want.tobytes(), "the catalogue's records hold the same bits"
     _, m0, o0, _ = oracle.merge_voxelize(base, params)
-    _, m1, o1, _ = oracle.merge_voxelize(other, params)
-    assert np.array_equal(m0["x"], m1["x"]) and np.array_equal(m0["z"], m1["z"])
-    if layout != "xyz12":
-        assert o0.tobytes() == o1.tobytes()
-    else:
-        assert np.all(o1["intensity"] == 0) and np.array_equal(o0["x"], o1["x"])
+    if layout in wl.NO_INTENSITY:
+        _, mz, oz, _ = oracle.merge_voxelize([wl.zero_intensity(s) for s in base], params)
+    for other in others:
+        _, m1, o1, _ = oracle.merge_voxelize(other, params)
+        assert np.array_equal(m0["x"], m1["x"]) and np.array_equal(m0["z"], m1["z"])
+        if layout not in wl.NO_INTENSITY:
+            assert m0.tobytes() == m1.tobytes() and o0.tobytes() == o1.tobytes()
+        else:
+            assert np.all(o1["intensity"] == 0) and np.array_equal(o0["x"], o1["x"])
+            assert mz.tobytes() == m1.tobytes() and oz.tobytes() == o1.tobytes()
+
+
+def test_layout_decoys_differ_from_every_field():
+    """a 4-byte read at any offset of a record that is not a field's own gives a value that is none of the fields"""
+    rng = np.random.default_rng(3)
+    xyz = rng.uniform(-20, 20, (2_000, 3)).astype(np.float32)
+    inten = rng.uniform(0, 255, 2_000).astype(np.float32)
+    for name, lay in wl.ALL.items():
+        c = wl.repack(xyz, inten, name, rng)
+        raw = c.data.view(np.uint8).reshape(c.n, c.point_step)
+        fields = {o for o in lay.off if o is not None}
+        vals = np.concatenate([xyz, inten[:, None]], axis=1).view(np.uint32)
+        for o in range(c.point_step - 3):
+            if o in fields:
+                continue
+            got = np.ascontiguousarray(raw[:, o:o + 4]).view("<u4").reshape(-1)
+            same = (got[:, None] == vals).any(axis=1)
+            assert not same.any(), (name, o)
+
+
+@pytest.mark.parametrize("layout", ["velo22", "odd17", "pcl32_i12"])
+def test_special_values_through_the_layouts(layout):
+    """the value probes (NaN payloads, signed zeros, subnormals, infinities) come through every layout bit for bit"""
+    from tests import edge_frames as ef
+    frame = ef.value_frame()
+    rng = np.random.default_rng(11)
+    other = [wl.relayout(s, layout, rng) for s in frame.sensors]
+    _, m0, o0, r0 = oracle.merge_voxelize(frame.sensors, frame.params, threads=4, stable=True)
+    _, m1, o1, r1 = oracle.merge_voxelize(other, frame.params, threads=4, stable=True)
+    assert m0.tobytes() == m1.tobytes() and o0.tobytes() == o1.tobytes()
+    assert np.array_equal(r0.cells, r1.cells) and np.array_equal(r0.counts, r1.counts)
 
 
 def test_unstable_vs_stable_within_tolerance():
