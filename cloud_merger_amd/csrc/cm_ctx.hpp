@@ -1,0 +1,211 @@
+// cm_ctx.hpp — the context behind the C-ABI handle, shared by the host translation units (cm_api.cpp: entry points and
+// their argument checks; cm_launch.cpp: frame assembly and launch sequences; cm_route.cpp: the route policy).
+//
+// Owns the HBM layout and the launch sequence; no arithmetic on points happens on the host. There is no
+// CPU fallback of any kind: without a gfx950 device cm_create fails.
+//
+// HBM layout per context (N = padded point capacity, multiples of CM_TILE per sensor):
+//   sensor slots      raw PointCloud2 payloads as submitted (or caller-owned device pointers)
+//   keys_a/b, vals_a/b  4 x N x u32   radix ping-pong: voxel index, padded point index
+//   hist              (N/4096) x 256 u32   digit counts per tile (one coalesced row each)
+//   grp               5 x (N/4096/32) x 256 u32   digit counts per group of 32 tiles, per pass
+//   seg_tile_counts   N/2048 u32      kept voxels per sorted tile (+ totals per 256 tiles)
+//   out               N x 16 B        centroids x,y,z,intensity (ascending voxel index = PCL order)
+//   out_key/out_cnt   N x u32 each    only with CM_FLAG_OCCUPANCY
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/cloudmerge.h"
+#include "cm_device.h"
+#include "cm_kernels.h"
+#include "cm_route.hpp"
+
+// A cloud as a frame sees it: where its payload lies in HBM and how its points are laid out.
+struct SlotCloud {
+    const void* dptr = nullptr;      // an owned buffer of the slot or a caller-owned device pointer
+    uint32_t n = 0, step = 0, ox = 0, oy = 0, oz = 0, oi = 0;
+};
+
+// One sensor. Two owned HBM buffers: the frame that was enqueued last reads `active` (and so do its by-products:
+// cm_merged_copy, cm_ground_copy, the overflow fallback, a hand-back's redo) until the NEXT frame is enqueued;
+// a submit meanwhile always goes to the other buffer and becomes `staged`. Nothing a subscriber thread does can
+// therefore touch what a frame in flight — or its by-products afterwards — read, and cm_submit_cloud never waits for a
+// merge (the reference's callbacks run beside its 10 Hz loop: pc_preprocessing_main.cpp:513, :318-337, :549-584).
+struct Slot {
+    std::mutex mu;
+    void* buf[2] = {nullptr, nullptr};   // owned HBM buffers (host submits)
+    size_t cap[2] = {0, 0};
+    int active_buf = -1;                 // which of them `active` lives in (-1: none / a caller-owned pointer)
+    SlotCloud active, staged;
+    bool has_data = false;               // `active` (or, while fresh, `staged`) holds a cloud
+    bool fresh = false;                  // `staged` holds a cloud no frame has consumed yet
+    bool copy_pending = false;           // its H2D copy was enqueued without waiting (cm_submit_cloud_async): ev_copy tells
+    float m[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_copy = nullptr;
+    uint64_t bytes_h2d = 0;              // payload bytes of the staged cloud that crossed PCIe (0: device submit)
+    uint64_t active_bytes_h2d = 0;
+    uint64_t gen = 0, active_gen = 0;    // accepted submits so far; the one `active` came from
+    uint32_t time_off = 0, time_type = CM_TIME_NONE;   // per-point time field (cm_set_sensor_time_field)
+};
+
+struct cm_ctx {
+    int device = 0;
+    uint32_t flags = 0, max_sensors = 0;
+    uint64_t max_points = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    Slot slots[CM_MAX_SENSORS];
+
+    uint32_t cap_padded = 0, cap_tiles = 0, cap_seg_tiles = 0;
+    uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
+    uint32_t *hist = nullptr, *grp = nullptr, *totals = nullptr, *seg_counts = nullptr, *seg_tile_counts = nullptr, *seg_groups = nullptr;
+    uint32_t cap_groups = 0, frame_seq = 0;
+    void* stage32 = nullptr;             // k3_local's staging for partial tables (32-byte entries)
+    void* out32 = nullptr;               // the result as pcl::PointXYZI images (cm_result_copy with point_step_out 32)
+    float* partials = nullptr;
+    uint32_t *out_key = nullptr, *out_cnt = nullptr, *merged_total = nullptr;
+    void* out = nullptr;
+    void* merged = nullptr;
+    unsigned char* mask = nullptr;       // outlier stage: keep-mask over the padded point indices
+    void* sorted_pts = nullptr;          // outlier stage: points in radius-grid order
+    void* rows = nullptr;                // outlier stage: (y,z)-row ranges
+    CmFrameState* d_state_o = nullptr;   // outlier stage: its grid and counts
+    const unsigned char* frame_mask = nullptr;   // mask of the last frame (nullptr: stage off)
+    void* partial = nullptr;             // cm_partial_entry table of the last cm_merge_partial
+    void* table_entries = nullptr;       // merged entries inside cm_merge_tables
+    int last_mode = 0;                   // what the last result is: 0 centroids, 1 partial table, 2 merged tables
+    CmFrameDev* d_frame = nullptr;
+    CmTileDev* d_tiles = nullptr;        // per-tile entries of the uploaded descriptor (k_setup)
+    CmFrameDev frame_uploaded;
+    bool frame_uploaded_valid = false;
+    CmFrameState* d_state[2] = {nullptr, nullptr};
+    int cur = 0;
+    CmFrameState* h_state = nullptr;     // pinned, written by the last kernel of a frame
+    uint32_t* h_state_dev = nullptr;     // device view of h_state
+    hipEvent_t ev_done = nullptr;
+
+    std::mutex merge_mu;
+    bool pending = false;                // an enqueued frame has not been waited for
+    bool pending_trivial = false;        // ... and it had no kernels (nothing submitted)
+    bool trivial_grid = false;           // ... but, as an empty share of a fused cloud, it has the shared grid
+    float trivial_box[6] = {0, 0, 0, 0, 0, 0};
+    CmFrameDev frame;                    // descriptor of the last enqueued frame
+    FramePlan plan;                      // ... and what it runs
+    RouteState route;
+    bool from_crop = false;
+    uint64_t n_in = 0;
+    uint32_t n_sensors_used = 0;
+    cm_result result;
+    bool have_result = false;
+
+    // zone-wise ground removal (cm_kernels_ground.hip)
+    bool ground_on = false;
+    CmGroundDev ground;                  // host copy of the slab table
+    bool ground_uploaded = false;
+    CmGroundDev* d_ground = nullptr;
+    CmFrameState* d_state_g = nullptr;   // state of the slab sort
+    unsigned char* gmask = nullptr;      // ground points of the last frame (padded index space)
+    uint32_t* zone_off = nullptr;
+    CmGroundPlaneDev* d_planes = nullptr;
+    void* hyp0 = nullptr;                // first round of hypotheses of every slab: planes, validity, inlier counts
+    uint32_t *valid0 = nullptr, *counts0 = nullptr;
+    double* chunk_sums = nullptr;        // least-squares sums per chunk of band points
+    bool frame_had_ground = false;
+    float ground_outlier_radius = 0.f;   // > 0: radius filter on every slab's band points that are not ground (:119)
+    uint32_t ground_outlier_min_nb = 0;
+    unsigned char* bmask = nullptr;      // those points (input of that filter)
+    unsigned char* zcode = nullptr;      // slab of every band point
+
+    // bucket path (cm_kernels_v2.hip)
+    void *rec_a = nullptr, *rec_b = nullptr;      // 16-byte point records, ping-pong
+    unsigned char* dig = nullptr;        // next digit of every record
+    unsigned long long* tile_state = nullptr;     // published kept-voxel counts of the local finish
+    uint32_t* wave_cnt = nullptr;                 // records k2_hist0 packed per wave (frames whose crop box drops most points)
+    float* records = nullptr;            // min/max/count per tile
+    int cell_min_b[3] = {0, 0, 0}, cell_div_b[3] = {1, 1, 1};   // grid the cells in out_key are relative to
+
+    // pipelined publish (cm_result_publish_async): the result buffers exist twice, so that the copy-out of frame n runs on
+    // its own stream beside the kernels of frame n + 1
+    void* out_other = nullptr;           // the result buffer the frame in flight does NOT write
+    void* out32_other = nullptr;
+    hipStream_t pub_stream = nullptr;
+    hipEvent_t ev_pub[2] = {nullptr, nullptr};   // [0]: the last copy-out that read `out`, [1]: ... `out_other`
+    bool pub_pending[2] = {false, false};
+
+    // quantile passes (cm_kernels_v4.hip): one global pass into buckets cut at the last frame's quantiles
+    uint32_t* spl[2] = {nullptr, nullptr};   // splitters: route.spl_cur says which one the next frame reads
+    uint32_t *qcnt = nullptr, *qtot = nullptr, *qbofs = nullptr;  // per-tile bucket counts / prefixes, bucket totals, bucket starts
+    uint32_t* qbig = nullptr;                                     // buckets beyond CM4_CAP records: count, then their numbers
+    uint16_t* qbid = nullptr;            // the bucket of every padded slot
+
+    // per-sensor figures of the last enqueued frame (cm_frame_stats)
+    uint32_t stats_n_sensors = 0;
+    uint32_t stats_sensor[CM_MAX_SENSORS] = {0}, stats_n[CM_MAX_SENSORS] = {0}, stats_fresh[CM_MAX_SENSORS] = {0};
+    uint64_t stats_bytes[CM_MAX_SENSORS] = {0}, stats_gen[CM_MAX_SENSORS] = {0};
+    uint32_t* d_tile_kept = nullptr;     // per 4096-slot tile: points that passed crop / masks and entered the sort — the first scatter
+    uint32_t* h_tile_kept = nullptr;     // writes them straight into pinned host memory (d_tile_kept is its device view)
+    uint64_t bytes_d2h = 0;              // result / merged / ground bytes copied to the host since the frame was enqueued
+
+    // ego-motion compensation (cm_kernels_motion.hip): k_motion writes the frame's compensated points here, at their padded
+    // indices, and the descriptor points at them; they live as long as the frame's by-products (until the next enqueue)
+    bool motion_on = false;
+    cm_motion motion;
+    void* motion_buf = nullptr;          // cap_padded x 16 B, allocated by the first cm_set_ego_motion
+    bool last_motion = false;            // the frame enqueued last was compensated (CM_PATH_MOTION)
+
+    // per-voxel covariance of the result (cm_kernels_cov.hip), on request after a frame: buffers of its own — no frame reads
+    // them — allocated by the first request and grown with the frames. (The merged records go to `merged`, which
+    // cm_merged_copy fills with the same bytes and which no frame reads either.)
+    uint32_t cov_cap_slots = 0;          // words of each keys / vals buffer
+    uint32_t *cov_keys_a = nullptr, *cov_keys_b = nullptr, *cov_vals_a = nullptr, *cov_vals_b = nullptr;
+    uint32_t *cov_hist = nullptr, *cov_grp = nullptr;    // (cov_cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
+    uint32_t* cov_tile_counts = nullptr; // cap_tiles words: cmk_merged's per-tile offsets
+    uint32_t* cov_words = nullptr;       // [0] merged records, [1] error word of k_cov_reduce, [2..257] digit totals (k_gscan)
+    CmFrameState* cov_state = nullptr;   // the sort's state record
+    void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
+    uint64_t cov_cap_entries = 0;
+
+    std::vector<hipEvent_t> prof_ev;
+    std::vector<std::string> prof_names;
+    size_t prof_used = 0;
+    cm_stage_times stage_times;
+
+    std::mutex err_mu;
+    std::string err;
+};
+
+// (subscriber threads and the loop thread may fail at the same time — an oversize cloud beside a refused merge — and a third
+// thread may be reading the text: the string is only touched under its own lock, and cm_last_error hands out a copy)
+inline int fail(cm_ctx* c, int code, const std::string& what) {
+    if (c) { std::lock_guard<std::mutex> lk(c->err_mu); c->err = what; }
+    return code;
+}
+
+#define HIP_TRY(c, call)                                                                        \
+    do {                                                                                        \
+        hipError_t e__ = (call);                                                                \
+        if (e__ != hipSuccess)                                                                  \
+            return fail((c), CM_HIP_ERROR, std::string(#call) + ": " + hipGetErrorString(e__)); \
+    } while (0)
+
+inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
+
+// cm_launch.cpp. Every one of them is called with merge_mu held.
+// Builds the frame descriptor in c->frame (consume: the frame takes the sensors' fresh clouds; false: a peek).
+int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::unique_lock<std::mutex>>& locks);
+// The frame's points that `mask` keeps (nullptr: every valid one) as 16-byte records in (sensor, point) order into `out`,
+// and their number (a host round trip). tile_counts: cap_tiles words.
+int fuse_points(cm_ctx* c, uint32_t* tile_counts, void* out, const unsigned char* mask, uint32_t* total);
+// k_minmax over the uploaded descriptor and a host round trip: the bounds of the frame's valid points and their count.
+int measure_bounds(cm_ctx* c, float mn[3], float mx[3], uint64_t* n_valid);
+// mode 0: the path (centroids). mode 1: partial table of per-voxel sums (fused cloud across GPUs); `bounds` (min xyz,
+// max xyz of the whole fused cloud) then fixes the grid unless the crop box does.
+int enqueue(cm_ctx* c, const cm_params* p, int mode = 0, const float* bounds = nullptr);
+int wait_frame(cm_ctx* c, cm_result* res);
+int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_entries, uint32_t n_tables, const cm_params* p,
+                 cm_result* res);
+int voxel_cov(cm_ctx* c, const cm_cov_params& q);

@@ -293,7 +293,7 @@ int CloudMergerNode::spin_once_pipelined(cm_result* res) {
 // spin_once with NodeConfig::deferred_wait (on top of pipelined_publish): the frame enqueued by the LAST call is waited for and
 // its copy-out started, then this tick's frame is enqueued and the call returns without waiting for it — the kernels of frame
 // n run while the subscriber callbacks of tick n + 1 copy their clouds to the device (a sensor's submit goes to the buffer
-// the frame in flight does not read: cm_api.cpp Slot). The return value says whether THIS tick fused a frame (CM_OK /
+// the frame in flight does not read: cm_ctx.hpp Slot). The return value says whether THIS tick fused a frame (CM_OK /
 // CM_NOT_READY, as always); `res` is the PREVIOUS frame's result (zero when there was none to wait for).
 int CloudMergerNode::spin_once_deferred(cm_result* res) {
     if (res) *res = cm_result{};
