@@ -24,6 +24,8 @@ FLAG_PROFILE, FLAG_LATEST_WINS, FLAG_OCCUPANCY = 0x1, 0x2, 0x4
 # cm_result.path_flags (CM_PATH_*)
 PATH_LDS_RANK, PATH_BUCKET, PATH_PREDICTED, PATH_REDONE, PATH_PACKED, PATH_SPLIT, PATH_QUANTILE = 1, 2, 4, 8, 16, 32, 64
 PATH_MOTION = 128
+PATH_SOR = 256
+SOR_MAX_K = 64
 # per-point time field types of cm_set_sensor_time_field (CM_TIME_*)
 TIME_NONE, TIME_F32_S, TIME_U32_NS = 0, 1, 2
 
@@ -40,6 +42,7 @@ SYMBOLS = [
     "cm_result_publish_async", "cm_publish_wait", "cm_host_register", "cm_host_unregister",
     "cm_set_sensor_time_field", "cm_set_ego_motion",
     "cm_result_voxel_cov", "cm_result_voxel_cov_device",
+    "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
 ]
 MAX_ZONES = 8
 
@@ -149,6 +152,16 @@ def sym6_to_3x3(a):
     return m
 
 
+class SorParams(C.Structure):
+    """cm_sor_params: pcl::StatisticalOutlierRemoval's setMeanK / setStddevMulThresh and the search grid's cell (0: auto)."""
+    _fields_ = [("mean_k", C.c_uint32), ("std_mul", C.c_float), ("search_cell", C.c_float), ("_pad", C.c_uint32)]
+
+
+class SorStats(C.Structure):
+    _fields_ = [("n_valid", C.c_uint64), ("n_removed", C.c_uint64), ("mean", C.c_double), ("stddev", C.c_double),
+                ("threshold", C.c_double)]
+
+
 class FrameStats(C.Structure):
     _fields_ = [("n_sensors", C.c_uint32), ("_pad", C.c_uint32), ("sensor", C.c_uint32 * MAX_SENSORS),
                 ("n_in", C.c_uint32 * MAX_SENSORS), ("n_kept", C.c_uint32 * MAX_SENSORS), ("fresh", C.c_uint32 * MAX_SENSORS),
@@ -229,6 +242,9 @@ def load():
     L.cm_host_free.argtypes = [vp]
     L.cm_set_sensor_time_field.argtypes = [vp, u32, u32, u32]
     L.cm_set_ego_motion.argtypes = [vp, C.POINTER(Motion)]
+    L.cm_set_statistical_outlier.argtypes = [vp, C.POINTER(SorParams)]
+    L.cm_get_sor_stats.argtypes = [vp, C.POINTER(SorStats)]
+    L.cm_sor_distances_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_result_voxel_cov.argtypes = [vp, C.POINTER(CovParams), vp, u64]
     L.cm_result_voxel_cov_device.argtypes = [vp, C.POINTER(CovParams), C.POINTER(vp), C.POINTER(u64)]
     for name in SYMBOLS:
@@ -511,6 +527,29 @@ class CloudMerger:
         self._check(self._lib.cm_result_voxel_cov_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)),
                     "cm_result_voxel_cov_device")
         return ptr.value, n.value
+
+    # ---- statistical outlier removal before the voxel grid (cm_set_statistical_outlier) ----
+    def set_statistical_outlier(self, mean_k, std_mul=1.0, search_cell=0.0):
+        """mean_k None switches the stage off; takes effect with the next merge."""
+        if mean_k is None:
+            self._check(self._lib.cm_set_statistical_outlier(self._ctx, None), "cm_set_statistical_outlier")
+            return
+        p = SorParams(int(mean_k), float(std_mul), float(search_cell), 0)
+        self._check(self._lib.cm_set_statistical_outlier(self._ctx, C.byref(p)), "cm_set_statistical_outlier")
+
+    def sor_stats(self):
+        """SorStats of the last waited-for frame: n_valid, n_removed, mean, stddev, threshold."""
+        s = SorStats()
+        self._check(self._lib.cm_get_sor_stats(self._ctx, C.byref(s)), "cm_get_sor_stats")
+        return s
+
+    def sor_distances(self, capacity):
+        """float32 d_i of the stage's input in (sensor, point) order."""
+        out = np.zeros(max(int(capacity), 1), dtype=np.float32)
+        n = C.c_uint64()
+        self._check(self._lib.cm_sor_distances_copy(self._ctx, out.ctypes.data, int(capacity), C.byref(n)),
+                    "cm_sor_distances_copy")
+        return out[: n.value].copy()
 
     def stage_times(self):
         t = StageTimes()

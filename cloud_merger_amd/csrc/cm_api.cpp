@@ -49,6 +49,7 @@ void free_all(cm_ctx* c) {
     F(c->out_other); F(c->out32_other); F(c->motion_buf);
     F(c->cov_keys_a); F(c->cov_keys_b); F(c->cov_vals_a); F(c->cov_vals_b); F(c->cov_hist); F(c->cov_grp);
     F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
+    F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
     F(c->d_ground); F(c->d_state_g); F(c->gmask); F(c->zone_off); F(c->d_planes); F(c->hyp0); F(c->valid0); F(c->counts0); F(c->chunk_sums); F(c->bmask); F(c->zcode);
@@ -619,6 +620,7 @@ int cm_local_bounds(cm_ctx* c, const cm_params* p, float min_xyz[3], float max_x
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->pending) return fail(c, CM_BAD_ARG, "previous frame not waited for (cm_wait)");
     if (c->motion_on) return fail(c, CM_BAD_ARG, "ego-motion compensation is not combined with cm_local_bounds (cm_set_ego_motion(NULL) first)");
+    if (c->sor_on) return fail(c, CM_BAD_ARG, "statistical outlier removal is not combined with cm_local_bounds (cm_set_statistical_outlier(NULL) first)");
     for (int a = 0; a < 3; ++a)
         if (!(p->leaf[a] > 0.0f)) return fail(c, CM_BAD_ARG, "leaf must be > 0");
     std::vector<std::unique_lock<std::mutex>> locks;
@@ -701,6 +703,63 @@ int cm_set_ego_motion(cm_ctx* c, const cm_motion* m) {
     }
     c->motion = *m;
     c->motion_on = true;
+    return CM_OK;
+}
+
+int cm_set_statistical_outlier(cm_ctx* c, const cm_sor_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (!p) { c->sor_on = false; return CM_OK; }
+    if (p->mean_k < 1 || p->mean_k > CM_SOR_MAX_K) return fail(c, CM_BAD_ARG, "mean_k must be 1..64");
+    if (!std::isfinite(p->std_mul)) return fail(c, CM_BAD_ARG, "std_mul must be finite");
+    if (!(p->search_cell >= 0.0f) || !std::isfinite(p->search_cell)) return fail(c, CM_BAD_ARG, "search_cell must be finite and >= 0");
+    const size_t npad = c->cap_padded;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto grab = [&](void** ptr, size_t bytes) {
+        if (*ptr) return true;
+        if (hipMalloc(ptr, bytes) == hipSuccess) return true;
+        *ptr = nullptr;
+        (void)hipGetLastError();
+        return false;
+    };
+    bool ok = grab(reinterpret_cast<void**>(&c->sor_d), npad * 4) && grab(&c->sor_list, npad * 8) &&
+              grab(reinterpret_cast<void**>(&c->sor_words), CM_SOR_WORDS * 8) && grab(reinterpret_cast<void**>(&c->mask), npad) &&
+              grab(&c->sorted_pts, npad * 16) && grab(&c->rows, static_cast<size_t>(CM_ROW_TABLE_CAP) * 8) &&
+              grab(reinterpret_cast<void**>(&c->d_state_o), sizeof(CmFrameState));
+    if (!ok) return fail(c, CM_HIP_ERROR, "could not allocate the statistical outlier stage's buffers");
+    c->sor = *p;
+    c->sor_on = true;
+    return CM_OK;
+}
+
+int cm_get_sor_stats(cm_ctx* c, cm_sor_stats* out) {
+    if (!c || !out) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    std::memset(out, 0, sizeof *out);
+    if (c->have_result && c->last_sor) *out = c->sor_stats;
+    return CM_OK;
+}
+
+int cm_sor_distances_copy(cm_ctx* c, float* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!c || !n) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    *n = 0;
+    if (c->pending) return fail(c, CM_BAD_ARG, "frame in flight (cm_wait first)");
+    if (!c->have_result || !c->last_sor) return fail(c, CM_BAD_ARG, "the last frame did not run statistical outlier removal");
+    const uint32_t np = c->frame.n_padded;
+    if (c->pending_trivial || np == 0 || c->result.status < 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<uint32_t> all(np);
+    HIP_TRY(c, hipMemcpyAsync(all.data(), c->sor_d, static_cast<size_t>(np) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    uint64_t m = 0;
+    for (uint32_t v : all) m += v != 0xFFFFFFFFu;
+    *n = m;
+    if (m > capacity) return fail(c, CM_CAPACITY, "destination too small");
+    if (m && !host_dst) return CM_BAD_ARG;
+    uint64_t o = 0;
+    for (uint32_t v : all)
+        if (v != 0xFFFFFFFFu) std::memcpy(host_dst + o++, &v, 4);
     return CM_OK;
 }
 

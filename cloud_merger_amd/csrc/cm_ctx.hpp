@@ -169,6 +169,17 @@ struct cm_ctx {
     void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
     uint64_t cov_cap_entries = 0;
 
+    // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
+    // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
+    bool sor_on = false;
+    cm_sor_params sor;
+    float* sor_d = nullptr;              // cap_padded floats: d_i per padded index (0xFFFFFFFF: not in the stage's input)
+    void* sor_list = nullptr;            // cap_padded x 8 B: the points the first search launch could not finish, and their bound
+    unsigned long long* sor_words = nullptr;   // CM_SOR_WORDS: bins, list count, stats record
+    bool last_sor = false;               // the frame enqueued last ran the stage
+    cm_sor_stats sor_stats;              // ... its figures, read back by cm_wait
+    double sor_last_mean = 0.0;          // mean distance of the last frame that had one (search_cell 0)
+
     std::vector<hipEvent_t> prof_ev;
     std::vector<std::string> prof_names;
     size_t prof_used = 0;

@@ -210,3 +210,14 @@ struct CmVoxelCovDev {
     float evals[3];
     uint32_t flags;
 };
+
+// Statistical outlier removal (cm_kernels_sor.hip): the stage's word array (u64): per-exponent bins of d_i and of
+// fp32(d_i * d_i), the count of the second launch's list, then the stats record (== cm_sor_stats).
+#define CM_SOR_KMAX 64
+#define CM_SOR_WORD_LIST 512
+#define CM_SOR_WORD_STATS 514
+#define CM_SOR_WORDS 520
+struct CmSorStatsDev {
+    unsigned long long n_valid, n_removed;
+    double mean, stddev, threshold;
+};

@@ -17,6 +17,11 @@ void cmk_outlier_mask(hipStream_t s, const CmFrameDev* fd, const CmFrameState* s
                       const uint32_t* vals_a, const uint32_t* keys_b, const uint32_t* vals_b, void* sorted_pts,
                       void* rows, unsigned char* mask, uint32_t n_padded, const unsigned char* cls, uint32_t* pend_n,
                       bool already_gathered = false);
+// ... its first half, which the statistical outlier stage shares: gather into sorted order (unless the bucket sort left the
+// points gathered) and the (y,z)-row table.
+void cmk_sorted_rows(hipStream_t s, const CmFrameDev* fd, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* vals_a,
+                     const uint32_t* keys_b, const uint32_t* vals_b, void* sorted_pts, void* rows, uint32_t n_padded,
+                     bool already_gathered);
 void cmk_hist(hipStream_t s, const CmFrameState* st, const uint32_t* keys, uint32_t* hist, uint32_t* grp,
               uint32_t pass, uint32_t n_tiles);
 void cmk_gscan(hipStream_t s, const CmFrameState* st, uint32_t* grp, uint32_t* totals, uint32_t pass,
@@ -134,3 +139,14 @@ void cmk_cov_keys(hipStream_t s, const void* recs, const uint32_t* total, const 
 void cmk_cov_reduce(hipStream_t s, const void* recs, const CmFrameState* st_sort, const uint32_t* keys_a, const uint32_t* vals_a,
                     const uint32_t* keys_b, const uint32_t* vals_b, const uint32_t* out_cnt, uint32_t n_out, uint32_t min_points,
                     float eig_mult, void* out, uint32_t* err);
+
+// ---- statistical outlier removal (cm_kernels_sor.hip) --------------------------------------------------------------------
+// After cmk_sorted_rows on the stage's grid (st): the k-nearest-neighbour search (first: the 3x3x3 cells around every point;
+// then the points it listed, ring by ring), the exact bins, the threshold, the keep-mask (points kept: 1).
+void cmk_sor_knn(hipStream_t s, const CmFrameDev* fd, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b,
+                 const void* sorted_pts, const void* rows, float* dist, void* list, unsigned long long* words, uint32_t n_padded,
+                 uint32_t k, bool first);
+void cmk_sor_bins(hipStream_t s, const CmFrameState* st, const float* dist, unsigned long long* words, uint32_t n_padded);
+void cmk_sor_threshold(hipStream_t s, const CmFrameState* st, unsigned long long* words, uint32_t k, float std_mul);
+void cmk_sor_mask(hipStream_t s, const CmFrameState* st, const float* dist, unsigned long long* words, unsigned char* mask,
+                  uint32_t n_padded);

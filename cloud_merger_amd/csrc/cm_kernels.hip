@@ -1299,15 +1299,20 @@ void cmk_keys(hipStream_t s, const CmFrameDev* fd, CmFrameState* st, uint32_t* k
               n_group_words, n_clear_a_words, seg_groups, n_seg_groups, partials, n_partials, from_crop,
               use_cell, mask, st_outlier);
 }
-void cmk_outlier_mask(hipStream_t s, const CmFrameDev* fd, const CmFrameState* st, const uint32_t* keys_a,
-                      const uint32_t* vals_a, const uint32_t* keys_b, const uint32_t* vals_b, void* sorted_pts,
-                      void* rows, unsigned char* mask, uint32_t n_padded, const unsigned char* cls, uint32_t* pend_n,
-                      bool already_gathered) {
+void cmk_sorted_rows(hipStream_t s, const CmFrameDev* fd, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* vals_a,
+                     const uint32_t* keys_b, const uint32_t* vals_b, void* sorted_pts, void* rows, uint32_t n_padded,
+                     bool already_gathered) {
     const uint32_t blocks = (n_padded + CM_BLOCK * 4 - 1) / (CM_BLOCK * 4);
     if (!already_gathered)
         CM_LAUNCH(k_gather_sorted, blocks, CM_BLOCK, s, fd, st, vals_a, vals_b, reinterpret_cast<float4*>(sorted_pts));
     CM_LAUNCH(k_row_clear, 1024, CM_BLOCK, s, st, reinterpret_cast<uint2*>(rows));
     CM_LAUNCH(k_row_table, blocks, CM_BLOCK, s, st, keys_a, keys_b, reinterpret_cast<uint2*>(rows));
+}
+void cmk_outlier_mask(hipStream_t s, const CmFrameDev* fd, const CmFrameState* st, const uint32_t* keys_a,
+                      const uint32_t* vals_a, const uint32_t* keys_b, const uint32_t* vals_b, void* sorted_pts,
+                      void* rows, unsigned char* mask, uint32_t n_padded, const unsigned char* cls, uint32_t* pend_n,
+                      bool already_gathered) {
+    cmk_sorted_rows(s, fd, st, keys_a, vals_a, keys_b, vals_b, sorted_pts, rows, n_padded, already_gathered);
     // pending list: point numbers in the keys buffer the sort did not end in, their counts in a vals buffer
     (void)hipMemsetAsync(pend_n, 0, 4, s);
     uint32_t* pa = const_cast<uint32_t*>(keys_a);

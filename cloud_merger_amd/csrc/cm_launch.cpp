@@ -243,9 +243,9 @@ void keys_and_sort(cm_ctx* c, CmFrameState* stg, int gmode, int use_cell, const 
                      c->route.lds_rank, use_cell ? nullptr : c->d_tile_kept, "k_scatter");
 }
 
-// Radius outlier filter over the points `in` marks (nullptr: every valid point), neighbours counted inside a
-// point's class only when `cls` is given; survivors are marked in `out`.
-int radius_filter(cm_ctx* c, const unsigned char* in, const unsigned char* cls, unsigned char* out) {
+// The outlier stages' sort: the points `in` marks (nullptr: every valid point) by the grid of f.inv_cell, into d_state_o
+// and (bucket kernels) sorted_pts. *gathered: the bucket kernels left the points in sorted order already.
+int cell_sort(cm_ctx* c, const unsigned char* in, bool* gathered) {
     const FramePlan& pl = c->plan;
     const CmFrameDev& f = c->frame;
     hipStream_t st = c->stream;
@@ -277,9 +277,49 @@ int radius_filter(cm_ctx* c, const unsigned char* in, const unsigned char* cls, 
         }
         keys_and_sort(c, c->d_state_o, pl.gm_o, 1, in, nullptr, pl.gm_o ? (pl.kb_o + CM_RADIX_BITS - 1) / CM_RADIX_BITS : CM_MAX_PASSES);
     }
+    *gathered = g != 0;
+    return CM_OK;
+}
+
+// Radius outlier filter over the points `in` marks (nullptr: every valid point), neighbours counted inside a
+// point's class only when `cls` is given; survivors are marked in `out`.
+int radius_filter(cm_ctx* c, const unsigned char* in, const unsigned char* cls, unsigned char* out) {
+    bool gathered = false;
+    const int e = cell_sort(c, in, &gathered);
+    if (e != CM_OK) return e;
     prof_mark(c, "outlier_mask");
-    cmk_outlier_mask(st, c->d_frame, c->d_state_o, c->keys_a, c->vals_a, c->keys_b, c->vals_b, c->sorted_pts,
-                     c->rows, out, f.n_padded, cls, c->merged_total + 8, g != 0);
+    cmk_outlier_mask(c->stream, c->d_frame, c->d_state_o, c->keys_a, c->vals_a, c->keys_b, c->vals_b, c->sorted_pts,
+                     c->rows, out, c->frame.n_padded, cls, c->merged_total + 8, gathered);
+    return CM_OK;
+}
+
+// Statistical outlier removal over every valid point: the sort by the search grid, the row table, the
+// k-nearest-neighbour search, the exact statistics and the keep-mask (c->mask, zeroed by the caller).
+int sor_filter(cm_ctx* c) {
+    const CmFrameDev& f = c->frame;
+    hipStream_t st = c->stream;
+    bool gathered = false;
+    const int e = cell_sort(c, nullptr, &gathered);
+    if (e != CM_OK) return e;
+    prof_mark(c, "sor_rows");
+    cmk_sorted_rows(st, c->d_frame, c->d_state_o, c->keys_a, c->vals_a, c->keys_b, c->vals_b, c->sorted_pts, c->rows,
+                    f.n_padded, gathered);
+    HIP_TRY(c, hipMemsetAsync(c->sor_d, 0xFF, static_cast<size_t>(f.n_padded) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->sor_words, 0, CM_SOR_WORD_STATS * 8, st));
+    const cm_sor_params& q = c->plan.sor_p;          // (a set call after the enqueue does not reach this frame or its redo)
+    const uint32_t k = q.mean_k;
+    prof_mark(c, "k_sor_knn");
+    cmk_sor_knn(st, c->d_frame, c->d_state_o, c->keys_a, c->keys_b, c->sorted_pts, c->rows, c->sor_d, c->sor_list, c->sor_words,
+                f.n_padded, k, true);
+    prof_mark(c, "k_sor_knn(list)");
+    cmk_sor_knn(st, c->d_frame, c->d_state_o, c->keys_a, c->keys_b, c->sorted_pts, c->rows, c->sor_d, c->sor_list, c->sor_words,
+                f.n_padded, k, false);
+    prof_mark(c, "k_sor_bins");
+    cmk_sor_bins(st, c->d_state_o, c->sor_d, c->sor_words, f.n_padded);
+    prof_mark(c, "k_sor_threshold");
+    cmk_sor_threshold(st, c->d_state_o, c->sor_words, k, q.std_mul);
+    prof_mark(c, "k_sor_mask");
+    cmk_sor_mask(st, c->d_state_o, c->sor_d, c->sor_words, c->mask, f.n_padded);
     return CM_OK;
 }
 
@@ -347,7 +387,14 @@ int launch_classic(cm_ctx* c) {
         if (e != CM_OK) return e;
         c->frame_mask = c->mask;
     }
-    const CmFrameState* st_outlier = (pl.outl || ground_outl) ? c->d_state_o : nullptr;
+    if (pl.sor) {
+        // Statistical outlier removal: like the radius stage, it decides which points the voxel grid sees at all.
+        HIP_TRY(c, hipMemsetAsync(c->mask, 0, f.n_padded, st));
+        const int e = sor_filter(c);
+        if (e != CM_OK) return e;
+        c->frame_mask = c->mask;
+    }
+    const CmFrameState* st_outlier = (pl.outl || ground_outl || pl.sor) ? c->d_state_o : nullptr;
     if (pl.post_bucket) return launch_bucket(c, c->frame_mask, st_outlier);   // the voxel stage, with the keep-mask
     if (!c->from_crop) {
         prof_mark(c, "k_minmax");
@@ -598,6 +645,17 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
     }
 
     if (mode == 1 && c->motion_on) return fail(c, CM_BAD_ARG, "ego-motion compensation is not combined with partial tables (cm_set_ego_motion(NULL) first)");
+    const bool sor = c->sor_on;
+    if (sor && mode != 0)
+        return fail(c, CM_BAD_ARG, "statistical outlier removal needs the whole fused cloud on one GPU (not with partial tables)");
+    if (sor && outl) return fail(c, CM_BAD_ARG, "statistical outlier removal is not combined with outlier_enable");
+    if (sor && c->ground_on) return fail(c, CM_BAD_ARG, "statistical outlier removal is not combined with ground removal");
+    // (its search grid: over the crop box when there is one — gm_o 1 — else over the cloud's bounds, measured below)
+    float sor_cell_m = sor ? sor_cell(c->sor.search_cell, c->sor_last_mean) : 0.0f;
+    if (sor && p->crop_enable) {
+        sor_cell_m = sor_fit_cell(sor_cell_m, p->crop_min, p->crop_max, CM_ROW_TABLE_CAP / 2, &kb_o);
+        gm_o = 1;
+    }
 
     std::vector<std::unique_lock<std::mutex>> locks;
     c->prof_used = 0;                                // (k_motion, when compensation is on, is the frame's first stage)
@@ -607,6 +665,24 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
     if (mode == 1 && bounds) {
         for (int a = 0; a < 3; ++a) { f.ext_min[a] = bounds[a]; f.ext_max[a] = bounds[3 + a]; }
     }
+    if (sor && f.n_padded) {
+        if (!p->crop_enable) {
+            // the grid over the cloud's own bounds (k_minmax, as the device will see them): a host round trip, then a cell
+            // whose grid fits with room to spare
+            if (descriptor_changed(c)) cmk_setup(c->stream, f, c->d_frame, c->d_tiles);
+            float mn[3], mx[3];
+            uint64_t cnt = 0;
+            const int e = measure_bounds(c, mn, mx, &cnt);
+            if (e != CM_OK) return e;
+            if (cnt) {
+                for (int a = 0; a < 3; ++a) { mn[a] -= sor_cell_m; mx[a] += sor_cell_m; }
+                sor_cell_m = sor_fit_cell(sor_cell_m, mn, mx, CM_ROW_TABLE_CAP / 4, &kb_o);
+            }
+        }
+        for (int a = 0; a < 3; ++a) inv_cell[a] = 1.0f / sor_cell_m;
+        for (int a = 0; a < 3; ++a) f.inv_cell[a] = inv_cell[a];
+    }
+    c->last_sor = sor;                               // (after the last step that can fail: a failed enqueue leaves the last frame's)
     if (any_outl) {
         for (int a = 0; a < 3; ++a) f.inv_cell[a] = inv_cell[a];
         f.outlier_r2 = static_cast<float>(static_cast<double>(o_radius) * static_cast<double>(o_radius));
@@ -654,7 +730,9 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
     pl.grid_mode = grid_mode;
     pl.key_bits = key_bits;
     pl.outl = outl;
-    pl.pre = outl || c->ground_on;
+    pl.sor = sor;
+    pl.sor_p = c->sor;
+    pl.pre = outl || c->ground_on || sor;
     pl.gm_o = gm_o;
     pl.kb_o = kb_o;
     RouteState& rt = c->route;
@@ -680,6 +758,10 @@ int wait_frame(cm_ctx* c, cm_result* res) {
     r.n_in = c->n_in;
     if (c->pending_trivial) {
         r.status = CM_EMPTY_INPUT;
+        if (c->last_sor) {
+            c->sor_stats = cm_sor_stats{0, 0, std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN(),
+                                        std::numeric_limits<double>::infinity()};
+        }
         if (c->last_mode == 1 && c->trivial_grid) {
             r.bounds_from_crop = 1;
             for (int a = 0; a < 3; ++a) {
@@ -700,6 +782,17 @@ int wait_frame(cm_ctx* c, cm_result* res) {
             const int e = replay(c, how);
             if (e != CM_OK) { c->pending = false; return e; }
             HIP_TRY(c, hipEventSynchronize(c->ev_done));
+        }
+        if (c->last_sor) {
+            static_assert(sizeof(CmSorStatsDev) == sizeof(cm_sor_stats), "cm_sor_stats layout");
+            HIP_TRY(c, hipMemcpy(&c->sor_stats, c->sor_words + CM_SOR_WORD_STATS, sizeof c->sor_stats, hipMemcpyDeviceToHost));
+            if (rt.verbose) {                               // (CM_VERBOSE: how many points the second search launch took)
+                uint32_t listed = 0;
+                HIP_TRY(c, hipMemcpy(&listed, c->sor_words + CM_SOR_WORD_LIST, 4, hipMemcpyDeviceToHost));
+                std::fprintf(stderr, "[cloudmerge] sor: n_valid %llu, second search launch %u points\n",
+                             static_cast<unsigned long long>(c->sor_stats.n_valid), listed);
+            }
+            if (c->sor_stats.mean > 0.0 && std::isfinite(c->sor_stats.mean)) c->sor_last_mean = c->sor_stats.mean;
         }
         const CmFrameState& h = *c->h_state;
         if (h.err) {
@@ -728,7 +821,8 @@ int wait_frame(cm_ctx* c, cm_result* res) {
         }
         r.key_bits = h.key_bits;
         r.sort_passes = h.n_passes;
-        r.path_flags = (rt.lds_rank ? CM_PATH_LDS_RANK : 0u) | (pl.redone ? CM_PATH_REDONE : 0u) | (c->last_motion ? CM_PATH_MOTION : 0u);
+        r.path_flags = (rt.lds_rank ? CM_PATH_LDS_RANK : 0u) | (pl.redone ? CM_PATH_REDONE : 0u) | (c->last_motion ? CM_PATH_MOTION : 0u) |
+                       (c->last_sor ? CM_PATH_SOR : 0u);
         if (pl.bucket)
             r.path_flags |= CM_PATH_BUCKET | (pl.predicted ? CM_PATH_PREDICTED : 0u) | (pl.pack ? CM_PATH_PACKED : 0u) |
                             (pl.k3 ? CM_PATH_SPLIT : 0u) | (pl.quant ? CM_PATH_QUANTILE : 0u);

@@ -41,6 +41,25 @@ uint32_t bucket_passes(uint32_t kb, uint64_t est, uint32_t extra) {
     return g <= CM_MAX_PASSES ? g : 0;
 }
 
+float sor_cell(float requested, double last_mean) {
+    if (requested > 0.0f) return requested;
+    if (!(last_mean > 0.0) || !std::isfinite(last_mean)) return 0.5f;
+    return static_cast<float>(std::min(5.0, std::max(0.05, last_mean)));
+}
+
+float sor_fit_cell(float cell, const float bmin[3], const float bmax[3], uint32_t row_cap, uint32_t* key_bits) {
+    for (;; cell *= 2.0f) {
+        const float inv = 1.0f / cell;
+        const float iv[3] = {inv, inv, inv};
+        int32_t mb[3], db[3];
+        if (!std::isfinite(cell)) return cell;
+        if (!box_grid(bmin, bmax, iv, key_bits, mb, db)) continue;
+        if (static_cast<uint64_t>(db[1]) * static_cast<uint64_t>(db[2]) > row_cap) continue;
+        if (db[0] >= (1 << 24) || db[1] >= (1 << 24) || db[2] >= (1 << 24)) continue;
+        return cell;
+    }
+}
+
 // A cloud near the limit of PCL's 32-bit index leaves no room for an eighth of its extent on every side: take what
 // fits (a frame right behind one that reached far out would otherwise lose its box, and with it the bucket path).
 void RouteState::set_predicted_box(const float mn[3], const float mx[3], const float leaf[3]) {

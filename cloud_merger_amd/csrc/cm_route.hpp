@@ -20,6 +20,13 @@ uint32_t key_width(unsigned long long cells);
 // capacity. 0: the bucket kernels do not fit this grid.
 uint32_t bucket_passes(uint32_t kb, uint64_t est, uint32_t extra);
 
+// Statistical outlier removal: the edge of the search grid's cells. requested > 0 is taken as it is; 0: the last
+// frame's mean distance (last_mean, NaN or <= 0: none) clamped to [0.05, 5] m, 0.5 m without one.
+float sor_cell(float requested, double last_mean);
+// The cell doubled until the grid over [bmin, bmax] fits: 32-bit keys, at most row_cap (y,z) rows, fewer than 2^24 cells per
+// axis (the bucket kernels' multiplier). Returns the cell and its grid's key width. The result never depends on the cell.
+float sor_fit_cell(float cell, const float bmin[3], const float bmax[3], uint32_t row_cap, uint32_t* key_bits);
+
 // What the frame in flight runs. Set by RouteState::plan at enqueue, rewritten for a replay inside cm_wait; the launch
 // functions read it and decide nothing. Fields marked (prev) are sized from the frame before this one (DESIGN.md names the
 // device check that catches each of them being wrong).
@@ -30,6 +37,8 @@ struct FramePlan {
     int grid_mode = 0;             // general path: 0 data min/max (k_minmax), 1 crop box, 2 bounds handed in
     uint32_t key_bits = 0;         // ... with a box: its key width
     bool outl = false;             // radius outlier removal (cm_params.outlier_enable)
+    bool sor = false;              // statistical outlier removal (cm_set_statistical_outlier); shares the outlier stage's grid
+    cm_sor_params sor_p = {};      // ... its parameters as the frame was enqueued (a redo inside cm_wait reads these)
     bool pre = false;              // pre-stages (ground / outlier removal) leave a keep-mask for the voxel stage
     int gm_o = 0;                  // grid of the outlier stage: 0 data min/max, 1 crop box
     uint32_t kb_o = 0;             // ... its key width

@@ -136,6 +136,14 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             ok = ok && sidx < c.sensors.size() && c.ground.n_zones[sidx] < CM_MAX_ZONES;
             if (ok) c.ground.zones[sidx][c.ground.n_zones[sidx]++] = z;
         }
+        else if (key == "statistical_outlier") {
+            cm_sor_params q{};
+            ok = static_cast<bool>(is >> q.mean_k >> q.std_mul) && q.mean_k >= 1 && q.mean_k <= CM_SOR_MAX_K;
+            float cell = 0.0f;
+            if (ok && (is >> cell)) q.search_cell = cell;
+            ok = ok && q.search_cell >= 0.0f;
+            if (ok) { c.sor = q; c.sor_enable = true; }
+        }
         else if (key == "motion_compensation") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.motion_compensation = v == 1; }
         else if (key == "time_field") {
             std::string name, type;
@@ -184,6 +192,14 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
         const int gs = cm_set_ground_removal(ctx_, &cfg_.ground);
         if (gs != CM_OK) {
             error_ = std::string("cm_set_ground_removal: ") + cm_last_error(ctx_);
+            cm_destroy(ctx_);
+            ctx_ = nullptr;
+        }
+    }
+    if (ctx_ && cfg_.sor_enable) {
+        const int ss = cm_set_statistical_outlier(ctx_, &cfg_.sor);
+        if (ss != CM_OK) {
+            error_ = std::string("cm_set_statistical_outlier: ") + cm_last_error(ctx_);
             cm_destroy(ctx_);
             ctx_ = nullptr;
         }

@@ -71,6 +71,10 @@ struct NodeConfig {
     // with, by the twist set_ego_twist() last gave. That stamp is then fixed when the frame is enqueued (the newest input
     // stamp with stamp_from_inputs, else the clock at that moment).
     bool motion_compensation = false;
+    // Statistical outlier removal on the fused cloud before the voxel grid (cm_set_statistical_outlier;
+    // pcl::StatisticalOutlierRemoval). Off by default; not combined with `outlier` or `ground`.
+    bool sor_enable = false;
+    cm_sor_params sor{};
     struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
     TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
@@ -85,6 +89,7 @@ struct NodeConfig {
 //   ground_outlier <radius> <min_neighbors>   (removeGround's outlierRemoval on every slab's band points, :119)
 //   motion_compensation <0|1> | time_field <sensor_name> <byte_offset> <f32|u32ns>   (ego-motion compensation; f32: seconds,
 //   u32ns: nanoseconds, relative to the cloud's header stamp)
+//   statistical_outlier <mean_k> <std_mul> [search_cell]   (pcl::StatisticalOutlierRemoval before the voxel grid)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 

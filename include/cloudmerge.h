@@ -125,6 +125,7 @@ typedef struct cm_result {
                                   for LDS, or more survivors of the crop than the last frame promised, on the general path */
 
 #define CM_PATH_MOTION 128u    /* the frame's points were motion-compensated (cm_set_ego_motion) before anything else read them */
+#define CM_PATH_SOR 256u       /* statistical outlier removal (cm_set_statistical_outlier) chose the points the voxel grid saw */
 
 #define CM_MAX_STAGES 48
 typedef struct cm_stage_times {
@@ -361,6 +362,46 @@ typedef struct cm_voxel_cov {          /* 80 bytes */
 CM_API int cm_result_voxel_cov(cm_ctx* ctx, const cm_cov_params* p, cm_voxel_cov* host_dst, uint64_t capacity);
 /* The same table left in device memory owned by the context: *n entries of 80 bytes at *dev_ptr. */
 CM_API int cm_result_voxel_cov_device(cm_ctx* ctx, const cm_cov_params* p, const void** dev_ptr, uint64_t* n);
+
+/* ---- statistical outlier removal before the voxel grid (pcl::StatisticalOutlierRemoval) ----------------------------
+ * PCL 1.8's StatisticalOutlierRemoval::applyFilterIndices restated (parity against libpcl is unpinned, as for
+ * every other stage). The stage's input is the fused cloud after transform, crop, the non-finite drop and deskew when it is
+ * on: P = p_1..p_n in (sensor, point) order, the order of cm_merged_copy.
+ *   1. d2(q, p) = (dx*dx + dy*dy) + dz*dz, dx = q.x - p.x ..., fp32, round-to-nearest, no contraction, over every OTHER index
+ *      (exact duplicates count, at distance 0).
+ *   2. d_i: the k = mean_k smallest d2 of p_i, sqrtf of each correctly rounded, added in ascending order in fp64 from 0.0,
+ *      d_i = float(sum / k).
+ *   3. S = sum double(d_i), Q = sum double(fp32(d_i * d_i)), both exact and rounded once to fp64 (math.fsum; PCL adds in index
+ *      order: a documented deviation that makes the result independent of launch geometry). fp64, no contraction:
+ *      mean = S / n, var = (Q - S*S/n) / (n - 1), stddev = sqrt(var), threshold = mean + std_mul * stddev.
+ *   4. p_i is removed iff double(d_i) > threshold (a NaN threshold, from a slightly negative variance, removes nothing).
+ *   5. n <= mean_k: nothing is removed, d_i, mean and stddev are NaN, threshold is +inf. An empty input stays CM_EMPTY_INPUT.
+ * The kept points go on in their order through the stage's keep-mask: cm_merged_copy, cm_result_*, cm_result_voxel_cov* and
+ * cm_frame_stats.n_kept see the surviving cloud.
+ * Refused at merge (CM_BAD_ARG, cm_last_error says why): with cm_params.outlier_enable, with ground removal, with
+ * cm_merge_partial / cm_local_bounds. Deskew combines with it. */
+#define CM_SOR_MAX_K 64
+typedef struct cm_sor_params {
+    uint32_t mean_k;       /* setMeanK, 1..CM_SOR_MAX_K */
+    float std_mul;         /* setStddevMulThresh, finite (negative allowed) */
+    float search_cell;     /* edge (m) of the search grid's cells: speed only, never the result; 0 = library's choice: the last
+                              frame's mean distance, clamped to [0.05, 5] m, 0.5 m on the first frame. A cell whose grid
+                              would exceed the row table or the 32-bit keys is doubled until it fits. */
+    uint32_t _pad;
+} cm_sor_params;
+typedef struct cm_sor_stats {
+    uint64_t n_valid, n_removed;
+    double mean, stddev, threshold;
+} cm_sor_stats;
+/* NULL: off; takes effect with the next merge. Refused (CM_BAD_ARG): mean_k 0 or above 64, a non-finite std_mul, a negative or
+ * non-finite search_cell. The stage's buffers are allocated by the first non-NULL call; if that fails the call returns
+ * CM_HIP_ERROR and the stage stays off. */
+CM_API int cm_set_statistical_outlier(cm_ctx* ctx, const cm_sor_params* p);
+/* Figures of the last waited-for frame (of a frame without the stage: all zero). */
+CM_API int cm_get_sor_stats(cm_ctx* ctx, cm_sor_stats* out);
+/* d_i of the stage's input, in (sensor, point) order (n_valid entries): what the threshold was applied to. *n: the entries;
+ * more than capacity: CM_CAPACITY. */
+CM_API int cm_sor_distances_copy(cm_ctx* ctx, float* host_dst, uint64_t capacity, uint64_t* n);
 
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
