@@ -336,7 +336,9 @@ __device__ __forceinline__ void compute_grid(const CmFrameDev* __restrict__ fd,
     bool overflow = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const float ext = __fmul_rn(__fsub_rn(g.max_p[a], g.min_p[a]), inv[a]);
+        // (an inverse of 0 — a cell of +inf, the statistical outlier stage's grid over a cloud wider than FLT_MAX — is one
+        // cell, whose extent may overflow to inf: inf * 0 would be NaN)
+        const float ext = inv[a] == 0.0f ? 0.0f : __fmul_rn(__fsub_rn(g.max_p[a], g.min_p[a]), inv[a]);
         if (!(ext < 2147483648.0f)) { overflow = true; d[a] = 0; }
         else d[a] = static_cast<long long>(ext) + 1;       // truncation toward zero
     }

@@ -650,12 +650,10 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
         return fail(c, CM_BAD_ARG, "statistical outlier removal needs the whole fused cloud on one GPU (not with partial tables)");
     if (sor && outl) return fail(c, CM_BAD_ARG, "statistical outlier removal is not combined with outlier_enable");
     if (sor && c->ground_on) return fail(c, CM_BAD_ARG, "statistical outlier removal is not combined with ground removal");
-    // (its search grid: over the crop box when there is one — gm_o 1 — else over the cloud's bounds, measured below)
+    // (its search grid: over the crop box when there is one and a cell fits it — gm_o 1 — else over the cloud's bounds,
+    // measured below: so for a crop box whose extent overflows fp32)
     float sor_cell_m = sor ? sor_cell(c->sor.search_cell, c->sor_last_mean) : 0.0f;
-    if (sor && p->crop_enable) {
-        sor_cell_m = sor_fit_cell(sor_cell_m, p->crop_min, p->crop_max, CM_ROW_TABLE_CAP / 2, &kb_o);
-        gm_o = 1;
-    }
+    if (sor) gm_o = sor_crop_grid(*p, &sor_cell_m, &kb_o);
 
     std::vector<std::unique_lock<std::mutex>> locks;
     c->prof_used = 0;                                // (k_motion, when compensation is on, is the frame's first stage)
@@ -666,18 +664,16 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
         for (int a = 0; a < 3; ++a) { f.ext_min[a] = bounds[a]; f.ext_max[a] = bounds[3 + a]; }
     }
     if (sor && f.n_padded) {
-        if (!p->crop_enable) {
+        if (!gm_o) {
             // the grid over the cloud's own bounds (k_minmax, as the device will see them): a host round trip, then a cell
-            // whose grid fits with room to spare
+            // whose grid fits with room to spare. A cloud whose extent overflows fp32 fits none: one cell (inv_cell 0,
+            // compute_grid's one cell per axis), every point a candidate of every other.
             if (descriptor_changed(c)) cmk_setup(c->stream, f, c->d_frame, c->d_tiles);
             float mn[3], mx[3];
             uint64_t cnt = 0;
             const int e = measure_bounds(c, mn, mx, &cnt);
             if (e != CM_OK) return e;
-            if (cnt) {
-                for (int a = 0; a < 3; ++a) { mn[a] -= sor_cell_m; mx[a] += sor_cell_m; }
-                sor_cell_m = sor_fit_cell(sor_cell_m, mn, mx, CM_ROW_TABLE_CAP / 4, &kb_o);
-            }
+            if (cnt) sor_cell_m = sor_bounds_cell(sor_cell_m, mn, mx, &kb_o);
         }
         for (int a = 0; a < 3; ++a) inv_cell[a] = 1.0f / sor_cell_m;
         for (int a = 0; a < 3; ++a) f.inv_cell[a] = inv_cell[a];

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 
 bool box_grid(const float bmin[3], const float bmax[3], const float inv[3], uint32_t* key_bits, int32_t* min_b, int32_t* div_b) {
     long long d[3];
@@ -52,12 +53,28 @@ float sor_fit_cell(float cell, const float bmin[3], const float bmax[3], uint32_
         const float inv = 1.0f / cell;
         const float iv[3] = {inv, inv, inv};
         int32_t mb[3], db[3];
-        if (!std::isfinite(cell)) return cell;
+        // (a box whose extent overflows fp32 fits no finite cell: the caller takes another grid, key_bits stays as it was)
+        if (!std::isfinite(cell)) return 0.0f;
         if (!box_grid(bmin, bmax, iv, key_bits, mb, db)) continue;
         if (static_cast<uint64_t>(db[1]) * static_cast<uint64_t>(db[2]) > row_cap) continue;
         if (db[0] >= (1 << 24) || db[1] >= (1 << 24) || db[2] >= (1 << 24)) continue;
         return cell;
     }
+}
+
+int sor_crop_grid(const cm_params& p, float* cell, uint32_t* key_bits) {
+    if (!p.crop_enable) return 0;
+    const float fit = sor_fit_cell(*cell, p.crop_min, p.crop_max, CM_ROW_TABLE_CAP / 2, key_bits);
+    if (!(fit > 0.0f)) return 0;
+    *cell = fit;
+    return 1;
+}
+
+float sor_bounds_cell(float cell, const float mn[3], const float mx[3], uint32_t* key_bits) {
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; ++a) { lo[a] = mn[a] - cell; hi[a] = mx[a] + cell; }
+    const float fit = sor_fit_cell(cell, lo, hi, CM_ROW_TABLE_CAP / 4, key_bits);
+    return fit > 0.0f ? fit : std::numeric_limits<float>::infinity();
 }
 
 // A cloud near the limit of PCL's 32-bit index leaves no room for an eighth of its extent on every side: take what

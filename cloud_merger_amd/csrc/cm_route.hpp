@@ -25,7 +25,15 @@ uint32_t bucket_passes(uint32_t kb, uint64_t est, uint32_t extra);
 float sor_cell(float requested, double last_mean);
 // The cell doubled until the grid over [bmin, bmax] fits: 32-bit keys, at most row_cap (y,z) rows, fewer than 2^24 cells per
 // axis (the bucket kernels' multiplier). Returns the cell and its grid's key width. The result never depends on the cell.
+// 0: no finite cell fits (an extent beyond FLT_MAX on some axis); *key_bits is then left unwritten.
 float sor_fit_cell(float cell, const float bmin[3], const float bmax[3], uint32_t row_cap, uint32_t* key_bits);
+// The search grid of a frame (cm_launch.cpp enqueue). sor_crop_grid: over the crop box when one is on and some finite cell
+// fits it (half the row table): returns 1 (the stage's grid mode) with that cell in *cell and its key width; else 0 with
+// *cell unchanged, and the grid is over the cloud's own bounds. sor_bounds_cell: the cell over the measured bounds [mn, mx],
+// widened by the cell on every side (a quarter of the row table); +inf — one cell, inverse 0 — when the cloud's extent
+// overflows fp32 and no finite cell fits.
+int sor_crop_grid(const cm_params& p, float* cell, uint32_t* key_bits);
+float sor_bounds_cell(float cell, const float mn[3], const float mx[3], uint32_t* key_bits);
 
 // What the frame in flight runs. Set by RouteState::plan at enqueue, rewritten for a replay inside cm_wait; the launch
 // functions read it and decide nothing. Fields marked (prev) are sized from the frame before this one (DESIGN.md names the

@@ -386,7 +386,10 @@ typedef struct cm_sor_params {
     float std_mul;         /* setStddevMulThresh, finite (negative allowed) */
     float search_cell;     /* edge (m) of the search grid's cells: speed only, never the result; 0 = library's choice: the last
                               frame's mean distance, clamped to [0.05, 5] m, 0.5 m on the first frame. A cell whose grid
-                              would exceed the row table or the 32-bit keys is doubled until it fits. */
+                              would exceed the row table or the 32-bit keys is doubled until it fits. The grid is over the
+                              crop box when one is on, else over the cloud's own bounds; a crop box whose extent overflows
+                              fp32 (e.g. +-2e38) fits no cell, and the grid is then over the cloud's own bounds as well. A
+                              cloud whose own extent overflows fp32 is searched as one cell. */
     uint32_t _pad;
 } cm_sor_params;
 typedef struct cm_sor_stats {

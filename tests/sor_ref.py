@@ -9,8 +9,11 @@ pcl::StatisticalOutlierRemoval::applyFilterIndices as the header states it, on t
 
 The k nearest neighbours come from an exact search without scipy: the points are bucketed in cubic cells, every point takes
 the candidates of the 27 cells around its own, and a point whose k-th distance is not provably inside that block (or that
-has fewer than k candidates) is searched again by brute force over the whole cloud."""
+has fewer than k candidates) is searched again by brute force over the whole cloud. knn_d2_brute has no cells at all: every
+pair, the point's own index left out. The probe frames (tests/sor_edge_frames.py) are judged by it, and the bucketed search
+is checked against it there (tests/test_sor_edges.py). exact_sums gives S and Q as exact rationals."""
 import math
+from fractions import Fraction
 
 import numpy as np
 
@@ -42,7 +45,11 @@ def knn_d2(xyz, k, cell=None, chunk=20_000):
     if cell is None:
         ext = float(np.max(xyz.max(0).astype(np.float64) - xyz.min(0).astype(np.float64))) if n else 1.0
         cell = max(ext / max(n, 1) ** (1 / 3) * 2.0, 1e-3)
-    ijk = np.floor(xyz.astype(np.float64) / cell).astype(np.int64)
+    fl = np.floor(xyz.astype(np.float64) / cell)
+    if n and float(np.prod(fl.max(0) - fl.min(0) + 3.0)) >= 2.0 ** 62:
+        # (a cloud whose extent in cells overflows the int64 cell keys — one wider than FLT_MAX at any cell: every pair)
+        return _brute(xyz, np.arange(n), k) if n > k else np.full((n, k), np.inf, np.float32)
+    ijk = fl.astype(np.int64)
     ijk -= ijk.min(0)
     dims = ijk.max(0) + 3
     key = ((ijk[:, 2] + 1) * dims[1] + (ijk[:, 1] + 1)) * dims[0] + (ijk[:, 0] + 1)
@@ -86,12 +93,26 @@ def knn_d2(xyz, k, cell=None, chunk=20_000):
     return out
 
 
-def distances(xyz, k, cell=None):
-    """d_i (float32) of every point; NaN everywhere when n <= k."""
+def knn_d2_brute(xyz, k, chunk=128):
+    """(n, k) float32: knn_d2 by brute force over every pair — no cells, no bounds, only the point's own index left out."""
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+    n = len(xyz)
+    out = np.empty((n, k), np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        for a in range(0, n, chunk):
+            sel = np.arange(a, min(n, a + chunk))
+            d = _d2(xyz[sel][:, None, :], xyz[None, :, :])
+            d[np.arange(len(sel)), sel] = np.inf
+            out[sel] = np.sort(np.partition(d, k - 1, axis=1)[:, :k], axis=1)
+    return out
+
+
+def distances(xyz, k, cell=None, brute=False):
+    """d_i (float32) of every point; NaN everywhere when n <= k. brute: the k nearest from knn_d2_brute."""
     n = len(xyz)
     if n <= k:
         return np.full(n, np.nan, np.float32)
-    d2 = knn_d2(xyz, k, cell)
+    d2 = knn_d2_brute(xyz, k) if brute else knn_d2(xyz, k, cell)
     r = np.sqrt(d2)                                              # float32, correctly rounded
     s = np.zeros(n)
     for j in range(k):
@@ -113,6 +134,16 @@ def stats(d, k, std_mul):
     return mean, sd, mean + float(np.float32(std_mul)) * sd
 
 
+def exact_sums(d):
+    """(S, Q) of finite d_i as exact rationals: sum d_i and sum fp32(d_i * d_i); None in place of a sum with an infinite term."""
+    d = np.asarray(d, np.float32)
+    with np.errstate(over="ignore"):
+        sq = (d * d).astype(np.float32)
+    S = None if np.isinf(d).any() else sum((Fraction(float(v)) for v in d), Fraction(0))
+    Q = None if np.isinf(sq).any() else sum((Fraction(float(v)) for v in sq), Fraction(0))
+    return S, Q
+
+
 def keep_mask(d, threshold):
     """True: kept. A NaN threshold (or d_i) keeps the point."""
     d = np.asarray(d, np.float32).astype(np.float64)
@@ -120,8 +151,8 @@ def keep_mask(d, threshold):
         return ~(d > threshold)
 
 
-def sor(xyz, k, std_mul, cell=None):
+def sor(xyz, k, std_mul, cell=None, brute=False):
     """(d, (mean, stddev, threshold), keep) of the cloud."""
-    d = distances(xyz, k, cell)
+    d = distances(xyz, k, cell, brute)
     st = stats(d, k, std_mul)
     return d, st, keep_mask(d, st[2])

@@ -13,6 +13,7 @@ CSRC = os.path.join(ROOT, "cloud_merger_amd", "csrc")
 
 DRIVER = r"""
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <sstream>
@@ -110,6 +111,45 @@ int main() {
             rt.size_fixed_grid(pl, f, n_in);
             std::printf("nt_later=%u pack=%d sparse=%d k3=%d", pl.nt_later, pl.pack, pl.sparse, pl.k3);
             counters();
+        } else if (cmd == "sorcell") {               // requested last_mean row_cap|crop|bounds min xyz max xyz
+            // (tokens through strtod: "nan" and "inf" parse; key_bits starts at 99 so an unwritten one shows)
+            std::string tok[9];
+            for (auto& t : tok) in >> t;
+            const float req = std::strtof(tok[0].c_str(), nullptr);
+            const double mean = std::strtod(tok[1].c_str(), nullptr);
+            float mn[3], mx[3];
+            for (int a = 0; a < 3; ++a) {
+                mn[a] = std::strtof(tok[3 + a].c_str(), nullptr);
+                mx[a] = std::strtof(tok[6 + a].c_str(), nullptr);
+            }
+            const float c0 = sor_cell(req, mean);
+            float cell = c0;
+            uint32_t kb = 99;
+            int gm = -1;
+            if (tok[2] == "crop") {
+                cm_params p;
+                std::memset(&p, 0, sizeof p);
+                p.crop_enable = 1;
+                for (int a = 0; a < 3; ++a) { p.crop_min[a] = mn[a]; p.crop_max[a] = mx[a]; }
+                gm = sor_crop_grid(p, &cell, &kb);
+            } else if (tok[2] == "bounds") {
+                cell = sor_bounds_cell(c0, mn, mx, &kb);
+                for (int a = 0; a < 3; ++a) { mn[a] -= c0; mx[a] += c0; }
+            } else {
+                cell = sor_fit_cell(c0, mn, mx, static_cast<uint32_t>(std::strtoul(tok[2].c_str(), nullptr, 10)), &kb);
+            }
+            // the fitted grid's rows ((y,z) cell pairs) and cells along x
+            unsigned long long rows = 0, nx = 0;
+            if (cell > 0.0f) {
+                const float inv = 1.0f / cell, iv[3] = {inv, inv, inv};
+                int32_t mb[3], db[3];
+                uint32_t kb2 = 0;
+                if (box_grid(mn, mx, iv, &kb2, mb, db)) {
+                    rows = static_cast<unsigned long long>(db[1]) * static_cast<unsigned long long>(db[2]);
+                    nx = static_cast<unsigned long long>(db[0]);
+                }
+            }
+            std::printf("%.9g %.9g %u %llu %llu %d\n", c0, cell, kb, rows, nx, gm);
         } else if (cmd == "box" || cmd == "update") {   // min xyz, max xyz, leaf xyz
             float mn[3], mx[3], leaf[3];
             for (float& v : mn) in >> v;
@@ -319,3 +359,101 @@ def test_predicted_box_margins(driver):
     # without a box, update_predicted_box makes one
     ok, b1 = box(driver([f"update {args(mn, mx)}"])[0])
     assert ok == 1 and b1 == b0
+
+
+# ---- the statistical outlier stage's search grid (sor_cell, sor_fit_cell, sor_crop_grid, sor_bounds_cell) --------------
+ROW_CAP = 1 << 22                                                # CM_ROW_TABLE_CAP (cm_device.h)
+
+
+def sorcell(driver, cmds):
+    """'sorcell req mean cap|crop|bounds mn.. mx..' -> (requested cell, fitted cell, key bits, rows, cells in x, grid mode)"""
+    out = []
+    for line in driver(["sorcell " + c for c in cmds]):
+        v = line.split()
+        out.append((np.float32(float(v[0])), np.float32(float(v[1])), int(v[2]), int(v[3]), int(v[4]), int(v[5])))
+    return out
+
+
+def fit_model(cell, mn, mx, cap):
+    """sor_fit_cell restated in numpy fp32: (cell, key bits, rows) of the first doubling whose grid fits, (0, None, 0)
+    when the cell reaches +inf first."""
+    f32 = np.float32
+    cell = f32(cell)
+    with np.errstate(over="ignore", invalid="ignore"):
+        while np.isfinite(cell):
+            inv = f32(1.0) / cell
+            ext = [f32(f32(f32(mx[a]) - f32(mn[a])) * inv) for a in range(3)]
+            if all(e < f32(2.0 ** 31) and e >= 0 for e in ext):
+                lo = [int(np.floor(f32(f32(mn[a]) * inv))) for a in range(3)]
+                hi = [int(np.floor(f32(f32(mx[a]) * inv))) for a in range(3)]
+                div = [h - l + 1 for l, h in zip(lo, hi)]
+                d = [int(e) + 1 for e in ext]
+                cells = div[0] * div[1] * div[2]
+                if d[0] * d[1] * d[2] <= 2 ** 31 - 1 and cells <= 2 ** 32 - 1 and div[1] * div[2] <= cap and max(div) < 2 ** 24:
+                    return cell, max(1, (cells - 1).bit_length()), div[1] * div[2]
+            cell = f32(cell * f32(2.0))
+    return f32(0.0), None, 0
+
+
+def test_sor_cell_choice(driver):
+    # (requested, last frame's mean) -> cell: a request is taken as it is; else the mean clamped to [0.05, 5], 0.5 without one
+    cases = [(0, "nan", 0.5), (0, "inf", 0.5), (0, "-inf", 0.5), (0, 0, 0.5), (0, -1, 0.5), (0, 1e-30, 0.05), (0, 0.3, 0.3),
+             (0, 1e6, 5.0), (0.7, 1e6, 0.7), (1e-6, "nan", 1e-6), (1e3, 0.1, 1e3)]
+    got = sorcell(driver, [f"{r} {m} {ROW_CAP} 0 0 0 1 1 1" for r, m, _ in cases])
+    assert [g[0] for g in got] == [np.float32(w) for *_, w in cases]
+
+
+def test_sor_fit_cell_pins(driver):
+    half, quarter = ROW_CAP // 2, ROW_CAP // 4
+    got = sorcell(driver, [f"0 nan {half} 0 0 0 1 1 1",
+                           f"0 nan {half} -5000 -5000 -5000 5000 5000 5000",
+                           f"0 nan {quarter} -5000 -5000 -5000 5000 5000 5000"])
+    # [0, 1]^3 at 0.5 m: cells 0..2 per axis, 27 cells (5 bits), 9 rows
+    assert got[0][1:5] == (np.float32(0.5), 5, 9, 3)
+    # +-5 km: 8 m is the first doubling with at most 2^21 rows (1251^2; 1251^3 cells: 31 bits); 16 m for 2^20 rows (626 per
+    # axis: floor(312.5) - floor(-312.5) + 1; 28 bits)
+    assert got[1][1:5] == (np.float32(8.0), 31, 1251 ** 2, 1251)
+    assert got[2][1:5] == (np.float32(16.0), 28, 626 ** 2, 626)
+
+
+@pytest.mark.parametrize("cap", [ROW_CAP // 2, ROW_CAP // 4])
+def test_sor_fit_cell_boxes(driver, cap):
+    boxes = [((0, 0, 0), (1, 1, 1)), ((-20, -20, -5), (20, 20, 5)), ((-5e3,) * 3, (5e3,) * 3), ((-5e29,) * 3, (5e29,) * 3),
+             ((1e6, -1e6, 0), (1e6 + 30, -1e6 + 30, 3)), ((-1e38,) * 3, (1e38,) * 3), ((-1.7e38, 0, 0), (1.7e38, 1, 1))]
+    over = [((-2e38,) * 3, (2e38,) * 3), ((-3.4e38,) * 3, (3.4e38,) * 3), ((-2e38, -10, -10), (2e38, 10, 10)),
+            ((0, 0, -3.4e38), (1, 1, 3.4e38))]
+    for req, mean in ((0, "nan"), (0, 1e-30), (0.05, 0), (1e-6, 0), (1e3, 0)):
+        cmds = [f"{req} {mean} {cap} " + " ".join(str(v) for v in (*mn, *mx)) for mn, mx in boxes + over]
+        got = sorcell(driver, cmds)
+        for (mn, mx), g in zip(boxes + over, got):
+            cell, kb, rows = fit_model(g[0], mn, mx, cap)
+            if (mn, mx) in over:
+                # no finite cell fits: 0, key_bits left as it was
+                assert (g[1], g[2], g[3]) == (0.0, 99, 0) and kb is None, (mn, mx, g)
+            else:
+                assert (g[1], g[2], g[3]) == (cell, kb, rows), (req, mean, mn, mx, g, (cell, kb, rows))
+                assert 0 < rows <= cap and 1 <= kb <= 32 and g[4] < 2 ** 24
+                # the first doubling that fits: half of it (above the request) did not
+                if g[1] > g[0]:
+                    assert fit_model(g[1] / np.float32(2.0), mn, mx, cap)[0] != g[1] / np.float32(2.0)
+
+
+def test_sor_search_grid_of_an_overflowing_crop_box(driver):
+    """A crop box of +-2e38 or +-FLT_MAX on any axis fits no finite cell: the frame's search grid is then over the cloud's own
+    bounds (grid mode 0, the cell untouched), as for a frame without a crop box. A cloud whose own extent overflows fp32 gets
+    one cell of +inf (inverse 0); any other cloud a finite cell whose grid fits a quarter of the row table."""
+    got = sorcell(driver, ["0 nan crop -20 -20 -5 20 20 5", "0 nan crop -2e38 -20 -5 2e38 20 5",
+                           "0 nan crop -20 -20 -2e38 20 20 2e38", "0 nan crop -3.4e38 -3.4e38 -3.4e38 3.4e38 3.4e38 3.4e38",
+                           "0 1.5 crop -2e38 -2e38 -2e38 2e38 2e38 2e38", "0 nan crop -1e30 -1e30 -1e30 1e30 1e30 1e30"])
+    assert got[0][5] == 1 and got[0][1] == np.float32(0.5) and got[0][2] < 32
+    for g in got[1:5]:
+        assert g[5] == 0 and g[1] == g[0] and g[2] == 99, g
+    assert got[5][5] == 1 and np.isfinite(got[5][1]) and got[5][2] <= 32
+    got = sorcell(driver, ["0 nan bounds -3e38 0 0 3e38 1 1", "0 nan bounds 0 0 -3.4e38 1 1 3.4e38",
+                           "0 nan bounds -1e38 -1e38 -1e38 1e38 1e38 1e38", "0 nan bounds -20 -20 -5 20 20 5",
+                           "0.05 nan bounds 1e6 1e6 1e6 1000010 1000010 1000010"])
+    for g in got[:2]:
+        assert g[1] == np.inf and g[2] == 99, g
+    for g in got[2:]:
+        assert np.isfinite(g[1]) and g[2] <= 32 and 0 < g[3] <= ROW_CAP // 4, g
+    assert got[3][1] == np.float32(0.5)
