@@ -43,6 +43,7 @@ SYMBOLS = [
     "cm_set_sensor_time_field", "cm_set_ego_motion",
     "cm_result_voxel_cov", "cm_result_voxel_cov_device",
     "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
+    "cm_result_clusters", "cm_result_clusters_device",
 ]
 MAX_ZONES = 8
 
@@ -140,6 +141,25 @@ class VoxelCov(C.Structure):
 VOXEL_COV_DTYPE = np.dtype([("mean", "<f4", (3,)), ("count", "<u4"), ("cov", "<f4", (6,)), ("icov", "<f4", (6,)),
                             ("evals", "<f4", (3,)), ("flags", "<u4")])
 assert VOXEL_COV_DTYPE.itemsize == C.sizeof(VoxelCov) == 80
+
+
+# Euclidean cluster extraction on the result (cm_result_clusters)
+CLUSTER_NONE = 0xFFFFFFFF
+
+
+class ClusterParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("min_cluster_size", C.c_uint32), ("max_cluster_size", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class Cluster(C.Structure):
+    """cm_cluster (40 bytes): members at indices[first : first + n_voxels]; min / max: the box of their centroids."""
+    _fields_ = [("first", C.c_uint32), ("n_voxels", C.c_uint32), ("n_points", C.c_uint32), ("_pad", C.c_uint32),
+                ("min", C.c_float * 3), ("max", C.c_float * 3)]
+
+
+CLUSTER_DTYPE = np.dtype([("first", "<u4"), ("n_voxels", "<u4"), ("n_points", "<u4"), ("_pad", "<u4"),
+                          ("min", "<f4", (3,)), ("max", "<f4", (3,))])
+assert CLUSTER_DTYPE.itemsize == C.sizeof(Cluster) == 40 and C.sizeof(ClusterParams) == 16
 
 
 def sym6_to_3x3(a):
@@ -247,6 +267,9 @@ def load():
     L.cm_sor_distances_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_result_voxel_cov.argtypes = [vp, C.POINTER(CovParams), vp, u64]
     L.cm_result_voxel_cov_device.argtypes = [vp, C.POINTER(CovParams), C.POINTER(vp), C.POINTER(u64)]
+    L.cm_result_clusters.argtypes = [vp, C.POINTER(ClusterParams), vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.cm_result_clusters_device.argtypes = [vp, C.POINTER(ClusterParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                            C.POINTER(u64), C.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -527,6 +550,32 @@ class CloudMerger:
         self._check(self._lib.cm_result_voxel_cov_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)),
                     "cm_result_voxel_cov_device")
         return ptr.value, n.value
+
+    # ---- Euclidean cluster extraction on the last result (cm_result_clusters) ----
+    def clusters(self, tolerance, min_size=1, max_size=2**32 - 1):
+        """(labels, clusters, indices) of the last result: labels (n_out,) uint32, CLUSTER_NONE where the size filter dropped
+        the voxel's component; clusters (n_clusters,) CLUSTER_DTYPE; indices (n_clustered,) uint32, the member voxels grouped
+        by cluster and ascending inside one (pcl::EuclideanClusterExtraction, numbered by smallest member)."""
+        p = ClusterParams(float(tolerance), int(min_size), int(max_size), 0)
+        _, n_out = self.result_device()
+        cap = max(int(n_out), 1)
+        labels = np.empty(cap, dtype=np.uint32)
+        table = np.empty(cap, dtype=CLUSTER_DTYPE)
+        indices = np.empty(cap, dtype=np.uint32)
+        nc, nm = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.cm_result_clusters(self._ctx, C.byref(p), labels.ctypes.data, cap, table.ctypes.data, cap,
+                                                 indices.ctypes.data, cap, C.byref(nc), C.byref(nm)), "cm_result_clusters")
+        return labels[: int(n_out)].copy(), table[: nc.value].copy(), indices[: nm.value].copy()
+
+    def clusters_device(self, tolerance, min_size=1, max_size=2**32 - 1):
+        """(labels ptr, clusters ptr, indices ptr, n_clusters, n_clustered): the same tables in device memory, owned by the
+        context and valid until the next merge or the next call."""
+        p = ClusterParams(float(tolerance), int(min_size), int(max_size), 0)
+        lp, cp, ip = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nc, nm = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.cm_result_clusters_device(self._ctx, C.byref(p), C.byref(lp), C.byref(cp), C.byref(ip), C.byref(nc),
+                                                        C.byref(nm)), "cm_result_clusters_device")
+        return lp.value, cp.value, ip.value, nc.value, nm.value
 
     # ---- statistical outlier removal before the voxel grid (cm_set_statistical_outlier) ----
     def set_statistical_outlier(self, mean_k, std_mul=1.0, search_cell=0.0):

@@ -49,6 +49,9 @@ void free_all(cm_ctx* c) {
     F(c->out_other); F(c->out32_other); F(c->motion_buf);
     F(c->cov_keys_a); F(c->cov_keys_b); F(c->cov_vals_a); F(c->cov_vals_b); F(c->cov_hist); F(c->cov_grp);
     F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
+    F(c->cl_keys_a); F(c->cl_keys_b); F(c->cl_vals_a); F(c->cl_vals_b); F(c->cl_hist); F(c->cl_grp); F(c->cl_parent); F(c->cl_root);
+    F(c->cl_size); F(c->cl_npts); F(c->cl_num); F(c->cl_labels); F(c->cl_pts); F(c->cl_tile_sums); F(c->cl_rows); F(c->cl_words);
+    F(c->cl_state); F(c->cl_clusters);
     F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
@@ -125,6 +128,21 @@ int voxel_cov_check(cm_ctx* c, const cm_cov_params* p, cm_cov_params* q) {
     *q = p ? *p : cm_cov_params{6u, 0.01f};
     if (q->min_points < 3) return fail(c, CM_BAD_ARG, "min_points must be at least 3");
     if (!(q->eig_mult >= 0.0f && q->eig_mult <= 1.0f)) return fail(c, CM_BAD_ARG, "eig_mult must lie in [0, 1]");
+    return CM_OK;
+}
+
+// The refusals of cm_result_clusters*: CM_OK when the last result can be clustered with *p. Caller holds merge_mu.
+int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
+    if (!p) return fail(c, CM_BAD_ARG, "no cluster parameters");
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->have_result) return fail(c, CM_BAD_ARG, "no result");
+    if (c->last_mode != 0) return fail(c, CM_BAD_ARG, "the last result is a partial or merged table (cm_merge_partial / cm_merge_tables)");
+    if (c->result.status != CM_OK) return fail(c, CM_BAD_ARG, std::string("last frame has no voxel grid (") + k_status_names(c->result.status) + ")");
+    if (!std::isfinite(p->tolerance) || !(p->tolerance > 0.0f)) return fail(c, CM_BAD_ARG, "tolerance must be finite and > 0");
+    const float t2 = p->tolerance * p->tolerance;
+    if (!std::isfinite(t2) || !(t2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of the tolerance must be finite and > 0");
+    if (p->min_cluster_size == 0) return fail(c, CM_BAD_ARG, "min_cluster_size must be at least 1");
+    if (p->min_cluster_size > p->max_cluster_size) return fail(c, CM_BAD_ARG, "min_cluster_size exceeds max_cluster_size");
     return CM_OK;
 }
 
@@ -548,6 +566,64 @@ int cm_result_voxel_cov_device(cm_ctx* c, const cm_cov_params* p, const void** d
     if (e != CM_OK) return e;
     *dev_ptr = c->cov_entries;
     *n = c->result.n_out;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_cluster) == 40 && sizeof(CmClusterDev) == sizeof(cm_cluster), "cm_cluster is 40 bytes");
+static_assert(sizeof(cm_cluster_params) == 16, "cm_cluster_params is 16 bytes");
+static_assert(CM_CLUSTER_NONE == CM_INVALID_KEY, "the radix sort drops the unclustered voxels as invalid keys");
+
+int cm_result_clusters(cm_ctx* c, const cm_cluster_params* p, uint32_t* labels_host, uint64_t labels_capacity,
+                       cm_cluster* clusters_host, uint64_t clusters_capacity, uint32_t* indices_host, uint64_t indices_capacity,
+                       uint64_t* n_clusters, uint64_t* n_clustered) {
+    if (!c || !n_clusters || !n_clustered) return CM_BAD_ARG;
+    *n_clusters = 0;
+    *n_clustered = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = clusters_check(c, p);
+    if (e != CM_OK) return e;
+    if ((!labels_host && labels_capacity) || (!clusters_host && clusters_capacity) || (!indices_host && indices_capacity))
+        return fail(c, CM_BAD_ARG, "a destination with a capacity but no pointer");
+    e = clusters(c, *p);
+    if (e != CM_OK) return e;
+    *n_clusters = c->cl_n_clusters;
+    *n_clustered = c->cl_n_clustered;
+    if (labels_host && c->result.n_out > labels_capacity) return fail(c, CM_CAPACITY, "labels destination too small");
+    if (clusters_host && c->cl_n_clusters > clusters_capacity) return fail(c, CM_CAPACITY, "clusters destination too small");
+    if (indices_host && c->cl_n_clustered > indices_capacity) return fail(c, CM_CAPACITY, "indices destination too small");
+    const uint64_t n = c->result.n_out;
+    uint64_t bytes = 0;
+    if (labels_host && n) {
+        HIP_TRY(c, hipMemcpyAsync(labels_host, c->cl_labels, n * 4, hipMemcpyDeviceToHost, c->stream));
+        bytes += n * 4;
+    }
+    if (clusters_host && c->cl_n_clusters) {
+        HIP_TRY(c, hipMemcpyAsync(clusters_host, c->cl_clusters, c->cl_n_clusters * sizeof(cm_cluster), hipMemcpyDeviceToHost, c->stream));
+        bytes += c->cl_n_clusters * sizeof(cm_cluster);
+    }
+    if (indices_host && c->cl_n_clustered) {
+        HIP_TRY(c, hipMemcpyAsync(indices_host, c->cl_indices, c->cl_n_clustered * 4, hipMemcpyDeviceToHost, c->stream));
+        bytes += c->cl_n_clustered * 4;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += bytes;
+    return CM_OK;
+}
+
+int cm_result_clusters_device(cm_ctx* c, const cm_cluster_params* p, const void** labels, const void** clusters_dev,
+                              const void** indices, uint64_t* n_clusters, uint64_t* n_clustered) {
+    if (!c || !labels || !clusters_dev || !indices || !n_clusters || !n_clustered) return CM_BAD_ARG;
+    *n_clusters = 0;
+    *n_clustered = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = clusters_check(c, p);
+    if (e == CM_OK) e = clusters(c, *p);
+    if (e != CM_OK) return e;
+    *labels = c->result.n_out ? c->cl_labels : nullptr;
+    *clusters_dev = c->cl_n_clusters ? c->cl_clusters : nullptr;
+    *indices = c->cl_n_clustered ? c->cl_indices : nullptr;
+    *n_clusters = c->cl_n_clusters;
+    *n_clustered = c->cl_n_clustered;
     return CM_OK;
 }
 

@@ -169,6 +169,24 @@ struct cm_ctx {
     void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
     uint64_t cov_cap_entries = 0;
 
+    // Euclidean cluster extraction on the result (cm_kernels_cluster.hip), on request after a frame: buffers of its own — no
+    // frame reads them — allocated by the first request and grown with the results. It reads `out` (and out_cnt).
+    uint32_t cl_cap_slots = 0;           // words of each per-voxel buffer (a multiple of CM_TILE)
+    uint32_t *cl_keys_a = nullptr, *cl_keys_b = nullptr, *cl_vals_a = nullptr, *cl_vals_b = nullptr;
+    uint32_t *cl_hist = nullptr, *cl_grp = nullptr;      // (cl_cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
+    uint32_t *cl_parent = nullptr, *cl_root = nullptr, *cl_size = nullptr, *cl_npts = nullptr, *cl_num = nullptr;
+    uint32_t* cl_labels = nullptr;       // the label table
+    void* cl_pts = nullptr;              // the centroids in search-grid order (x, y, z, result index)
+    void* cl_tile_sums = nullptr;        // per tile: kept roots and their voxels, then their exclusive prefixes
+    void* cl_rows = nullptr;             // (y,z)-row ranges of the search grid
+    uint64_t cl_cap_rows = 0;
+    uint32_t* cl_words = nullptr;        // [0] clusters, [1] clustered voxels, [2..7] bounds images, [8..263] digit totals (k_gscan)
+    CmFrameState* cl_state = nullptr;    // two records: the sort by cell, the sort by cluster number
+    void* cl_clusters = nullptr;         // the cluster table: cm_cluster per cluster
+    uint64_t cl_cap_clusters = 0;
+    const uint32_t* cl_indices = nullptr;   // the member lists of the last call (one of cl_vals_a / cl_vals_b)
+    uint64_t cl_n_clusters = 0, cl_n_clustered = 0;
+
     // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
     // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
     bool sor_on = false;
@@ -220,3 +238,5 @@ int wait_frame(cm_ctx* c, cm_result* res);
 int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_entries, uint32_t n_tables, const cm_params* p,
                  cm_result* res);
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
+// The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
+int clusters(cm_ctx* c, const cm_cluster_params& q);

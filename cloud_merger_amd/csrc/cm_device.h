@@ -221,3 +221,16 @@ struct CmSorStatsDev {
     unsigned long long n_valid, n_removed;
     double mean, stddev, threshold;
 };
+
+// Euclidean cluster extraction (cm_kernels_cluster.hip): the search grid of the result's centroids — cell c = floor((p - min)
+// * inv) per axis, clamped to [0, dims - 1], key = c0 + dims0 * (c1 + dims1 * c2) — passed by value to k_cl_keys; and one
+// table entry (== cm_cluster, 40 bytes; the AABB as order-preserving integer images until k_cl_decode).
+struct CmClusterGridDev {
+    float min[3];
+    float inv;
+    uint32_t dims[3];
+};
+struct CmClusterDev {
+    uint32_t first, n_voxels, n_points, _pad;
+    uint32_t lo[3], hi[3];
+};

@@ -150,3 +150,31 @@ void cmk_sor_bins(hipStream_t s, const CmFrameState* st, const float* dist, unsi
 void cmk_sor_threshold(hipStream_t s, const CmFrameState* st, unsigned long long* words, uint32_t k, float std_mul);
 void cmk_sor_mask(hipStream_t s, const CmFrameState* st, const float* dist, unsigned long long* words, unsigned char* mask,
                   uint32_t n_padded);
+
+// ---- Euclidean cluster extraction on the last result (cm_kernels_cluster.hip) ----------------------------------------------
+// recs: the n result records. bounds: 6 words, [0..2] set to 0xFFFFFFFF and [3..5] to 0 before the launch.
+void cmk_cl_bounds(hipStream_t s, const void* recs, uint32_t n, uint32_t* bounds);
+// keys: n_tiles * CM_TILE words; hist: n_tiles rows; grp: the pass-0 group rows (zeroed). Leaves in st what the radix kernels
+// and the row table read (status, n_passes, div_b).
+void cmk_cl_keys(hipStream_t s, const void* recs, uint32_t n, const CmClusterGridDev& g, uint32_t n_passes, CmFrameState* st,
+                 uint32_t* keys, uint32_t* hist, uint32_t* grp, uint32_t n_tiles);
+// After the sort: pts = (x, y, z, result index) in sorted order; parent[i] = i; size / npts zeroed.
+void cmk_cl_gather(hipStream_t s, const void* recs, const CmFrameState* st, const uint32_t* vals_a, const uint32_t* vals_b, uint32_t n,
+                   void* pts, uint32_t* parent, uint32_t* size, uint32_t* npts);
+// After cmk_sorted_rows on st's grid: every edge of the tolerance graph united in parent (indices of the result).
+void cmk_cl_hook(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
+                 const void* rows, uint32_t n, float tol2, uint32_t* parent);
+// root[i]; size[r] / npts[r] (sum of out_cnt; nullptr: left 0) at every root r.
+void cmk_cl_roots(hipStream_t s, const uint32_t* parent, const uint32_t* out_cnt, uint32_t n, uint32_t* root, uint32_t* size,
+                  uint32_t* npts);
+// tile_sums: n_tiles uint2 -> exclusive (clusters, clustered voxels) before every tile; words[0] / [1]: the totals.
+void cmk_cl_count(hipStream_t s, const uint32_t* root, const uint32_t* size, uint32_t n, uint32_t min_size, uint32_t max_size,
+                  void* tile_sums, uint32_t* words, uint32_t n_tiles);
+// num[i]: cluster number of a kept root, else CM_INVALID_KEY; clusters: first / n_voxels / n_points, empty AABB images.
+void cmk_cl_number(hipStream_t s, const uint32_t* root, const uint32_t* size, const uint32_t* npts, const void* tile_excl,
+                   uint32_t n, uint32_t min_size, uint32_t max_size, uint32_t* num, void* clusters, uint32_t n_tiles);
+// labels[i]; the AABB images; keys / hist / grp / st for the sort of (cluster number, voxel index) as cmk_cl_keys leaves them.
+void cmk_cl_labels(hipStream_t s, const void* recs, const uint32_t* root, const uint32_t* num, uint32_t n, uint32_t n_passes,
+                   CmFrameState* st, uint32_t* labels, uint32_t* keys, uint32_t* hist, uint32_t* grp, void* clusters,
+                   uint32_t n_tiles);
+void cmk_cl_decode(hipStream_t s, void* clusters, uint32_t n_clusters);     // AABB images -> floats

@@ -1,6 +1,6 @@
 // cm_launch.cpp — frame assembly and the launch sequences: the general path (cm_kernels.hip, with the ground and outlier
 // pre-stages), the bucket path's fixed-grid and quantile passes (cm_kernels_v2/v3/v4.hip), the replays of a frame the bucket
-// path hands back, the table merge and the covariance sort. Which route a frame takes is decided in cm_route.cpp: everything
+// path hands back, the table merge, the covariance sort and the cluster extraction. Which route a frame takes is decided in cm_route.cpp: everything
 // here reads c->plan.
 #include <algorithm>
 #include <cmath>
@@ -1007,5 +1007,150 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
     HIP_TRY(c, hipMemcpyAsync(&err, c->cov_words + 1, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (err) return fail(c, CM_INTERNAL, "covariance: a voxel's points did not match its count in the result");
+    return CM_OK;
+}
+
+namespace {
+
+// Host inverse of the kernels' order-preserving float image (k_cl_bounds).
+float ord_to_float(uint32_t o) {
+    const uint32_t b = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+// The stages a by-product marked (prof_mark) into c->stage_times, as wait_frame does for a frame's.
+void collect_stage_times(cm_ctx* c) {
+    if (!(c->flags & CM_FLAG_PROFILE)) return;
+    cm_stage_times& t = c->stage_times;
+    std::memset(&t, 0, sizeof t);
+    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
+    for (size_t i = 0; i < n && i < CM_MAX_STAGES; ++i) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
+        std::snprintf(t.name[i], sizeof t.name[i], "%s", c->prof_names[i].c_str());
+        t.ms[i] = ms;
+        t.n_stages = static_cast<uint32_t>(i + 1);
+    }
+}
+
+}  // namespace
+
+// Euclidean cluster extraction on the last result (cm_kernels_cluster.hip): labels, cluster table and member lists into the
+// cl_* buffers. Launches on the context's stream, reads `out` — what cm_result_copy reads — and out_cnt where the context
+// keeps it, and writes only the cl_* buffers: nothing a later frame reads. Two host round trips: the bounds of the
+// centroids (the search grid is decided on the host, cluster_grid) and the cluster count (the second sort's passes, the
+// table's size). Under CM_FLAG_PROFILE the stage times of the call replace the frame's in cm_get_stage_times.
+int clusters(cm_ctx* c, const cm_cluster_params& q) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    c->cl_n_clusters = 0;
+    c->cl_n_clustered = 0;
+    c->cl_indices = nullptr;
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
+    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    if (n_slots > c->cl_cap_slots) {
+        uint32_t** words[] = {&c->cl_keys_a, &c->cl_keys_b, &c->cl_vals_a, &c->cl_vals_b, &c->cl_parent, &c->cl_root,
+                              &c->cl_size,   &c->cl_npts,   &c->cl_num,    &c->cl_labels, &c->cl_hist,   &c->cl_grp};
+        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
+        if (c->cl_pts) { (void)hipFree(c->cl_pts); c->cl_pts = nullptr; }
+        if (c->cl_tile_sums) { (void)hipFree(c->cl_tile_sums); c->cl_tile_sums = nullptr; }
+        c->cl_cap_slots = 0;
+        bool ok = true;
+        for (int k = 0; k < 10; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->cl_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->cl_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
+        ok = ok && A(&c->cl_pts, static_cast<size_t>(n_slots) * 16);
+        ok = ok && A(&c->cl_tile_sums, static_cast<size_t>(nt) * 8);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's buffers");
+        c->cl_cap_slots = n_slots;
+    }
+    if (!c->cl_state) {
+        bool ok = A(reinterpret_cast<void**>(&c->cl_state), 2 * sizeof(CmFrameState)) &&
+                  A(reinterpret_cast<void**>(&c->cl_words), (8 + CM_RADIX) * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's state");
+    }
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->cl_words;
+    SortPairs sp = {c->cl_keys_a, c->cl_keys_b, c->cl_vals_a, c->cl_vals_b, c->cl_hist, w + 8, c->cl_grp, c->cl_grp + gw};
+    c->prof_used = 0;
+
+    // the search grid: over the centroids' own bounds
+    prof_mark(c, "k_cl_bounds");
+    HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
+    HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
+    cmk_cl_bounds(st, c->out, n, w + 2);
+    uint32_t img[6];
+    HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
+    const ClusterGrid grid = cluster_grid(q.tolerance, mn, mx, CM_ROW_TABLE_CAP);
+    const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
+    if (n_rows > c->cl_cap_rows) {
+        if (c->cl_rows) { (void)hipFree(c->cl_rows); c->cl_rows = nullptr; c->cl_cap_rows = 0; }
+        if (!A(&c->cl_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's row table");
+        c->cl_cap_rows = n_rows;
+    }
+    CmClusterGridDev gd;
+    for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
+    gd.inv = grid.inv;
+
+    // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
+    CmFrameState* st_cell = c->cl_state;
+    CmFrameState* st_num = c->cl_state + 1;
+    const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    HIP_TRY(c, hipMemsetAsync(c->cl_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+    prof_mark(c, "k_cl_keys");
+    cmk_cl_keys(st, c->out, n, gd, passes, st_cell, c->cl_keys_a, c->cl_hist, c->cl_grp, nt);
+    radix_sort_pairs(c, st_cell, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
+    prof_mark(c, "k_cl_gather");
+    cmk_cl_gather(st, c->out, st_cell, c->cl_vals_a, c->cl_vals_b, n, c->cl_pts, c->cl_parent, c->cl_size, c->cl_npts);
+    prof_mark(c, "cl_rows");
+    cmk_sorted_rows(st, nullptr, st_cell, c->cl_keys_a, c->cl_vals_a, c->cl_keys_b, c->cl_vals_b, c->cl_pts, c->cl_rows, n_slots, true);
+
+    // connected components, sizes, the roots the size filter keeps
+    const float tol2 = q.tolerance * q.tolerance;
+    prof_mark(c, "k_cl_hook");
+    cmk_cl_hook(st, st_cell, c->cl_keys_a, c->cl_keys_b, c->cl_pts, c->cl_rows, n, tol2, c->cl_parent);
+    prof_mark(c, "k_cl_roots");
+    cmk_cl_roots(st, c->cl_parent, (c->flags & CM_FLAG_OCCUPANCY) ? c->out_cnt : nullptr, n, c->cl_root, c->cl_size, c->cl_npts);
+    prof_mark(c, "k_cl_count");
+    cmk_cl_count(st, c->cl_root, c->cl_size, n, q.min_cluster_size, q.max_cluster_size, c->cl_tile_sums, w, nt);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t counts[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const uint32_t n_clusters = counts[0];
+    if (n_clusters > c->cl_cap_clusters) {
+        if (c->cl_clusters) { (void)hipFree(c->cl_clusters); c->cl_clusters = nullptr; c->cl_cap_clusters = 0; }
+        if (!A(&c->cl_clusters, static_cast<size_t>(n_clusters) * sizeof(cm_cluster))) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster table");
+        c->cl_cap_clusters = n_clusters;
+    }
+
+    // numbers, labels, AABB, and the member lists: (cluster number, voxel index) sorted by cluster number, stable
+    const uint32_t passes_num = (key_width(n_clusters ? n_clusters : 1u) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    prof_mark(c, "k_cl_number");
+    cmk_cl_number(st, c->cl_root, c->cl_size, c->cl_npts, c->cl_tile_sums, n, q.min_cluster_size, q.max_cluster_size, c->cl_num,
+                  c->cl_clusters, nt);
+    HIP_TRY(c, hipMemsetAsync(c->cl_grp, 0, static_cast<size_t>(passes_num) * gw * 4, st));
+    prof_mark(c, "k_cl_labels");
+    cmk_cl_labels(st, c->out, c->cl_root, c->cl_num, n, passes_num, st_num, c->cl_labels, c->cl_keys_a, c->cl_hist, c->cl_grp,
+                  c->cl_clusters, nt);
+    if (n_clusters) {
+        radix_sort_pairs(c, st_num, sp, passes_num, nt, n_slots, false, nullptr, "k_scatter(lists)");
+        prof_mark(c, "k_cl_decode");
+        cmk_cl_decode(st, c->cl_clusters, n_clusters);
+    }
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->cl_n_clusters = n_clusters;
+    c->cl_n_clustered = counts[1];
+    c->cl_indices = (passes_num & 1u) ? c->cl_vals_b : c->cl_vals_a;
     return CM_OK;
 }

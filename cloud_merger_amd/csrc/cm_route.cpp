@@ -77,6 +77,38 @@ float sor_bounds_cell(float cell, const float mn[3], const float mx[3], uint32_t
     return fit > 0.0f ? fit : std::numeric_limits<float>::infinity();
 }
 
+ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], uint32_t row_cap) {
+    ClusterGrid g;
+    g.doublings = 0;
+    float ext[3];
+    bool finite = true;
+    for (int a = 0; a < 3; ++a) {
+        ext[a] = mx[a] - mn[a];
+        finite = finite && std::isfinite(ext[a]);
+    }
+    for (float cell = tolerance * 1.00390625f; finite && std::isfinite(cell); cell *= 2.0f, ++g.doublings) {
+        const float inv = 1.0f / cell;
+        unsigned long long d[3];
+        bool fits = true;
+        for (int a = 0; a < 3 && fits; ++a) {
+            const float v = ext[a] * inv;
+            fits = v >= 0.0f && v < static_cast<float>(CM_CLUSTER_AXIS_CAP);
+            if (fits) d[a] = static_cast<unsigned long long>(std::floor(v)) + 1ull;
+        }
+        if (!fits || d[1] * d[2] > row_cap || d[0] * d[1] * d[2] > 0xFFFFFFFFull) continue;
+        g.cell = cell;
+        g.inv = inv;
+        for (int a = 0; a < 3; ++a) g.dims[a] = static_cast<uint32_t>(d[a]);
+        g.key_bits = key_width(d[0] * d[1] * d[2]);
+        return g;
+    }
+    g.cell = std::numeric_limits<float>::infinity();
+    g.inv = 0.0f;
+    g.dims[0] = g.dims[1] = g.dims[2] = 1u;
+    g.key_bits = 1;
+    return g;
+}
+
 // A cloud near the limit of PCL's 32-bit index leaves no room for an eighth of its extent on every side: take what
 // fits (a frame right behind one that reached far out would otherwise lose its box, and with it the bucket path).
 void RouteState::set_predicted_box(const float mn[3], const float mx[3], const float leaf[3]) {

@@ -27,6 +27,20 @@ float sor_cell(float requested, double last_mean);
 // axis (the bucket kernels' multiplier). Returns the cell and its grid's key width. The result never depends on the cell.
 // 0: no finite cell fits (an extent beyond FLT_MAX on some axis); *key_bits is then left unwritten.
 float sor_fit_cell(float cell, const float bmin[3], const float bmax[3], uint32_t row_cap, uint32_t* key_bits);
+// Euclidean cluster extraction (cm_result_clusters): the search grid over the bounds [mn, mx] of the result's centroids. A
+// centroid's cell is floor((p - mn) * inv) per axis, in fp32. The cell starts a little above the tolerance (1 + 2^-8: with
+// at most CM_CLUSTER_AXIS_CAP cells per axis the fp32 rounding of that expression moves a centroid by less than 2^-10 of a
+// cell, so two centroids the fp32 predicate joins never lie two cells apart) and doubles until the grid fits: at most
+// CM_CLUSTER_AXIS_CAP cells per axis, at most row_cap (y,z) rows, keys below 0xFFFFFFFF. An extent that overflows fp32 on
+// some axis (or a cell that does) is searched as one cell: cell +inf, inverse 0. The partition never depends on the cell.
+#define CM_CLUSTER_AXIS_CAP 4096u
+struct ClusterGrid {
+    float cell, inv;
+    uint32_t dims[3];
+    uint32_t key_bits;
+    uint32_t doublings;
+};
+ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], uint32_t row_cap);
 // The search grid of a frame (cm_launch.cpp enqueue). sor_crop_grid: over the crop box when one is on and some finite cell
 // fits it (half the row table): returns 1 (the stage's grid mode) with that cell in *cell and its key width; else 0 with
 // *cell unchanged, and the grid is over the cloud's own bounds. sor_bounds_cell: the cell over the measured bounds [mn, mx],

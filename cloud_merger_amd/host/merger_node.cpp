@@ -144,6 +144,9 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             ok = ok && q.search_cell >= 0.0f;
             if (ok) { c.sor = q; c.sor_enable = true; }
         }
+        else if (key == "cluster_tolerance") ok = static_cast<bool>(is >> c.cluster_tolerance) && c.cluster_tolerance >= 0.0f && std::isfinite(c.cluster_tolerance);
+        else if (key == "cluster_min_size") ok = static_cast<bool>(is >> c.cluster_min_size) && c.cluster_min_size >= 1;
+        else if (key == "cluster_max_size") ok = static_cast<bool>(is >> c.cluster_max_size) && c.cluster_max_size >= 1;
         else if (key == "motion_compensation") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.motion_compensation = v == 1; }
         else if (key == "time_field") {
             std::string name, type;
@@ -263,6 +266,20 @@ int CloudMergerNode::enqueue_frame(bool wait, cm_result* r) {
     return cm_wait(ctx_, r);
 }
 
+int CloudMergerNode::clusters_of_frame(const cm_result& r) {
+    n_clusters_ = 0;
+    cluster_labels_.clear();
+    if (!(cfg_.cluster_tolerance > 0.0f) || r.status != CM_OK) return CM_OK;
+    const cm_cluster_params q{cfg_.cluster_tolerance, cfg_.cluster_min_size, cfg_.cluster_max_size, 0};
+    cluster_labels_.resize(r.n_out);
+    uint64_t n_clusters = 0, n_clustered = 0;
+    const int st = cm_result_clusters(ctx_, &q, cluster_labels_.data(), cluster_labels_.size(), nullptr, 0, nullptr, 0,
+                                      &n_clusters, &n_clustered);
+    if (st != CM_OK) { cluster_labels_.clear(); set_error(cm_last_error(ctx_)); return st; }
+    n_clusters_ = n_clusters;
+    return CM_OK;
+}
+
 uint64_t CloudMergerNode::newest_stamp() const {
     uint64_t newest = 0;
     for (const auto& t : stamp_ns_) newest = std::max(newest, t.load());
@@ -344,6 +361,7 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
     if (st < 0) { set_error(cm_last_error(ctx_)); return st; }
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
+    { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
     {
         cm_frame_stats fs;
         if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
@@ -444,6 +462,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     if (st < 0) { set_error(cm_last_error(ctx_)); return st; }
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
+    { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
     {
         // flag reset, :151-157 — for exactly the clouds this fuse read: a callback may have delivered the next one since
         cm_frame_stats fs;

@@ -75,6 +75,11 @@ struct NodeConfig {
     // pcl::StatisticalOutlierRemoval). Off by default; not combined with `outlier` or `ground`.
     bool sor_enable = false;
     cm_sor_params sor{};
+    // Euclidean cluster extraction on every published voxel cloud (cm_result_clusters; pcl::EuclideanClusterExtraction). Off
+    // by default (tolerance 0). On: after the frame has been waited for the node asks for the labels and keeps them, with
+    // the cluster count, until the next frame (cluster_count(), cluster_labels()).
+    float cluster_tolerance = 0.0f;
+    uint32_t cluster_min_size = 1, cluster_max_size = 0xFFFFFFFFu;
     struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
     TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
@@ -90,6 +95,7 @@ struct NodeConfig {
 //   motion_compensation <0|1> | time_field <sensor_name> <byte_offset> <f32|u32ns>   (ego-motion compensation; f32: seconds,
 //   u32ns: nanoseconds, relative to the cloud's header stamp)
 //   statistical_outlier <mean_k> <std_mul> [search_cell]   (pcl::StatisticalOutlierRemoval before the voxel grid)
+//   cluster_tolerance <metres> | cluster_min_size <n> | cluster_max_size <n>   (clusters of every voxel cloud; 0: off)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
@@ -154,6 +160,10 @@ public:
     uint64_t frames_quantile() const { return n_quantile_; }
     uint64_t frames_redone() const { return n_redone_; }
     uint64_t clouds_dropped_for_sync() const { return dropped_; }
+    // cluster_tolerance > 0: clusters of the frame waited for last, and the label of each of its voxels (CM_CLUSTER_NONE:
+    // in no cluster), in the order of the published cloud. Read from the thread that calls spin_once.
+    uint64_t cluster_count() const { return n_clusters_; }
+    const std::vector<uint32_t>& cluster_labels() const { return cluster_labels_; }
 
 private:
     NodeConfig cfg_;
@@ -192,6 +202,9 @@ private:
     std::mutex twist_mu_;
     float twist_v_[3] = {0, 0, 0}, twist_w_[3] = {0, 0, 0};
     uint64_t motion_t_ref_ = 0;
+    uint64_t n_clusters_ = 0;
+    std::vector<uint32_t> cluster_labels_;
+    int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters when the config asks for it
     int enqueue_frame(bool wait, cm_result* r);   // cm_merge_voxelize(_async), with the motion of the frame set under the slot locks
 };
 

@@ -406,6 +406,56 @@ CM_API int cm_get_sor_stats(cm_ctx* ctx, cm_sor_stats* out);
  * more than capacity: CM_CAPACITY. */
 CM_API int cm_sor_distances_copy(cm_ctx* ctx, float* host_dst, uint64_t capacity, uint64_t* n);
 
+/* ---- Euclidean cluster extraction on the result (pcl::EuclideanClusterExtraction; an extension) ----------------------
+ * Obstacle segmentation of the cloud this library publishes, computed on request after a frame. Input: the
+ * n_out records of the last result, c_0 .. c_{n-1} in the order of cm_result_copy, their x, y, z as fp32.
+ *   1. Edge. i ~ j iff d2(c_i, c_j) < float(tolerance * tolerance), d2 = (dx*dx + dy*dy) + dz*dz, dx = c_i.x - c_j.x ..., fp32,
+ *      round-to-nearest, no contraction: the distance and the strict < of the radius outlier stage. Symmetric bit for bit.
+ *   2. Component. The connected components of that graph.
+ *   3. Size filter. A component of m voxels is a cluster iff min_cluster_size <= m <= max_cluster_size. As in PCL the whole
+ *      component is grown first and then kept or dropped as a whole. Sizes count voxels: points of the cloud being clustered.
+ *   4. Numbering. The kept clusters are numbered 0, 1, ... by ascending smallest member index. (The one deviation: PCL then
+ *      std::sorts its clusters by size, which is unstable for ties. The table carries the sizes; sort it if that order is
+ *      wanted.)
+ *   5. Outputs, owned by the context and valid until the next merge or the next call:
+ *        labels[n_out]         entry k belongs to result record k: its cluster number, or CM_CLUSTER_NONE for a voxel whose
+ *                              component the size filter dropped
+ *        indices[n_clustered]  the member voxels grouped by cluster, ascending inside a cluster (PCL's
+ *                              std::vector<PointIndices>, flattened)
+ *        clusters[n_clusters]  one cm_cluster each: where its members start in indices, how many, the sum of their point
+ *                              counts (context with CM_FLAG_OCCUPANCY; 0 without), and the axis-aligned box of the member
+ *                              centroids (of two zeros of either sign, min takes -0 and max +0). No centroid: a floating
+ *                              sum over a cluster depends on its order; min / max and integer sums do not.
+ * The partition is independent of summation order and launch geometry. CM_FLAG_OCCUPANCY is not required.
+ * Refused with CM_BAD_ARG (cm_last_error says why): a frame in flight, no result, a result of cm_merge_partial /
+ * cm_merge_tables, a last status other than CM_OK (no voxel grid), a tolerance that is not finite and > 0 or whose fp32
+ * square is 0 or not finite, min_cluster_size 0, min_cluster_size > max_cluster_size. A result in which no component
+ * passes the filter is CM_OK with zero clusters and every label CM_CLUSTER_NONE. No later frame depends on whether the
+ * tables were asked for; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists the stages of this call. */
+#define CM_CLUSTER_NONE 0xFFFFFFFFu
+typedef struct cm_cluster_params {
+    float tolerance;                   /* setClusterTolerance, metres */
+    uint32_t min_cluster_size;         /* setMinClusterSize, >= 1 */
+    uint32_t max_cluster_size;         /* setMaxClusterSize */
+    uint32_t _pad;
+} cm_cluster_params;
+typedef struct cm_cluster {            /* 40 bytes */
+    uint32_t first;                    /* offset of the members in indices */
+    uint32_t n_voxels;
+    uint32_t n_points;                 /* sum of the members' point counts; 0 without CM_FLAG_OCCUPANCY */
+    uint32_t _pad;
+    float min[3], max[3];              /* box of the member centroids */
+} cm_cluster;
+/* Host copies; capacities in entries. A destination may be NULL with capacity 0 to skip it; one that is too small:
+ * CM_CAPACITY (nothing is copied). *n_clusters / *n_clustered are always written (0 when the call is refused). */
+CM_API int cm_result_clusters(cm_ctx* ctx, const cm_cluster_params* p, uint32_t* labels_host, uint64_t labels_capacity,
+                              cm_cluster* clusters_host, uint64_t clusters_capacity, uint32_t* indices_host,
+                              uint64_t indices_capacity, uint64_t* n_clusters, uint64_t* n_clustered);
+/* The same three tables left in device memory owned by the context (n_out labels, *n_clusters entries of 40 bytes,
+ * *n_clustered indices; a pointer is NULL where its table is empty). */
+CM_API int cm_result_clusters_device(cm_ctx* ctx, const cm_cluster_params* p, const void** labels, const void** clusters,
+                                     const void** indices, uint64_t* n_clusters, uint64_t* n_clustered);
+
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
 CM_API int cm_host_free(void* ptr);
