@@ -240,6 +240,12 @@ template <int LAYOUT, int N, bool NT = false>
 __device__ __forceinline__ void load_tile_raw(const unsigned char* __restrict__ data, uint32_t n, uint32_t step, uint32_t ox,
                                               uint32_t oy, uint32_t oz, uint32_t oi, uint32_t first, Pt (&p)[N]) {
     const float nan = __uint_as_float(0x7FC00000u);
+    // A full tile (all but the last one of a sensor; n is wave-uniform): every slot holds a point — no clamp, no NaN.
+    if (LAYOUT != CM_LAYOUT_GENERIC && static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(n))) >= CM_TILE) {
+#pragma unroll
+        for (int r = 0; r < N; ++r) p[r] = load_point_near<LAYOUT, NT>(data, first + r * 64);
+        return;
+    }
 #pragma unroll
     for (int r = 0; r < N; ++r) {
         const uint32_t i = first + r * 64;
@@ -253,12 +259,64 @@ __device__ __forceinline__ void load_tile_raw(const unsigned char* __restrict__ 
         p[r].i = ok ? p[r].i : 0.f;
     }
 }
+
 template <int N, bool NT = false>
 __device__ __forceinline__ void load_tile_te(const CmTileDev& te, const CmSensorDev& sd, uint32_t first, Pt (&p)[N]) {
     const uint32_t layout = te.info >> 8;
     if (layout == CM_LAYOUT_XYZI16) load_tile_raw<CM_LAYOUT_XYZI16, N, NT>(te.data, te.n_left, 16u, 0u, 4u, 8u, 12u, first, p);
     else if (layout == CM_LAYOUT_PCL32) load_tile_raw<CM_LAYOUT_PCL32, N, NT>(te.data, te.n_left, 32u, 0u, 4u, 8u, 16u, first, p);
     else load_tile_raw<CM_LAYOUT_GENERIC, N>(te.data, te.n_left, sd.point_step, sd.off_x, sd.off_y, sd.off_z, sd.off_i, first, p);
+}
+
+// The coordinates alone (k4_hist never looks at the intensity): N points of a tile entry, 64 apart, from slot `first` of
+// the tile. The two aligned layouts fetch twelve bytes per point; a full tile takes the path without clamps.
+struct Pt3 { float x, y, z; };
+typedef float cm_v3f __attribute__((ext_vector_type(3)));
+template <int LAYOUT, int N>
+__device__ __forceinline__ void load_tile_xyz_raw(const unsigned char* __restrict__ data_generic, uint32_t n, uint32_t step,
+                                                  uint32_t ox, uint32_t oy, uint32_t oz, uint32_t first, Pt3 (&p)[N]) {
+    cm_gptr data = (cm_gptr)data_generic;
+    typedef const CM_GLOBAL_AS cm_v3f* f3ptr;
+    constexpr uint32_t STEP = LAYOUT == CM_LAYOUT_XYZI16 ? 16u : 32u;
+    const float nan = __uint_as_float(0x7FC00000u);
+    if (LAYOUT != CM_LAYOUT_GENERIC && static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(n))) >= CM_TILE) {
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+            const cm_v3f v = *(f3ptr)(data + (first + r * 64) * STEP);
+            p[r].x = v.x; p[r].y = v.y; p[r].z = v.z;
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        const uint32_t i = first + r * 64, ic = i < n ? i : n - 1;
+        if (LAYOUT == CM_LAYOUT_GENERIC) {
+            cm_gptr q = data + static_cast<size_t>(ic) * step;
+            p[r].x = load_f32_unaligned(q + ox); p[r].y = load_f32_unaligned(q + oy); p[r].z = load_f32_unaligned(q + oz);
+        } else {
+            const cm_v3f v = *(f3ptr)(data + ic * STEP);
+            p[r].x = v.x; p[r].y = v.y; p[r].z = v.z;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        const bool ok = first + r * 64 < n;
+        p[r].x = ok ? p[r].x : nan; p[r].y = ok ? p[r].y : nan; p[r].z = ok ? p[r].z : nan;
+    }
+}
+// The two aligned layouts (nothing for a generic one) / the generic layout (nothing for the aligned ones): k4_hist asks for
+// the former a half-tile ahead, and for the latter — up to twelve byte loads per point — only where it uses them.
+template <int N>
+__device__ __forceinline__ void load_tile_xyz_aligned(const CmTileDev& te, uint32_t first, Pt3 (&p)[N]) {
+    const uint32_t layout = te.info >> 8;
+    if (layout == CM_LAYOUT_XYZI16) load_tile_xyz_raw<CM_LAYOUT_XYZI16, N>(te.data, te.n_left, 16u, 0u, 4u, 8u, first, p);
+    else if (layout == CM_LAYOUT_PCL32) load_tile_xyz_raw<CM_LAYOUT_PCL32, N>(te.data, te.n_left, 32u, 0u, 4u, 8u, first, p);
+}
+template <int N>
+__device__ __forceinline__ void load_tile_xyz_generic(const CmTileDev& te, const CmSensorDev& sd, uint32_t first, Pt3 (&p)[N]) {
+    const uint32_t layout = te.info >> 8;
+    if (layout != CM_LAYOUT_XYZI16 && layout != CM_LAYOUT_PCL32)
+        load_tile_xyz_raw<CM_LAYOUT_GENERIC, N>(te.data, te.n_left, sd.point_step, sd.off_x, sd.off_y, sd.off_z, first, p);
 }
 
 // N points of one lane, 64 apart (wave-striped), starting at index `first` of the sensor's cloud.

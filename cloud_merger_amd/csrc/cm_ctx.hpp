@@ -141,6 +141,7 @@ struct cm_ctx {
     uint32_t *qcnt = nullptr, *qtot = nullptr, *qbofs = nullptr;  // per-tile bucket counts / prefixes, bucket totals, bucket starts
     uint32_t* qbig = nullptr;                                     // buckets beyond CM4_CAP records: count, then their numbers
     uint16_t* qbid = nullptr;            // the bucket of every padded slot
+    uint32_t hist_resident[3] = {0, 0, 0};   // workgroups of k4_hist<11 .. 13> resident at once on this device (0: not asked yet)
 
     // per-sensor figures of the last enqueued frame (cm_frame_stats)
     uint32_t stats_n_sensors = 0;

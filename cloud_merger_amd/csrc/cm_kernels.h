@@ -98,7 +98,8 @@ void cmk4_hist(hipStream_t s, const CmFrameDev& f, CmFrameDev* fd, CmTileDev* ti
                int grid_mode, int check_box, uint32_t n_tiles,        // bid: the bucket of every padded slot (0xFFFF: no record)
                uint32_t n_buckets,
                uint32_t* big_list,                                   // (word 0 zeroed: k4_colscan's list of buckets beyond CM4_CAP)
-               uint32_t sub_shift = 0);                              // shared bins (cm_quant_sub_shift): counted per bucket >> sub_shift
+               uint32_t sub_shift,                                   // shared bins (cm_quant_sub_shift): counted per bucket >> sub_shift
+               uint32_t* resident);                                  // three words of the context (0 at first): the grid-stride launch's size for 11, 12, 13 levels
 // cap / cap_big / big_list: buckets of (cap, cap_big] records are listed (count, then numbers) for cmk3_local_big; beyond cap_big the frame aborts
 void cmk4_colscan(hipStream_t s, CmFrameState* st, uint32_t* host_state, uint32_t* cnt, uint32_t* totals, uint32_t n_tiles,
                   uint32_t cap, uint32_t cap_big, uint32_t* big_list);

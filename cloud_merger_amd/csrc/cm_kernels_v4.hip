@@ -8,6 +8,7 @@
 //
 //   k4_hist     transform + crop + index of every raw point, bucket by binary search over the splitters (LDS), counts
 //               per (4096-slot tile, bucket) as one row of 16-bit words; min/max records, frame set-up  [16 B/pt read]
+//               (grid-stride over the tiles, the next half-tile's loads in flight under the search)
 //   k4_colscan  the rows become "records of bucket b in the tiles before this one" (column prefix, in place); totals
 //               per bucket; a bucket that would not fit the finish aborts the frame                      [4 MB r + w]
 //   k4_scatter  raw points again -> records, ranked per wave by returning LDS adds, staged through LDS in sorted order
@@ -58,7 +59,8 @@ __device__ __forceinline__ uint32_t block_excl_scan4(uint32_t v, uint32_t* lds, 
 // that way). Eight searches side by side.
 static_assert(CM4_BINS == 2048 && CM4_MAX_BUCKETS == 8192, "eleven to thirteen levels");
 // (nodes numbered from 1, heap fashion: children of node b are 2b and 2b + 1, so a step is b = 2b + (tree[b] <= key) — one
-// add-with-carry behind the compare; word 0 of the tree is unused. After LEVELS steps b - 2^LEVELS is the bucket.)
+// add-with-carry behind the compare; word 0 of the tree is unused. After LEVELS steps b - 2^LEVELS is the bucket. The search
+// keeps the node as its BYTE offset, a = 4b: a = 2a + (tree[a / 4] <= key ? 4 : 0) — the LDS address needs no shift per step.)
 // LEVELS = 11: up to 2048 buckets. 12, 13: up to 8192 buckets for frames of up to 15 M records — 2 or 4 neighbouring buckets
 // then share one of the pass's 2048 bins (cm_device.h cm_quant_sub_shift): the pass scatters by bucket >> shift and leaves
 // the low bits as a byte beside every record; the finish workgroup of a bucket picks its records out of its bin by them.
@@ -75,14 +77,15 @@ __device__ __forceinline__ void load_splitter_tree(uint32_t* __restrict__ tree, 
 template <int LEVELS, int N>
 __device__ __forceinline__ void buckets_of(const uint32_t* __restrict__ tree, const uint32_t (&key)[N], uint32_t (&bk)[N]) {
 #pragma unroll
-    for (int r = 0; r < N; ++r) bk[r] = 1;
+    for (int r = 0; r < N; ++r) bk[r] = 4;
+    const unsigned char* tb = reinterpret_cast<const unsigned char*>(tree);
 #pragma unroll
     for (int l = 0; l < LEVELS; ++l) {
 #pragma unroll
-        for (int r = 0; r < N; ++r) bk[r] = bk[r] + bk[r] + ((tree[bk[r]] <= key[r]) ? 1u : 0u);
+        for (int r = 0; r < N; ++r) bk[r] = (bk[r] << 1) + ((*reinterpret_cast<const uint32_t*>(tb + bk[r]) <= key[r]) ? 4u : 0u);
     }
 #pragma unroll
-    for (int r = 0; r < N; ++r) bk[r] -= 1u << LEVELS;
+    for (int r = 0; r < N; ++r) bk[r] = (bk[r] >> 2) - (1u << LEVELS);
 }
 
 // Where counter word `word` (two 16-bit bucket counters) of tile `tile` lives: column blocks of eight words, the tiles of a
@@ -135,44 +138,72 @@ __device__ __forceinline__ void fold_bounds4(float* s_f, CmFrameState* __restric
     }
 }
 
+// Phase timing of k4_hist (scripts/phase_times4.py; build with CM_PHASE_TIMING=1): thread 0 of every workgroup adds up the
+// 100 MHz ticks it spends in each phase over its tiles (word 15: its tiles). The timed build waits for the loads where the
+// product lets them fly. Compiled out of the product build.
+#ifdef CM_PHASE_TIMING
+__device__ unsigned long long g_phase4[4096 * 16];
+#define PH4_START() long long t0_ = wall_clock64()
+#define PH4(k) do { if (threadIdx.x == 0) { const long long t1_ = wall_clock64(); g_phase4[(blockIdx.x & 4095) * 16 + (k)] += (unsigned long long)(t1_ - t0_); t0_ = t1_; } } while (0)
+#define PH4_LOADS_BACK() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#else
+#define PH4_START() do {} while (0)
+#define PH4(k) do {} while (0)
+#define PH4_LOADS_BACK() do {} while (0)
+#endif
+
 // ------------------------------------------------------------------------------------------------
 // k4_hist: what k2_hist0 does for the fixed-grid passes (frame set-up, clears, box check, min/max records), with the
 // counts taken per quantile bucket: row `tile` of cnt = CM4_BINS 16-bit counters (a tile holds 4096 points: no overflow).
+//
+// Grid-stride: the launch holds what is resident at once (cmk4_hist), a workgroup takes tiles blockIdx.x, blockIdx.x +
+// gridDim.x, ... — the splitter tree, the frame set-up and the box constants are paid once per workgroup, and no workgroup
+// waits for another one. A tile goes through in two halves of four points per thread: once a half's coordinates have become
+// keys, masks and min/max they are dead, and the loads of the next half (of this tile or of the workgroup's next one) go
+// out into the same twelve registers BEFORE the half is searched and counted — the search's dependent LDS reads run under
+// the memory latency instead of behind it.
 // ------------------------------------------------------------------------------------------------
 template <int LEVELS>
-__global__ __launch_bounds__(CM2_BLOCK) void k4_hist(const CmFrameDev fv, CmFrameDev* __restrict__ fd_dst,
+__global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmFrameDev* __restrict__ fd_dst,
                                                      CmTileDev* __restrict__ tiles_dst, int do_setup,
                                                      CmFrameState* __restrict__ st, const uint32_t* __restrict__ spl_g,
                                                      uint32_t* __restrict__ cnt, uint16_t* __restrict__ bid,
                                                      unsigned long long* __restrict__ tile_state, uint32_t n_tile_state,
                                                      float* __restrict__ records, int grid_mode, int check_box,
-                                                     uint32_t* __restrict__ big_list, uint32_t bin_shift) {
+                                                     uint32_t* __restrict__ big_list, uint32_t bin_shift, uint32_t n_tiles) {
+    constexpr int H = CM2_ITEMS / 2;                      // points of a thread per half-tile
     __shared__ uint32_t spl[1 << LEVELS];
     __shared__ uint32_t lh[CM4_BINS / 2];
     __shared__ float s_mm[CM2_WAVES][6];
     __shared__ uint32_t s_cnt[CM2_WAVES];
     __shared__ uint32_t s_out;
-    const uint32_t tile = blockIdx.x;
+    PH4_START();
     const CmFrameDev* __restrict__ fd = &fv;
-    CmTileDev te;                                         // where this tile's points lie (k_setup's arithmetic)
-    {
-        const uint32_t first = tile * CM_TILE;
+    auto entry = [&](uint32_t t, CmTileDev& e) {          // where tile t's points lie (k_setup's arithmetic)
+        const uint32_t first = t * CM_TILE;
         uint32_t k = 0;
         for (uint32_t q = 1; q < fv.n_sensors; ++q) k += (first >= fv.s[q].base) ? 1u : 0u;
         const CmSensorDev& sd0 = fv.s[k];
         const uint32_t off = first - sd0.base;
-        te.data = sd0.data + static_cast<size_t>(off) * sd0.point_step;
-        te.n_left = sd0.n > off ? sd0.n - off : 0u;
-        te.info = k | (sd0.layout << 8);
-    }
+        e.data = sd0.data + static_cast<size_t>(off) * sd0.point_step;
+        e.n_left = sd0.n > off ? sd0.n - off : 0u;
+        e.info = k | (sd0.layout << 8);
+    };
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t first = w * (64 * CM2_ITEMS) + lane;   // the thread's first slot in a tile
+    uint32_t tile = blockIdx.x;
+    CmTileDev te;
+    entry(tile, te);
+    Pt3 p[H] = {};                                        // the half-tile in flight
+    load_tile_xyz_aligned<H>(te, first, p);
+    load_splitter_tree<LEVELS>(spl, spl_g);
     if (do_setup) {
         static_assert(sizeof(CmFrameDev) % 4 == 0 && sizeof(CmFrameDev) / 4 <= CM2_BLOCK, "one word of the descriptor per thread");
-        if (threadIdx.x == 0) tiles_dst[tile] = te;
-        if (tile == 0 && threadIdx.x < sizeof(CmFrameDev) / 4)
+        if (blockIdx.x == 0 && threadIdx.x < sizeof(CmFrameDev) / 4)
             reinterpret_cast<uint32_t*>(fd_dst)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&fv)[threadIdx.x];
     }
-    for (uint32_t k = tile * CM2_BLOCK + threadIdx.x; k < n_tile_state; k += gridDim.x * CM2_BLOCK) tile_state[k] = 0ull;
-    if (tile == 0 && threadIdx.x == 0) {                 // the box and its grid, as the host set them up
+    for (uint32_t k = blockIdx.x * CM2_BLOCK + threadIdx.x; k < n_tile_state; k += gridDim.x * CM2_BLOCK) tile_state[k] = 0ull;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {           // the box and its grid, as the host set them up
         st->status = CM_DEV_OK;
         for (int a = 0; a < 3; ++a) {
             st->min_p[a] = grid_mode == 2 ? fd->ext_min[a] : fd->crop_min[a];
@@ -187,15 +218,6 @@ __global__ __launch_bounds__(CM2_BLOCK) void k4_hist(const CmFrameDev fv, CmFram
     }
     const BoxGrid b = box_grid_of(fd);
     const bool predicted = check_box != 0;
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const CmSensorDev& sd = fd->s[te.info & 0xFFu];
-    Pt p[CM2_ITEMS];
-    load_tile_te<CM2_ITEMS>(te, sd, w * (64 * CM2_ITEMS) + lane, p);
-    load_splitter_tree<LEVELS>(spl, spl_g);
-    float m[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
     const uint32_t crop = fd->crop_enable;
     float cmn0 = 0.f, cmn1 = 0.f, cmn2 = 0.f, cmx0 = 0.f, cmx1 = 0.f, cmx2 = 0.f;
     if (crop) {
@@ -206,86 +228,133 @@ __global__ __launch_bounds__(CM2_BLOCK) void k4_hist(const CmFrameDev fv, CmFram
     for (int q = 0; q < CM4_BINS / 2 / CM2_BLOCK; ++q) lh[q * CM2_BLOCK + threadIdx.x] = 0;
     if (threadIdx.x == 0) s_out = 0;
     __syncthreads();
+    PH4(0);
     const float inf = __uint_as_float(0x7F800000u);
-    float mn0 = inf, mn1 = inf, mn2 = inf, mx0 = -inf, mx1 = -inf, mx2 = -inf;
-    uint32_t cnt_ok = 0;
-    bool any_out = false;
-    float tx[CM2_ITEMS], ty[CM2_ITEMS], tz[CM2_ITEMS];
-    uint32_t key[CM2_ITEMS], bk[CM2_ITEMS];
-    uint32_t okm = 0, keepm = 0;
+    for (;;) {
+        const uint32_t tile_n = tile + gridDim.x;
+        const bool more = tile_n < n_tiles;
+        CmTileDev ten = te;
+        float m[12];
+        {
+            const CmSensorDev& sd = fd->s[te.info & 0xFFu];
 #pragma unroll
-    for (int r = 0; r < CM2_ITEMS; ++r) {
-        const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-        const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-        const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
-        tx[r] = x; ty[r] = y; tz[r] = z;
-        bool ok = finite_f32(x) & finite_f32(y) & finite_f32(z);
-        if (crop) ok = ok & !((x < cmn0) | (x > cmx0) | (y < cmn1) | (y > cmx1) | (z < cmn2) | (z > cmx2));
-        bool in;
-        key[r] = key_of(b, x, y, z, &in);
-        if (predicted) any_out = any_out | (ok & !in);     // a crop box holds every valid point by construction
-        else in = true;
-        okm |= ok ? (1u << r) : 0u;
-        keepm |= (ok & in) ? (1u << r) : 0u;
-    }
-    buckets_of<LEVELS, CM2_ITEMS>(spl, key, bk);
-    const uint32_t slot0 = tile * CM_TILE + w * (64 * CM2_ITEMS) + lane;
+            for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+        }
+        if (do_setup && threadIdx.x == 0) tiles_dst[tile] = te;
+        float mn0 = inf, mn1 = inf, mn2 = inf, mx0 = -inf, mx1 = -inf, mx2 = -inf;
+        uint32_t cnt_ok = 0;
+        bool any_out = false;
+        const uint32_t slot0 = tile * CM_TILE + first;
 #pragma unroll
-    for (int r = 0; r < CM2_ITEMS; ++r) {
-        // (a slot without a record adds nothing, to a word of its own: same-address LDS adds of a wave serialise;
-        // the counters are per bin — what this pass scatters by: the bucket number without its low bin_shift bits
-        // (shared bins above CM4_BINS buckets, cm_device.h; bin_shift == 0: a bin is a bucket))
-        const bool keep = (keepm >> r) & 1u;
-        const uint32_t lo = bk[r] >> bin_shift;
-        atomicAdd(&lh[keep ? lo >> 1 : static_cast<uint32_t>(lane)], (keep ? 1u : 0u) << ((lo & 1u) * 16u));
-        // the bucket of every slot (0xFFFF: no record), so that k4_scatter neither tests nor searches a second time
-        bid[slot0 + r * 64] = static_cast<uint16_t>(keep ? bk[r] : 0xFFFFu);
-    }
-    if (predicted) {
-        cnt_ok = static_cast<uint32_t>(__builtin_popcount(okm));
-        if (__ballot(okm != (1u << CM2_ITEMS) - 1u) == 0ull) {
+        for (int h = 0; h < 2; ++h) {
+            uint32_t key[H], bk[H];
+            uint32_t okm = 0, keepm = 0;
+            uint32_t fs = first;                                   // (opaque: the loads' offsets are formed where they are used —
+            asm volatile("" : "+v"(fs));                           //  hoisted out of the tile loop they stay live across it and spill)
+            load_tile_xyz_generic<H>(te, fd->s[te.info & 0xFFu], fs + h * (H * 64), p);   // (a generic layout: fetched here)
+            PH4_LOADS_BACK();
+            PH4(1);
+            {
+                float tx[H], ty[H], tz[H];
 #pragma unroll
-            for (int r = 0; r < CM2_ITEMS; r += 2) {
-                mn0 = fminf(fminf(mn0, tx[r]), tx[r + 1]); mx0 = fmaxf(fmaxf(mx0, tx[r]), tx[r + 1]);
-                mn1 = fminf(fminf(mn1, ty[r]), ty[r + 1]); mx1 = fmaxf(fmaxf(mx1, ty[r]), ty[r + 1]);
-                mn2 = fminf(fminf(mn2, tz[r]), tz[r + 1]); mx2 = fmaxf(fmaxf(mx2, tz[r]), tz[r + 1]);
+                for (int r = 0; r < H; ++r) {
+                    const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
+                    const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
+                    const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+                    tx[r] = x; ty[r] = y; tz[r] = z;
+                    bool ok = finite_f32(x) & finite_f32(y) & finite_f32(z);
+                    if (crop) ok = ok & !((x < cmn0) | (x > cmx0) | (y < cmn1) | (y > cmx1) | (z < cmn2) | (z > cmx2));
+                    bool in;
+                    key[r] = key_of(b, x, y, z, &in);
+                    if (predicted) any_out = any_out | (ok & !in);     // a crop box holds every valid point by construction
+                    else in = true;
+                    okm |= ok ? (1u << r) : 0u;
+                    keepm |= (ok & in) ? (1u << r) : 0u;
+                }
+                if (predicted) {                                   // (here, so that the coordinates are dead before the next loads go out)
+                    cnt_ok += static_cast<uint32_t>(__builtin_popcount(okm));
+                    if (__ballot(okm != (1u << H) - 1u) == 0ull) {
+#pragma unroll
+                        for (int r = 0; r < H; r += 2) {
+                            mn0 = fminf(fminf(mn0, tx[r]), tx[r + 1]); mx0 = fmaxf(fmaxf(mx0, tx[r]), tx[r + 1]);
+                            mn1 = fminf(fminf(mn1, ty[r]), ty[r + 1]); mx1 = fmaxf(fmaxf(mx1, ty[r]), ty[r + 1]);
+                            mn2 = fminf(fminf(mn2, tz[r]), tz[r + 1]); mx2 = fmaxf(fmaxf(mx2, tz[r]), tz[r + 1]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < H; ++r) {
+                            const bool ok = (okm >> r) & 1u;
+                            mn0 = fminf(mn0, ok ? tx[r] : inf); mx0 = fmaxf(mx0, ok ? tx[r] : -inf);
+                            mn1 = fminf(mn1, ok ? ty[r] : inf); mx1 = fmaxf(mx1, ok ? ty[r] : -inf);
+                            mn2 = fminf(mn2, ok ? tz[r] : inf); mx2 = fmaxf(mx2, ok ? tz[r] : -inf);
+                        }
+                    }
+                }
             }
-        } else {
+            // the next half-tile's loads: the second half of this tile, or the first of the workgroup's next one
+            if (h == 0) {
+                load_tile_xyz_aligned<H>(te, fs + H * 64, p);
+            } else if (more) {
+                entry(tile_n, ten);
+                load_tile_xyz_aligned<H>(ten, fs, p);
+            }
+            PH4(2);
+            buckets_of<LEVELS, H>(spl, key, bk);
 #pragma unroll
-            for (int r = 0; r < CM2_ITEMS; ++r) {
-                const bool ok = (okm >> r) & 1u;
-                mn0 = fminf(mn0, ok ? tx[r] : inf); mx0 = fmaxf(mx0, ok ? tx[r] : -inf);
-                mn1 = fminf(mn1, ok ? ty[r] : inf); mx1 = fmaxf(mx1, ok ? ty[r] : -inf);
-                mn2 = fminf(mn2, ok ? tz[r] : inf); mx2 = fmaxf(mx2, ok ? tz[r] : -inf);
+            for (int r = 0; r < H; ++r) {
+                // (a slot without a record adds nothing, to a word of its own: same-address LDS adds of a wave serialise;
+                // the counters are per bin — what this pass scatters by: the bucket number without its low bin_shift bits
+                // (shared bins above CM4_BINS buckets, cm_device.h; bin_shift == 0: a bin is a bucket))
+                const bool keep = (keepm >> r) & 1u;
+                const uint32_t lo = bk[r] >> bin_shift;
+                atomicAdd(&lh[keep ? lo >> 1 : static_cast<uint32_t>(lane)], (keep ? 1u : 0u) << ((lo & 1u) * 16u));
+                // the bucket of every slot (0xFFFF: no record), so that k4_scatter neither tests nor searches a second time
+                bid[slot0 + (h * H + r) * 64] = static_cast<uint16_t>(keep ? bk[r] : 0xFFFFu);
+            }
+            PH4(3);
+        }
+        if (predicted) {
+            if (any_out) s_out = 1u;
+            mn0 = wave_min_f32_l63(mn0); mn1 = wave_min_f32_l63(mn1); mn2 = wave_min_f32_l63(mn2);
+            mx0 = wave_max_f32_l63(mx0); mx1 = wave_max_f32_l63(mx1); mx2 = wave_max_f32_l63(mx2);
+            cnt_ok = wave_sum_u32(cnt_ok);
+            if (lane == 63) {
+                s_mm[w][0] = mn0; s_mm[w][1] = mn1; s_mm[w][2] = mn2;
+                s_mm[w][3] = mx0; s_mm[w][4] = mx1; s_mm[w][5] = mx2;
+                s_cnt[w] = cnt_ok;
             }
         }
-        if (any_out) s_out = 1u;
-        mn0 = wave_min_f32_l63(mn0); mn1 = wave_min_f32_l63(mn1); mn2 = wave_min_f32_l63(mn2);
-        mx0 = wave_max_f32_l63(mx0); mx1 = wave_max_f32_l63(mx1); mx2 = wave_max_f32_l63(mx2);
-        cnt_ok = wave_sum_u32(cnt_ok);
-        if (lane == 63) {
-            s_mm[w][0] = mn0; s_mm[w][1] = mn1; s_mm[w][2] = mn2;
-            s_mm[w][3] = mx0; s_mm[w][4] = mx1; s_mm[w][5] = mx2;
-            s_cnt[w] = cnt_ok;
-        }
-    }
-    __syncthreads();
-    // The counts go out in column blocks of eight words (cnt_at): k4_colscan then streams one contiguous block per workgroup.
+        __syncthreads();
+        PH4(4);
+        uint32_t tx_ = threadIdx.x;                            // (opaque, as the loads' offsets: the addresses below are per-tile work)
+        asm volatile("" : "+v"(tx_));
+        // The counts go out in column blocks of eight words (cnt_at): k4_colscan then streams one contiguous block per
+        // workgroup. A thread clears the words it has just read for the workgroup's next tile.
 #pragma unroll
-    for (int q = 0; q < CM4_BINS / 2 / CM2_BLOCK; ++q)
-        cnt[cnt_at(tile, q * CM2_BLOCK + threadIdx.x, gridDim.x)] = lh[q * CM2_BLOCK + threadIdx.x];
-    if (predicted && threadIdx.x < 8) {                    // record: min xyz, max xyz, count, pad
-        const int k = threadIdx.x;
-        float v = 0.f;
-        if (k < 6) {
-            v = s_mm[0][k];
-            for (int q = 1; q < CM2_WAVES; ++q) v = (k < 3) ? fminf(v, s_mm[q][k]) : fmaxf(v, s_mm[q][k]);
-        } else if (k == 6) {
-            uint32_t c = 0;
-            for (int q = 0; q < CM2_WAVES; ++q) c += s_cnt[q];
-            v = __uint_as_float(c);
+        for (int q = 0; q < CM4_BINS / 2 / CM2_BLOCK; ++q) {
+            cnt[cnt_at(tile, q * CM2_BLOCK + tx_, n_tiles)] = lh[q * CM2_BLOCK + tx_];
+            lh[q * CM2_BLOCK + tx_] = 0;
         }
-        records[static_cast<size_t>(tile) * 8 + k] = v;
+        if (predicted && tx_ < 8) {                    // record: min xyz, max xyz, count, pad
+            const int k = tx_;
+            float v = 0.f;
+            if (k < 6) {
+                v = s_mm[0][k];
+                for (int q = 1; q < CM2_WAVES; ++q) v = (k < 3) ? fminf(v, s_mm[q][k]) : fmaxf(v, s_mm[q][k]);
+            } else if (k == 6) {
+                uint32_t c = 0;
+                for (int q = 0; q < CM2_WAVES; ++q) c += s_cnt[q];
+                v = __uint_as_float(c);
+            }
+            records[static_cast<size_t>(tile) * 8 + k] = v;
+        }
+        PH4(5);
+#ifdef CM_PHASE_TIMING
+        if (threadIdx.x == 0) g_phase4[(blockIdx.x & 4095) * 16 + 15] += 1ull;
+#endif
+        if (!more) break;
+        __syncthreads();                                       // (the cleared counters, the read records: before the next tile's)
+        te = ten; tile = tile_n;
     }
     if (threadIdx.x == 0 && s_out) st->outside = 1u;
 }
@@ -538,12 +607,37 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
 
 }  // namespace
 
+#ifdef CM_PHASE_TIMING
+extern "C" __attribute__((visibility("default"))) void cm_debug_phases4(unsigned long long* out, int reset) {
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase4), sizeof(unsigned long long) * 16 * 4096);
+    if (reset) { void* p_; (void)hipGetSymbolAddress(&p_, HIP_SYMBOL(g_phase4)); (void)hipMemset(p_, 0, sizeof(unsigned long long) * 16 * 4096); }
+}
+#endif
+
+
+
+// What of k4_hist<L> is resident at once on the current device: workgroups per CU (asked of the runtime) times its CUs.
+template <int L>
+static uint32_t k4_hist_resident() {
+    int dev = 0, per_cu = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k4_hist<L>, CM2_BLOCK, 0) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return per_cu > 0 && cus > 0 ? static_cast<uint32_t>(per_cu) * static_cast<uint32_t>(cus) : 0u;
+}
 void cmk4_hist(hipStream_t s, const CmFrameDev& f, CmFrameDev* fd, CmTileDev* tiles, bool do_setup, CmFrameState* st,
                const uint32_t* spl, uint32_t* cnt, uint16_t* bid, unsigned long long* tile_state, uint32_t n_tile_state, float* records,
-               int grid_mode, int check_box, uint32_t n_tiles, uint32_t n_buckets, uint32_t* big_list, uint32_t sub_shift) {
+               int grid_mode, int check_box, uint32_t n_tiles, uint32_t n_buckets, uint32_t* big_list, uint32_t sub_shift,
+               uint32_t* resident) {
     // sub_shift (cm_quant_sub_shift(n_buckets)) != 0: shared bins — counted per bucket >> sub_shift (<= CM4_BINS bins)
-#define CM4_HIST(L) hipLaunchKernelGGL(k4_hist<L>, dim3(n_tiles), dim3(CM2_BLOCK), 0, s, f, fd, tiles, do_setup ? 1 : 0, st, spl, cnt, bid, \
-                                       tile_state, n_tile_state, records, grid_mode, check_box, big_list, sub_shift)
+    // resident[LEVELS - 11]: the grid-stride launch's size, asked once per context (0: not yet; the answer only sizes the
+    // launch — a workgroup never waits for another one, so a wrong one costs time, not the result)
+#define CM4_HIST(L) do { \
+        uint32_t& g = resident[L - 11]; \
+        if (!g) { g = k4_hist_resident<L>(); if (!g) g = n_tiles; } \
+        hipLaunchKernelGGL(k4_hist<L>, dim3(n_tiles < g ? n_tiles : g), dim3(CM2_BLOCK), 0, s, f, fd, tiles, do_setup ? 1 : 0, st, spl, cnt, bid, \
+                           tile_state, n_tile_state, records, grid_mode, check_box, big_list, sub_shift, n_tiles); \
+    } while (0)
     if (n_buckets <= 2048) CM4_HIST(11);
     else if (n_buckets <= 4096) CM4_HIST(12);
     else CM4_HIST(13);

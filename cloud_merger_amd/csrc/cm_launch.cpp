@@ -167,7 +167,7 @@ int launch_bucket(cm_ctx* c, const unsigned char* mask, const CmFrameState* st_o
         uint32_t* spl_next = c->spl[c->route.spl_cur ^ 1];
         prof_mark(c, "k4_hist");
         cmk4_hist(st, f, c->d_frame, c->d_tiles, do_setup, state, spl, c->qcnt, c->qbid, c->tile_state, pl.n_tile_state, c->records,
-                  pl.b_grid_mode, pl.predicted ? 1 : 0, nt, nb, sub ? nullptr : c->qbig, sub);
+                  pl.b_grid_mode, pl.predicted ? 1 : 0, nt, nb, sub ? nullptr : c->qbig, sub, c->hist_resident);
         prof_mark(c, "k4_colscan");
         // (shared bins: a bin beyond 2^sub finish capacities holds a bucket beyond one; the finish itself checks the buckets)
         if (sub) cmk4_colscan(st, state, c->h_state_dev, c->qcnt, c->qtot, nt, CM4_CAP << sub, CM4_CAP << sub, nullptr);
