@@ -1,6 +1,6 @@
-// cm_common.hpp — device helpers shared by the kernel files (cm_kernels.hip, cm_kernels_v2.hip):
-// point loaders, the reference's fp32 transform / crop arithmetic, PCL's grid set-up, workgroup scans,
-// the centroid accumulator and the frame-state report. Semantics in SURVEY.md Appendix A.
+// cm_common.hpp — device helpers shared by the kernel files: point loaders, the reference's fp32 transform / crop
+// arithmetic, PCL's grid set-up, workgroup scans, the raw-point front end of the bucket path (matrix, crop box, validity,
+// frame set-up, min/max records), the centroid accumulator, the frame-state report and the phase stamps. Semantics in SURVEY.md Appendix A.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -90,7 +90,10 @@ __device__ __forceinline__ float centroid_div_rc(float s, float c, float rc) {
     return q2;
 }
 
-// PassThrough x3 (closed box) + "non-finite points vanish" (A.2, A.3).
+// PassThrough x3 (closed box) + "non-finite points vanish" (A.2, A.3). The general path's form (k_minmax, k_keys, the
+// compaction kernels of cm_kernels.hip, kg_classify): same predicate as valid_point below, but short-circuit and with the
+// box read through the descriptor where it is tested — those kernels test under a branch anyway and keep no box in
+// registers. The bucket path's per-point straight-line code uses valid_point.
 __device__ __forceinline__ bool point_valid(float x, float y, float z, uint32_t crop,
                                             const float* __restrict__ cmin, const float* __restrict__ cmax) {
     bool ok = finite_f32(x) && finite_f32(y) && finite_f32(z);
@@ -152,15 +155,16 @@ __device__ __forceinline__ uint32_t wave_rank_ballot(uint32_t* __restrict__ row,
     return old + static_cast<uint32_t>(__popcll(m & ((1ull << lane) - 1ull)));
 }
 
-// Exclusive scan over the 256 threads of a workgroup. lds: CM_WAVES words. Ends with a barrier.
-__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* lds, uint32_t* total) {
+// Exclusive scan over the WAVES * 64 threads of a workgroup. lds: WAVES words. Ends with a barrier.
+template <int WAVES>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* lds, uint32_t* total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t incl = wave_incl_scan_u32(v, lane);
     if (lane == 63) lds[w] = incl;
     __syncthreads();
     uint32_t woff = 0, tot = 0;
 #pragma unroll
-    for (int k = 0; k < CM_WAVES; ++k) {
+    for (int k = 0; k < WAVES; ++k) {
         const uint32_t c = lds[k];
         if (k < w) woff += c;
         tot += c;
@@ -170,23 +174,47 @@ __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t v, uint32_t* ld
     return woff + incl - v;
 }
 
-__device__ __forceinline__ uint32_t block_sum_u32(uint32_t v, uint32_t* lds) {
+template <int WAVES>
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t* lds) {
     v = wave_sum_u32(v);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
     __syncthreads();
     uint32_t tot = 0;
 #pragma unroll
-    for (int k = 0; k < CM_WAVES; ++k) tot += lds[k];
+    for (int k = 0; k < WAVES; ++k) tot += lds[k];
     __syncthreads();
     return tot;
 }
 
-// Which sensor owns padded tile `tile` (wave-uniform).
-__device__ __forceinline__ uint32_t sensor_of_tile(const CmFrameDev* __restrict__ fd, uint32_t tile) {
-    const uint32_t first = tile * CM_TILE;
+// Which sensor owns padded slot `first_slot` / padded tile `tile` (wave-uniform).
+__device__ __forceinline__ uint32_t sensor_of_slot(const CmFrameDev* __restrict__ fd, uint32_t first_slot) {
     uint32_t s = 0;
-    for (uint32_t q = 1; q < fd->n_sensors; ++q) s += (first >= fd->s[q].base) ? 1u : 0u;
+    for (uint32_t q = 1; q < fd->n_sensors; ++q) s += (first_slot >= fd->s[q].base) ? 1u : 0u;
     return s;
+}
+__device__ __forceinline__ uint32_t sensor_of_tile(const CmFrameDev* __restrict__ fd, uint32_t tile) {
+    return sensor_of_slot(fd, tile * CM_TILE);
+}
+
+// Where padded tile `tile`'s points lie: the table k_setup writes, and what k2_hist0 / k4_hist form for themselves from
+// the descriptor in their kernel arguments.
+__device__ __forceinline__ CmTileDev tile_entry(const CmFrameDev& f, uint32_t tile) {
+    const uint32_t first = tile * CM_TILE;
+    const uint32_t k = sensor_of_slot(&f, first);
+    const CmSensorDev& sd = f.s[k];
+    const uint32_t off = first - sd.base;
+    CmTileDev te;
+    te.data = sd.data + static_cast<size_t>(off) * sd.point_step;
+    te.n_left = sd.n > off ? sd.n - off : 0u;
+    te.info = k | (sd.layout << 8);
+    return te;
+}
+
+// The tile a scatter workgroup takes: every XCD (workgroups are dealt to the eight round-robin) gets a contiguous range
+// of tiles, so that neighbouring tiles' short runs meet in one L2; the remainder of the grid keeps its own number.
+__device__ __forceinline__ uint32_t xcd_tile(uint32_t block, uint32_t n_blocks) {
+    const uint32_t per = n_blocks / 8;
+    return block < per * 8 ? (block & 7u) * per + (block >> 3) : block;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -419,7 +447,7 @@ __device__ __forceinline__ void compute_grid(const CmFrameDev* __restrict__ fd,
 }
 
 // ------------------------------------------------------------------------------------------------
-// The box grid of the bucket path (crop box / predicted box; cm_api.cpp box_grid) and the cell of a point in it.
+// The box grid of the bucket path (crop box / predicted box; cm_route.cpp box_grid) and the cell of a point in it.
 // ------------------------------------------------------------------------------------------------
 struct BoxGrid {
     float inv0, inv1, inv2, fb0, fb1, fb2;
@@ -443,7 +471,7 @@ __device__ __forceinline__ BoxGrid box_grid_of(const CmFrameDev* __restrict__ fd
 }
 
 // Linear index c0 + c1 * d0 + c2 * d0 * d1 (mod 2^32; exact for a cell of the box: the host only takes the bucket
-// path when the box has fewer than 2^32 cells and fewer than 2^24 per axis — cm_api.cpp) on the full-rate 24-bit
+// path when the box has fewer than 2^32 cells and fewer than 2^24 per axis — cm_route.cpp) on the full-rate 24-bit
 // multiplier: v_mul_lo_u32 / v_mad_u64_u32 run at a quarter of the rate, and the index is formed several times per point.
 __device__ __forceinline__ uint32_t box_index(const BoxGrid& b, uint32_t c0, uint32_t c1, uint32_t c2) {
     uint32_t hi = __umul24(c2, b.mul2h);
@@ -466,6 +494,173 @@ __device__ __forceinline__ uint32_t key_of(const BoxGrid& b, const float4& r) {
     const uint32_t c1 = static_cast<uint32_t>(static_cast<int>(__fsub_rn(floorf(__fmul_rn(r.y, b.inv1)), b.fb1)));
     const uint32_t c2 = static_cast<uint32_t>(static_cast<int>(__fsub_rn(floorf(__fmul_rn(r.z, b.inv2)), b.fb2)));
     return box_index(b, c0, c1, c2);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The raw-point front end of the bucket path (k2_hist0, k4_hist, the first scatters; the transform also in the general
+// path, the ground and the motion kernels): sensor matrix and crop box in registers, transform, validity, frame set-up,
+// and the min/max records of a predicted box.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void load_matrix(const CmSensorDev& sd, float (&m)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+}
+// (m: the twelve words in registers, or the descriptor's own array)
+template <class M, class P>
+__device__ __forceinline__ void xf_point(const M& m, const P& p, float& x, float& y, float& z) {
+    x = xf_row(m[0], m[1], m[2], m[3], p.x, p.y, p.z);
+    y = xf_row(m[4], m[5], m[6], m[7], p.x, p.y, p.z);
+    z = xf_row(m[8], m[9], m[10], m[11], p.x, p.y, p.z);
+}
+
+struct CropBox { uint32_t on; float mn0, mn1, mn2, mx0, mx1, mx2; };
+__device__ __forceinline__ CropBox load_crop(const CmFrameDev* __restrict__ fd) {
+    CropBox c = {fd->crop_enable, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (c.on) {
+        c.mn0 = fd->crop_min[0]; c.mn1 = fd->crop_min[1]; c.mn2 = fd->crop_min[2];
+        c.mx0 = fd->crop_max[0]; c.mx1 = fd->crop_max[1]; c.mx2 = fd->crop_max[2];
+    }
+    return c;
+}
+// Finite and inside the closed crop box (A.2, A.3). Straight-line code per point: every test is formed as a flag (no
+// short-circuit evaluation — the compiler turns that into a chain of exec-mask branches with the callers' running
+// min/max re-materialised at every join); callers combine the result with `&` for the same reason.
+__device__ __forceinline__ bool valid_point(float x, float y, float z, const CropBox& c) {
+    bool ok = finite_f32(x) & finite_f32(y) & finite_f32(z);
+    if (c.on) ok = ok & !((x < c.mn0) | (x > c.mx0) | (y < c.mn1) | (y > c.mx1) | (z < c.mn2) | (z > c.mx2));
+    return ok;
+}
+
+// The frame descriptor that arrived as a kernel argument, left in HBM for the kernels behind (one workgroup calls this).
+__device__ __forceinline__ void store_frame_desc(const CmFrameDev& fv, CmFrameDev* dst) {
+    static_assert(sizeof(CmFrameDev) % 4 == 0 && sizeof(CmFrameDev) / 4 <= CM2_BLOCK, "one word of the descriptor per thread");
+    if (threadIdx.x < sizeof(CmFrameDev) / 4)
+        reinterpret_cast<uint32_t*>(dst)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&fv)[threadIdx.x];
+}
+
+// The box and its grid, as the host set them up, into the frame state (one thread calls this). grid_mode 2: the box is
+// the host's bounds of the whole cloud, otherwise the crop box; use_cell: the outlier stage's radius grid.
+__device__ __forceinline__ void init_box_state(CmFrameState* __restrict__ st, const CmFrameDev* __restrict__ fd, int grid_mode,
+                                               int use_cell, uint32_t n_passes, int32_t status) {
+    st->status = status;
+    for (int a = 0; a < 3; ++a) {
+        st->min_p[a] = grid_mode == 2 ? fd->ext_min[a] : fd->crop_min[a];
+        st->max_p[a] = grid_mode == 2 ? fd->ext_max[a] : fd->crop_max[a];
+        const int32_t mb = use_cell ? fd->cell_min_b[a] : fd->box_min_b[a], db = use_cell ? fd->cell_div_b[a] : fd->box_div_b[a];
+        st->min_b[a] = mb; st->max_b[a] = mb + db - 1;
+        st->div_b[a] = db;
+    }
+    st->key_bits = use_cell ? fd->cell_key_bits : fd->box_key_bits;
+    st->n_passes = n_passes;
+}
+
+// The exact bounds and the number of a tile's valid points (pcl::getMinMax3D), for the per-tile records a predicted box
+// is checked and the next one predicted with: a thread adds its points, the waves meet in LDS (WAVES rows of six floats
+// and a count), eight threads write the record — min xyz, max xyz, count, pad. (k_minmax of the general path shares only
+// the record's layout, record_word: it folds its waves with its own shuffles into rows of its own.)
+struct MinMax3 {
+    float mn0, mn1, mn2, mx0, mx1, mx2;
+    uint32_t cnt;
+    __device__ __forceinline__ MinMax3() {
+        const float inf = __uint_as_float(0x7F800000u);
+        mn0 = mn1 = mn2 = inf; mx0 = mx1 = mx2 = -inf; cnt = 0;
+    }
+    // N points (N even), bit r of okm: point r is valid. Nearly every wave holds valid points only: then the values of
+    // a lane fold with three-operand min / max, no masking.
+    template <int N>
+    __device__ __forceinline__ void add(const float (&tx)[N], const float (&ty)[N], const float (&tz)[N], uint32_t okm) {
+        const float inf = __uint_as_float(0x7F800000u);
+        cnt += static_cast<uint32_t>(__builtin_popcount(okm));
+        if (__ballot(okm != (1u << N) - 1u) == 0ull) {
+#pragma unroll
+            for (int r = 0; r < N; r += 2) {
+                mn0 = fminf(fminf(mn0, tx[r]), tx[r + 1]); mx0 = fmaxf(fmaxf(mx0, tx[r]), tx[r + 1]);
+                mn1 = fminf(fminf(mn1, ty[r]), ty[r + 1]); mx1 = fmaxf(fmaxf(mx1, ty[r]), ty[r + 1]);
+                mn2 = fminf(fminf(mn2, tz[r]), tz[r + 1]); mx2 = fmaxf(fmaxf(mx2, tz[r]), tz[r + 1]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < N; ++r) {
+                const bool ok = (okm >> r) & 1u;
+                mn0 = fminf(mn0, ok ? tx[r] : inf); mx0 = fmaxf(mx0, ok ? tx[r] : -inf);
+                mn1 = fminf(mn1, ok ? ty[r] : inf); mx1 = fmaxf(mx1, ok ? ty[r] : -inf);
+                mn2 = fminf(mn2, ok ? tz[r] : inf); mx2 = fmaxf(mx2, ok ? tz[r] : -inf);
+            }
+        }
+    }
+    // the wave's fold into row w of the LDS arrays
+    __device__ __forceinline__ void fold_wave(float (*s_mm)[6], uint32_t* s_cnt, int w, int lane) {
+        mn0 = wave_min_f32_l63(mn0); mn1 = wave_min_f32_l63(mn1); mn2 = wave_min_f32_l63(mn2);
+        mx0 = wave_max_f32_l63(mx0); mx1 = wave_max_f32_l63(mx1); mx2 = wave_max_f32_l63(mx2);
+        cnt = wave_sum_u32(cnt);
+        if (lane == 63) {
+            s_mm[w][0] = mn0; s_mm[w][1] = mn1; s_mm[w][2] = mn2;
+            s_mm[w][3] = mx0; s_mm[w][4] = mx1; s_mm[w][5] = mx2;
+            s_cnt[w] = cnt;
+        }
+    }
+    // word k (0 .. 7) of the tile's record from the rows (behind a barrier)
+    template <int WAVES>
+    static __device__ __forceinline__ float record_word(const float (*s_mm)[6], const uint32_t* s_cnt, int k) {
+        float v = 0.f;
+        if (k < 6) {
+            v = s_mm[0][k];
+            for (int q = 1; q < WAVES; ++q) v = (k < 3) ? fminf(v, s_mm[q][k]) : fmaxf(v, s_mm[q][k]);
+        } else if (k == 6) {
+            uint32_t c = 0;
+            for (int q = 0; q < WAVES; ++q) c += s_cnt[q];
+            v = __uint_as_float(c);
+        }
+        return v;
+    }
+};
+
+// The exact bounds of the frame's valid points from those per-tile records: one workgroup of CM2_BLOCK threads,
+// s_f = CM2_WAVES x 8 floats of LDS; writes st->min_p / max_p / n_valid_k0.
+__device__ __forceinline__ void fold_bounds(float* s_f, CmFrameState* __restrict__ st, const float* __restrict__ records,
+                                            uint32_t n_records) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float inf = __uint_as_float(0x7F800000u);
+    float v[6] = {inf, inf, inf, -inf, -inf, -inf};
+    uint32_t cnt = 0;
+    for (uint32_t r = threadIdx.x; r < n_records; r += CM2_BLOCK) {
+        const float4 lo = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8);
+        const float4 hi = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8 + 4);
+        v[0] = fminf(v[0], lo.x); v[1] = fminf(v[1], lo.y); v[2] = fminf(v[2], lo.z);
+        v[3] = fmaxf(v[3], lo.w); v[4] = fmaxf(v[4], hi.x); v[5] = fmaxf(v[5], hi.y);
+        cnt += __float_as_uint(hi.z);
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], d));
+#pragma unroll
+        for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], d));
+        cnt += __shfl_xor(cnt, d);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_f[w * 8 + k] = v[k];
+        s_f[w * 8 + 6] = __uint_as_float(cnt);
+    }
+    __syncthreads();
+    if (threadIdx.x < 7) {
+        const int k = threadIdx.x;
+        if (k < 6) {
+            float r = s_f[k];
+            for (int q = 1; q < CM2_WAVES; ++q) r = (k < 3) ? fminf(r, s_f[q * 8 + k]) : fmaxf(r, s_f[q * 8 + k]);
+            if (k < 3) st->min_p[k] = r; else st->max_p[k - 3] = r;
+        } else {
+            uint32_t c = 0;
+            for (int q = 0; q < CM2_WAVES; ++q) c += __float_as_uint(s_f[q * 8 + 6]);
+            st->n_valid_k0 = c;
+        }
+    }
+}
+
+// Which of the two sort buffers holds the sorted data: pass p reads A when p is even and writes the other.
+__device__ __forceinline__ const uint32_t* pick(const CmFrameState* st, const uint32_t* a, const uint32_t* b) {
+    return (st->n_passes & 1u) ? b : a;
 }
 
 struct Acc { float x, y, z, i; uint32_t c; };
@@ -526,5 +721,39 @@ __device__ __forceinline__ void report_state(uint32_t* __restrict__ host, const 
         host[threadIdx.x] = wv;
     }
 }
+
+// Phase timing (scripts/phase_times*.py; build with CM_PHASE_TIMING=1): a kernel file declares an array of 4096 rows of 16
+// words, row blockIdx.x & 4095, and thread 0 of every workgroup keeps the 100 MHz ticks between phase boundaries in it:
+// PH stores them, PH_ACC adds them up (kernels that loop over tiles), PH_COUNT counts. PH_MARK / PH_SINCE time a span of
+// their own, in whichever thread executes them. The timed build waits for the loads at PH_LOADS_BACK, where the product
+// lets them fly. All compiled out of the product build.
+#ifdef CM_PHASE_TIMING
+#define CM_PHASE_DECLARE(arr) __device__ unsigned long long arr[4096 * 16]
+#define PH_SLOT(arr, k) arr[(blockIdx.x & 4095) * 16 + (k)]
+#define PH_START() long long t0_ = wall_clock64()
+#define PH_STEP(arr, k, op) do { if (threadIdx.x == 0) { const long long t1_ = wall_clock64(); PH_SLOT(arr, k) op (unsigned long long)(t1_ - t0_); t0_ = t1_; } } while (0)
+#define PH(arr, k) PH_STEP(arr, k, =)
+#define PH_ACC(arr, k) PH_STEP(arr, k, +=)
+#define PH_COUNT(arr, k) do { if (threadIdx.x == 0) PH_SLOT(arr, k) += 1ull; } while (0)
+#define PH_MARK(t) const long long t = wall_clock64()
+#define PH_SINCE(arr, k, t) do { PH_SLOT(arr, k) = (unsigned long long)(wall_clock64() - (t)); } while (0)
+#define PH_LOADS_BACK() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// Host side, the one such function in this header: the body of a file's exported read-out (cm_debug_phases*), which
+// copies the array to `out` and clears it if asked.
+inline void phase_readout(const void* symbol, unsigned long long* out, int reset) {
+    const size_t bytes = sizeof(unsigned long long) * 16 * 4096;
+    (void)hipMemcpyFromSymbol(out, symbol, bytes);
+    if (reset) { void* p_; (void)hipGetSymbolAddress(&p_, symbol); (void)hipMemset(p_, 0, bytes); }
+}
+#else
+#define CM_PHASE_DECLARE(arr)
+#define PH_START() do {} while (0)
+#define PH(arr, k) do {} while (0)
+#define PH_ACC(arr, k) do {} while (0)
+#define PH_COUNT(arr, k) do {} while (0)
+#define PH_MARK(t) do {} while (0)
+#define PH_SINCE(arr, k, t) do {} while (0)
+#define PH_LOADS_BACK() do {} while (0)
+#endif
 
 }  // namespace

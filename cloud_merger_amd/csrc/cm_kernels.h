@@ -1,4 +1,4 @@
-// cm_kernels.h — launch wrappers of the gfx950 kernels (cm_kernels.hip), used by cm_api.cpp.
+// cm_kernels.h — launch wrappers of the gfx950 kernels (cm_kernels.hip), used by cm_launch.cpp (cmk_setup also by cm_api.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -34,16 +34,7 @@ __global__ void k_setup(CmFrameDev f, CmFrameDev* __restrict__ dst, CmTileDev* _
     if (threadIdx.x == 0 && blockIdx.x == 0) *dst = f;
     const uint32_t tile = blockIdx.x * blockDim.x + threadIdx.x;
     if (tiles && tile < f.n_tiles) {
-        const uint32_t first = tile * CM_TILE;
-        uint32_t k = 0;
-        for (uint32_t q = 1; q < f.n_sensors; ++q) k += (first >= f.s[q].base) ? 1u : 0u;
-        const CmSensorDev& sd = f.s[k];
-        CmTileDev te;
-        const uint32_t off = first - sd.base;
-        te.data = sd.data + static_cast<size_t>(off) * sd.point_step;
-        te.n_left = sd.n > off ? sd.n - off : 0u;
-        te.info = k | (sd.layout << 8);
-        tiles[tile] = te;
+        tiles[tile] = tile_entry(f, tile);
     }
 }
 
@@ -66,17 +57,15 @@ __global__ __launch_bounds__(CM_BLOCK) void k_minmax(const CmFrameDev* __restric
         const uint32_t s = sensor_of_tile(fd, tile);
         const CmSensorDev& sd = fd->s[s];
         float m[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+        load_matrix(sd, m);
         const uint32_t slot0 = tile * CM_TILE + w * (64 * CM_ITEMS) + lane;
         const uint32_t first = slot0 - sd.base;
         Pt p[CM_ITEMS];
         load_tile(sd, first, p);
 #pragma unroll
         for (int r = 0; r < CM_ITEMS; ++r) {
-            const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-            const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-            const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+            float x, y, z;
+            xf_point(m, p[r], x, y, z);
             if (point_valid(x, y, z, crop, fd->crop_min, fd->crop_max) && (!mask || mask[slot0 + r * 64])) {
                 mn0 = fminf(mn0, x); mx0 = fmaxf(mx0, x);
                 mn1 = fminf(mn1, y); mx1 = fmaxf(mx1, y);
@@ -98,17 +87,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_minmax(const CmFrameDev* __restric
         s_cnt[w] = cnt;
     }
     __syncthreads();
-    if (threadIdx.x < 8) {                       // record: min xyz, max xyz, count, pad
-        const int k = threadIdx.x;
-        float v = 0.f;
-        if (k < 6) {
-            v = s_red[0][k];
-            for (int q = 1; q < CM_WAVES; ++q) v = (k < 3) ? fminf(v, s_red[q][k]) : fmaxf(v, s_red[q][k]);
-        } else if (k == 6) {
-            v = __uint_as_float(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
-        }
-        partials[blockIdx.x * 8 + k] = v;
-    }
+    if (threadIdx.x < 8) partials[blockIdx.x * 8 + threadIdx.x] = MinMax3::record_word<CM_WAVES>(s_red, s_cnt, threadIdx.x);
 }
 
 
@@ -167,8 +146,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_keys(const CmFrameDev* __restrict_
     const uint32_t s = sensor_of_tile(fd, tile);
     const CmSensorDev& sd = fd->s[s];
     float m[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+    load_matrix(sd, m);
     const uint32_t crop = fd->crop_enable;
     const float inv0 = inv[0], inv1 = inv[1], inv2 = inv[2];
     const float fb0 = static_cast<float>(g.min_b[0]), fb1 = static_cast<float>(g.min_b[1]),
@@ -186,9 +164,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_keys(const CmFrameDev* __restrict_
 #pragma unroll
     for (int r = 0; r < CM_ITEMS; ++r) {
         uint32_t key = CM_INVALID_KEY;
-        const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-        const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-        const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+        float x, y, z;
+        xf_point(m, p[r], x, y, z);
         if (point_valid(x, y, z, crop, fd->crop_min, fd->crop_max) && (!mask || mask[slot0 + r * 64])) {
             const int c0 = static_cast<int>(__fsub_rn(floorf(__fmul_rn(x, inv0)), fb0));
             const int c1 = static_cast<int>(__fsub_rn(floorf(__fmul_rn(y, inv1)), fb1));
@@ -356,11 +333,7 @@ __global__ __launch_bounds__(CM_BLOCK, 4) void k_scatter(CmFrameState* __restric
     // Workgroups are dealt round-robin over the 8 XCDs (speed only, never correctness): give each
     // XCD a contiguous range of tiles, so the digit runs of neighbouring tiles — adjacent in the
     // output — meet in one L2 instead of leaving as partial lines from eight.
-    uint32_t tile = blockIdx.x;
-    {
-        const uint32_t per = gridDim.x / 8;
-        if (blockIdx.x < per * 8) tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    }
+    const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
     // After pass 0 only the valid items are left, and pass 0 recorded how many: a crop box may have dropped most
     // of the frame, and the tiles past the end have nothing to read.
     if (!FIRST && tile * CM_TILE >= st->n_valid) return;
@@ -407,7 +380,7 @@ __global__ __launch_bounds__(CM_BLOCK, 4) void k_scatter(CmFrameState* __restric
         }
     }
     uint32_t gtot;
-    const uint32_t gbase = block_excl_scan_u32(my_total, lds, &gtot);
+    const uint32_t gbase = block_excl_scan<CM_WAVES>(my_total, lds, &gtot);
     if (FIRST && tile == 0 && threadIdx.x == 0) st->n_valid = gtot;
     const uint32_t n = FIRST ? n_padded : gtot;        // every pass sorts the same valid items
     if (tile * CM_TILE >= n) return;                   // uniform: empty tile (after the scan's barriers)
@@ -450,7 +423,7 @@ __global__ __launch_bounds__(CM_BLOCK, 4) void k_scatter(CmFrameState* __restric
         const uint32_t d = threadIdx.x;
         const uint32_t c0 = whist[0][d], c1 = whist[1][d], c2 = whist[2][d], c3 = whist[3][d];
         uint32_t tile_valid;
-        const uint32_t dbase = block_excl_scan_u32(c0 + c1 + c2 + c3, lds, &tile_valid);
+        const uint32_t dbase = block_excl_scan<CM_WAVES>(c0 + c1 + c2 + c3, lds, &tile_valid);
         whist[0][d] = dbase;
         whist[1][d] = dbase + c0;
         whist[2][d] = dbase + c0 + c1;
@@ -485,10 +458,6 @@ __global__ __launch_bounds__(CM_BLOCK, 4) void k_scatter(CmFrameState* __restric
             vals_out[p] = sval[t];
         }
     }
-}
-
-__device__ __forceinline__ const uint32_t* pick(const CmFrameState* st, const uint32_t* a, const uint32_t* b) {
-    return (st->n_passes & 1u) ? b : a;      // pass p reads A when p is even and writes the other
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -528,7 +497,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_seg_count(CmFrameState* __restrict
         }
     }
     if (unsorted) st->err = 2u;
-    const uint32_t tot = block_sum_u32(cnt, lds);
+    const uint32_t tot = block_sum<CM_WAVES>(cnt, lds);
     if (threadIdx.x == 0) {
         counts[blockIdx.x] = tot;
         // Large frames only. One 128-byte line per group: same-line atomic requests serialise.
@@ -570,9 +539,7 @@ __device__ __forceinline__ Acc gather_item(const SensorLds* __restrict__ tab, ui
         o.x = lo.z; o.y = lo.w; o.z = hi.x; o.i = hi.y;
     } else {
         const Pt p = load_point(sd.data, sd.layout, sd.step, sd.ox, sd.oy, sd.oz, sd.oi, gidx - sd.base);
-        o.x = xf_row(sd.m[0], sd.m[1], sd.m[2], sd.m[3], p.x, p.y, p.z);
-        o.y = xf_row(sd.m[4], sd.m[5], sd.m[6], sd.m[7], p.x, p.y, p.z);
-        o.z = xf_row(sd.m[8], sd.m[9], sd.m[10], sd.m[11], p.x, p.y, p.z);
+        xf_point(sd.m, p, o.x, o.y, o.z);
         o.i = all_fields ? p.i : 0.f;
         o.c = 1u;
     }
@@ -814,10 +781,10 @@ __global__ __launch_bounds__(CM_BLOCK) void k_seg_reduce(const CmFrameDev* __res
 #pragma unroll
     for (int j = 0; j < CM_SEG_ITEMS; ++j)
         if ((fmask >> j & 1u) && fin[j].c >= min_pts) ++nkeep;
-    const uint32_t tile_off = block_sum_u32(before, lds);
+    const uint32_t tile_off = block_sum<CM_WAVES>(before, lds);
     if (tile == n_tiles - 1) report_state(host_state, st, CM_DEV_OK, tile_off + counts[tile]);
     uint32_t tot;
-    uint32_t slot = tile_off + block_excl_scan_u32(nkeep, lds, &tot);
+    uint32_t slot = tile_off + block_excl_scan<CM_WAVES>(nkeep, lds, &tot);
 #pragma unroll
     for (int j = 0; j <= CM_SEG_ITEMS; ++j) {
         const bool is_last = (j == CM_SEG_ITEMS);
@@ -911,7 +878,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_table_finish(const float4* __restr
             keep = __float_as_uint(lo.y) >= need;
         }
         uint32_t tot;
-        const uint32_t ex = block_excl_scan_u32(keep ? 1u : 0u, lds, &tot);
+        const uint32_t ex = block_excl_scan<CM_WAVES>(keep ? 1u : 0u, lds, &tot);
         if (write && keep) {
             const uint32_t cnt = __float_as_uint(lo.y);
             const float c = static_cast<float>(cnt);
@@ -1210,14 +1177,13 @@ __global__ __launch_bounds__(CM_BLOCK) void k_merged_count(const CmFrameDev* __r
         const uint32_t i = first + r * CM_BLOCK + threadIdx.x;
         if (i < sd.n) {
             const Pt p = load_point(sd.data, sd.layout, sd.point_step, sd.off_x, sd.off_y, sd.off_z, sd.off_i, i);
-            const float x = xf_row(sd.m[0], sd.m[1], sd.m[2], sd.m[3], p.x, p.y, p.z);
-            const float y = xf_row(sd.m[4], sd.m[5], sd.m[6], sd.m[7], p.x, p.y, p.z);
-            const float z = xf_row(sd.m[8], sd.m[9], sd.m[10], sd.m[11], p.x, p.y, p.z);
+            float x, y, z;
+            xf_point(sd.m, p, x, y, z);
             cnt += (point_valid(x, y, z, fd->crop_enable, fd->crop_min, fd->crop_max) &&
                     (!mask || mask[tile * CM_TILE + r * CM_BLOCK + threadIdx.x])) ? 1u : 0u;
         }
     }
-    const uint32_t tot = block_sum_u32(cnt, lds);
+    const uint32_t tot = block_sum<CM_WAVES>(cnt, lds);
     if (threadIdx.x == 0) tile_counts[tile] = tot;
 }
 
@@ -1229,7 +1195,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_scan_counts(uint32_t* __restrict__
         const uint32_t t = base + threadIdx.x;
         const uint32_t v = (t < n) ? counts[t] : 0u;
         uint32_t tot;
-        const uint32_t ex = block_excl_scan_u32(v, lds, &tot);
+        const uint32_t ex = block_excl_scan<CM_WAVES>(v, lds, &tot);
         if (t < n) counts[t] = carry + ex;
         carry += tot;
     }
@@ -1252,15 +1218,13 @@ __global__ __launch_bounds__(CM_BLOCK) void k_merged_write(const CmFrameDev* __r
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < sd.n) {
             const Pt p = load_point(sd.data, sd.layout, sd.point_step, sd.off_x, sd.off_y, sd.off_z, sd.off_i, i);
-            o.x = xf_row(sd.m[0], sd.m[1], sd.m[2], sd.m[3], p.x, p.y, p.z);
-            o.y = xf_row(sd.m[4], sd.m[5], sd.m[6], sd.m[7], p.x, p.y, p.z);
-            o.z = xf_row(sd.m[8], sd.m[9], sd.m[10], sd.m[11], p.x, p.y, p.z);
+            xf_point(sd.m, p, o.x, o.y, o.z);
             o.w = p.i;
             ok = point_valid(o.x, o.y, o.z, fd->crop_enable, fd->crop_min, fd->crop_max) &&
                  (!mask || mask[tile * CM_TILE + r * CM_BLOCK + threadIdx.x]);
         }
         uint32_t tot;
-        const uint32_t ex = block_excl_scan_u32(ok ? 1u : 0u, lds, &tot);
+        const uint32_t ex = block_excl_scan<CM_WAVES>(ok ? 1u : 0u, lds, &tot);
         if (ok) out[slot + ex] = o;
         slot += tot;
     }
@@ -1279,7 +1243,7 @@ __global__ __launch_bounds__(256) void k_to_pcl32(const float4* __restrict__ in,
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-// launch wrappers (called from cm_api.cpp)
+// launch wrappers (called from cm_launch.cpp)
 // ------------------------------------------------------------------------------------------------
 #define CM_LAUNCH(kernel, grid, block, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)

@@ -51,10 +51,6 @@ __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
 __device__ __forceinline__ void min_into(uint32_t* p, uint32_t v) { if (v < ld_agent(p)) atomicMin(p, v); }
 __device__ __forceinline__ void max_into(uint32_t* p, uint32_t v) { if (v > ld_agent(p)) atomicMax(p, v); }
 
-__device__ __forceinline__ const uint32_t* pick_sorted(const CmFrameState* st, const uint32_t* a, const uint32_t* b) {
-    return (st->n_passes & 1u) ? b : a;                   // pass p reads A when p is even and writes the other
-}
-
 // bounds: [0..2] min images (set to 0xFFFFFFFF), [3..5] max images (set to 0)
 __global__ __launch_bounds__(CM_BLOCK) void k_cl_bounds(const float4* __restrict__ recs, uint32_t n, uint32_t* __restrict__ bounds) {
     __shared__ uint32_t sb[6];
@@ -122,7 +118,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_gather(const float4* __restrict
                                                         uint32_t* __restrict__ size, uint32_t* __restrict__ npts) {
     const uint32_t s = blockIdx.x * CM_BLOCK + threadIdx.x;
     if (s >= n) return;
-    const uint32_t* __restrict__ vals = pick_sorted(st, vals_a, vals_b);
+    const uint32_t* __restrict__ vals = pick(st, vals_a, vals_b);
     const uint32_t idx = vals[s];
     const float4 p = recs[idx];
     pts[s] = make_float4(p.x, p.y, p.z, __uint_as_float(idx));
@@ -161,7 +157,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_hook(const CmFrameState* __rest
                                                       uint32_t* __restrict__ parent) {
     const uint32_t s = blockIdx.x * CM_BLOCK + threadIdx.x;
     if (s >= n) return;
-    const uint32_t* __restrict__ keys = pick_sorted(st, keys_a, keys_b);
+    const uint32_t* __restrict__ keys = pick(st, keys_a, keys_b);
     const uint32_t dx = static_cast<uint32_t>(st->div_b[0]), dy = static_cast<uint32_t>(st->div_b[1]);
     const uint32_t key = keys[s];
     const float4 me = pts[s];
@@ -240,8 +236,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_count(const uint32_t* __restric
         const uint32_t i = blockIdx.x * CM_TILE + r * CM_BLOCK + threadIdx.x;
         if (i < n && cl_kept(i, root[i], size[i], min_size, max_size)) { ++k; v += size[i]; }
     }
-    k = block_sum_u32(k, lds);
-    v = block_sum_u32(v, lds);
+    k = block_sum<CM_WAVES>(k, lds);
+    v = block_sum<CM_WAVES>(v, lds);
     if (threadIdx.x == 0) tile_sums[blockIdx.x] = make_uint2(k, v);
 }
 
@@ -253,8 +249,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_scan(uint2* __restrict__ tile_s
         const uint32_t t = t0 + threadIdx.x;
         const uint2 c = t < n_tiles ? tile_sums[t] : make_uint2(0u, 0u);
         uint32_t tot_k, tot_v;
-        const uint32_t ek = block_excl_scan_u32(c.x, lds, &tot_k);
-        const uint32_t ev = block_excl_scan_u32(c.y, lds, &tot_v);
+        const uint32_t ek = block_excl_scan<CM_WAVES>(c.x, lds, &tot_k);
+        const uint32_t ev = block_excl_scan<CM_WAVES>(c.y, lds, &tot_v);
         if (t < n_tiles) tile_sums[t] = make_uint2(run_k + ek, run_v + ev);
         run_k += tot_k;
         run_v += tot_v;
@@ -283,8 +279,8 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_number(const uint32_t* __restri
     }
     uint32_t tot;
     const uint2 base = tile_excl[blockIdx.x];
-    uint32_t ck = base.x + block_excl_scan_u32(k, lds, &tot);
-    uint32_t cv = base.y + block_excl_scan_u32(v, lds, &tot);
+    uint32_t ck = base.x + block_excl_scan<CM_WAVES>(k, lds, &tot);
+    uint32_t cv = base.y + block_excl_scan<CM_WAVES>(v, lds, &tot);
 #pragma unroll
     for (int r = 0; r < CM_ITEMS; ++r) {
         const uint32_t i = first + r;

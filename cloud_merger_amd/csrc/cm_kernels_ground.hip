@@ -57,8 +57,7 @@ __global__ __launch_bounds__(CM_BLOCK) void kg_classify(const CmFrameDev* __rest
     const CmSensorDev& sd = fd->s[sensor_of_tile(fd, tile)];
     const uint32_t s = sd.slot;                          // slab tables, zone keys and planes go by the caller's sensor number
     float m[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+    load_matrix(sd, m);
     const uint32_t crop = fd->crop_enable;
     const uint32_t nz = gd->n_zones[s];
     const float zkeep = gd->z_keep_max;
@@ -72,9 +71,8 @@ __global__ __launch_bounds__(CM_BLOCK) void kg_classify(const CmFrameDev* __rest
     for (int r = 0; r < CM_ITEMS; ++r) {
         uint32_t key = CM_INVALID_KEY;
         bool keep = false;
-        const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-        const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-        const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+        float x, y, z;
+        xf_point(m, p[r], x, y, z);
         if (point_valid(x, y, z, crop, fd->crop_min, fd->crop_max)) {
             for (uint32_t q = 0; q < nz; ++q) {                 // first slab that holds the point (PassThrough: closed interval)
                 if (!(x < gd->x0[s][q] || x > gd->x1[s][q])) {
@@ -138,9 +136,10 @@ __global__ __launch_bounds__(CM_BLOCK) void kg_gather(const CmFrameDev* __restri
         for (uint32_t q = 1; q < n_sensors; ++q) s += (idx >= tab[q].base) ? 1u : 0u;
         const SensorLdsG& sd = tab[s];
         const Pt pt = load_point(sd.data, sd.layout, sd.step, sd.ox, sd.oy, sd.oz, sd.oi, idx - sd.base);
-        band_pts[p] = make_float4(xf_row(sd.m[0], sd.m[1], sd.m[2], sd.m[3], pt.x, pt.y, pt.z),
-                                  xf_row(sd.m[4], sd.m[5], sd.m[6], sd.m[7], pt.x, pt.y, pt.z),
-                                  xf_row(sd.m[8], sd.m[9], sd.m[10], sd.m[11], pt.x, pt.y, pt.z), __uint_as_float(idx));
+        float4 o;
+        xf_point(sd.m, pt, o.x, o.y, o.z);
+        o.w = __uint_as_float(idx);
+        band_pts[p] = o;
     }
 }
 

@@ -7,7 +7,7 @@
 //                  dt = dt0_s + tau,  h = 0.5 (dt dt),  c = w x q,  e = w x c,  k = w x v
 //                  out = q + ((dt (c + v)) + (h (e + k)))
 //              every operation rounded on its own (no contraction), in this order. Written as 16-byte x,y,z,intensity
-//              records at the point's padded index: the frame descriptor is then pointed at them (cm_api.cpp build_frame),
+//              records at the point's padded index: the frame descriptor is then pointed at them (cm_launch.cpp build_frame),
 //              with identity matrices, and every route runs unchanged on the compensated points.  [raw read, 16 B/pt write]
 // A non-finite coordinate or time leaves the record non-finite (NaN / inf propagate through every term that holds them):
 // the point is dropped downstream exactly as an uncompensated one would be.
@@ -71,6 +71,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_motion(const CmMotionDev md, cm_v4
 #pragma unroll
     for (int r = 0; r < CM_MOTION_ITEMS; ++r) {
         const uint32_t i = i0 + r * CM_BLOCK;
+        // (the three rows written out, not xf_point: through the helper this kernel takes 78 VGPRs instead of 70, 6 waves/SIMD for 7)
         const float qx = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
         const float qy = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
         const float qz = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);

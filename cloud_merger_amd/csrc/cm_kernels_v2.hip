@@ -19,7 +19,7 @@
 //
 // The voxel keys need the grid before the first point is read, so this path runs only when the host
 // knows a box that contains the cloud: the crop box, or the previous frame's bounds plus a margin
-// (cm_api.cpp). Keys are linear indices in that box: the same order as PCL's (x fastest), so kept
+// (cm_route.cpp). Keys are linear indices in that box: the same order as PCL's (x fastest), so kept
 // voxels, their order and their point sums are those of pcl::VoxelGrid; a point
 // outside a predicted box raises CmFrameState.outside and the host redoes the frame with
 // cm_kernels.hip. A bucket that does not fit LDS raises CM_DEV_ERR_BUCKET, same remedy.
@@ -32,42 +32,6 @@
 #include "cm_kernels.h"
 
 namespace {
-
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_excl_scan_w(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v, lane);
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; ++k) {
-        const uint32_t c = lds[k];
-        if (k < w) woff += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
-
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_sum_w(uint32_t v, uint32_t* lds) {
-    v = wave_sum_u32(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t tot = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; ++k) tot += lds[k];
-    __syncthreads();
-    return tot;
-}
-
-__device__ __forceinline__ uint32_t sensor_of_slot(const CmFrameDev* __restrict__ fd, uint32_t first) {
-    uint32_t s = 0;
-    for (uint32_t q = 1; q < fd->n_sensors; ++q) s += (first >= fd->s[q].base) ? 1u : 0u;
-    return s;
-}
 
 // ------------------------------------------------------------------------------------------------
 // k2_hist0: per 4096-slot tile of the padded index space, counts of the first (lowest of the HIGH)
@@ -103,39 +67,18 @@ __global__ __launch_bounds__(CM2_BLOCK, PACK ? 8 : 1) void k2_hist0(const CmFram
     __shared__ uint32_t s_out;
     const uint32_t tile = blockIdx.x;
     const CmFrameDev* __restrict__ fd = &fv;
-    CmTileDev te;                                         // where this tile's points lie (k_setup's arithmetic)
-    {
-        const uint32_t first = tile * CM_TILE;
-        uint32_t k = 0;
-        for (uint32_t q = 1; q < fv.n_sensors; ++q) k += (first >= fv.s[q].base) ? 1u : 0u;
-        const CmSensorDev& sd0 = fv.s[k];
-        const uint32_t off = first - sd0.base;
-        te.data = sd0.data + static_cast<size_t>(off) * sd0.point_step;
-        te.n_left = sd0.n > off ? sd0.n - off : 0u;
-        te.info = k | (sd0.layout << 8);
-    }
+    const CmTileDev te = tile_entry(fv, tile);
     if (do_setup) {
-        static_assert(sizeof(CmFrameDev) % 4 == 0 && sizeof(CmFrameDev) / 4 <= CM2_BLOCK, "one word of the descriptor per thread");
         if (threadIdx.x == 0) tiles_dst[tile] = te;
-        if (tile == 0 && threadIdx.x < sizeof(CmFrameDev) / 4)
-            reinterpret_cast<uint32_t*>(fd_dst)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&fv)[threadIdx.x];
+        if (tile == 0) store_frame_desc(fv, fd_dst);
     }
     for (uint32_t k = tile * CM2_BLOCK + threadIdx.x; k < 3 * n_group_words; k += gridDim.x * CM2_BLOCK) grp_clear_b[k] = 0;
     for (uint32_t k = tile * CM2_BLOCK + threadIdx.x; k < n_clear_a_words; k += gridDim.x * CM2_BLOCK) grp_clear_a[k] = 0;
     for (uint32_t k = tile * CM2_BLOCK + threadIdx.x; k < n_tile_state; k += gridDim.x * CM2_BLOCK) tile_state[k] = 0ull;
 
-    if (tile == 0 && threadIdx.x == 0) {                 // the box and its grid, as the host set them up
+    if (tile == 0 && threadIdx.x == 0) {
         const int32_t so = st_outlier ? st_outlier->status : CM_DEV_OK;      // a stage before this one failed: so does the frame
-        st->status = (so == CM_DEV_OUTLIER_GRID || so == CM_DEV_ABORTED) ? so : CM_DEV_OK;
-        for (int a = 0; a < 3; ++a) {
-            st->min_p[a] = grid_mode == 2 ? fd->ext_min[a] : fd->crop_min[a];
-            st->max_p[a] = grid_mode == 2 ? fd->ext_max[a] : fd->crop_max[a];
-            const int32_t mb = use_cell ? fd->cell_min_b[a] : fd->box_min_b[a], db = use_cell ? fd->cell_div_b[a] : fd->box_div_b[a];
-            st->min_b[a] = mb; st->max_b[a] = mb + db - 1;
-            st->div_b[a] = db;
-        }
-        st->key_bits = use_cell ? fd->cell_key_bits : fd->box_key_bits;
-        st->n_passes = n_global_passes;
+        init_box_state(st, fd, grid_mode, use_cell, n_global_passes, (so == CM_DEV_OUTLIER_GRID || so == CM_DEV_ABORTED) ? so : CM_DEV_OK);
     }
     const BoxGrid b = box_grid_of(fd, use_cell);
     const bool predicted = check_box != 0;        // the box is a prediction: verify every point, record the true bounds
@@ -146,14 +89,8 @@ __global__ __launch_bounds__(CM2_BLOCK, PACK ? 8 : 1) void k2_hist0(const CmFram
     Pt p[CM2_ITEMS];
     load_tile_te<CM2_ITEMS>(te, sd, w * (64 * CM2_ITEMS) + lane, p);
     float m[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
-    const uint32_t crop = fd->crop_enable;
-    float cmn0 = 0.f, cmn1 = 0.f, cmn2 = 0.f, cmx0 = 0.f, cmx1 = 0.f, cmx2 = 0.f;
-    if (crop) {
-        cmn0 = fd->crop_min[0]; cmn1 = fd->crop_min[1]; cmn2 = fd->crop_min[2];
-        cmx0 = fd->crop_max[0]; cmx1 = fd->crop_max[1]; cmx2 = fd->crop_max[2];
-    }
+    load_matrix(sd, m);
+    const CropBox crop = load_crop(fd);
     if (threadIdx.x < CM_RADIX) lh[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_out = 0;
     uint32_t mk[CM2_ITEMS];                               // keep-mask bytes of the pre-stages (outlier / ground removal)
@@ -162,25 +99,19 @@ __global__ __launch_bounds__(CM2_BLOCK, PACK ? 8 : 1) void k2_hist0(const CmFram
         for (int r = 0; r < CM2_ITEMS; ++r) mk[r] = mask[slot0 + r * 64];
     }
     __syncthreads();
-    const float inf = __uint_as_float(0x7F800000u);
-    float mn0 = inf, mn1 = inf, mn2 = inf, mx0 = -inf, mx1 = -inf, mx2 = -inf;
-    uint32_t cnt = 0;
+    MinMax3 mm;
     bool any_out = false;
     const bool all_fields = fd->downsample_all != 0;
     uint32_t wrun = 0;                                    // records this wave has packed so far (wave-uniform)
-    // Straight-line code per point: every test is formed as a flag (no short-circuit evaluation — the compiler turns
-    // that into a chain of exec-mask branches with the running min/max re-materialised at every join), and only the
-    // LDS add sits under a mask.
+    // Straight-line code per point (flags, no short-circuit evaluation: see valid_point); only the LDS add sits under a mask.
     float tx[CM2_ITEMS], ty[CM2_ITEMS], tz[CM2_ITEMS];
     uint32_t okm = 0;
 #pragma unroll
     for (int r = 0; r < CM2_ITEMS; ++r) {
-        const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-        const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-        const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+        float x, y, z;
+        xf_point(m, p[r], x, y, z);
         tx[r] = x; ty[r] = y; tz[r] = z;
-        bool ok = finite_f32(x) & finite_f32(y) & finite_f32(z);
-        if (crop) ok = ok & !((x < cmn0) | (x > cmx0) | (y < cmn1) | (y > cmx1) | (z < cmn2) | (z > cmx2));
+        bool ok = valid_point(x, y, z, crop);
         if (mask) ok = ok & (mk[r] != 0u);
         bool in;
         const uint32_t key = key_of(b, x, y, z, &in);
@@ -199,56 +130,20 @@ __global__ __launch_bounds__(CM2_BLOCK, PACK ? 8 : 1) void k2_hist0(const CmFram
             wrun += static_cast<uint32_t>(__popcll(bal));
         }
     }
-    if (predicted) {
-        // The exact bounds of the valid points (pcl::getMinMax3D). Nearly every wave holds valid points only: then the
-        // eight values of a lane fold with three-operand min / max, no masking.
-        cnt = static_cast<uint32_t>(__builtin_popcount(okm));
-        if (__ballot(okm != (1u << CM2_ITEMS) - 1u) == 0ull) {
-#pragma unroll
-            for (int r = 0; r < CM2_ITEMS; r += 2) {
-                mn0 = fminf(fminf(mn0, tx[r]), tx[r + 1]); mx0 = fmaxf(fmaxf(mx0, tx[r]), tx[r + 1]);
-                mn1 = fminf(fminf(mn1, ty[r]), ty[r + 1]); mx1 = fmaxf(fmaxf(mx1, ty[r]), ty[r + 1]);
-                mn2 = fminf(fminf(mn2, tz[r]), tz[r + 1]); mx2 = fmaxf(fmaxf(mx2, tz[r]), tz[r + 1]);
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < CM2_ITEMS; ++r) {
-                const bool ok = (okm >> r) & 1u;
-                mn0 = fminf(mn0, ok ? tx[r] : inf); mx0 = fmaxf(mx0, ok ? tx[r] : -inf);
-                mn1 = fminf(mn1, ok ? ty[r] : inf); mx1 = fmaxf(mx1, ok ? ty[r] : -inf);
-                mn2 = fminf(mn2, ok ? tz[r] : inf); mx2 = fmaxf(mx2, ok ? tz[r] : -inf);
-            }
-        }
-    }
+    if (predicted) mm.add(tx, ty, tz, okm);       // the exact bounds of the valid points (pcl::getMinMax3D)
     if (PACK && lane == 0) wave_cnt[tile * CM2_WAVES + w] = wrun;
     if (predicted) {
         if (any_out) s_out = 1u;
-        mn0 = wave_min_f32_l63(mn0); mn1 = wave_min_f32_l63(mn1); mn2 = wave_min_f32_l63(mn2);
-        mx0 = wave_max_f32_l63(mx0); mx1 = wave_max_f32_l63(mx1); mx2 = wave_max_f32_l63(mx2);
-        cnt = wave_sum_u32(cnt);
-        if (lane == 63) {
-            s_mm[w][0] = mn0; s_mm[w][1] = mn1; s_mm[w][2] = mn2;
-            s_mm[w][3] = mx0; s_mm[w][4] = mx1; s_mm[w][5] = mx2;
-            s_cnt[w] = cnt;
-        }
+        mm.fold_wave(s_mm, s_cnt, w, lane);
     }
     __syncthreads();
     if (threadIdx.x < CM_RADIX) {
         const uint32_t c = lh[threadIdx.x];
         hist[static_cast<size_t>(tile) * CM_RADIX + threadIdx.x] = c;
         if (c) atomicAdd(&grp_acc[static_cast<size_t>(tile / CM_GROUP) * CM_RADIX + threadIdx.x], c);
-    } else if (predicted && threadIdx.x < CM_RADIX + 8) {         // record: min xyz, max xyz, count, pad
+    } else if (predicted && threadIdx.x < CM_RADIX + 8) {
         const int k = threadIdx.x - CM_RADIX;
-        float v = 0.f;
-        if (k < 6) {
-            v = s_mm[0][k];
-            for (int q = 1; q < CM2_WAVES; ++q) v = (k < 3) ? fminf(v, s_mm[q][k]) : fmaxf(v, s_mm[q][k]);
-        } else if (k == 6) {
-            uint32_t c = 0;
-            for (int q = 0; q < CM2_WAVES; ++q) c += s_cnt[q];
-            v = __uint_as_float(c);
-        }
-        records[static_cast<size_t>(tile) * 8 + k] = v;
+        records[static_cast<size_t>(tile) * 8 + k] = MinMax3::record_word<CM2_WAVES>(s_mm, s_cnt, k);
     }
     if (threadIdx.x == 0 && s_out) st->outside = 1u;
 }
@@ -281,58 +176,8 @@ __global__ __launch_bounds__(CM2_BLOCK) void k2_hist(const CmFrameState* __restr
     }
 }
 
-// Phase timing of the local finish (scripts/phase_times.py; build with CM_PHASE_TIMING=1): thread 0 of every
-// workgroup stores the 100 MHz ticks between phase boundaries. Compiled out of the product build.
-#ifdef CM_PHASE_TIMING
-__device__ unsigned long long g_phase[4096 * 16];
-#define PH_START() long long t0_ = wall_clock64()
-#define PH(k) do { if (threadIdx.x == 0) { const long long t1_ = wall_clock64(); g_phase[(blockIdx.x & 4095) * 16 + (k)] = (unsigned long long)(t1_ - t0_); t0_ = t1_; } } while (0)
-#else
-#define PH_START() do {} while (0)
-#define PH(k) do {} while (0)
-#endif
-// The exact bounds of the frame's valid points from k2_hist0's per-tile records (min xyz, max xyz, count): one workgroup,
-// s_f = CM2_WAVES x 8 floats of LDS; writes st->min_p / max_p / n_valid_k0.
-__device__ __forceinline__ void fold_bounds(float* s_f, CmFrameState* __restrict__ st, const float* __restrict__ records,
-                                            uint32_t n_records) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float inf = __uint_as_float(0x7F800000u);
-    float v[6] = {inf, inf, inf, -inf, -inf, -inf};
-    uint32_t cnt = 0;
-    for (uint32_t r = threadIdx.x; r < n_records; r += CM2_BLOCK) {
-        const float4 lo = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8);
-        const float4 hi = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8 + 4);
-        v[0] = fminf(v[0], lo.x); v[1] = fminf(v[1], lo.y); v[2] = fminf(v[2], lo.z);
-        v[3] = fmaxf(v[3], lo.w); v[4] = fmaxf(v[4], hi.x); v[5] = fmaxf(v[5], hi.y);
-        cnt += __float_as_uint(hi.z);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], d));
-#pragma unroll
-        for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], d));
-        cnt += __shfl_xor(cnt, d);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s_f[w * 8 + k] = v[k];
-        s_f[w * 8 + 6] = __uint_as_float(cnt);
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int k = threadIdx.x;
-        if (k < 6) {
-            float r = s_f[k];
-            for (int q = 1; q < CM2_WAVES; ++q) r = (k < 3) ? fminf(r, s_f[q * 8 + k]) : fmaxf(r, s_f[q * 8 + k]);
-            if (k < 3) st->min_p[k] = r; else st->max_p[k - 3] = r;
-        } else {
-            uint32_t c = 0;
-            for (int q = 0; q < CM2_WAVES; ++q) c += __float_as_uint(s_f[q * 8 + 6]);
-            st->n_valid_k0 = c;
-        }
-    }
-}
+// Phase timing of the scatters and the local finish (scripts/phase_times.py, phase_times_scatter.py; cm_common.hpp).
+CM_PHASE_DECLARE(g_phase);
 
 // ------------------------------------------------------------------------------------------------
 // k2_scatter: stable scatter of one 4096-record tile by one 8-bit digit; the record itself moves.
@@ -374,16 +219,12 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
     if (st->status != CM_DEV_OK) return;
     if (st->outside) {
         // A point left the predicted box: the frame is handed back — with the cloud's exact bounds, which k2_hist0's records
-        // hold all the same, so that the host can redo it in a box that fits (cm_api.cpp wait_frame) instead of measuring again.
+        // hold all the same, so that the host can redo it in a box that fits (cm_launch.cpp wait_frame) instead of measuring again.
         if (FIRST && fold && blockIdx.x == 0) fold_bounds(reinterpret_cast<float*>(whist), st, records, n_records);
         return;
     }
     PH_START();
-    uint32_t tile = blockIdx.x;
-    {
-        const uint32_t per = gridDim.x / 8;              // contiguous tile range per XCD (see k_scatter)
-        if (blockIdx.x < per * 8) tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    }
+    const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
     if (!FIRST && tile * CM_TILE >= st->n_valid) return;    // (the first pass recorded how many records are left: see k_scatter)
     const BoxGrid b = box_grid_of(fd, use_cell);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -475,24 +316,14 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
     if (FIRST && !compact_in) {
         const CmSensorDev& sd = fd->s[sidx];
         float m[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
-        const uint32_t crop = fd->crop_enable;
-        float cmn0 = 0.f, cmn1 = 0.f, cmn2 = 0.f, cmx0 = 0.f, cmx1 = 0.f, cmx2 = 0.f;
-        if (crop) {
-            cmn0 = fd->crop_min[0]; cmn1 = fd->crop_min[1]; cmn2 = fd->crop_min[2];
-            cmx0 = fd->crop_max[0]; cmx1 = fd->crop_max[1]; cmx2 = fd->crop_max[2];
-        }
+        load_matrix(sd, m);
+        const CropBox crop = load_crop(fd);
         const bool all_fields = fd->downsample_all != 0;
 #pragma unroll
         for (int r = 0; r < CM2_ITEMS; ++r) {
-            rec[r].x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-            rec[r].y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-            rec[r].z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+            xf_point(m, p[r], rec[r].x, rec[r].y, rec[r].z);
             rec[r].w = use_cell ? __uint_as_float(first + r * 64) : (all_fields ? p[r].i : 0.f);   // outlier stage: the point's padded index rides along
-            bool ok = finite_f32(rec[r].x) & finite_f32(rec[r].y) & finite_f32(rec[r].z);
-            if (crop) ok = ok & !((rec[r].x < cmn0) | (rec[r].x > cmx0) | (rec[r].y < cmn1) | (rec[r].y > cmx1) |
-                                  (rec[r].z < cmn2) | (rec[r].z > cmx2));
+            bool ok = valid_point(rec[r].x, rec[r].y, rec[r].z, crop);
             if (mask) ok = ok & (mask[first + r * 64] != 0);        // (frames behind a pre-stage only)
             bool in;
             const uint32_t k = key_of(b, rec[r].x, rec[r].y, rec[r].z, &in);
@@ -502,13 +333,13 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
         }
     }
 
-    PH((FIRST ? 0 : 8) + 0);
+    PH(g_phase, (FIRST ? 0 : 8) + 0);
     uint32_t gtot;
-    const uint32_t gbase = block_excl_scan_w<CM2_WAVES>(my_total, lds, &gtot);
+    const uint32_t gbase = block_excl_scan<CM2_WAVES>(my_total, lds, &gtot);
     if (FIRST && tile == 0 && threadIdx.x == 0) st->n_valid = gtot;
     const uint32_t n = FIRST ? n_padded : gtot;
     if (tile * CM_TILE >= n) return;                     // uniform (n is the same in every workgroup)
-    PH((FIRST ? 0 : 8) + 1);
+    PH(g_phase, (FIRST ? 0 : 8) + 1);
 
     if (!FIRST) {
 #pragma unroll
@@ -550,7 +381,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
     }
     }
     __syncthreads();
-    PH((FIRST ? 0 : 8) + 2);
+    PH(g_phase, (FIRST ? 0 : 8) + 2);
     {
         // thread t < 128: digits 2t and 2t+1 — totals over the waves, exclusive prefix over the digits, then every wave's
         // counter becomes the first sorted position of its records of that digit
@@ -560,7 +391,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
             for (int q = 0; q < CM2_WAVES; ++q) { cw[q] = whist[q][threadIdx.x]; t0 += cw[q] & 0xFFFFu; t1 += cw[q] >> 16; }
         }
         uint32_t tile_valid;
-        const uint32_t db = block_excl_scan_w<CM2_WAVES>(t0 + t1, lds, &tile_valid);
+        const uint32_t db = block_excl_scan<CM2_WAVES>(t0 + t1, lds, &tile_valid);
         if (threadIdx.x < CM_RADIX / 2) {
             uint32_t r0 = db, r1 = db + t0;
             s_dbase[2 * threadIdx.x] = static_cast<uint16_t>(r0);
@@ -574,7 +405,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
         }
     }
     __syncthreads();
-    PH((FIRST ? 0 : 8) + 3);
+    PH(g_phase, (FIRST ? 0 : 8) + 3);
     if (threadIdx.x < CM_RADIX)                                  // (read again behind the barrier of the first staging round)
         gofs[threadIdx.x] = gbase + before + gofs[threadIdx.x] - s_dbase[threadIdx.x];   // (+ the part threads 256-511 summed)
     const uint32_t tile_valid = s_tile_valid;
@@ -594,7 +425,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
     for (int h = 0; h < 2; ++h) {
         const uint32_t lo = h * (CM_TILE / 2);
         if (h == 1) {
-            PH((FIRST ? 0 : 8) + 4);
+            PH(g_phase, (FIRST ? 0 : 8) + 4);
             if (tile_valid <= lo) break;                   // uniform
         }
         __syncthreads();                                   // (round 0: the last reads of the counters; round 1: of the staged records)
@@ -627,7 +458,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k2_scatter(const CmFrameDev* __r
         }
     }
 
-    PH((FIRST ? 0 : 8) + 5);
+    PH(g_phase, (FIRST ? 0 : 8) + 5);
     // The exact bounds of the cloud (pcl::getMinMax3D) for the result and for the next frame's box.
     if (FIRST && fold && tile == 0) {
         __syncthreads();
@@ -692,7 +523,7 @@ __global__ __launch_bounds__(CM2_BLOCK) void k2_scatter_sparse(const CmFrameDev*
     (&wcnt[0][0])[CM2_BLOCK + threadIdx.x] = 0;
     static_assert(CM2_WAVES * (CM_RADIX / 2) == 2 * CM2_BLOCK, "counter words per thread");
     uint32_t gtot;
-    const uint32_t gbase = block_excl_scan_w<CM2_WAVES>(my_total, lds, &gtot);     // (its barriers publish part[])
+    const uint32_t gbase = block_excl_scan<CM2_WAVES>(my_total, lds, &gtot);     // (its barriers publish part[])
     if (blockIdx.x == 0 && threadIdx.x == 0) st->n_valid = gtot;
     if (threadIdx.x < CM_RADIX) {
         uint32_t hv[CM2_WAVES];
@@ -808,7 +639,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
     const uint32_t tile = s_a;
     __syncthreads();
     const BoxGrid b = b0;
-    PH(0);
+    PH(g_phase, 0);
     const uint32_t L = low_bits;
     // partial_out: this GPU's share of a fused cloud — per-voxel sums and counts, no threshold, no division (§6)
     const uint32_t min_pts = (!partial_out && fd->min_pts > 1) ? fd->min_pts : 1u;
@@ -837,7 +668,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
         if (threadIdx.x == 0) { s_keyprev = base > 0 ? key_of(b, pv) : 0u; s_a = 0xFFFFFFFFu; }
     }
     __syncthreads();
-    PH(1);
+    PH(g_phase, 1);
 
     // ---- a: first bucket start in the nominal tile; the bucket number must not decrease anywhere (free check of the
     // global passes' ranking, as k3_local does: CM_DEV_ERR_UNSORTED hands the frame back)
@@ -891,7 +722,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
         if (WRITEBACK) st->status = CM_DEV_ABORTED;
     }
 
-    PH(2);
+    PH(g_phase, 2);
     // ---- sort the owned slots [a, a+m) by key: LSD over the bits in which the keys of this tile can
     // differ, up to 10 per pass, stable. Only the slot numbers move (si); a pass reads its digit
     // through the slot. Ranking: returning LDS adds on per-wave counters (lane order, see k_scatter).
@@ -946,7 +777,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
                 }
             }
             uint32_t all;
-            const uint32_t db = block_excl_scan_w<LWAVES>(t0 + t1, lds, &all);
+            const uint32_t db = block_excl_scan<LWAVES>(t0 + t1, lds, &all);
             if (threadIdx.x < words) {
                 dbase[2 * threadIdx.x] = static_cast<uint16_t>(db);
                 dbase[2 * threadIdx.x + 1] = static_cast<uint16_t>(db + t0);
@@ -964,7 +795,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
         }
     }
 
-    PH(3);
+    PH(g_phase, 3);
     if (WRITEBACK) {
         const uint32_t rounds_w = (m + LBLOCK - 1) / LBLOCK;
         for (uint32_t r = 0; r < rounds_w; ++r) {
@@ -995,7 +826,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
     }
     uint32_t n_vox;
     {
-        uint32_t v = block_excl_scan_w<LWAVES>(nh, lds, &n_vox);     // its barriers also retire the last reads of whist
+        uint32_t v = block_excl_scan<LWAVES>(nh, lds, &n_vox);     // its barriers also retire the last reads of whist
         const uint32_t i0 = threadIdx.x * per;
 #pragma unroll
         for (int j = 0; j < LITEMS; ++j)
@@ -1003,7 +834,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
     }
     __syncthreads();
 
-    PH(4);
+    PH(g_phase, 4);
     // ---- kept voxels (A.4 step 7: at least min_pts points), published at once for the look-back
     // Thread t takes voxels [t * pv, (t + 1) * pv): a wave covers 64 * pv consecutive voxels (similar run
     // lengths), and the kept ones get consecutive output slots from one scan.
@@ -1026,18 +857,16 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
         }
     }
     uint32_t c_t;
-    const uint32_t my_slot = block_excl_scan_w<LWAVES>(nkeep, lds, &c_t);
+    const uint32_t my_slot = block_excl_scan<LWAVES>(nkeep, lds, &c_t);
     if (threadIdx.x == (LWAVES - 1) * 64) {              // the lane that later publishes the prefix: same-address stores stay in order
         const unsigned long long v = (tile == 0 ? CM2_FLAG_PREFIX : CM2_FLAG_AGG) | c_t;
         __hip_atomic_store(&tile_state[tile], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    PH(5);
+    PH(g_phase, 5);
     // ---- output offset: kept voxels of every earlier tile (decoupled look-back). The last wave does
     // it while the others add up their voxels: it has the fewest voxels (often none), and what it waits for —
     // the counts of the tiles before this one — is being published in the meantime.
-#ifdef CM_PHASE_TIMING
-    const long long tw0_ = wall_clock64();
-#endif
+    PH_MARK(tw0_);
     if (w == LWAVES - 1) {
         uint32_t excl = 0;
         bool timed_out = false, done = false;
@@ -1077,9 +906,7 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
             s_off = excl;
         }
         if (__ballot(timed_out) && lane == 0) host_state[offsetof(CmFrameState, err) / 4] = CM_DEV_ERR_LOOKBACK;
-#ifdef CM_PHASE_TIMING
-        if (lane == 0) g_phase[(blockIdx.x & 4095) * 16 + 9] = (unsigned long long)(wall_clock64() - tw0_);
-#endif
+        if (lane == 0) PH_SINCE(g_phase, 9, tw0_);
     }
     // ---- centroid sums: one lane per kept voxel adds its points in sorted (= stable) order, the
     // order pcl::VoxelGrid itself adds them in (A.4 step 6).
@@ -1098,12 +925,10 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
         }
     }
 
-#ifdef CM_PHASE_TIMING
-    if (lane == 0 && w >= 1 && w <= 6) g_phase[(blockIdx.x & 4095) * 16 + 9 + w] = (unsigned long long)(wall_clock64() - tw0_);   // 10..15: waves 1..6
-#endif
-    PH(6);
+    if (lane == 0 && w >= 1 && w <= 6) PH_SINCE(g_phase, 9 + w, tw0_);   // 10..15: waves 1..6
+    PH(g_phase, 6);
     __syncthreads();
-    PH(7);
+    PH(g_phase, 7);
     const uint32_t tile_off = s_off;
     if (tile == n_lt - 1) report_state(host_state, st, CM_DEV_OK, tile_off + c_t, true);
 
@@ -1125,14 +950,13 @@ __global__ __launch_bounds__(LBLOCK, LBLOCK <= 512 ? 6 : 4) void k2_local(const 
             ++slot;
         }
     }
-    PH(8);
+    PH(g_phase, 8);
 }
 
 }  // namespace
 #ifdef CM_PHASE_TIMING
 extern "C" __attribute__((visibility("default"))) void cm_debug_phases(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(unsigned long long) * 16 * 4096);
-    if (reset) { void* p_; (void)hipGetSymbolAddress(&p_, HIP_SYMBOL(g_phase)); (void)hipMemset(p_, 0, sizeof(unsigned long long) * 16 * 4096); }
+    phase_readout(HIP_SYMBOL(g_phase), out, reset);
 }
 #endif
 

@@ -20,7 +20,7 @@
 //     sequential chain — but it takes ~200-250 cycles per wave instruction against 4 for ds_add_u32
 //     (scripts/micro/lds_atomic_rate.hip) and holds the CU's LDS pipe meanwhile: k3_local 89 us against 39.)
 //   * the order the global passes left is checked: H must not decrease from one record to the
-//     next; a violation raises CM_DEV_ERR_UNSORTED and the frame is handed back (cm_api.cpp wait_frame).
+//     next; a violation raises CM_DEV_ERR_UNSORTED and the frame is handed back (cm_launch.cpp wait_frame).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -50,35 +50,8 @@ struct Job3 {                      // a voxel that runs far past its owner's blo
 #define CM3_EXT_SEQ 16u            // positions past its block a thread still adds one after the other
 #define CM3_RUN_MAX (1u << 20)     // a voxel with more points than this goes back to the general path (parallel tree sums)
 
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_excl_scan3(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v, lane);
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; ++k) {
-        const uint32_t c = lds[k];
-        if (k < w) woff += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
-
-// Phase timing (scripts/phase_times3.py; build with CM_PHASE_TIMING=1): thread 0 of every workgroup stores the 100 MHz
-// ticks between phase boundaries. Compiled out of the product build.
-#ifdef CM_PHASE_TIMING
-__device__ unsigned long long g_phase3[4096 * 16];
-#define PH3_START() long long t0_ = wall_clock64()
-#define PH3(k) do { if (threadIdx.x == 0) { const long long t1_ = wall_clock64(); g_phase3[(blockIdx.x & 4095) * 16 + (k)] = (unsigned long long)(t1_ - t0_); t0_ = t1_; } } while (0)
-#else
-#define PH3_START() do {} while (0)
-#define PH3(k) do {} while (0)
-#endif
-
+// Phase timing of the finish (scripts/phase_times3.py; cm_common.hpp).
+CM_PHASE_DECLARE(g_phase_k3);
 
 // ------------------------------------------------------------------------------------------------
 // k3_local
@@ -127,7 +100,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
     Job3* jobs = reinterpret_cast<Job3*>(&whist[0][0]);         // (the counters are dead once the sort is over: 512 jobs fit)
 
     if (QUANT && big_list && blockIdx.x >= big_list[0]) return;        // (the large shape's launch: usually nothing to do — leave at once)
-    PH3_START();
+    PH_START();
     // (values that are the same in every lane are put into scalar registers by hand — the compiler cannot tell for what
     // comes out of LDS or global memory — so that the loops below branch and count on the scalar unit)
     const int lane = threadIdx.x & 63;
@@ -182,7 +155,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
                 below_t += (valid && v < sub) ? 1u : 0u;
             }
             uint32_t tot;
-            uint32_t pos = kept + block_excl_scan3<LWAVES>(static_cast<uint32_t>(__builtin_popcount(mm)), lds, &tot);
+            uint32_t pos = kept + block_excl_scan<LWAVES>(static_cast<uint32_t>(__builtin_popcount(mm)), lds, &tot);
             while (mm) {
                 const uint32_t i = static_cast<uint32_t>(__builtin_ctz(mm));
                 mm &= mm - 1u;
@@ -192,7 +165,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
             kept += SCAL(tot);
         }
         uint32_t below;
-        (void)block_excl_scan3<LWAVES>(below_t, lds, &below);
+        (void)block_excl_scan<LWAVES>(below_t, lds, &below);
         base = rbase + SCAL(below);
         q_big = kept > static_cast<uint32_t>(LCAP);          // (no large shape behind this one: the frame is handed back)
         nom = q_big ? 0u : kept;
@@ -242,7 +215,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
         if (threadIdx.x == 0) { s_keyprev = base > 0 ? key_of(b, pv) : 0u; s_a = 0xFFFFFFFFu; s_bad = 0u; s_njobs = 0u; }
     }
     __syncthreads();
-    PH3(0);
+    PH(g_phase_k3, 0);
 
     // ---- a: first bucket start in the nominal tile; H must not decrease anywhere (free check of the global passes)
     bool bad_order = q_bad;
@@ -296,7 +269,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
     const uint32_t m = (a == 0xFFFFFFFFu || too_big) ? 0u : nom + ext - a;
     if (too_big && threadIdx.x == 0) host_state[offsetof(CmFrameState, err) / 4] = CM_DEV_ERR_BUCKET;
 
-    PH3(1);
+    PH(g_phase_k3, 1);
     // ---- sort the owned slots [a, a+m) by key: LSD over the bits in which the keys of this tile can differ, up to
     // 10 per pass, stable; only the slot numbers move. Ranking: returning LDS adds on per-wave counters.
     if (m && L == 0) {                                         // already in key order: the sorted position IS the slot
@@ -385,7 +358,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
         }
     }
     if (s_bad && threadIdx.x == 0) host_state[offsetof(CmFrameState, err) / 4] = CM_DEV_ERR_UNSORTED;
-    PH3(2);
+    PH(g_phase_k3, 2);
 
     // ---- the next frame's splitters (cm_kernels_v4.hip): sorted position e of this tile is record base + a + e of the whole
     // frame in index order; splitter j of bn is the index at record j * Q, Q = ceil(n / bn) (buckets of Q records; the last
@@ -468,7 +441,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
             if (static_cast<uint32_t>(j) >= per) break;        // (uniform)
             if ((ldm >> j) & 1u) r4[j] = rec[rbase + (SUB ? sp[sl[j]] : sl[j])];
         }
-        const uint32_t kid0 = block_excl_scan3<LWAVES>(static_cast<uint32_t>(__builtin_popcount(kheads)), lds, &c_t);
+        const uint32_t kid0 = block_excl_scan<LWAVES>(static_cast<uint32_t>(__builtin_popcount(kheads)), lds, &c_t);
 
         auto emit = [&](uint32_t kid, uint32_t key, float sx, float sy, float sz, float sw, uint32_t cn) {
             const size_t o = static_cast<size_t>(base) + a + kid;
@@ -497,7 +470,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
                 ++cn;
             }
         }
-        PH3(3);
+        PH(g_phase_k3, 3);
         if (on) {
             // the last voxel may go on past the block: four positions at a time, loads first — up to CM3_EXT_SEQ positions
             // one after the other (stable order, bit for bit pcl's sum); a voxel longer than that is finished by a wave
@@ -541,7 +514,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
             }
         }
 
-        PH3(4);
+        PH(g_phase_k3, 4);
         // ---- long voxels. A wave sums 64 positions per chunk, eight chunks (512 positions) per step: every record of a step
         // asked for at once, a chunk's sum formed in a fixed tree order and added to the running sum chunk after chunk:
         // deterministic, within 1e-4 m of pcl's one-after-the-other sum (closer to the exact mean, in fact), not
@@ -661,7 +634,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
             }
         }
     }
-    PH3(5);
+    PH(g_phase_k3, 5);
     if (threadIdx.x == 0) {
         tile_info[tile] = make_uint2(QUANT ? base : (a == 0xFFFFFFFFu ? 0u : a), c_t);   // (QUANT: a == 0; where the tile's centroids start)
         if (c_t) atomicAdd(&grp_cnt[tile >> 6], c_t);
@@ -699,7 +672,7 @@ __global__ __launch_bounds__(256) void k3_compact(const CmFrameState* __restrict
         return;
     }
     // The kernels behind pass 0 may have been launched for fewer records than the frame's slots (a crop box that dropped
-    // most points of the last frame: cm_api.cpp launch_bucket): more records than that, and the frame is handed back.
+    // most points of the last frame: cm_launch.cpp launch_bucket): more records than that, and the frame is handed back.
     if (tile == 0 && threadIdx.x == 0 && n_lt > gridDim.x) host_state[offsetof(CmFrameState, err) / 4] = CM_DEV_ERR_GRID;
     if (tile >= n_lt) return;
     const uint2 info = tile_info[tile];
@@ -733,8 +706,7 @@ __global__ __launch_bounds__(256) void k3_compact(const CmFrameState* __restrict
 }  // namespace
 #ifdef CM_PHASE_TIMING
 extern "C" __attribute__((visibility("default"))) void cm_debug_phases3(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase3), sizeof(unsigned long long) * 16 * 4096);
-    if (reset) { void* p_; (void)hipGetSymbolAddress(&p_, HIP_SYMBOL(g_phase3)); (void)hipMemset(p_, 0, sizeof(unsigned long long) * 16 * 4096); }
+    phase_readout(HIP_SYMBOL(g_phase_k3), out, reset);
 }
 #endif
 

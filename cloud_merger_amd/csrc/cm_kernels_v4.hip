@@ -32,24 +32,6 @@
 
 namespace {
 
-template <int WAVES>
-__device__ __forceinline__ uint32_t block_excl_scan4(uint32_t v, uint32_t* lds, uint32_t* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan_u32(v, lane);
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < WAVES; ++k) {
-        const uint32_t c = lds[k];
-        if (k < w) woff += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + incl - v;
-}
-
 // Bucket of an index = the number of splitters S[1 .. CM4_BINS - 1] that are <= key (S[0] = 0 is below every index; S is
 // ascending, 0xFFFFFFFF beyond the frame's buckets; an index is below 2^31: the host only takes this path for key_bits < 32).
 // The splitters sit in LDS as a perfect binary tree in breadth-first order (node i: children 2i + 1, 2i + 2; node of level l,
@@ -96,61 +78,9 @@ __device__ __forceinline__ size_t cnt_at(uint32_t tile, uint32_t word, uint32_t 
     return (static_cast<size_t>(word >> 3) * n_tiles + tile) * 8u + (word & 7u);
 }
 
-// The exact bounds of the frame's valid points from the per-tile records (see fold_bounds, cm_kernels_v2.hip).
-__device__ __forceinline__ void fold_bounds4(float* s_f, CmFrameState* __restrict__ st, const float* __restrict__ records,
-                                             uint32_t n_records) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float inf = __uint_as_float(0x7F800000u);
-    float v[6] = {inf, inf, inf, -inf, -inf, -inf};
-    uint32_t cnt = 0;
-    for (uint32_t r = threadIdx.x; r < n_records; r += CM2_BLOCK) {
-        const float4 lo = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8);
-        const float4 hi = *reinterpret_cast<const float4*>(records + static_cast<size_t>(r) * 8 + 4);
-        v[0] = fminf(v[0], lo.x); v[1] = fminf(v[1], lo.y); v[2] = fminf(v[2], lo.z);
-        v[3] = fmaxf(v[3], lo.w); v[4] = fmaxf(v[4], hi.x); v[5] = fmaxf(v[5], hi.y);
-        cnt += __float_as_uint(hi.z);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = fminf(v[k], __shfl_xor(v[k], d));
-#pragma unroll
-        for (int k = 3; k < 6; ++k) v[k] = fmaxf(v[k], __shfl_xor(v[k], d));
-        cnt += __shfl_xor(cnt, d);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s_f[w * 8 + k] = v[k];
-        s_f[w * 8 + 6] = __uint_as_float(cnt);
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int k = threadIdx.x;
-        if (k < 6) {
-            float r = s_f[k];
-            for (int q = 1; q < CM2_WAVES; ++q) r = (k < 3) ? fminf(r, s_f[q * 8 + k]) : fmaxf(r, s_f[q * 8 + k]);
-            if (k < 3) st->min_p[k] = r; else st->max_p[k - 3] = r;
-        } else {
-            uint32_t c = 0;
-            for (int q = 0; q < CM2_WAVES; ++q) c += __float_as_uint(s_f[q * 8 + 6]);
-            st->n_valid_k0 = c;
-        }
-    }
-}
-
-// Phase timing of k4_hist (scripts/phase_times4.py; build with CM_PHASE_TIMING=1): thread 0 of every workgroup adds up the
-// 100 MHz ticks it spends in each phase over its tiles (word 15: its tiles). The timed build waits for the loads where the
-// product lets them fly. Compiled out of the product build.
-#ifdef CM_PHASE_TIMING
-__device__ unsigned long long g_phase4[4096 * 16];
-#define PH4_START() long long t0_ = wall_clock64()
-#define PH4(k) do { if (threadIdx.x == 0) { const long long t1_ = wall_clock64(); g_phase4[(blockIdx.x & 4095) * 16 + (k)] += (unsigned long long)(t1_ - t0_); t0_ = t1_; } } while (0)
-#define PH4_LOADS_BACK() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define PH4_START() do {} while (0)
-#define PH4(k) do {} while (0)
-#define PH4_LOADS_BACK() do {} while (0)
-#endif
+// Phase timing of k4_hist (scripts/phase_times4.py; cm_common.hpp): the ticks it spends in each phase, added up over its
+// tiles (word 15: its tiles).
+CM_PHASE_DECLARE(g_phase_k4);
 
 // ------------------------------------------------------------------------------------------------
 // k4_hist: what k2_hist0 does for the fixed-grid passes (frame set-up, clears, box check, min/max records), with the
@@ -177,72 +107,37 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmF
     __shared__ float s_mm[CM2_WAVES][6];
     __shared__ uint32_t s_cnt[CM2_WAVES];
     __shared__ uint32_t s_out;
-    PH4_START();
+    PH_START();
     const CmFrameDev* __restrict__ fd = &fv;
-    auto entry = [&](uint32_t t, CmTileDev& e) {          // where tile t's points lie (k_setup's arithmetic)
-        const uint32_t first = t * CM_TILE;
-        uint32_t k = 0;
-        for (uint32_t q = 1; q < fv.n_sensors; ++q) k += (first >= fv.s[q].base) ? 1u : 0u;
-        const CmSensorDev& sd0 = fv.s[k];
-        const uint32_t off = first - sd0.base;
-        e.data = sd0.data + static_cast<size_t>(off) * sd0.point_step;
-        e.n_left = sd0.n > off ? sd0.n - off : 0u;
-        e.info = k | (sd0.layout << 8);
-    };
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t first = w * (64 * CM2_ITEMS) + lane;   // the thread's first slot in a tile
     uint32_t tile = blockIdx.x;
-    CmTileDev te;
-    entry(tile, te);
+    CmTileDev te = tile_entry(fv, tile);
     Pt3 p[H] = {};                                        // the half-tile in flight
     load_tile_xyz_aligned<H>(te, first, p);
     load_splitter_tree<LEVELS>(spl, spl_g);
-    if (do_setup) {
-        static_assert(sizeof(CmFrameDev) % 4 == 0 && sizeof(CmFrameDev) / 4 <= CM2_BLOCK, "one word of the descriptor per thread");
-        if (blockIdx.x == 0 && threadIdx.x < sizeof(CmFrameDev) / 4)
-            reinterpret_cast<uint32_t*>(fd_dst)[threadIdx.x] = reinterpret_cast<const uint32_t*>(&fv)[threadIdx.x];
-    }
+    if (do_setup && blockIdx.x == 0) store_frame_desc(fv, fd_dst);
     for (uint32_t k = blockIdx.x * CM2_BLOCK + threadIdx.x; k < n_tile_state; k += gridDim.x * CM2_BLOCK) tile_state[k] = 0ull;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {           // the box and its grid, as the host set them up
-        st->status = CM_DEV_OK;
-        for (int a = 0; a < 3; ++a) {
-            st->min_p[a] = grid_mode == 2 ? fd->ext_min[a] : fd->crop_min[a];
-            st->max_p[a] = grid_mode == 2 ? fd->ext_max[a] : fd->crop_max[a];
-            const int32_t mb = fd->box_min_b[a], db = fd->box_div_b[a];
-            st->min_b[a] = mb; st->max_b[a] = mb + db - 1;
-            st->div_b[a] = db;
-        }
-        st->key_bits = fd->box_key_bits;
-        st->n_passes = 1u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        init_box_state(st, fd, grid_mode, 0, 1u, CM_DEV_OK);
         if (big_list) big_list[0] = 0u;                    // (k4_colscan's list of buckets for the large finish shape)
     }
     const BoxGrid b = box_grid_of(fd);
     const bool predicted = check_box != 0;
-    const uint32_t crop = fd->crop_enable;
-    float cmn0 = 0.f, cmn1 = 0.f, cmn2 = 0.f, cmx0 = 0.f, cmx1 = 0.f, cmx2 = 0.f;
-    if (crop) {
-        cmn0 = fd->crop_min[0]; cmn1 = fd->crop_min[1]; cmn2 = fd->crop_min[2];
-        cmx0 = fd->crop_max[0]; cmx1 = fd->crop_max[1]; cmx2 = fd->crop_max[2];
-    }
+    const CropBox crop = load_crop(fd);
 #pragma unroll
     for (int q = 0; q < CM4_BINS / 2 / CM2_BLOCK; ++q) lh[q * CM2_BLOCK + threadIdx.x] = 0;
     if (threadIdx.x == 0) s_out = 0;
     __syncthreads();
-    PH4(0);
-    const float inf = __uint_as_float(0x7F800000u);
+    PH_ACC(g_phase_k4, 0);
     for (;;) {
         const uint32_t tile_n = tile + gridDim.x;
         const bool more = tile_n < n_tiles;
         CmTileDev ten = te;
         float m[12];
-        {
-            const CmSensorDev& sd = fd->s[te.info & 0xFFu];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
-        }
+        load_matrix(fd->s[te.info & 0xFFu], m);
         if (do_setup && threadIdx.x == 0) tiles_dst[tile] = te;
-        float mn0 = inf, mn1 = inf, mn2 = inf, mx0 = -inf, mx1 = -inf, mx2 = -inf;
-        uint32_t cnt_ok = 0;
+        MinMax3 mm;
         bool any_out = false;
         const uint32_t slot0 = tile * CM_TILE + first;
 #pragma unroll
@@ -252,18 +147,16 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmF
             uint32_t fs = first;                                   // (opaque: the loads' offsets are formed where they are used —
             asm volatile("" : "+v"(fs));                           //  hoisted out of the tile loop they stay live across it and spill)
             load_tile_xyz_generic<H>(te, fd->s[te.info & 0xFFu], fs + h * (H * 64), p);   // (a generic layout: fetched here)
-            PH4_LOADS_BACK();
-            PH4(1);
+            PH_LOADS_BACK();
+            PH_ACC(g_phase_k4, 1);
             {
                 float tx[H], ty[H], tz[H];
 #pragma unroll
                 for (int r = 0; r < H; ++r) {
-                    const float x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-                    const float y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-                    const float z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+                    float x, y, z;
+                    xf_point(m, p[r], x, y, z);
                     tx[r] = x; ty[r] = y; tz[r] = z;
-                    bool ok = finite_f32(x) & finite_f32(y) & finite_f32(z);
-                    if (crop) ok = ok & !((x < cmn0) | (x > cmx0) | (y < cmn1) | (y > cmx1) | (z < cmn2) | (z > cmx2));
+                    const bool ok = valid_point(x, y, z, crop);
                     bool in;
                     key[r] = key_of(b, x, y, z, &in);
                     if (predicted) any_out = any_out | (ok & !in);     // a crop box holds every valid point by construction
@@ -271,34 +164,16 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmF
                     okm |= ok ? (1u << r) : 0u;
                     keepm |= (ok & in) ? (1u << r) : 0u;
                 }
-                if (predicted) {                                   // (here, so that the coordinates are dead before the next loads go out)
-                    cnt_ok += static_cast<uint32_t>(__builtin_popcount(okm));
-                    if (__ballot(okm != (1u << H) - 1u) == 0ull) {
-#pragma unroll
-                        for (int r = 0; r < H; r += 2) {
-                            mn0 = fminf(fminf(mn0, tx[r]), tx[r + 1]); mx0 = fmaxf(fmaxf(mx0, tx[r]), tx[r + 1]);
-                            mn1 = fminf(fminf(mn1, ty[r]), ty[r + 1]); mx1 = fmaxf(fmaxf(mx1, ty[r]), ty[r + 1]);
-                            mn2 = fminf(fminf(mn2, tz[r]), tz[r + 1]); mx2 = fmaxf(fmaxf(mx2, tz[r]), tz[r + 1]);
-                        }
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < H; ++r) {
-                            const bool ok = (okm >> r) & 1u;
-                            mn0 = fminf(mn0, ok ? tx[r] : inf); mx0 = fmaxf(mx0, ok ? tx[r] : -inf);
-                            mn1 = fminf(mn1, ok ? ty[r] : inf); mx1 = fmaxf(mx1, ok ? ty[r] : -inf);
-                            mn2 = fminf(mn2, ok ? tz[r] : inf); mx2 = fmaxf(mx2, ok ? tz[r] : -inf);
-                        }
-                    }
-                }
+                if (predicted) mm.add(tx, ty, tz, okm);            // (here, so that the coordinates are dead before the next loads go out)
             }
             // the next half-tile's loads: the second half of this tile, or the first of the workgroup's next one
             if (h == 0) {
                 load_tile_xyz_aligned<H>(te, fs + H * 64, p);
             } else if (more) {
-                entry(tile_n, ten);
+                ten = tile_entry(fv, tile_n);
                 load_tile_xyz_aligned<H>(ten, fs, p);
             }
-            PH4(2);
+            PH_ACC(g_phase_k4, 2);
             buckets_of<LEVELS, H>(spl, key, bk);
 #pragma unroll
             for (int r = 0; r < H; ++r) {
@@ -311,21 +186,14 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmF
                 // the bucket of every slot (0xFFFF: no record), so that k4_scatter neither tests nor searches a second time
                 bid[slot0 + (h * H + r) * 64] = static_cast<uint16_t>(keep ? bk[r] : 0xFFFFu);
             }
-            PH4(3);
+            PH_ACC(g_phase_k4, 3);
         }
         if (predicted) {
             if (any_out) s_out = 1u;
-            mn0 = wave_min_f32_l63(mn0); mn1 = wave_min_f32_l63(mn1); mn2 = wave_min_f32_l63(mn2);
-            mx0 = wave_max_f32_l63(mx0); mx1 = wave_max_f32_l63(mx1); mx2 = wave_max_f32_l63(mx2);
-            cnt_ok = wave_sum_u32(cnt_ok);
-            if (lane == 63) {
-                s_mm[w][0] = mn0; s_mm[w][1] = mn1; s_mm[w][2] = mn2;
-                s_mm[w][3] = mx0; s_mm[w][4] = mx1; s_mm[w][5] = mx2;
-                s_cnt[w] = cnt_ok;
-            }
+            mm.fold_wave(s_mm, s_cnt, w, lane);
         }
         __syncthreads();
-        PH4(4);
+        PH_ACC(g_phase_k4, 4);
         uint32_t tx_ = threadIdx.x;                            // (opaque, as the loads' offsets: the addresses below are per-tile work)
         asm volatile("" : "+v"(tx_));
         // The counts go out in column blocks of eight words (cnt_at): k4_colscan then streams one contiguous block per
@@ -335,23 +203,9 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_hist(const CmFrameDev fv, CmF
             cnt[cnt_at(tile, q * CM2_BLOCK + tx_, n_tiles)] = lh[q * CM2_BLOCK + tx_];
             lh[q * CM2_BLOCK + tx_] = 0;
         }
-        if (predicted && tx_ < 8) {                    // record: min xyz, max xyz, count, pad
-            const int k = tx_;
-            float v = 0.f;
-            if (k < 6) {
-                v = s_mm[0][k];
-                for (int q = 1; q < CM2_WAVES; ++q) v = (k < 3) ? fminf(v, s_mm[q][k]) : fmaxf(v, s_mm[q][k]);
-            } else if (k == 6) {
-                uint32_t c = 0;
-                for (int q = 0; q < CM2_WAVES; ++q) c += s_cnt[q];
-                v = __uint_as_float(c);
-            }
-            records[static_cast<size_t>(tile) * 8 + k] = v;
-        }
-        PH4(5);
-#ifdef CM_PHASE_TIMING
-        if (threadIdx.x == 0) g_phase4[(blockIdx.x & 4095) * 16 + 15] += 1ull;
-#endif
+        if (predicted && tx_ < 8) records[static_cast<size_t>(tile) * 8 + tx_] = MinMax3::record_word<CM2_WAVES>(s_mm, s_cnt, tx_);
+        PH_ACC(g_phase_k4, 5);
+        PH_COUNT(g_phase_k4, 15);
         if (!more) break;
         __syncthreads();                                       // (the cleared counters, the read records: before the next tile's)
         te = ten; tile = tile_n;
@@ -466,15 +320,11 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
     uint16_t* sbk = reinterpret_cast<uint16_t*>(buf + STG * 4);
     if (st->status != CM_DEV_OK) return;
     if (st->outside) {                                     // handed back — with the cloud's exact bounds (see k2_scatter)
-        if (fold && blockIdx.x == 0) fold_bounds4(reinterpret_cast<float*>(buf), st, records, n_records);
+        if (fold && blockIdx.x == 0) fold_bounds(reinterpret_cast<float*>(buf), st, records, n_records);
         return;
     }
     if (st->quant_abort) return;
-    uint32_t tile = blockIdx.x;
-    {
-        const uint32_t per = gridDim.x / 8;              // contiguous tile range per XCD
-        if (blockIdx.x < per * 8) tile = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-    }
+    const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 
     const CmTileDev te = tiles[tile];
@@ -494,14 +344,11 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
     {
         const CmSensorDev& sd = fd->s[sidx];
         float m[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) m[k] = sd.m[k];
+        load_matrix(sd, m);
         const bool all_fields = fd->downsample_all != 0;
 #pragma unroll
         for (int r = 0; r < CM2_ITEMS; ++r) {
-            rec[r].x = xf_row(m[0], m[1], m[2], m[3], p[r].x, p[r].y, p[r].z);
-            rec[r].y = xf_row(m[4], m[5], m[6], m[7], p[r].x, p[r].y, p[r].z);
-            rec[r].z = xf_row(m[8], m[9], m[10], m[11], p[r].x, p[r].y, p[r].z);
+            xf_point(m, p[r], rec[r].x, rec[r].y, rec[r].z);
             rec[r].w = all_fields ? p[r].i : 0.f;
             vmask |= (bk[r] != 0xFFFFu) ? (1u << r) : 0u;
             bk[r] &= SUB ? (CM4_MAX_BUCKETS - 1) : (CM4_BINS - 1);
@@ -544,9 +391,9 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
         c4[0] += cwq.x & 0xFFFFu; c4[1] += cwq.x >> 16; c4[2] += cwq.y & 0xFFFFu; c4[3] += cwq.y >> 16;
     }
     uint32_t tile_valid, n_total;
-    const uint32_t db = block_excl_scan4<CM2_WAVES>(c4[0] + c4[1] + c4[2] + c4[3], lds, &tile_valid);
+    const uint32_t db = block_excl_scan<CM2_WAVES>(c4[0] + c4[1] + c4[2] + c4[3], lds, &tile_valid);
     const uint32_t t4[4] = {tot4.x, tot4.y, tot4.z, tot4.w};
-    const uint32_t gb = block_excl_scan4<CM2_WAVES>(t4[0] + t4[1] + t4[2] + t4[3], lds, &n_total);
+    const uint32_t gb = block_excl_scan<CM2_WAVES>(t4[0] + t4[1] + t4[2] + t4[3], lds, &n_total);
     {
         const uint32_t pre[4] = {trow.x & 0xFFFFu, trow.x >> 16, trow.y & 0xFFFFu, trow.y >> 16};
         uint32_t d = db, g = gb;
@@ -601,7 +448,7 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
     // The exact bounds of the cloud (pcl::getMinMax3D) for the result and for the next frame's box.
     if (fold && tile == 0) {
         __syncthreads();
-        fold_bounds4(reinterpret_cast<float*>(buf), st, records, n_records);
+        fold_bounds(reinterpret_cast<float*>(buf), st, records, n_records);
     }
 }
 
@@ -609,12 +456,9 @@ __global__ __launch_bounds__(CM2_BLOCK, 6) void k4_scatter(const CmFrameDev* __r
 
 #ifdef CM_PHASE_TIMING
 extern "C" __attribute__((visibility("default"))) void cm_debug_phases4(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase4), sizeof(unsigned long long) * 16 * 4096);
-    if (reset) { void* p_; (void)hipGetSymbolAddress(&p_, HIP_SYMBOL(g_phase4)); (void)hipMemset(p_, 0, sizeof(unsigned long long) * 16 * 4096); }
+    phase_readout(HIP_SYMBOL(g_phase_k4), out, reset);
 }
 #endif
-
-
 
 // What of k4_hist<L> is resident at once on the current device: workgroups per CU (asked of the runtime) times its CUs.
 template <int L>
