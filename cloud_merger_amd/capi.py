@@ -44,6 +44,7 @@ SYMBOLS = [
     "cm_result_voxel_cov", "cm_result_voxel_cov_device",
     "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
     "cm_result_clusters", "cm_result_clusters_device",
+    "cm_result_normals", "cm_result_normals_device",
 ]
 MAX_ZONES = 8
 
@@ -162,6 +163,20 @@ CLUSTER_DTYPE = np.dtype([("first", "<u4"), ("n_voxels", "<u4"), ("n_points", "<
 assert CLUSTER_DTYPE.itemsize == C.sizeof(Cluster) == 40 and C.sizeof(ClusterParams) == 16
 
 
+# normals and curvature of the result (cm_result_normals)
+NORMAL_MAX_K = 64
+NORMAL_VALID = 1
+
+
+class NormalParams(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("viewpoint", C.c_float * 3), ("search_cell", C.c_float), ("_pad", C.c_uint32)]
+
+
+VOXEL_NORMAL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("curvature", "<f4"), ("r2_k", "<f4"), ("n_neighbors", "<u4"),
+                               ("last", "<u4"), ("flags", "<u4")])
+assert VOXEL_NORMAL_DTYPE.itemsize == 32 and C.sizeof(NormalParams) == 24
+
+
 def sym6_to_3x3(a):
     """(..., 6) lower-triangle entries in cm_voxel_cov order -> (..., 3, 3) symmetric matrices."""
     a = np.asarray(a)
@@ -270,6 +285,8 @@ def load():
     L.cm_result_clusters.argtypes = [vp, C.POINTER(ClusterParams), vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.cm_result_clusters_device.argtypes = [vp, C.POINTER(ClusterParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                             C.POINTER(u64), C.POINTER(u64)]
+    L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
+    L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -576,6 +593,23 @@ class CloudMerger:
         self._check(self._lib.cm_result_clusters_device(self._ctx, C.byref(p), C.byref(lp), C.byref(cp), C.byref(ip), C.byref(nc),
                                                         C.byref(nm)), "cm_result_clusters_device")
         return lp.value, cp.value, ip.value, nc.value, nm.value
+
+    # ---- normals and curvature of the last result (cm_result_normals) ----
+    def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):
+        """(n_out,) VOXEL_NORMAL_DTYPE array: entry i belongs to result record i (pcl::NormalEstimation with setKSearch(k),
+        neighbours by (distance, result index), turned towards the viewpoint)."""
+        p = NormalParams(int(k), (C.c_float * 3)(*[float(v) for v in viewpoint]), float(search_cell), 0)
+        _, n_out = self.result_device()
+        out = np.empty(max(int(n_out), 1), dtype=VOXEL_NORMAL_DTYPE)
+        self._check(self._lib.cm_result_normals(self._ctx, C.byref(p), out.ctypes.data, out.shape[0]), "cm_result_normals")
+        return out[: int(n_out)].copy()
+
+    def normals_device(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):
+        """(device pointer, entries) of the same table, owned by the context and valid until the next merge or the next call."""
+        p = NormalParams(int(k), (C.c_float * 3)(*[float(v) for v in viewpoint]), float(search_cell), 0)
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self._check(self._lib.cm_result_normals_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)), "cm_result_normals_device")
+        return ptr.value, n.value
 
     # ---- statistical outlier removal before the voxel grid (cm_set_statistical_outlier) ----
     def set_statistical_outlier(self, mean_k, std_mul=1.0, search_cell=0.0):

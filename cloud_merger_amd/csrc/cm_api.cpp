@@ -52,6 +52,8 @@ void free_all(cm_ctx* c) {
     F(c->cl_keys_a); F(c->cl_keys_b); F(c->cl_vals_a); F(c->cl_vals_b); F(c->cl_hist); F(c->cl_grp); F(c->cl_parent); F(c->cl_root);
     F(c->cl_size); F(c->cl_npts); F(c->cl_num); F(c->cl_labels); F(c->cl_pts); F(c->cl_tile_sums); F(c->cl_rows); F(c->cl_words);
     F(c->cl_state); F(c->cl_clusters);
+    F(c->nrm_keys_a); F(c->nrm_keys_b); F(c->nrm_vals_a); F(c->nrm_vals_b); F(c->nrm_hist); F(c->nrm_grp); F(c->nrm_aux);
+    F(c->nrm_pts); F(c->nrm_list); F(c->nrm_rows); F(c->nrm_words); F(c->nrm_state); F(c->nrm_entries);
     F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
@@ -132,17 +134,34 @@ int voxel_cov_check(cm_ctx* c, const cm_cov_params* p, cm_cov_params* q) {
 }
 
 // The refusals of cm_result_clusters*: CM_OK when the last result can be clustered with *p. Caller holds merge_mu.
-int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
-    if (!p) return fail(c, CM_BAD_ARG, "no cluster parameters");
+// The refusals the tables computed from the last result's centroids share: CM_OK when there is such a result at rest.
+int centroid_result_check(cm_ctx* c) {
     if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
     if (!c->have_result) return fail(c, CM_BAD_ARG, "no result");
     if (c->last_mode != 0) return fail(c, CM_BAD_ARG, "the last result is a partial or merged table (cm_merge_partial / cm_merge_tables)");
     if (c->result.status != CM_OK) return fail(c, CM_BAD_ARG, std::string("last frame has no voxel grid (") + k_status_names(c->result.status) + ")");
+    return CM_OK;
+}
+
+int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
+    if (!p) return fail(c, CM_BAD_ARG, "no cluster parameters");
+    if (const int e = centroid_result_check(c)) return e;
     if (!std::isfinite(p->tolerance) || !(p->tolerance > 0.0f)) return fail(c, CM_BAD_ARG, "tolerance must be finite and > 0");
     const float t2 = p->tolerance * p->tolerance;
     if (!std::isfinite(t2) || !(t2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of the tolerance must be finite and > 0");
     if (p->min_cluster_size == 0) return fail(c, CM_BAD_ARG, "min_cluster_size must be at least 1");
     if (p->min_cluster_size > p->max_cluster_size) return fail(c, CM_BAD_ARG, "min_cluster_size exceeds max_cluster_size");
+    return CM_OK;
+}
+
+// The refusals of cm_result_normals*: CM_OK when the last result's normals can be computed with *p. Caller holds merge_mu.
+int normals_check(cm_ctx* c, const cm_normal_params* p) {
+    if (!p) return fail(c, CM_BAD_ARG, "no normal parameters");
+    if (const int e = centroid_result_check(c)) return e;
+    if (p->k < 3 || p->k > CM_NORMAL_MAX_K) return fail(c, CM_BAD_ARG, "k must be in 3..CM_NORMAL_MAX_K");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(p->viewpoint[a])) return fail(c, CM_BAD_ARG, "the viewpoint must be finite");
+    if (!std::isfinite(p->search_cell) || p->search_cell < 0.0f) return fail(c, CM_BAD_ARG, "search_cell must be finite and >= 0");
     return CM_OK;
 }
 
@@ -624,6 +643,38 @@ int cm_result_clusters_device(cm_ctx* c, const cm_cluster_params* p, const void*
     *indices = c->cl_n_clustered ? c->cl_indices : nullptr;
     *n_clusters = c->cl_n_clusters;
     *n_clustered = c->cl_n_clustered;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");
+static_assert(CM_NORMAL_VALID == CM_NORMAL_VALID_DEV && CM_NORMAL_MAX_K == 64, "the kernels' flag and largest list");
+
+int cm_result_normals(cm_ctx* c, const cm_normal_params* p, cm_voxel_normal* host_dst, uint64_t capacity) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = normals_check(c, p);
+    if (e != CM_OK) return e;
+    const uint64_t n = c->result.n_out;
+    if (n > capacity) return fail(c, CM_CAPACITY, "normals destination too small");
+    if (n && !host_dst) return fail(c, CM_BAD_ARG, "null destination");
+    e = normals(c, *p);
+    if (e != CM_OK || n == 0) return e;
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->nrm_entries, n * sizeof(cm_voxel_normal), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_voxel_normal);
+    return CM_OK;
+}
+
+int cm_result_normals_device(cm_ctx* c, const cm_normal_params* p, const void** dev_ptr, uint64_t* n) {
+    if (!c || !dev_ptr || !n) return CM_BAD_ARG;
+    *dev_ptr = nullptr;
+    *n = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = normals_check(c, p);
+    if (e == CM_OK) e = normals(c, *p);
+    if (e != CM_OK) return e;
+    *dev_ptr = c->result.n_out ? c->nrm_entries : nullptr;
+    *n = c->result.n_out;
     return CM_OK;
 }
 

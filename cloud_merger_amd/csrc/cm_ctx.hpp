@@ -188,6 +188,21 @@ struct cm_ctx {
     const uint32_t* cl_indices = nullptr;   // the member lists of the last call (one of cl_vals_a / cl_vals_b)
     uint64_t cl_n_clusters = 0, cl_n_clustered = 0;
 
+    // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
+    // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
+    uint32_t nrm_cap_slots = 0;          // words of each per-voxel buffer (a multiple of CM_TILE)
+    uint32_t *nrm_keys_a = nullptr, *nrm_keys_b = nullptr, *nrm_vals_a = nullptr, *nrm_vals_b = nullptr;
+    uint32_t *nrm_hist = nullptr, *nrm_grp = nullptr;
+    uint32_t* nrm_aux = nullptr;         // 3 x nrm_cap_slots words: what k_cl_gather initialises for the cluster call (unused here)
+    void* nrm_pts = nullptr;             // the centroids in search-grid order (x, y, z, result index)
+    void* nrm_list = nullptr;            // nrm_cap_slots x 8 B: the centroids the first search launch could not finish
+    void* nrm_rows = nullptr;            // (y,z)-row ranges of the search grid
+    uint64_t nrm_cap_rows = 0;
+    uint32_t* nrm_words = nullptr;       // [0] list count, [2..7] bounds images, [8..263] digit totals (k_gscan)
+    CmFrameState* nrm_state = nullptr;   // the sort's state record
+    void* nrm_entries = nullptr;         // the table: cm_voxel_normal per voxel (nrm_cap_slots entries)
+    uint32_t nrm_n_listed = 0;           // centroids the last call's second launch took
+
     // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
     // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
     bool sor_on = false;
@@ -241,3 +256,5 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 // The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
 int clusters(cm_ctx* c, const cm_cluster_params& q);
+// The normal table of the last result (nrm_entries, n_out entries).
+int normals(cm_ctx* c, const cm_normal_params& q);

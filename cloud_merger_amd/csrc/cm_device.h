@@ -234,3 +234,7 @@ struct CmClusterDev {
     uint32_t first, n_voxels, n_points, _pad;
     uint32_t lo[3], hi[3];
 };
+
+// Normals of the result (cm_kernels_normals.hip): the search grid is a CmClusterGridDev; an entry (== cm_voxel_normal, 32
+// bytes) is written as two 16-byte words; the flag == CM_NORMAL_VALID.
+#define CM_NORMAL_VALID_DEV 1u

@@ -179,3 +179,11 @@ void cmk_cl_labels(hipStream_t s, const void* recs, const uint32_t* root, const 
                    CmFrameState* st, uint32_t* labels, uint32_t* keys, uint32_t* hist, uint32_t* grp, void* clusters,
                    uint32_t n_tiles);
 void cmk_cl_decode(hipStream_t s, void* clusters, uint32_t n_clusters);     // AABB images -> floats
+
+// ---- normals and curvature of the last result (cm_kernels_normals.hip) ----------------------------------------------------
+// After cmk_cl_gather and cmk_sorted_rows on st's grid g: the exact k nearest neighbours of every centroid by (d2, result
+// index) and its entry (32 bytes at its result index in out). first: the 3x3x3 cells around each of the n centroids, the
+// unfinished ones onto list (*list_n, zeroed before); then n_items = *list_n of them ring by ring. n_items 0: no launch.
+void cmk_nrm_knn(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
+                 const void* rows, const void* recs, const CmClusterGridDev& g, uint32_t n, uint32_t k, const float viewpoint[3],
+                 void* out, void* list, uint32_t* list_n, uint32_t n_items, bool first);

@@ -1154,3 +1154,103 @@ int clusters(cm_ctx* c, const cm_cluster_params& q) {
     c->cl_indices = (passes_num & 1u) ? c->cl_vals_b : c->cl_vals_a;
     return CM_OK;
 }
+
+// Normals and curvature of the last result (cm_kernels_normals.hip): one cm_voxel_normal per result record into nrm_entries.
+// The cluster call's front end — bounds, the search grid decided on the host (normals_grid), keys, radix passes, gather, row
+// table — on buffers and a state record of this call's own, then the exact k-nearest-neighbour search in two launches. Reads
+// `out` and writes only the nrm_* buffers: nothing a later frame reads. Two host round trips: the bounds of the centroids
+// and the length of the second launch's list (an empty list costs no launch). Under CM_FLAG_PROFILE the stage times of the
+// call replace the frame's in cm_get_stage_times; the second launch's stage is named "k_nrm_rings n=<centroids it took>".
+int normals(cm_ctx* c, const cm_normal_params& q) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    c->nrm_n_listed = 0;
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
+    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    if (n_slots > c->nrm_cap_slots) {
+        uint32_t** words[] = {&c->nrm_keys_a, &c->nrm_keys_b, &c->nrm_vals_a, &c->nrm_vals_b, &c->nrm_hist, &c->nrm_grp, &c->nrm_aux};
+        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
+        void** blocks[] = {&c->nrm_pts, &c->nrm_list, &c->nrm_entries};
+        for (void** b : blocks) if (*b) { (void)hipFree(*b); *b = nullptr; }
+        c->nrm_cap_slots = 0;
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->nrm_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->nrm_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->nrm_aux), static_cast<size_t>(n_slots) * 12);
+        ok = ok && A(&c->nrm_pts, static_cast<size_t>(n_slots) * 16);
+        ok = ok && A(&c->nrm_list, static_cast<size_t>(n_slots) * 8);
+        ok = ok && A(&c->nrm_entries, static_cast<size_t>(n_slots) * sizeof(cm_voxel_normal));
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's buffers");
+        c->nrm_cap_slots = n_slots;
+    }
+    if (!c->nrm_state) {
+        bool ok = A(reinterpret_cast<void**>(&c->nrm_state), sizeof(CmFrameState)) &&
+                  A(reinterpret_cast<void**>(&c->nrm_words), (8 + CM_RADIX) * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's state");
+    }
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->nrm_words;
+    SortPairs sp = {c->nrm_keys_a, c->nrm_keys_b, c->nrm_vals_a, c->nrm_vals_b, c->nrm_hist, w + 8, c->nrm_grp, c->nrm_grp + gw};
+    c->prof_used = 0;
+
+    // the search grid: over the centroids' own bounds
+    prof_mark(c, "k_cl_bounds");
+    HIP_TRY(c, hipMemsetAsync(w, 0, 8, st));
+    HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
+    HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
+    cmk_cl_bounds(st, c->out, n, w + 2);
+    uint32_t img[6];
+    HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
+    const ClusterGrid grid = normals_grid(q.search_cell, c->plan.params.leaf, q.k, mn, mx, CM_ROW_TABLE_CAP);
+    const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
+    if (n_rows > c->nrm_cap_rows) {
+        if (c->nrm_rows) { (void)hipFree(c->nrm_rows); c->nrm_rows = nullptr; c->nrm_cap_rows = 0; }
+        if (!A(&c->nrm_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's row table");
+        c->nrm_cap_rows = n_rows;
+    }
+    CmClusterGridDev gd;
+    for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
+    gd.inv = grid.inv;
+
+    // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
+    const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    HIP_TRY(c, hipMemsetAsync(c->nrm_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+    prof_mark(c, "k_cl_keys");
+    cmk_cl_keys(st, c->out, n, gd, passes, c->nrm_state, c->nrm_keys_a, c->nrm_hist, c->nrm_grp, nt);
+    radix_sort_pairs(c, c->nrm_state, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
+    prof_mark(c, "k_cl_gather");
+    cmk_cl_gather(st, c->out, c->nrm_state, c->nrm_vals_a, c->nrm_vals_b, n, c->nrm_pts, c->nrm_aux, c->nrm_aux + n_slots,
+                  c->nrm_aux + 2 * static_cast<size_t>(n_slots));
+    prof_mark(c, "cl_rows");
+    cmk_sorted_rows(st, nullptr, c->nrm_state, c->nrm_keys_a, c->nrm_vals_a, c->nrm_keys_b, c->nrm_vals_b, c->nrm_pts, c->nrm_rows,
+                    n_slots, true);
+
+    // the neighbourhoods and the planes: the 3x3x3 cells first, then whoever needs more, ring by ring
+    prof_mark(c, "k_nrm_knn(block)");
+    cmk_nrm_knn(st, c->nrm_state, c->nrm_keys_a, c->nrm_keys_b, c->nrm_pts, c->nrm_rows, c->out, gd, n, q.k, q.viewpoint,
+                c->nrm_entries, c->nrm_list, w, n, true);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t listed = 0;
+    HIP_TRY(c, hipMemcpyAsync(&listed, w, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (listed > n) return fail(c, CM_INTERNAL, "normals: the first search launch listed more centroids than the result holds");
+    if (listed) {
+        char name[24];                                    // (the stage's name carries the length of its list: 24 bytes with the NUL)
+        std::snprintf(name, sizeof name, "k_nrm_rings n=%u", listed);
+        prof_mark(c, name);
+        cmk_nrm_knn(st, c->nrm_state, c->nrm_keys_a, c->nrm_keys_b, c->nrm_pts, c->nrm_rows, c->out, gd, n, q.k, q.viewpoint,
+                    c->nrm_entries, c->nrm_list, w, listed, false);
+    }
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->nrm_n_listed = listed;
+    return CM_OK;
+}

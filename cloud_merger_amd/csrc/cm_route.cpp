@@ -77,7 +77,10 @@ float sor_bounds_cell(float cell, const float mn[3], const float mx[3], uint32_t
     return fit > 0.0f ? fit : std::numeric_limits<float>::infinity();
 }
 
-ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], uint32_t row_cap) {
+namespace {
+
+// The grid over [mn, mx] whose cell is `start` doubled until it fits (cm_route.hpp, cluster_grid).
+ClusterGrid fit_centroid_grid(float start, const float mn[3], const float mx[3], uint32_t row_cap) {
     ClusterGrid g;
     g.doublings = 0;
     float ext[3];
@@ -86,7 +89,7 @@ ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], 
         ext[a] = mx[a] - mn[a];
         finite = finite && std::isfinite(ext[a]);
     }
-    for (float cell = tolerance * 1.00390625f; finite && std::isfinite(cell); cell *= 2.0f, ++g.doublings) {
+    for (float cell = start; finite && std::isfinite(cell); cell *= 2.0f, ++g.doublings) {
         const float inv = 1.0f / cell;
         unsigned long long d[3];
         bool fits = true;
@@ -107,6 +110,22 @@ ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], 
     g.dims[0] = g.dims[1] = g.dims[2] = 1u;
     g.key_bits = 1;
     return g;
+}
+
+}  // namespace
+
+ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], uint32_t row_cap) {
+    return fit_centroid_grid(tolerance * 1.00390625f, mn, mx, row_cap);
+}
+
+ClusterGrid normals_grid(float search_cell, const float leaf[3], uint32_t k, const float mn[3], const float mx[3], uint32_t row_cap) {
+    float cell = search_cell;
+    if (!(cell > 0.0f)) {
+        float l = std::max(leaf[0], std::max(leaf[1], leaf[2]));
+        if (!(l > 0.0f) || !std::isfinite(l)) l = 1.0f;
+        cell = l * std::cbrt(static_cast<float>(k));
+    }
+    return fit_centroid_grid(cell, mn, mx, row_cap);
 }
 
 // A cloud near the limit of PCL's 32-bit index leaves no room for an eighth of its extent on every side: take what

@@ -41,6 +41,12 @@ struct ClusterGrid {
     uint32_t doublings;
 };
 ClusterGrid cluster_grid(float tolerance, const float mn[3], const float mx[3], uint32_t row_cap);
+// Normals of the result (cm_result_normals): the same kind of grid for the k-nearest-neighbour search. The cell starts at
+// search_cell, or for 0 at max(leaf) * cbrt(k): the result holds at most one centroid per voxel, so such a cell holds at most
+// about k of them and the 27 cells around a centroid on a surface (about 9 k^(2/3) voxels of it) usually hold its k nearest.
+// It doubles until the grid fits, exactly as cluster_grid's does, and an extent that overflows fp32 is one cell. The search is
+// exact for every cell: the cell sets the cost of the call, never its result.
+ClusterGrid normals_grid(float search_cell, const float leaf[3], uint32_t k, const float mn[3], const float mx[3], uint32_t row_cap);
 // The search grid of a frame (cm_launch.cpp enqueue). sor_crop_grid: over the crop box when one is on and some finite cell
 // fits it (half the row table): returns 1 (the stage's grid mode) with that cell in *cell and its key width; else 0 with
 // *cell unchanged, and the grid is over the cloud's own bounds. sor_bounds_cell: the cell over the measured bounds [mn, mx],

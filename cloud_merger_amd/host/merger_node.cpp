@@ -147,6 +147,11 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "cluster_tolerance") ok = static_cast<bool>(is >> c.cluster_tolerance) && c.cluster_tolerance >= 0.0f && std::isfinite(c.cluster_tolerance);
         else if (key == "cluster_min_size") ok = static_cast<bool>(is >> c.cluster_min_size) && c.cluster_min_size >= 1;
         else if (key == "cluster_max_size") ok = static_cast<bool>(is >> c.cluster_max_size) && c.cluster_max_size >= 1;
+        else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
+        else if (key == "normals_viewpoint") {
+            float* v = c.normals_viewpoint;
+            ok = static_cast<bool>(is >> v[0] >> v[1] >> v[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+        }
         else if (key == "motion_compensation") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.motion_compensation = v == 1; }
         else if (key == "time_field") {
             std::string name, type;
@@ -280,6 +285,18 @@ int CloudMergerNode::clusters_of_frame(const cm_result& r) {
     return CM_OK;
 }
 
+int CloudMergerNode::normals_of_frame(const cm_result& r) {
+    normals_.clear();
+    if (cfg_.normals_k == 0 || r.status != CM_OK) return CM_OK;
+    cm_normal_params q{};
+    q.k = cfg_.normals_k;
+    for (int a = 0; a < 3; ++a) q.viewpoint[a] = cfg_.normals_viewpoint[a];
+    normals_.resize(r.n_out);
+    const int st = cm_result_normals(ctx_, &q, normals_.data(), normals_.size());
+    if (st != CM_OK) { normals_.clear(); set_error(cm_last_error(ctx_)); return st; }
+    return CM_OK;
+}
+
 uint64_t CloudMergerNode::newest_stamp() const {
     uint64_t newest = 0;
     for (const auto& t : stamp_ns_) newest = std::max(newest, t.load());
@@ -362,6 +379,7 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
+    { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
     {
         cm_frame_stats fs;
         if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
@@ -463,6 +481,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
+    { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
     {
         // flag reset, :151-157 — for exactly the clouds this fuse read: a callback may have delivered the next one since
         cm_frame_stats fs;

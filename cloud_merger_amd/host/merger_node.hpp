@@ -80,6 +80,11 @@ struct NodeConfig {
     // the cluster count, until the next frame (cluster_count(), cluster_labels()).
     float cluster_tolerance = 0.0f;
     uint32_t cluster_min_size = 1, cluster_max_size = 0xFFFFFFFFu;
+    // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
+    // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
+    // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
+    uint32_t normals_k = 0;
+    float normals_viewpoint[3] = {0.0f, 0.0f, 0.0f};
     struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
     TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
@@ -96,6 +101,7 @@ struct NodeConfig {
 //   u32ns: nanoseconds, relative to the cloud's header stamp)
 //   statistical_outlier <mean_k> <std_mul> [search_cell]   (pcl::StatisticalOutlierRemoval before the voxel grid)
 //   cluster_tolerance <metres> | cluster_min_size <n> | cluster_max_size <n>   (clusters of every voxel cloud; 0: off)
+//   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
@@ -164,6 +170,8 @@ public:
     // in no cluster), in the order of the published cloud. Read from the thread that calls spin_once.
     uint64_t cluster_count() const { return n_clusters_; }
     const std::vector<uint32_t>& cluster_labels() const { return cluster_labels_; }
+    // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
+    const std::vector<cm_voxel_normal>& normals() const { return normals_; }
 
 private:
     NodeConfig cfg_;
@@ -205,6 +213,8 @@ private:
     uint64_t n_clusters_ = 0;
     std::vector<uint32_t> cluster_labels_;
     int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters when the config asks for it
+    std::vector<cm_voxel_normal> normals_;
+    int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     int enqueue_frame(bool wait, cm_result* r);   // cm_merge_voxelize(_async), with the motion of the frame set under the slot locks
 };
 

@@ -456,6 +456,53 @@ CM_API int cm_result_clusters(cm_ctx* ctx, const cm_cluster_params* p, uint32_t*
 CM_API int cm_result_clusters_device(cm_ctx* ctx, const cm_cluster_params* p, const void** labels, const void** clusters,
                                      const void** indices, uint64_t* n_clusters, uint64_t* n_clustered);
 
+/* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
+ * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
+ * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
+ * order of cm_result_copy, their x, y, z as fp32.
+ *   1. Distance. d2(i, j) = (dx*dx + dy*dy) + dz*dz, dx = c_i.x - c_j.x ..., fp32, round-to-nearest, no contraction: the
+ *      distance of the radius, statistical-outlier and cluster stages. It may be +inf; it is never NaN.
+ *   2. Neighbourhood. N_i is i itself plus the m - 1 other indices j with the smallest (d2(i, j), j) in lexicographic order,
+ *      m = min(k, n): ties in distance go to the smaller result index, exact duplicates count (at distance 0). r2_k and
+ *      last are the d2 and the index of the last of them. The table is therefore a function of the result alone.
+ *   3. Moments, in fp64, every operation rounded on its own, no contraction. Offsets e_j = double(c_j) - double(c_i) per
+ *      axis; s_a = sum e_a and S_ab = sum e_a e_b, added one neighbour after the other from 0 in the ascending (d2, j) order
+ *      of step 2 (the point itself contributes zeros); mu = s / m; C_ab = S_ab / m - mu_a mu_b for a >= b, mirrored.
+ *      (The deviation from PCL 1.8, which accumulates raw coordinates in fp32 and so cancels away from the origin — §12
+ *      records the effect; offsets about the query point are what later PCL versions use.)
+ *   4. Plane. The eigenvalues l0 <= l1 <= l2 of C by cyclic Jacobi rotations in fp64. normal: the eigenvector of l0,
+ *      normalised in fp64; curvature |l0 / (l0 + l1 + l2)|; orientation by PCL's flipNormalTowardsViewpoint: with
+ *      v = double(viewpoint) - double(c_i) a normal with n.v < 0 is negated (at n.v == 0 the sign is unspecified). The
+ *      outputs are rounded to fp32.
+ *   5. Validity. An entry is valid (CM_NORMAL_VALID) when m >= 3, l2 > 0 and every figure is finite; otherwise flags is 0
+ *      and normal and curvature are NaN. n_neighbors, r2_k and last are written in either case.
+ * Entry i belongs to result record i. The table is owned by the context and valid until the next merge or the next call.
+ * search_cell sets the cells of the search grid and with them the speed of the call, never its result. CM_FLAG_OCCUPANCY is
+ * not required. Refused with CM_BAD_ARG (cm_last_error says why): a frame in flight, no result, a result of cm_merge_partial
+ * / cm_merge_tables, a last status other than CM_OK (no voxel grid), k outside 3..CM_NORMAL_MAX_K, a viewpoint that is not
+ * finite, a search_cell that is negative or not finite. No later frame depends on whether the table was asked for; with
+ * CM_FLAG_PROFILE, cm_get_stage_times afterwards lists the stages of this call. */
+#define CM_NORMAL_MAX_K 64
+#define CM_NORMAL_VALID 1u
+typedef struct cm_normal_params {
+    uint32_t k;                        /* setKSearch: the point itself plus its k-1 nearest others; 3..CM_NORMAL_MAX_K */
+    float viewpoint[3];                /* setViewPoint, common frame; finite. PCL's default is (0,0,0) */
+    float search_cell;                 /* edge (m) of the search grid's cells: speed only, never the result; 0 = library's choice */
+    uint32_t _pad;
+} cm_normal_params;
+typedef struct cm_voxel_normal {       /* 32 bytes */
+    float normal[3];                   /* unit; NaN unless valid */
+    float curvature;                   /* lambda_0 / (lambda_0 + lambda_1 + lambda_2); NaN unless valid */
+    float r2_k;                        /* fp32 squared distance to the farthest neighbour used (0 when there is none) */
+    uint32_t n_neighbors;              /* m = min(k, n_out): points in the neighbourhood, the point itself included */
+    uint32_t last;                     /* result index of that farthest neighbour (the entry's own index when m == 1) */
+    uint32_t flags;                    /* CM_NORMAL_* */
+} cm_voxel_normal;
+/* Host copy; capacity in entries, fewer than n_out: CM_CAPACITY (nothing is computed or copied). */
+CM_API int cm_result_normals(cm_ctx* ctx, const cm_normal_params* p, cm_voxel_normal* host_dst, uint64_t capacity);
+/* The same table left in device memory owned by the context (*n entries of 32 bytes; NULL when the result is empty). */
+CM_API int cm_result_normals_device(cm_ctx* ctx, const cm_normal_params* p, const void** dev_ptr, uint64_t* n);
+
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
 CM_API int cm_host_free(void* ptr);
