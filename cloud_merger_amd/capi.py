@@ -45,6 +45,7 @@ SYMBOLS = [
     "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
     "cm_result_clusters", "cm_result_clusters_device",
     "cm_result_normals", "cm_result_normals_device",
+    "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
 ]
 MAX_ZONES = 8
 
@@ -177,6 +178,31 @@ VOXEL_NORMAL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("curvature", "<f4"), ("
 assert VOXEL_NORMAL_DTYPE.itemsize == 32 and C.sizeof(NormalParams) == 24
 
 
+# registration of a cloud against the result (cm_result_align)
+ALIGN_MAX_ITER = 64
+ALIGN_NONE = 0xFFFFFFFF
+ALIGN_PIVOT_MIN = 1e-9
+ALIGN_CONVERGED, ALIGN_MAX_ITER_HIT, ALIGN_FEW, ALIGN_SINGULAR = 1, 2, 4, 8
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("max_corr_dist", C.c_float), ("max_iterations", C.c_uint32), ("normals_k", C.c_uint32),
+                ("min_correspondences", C.c_uint32), ("trans_eps", C.c_double), ("rot_eps", C.c_double), ("guess", C.c_double * 12)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 12), ("H", C.c_double * 21), ("g", C.c_double * 6), ("sse", C.c_double), ("rms", C.c_double),
+                ("pivot", C.c_double * 3), ("n_corr", C.c_uint64), ("iterations", C.c_uint32), ("flags", C.c_uint32)]
+
+    def pose_matrix(self):
+        """(3, 4) float64 [R|t]."""
+        return np.array(self.pose[:], np.float64).reshape(3, 4)
+
+
+ALIGN_CORR_DTYPE = np.dtype([("idx", "<u4"), ("d2", "<f4")])
+assert C.sizeof(AlignParams) == 128 and C.sizeof(AlignResult) == 368 and ALIGN_CORR_DTYPE.itemsize == 8
+
+
 def sym6_to_3x3(a):
     """(..., 6) lower-triangle entries in cm_voxel_cov order -> (..., 3, 3) symmetric matrices."""
     a = np.asarray(a)
@@ -287,6 +313,9 @@ def load():
                                             C.POINTER(u64), C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
+    L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
+    L.cm_result_align_device.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
+    L.cm_align_correspondences_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -610,6 +639,51 @@ class CloudMerger:
         ptr, n = C.c_void_p(), C.c_uint64()
         self._check(self._lib.cm_result_normals_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)), "cm_result_normals_device")
         return ptr.value, n.value
+
+    # ---- registration of a cloud against the last result (cm_result_align) ----
+    @staticmethod
+    def align_params(max_corr_dist, guess=None, max_iterations=30, normals_k=10, trans_eps=1e-6, rot_eps=1e-6,
+                     min_correspondences=6):
+        g = np.eye(3, 4) if guess is None else np.asarray(guess, np.float64).reshape(3, 4)
+        return AlignParams(float(max_corr_dist), int(max_iterations), int(normals_k), int(min_correspondences), float(trans_eps),
+                           float(rot_eps), (C.c_double * 12)(*g.ravel().tolist()))
+
+    def align(self, source, max_corr_dist, guess=None, max_iterations=30, normals_k=10, trans_eps=1e-6, rot_eps=1e-6,
+              min_correspondences=6):
+        """Point-to-plane ICP of `source` — (n, 3) or (n, 4) float32, or a structured XYZI array as result() returns — against
+        the last result: an AlignResult (pose_matrix() maps source coordinates onto the result). max_iterations 0 evaluates
+        the guess alone: nearest neighbours (align_correspondences) and fitness."""
+        src = np.asarray(source)
+        if len(src) == 0:
+            rec = np.zeros((0, 4), np.float32)
+        elif src.dtype.names:
+            rec = np.ascontiguousarray(src).view(np.float32).reshape(len(src), -1)[:, :4]
+        else:
+            src = np.asarray(src, np.float32).reshape(len(src), -1)
+            rec = np.zeros((len(src), 4), np.float32)
+            rec[:, :min(src.shape[1], 4)] = src[:, :4]
+        rec = np.ascontiguousarray(rec, np.float32)
+        p = self.align_params(max_corr_dist, guess, max_iterations, normals_k, trans_eps, rot_eps, min_correspondences)
+        out = AlignResult()
+        self._check(self._lib.cm_result_align(self._ctx, C.byref(p), rec.ctypes.data if len(rec) else None, len(rec), C.byref(out)),
+                    "cm_result_align")
+        return out
+
+    def align_device(self, src_ptr, n_src, max_corr_dist, **kw):
+        """The same with n_src 16-byte records already in device memory."""
+        p = self.align_params(max_corr_dist, **kw)
+        out = AlignResult()
+        self._check(self._lib.cm_result_align_device(self._ctx, C.byref(p), C.c_void_p(src_ptr), int(n_src), C.byref(out)),
+                    "cm_result_align_device")
+        return out
+
+    def align_correspondences(self, n):
+        """(n,) ALIGN_CORR_DTYPE array of the last align call's final evaluation: entry i belongs to source record i."""
+        out = np.zeros(max(int(n), 1), dtype=ALIGN_CORR_DTYPE)
+        got = C.c_uint64()
+        self._check(self._lib.cm_align_correspondences_copy(self._ctx, out.ctypes.data, int(n), C.byref(got)),
+                    "cm_align_correspondences_copy")
+        return out[: got.value].copy()
 
     # ---- statistical outlier removal before the voxel grid (cm_set_statistical_outlier) ----
     def set_statistical_outlier(self, mean_k, std_mul=1.0, search_cell=0.0):

@@ -54,6 +54,8 @@ void free_all(cm_ctx* c) {
     F(c->cl_state); F(c->cl_clusters);
     F(c->nrm_keys_a); F(c->nrm_keys_b); F(c->nrm_vals_a); F(c->nrm_vals_b); F(c->nrm_hist); F(c->nrm_grp); F(c->nrm_aux);
     F(c->nrm_pts); F(c->nrm_list); F(c->nrm_rows); F(c->nrm_words); F(c->nrm_state); F(c->nrm_entries);
+    F(c->aln_keys_a); F(c->aln_keys_b); F(c->aln_vals_a); F(c->aln_vals_b); F(c->aln_hist); F(c->aln_grp); F(c->aln_aux);
+    F(c->aln_pts); F(c->aln_rows); F(c->aln_words); F(c->aln_state); F(c->aln_corr); F(c->aln_part); F(c->aln_sums); F(c->aln_src);
     F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
@@ -162,6 +164,26 @@ int normals_check(cm_ctx* c, const cm_normal_params* p) {
     for (int a = 0; a < 3; ++a)
         if (!std::isfinite(p->viewpoint[a])) return fail(c, CM_BAD_ARG, "the viewpoint must be finite");
     if (!std::isfinite(p->search_cell) || p->search_cell < 0.0f) return fail(c, CM_BAD_ARG, "search_cell must be finite and >= 0");
+    return CM_OK;
+}
+
+// The refusals of cm_result_align*: CM_OK when n_src records at src can be aligned to the last result with *p. Caller holds
+// merge_mu.
+int align_check(cm_ctx* c, const cm_align_params* p, const void* src, uint64_t n_src, const cm_align_result* out) {
+    if (!p) return fail(c, CM_BAD_ARG, "no alignment parameters");
+    if (!out) return fail(c, CM_BAD_ARG, "no place for the alignment's outcome");
+    if (const int e = centroid_result_check(c)) return e;
+    if (!std::isfinite(p->max_corr_dist) || !(p->max_corr_dist > 0.0f)) return fail(c, CM_BAD_ARG, "max_corr_dist must be finite and > 0");
+    const float r2 = p->max_corr_dist * p->max_corr_dist;
+    if (!std::isfinite(r2) || !(r2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of max_corr_dist must be finite and > 0");
+    if (p->normals_k < 3 || p->normals_k > CM_NORMAL_MAX_K) return fail(c, CM_BAD_ARG, "normals_k must be in 3..CM_NORMAL_MAX_K");
+    if (p->max_iterations > CM_ALIGN_MAX_ITER) return fail(c, CM_BAD_ARG, "max_iterations must be in 0..CM_ALIGN_MAX_ITER");
+    if (p->min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
+    if (!(p->trans_eps >= 0.0) || !(p->rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(p->guess[k])) return fail(c, CM_BAD_ARG, "the guess must be finite");
+    if (n_src >= (1ull << 30)) return fail(c, CM_BAD_ARG, "the source must hold fewer than 2^30 records");
+    if (n_src && !src) return fail(c, CM_BAD_ARG, "null source");
     return CM_OK;
 }
 
@@ -675,6 +697,53 @@ int cm_result_normals_device(cm_ctx* c, const cm_normal_params* p, const void** 
     if (e != CM_OK) return e;
     *dev_ptr = c->result.n_out ? c->nrm_entries : nullptr;
     *n = c->result.n_out;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_align_params) == 128 && sizeof(cm_align_result) == 368 && sizeof(cm_align_corr) == 8,
+              "cm_align_params is 128 bytes, cm_align_result 368, a correspondence 8");
+static_assert(CM_ALIGN_NONE == CM_ALIGN_NONE_DEV && offsetof(cm_align_result, H) == 96 && offsetof(cm_align_result, n_corr) == 352,
+              "the kernels' mark of no match; the outcome's layout");
+
+int cm_result_align(cm_ctx* c, const cm_align_params* p, const void* src_host, uint64_t n_src, cm_align_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    const int e = align_check(c, p, src_host, n_src, out);
+    if (e != CM_OK) return e;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_src > c->aln_cap_src_host) {
+        if (c->aln_src) { (void)hipFree(c->aln_src); c->aln_src = nullptr; c->aln_cap_src_host = 0; }
+        if (hipMalloc(&c->aln_src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's source");
+        c->aln_cap_src_host = n_src;
+    }
+    if (n_src) {
+        HIP_TRY(c, hipMemcpyAsync(c->aln_src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return align(c, *p, c->aln_src, n_src, out);
+}
+
+int cm_result_align_device(cm_ctx* c, const cm_align_params* p, const void* src_dev, uint64_t n_src, cm_align_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    const int e = align_check(c, p, src_dev, n_src, out);
+    if (e != CM_OK) return e;
+    return align(c, *p, src_dev, n_src, out);
+}
+
+int cm_align_correspondences_copy(cm_ctx* c, cm_align_corr* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!c || !n) return CM_BAD_ARG;
+    *n = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (!c->aln_have) return fail(c, CM_BAD_ARG, "no alignment since the last merge");
+    *n = c->aln_n_src;
+    if (c->aln_n_src > capacity) return fail(c, CM_CAPACITY, "correspondence destination too small");
+    if (c->aln_n_src == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "null destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->aln_corr, c->aln_n_src * sizeof(cm_align_corr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += c->aln_n_src * sizeof(cm_align_corr);
     return CM_OK;
 }
 

@@ -202,6 +202,29 @@ struct cm_ctx {
     CmFrameState* nrm_state = nullptr;   // the sort's state record
     void* nrm_entries = nullptr;         // the table: cm_voxel_normal per voxel (nrm_cap_slots entries)
     uint32_t nrm_n_listed = 0;           // centroids the last call's second launch took
+    bool nrm_have = false;               // nrm_entries holds the table of the result at rest, computed with k = nrm_k:
+    uint32_t nrm_k = 0;                  // set by normals(), cleared where a merge invalidates the result
+
+    // Registration of a source cloud against the result (cm_kernels_align.hip), on request after a frame: the cluster call's
+    // front end on buffers and a state record of its own, as the normals' — no frame reads them — allocated by the first
+    // request and grown with the results and the sources. It reads `out` and nrm_entries.
+    uint32_t aln_cap_slots = 0;          // words of each per-voxel buffer (a multiple of CM_TILE)
+    uint32_t *aln_keys_a = nullptr, *aln_keys_b = nullptr, *aln_vals_a = nullptr, *aln_vals_b = nullptr;
+    uint32_t *aln_hist = nullptr, *aln_grp = nullptr;
+    uint32_t* aln_aux = nullptr;         // 3 x aln_cap_slots words: what k_cl_gather initialises for the cluster call (unused here)
+    void* aln_pts = nullptr;             // the centroids in search-grid order (x, y, z, result index)
+    void* aln_rows = nullptr;            // (y,z)-row ranges of the search grid
+    uint64_t aln_cap_rows = 0;
+    uint32_t* aln_words = nullptr;       // [2..7] bounds images, [8..263] digit totals (k_gscan)
+    CmFrameState* aln_state = nullptr;   // the sort's state record
+    uint64_t aln_cap_src = 0;            // source records aln_corr and aln_part are sized for
+    void* aln_corr = nullptr;            // cm_align_corr per source record: the last evaluation's
+    double* aln_part = nullptr;          // CM_ALIGN_STRIDE doubles per block of 256 source records
+    double* aln_sums = nullptr;          // CM_ALIGN_SUMS doubles: what the host reads back per evaluation
+    void* aln_src = nullptr;             // cm_result_align's device copy of a host source (aln_cap_src_host records)
+    uint64_t aln_cap_src_host = 0;
+    bool aln_have = false;               // aln_corr holds the table of a call since the last merge, aln_n_src entries
+    uint64_t aln_n_src = 0;
 
     // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
     // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
@@ -258,3 +281,5 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 int clusters(cm_ctx* c, const cm_cluster_params& q);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
+// Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_corr.
+int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src, cm_align_result* out);

@@ -238,3 +238,16 @@ struct CmClusterDev {
 // Normals of the result (cm_kernels_normals.hip): the search grid is a CmClusterGridDev; an entry (== cm_voxel_normal, 32
 // bytes) is written as two 16-byte words; the flag == CM_NORMAL_VALID.
 #define CM_NORMAL_VALID_DEV 1u
+
+// Registration against the result (cm_kernels_align.hip): the search grid is a CmClusterGridDev; a correspondence
+// (== cm_align_corr, 8 bytes) is one uint2. The pose and the pivot go to k_aln_eval by value, in fp64. A block's partials:
+// CM_ALIGN_TERMS sums (the lower triangle of H row by row, g, sse) and the count as a 64-bit integer, CM_ALIGN_STRIDE
+// doubles apart.
+#define CM_ALIGN_NONE_DEV 0xFFFFFFFFu
+#define CM_ALIGN_TERMS 28
+#define CM_ALIGN_SUMS 29
+#define CM_ALIGN_STRIDE 32
+struct CmAlignPoseDev {
+    double m[12];          // row-major 3x4 [R|t]
+    double p0[3];          // the pivot
+};

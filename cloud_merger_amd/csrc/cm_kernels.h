@@ -187,3 +187,14 @@ void cmk_cl_decode(hipStream_t s, void* clusters, uint32_t n_clusters);     // A
 void cmk_nrm_knn(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
                  const void* rows, const void* recs, const CmClusterGridDev& g, uint32_t n, uint32_t k, const float viewpoint[3],
                  void* out, void* list, uint32_t* list_n, uint32_t n_items, bool first);
+
+// ---- registration of a source cloud against the last result (cm_kernels_align.hip) -----------------------------------------
+// After cmk_cl_gather and cmk_sorted_rows on st's grid g (cell >= 1.0039 r): one evaluation of `pose` over the n_src source
+// records — the correspondences (8 bytes each, at the source index) and, per aligned block of 256, the 28 sums and the count
+// (CM_ALIGN_STRIDE doubles per block). normals: the cm_voxel_normal table of the n_tgt result records recs. n_tgt 0: nothing
+// is matched and st, the keys, pts, rows, recs and normals are not read. n_src 0: no launch.
+void cmk_aln_eval(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
+                  const void* rows, const void* recs, const void* normals, const void* src, uint32_t n_src, uint32_t n_tgt,
+                  const CmClusterGridDev& g, float r2, const CmAlignPoseDev& pose, void* corr, double* partials);
+// sums[0..27]: the block partials added in ascending block order from 0.0; sums[28]: the count, a 64-bit integer.
+void cmk_aln_sum(hipStream_t s, const double* partials, uint32_t n_blocks, double* sums);

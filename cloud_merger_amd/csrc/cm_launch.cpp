@@ -8,6 +8,7 @@
 #include <cstring>
 #include <limits>
 
+#include "cm_align_solve.hpp"
 #include "cm_ctx.hpp"
 
 namespace {
@@ -685,6 +686,8 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
         f.outlier_min_nb = o_min_nb;
     }
     c->have_result = false;
+    c->nrm_have = false;                             // (the tables of the last result go with it)
+    c->aln_have = false;
     c->last_mode = mode;
     c->bytes_d2h = 0;
     if (c->pub_pending[0]) {
@@ -895,6 +898,8 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     r.n_sensors = n_tables;
     r.n_in = total;
     c->have_result = false;
+    c->nrm_have = false;
+    c->aln_have = false;
     c->last_mode = 2;
     c->prof_used = 0;
     if (f.n_padded == 0) {
@@ -1164,6 +1169,7 @@ int clusters(cm_ctx* c, const cm_cluster_params& q) {
 int normals(cm_ctx* c, const cm_normal_params& q) {
     const uint32_t n = static_cast<uint32_t>(c->result.n_out);
     c->nrm_n_listed = 0;
+    c->nrm_have = false;
     if (n == 0) return CM_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
@@ -1252,5 +1258,177 @@ int normals(cm_ctx* c, const cm_normal_params& q) {
     HIP_TRY(c, hipStreamSynchronize(st));
     collect_stage_times(c);
     c->nrm_n_listed = listed;
+    c->nrm_have = true;
+    c->nrm_k = q.k;
+    return CM_OK;
+}
+
+namespace {
+
+// The stages an iterated by-product marked, one entry per name in order of first appearance, the milliseconds of equally
+// named stages added up (collect_stage_times lists every launch; a registration has up to 65 evaluations).
+void collect_stage_times_by_name(cm_ctx* c) {
+    if (!(c->flags & CM_FLAG_PROFILE)) return;
+    cm_stage_times& t = c->stage_times;
+    std::memset(&t, 0, sizeof t);
+    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
+    for (size_t i = 0; i < n; ++i) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
+        char name[sizeof t.name[0]];
+        std::snprintf(name, sizeof name, "%s", c->prof_names[i].c_str());
+        uint32_t k = 0;
+        while (k < t.n_stages && std::strcmp(t.name[k], name) != 0) ++k;
+        if (k == CM_MAX_STAGES) continue;
+        if (k == t.n_stages) { std::memcpy(t.name[k], name, sizeof name); ++t.n_stages; }
+        t.ms[k] += ms;
+    }
+}
+
+}  // namespace
+
+// Point-to-plane registration of a source cloud against the last result (cm_kernels_align.hip; the semantics are in
+// include/cloudmerge.h). The normals table first: the one the context holds for this result at normals_k, else normals()
+// with viewpoint 0 and search_cell 0. Then the cluster call's front end — bounds, the search grid decided on the host
+// (cluster_grid of the matching radius), keys, radix passes, gather, row table — on buffers and a state record of this
+// call's own, once per call; the bounds also give the pivot. Then the loop: per evaluation k_aln_eval, k_aln_sum and one
+// host round trip of 28 doubles and a count; the solve and the pose update are cm_align_solve.hpp's. Reads `out` and
+// nrm_entries and writes only the aln_* buffers: nothing a later frame reads. Under CM_FLAG_PROFILE the stage times of the
+// call (without those of a normals call it made) replace the frame's, one entry per name, summed over the evaluations;
+// "aln_readback" is the round trip with the host's solve.
+int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src64, cm_align_result* out) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    const uint32_t n_src = static_cast<uint32_t>(n_src64);
+    c->aln_have = false;
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(out->pose, q.guess, sizeof out->pose);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n && !(c->nrm_have && c->nrm_k == q.normals_k)) {
+        cm_normal_params np{};
+        np.k = q.normals_k;
+        if (const int e = normals(c, np)) return e;
+    }
+    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
+    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    if (n_slots > c->aln_cap_slots) {
+        uint32_t** words[] = {&c->aln_keys_a, &c->aln_keys_b, &c->aln_vals_a, &c->aln_vals_b, &c->aln_hist, &c->aln_grp, &c->aln_aux};
+        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
+        if (c->aln_pts) { (void)hipFree(c->aln_pts); c->aln_pts = nullptr; }
+        c->aln_cap_slots = 0;
+        bool ok = true;
+        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->aln_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->aln_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
+        ok = ok && A(reinterpret_cast<void**>(&c->aln_aux), static_cast<size_t>(n_slots) * 12);
+        ok = ok && A(&c->aln_pts, static_cast<size_t>(n_slots) * 16);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's search buffers");
+        c->aln_cap_slots = n_slots;
+    }
+    if (!c->aln_state) {
+        bool ok = A(reinterpret_cast<void**>(&c->aln_state), sizeof(CmFrameState)) &&
+                  A(reinterpret_cast<void**>(&c->aln_words), (8 + CM_RADIX) * 4) &&
+                  A(reinterpret_cast<void**>(&c->aln_sums), CM_ALIGN_SUMS * sizeof(double));
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's state");
+    }
+    const uint32_t n_blocks = (n_src + CM_BLOCK - 1) / CM_BLOCK;
+    if (n_src64 > c->aln_cap_src) {
+        if (c->aln_corr) { (void)hipFree(c->aln_corr); c->aln_corr = nullptr; }
+        if (c->aln_part) { (void)hipFree(c->aln_part); c->aln_part = nullptr; }
+        c->aln_cap_src = 0;
+        bool ok = A(&c->aln_corr, static_cast<size_t>(n_src) * sizeof(cm_align_corr)) &&
+                  A(reinterpret_cast<void**>(&c->aln_part), static_cast<size_t>(n_blocks) * CM_ALIGN_STRIDE * sizeof(double));
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's correspondence table");
+        c->aln_cap_src = n_src64;
+    }
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->aln_words;
+    c->prof_used = 0;
+
+    CmClusterGridDev gd{};
+    if (n) {
+        SortPairs sp = {c->aln_keys_a, c->aln_keys_b, c->aln_vals_a, c->aln_vals_b, c->aln_hist, w + 8, c->aln_grp, c->aln_grp + gw};
+        // the search grid: over the centroids' own bounds, whose midpoint is the pivot
+        prof_mark(c, "k_cl_bounds");
+        HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
+        HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
+        cmk_cl_bounds(st, c->out, n, w + 2);
+        uint32_t img[6];
+        HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        float mn[3], mx[3];
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]);
+            out->pivot[a] = static_cast<double>(mn[a]) + (static_cast<double>(mx[a]) - static_cast<double>(mn[a])) * 0.5;
+        }
+        const ClusterGrid grid = cluster_grid(q.max_corr_dist, mn, mx, CM_ROW_TABLE_CAP);
+        const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
+        if (n_rows > c->aln_cap_rows) {
+            if (c->aln_rows) { (void)hipFree(c->aln_rows); c->aln_rows = nullptr; c->aln_cap_rows = 0; }
+            if (!A(&c->aln_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's row table");
+            c->aln_cap_rows = n_rows;
+        }
+        for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
+        gd.inv = grid.inv;
+
+        // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
+        const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+        HIP_TRY(c, hipMemsetAsync(c->aln_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+        prof_mark(c, "k_cl_keys");
+        cmk_cl_keys(st, c->out, n, gd, passes, c->aln_state, c->aln_keys_a, c->aln_hist, c->aln_grp, nt);
+        radix_sort_pairs(c, c->aln_state, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
+        prof_mark(c, "k_cl_gather");
+        cmk_cl_gather(st, c->out, c->aln_state, c->aln_vals_a, c->aln_vals_b, n, c->aln_pts, c->aln_aux, c->aln_aux + n_slots,
+                      c->aln_aux + 2 * static_cast<size_t>(n_slots));
+        prof_mark(c, "cl_rows");
+        cmk_sorted_rows(st, nullptr, c->aln_state, c->aln_keys_a, c->aln_vals_a, c->aln_keys_b, c->aln_vals_b, c->aln_pts,
+                        c->aln_rows, n_slots, true);
+        HIP_TRY(c, hipGetLastError());
+    }
+
+    // one evaluation at out->pose: the correspondences into aln_corr, the sums and the count into s[]
+    const float r2 = q.max_corr_dist * q.max_corr_dist;
+    double s[CM_ALIGN_SUMS];
+    uint64_t n_corr = 0;
+    auto evaluate = [&]() -> int {
+        CmAlignPoseDev P;
+        std::memcpy(P.m, out->pose, sizeof P.m);
+        std::memcpy(P.p0, out->pivot, sizeof P.p0);
+        prof_mark(c, "k_aln_eval");
+        cmk_aln_eval(st, c->aln_state, c->aln_keys_a, c->aln_keys_b, c->aln_pts, c->aln_rows, c->out, c->nrm_entries, src_dev,
+                     n_src, n, gd, r2, P, c->aln_corr, c->aln_part);
+        prof_mark(c, "k_aln_sum");
+        cmk_aln_sum(st, c->aln_part, n_blocks, c->aln_sums);
+        prof_mark(c, "aln_readback");
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(s, c->aln_sums, sizeof s, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        std::memcpy(&n_corr, &s[CM_ALIGN_TERMS], 8);
+        return CM_OK;
+    };
+    uint32_t flags = 0, it = 0;
+    for (; it < q.max_iterations; ++it) {
+        if (const int e = evaluate()) return e;
+        if (n_corr < q.min_correspondences) break;
+        double x[6];
+        if (!cm_align_solve(s, s + 21, x)) { flags |= CM_ALIGN_SINGULAR; break; }
+        cm_align_update(out->pose, x, out->pivot);
+        if (cm_align_norm3(x) < q.rot_eps && cm_align_norm3(x + 3) < q.trans_eps) { flags |= CM_ALIGN_CONVERGED; ++it; break; }
+    }
+    out->iterations = it;
+    if (q.max_iterations && it == q.max_iterations && !(flags & CM_ALIGN_CONVERGED)) flags |= CM_ALIGN_MAX_ITER_HIT;
+    if (const int e = evaluate()) return e;
+    prof_mark(c, "end");
+    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times_by_name(c);
+    if (n_corr < q.min_correspondences) flags |= CM_ALIGN_FEW;
+    std::memcpy(out->H, s, sizeof out->H);
+    std::memcpy(out->g, s + 21, sizeof out->g);
+    out->sse = s[27];
+    out->rms = n_corr ? std::sqrt(s[27] / static_cast<double>(n_corr)) : 0.0;
+    out->n_corr = n_corr;
+    out->flags = flags;
+    c->aln_have = true;
+    c->aln_n_src = n_src64;
     return CM_OK;
 }

@@ -148,6 +148,10 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "cluster_min_size") ok = static_cast<bool>(is >> c.cluster_min_size) && c.cluster_min_size >= 1;
         else if (key == "cluster_max_size") ok = static_cast<bool>(is >> c.cluster_max_size) && c.cluster_max_size >= 1;
         else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
+        else if (key == "align_prev") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.align_prev = v == 1; }
+        else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
+        else if (key == "align_normals_k") ok = static_cast<bool>(is >> c.align_normals_k) && c.align_normals_k >= 3 && c.align_normals_k <= CM_NORMAL_MAX_K;
+        else if (key == "align_max_iterations") ok = static_cast<bool>(is >> c.align_max_iterations) && c.align_max_iterations <= CM_ALIGN_MAX_ITER;
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
             ok = static_cast<bool>(is >> v[0] >> v[1] >> v[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
@@ -297,6 +301,29 @@ int CloudMergerNode::normals_of_frame(const cm_result& r) {
     return CM_OK;
 }
 
+int CloudMergerNode::align_of_frame(const cm_result& r) {
+    has_alignment_ = false;
+    if (!cfg_.align_prev) return CM_OK;
+    if (r.status != CM_OK) { prev_records_.clear(); return CM_OK; }
+    if (!prev_records_.empty()) {
+        cm_align_params q{};
+        q.max_corr_dist = cfg_.align_max_corr;
+        q.max_iterations = cfg_.align_max_iterations;
+        q.normals_k = cfg_.align_normals_k;
+        q.min_correspondences = 6;
+        q.trans_eps = q.rot_eps = 1e-6;
+        q.guess[0] = q.guess[5] = q.guess[10] = 1.0;
+        const int st = cm_result_align(ctx_, &q, prev_records_.data(), prev_records_.size() / 4, &alignment_);
+        if (st != CM_OK) { set_error(cm_last_error(ctx_)); return st; }
+        has_alignment_ = true;
+    }
+    // this frame's records, for the next frame (the 16-byte records of cm_result_copy, whatever layout is published)
+    prev_records_.resize(static_cast<size_t>(r.n_out) * 4);
+    const int st = r.n_out ? cm_result_copy(ctx_, prev_records_.data(), r.n_out, 16) : CM_OK;
+    if (st != CM_OK) { prev_records_.clear(); set_error(cm_last_error(ctx_)); return st; }
+    return CM_OK;
+}
+
 uint64_t CloudMergerNode::newest_stamp() const {
     uint64_t newest = 0;
     for (const auto& t : stamp_ns_) newest = std::max(newest, t.load());
@@ -380,6 +407,7 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
     { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
+    { const int as = align_of_frame(r); if (as != CM_OK) return as; }
     {
         cm_frame_stats fs;
         if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
@@ -482,6 +510,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
     { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
+    { const int as = align_of_frame(r); if (as != CM_OK) return as; }
     {
         // flag reset, :151-157 — for exactly the clouds this fuse read: a callback may have delivered the next one since
         cm_frame_stats fs;

@@ -85,6 +85,13 @@ struct NodeConfig {
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
     uint32_t normals_k = 0;
     float normals_viewpoint[3] = {0.0f, 0.0f, 0.0f};
+    // Frame-to-frame registration (cm_result_align; point-to-plane ICP). Off by default (align_prev 0). On: after the frame has
+    // been waited for the node aligns the records it published for the previous frame to this frame's result, from the
+    // identity, and keeps the outcome until the next frame (alignment()): the pose maps the previous cloud onto this one.
+    bool align_prev = false;
+    float align_max_corr = 0.5f;        // matching radius, metres
+    uint32_t align_normals_k = 10;
+    uint32_t align_max_iterations = 30;
     struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
     TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
@@ -102,6 +109,8 @@ struct NodeConfig {
 //   statistical_outlier <mean_k> <std_mul> [search_cell]   (pcl::StatisticalOutlierRemoval before the voxel grid)
 //   cluster_tolerance <metres> | cluster_min_size <n> | cluster_max_size <n>   (clusters of every voxel cloud; 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
+//   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
+//   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
@@ -172,6 +181,10 @@ public:
     const std::vector<uint32_t>& cluster_labels() const { return cluster_labels_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
+    // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
+    // there is none (the first frame, a frame without a voxel grid, or one after such a frame).
+    bool has_alignment() const { return has_alignment_; }
+    const cm_align_result& alignment() const { return alignment_; }
 
 private:
     NodeConfig cfg_;
@@ -215,6 +228,10 @@ private:
     int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
+    bool has_alignment_ = false;
+    cm_align_result alignment_{};
+    std::vector<float> prev_records_;              // the records published for the previous frame (16 bytes each)
+    int align_of_frame(const cm_result& r);        // after cm_wait: cm_result_align of prev_records_ when the config asks for it
     int enqueue_frame(bool wait, cm_result* r);   // cm_merge_voxelize(_async), with the motion of the frame set under the slot locks
 };
 

@@ -503,6 +503,79 @@ CM_API int cm_result_normals(cm_ctx* ctx, const cm_normal_params* p, cm_voxel_no
 /* The same table left in device memory owned by the context (*n entries of 32 bytes; NULL when the result is empty). */
 CM_API int cm_result_normals_device(cm_ctx* ctx, const cm_normal_params* p, const void** dev_ptr, uint64_t* n);
 
+/* ---- point-to-plane ICP registration of a cloud against the result (an extension) --------------------------------------
+ * Aligns a source cloud to the last result with its normals (Chen & Medioni's point-to-plane error, linearised about a
+ * pivot), computed on request after a frame. Source: n_src 16-byte records (x, y, z as fp32, the fourth word
+ * ignored: the format of cm_result_copy, so a previous result feeds straight in), n_src < 2^30. Target: the n = n_out records
+ * c_0 .. c_{n-1} of the last result and their normals at normals_k (cm_result_normals). A pose T = [R|t] is 12 doubles,
+ * row-major 3x4; it is never rounded to fp32. One evaluation E(T):
+ *   1. Transform. q64 = ((r00*x + r01*y) + r02*z) + t0 and likewise for the other rows, x = double(src.x) ..., fp64, every
+ *      operation rounded on its own, no contraction. qf = float(q64) per axis.
+ *   2. Match. j(i) is the result index with the smallest (d2(qf_i, c_j), j) in lexicographic order among those with
+ *      d2 < float(max_corr_dist * max_corr_dist); d2 = (dx*dx + dy*dy) + dz*dz in fp32, the distance of the cluster and
+ *      normals stages; strict <; ties go to the smaller result index. No such j, or a qf that is not finite: the
+ *      correspondence is idx = CM_ALIGN_NONE, d2 = 0.
+ *   3. Terms, for every matched i whose target normal is CM_NORMAL_VALID (every other i contributes +0.0), in fp64, every
+ *      operation rounded on its own. p0 = pivot = double(mn) + (double(mx) - double(mn)) * 0.5 per axis, mn / mx the fp32
+ *      bounds of the result's records. a = q64 - p0, b = double(c_j) - p0, n = double(normal_j);
+ *      res = (n0*(a0-b0) + n1*(a1-b1)) + n2*(a2-b2); J = [a x n, n] (6 entries). The 28 terms: J_u J_v for u >= v (the lower
+ *      triangle of H, row by row), J_u res (g), res*res (sse); and the integer count n_corr of the i that have terms.
+ *   4. Sums in a defined order, so that the result is a function of the inputs alone. Terms sit at their source index in
+ *      aligned blocks of 256. Inside 64 consecutive indices v[l] += v[l + s] for s = 32, 16, 8, 4, 2, 1 and v[0] is their
+ *      sum; a block is ((w0 + w1) + w2) + w3; the block sums are added one after the other in ascending order from 0.0.
+ *      The sign of a normal cancels exactly in every term: the viewpoint the normals were turned to never matters.
+ * The loop, on the host, for it = 0 .. max_iterations - 1: E(T_it); n_corr < min_correspondences: stop. Solve H x = -g by
+ * LDL^T without pivoting in fp64; a pivot <= CM_ALIGN_PIVOT_MIN * max_i H_ii (or NaN): CM_ALIGN_SINGULAR, stop, pose
+ * unchanged. x = (w, v) is a twist about the pivot: R' = Rodrigues(w) R, t' = Rodrigues(w)(t - p0) + p0 + v; iterations
+ * counts these updates. Converged (CM_ALIGN_CONVERGED, stop) when |w| < rot_eps and |v| < trans_eps. All max_iterations
+ * updates applied without that: CM_ALIGN_MAX_ITER_HIT. After the loop one more E(T_final) fills H, g, sse, n_corr,
+ * rms = sqrt(sse / n_corr) (0 without terms) and the correspondence table; CM_ALIGN_FEW is set iff that n_corr is below
+ * min_correspondences. max_iterations 0 is that evaluation alone at the guess: a nearest-neighbour and fitness query.
+ * The normals are those of cm_result_normals at normals_k: a table the context already holds for this result at that k is
+ * used as it is, otherwise the call computes it (viewpoint 0, search_cell 0) — the outcome is the same bytes either way.
+ * Refused with CM_BAD_ARG (cm_last_error says why): what cm_result_normals refuses about the result, a max_corr_dist that is
+ * not finite and > 0 or whose fp32 square is 0 or not finite, normals_k outside 3..CM_NORMAL_MAX_K, max_iterations above
+ * CM_ALIGN_MAX_ITER, min_correspondences below 6, an eps that is negative or NaN, a guess that is not finite, a NULL source
+ * with n_src > 0, n_src >= 2^30. n_src 0 is CM_OK with CM_ALIGN_FEW. The call reads the result and the normals table and
+ * writes only buffers of its own; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists one entry per kernel of the call,
+ * its milliseconds summed over the evaluations. */
+#define CM_ALIGN_MAX_ITER 64
+#define CM_ALIGN_NONE 0xFFFFFFFFu
+#define CM_ALIGN_PIVOT_MIN 1e-9
+#define CM_ALIGN_CONVERGED 1u
+#define CM_ALIGN_MAX_ITER_HIT 2u
+#define CM_ALIGN_FEW 4u
+#define CM_ALIGN_SINGULAR 8u
+typedef struct cm_align_params {       /* 128 bytes */
+    float max_corr_dist;               /* matching radius r, metres */
+    uint32_t max_iterations;           /* 0..CM_ALIGN_MAX_ITER */
+    uint32_t normals_k;                /* 3..CM_NORMAL_MAX_K */
+    uint32_t min_correspondences;      /* >= 6 */
+    double trans_eps, rot_eps;         /* >= 0; 0: never converged by that criterion */
+    double guess[12];                  /* row-major 3x4 [R|t], used verbatim as T_0 */
+} cm_align_params;
+typedef struct cm_align_result {       /* 368 bytes */
+    double pose[12];                   /* final pose, row-major 3x4 */
+    double H[21];                      /* lower triangle, row by row, at the final pose */
+    double g[6];
+    double sse, rms;
+    double pivot[3];
+    uint64_t n_corr;
+    uint32_t iterations;               /* updates applied */
+    uint32_t flags;                    /* CM_ALIGN_* */
+} cm_align_result;
+typedef struct cm_align_corr {         /* 8 bytes */
+    uint32_t idx;                      /* result index, or CM_ALIGN_NONE */
+    float d2;                          /* fp32 squared distance to it (0 without a match) */
+} cm_align_corr;
+CM_API int cm_result_align(cm_ctx* ctx, const cm_align_params* p, const void* src_host, uint64_t n_src, cm_align_result* out);
+/* The same with the source already in device memory, read in place. */
+CM_API int cm_result_align_device(cm_ctx* ctx, const cm_align_params* p, const void* src_dev, uint64_t n_src,
+                                  cm_align_result* out);
+/* The correspondences of the last call's final evaluation, entry i for source record i. *n: the entries (written whenever
+ * there was such a call); more than capacity: CM_CAPACITY (nothing is copied). No call since the last merge: CM_BAD_ARG. */
+CM_API int cm_align_correspondences_copy(cm_ctx* ctx, cm_align_corr* host_dst, uint64_t capacity, uint64_t* n);
+
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
 CM_API int cm_host_free(void* ptr);
