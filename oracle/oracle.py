@@ -177,6 +177,7 @@ def ground_split(points, zones, sensor, gp):
         idx = np.nonzero(band)[0]
         res, inl = ransac_plane(points[idx], gp["max_iterations"], gp["threshold"], gp["probability"], gp["optimize"],
                                 gp["seed"], sensor * 8 + k)
+        res.band_points = len(idx)                 # (a Python attribute beside the C fields: the size of the slab's band)
         ground[idx[inl]] = True
         rest = idx[~inl]
         if gp.get("outlier_radius", 0) and len(rest):
