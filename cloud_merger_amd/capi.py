@@ -46,6 +46,7 @@ SYMBOLS = [
     "cm_result_clusters", "cm_result_clusters_device",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
+    "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
 ]
 MAX_ZONES = 8
 
@@ -203,6 +204,32 @@ ALIGN_CORR_DTYPE = np.dtype([("idx", "<u4"), ("d2", "<f4")])
 assert C.sizeof(AlignParams) == 128 and C.sizeof(AlignResult) == 368 and ALIGN_CORR_DTYPE.itemsize == 8
 
 
+# NDT registration of a cloud against the covariance table (cm_result_ndt_align)
+NDT_MAX_ITER = 64
+NDT_NONE = 0xFFFFFFFF
+NDT_CONVERGED, NDT_MAX_ITER_HIT, NDT_FEW, NDT_SINGULAR = 1, 2, 4, 8
+
+
+class NdtParams(C.Structure):
+    _fields_ = [("outlier_ratio", C.c_float), ("neighborhood", C.c_uint32), ("max_iterations", C.c_uint32),
+                ("min_correspondences", C.c_uint32), ("cov", CovParams), ("trans_eps", C.c_double), ("rot_eps", C.c_double),
+                ("guess", C.c_double * 12)]
+
+
+class NdtResult(C.Structure):
+    _fields_ = [("pose", C.c_double * 12), ("H", C.c_double * 21), ("g", C.c_double * 6), ("score", C.c_double),
+                ("gauss_d1", C.c_double), ("gauss_d2", C.c_double), ("pivot", C.c_double * 3), ("n_corr", C.c_uint64),
+                ("iterations", C.c_uint32), ("flags", C.c_uint32)]
+
+    def pose_matrix(self):
+        """(3, 4) float64 [R|t]."""
+        return np.array(self.pose[:], np.float64).reshape(3, 4)
+
+
+NDT_CORR_DTYPE = np.dtype([("idx", "<u4"), ("n_used", "<u4"), ("score", "<f8")])
+assert C.sizeof(NdtParams) == 136 and C.sizeof(NdtResult) == 376 and NDT_CORR_DTYPE.itemsize == 16
+
+
 def sym6_to_3x3(a):
     """(..., 6) lower-triangle entries in cm_voxel_cov order -> (..., 3, 3) symmetric matrices."""
     a = np.asarray(a)
@@ -316,6 +343,9 @@ def load():
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
     L.cm_result_align_device.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
     L.cm_align_correspondences_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.cm_result_ndt_align.argtypes = [vp, C.POINTER(NdtParams), vp, u64, C.POINTER(NdtResult)]
+    L.cm_result_ndt_align_device.argtypes = [vp, C.POINTER(NdtParams), vp, u64, C.POINTER(NdtResult)]
+    L.cm_ndt_correspondences_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
@@ -683,6 +713,53 @@ class CloudMerger:
         got = C.c_uint64()
         self._check(self._lib.cm_align_correspondences_copy(self._ctx, out.ctypes.data, int(n), C.byref(got)),
                     "cm_align_correspondences_copy")
+        return out[: got.value].copy()
+
+    # ---- NDT registration of a cloud against the last result's covariance table (cm_result_ndt_align) ----
+    @staticmethod
+    def ndt_params(guess=None, neighborhood=7, outlier_ratio=0.55, max_iterations=30, cov_min_points=6, cov_eig_mult=0.01,
+                   trans_eps=1e-6, rot_eps=1e-6, min_correspondences=6):
+        g = np.eye(3, 4) if guess is None else np.asarray(guess, np.float64).reshape(3, 4)
+        return NdtParams(float(outlier_ratio), int(neighborhood), int(max_iterations), int(min_correspondences),
+                         CovParams(int(cov_min_points), float(cov_eig_mult)), float(trans_eps), float(rot_eps),
+                         (C.c_double * 12)(*g.ravel().tolist()))
+
+    def ndt_align(self, source, guess=None, neighborhood=7, outlier_ratio=0.55, max_iterations=30, cov_min_points=6,
+                  cov_eig_mult=0.01, trans_eps=1e-6, rot_eps=1e-6, min_correspondences=6):
+        """NDT registration of `source` — (n, 3) or (n, 4) float32, or a structured XYZI array as result() returns — against
+        the last result's voxel statistics (voxel_covariance at cov_min_points / cov_eig_mult): an NdtResult (pose_matrix()
+        maps source coordinates onto the result). max_iterations 0 evaluates the guess alone (ndt_correspondences, score)."""
+        src = np.asarray(source)
+        if len(src) == 0:
+            rec = np.zeros((0, 4), np.float32)
+        elif src.dtype.names:
+            rec = np.ascontiguousarray(src).view(np.float32).reshape(len(src), -1)[:, :4]
+        else:
+            src = np.asarray(src, np.float32).reshape(len(src), -1)
+            rec = np.zeros((len(src), 4), np.float32)
+            rec[:, :min(src.shape[1], 4)] = src[:, :4]
+        rec = np.ascontiguousarray(rec, np.float32)
+        p = self.ndt_params(guess, neighborhood, outlier_ratio, max_iterations, cov_min_points, cov_eig_mult, trans_eps, rot_eps,
+                            min_correspondences)
+        out = NdtResult()
+        self._check(self._lib.cm_result_ndt_align(self._ctx, C.byref(p), rec.ctypes.data if len(rec) else None, len(rec),
+                                                  C.byref(out)), "cm_result_ndt_align")
+        return out
+
+    def ndt_align_device(self, src_ptr, n_src, **kw):
+        """The same with n_src 16-byte records already in device memory."""
+        p = self.ndt_params(**kw)
+        out = NdtResult()
+        self._check(self._lib.cm_result_ndt_align_device(self._ctx, C.byref(p), C.c_void_p(src_ptr), int(n_src), C.byref(out)),
+                    "cm_result_ndt_align_device")
+        return out
+
+    def ndt_correspondences(self, n):
+        """(n,) NDT_CORR_DTYPE array of the last ndt_align call's final evaluation: entry i belongs to source record i."""
+        out = np.zeros(max(int(n), 1), dtype=NDT_CORR_DTYPE)
+        got = C.c_uint64()
+        self._check(self._lib.cm_ndt_correspondences_copy(self._ctx, out.ctypes.data, int(n), C.byref(got)),
+                    "cm_ndt_correspondences_copy")
         return out[: got.value].copy()
 
     # ---- statistical outlier removal before the voxel grid (cm_set_statistical_outlier) ----

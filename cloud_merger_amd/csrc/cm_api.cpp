@@ -56,6 +56,7 @@ void free_all(cm_ctx* c) {
     F(c->nrm_pts); F(c->nrm_list); F(c->nrm_rows); F(c->nrm_words); F(c->nrm_state); F(c->nrm_entries);
     F(c->aln_keys_a); F(c->aln_keys_b); F(c->aln_vals_a); F(c->aln_vals_b); F(c->aln_hist); F(c->aln_grp); F(c->aln_aux);
     F(c->aln_pts); F(c->aln_rows); F(c->aln_words); F(c->aln_state); F(c->aln_corr); F(c->aln_part); F(c->aln_sums); F(c->aln_src);
+    F(c->ndt_corr); F(c->ndt_part); F(c->ndt_sums); F(c->ndt_words); F(c->ndt_src);
     F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
@@ -178,6 +179,26 @@ int align_check(cm_ctx* c, const cm_align_params* p, const void* src, uint64_t n
     if (!std::isfinite(r2) || !(r2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of max_corr_dist must be finite and > 0");
     if (p->normals_k < 3 || p->normals_k > CM_NORMAL_MAX_K) return fail(c, CM_BAD_ARG, "normals_k must be in 3..CM_NORMAL_MAX_K");
     if (p->max_iterations > CM_ALIGN_MAX_ITER) return fail(c, CM_BAD_ARG, "max_iterations must be in 0..CM_ALIGN_MAX_ITER");
+    if (p->min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
+    if (!(p->trans_eps >= 0.0) || !(p->rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(p->guess[k])) return fail(c, CM_BAD_ARG, "the guess must be finite");
+    if (n_src >= (1ull << 30)) return fail(c, CM_BAD_ARG, "the source must hold fewer than 2^30 records");
+    if (n_src && !src) return fail(c, CM_BAD_ARG, "null source");
+    return CM_OK;
+}
+
+// The refusals of cm_result_ndt_align*: CM_OK when n_src records at src can be aligned to the last result's covariance table
+// with *p; *cov: the table's parameters, the default for {0, 0}. Caller holds merge_mu.
+int ndt_check(cm_ctx* c, const cm_ndt_params* p, const void* src, uint64_t n_src, const cm_ndt_result* out, cm_cov_params* cov) {
+    if (!p) return fail(c, CM_BAD_ARG, "no NDT parameters");
+    if (!out) return fail(c, CM_BAD_ARG, "no place for the NDT registration's outcome");
+    const bool dflt = p->cov.min_points == 0 && p->cov.eig_mult == 0.0f;
+    if (const int e = voxel_cov_check(c, dflt ? nullptr : &p->cov, cov)) return e;
+    if (!std::isfinite(p->outlier_ratio) || !(p->outlier_ratio > 0.0f && p->outlier_ratio < 1.0f))
+        return fail(c, CM_BAD_ARG, "outlier_ratio must be finite and in (0, 1)");
+    if (p->neighborhood != 1 && p->neighborhood != 7) return fail(c, CM_BAD_ARG, "neighborhood must be 1 or 7");
+    if (p->max_iterations > CM_NDT_MAX_ITER) return fail(c, CM_BAD_ARG, "max_iterations must be in 0..CM_NDT_MAX_ITER");
     if (p->min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
     if (!(p->trans_eps >= 0.0) || !(p->rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
     for (int k = 0; k < 12; ++k)
@@ -744,6 +765,58 @@ int cm_align_correspondences_copy(cm_ctx* c, cm_align_corr* host_dst, uint64_t c
     HIP_TRY(c, hipMemcpyAsync(host_dst, c->aln_corr, c->aln_n_src * sizeof(cm_align_corr), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bytes_d2h += c->aln_n_src * sizeof(cm_align_corr);
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_ndt_params) == 136 && sizeof(cm_ndt_result) == 376 && sizeof(cm_ndt_corr) == 16,
+              "cm_ndt_params is 136 bytes, cm_ndt_result 376, a correspondence 16");
+static_assert(CM_NDT_NONE == CM_NDT_NONE_DEV && offsetof(cm_ndt_params, trans_eps) == 24 && offsetof(cm_ndt_result, H) == 96 &&
+                  offsetof(cm_ndt_result, n_corr) == 360 && offsetof(cm_ndt_corr, score) == 8,
+              "the kernels' mark of no voxel; the layouts");
+static_assert(CM_NDT_CONVERGED == CM_ALIGN_CONVERGED && CM_NDT_MAX_ITER_HIT == CM_ALIGN_MAX_ITER_HIT && CM_NDT_FEW == CM_ALIGN_FEW &&
+                  CM_NDT_SINGULAR == CM_ALIGN_SINGULAR, "the same four meanings as CM_ALIGN_*");
+
+int cm_result_ndt_align(cm_ctx* c, const cm_ndt_params* p, const void* src_host, uint64_t n_src, cm_ndt_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_cov_params cov;
+    const int e = ndt_check(c, p, src_host, n_src, out, &cov);
+    if (e != CM_OK) return e;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_src > c->ndt_cap_src_host) {
+        if (c->ndt_src) { (void)hipFree(c->ndt_src); c->ndt_src = nullptr; c->ndt_cap_src_host = 0; }
+        if (hipMalloc(&c->ndt_src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's source");
+        c->ndt_cap_src_host = n_src;
+    }
+    if (n_src) {
+        HIP_TRY(c, hipMemcpyAsync(c->ndt_src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return ndt(c, *p, cov, c->ndt_src, n_src, out);
+}
+
+int cm_result_ndt_align_device(cm_ctx* c, const cm_ndt_params* p, const void* src_dev, uint64_t n_src, cm_ndt_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_cov_params cov;
+    const int e = ndt_check(c, p, src_dev, n_src, out, &cov);
+    if (e != CM_OK) return e;
+    return ndt(c, *p, cov, src_dev, n_src, out);
+}
+
+int cm_ndt_correspondences_copy(cm_ctx* c, cm_ndt_corr* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!c || !n) return CM_BAD_ARG;
+    *n = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (!c->ndt_have) return fail(c, CM_BAD_ARG, "no NDT registration since the last merge");
+    *n = c->ndt_n_src;
+    if (c->ndt_n_src > capacity) return fail(c, CM_CAPACITY, "correspondence destination too small");
+    if (c->ndt_n_src == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "null destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ndt_corr, c->ndt_n_src * sizeof(cm_ndt_corr), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += c->ndt_n_src * sizeof(cm_ndt_corr);
     return CM_OK;
 }
 

@@ -169,6 +169,9 @@ struct cm_ctx {
     CmFrameState* cov_state = nullptr;   // the sort's state record
     void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
     uint64_t cov_cap_entries = 0;
+    bool cov_have = false;               // cov_entries holds the table of the result at rest, computed with these parameters:
+    uint32_t cov_min_points = 0;         // what ndt() reuses
+    float cov_eig_mult = 0.0f;
 
     // Euclidean cluster extraction on the result (cm_kernels_cluster.hip), on request after a frame: buffers of its own — no
     // frame reads them — allocated by the first request and grown with the results. It reads `out` (and out_cnt).
@@ -225,6 +228,18 @@ struct cm_ctx {
     uint64_t aln_cap_src_host = 0;
     bool aln_have = false;               // aln_corr holds the table of a call since the last merge, aln_n_src entries
     uint64_t aln_n_src = 0;
+
+    // NDT registration of a source cloud against the covariance table (cm_kernels_ndt.hip), on request after a frame: reads
+    // out, out_key and cov_entries; these buffers are the call's own.
+    uint64_t ndt_cap_src = 0;            // source records ndt_corr and ndt_part are sized for
+    void* ndt_corr = nullptr;            // cm_ndt_corr per source record: the last evaluation's
+    double* ndt_part = nullptr;          // CM_ALIGN_STRIDE doubles per block of 256 source records
+    double* ndt_sums = nullptr;          // CM_ALIGN_SUMS doubles: what the host reads back per evaluation
+    uint32_t* ndt_words = nullptr;       // [2..7] bounds images (k_cl_bounds)
+    void* ndt_src = nullptr;             // cm_result_ndt_align's device copy of a host source (ndt_cap_src_host records)
+    uint64_t ndt_cap_src_host = 0;
+    bool ndt_have = false;               // ndt_corr holds the table of a call since the last merge, ndt_n_src entries
+    uint64_t ndt_n_src = 0;
 
     // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
     // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
@@ -283,3 +298,6 @@ int clusters(cm_ctx* c, const cm_cluster_params& q);
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_corr.
 int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src, cm_align_result* out);
+// NDT registration of the n_src source records at src_dev against the last result's covariance table at cov (resolved, never
+// {0, 0}): *out, and the correspondences in ndt_corr.
+int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void* src_dev, uint64_t n_src, cm_ndt_result* out);

@@ -251,3 +251,8 @@ struct CmAlignPoseDev {
     double m[12];          // row-major 3x4 [R|t]
     double p0[3];          // the pivot
 };
+
+// NDT registration against the covariance table (cm_kernels_ndt.hip): the grid is k_cov_keys' CmCovGridDev, the pose a
+// CmAlignPoseDev, the block partials k_aln_eval's (the 28th sum is the score); a correspondence (== cm_ndt_corr, 16 bytes:
+// idx, n_used, the score's 8 bytes) is one uint4.
+#define CM_NDT_NONE_DEV 0xFFFFFFFFu

@@ -198,3 +198,12 @@ void cmk_aln_eval(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a,
                   const CmClusterGridDev& g, float r2, const CmAlignPoseDev& pose, void* corr, double* partials);
 // sums[0..27]: the block partials added in ascending block order from 0.0; sums[28]: the count, a 64-bit integer.
 void cmk_aln_sum(hipStream_t s, const double* partials, uint32_t n_blocks, double* sums);
+
+// ---- NDT registration of a source cloud against the covariance table (cm_kernels_ndt.hip) -----------------------------------
+// One evaluation of `pose` over the n_src source records against the n_out voxels whose sorted keys are out_key and whose
+// cm_voxel_cov entries are cov, in the grid g (cmk_cov_keys'): the correspondences (16 bytes each, at the source index) and,
+// per aligned block of 256, the 28 sums and the count in cmk_aln_eval's layout, for cmk_aln_sum. neighborhood: 1 or 7
+// candidates per point; d2h: half of NDT's d2. n_out 0: out_key and cov are not read. n_src 0: no launch.
+void cmk_ndt_eval(hipStream_t s, const uint32_t* out_key, uint32_t n_out, const void* cov, const void* src, uint32_t n_src,
+                  const CmCovGridDev& g, uint32_t neighborhood, double d2h, const CmAlignPoseDev& pose, void* corr,
+                  double* partials);

@@ -688,6 +688,8 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
     c->have_result = false;
     c->nrm_have = false;                             // (the tables of the last result go with it)
     c->aln_have = false;
+    c->cov_have = false;
+    c->ndt_have = false;
     c->last_mode = mode;
     c->bytes_d2h = 0;
     if (c->pub_pending[0]) {
@@ -900,6 +902,8 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     c->have_result = false;
     c->nrm_have = false;
     c->aln_have = false;
+    c->cov_have = false;
+    c->ndt_have = false;
     c->last_mode = 2;
     c->prof_used = 0;
     if (f.n_padded == 0) {
@@ -957,6 +961,7 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
 // `merged`: nothing a later frame reads.
 int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
     const uint64_t n_out = c->result.n_out;
+    c->cov_have = false;
     if (n_out == 0) return CM_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
@@ -1012,6 +1017,9 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
     HIP_TRY(c, hipMemcpyAsync(&err, c->cov_words + 1, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     if (err) return fail(c, CM_INTERNAL, "covariance: a voxel's points did not match its count in the result");
+    c->cov_have = true;                              // (what ndt() may reuse)
+    c->cov_min_points = q.min_points;
+    c->cov_eig_mult = q.eig_mult;
     return CM_OK;
 }
 
@@ -1430,5 +1438,123 @@ int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_s
     out->flags = flags;
     c->aln_have = true;
     c->aln_n_src = n_src64;
+    return CM_OK;
+}
+
+// NDT registration of a source cloud against the last result's covariance table (cm_kernels_ndt.hip; the semantics are in
+// include/cloudmerge.h). The table first: the one the context holds for this result at these parameters, else voxel_cov().
+// Then k_cl_bounds on the result for the pivot, one round trip per call. Then align()'s loop: per evaluation k_ndt_eval,
+// k_aln_sum and one host round trip of 28 doubles and a count; the solve and the pose update are cm_align_solve.hpp's. Reads
+// `out`, out_key and cov_entries and writes only the ndt_* buffers: nothing a later frame reads. Under CM_FLAG_PROFILE the
+// stage times of the call replace the frame's, one entry per name, summed over the evaluations: "voxel_cov" is the covariance
+// call it made (absent when the table was held), "ndt_readback" the round trip with the host's solve.
+int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void* src_dev, uint64_t n_src64, cm_ndt_result* out) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    const uint32_t n_src = static_cast<uint32_t>(n_src64);
+    c->ndt_have = false;
+    // the constants of the score, PCL's gauss_d1 / gauss_d2 at the frame's voxel volume
+    const CmFrameDev& f = c->frame;
+    const float* const leaf = c->plan.params.leaf;
+    const double res3 = (static_cast<double>(leaf[0]) * static_cast<double>(leaf[1])) * static_cast<double>(leaf[2]);
+    const double p = static_cast<double>(q.outlier_ratio);
+    const double c1 = 10.0 * (1.0 - p), c2 = p / res3;
+    const double d3 = -std::log(c2);
+    const double d1 = -std::log(c1 + c2) - d3;
+    const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+    if (!(std::isfinite(d2) && d2 > 0.0)) return fail(c, CM_BAD_ARG, "the score's d2 is not finite and > 0 at this outlier_ratio and leaf");
+    const double d2h = d2 * 0.5;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->prof_used = 0;
+    if (n && !(c->cov_have && c->cov_min_points == cov.min_points && c->cov_eig_mult == cov.eig_mult)) {
+        prof_mark(c, "voxel_cov");                   // (there only when the call computed the table)
+        if (const int e = voxel_cov(c, cov)) return e;
+    }
+    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
+    if (!c->ndt_sums) {
+        bool ok = A(reinterpret_cast<void**>(&c->ndt_sums), CM_ALIGN_SUMS * sizeof(double)) &&
+                  A(reinterpret_cast<void**>(&c->ndt_words), 8 * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's state");
+    }
+    const uint32_t n_blocks = (n_src + CM_BLOCK - 1) / CM_BLOCK;
+    if (n_src64 > c->ndt_cap_src) {
+        if (c->ndt_corr) { (void)hipFree(c->ndt_corr); c->ndt_corr = nullptr; }
+        if (c->ndt_part) { (void)hipFree(c->ndt_part); c->ndt_part = nullptr; }
+        c->ndt_cap_src = 0;
+        bool ok = A(&c->ndt_corr, static_cast<size_t>(n_src) * sizeof(cm_ndt_corr)) &&
+                  A(reinterpret_cast<void**>(&c->ndt_part), static_cast<size_t>(n_blocks) * CM_ALIGN_STRIDE * sizeof(double));
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's correspondence table");
+        c->ndt_cap_src = n_src64;
+    }
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->ndt_words;
+    // nothing is refused from here on: a refused call leaves *out as it was
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(out->pose, q.guess, sizeof out->pose);
+    out->gauss_d1 = d1;
+    out->gauss_d2 = d2;
+
+    CmCovGridDev g{};
+    if (n) {
+        // the pivot: the midpoint of the centroids' own bounds
+        prof_mark(c, "k_cl_bounds");
+        HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
+        HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
+        cmk_cl_bounds(st, c->out, n, w + 2);
+        uint32_t img[6];
+        HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        for (int a = 0; a < 3; ++a) {
+            const float mn = ord_to_float(img[a]), mx = ord_to_float(img[3 + a]);
+            out->pivot[a] = static_cast<double>(mn) + (static_cast<double>(mx) - static_cast<double>(mn)) * 0.5;
+        }
+        // the grid of out_key, as voxel_cov hands it to k_cov_keys
+        for (int a = 0; a < 3; ++a) {
+            g.inv[a] = f.inv_leaf[a];
+            g.min_b[a] = c->cell_min_b[a];
+            g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
+        }
+    }
+
+    // one evaluation at out->pose: the correspondences into ndt_corr, the sums and the count into s[]
+    double s[CM_ALIGN_SUMS];
+    uint64_t n_corr = 0;
+    auto evaluate = [&]() -> int {
+        CmAlignPoseDev P;
+        std::memcpy(P.m, out->pose, sizeof P.m);
+        std::memcpy(P.p0, out->pivot, sizeof P.p0);
+        prof_mark(c, "k_ndt_eval");
+        cmk_ndt_eval(st, c->out_key, n, c->cov_entries, src_dev, n_src, g, q.neighborhood, d2h, P, c->ndt_corr, c->ndt_part);
+        prof_mark(c, "k_aln_sum");
+        cmk_aln_sum(st, c->ndt_part, n_blocks, c->ndt_sums);
+        prof_mark(c, "ndt_readback");
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(s, c->ndt_sums, sizeof s, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        std::memcpy(&n_corr, &s[CM_ALIGN_TERMS], 8);
+        return CM_OK;
+    };
+    uint32_t flags = 0, it = 0;
+    for (; it < q.max_iterations; ++it) {
+        if (const int e = evaluate()) return e;
+        if (n_corr < q.min_correspondences) break;
+        double x[6];
+        if (!cm_align_solve(s, s + 21, x)) { flags |= CM_NDT_SINGULAR; break; }
+        cm_align_update(out->pose, x, out->pivot);
+        if (cm_align_norm3(x) < q.rot_eps && cm_align_norm3(x + 3) < q.trans_eps) { flags |= CM_NDT_CONVERGED; ++it; break; }
+    }
+    out->iterations = it;
+    if (q.max_iterations && it == q.max_iterations && !(flags & CM_NDT_CONVERGED)) flags |= CM_NDT_MAX_ITER_HIT;
+    if (const int e = evaluate()) return e;
+    prof_mark(c, "end");
+    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times_by_name(c);
+    if (n_corr < q.min_correspondences) flags |= CM_NDT_FEW;
+    std::memcpy(out->H, s, sizeof out->H);
+    std::memcpy(out->g, s + 21, sizeof out->g);
+    out->score = s[27];
+    out->n_corr = n_corr;
+    out->flags = flags;
+    c->ndt_have = true;
+    c->ndt_n_src = n_src64;
     return CM_OK;
 }

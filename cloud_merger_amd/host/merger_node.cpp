@@ -3,6 +3,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstring>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -152,6 +153,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
         else if (key == "align_normals_k") ok = static_cast<bool>(is >> c.align_normals_k) && c.align_normals_k >= 3 && c.align_normals_k <= CM_NORMAL_MAX_K;
         else if (key == "align_max_iterations") ok = static_cast<bool>(is >> c.align_max_iterations) && c.align_max_iterations <= CM_ALIGN_MAX_ITER;
+        else if (key == "align_method") ok = static_cast<bool>(is >> c.align_method) && (c.align_method == "icp" || c.align_method == "ndt");
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
             ok = static_cast<bool>(is >> v[0] >> v[1] >> v[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
@@ -186,6 +188,14 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     for (auto& f : consumed_) f.store(0);
     if (cfg_.sensors.empty() || cfg_.sensors.size() > CM_MAX_SENSORS) {
         error_ = "sensor count must be 1..CM_MAX_SENSORS";
+        return;
+    }
+    if (cfg_.align_method != "icp" && cfg_.align_method != "ndt") {
+        error_ = "align_method must be icp or ndt";
+        return;
+    }
+    if (cfg_.align_prev && cfg_.align_method == "ndt" && !(cfg_.flags & CM_FLAG_OCCUPANCY)) {
+        error_ = "align_method ndt needs CM_FLAG_OCCUPANCY (the voxel covariance table)";
         return;
     }
     uint32_t mask = 0;
@@ -305,7 +315,27 @@ int CloudMergerNode::align_of_frame(const cm_result& r) {
     has_alignment_ = false;
     if (!cfg_.align_prev) return CM_OK;
     if (r.status != CM_OK) { prev_records_.clear(); return CM_OK; }
-    if (!prev_records_.empty()) {
+    if (!prev_records_.empty() && cfg_.align_method == "ndt") {
+        cm_ndt_params q{};
+        q.outlier_ratio = 0.55f;
+        q.neighborhood = 7;
+        q.max_iterations = cfg_.align_max_iterations;
+        q.min_correspondences = 6;
+        q.trans_eps = q.rot_eps = 1e-6;
+        q.guess[0] = q.guess[5] = q.guess[10] = 1.0;
+        const int st = cm_result_ndt_align(ctx_, &q, prev_records_.data(), prev_records_.size() / 4, &ndt_alignment_);
+        if (st != CM_OK) { set_error(cm_last_error(ctx_)); return st; }
+        const cm_ndt_result& n = ndt_alignment_;
+        alignment_ = cm_align_result{};
+        std::memcpy(alignment_.pose, n.pose, sizeof n.pose);
+        std::memcpy(alignment_.H, n.H, sizeof n.H);
+        std::memcpy(alignment_.g, n.g, sizeof n.g);
+        std::memcpy(alignment_.pivot, n.pivot, sizeof n.pivot);
+        alignment_.n_corr = n.n_corr;
+        alignment_.iterations = n.iterations;
+        alignment_.flags = n.flags;
+        has_alignment_ = true;
+    } else if (!prev_records_.empty()) {
         cm_align_params q{};
         q.max_corr_dist = cfg_.align_max_corr;
         q.max_iterations = cfg_.align_max_iterations;

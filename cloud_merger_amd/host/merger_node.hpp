@@ -92,6 +92,10 @@ struct NodeConfig {
     float align_max_corr = 0.5f;        // matching radius, metres
     uint32_t align_normals_k = 10;
     uint32_t align_max_iterations = 30;
+    // The matcher of align_prev: "icp" (cm_result_align, the default) or "ndt" (cm_result_ndt_align against the frame's voxel
+    // covariance table at the library's defaults; align_max_iterations applies, align_max_corr and align_normals_k do not).
+    // "ndt" needs a context with CM_FLAG_OCCUPANCY: a node whose flags lack it refuses the combination at start-up.
+    std::string align_method = "icp";
     struct TimeField { uint32_t offset = 0, type = CM_TIME_NONE; };
     TimeField time_field[CM_MAX_SENSORS];           // per sensor, in sensor order: cm_set_sensor_time_field
 };
@@ -111,6 +115,7 @@ struct NodeConfig {
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
+//   align_method <icp|ndt>   (the matcher of align_prev; ndt needs the occupancy flag)
 // Starts from reference_config() minus its sensors when the file names any. Returns false + *err.
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
@@ -185,6 +190,9 @@ public:
     // there is none (the first frame, a frame without a voxel grid, or one after such a frame).
     bool has_alignment() const { return has_alignment_; }
     const cm_align_result& alignment() const { return alignment_; }
+    // align_method ndt: the call's own outcome; alignment() then carries its pose, H, g, pivot, n_corr, iterations and flags
+    // (the CM_NDT_* flags are the CM_ALIGN_* ones), sse and rms 0.
+    const cm_ndt_result& ndt_alignment() const { return ndt_alignment_; }
 
 private:
     NodeConfig cfg_;
@@ -230,6 +238,7 @@ private:
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     bool has_alignment_ = false;
     cm_align_result alignment_{};
+    cm_ndt_result ndt_alignment_{};
     std::vector<float> prev_records_;              // the records published for the previous frame (16 bytes each)
     int align_of_frame(const cm_result& r);        // after cm_wait: cm_result_align of prev_records_ when the config asks for it
     int enqueue_frame(bool wait, cm_result* r);   // cm_merge_voxelize(_async), with the motion of the frame set under the slot locks

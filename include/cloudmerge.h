@@ -576,6 +576,86 @@ CM_API int cm_result_align_device(cm_ctx* ctx, const cm_align_params* p, const v
  * there was such a call); more than capacity: CM_CAPACITY (nothing is copied). No call since the last merge: CM_BAD_ARG. */
 CM_API int cm_align_correspondences_copy(cm_ctx* ctx, cm_align_corr* host_dst, uint64_t capacity, uint64_t* n);
 
+/* ---- NDT registration of a cloud against the per-voxel covariance table (an extension) ----------------------------------
+ * Aligns a source cloud to the last result's voxel statistics (cm_result_voxel_cov at `cov`; Biber & Strasser's normal
+ * distributions transform with Magnusson's score), computed on request after a frame. It needs no
+ * nearest-neighbour search and no normals: the result's voxel keys are sorted, and a voxel is found by one binary search.
+ * Source, pose and pivot are cm_result_align's: n_src 16-byte records, 12 doubles row-major 3x4 never rounded to fp32, the
+ * midpoint of the result's fp32 bounds. All fp64 work is rounded per operation, no contraction. One evaluation E(T):
+ *   0. Constants, on the host with std::log / std::exp: res3 = (double(leaf0) * double(leaf1)) * double(leaf2) of the frame,
+ *      p = double(outlier_ratio), c1 = 10 (1 - p), c2 = p / res3, d3 = -log(c2), d1 = -log(c1 + c2) - d3,
+ *      d2 = -2 log((-log(c1 exp(-0.5) + c2) - d3) / d1) (PCL's gauss_d1 / gauss_d2; returned). d2h = d2 * 0.5.
+ *   1. Transform: cm_result_align's step 1, q64 and qf = float(q64).
+ *   2. Voxels of a point, in the grid of the result's keys (inv = the frame's fp32 1 / leaf, min_b / div_b the grid's origin
+ *      cell and extent): per axis v_a = fsub(floorf(fmul(qf_a, inv_a)), float(min_b_a)) in fp32. A qf that is not finite, or
+ *      a v_a outside [-1, float(div_a)] on any axis (tested in float), has no voxel. Otherwise c_a = (int)v_a and the
+ *      candidates are c, c - e0, c + e0, c - e1, c + e1, c - e2, c + e2 in this order (neighborhood 1: the first alone). A
+ *      candidate counts only if every coordinate lies in [0, div_a) as an integer, per axis — never on the linear key, so a
+ *      neighbour across the x border does not alias into the next row. It is USED iff its key c0 + c1 div0 + c2 div0 div1 is
+ *      among the result's keys, its table entry is CM_COV_VALID, and m below is finite and >= 0.
+ *   3. Terms per used voxel j: a = q64 - p0, b = double(mean_j) - p0, r = a - b, B = double(icov_j);
+ *      u_i = (B_i0 r_0 + B_i1 r_1) + B_i2 r_2; m = (r_0 u_0 + r_1 u_1) + r_2 u_2; w = cm_exp_neg(d2h * m) (cm_ndt_math.hpp:
+ *      the exponential spelled out, 0 for an argument >= 700). The Jacobian columns of a twist about the pivot:
+ *      c_0 = (0, -a2, a1), c_1 = (a2, 0, -a0), c_2 = (-a1, a0, 0), c_3..5 = e_0..2; y_v = B c_v and z_u = c_u . u in the same
+ *      three-term form (exact zeros and ones may be skipped: values are compared, the sign of a zero is free). The 28 terms:
+ *      w (c_u . y_v) for u >= v row by row (H), w z_u (g), w (score). A point's terms are added over its used voxels in
+ *      candidate order from 0.0; n_corr counts the points with at least one used voxel.
+ *   4. Sums: cm_result_align's step 4 unchanged.
+ * The loop is cm_result_align's: solve H x = -g by LDL^T without pivoting, x a twist about the pivot, the same stops, flags
+ * and final evaluation; CM_NDT_FEW iff the final n_corr is below min_correspondences. This is iteratively reweighted
+ * Gauss-Newton on NDT's score: each step minimises the quadratic that majorises -sum exp(-d2h m) at the current weights. It
+ * is the one deviation from pcl::NormalDistributionsTransform, which takes Newton steps with the full Hessian and a
+ * More-Thuente line search over Euler angles; H here is positive semi-definite by construction, which is why LDL^T without
+ * pivoting suffices.
+ * The table is cm_result_voxel_cov's at `cov`: one the context already holds for this result at these parameters is used as
+ * it is, otherwise the call computes it — the outcome is the same bytes either way.
+ * Refused with CM_BAD_ARG (cm_last_error says why): everything cm_result_voxel_cov refuses (a context without
+ * CM_FLAG_OCCUPANCY among it), an outlier_ratio that is not finite or outside (0, 1), a d2 that is not finite and > 0, a
+ * neighborhood other than 1 or 7, max_iterations above CM_NDT_MAX_ITER, min_correspondences below 6, an eps that is negative
+ * or NaN, a guess that is not finite, a NULL source with n_src > 0, n_src >= 2^30. A refused call leaves
+ * *out as it was. (d2 fails only where c1 vanishes beside c2: an outlier_ratio next to 1 at a leaf volume below about 1e-10.)
+ * n_src 0 is CM_OK with CM_NDT_FEW. The call reads the result, its keys and the covariance table and writes only buffers of
+ * its own; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists one entry per kernel of the call, its milliseconds summed
+ * over the evaluations, and before them an entry "voxel_cov" iff the call computed the table itself. */
+#define CM_NDT_MAX_ITER 64
+#define CM_NDT_NONE 0xFFFFFFFFu
+#define CM_NDT_CONVERGED 1u            /* the same four meanings as CM_ALIGN_* */
+#define CM_NDT_MAX_ITER_HIT 2u
+#define CM_NDT_FEW 4u
+#define CM_NDT_SINGULAR 8u
+typedef struct cm_ndt_params {         /* 136 bytes, no padding */
+    float outlier_ratio;               /* PCL's 0.55; finite, in (0, 1) */
+    uint32_t neighborhood;             /* 1: the voxel that holds the point; 7: it and its six face neighbours */
+    uint32_t max_iterations;           /* 0..CM_NDT_MAX_ITER */
+    uint32_t min_correspondences;      /* >= 6 */
+    cm_cov_params cov;                 /* the table used; {0, 0}: the default {6, 0.01f} */
+    double trans_eps, rot_eps;         /* >= 0; 0: never converged by that criterion */
+    double guess[12];                  /* row-major 3x4 [R|t], used verbatim as T_0 */
+} cm_ndt_params;
+typedef struct cm_ndt_result {         /* 376 bytes */
+    double pose[12];                   /* final pose, row-major 3x4 */
+    double H[21];                      /* lower triangle, row by row, at the final pose */
+    double g[6];
+    double score;                      /* sum of the weights w at the final pose */
+    double gauss_d1, gauss_d2;         /* the constants the call used */
+    double pivot[3];
+    uint64_t n_corr;                   /* source points with at least one voxel used */
+    uint32_t iterations;               /* updates applied */
+    uint32_t flags;                    /* CM_NDT_* */
+} cm_ndt_result;
+typedef struct cm_ndt_corr {           /* 16 bytes */
+    uint32_t idx;                      /* result index of the voxel holding the point if it was used, else CM_NDT_NONE */
+    uint32_t n_used;                   /* voxels used for this point, 0..7 */
+    double score;                      /* this point's sum of w */
+} cm_ndt_corr;
+CM_API int cm_result_ndt_align(cm_ctx* ctx, const cm_ndt_params* p, const void* src_host, uint64_t n_src, cm_ndt_result* out);
+/* The same with the source already in device memory, read in place. */
+CM_API int cm_result_ndt_align_device(cm_ctx* ctx, const cm_ndt_params* p, const void* src_dev, uint64_t n_src,
+                                      cm_ndt_result* out);
+/* The correspondences of the last call's final evaluation, entry i for source record i. *n: the entries (written whenever
+ * there was such a call); more than capacity: CM_CAPACITY (nothing is copied). No call since the last merge: CM_BAD_ARG. */
+CM_API int cm_ndt_correspondences_copy(cm_ctx* ctx, cm_ndt_corr* host_dst, uint64_t capacity, uint64_t* n);
+
 /* ---- host memory helpers (pinned staging for PointCloud2 payloads) --------------------------- */
 CM_API int cm_host_alloc(void** ptr, size_t bytes);
 CM_API int cm_host_free(void* ptr);
