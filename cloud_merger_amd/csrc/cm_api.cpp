@@ -1,5 +1,6 @@
 // cm_api.cpp — the C-ABI declared in include/cloudmerge.h: entry points and their argument checks. Frames are
-// assembled and launched in cm_launch.cpp, routed in cm_route.cpp; the context is cm_ctx.hpp.
+// assembled and launched in cm_launch.cpp, routed in cm_route.cpp; the tables computed from a result on request are
+// cm_byproducts.cpp's; the context is cm_ctx.hpp.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -47,16 +48,11 @@ void free_all(cm_ctx* c) {
     F(c->stage32); F(c->out32); F(c->rec_a); F(c->rec_b); F(c->dig); F(c->tile_state); F(c->wave_cnt); F(c->records);
     F(c->spl[0]); F(c->spl[1]); F(c->qcnt); F(c->qtot); F(c->qbofs); F(c->qbid); F(c->qbig);
     F(c->out_other); F(c->out32_other); F(c->motion_buf);
-    F(c->cov_keys_a); F(c->cov_keys_b); F(c->cov_vals_a); F(c->cov_vals_b); F(c->cov_hist); F(c->cov_grp);
-    F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
-    F(c->cl_keys_a); F(c->cl_keys_b); F(c->cl_vals_a); F(c->cl_vals_b); F(c->cl_hist); F(c->cl_grp); F(c->cl_parent); F(c->cl_root);
-    F(c->cl_size); F(c->cl_npts); F(c->cl_num); F(c->cl_labels); F(c->cl_pts); F(c->cl_tile_sums); F(c->cl_rows); F(c->cl_words);
-    F(c->cl_state); F(c->cl_clusters);
-    F(c->nrm_keys_a); F(c->nrm_keys_b); F(c->nrm_vals_a); F(c->nrm_vals_b); F(c->nrm_hist); F(c->nrm_grp); F(c->nrm_aux);
-    F(c->nrm_pts); F(c->nrm_list); F(c->nrm_rows); F(c->nrm_words); F(c->nrm_state); F(c->nrm_entries);
-    F(c->aln_keys_a); F(c->aln_keys_b); F(c->aln_vals_a); F(c->aln_vals_b); F(c->aln_hist); F(c->aln_grp); F(c->aln_aux);
-    F(c->aln_pts); F(c->aln_rows); F(c->aln_words); F(c->aln_state); F(c->aln_corr); F(c->aln_part); F(c->aln_sums); F(c->aln_src);
-    F(c->ndt_corr); F(c->ndt_part); F(c->ndt_sums); F(c->ndt_words); F(c->ndt_src);
+    c->cov.release(); F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
+    c->cl.release(); F(c->cl_root); F(c->cl_num); F(c->cl_labels); F(c->cl_tile_sums); F(c->cl_words); F(c->cl_clusters);
+    c->nrm.release(); F(c->nrm_list); F(c->nrm_words); F(c->nrm_entries);
+    c->aln.release(); c->aln_fit.release();
+    c->ndt_fit.release(); F(c->ndt_bounds);
     F(c->sor_d); F(c->sor_list); F(c->sor_words);
     if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
     for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
@@ -123,21 +119,8 @@ int set_slot_cloud(cm_ctx* c, uint32_t sensor, const void* data, bool on_device,
     return CM_OK;
 }
 
-// The refusals of cm_result_voxel_cov*: CM_OK when a table can be computed with *q. Caller holds merge_mu.
-int voxel_cov_check(cm_ctx* c, const cm_cov_params* p, cm_cov_params* q) {
-    if (!(c->flags & CM_FLAG_OCCUPANCY)) return fail(c, CM_BAD_ARG, "context created without CM_FLAG_OCCUPANCY");
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->have_result) return fail(c, CM_BAD_ARG, "no result");
-    if (c->last_mode != 0) return fail(c, CM_BAD_ARG, "the last result is a partial or merged table (cm_merge_partial / cm_merge_tables)");
-    if (c->result.status != CM_OK) return fail(c, CM_BAD_ARG, std::string("last frame has no voxel grid (") + k_status_names(c->result.status) + ")");
-    *q = p ? *p : cm_cov_params{6u, 0.01f};
-    if (q->min_points < 3) return fail(c, CM_BAD_ARG, "min_points must be at least 3");
-    if (!(q->eig_mult >= 0.0f && q->eig_mult <= 1.0f)) return fail(c, CM_BAD_ARG, "eig_mult must lie in [0, 1]");
-    return CM_OK;
-}
-
-// The refusals of cm_result_clusters*: CM_OK when the last result can be clustered with *p. Caller holds merge_mu.
 // The refusals the tables computed from the last result's centroids share: CM_OK when there is such a result at rest.
+// Caller holds merge_mu, as for every check below.
 int centroid_result_check(cm_ctx* c) {
     if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
     if (!c->have_result) return fail(c, CM_BAD_ARG, "no result");
@@ -146,6 +129,17 @@ int centroid_result_check(cm_ctx* c) {
     return CM_OK;
 }
 
+// The refusals of cm_result_voxel_cov*: CM_OK when a table can be computed with *q.
+int voxel_cov_check(cm_ctx* c, const cm_cov_params* p, cm_cov_params* q) {
+    if (!(c->flags & CM_FLAG_OCCUPANCY)) return fail(c, CM_BAD_ARG, "context created without CM_FLAG_OCCUPANCY");
+    if (const int e = centroid_result_check(c)) return e;
+    *q = p ? *p : cm_cov_params{6u, 0.01f};
+    if (q->min_points < 3) return fail(c, CM_BAD_ARG, "min_points must be at least 3");
+    if (!(q->eig_mult >= 0.0f && q->eig_mult <= 1.0f)) return fail(c, CM_BAD_ARG, "eig_mult must lie in [0, 1]");
+    return CM_OK;
+}
+
+// The refusals of cm_result_clusters*: CM_OK when the last result can be clustered with *p.
 int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
     if (!p) return fail(c, CM_BAD_ARG, "no cluster parameters");
     if (const int e = centroid_result_check(c)) return e;
@@ -157,7 +151,7 @@ int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
     return CM_OK;
 }
 
-// The refusals of cm_result_normals*: CM_OK when the last result's normals can be computed with *p. Caller holds merge_mu.
+// The refusals of cm_result_normals*: CM_OK when the last result's normals can be computed with *p.
 int normals_check(cm_ctx* c, const cm_normal_params* p) {
     if (!p) return fail(c, CM_BAD_ARG, "no normal parameters");
     if (const int e = centroid_result_check(c)) return e;
@@ -168,8 +162,20 @@ int normals_check(cm_ctx* c, const cm_normal_params* p) {
     return CM_OK;
 }
 
-// The refusals of cm_result_align*: CM_OK when n_src records at src can be aligned to the last result with *p. Caller holds
-// merge_mu.
+// The refusals the two registrations share, behind those of their own parameters: the loop's limits, the guess, the source.
+int registration_check(cm_ctx* c, uint32_t max_iterations, uint32_t iter_cap, const char* iter_text, uint32_t min_correspondences,
+                       double trans_eps, double rot_eps, const double guess[12], const void* src, uint64_t n_src) {
+    if (max_iterations > iter_cap) return fail(c, CM_BAD_ARG, iter_text);
+    if (min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
+    if (!(trans_eps >= 0.0) || !(rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(guess[k])) return fail(c, CM_BAD_ARG, "the guess must be finite");
+    if (n_src >= (1ull << 30)) return fail(c, CM_BAD_ARG, "the source must hold fewer than 2^30 records");
+    if (n_src && !src) return fail(c, CM_BAD_ARG, "null source");
+    return CM_OK;
+}
+
+// The refusals of cm_result_align*: CM_OK when n_src records at src can be aligned to the last result with *p.
 int align_check(cm_ctx* c, const cm_align_params* p, const void* src, uint64_t n_src, const cm_align_result* out) {
     if (!p) return fail(c, CM_BAD_ARG, "no alignment parameters");
     if (!out) return fail(c, CM_BAD_ARG, "no place for the alignment's outcome");
@@ -178,18 +184,12 @@ int align_check(cm_ctx* c, const cm_align_params* p, const void* src, uint64_t n
     const float r2 = p->max_corr_dist * p->max_corr_dist;
     if (!std::isfinite(r2) || !(r2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of max_corr_dist must be finite and > 0");
     if (p->normals_k < 3 || p->normals_k > CM_NORMAL_MAX_K) return fail(c, CM_BAD_ARG, "normals_k must be in 3..CM_NORMAL_MAX_K");
-    if (p->max_iterations > CM_ALIGN_MAX_ITER) return fail(c, CM_BAD_ARG, "max_iterations must be in 0..CM_ALIGN_MAX_ITER");
-    if (p->min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
-    if (!(p->trans_eps >= 0.0) || !(p->rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(p->guess[k])) return fail(c, CM_BAD_ARG, "the guess must be finite");
-    if (n_src >= (1ull << 30)) return fail(c, CM_BAD_ARG, "the source must hold fewer than 2^30 records");
-    if (n_src && !src) return fail(c, CM_BAD_ARG, "null source");
-    return CM_OK;
+    return registration_check(c, p->max_iterations, CM_ALIGN_MAX_ITER, "max_iterations must be in 0..CM_ALIGN_MAX_ITER",
+                              p->min_correspondences, p->trans_eps, p->rot_eps, p->guess, src, n_src);
 }
 
 // The refusals of cm_result_ndt_align*: CM_OK when n_src records at src can be aligned to the last result's covariance table
-// with *p; *cov: the table's parameters, the default for {0, 0}. Caller holds merge_mu.
+// with *p; *cov: the table's parameters, the default for {0, 0}.
 int ndt_check(cm_ctx* c, const cm_ndt_params* p, const void* src, uint64_t n_src, const cm_ndt_result* out, cm_cov_params* cov) {
     if (!p) return fail(c, CM_BAD_ARG, "no NDT parameters");
     if (!out) return fail(c, CM_BAD_ARG, "no place for the NDT registration's outcome");
@@ -198,13 +198,38 @@ int ndt_check(cm_ctx* c, const cm_ndt_params* p, const void* src, uint64_t n_src
     if (!std::isfinite(p->outlier_ratio) || !(p->outlier_ratio > 0.0f && p->outlier_ratio < 1.0f))
         return fail(c, CM_BAD_ARG, "outlier_ratio must be finite and in (0, 1)");
     if (p->neighborhood != 1 && p->neighborhood != 7) return fail(c, CM_BAD_ARG, "neighborhood must be 1 or 7");
-    if (p->max_iterations > CM_NDT_MAX_ITER) return fail(c, CM_BAD_ARG, "max_iterations must be in 0..CM_NDT_MAX_ITER");
-    if (p->min_correspondences < 6) return fail(c, CM_BAD_ARG, "min_correspondences must be at least 6");
-    if (!(p->trans_eps >= 0.0) || !(p->rot_eps >= 0.0)) return fail(c, CM_BAD_ARG, "trans_eps and rot_eps must be >= 0");
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(p->guess[k])) return fail(c, CM_BAD_ARG, "the guess must be finite");
-    if (n_src >= (1ull << 30)) return fail(c, CM_BAD_ARG, "the source must hold fewer than 2^30 records");
-    if (n_src && !src) return fail(c, CM_BAD_ARG, "null source");
+    return registration_check(c, p->max_iterations, CM_NDT_MAX_ITER, "max_iterations must be in 0..CM_NDT_MAX_ITER",
+                              p->min_correspondences, p->trans_eps, p->rot_eps, p->guess, src, n_src);
+}
+
+// A registration's host source into fit.src, grown on demand: *src_dev is where the n_src records of 16 bytes then lie.
+// what: the error text of a failure to grow.
+int stage_source(cm_ctx* c, PoseFit& fit, const void* src_host, uint64_t n_src, const char* what, const void** src_dev) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_src > fit.cap_src_host) {
+        if (fit.src) { (void)hipFree(fit.src); fit.src = nullptr; fit.cap_src_host = 0; }
+        if (hipMalloc(&fit.src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, what);
+        fit.cap_src_host = n_src;
+    }
+    if (n_src) {
+        HIP_TRY(c, hipMemcpyAsync(fit.src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    *src_dev = fit.src;
+    return CM_OK;
+}
+
+// cm_*_correspondences_copy: the entries of `bytes` each that fit's last call left. what: the error text without such a call.
+int copy_correspondences(cm_ctx* c, const PoseFit& fit, size_t bytes, const char* what, void* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!fit.have) return fail(c, CM_BAD_ARG, what);
+    *n = fit.n_src;
+    if (fit.n_src > capacity) return fail(c, CM_CAPACITY, "correspondence destination too small");
+    if (fit.n_src == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "null destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, fit.corr, fit.n_src * bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += fit.n_src * bytes;
     return CM_OK;
 }
 
@@ -729,26 +754,16 @@ static_assert(CM_ALIGN_NONE == CM_ALIGN_NONE_DEV && offsetof(cm_align_result, H)
 int cm_result_align(cm_ctx* c, const cm_align_params* p, const void* src_host, uint64_t n_src, cm_align_result* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    const int e = align_check(c, p, src_host, n_src, out);
-    if (e != CM_OK) return e;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n_src > c->aln_cap_src_host) {
-        if (c->aln_src) { (void)hipFree(c->aln_src); c->aln_src = nullptr; c->aln_cap_src_host = 0; }
-        if (hipMalloc(&c->aln_src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's source");
-        c->aln_cap_src_host = n_src;
-    }
-    if (n_src) {
-        HIP_TRY(c, hipMemcpyAsync(c->aln_src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return align(c, *p, c->aln_src, n_src, out);
+    const void* src_dev = nullptr;
+    if (const int e = align_check(c, p, src_host, n_src, out)) return e;
+    if (const int e = stage_source(c, c->aln_fit, src_host, n_src, "cannot allocate the registration's source", &src_dev)) return e;
+    return align(c, *p, src_dev, n_src, out);
 }
 
 int cm_result_align_device(cm_ctx* c, const cm_align_params* p, const void* src_dev, uint64_t n_src, cm_align_result* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    const int e = align_check(c, p, src_dev, n_src, out);
-    if (e != CM_OK) return e;
+    if (const int e = align_check(c, p, src_dev, n_src, out)) return e;
     return align(c, *p, src_dev, n_src, out);
 }
 
@@ -756,16 +771,7 @@ int cm_align_correspondences_copy(cm_ctx* c, cm_align_corr* host_dst, uint64_t c
     if (!c || !n) return CM_BAD_ARG;
     *n = 0;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (!c->aln_have) return fail(c, CM_BAD_ARG, "no alignment since the last merge");
-    *n = c->aln_n_src;
-    if (c->aln_n_src > capacity) return fail(c, CM_CAPACITY, "correspondence destination too small");
-    if (c->aln_n_src == 0) return CM_OK;
-    if (!host_dst) return fail(c, CM_BAD_ARG, "null destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->aln_corr, c->aln_n_src * sizeof(cm_align_corr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += c->aln_n_src * sizeof(cm_align_corr);
-    return CM_OK;
+    return copy_correspondences(c, c->aln_fit, sizeof(cm_align_corr), "no alignment since the last merge", host_dst, capacity, n);
 }
 
 static_assert(sizeof(cm_ndt_params) == 136 && sizeof(cm_ndt_result) == 376 && sizeof(cm_ndt_corr) == 16,
@@ -780,27 +786,17 @@ int cm_result_ndt_align(cm_ctx* c, const cm_ndt_params* p, const void* src_host,
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     cm_cov_params cov;
-    const int e = ndt_check(c, p, src_host, n_src, out, &cov);
-    if (e != CM_OK) return e;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n_src > c->ndt_cap_src_host) {
-        if (c->ndt_src) { (void)hipFree(c->ndt_src); c->ndt_src = nullptr; c->ndt_cap_src_host = 0; }
-        if (hipMalloc(&c->ndt_src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's source");
-        c->ndt_cap_src_host = n_src;
-    }
-    if (n_src) {
-        HIP_TRY(c, hipMemcpyAsync(c->ndt_src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return ndt(c, *p, cov, c->ndt_src, n_src, out);
+    const void* src_dev = nullptr;
+    if (const int e = ndt_check(c, p, src_host, n_src, out, &cov)) return e;
+    if (const int e = stage_source(c, c->ndt_fit, src_host, n_src, "cannot allocate the NDT registration's source", &src_dev)) return e;
+    return ndt(c, *p, cov, src_dev, n_src, out);
 }
 
 int cm_result_ndt_align_device(cm_ctx* c, const cm_ndt_params* p, const void* src_dev, uint64_t n_src, cm_ndt_result* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     cm_cov_params cov;
-    const int e = ndt_check(c, p, src_dev, n_src, out, &cov);
-    if (e != CM_OK) return e;
+    if (const int e = ndt_check(c, p, src_dev, n_src, out, &cov)) return e;
     return ndt(c, *p, cov, src_dev, n_src, out);
 }
 
@@ -808,16 +804,7 @@ int cm_ndt_correspondences_copy(cm_ctx* c, cm_ndt_corr* host_dst, uint64_t capac
     if (!c || !n) return CM_BAD_ARG;
     *n = 0;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (!c->ndt_have) return fail(c, CM_BAD_ARG, "no NDT registration since the last merge");
-    *n = c->ndt_n_src;
-    if (c->ndt_n_src > capacity) return fail(c, CM_CAPACITY, "correspondence destination too small");
-    if (c->ndt_n_src == 0) return CM_OK;
-    if (!host_dst) return fail(c, CM_BAD_ARG, "null destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ndt_corr, c->ndt_n_src * sizeof(cm_ndt_corr), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += c->ndt_n_src * sizeof(cm_ndt_corr);
-    return CM_OK;
+    return copy_correspondences(c, c->ndt_fit, sizeof(cm_ndt_corr), "no NDT registration since the last merge", host_dst, capacity, n);
 }
 
 int cm_set_ground_removal(cm_ctx* c, const cm_ground_params* g) {

@@ -1,0 +1,561 @@
+// cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
+// (voxel_cov), the cluster extraction (clusters), normals and curvature (normals), and the two registrations of a source cloud
+// (align, ndt). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
+// search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
+// Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "cm_align_solve.hpp"
+#include "cm_ctx.hpp"
+
+namespace {
+
+bool dev_alloc(void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; }
+template <class T> bool dev_alloc(T** ptr, size_t bytes) { return dev_alloc(reinterpret_cast<void**>(ptr), bytes); }
+template <class T> void dev_free(T*& ptr) { if (ptr) { (void)hipFree(ptr); ptr = nullptr; } }
+
+// One table of `need` entries of `bytes` each: beyond *cap it is freed and allocated anew. false: out of memory, *cap is 0.
+bool grow_table(void** ptr, uint64_t* cap, uint64_t need, size_t bytes) {
+    if (need <= *cap) return true;
+    dev_free(*ptr);
+    *cap = 0;
+    if (!dev_alloc(ptr, need * bytes)) return false;
+    *cap = need;
+    return true;
+}
+
+}  // namespace
+
+int PairSort::reserve(cm_ctx* c, uint32_t n_slots, const char* what) {
+    if (n_slots <= cap_slots) return CM_OK;
+    release();
+    const size_t tiles = n_slots / CM_TILE, groups = (tiles + CM_GROUP - 1) / CM_GROUP;
+    bool ok = true;
+    for (uint32_t** b : {&keys_a, &keys_b, &vals_a, &vals_b}) ok = ok && dev_alloc(b, static_cast<size_t>(n_slots) * 4);
+    ok = ok && dev_alloc(&hist, tiles * CM_RADIX * 4);
+    ok = ok && dev_alloc(&grp, CM_MAX_PASSES * groups * CM_RADIX * 4);
+    ok = ok && dev_alloc(&totals, CM_RADIX * 4);
+    if (!ok) return fail(c, CM_HIP_ERROR, what);
+    cap_slots = n_slots;
+    return CM_OK;
+}
+
+void PairSort::release() {
+    for (uint32_t** b : {&keys_a, &keys_b, &vals_a, &vals_b, &hist, &grp, &totals}) dev_free(*b);
+    cap_slots = 0;
+}
+
+void SearchIndex::release() {
+    sort.release();
+    dev_free(state); dev_free(bounds); dev_free(pts); dev_free(aux); dev_free(rows);
+    cap_rows = 0;
+}
+
+int PoseFit::reserve(cm_ctx* c, uint64_t n, size_t corr_bytes, const char* what_state, const char* what_table) {
+    if (!sums && !dev_alloc(&sums, CM_ALIGN_SUMS * sizeof(double))) return fail(c, CM_HIP_ERROR, what_state);
+    if (n <= cap_src) return CM_OK;
+    dev_free(corr); dev_free(part);
+    cap_src = 0;
+    const size_t n_blocks = (n + CM_BLOCK - 1) / CM_BLOCK;
+    if (!dev_alloc(&corr, n * corr_bytes) || !dev_alloc(&part, n_blocks * CM_ALIGN_STRIDE * sizeof(double)))
+        return fail(c, CM_HIP_ERROR, what_table);
+    cap_src = n;
+    return CM_OK;
+}
+
+void PoseFit::release() {
+    dev_free(corr); dev_free(part); dev_free(sums); dev_free(src);
+    cap_src = cap_src_host = 0;
+}
+
+// The per-voxel covariance table of the last result into c->cov_entries (cm_kernels_cov.hip). Launches on the context's
+// stream, reads what the frame left (descriptor, mask, out_key / out_cnt, cell grid) and writes only the cov buffers and
+// `merged`: nothing a later frame reads.
+int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
+    const uint64_t n_out = c->result.n_out;
+    c->cov_have = false;
+    if (n_out == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!grow_table(&c->cov_entries, &c->cov_cap_entries, n_out, sizeof(cm_voxel_cov)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the covariance table");
+    const CmFrameDev& f = c->frame;
+    const uint32_t nt = f.n_tiles, n_slots = f.n_padded;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    PairSort& so = c->cov;
+    if (const int e = so.reserve(c, n_slots, "cannot allocate the covariance sort's buffers")) return e;
+    if (!c->cov_state) {
+        bool ok = dev_alloc(&c->cov_state, sizeof(CmFrameState)) && dev_alloc(&c->cov_tile_counts, static_cast<size_t>(c->cap_tiles) * 4) &&
+                  dev_alloc(&c->cov_words, 2 * 4);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's state");
+    }
+    if (!c->merged) HIP_TRY(c, hipMalloc(&c->merged, static_cast<size_t>(c->cap_padded) * 16));
+    hipStream_t st = c->stream;
+    // the kept points in (sensor, point) order, as cm_merged_copy returns them
+    cmk_merged(st, c->d_frame, c->cov_tile_counts, c->cov_words, c->merged, nt, c->frame_mask);
+    // (voxel number, record index) pairs, sorted by voxel number: as many 8-bit passes as the numbers need
+    const uint32_t passes = (key_width(n_out) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    CmCovGridDev g;
+    for (int a = 0; a < 3; ++a) {
+        g.inv[a] = f.inv_leaf[a];
+        g.min_b[a] = c->cell_min_b[a];
+        g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
+    }
+    HIP_TRY(c, hipMemsetAsync(so.grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->cov_words + 1, 0, 4, st));
+    cmk_cov_keys(st, c->merged, c->cov_words, g, c->out_key, static_cast<uint32_t>(n_out), passes, c->cov_state, so.keys_a, so.hist,
+                 so.grp, nt);
+    // ballot ranking whatever the context's probe found: stable by construction, the sums' order depends on it
+    radix_sort_pairs(c, c->cov_state, so.pairs(gw), passes, nt, n_slots, false, nullptr, nullptr);
+    cmk_cov_reduce(st, c->merged, c->cov_state, so.keys_a, so.vals_a, so.keys_b, so.vals_b, c->out_cnt, static_cast<uint32_t>(n_out),
+                   q.min_points, q.eig_mult, c->cov_entries, c->cov_words + 1);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t err = 0;
+    HIP_TRY(c, hipMemcpyAsync(&err, c->cov_words + 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (err) return fail(c, CM_INTERNAL, "covariance: a voxel's points did not match its count in the result");
+    c->cov_have = true;                              // (what ndt() may reuse)
+    c->cov_min_points = q.min_points;
+    c->cov_eig_mult = q.eig_mult;
+    return CM_OK;
+}
+
+namespace {
+
+// Host inverse of the kernels' order-preserving float image (k_cl_bounds).
+float ord_to_float(uint32_t o) {
+    const uint32_t b = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+
+// The stages a by-product marked (prof_mark) into c->stage_times, as wait_frame does for a frame's.
+void collect_stage_times(cm_ctx* c) {
+    if (!(c->flags & CM_FLAG_PROFILE)) return;
+    cm_stage_times& t = c->stage_times;
+    std::memset(&t, 0, sizeof t);
+    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
+    for (size_t i = 0; i < n && i < CM_MAX_STAGES; ++i) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
+        std::snprintf(t.name[i], sizeof t.name[i], "%s", c->prof_names[i].c_str());
+        t.ms[i] = ms;
+        t.n_stages = static_cast<uint32_t>(i + 1);
+    }
+}
+
+// The stages an iterated by-product marked, one entry per name in order of first appearance, the milliseconds of equally
+// named stages added up (collect_stage_times lists every launch; a registration has up to 65 evaluations).
+void collect_stage_times_by_name(cm_ctx* c) {
+    if (!(c->flags & CM_FLAG_PROFILE)) return;
+    cm_stage_times& t = c->stage_times;
+    std::memset(&t, 0, sizeof t);
+    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
+    for (size_t i = 0; i < n; ++i) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
+        char name[sizeof t.name[0]];
+        std::snprintf(name, sizeof name, "%s", c->prof_names[i].c_str());
+        uint32_t k = 0;
+        while (k < t.n_stages && std::strcmp(t.name[k], name) != 0) ++k;
+        if (k == CM_MAX_STAGES) continue;
+        if (k == t.n_stages) { std::memcpy(t.name[k], name, sizeof name); ++t.n_stages; }
+        t.ms[k] += ms;
+    }
+}
+
+// The bounds of the last result's centroids (k_cl_bounds into the six `words`, one host round trip): what a search grid is
+// laid over, and whose midpoint is a registration's pivot. The result holds at least one record.
+int result_bounds(cm_ctx* c, uint32_t* words, float mn[3], float mx[3]) {
+    hipStream_t st = c->stream;
+    prof_mark(c, "k_cl_bounds");
+    HIP_TRY(c, hipMemsetAsync(words, 0xFF, 12, st));
+    HIP_TRY(c, hipMemsetAsync(words + 3, 0, 12, st));
+    cmk_cl_bounds(st, c->out, static_cast<uint32_t>(c->result.n_out), words);
+    uint32_t img[6];
+    HIP_TRY(c, hipMemcpyAsync(img, words, sizeof img, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
+    return CM_OK;
+}
+
+void bounds_midpoint(const float mn[3], const float mx[3], double pivot[3]) {
+    for (int a = 0; a < 3; ++a)
+        pivot[a] = static_cast<double>(mn[a]) + (static_cast<double>(mx[a]) - static_cast<double>(mn[a])) * 0.5;
+}
+
+// Room in ix for the last result (none for an empty one): n_states state records and the bounds words on the first call, the
+// sort's buffers, the points and the aux words grown with the result. what_buffers, what_state: the error texts.
+int reserve_search_index(cm_ctx* c, SearchIndex& ix, uint32_t n_states, const char* what_buffers, const char* what_state) {
+    const uint32_t n_slots = round_up(static_cast<uint32_t>(c->result.n_out), CM_TILE);
+    if (n_slots > ix.sort.cap_slots) {
+        dev_free(ix.pts); dev_free(ix.aux);
+        if (const int e = ix.sort.reserve(c, n_slots, what_buffers)) return e;
+        if (!dev_alloc(&ix.pts, static_cast<size_t>(n_slots) * 16) || !dev_alloc(&ix.aux, static_cast<size_t>(n_slots) * 12)) {
+            ix.sort.release();                       // (the next call grows all of it again)
+            return fail(c, CM_HIP_ERROR, what_buffers);
+        }
+    }
+    if (!ix.state && !(dev_alloc(&ix.state, n_states * sizeof(CmFrameState)) && dev_alloc(&ix.bounds, 6 * 4)))
+        return fail(c, CM_HIP_ERROR, what_state);
+    return CM_OK;
+}
+
+// The last result's centroids into ix in the order of `grid`, which the caller laid over their bounds (mn: the minimum):
+// (cell key, result index) sorted by cell key — ballot ranking whatever the context's probe found —, the points gathered in
+// that order, the (y,z)-row ranges. ix.grid is then what the search kernels take. what: the error text of a row table that
+// cannot grow.
+int build_search_index(cm_ctx* c, SearchIndex& ix, const ClusterGrid& grid, const float mn[3], const char* what) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    if (!grow_table(&ix.rows, &ix.cap_rows, static_cast<uint64_t>(grid.dims[1]) * grid.dims[2], 8)) return fail(c, CM_HIP_ERROR, what);
+    for (int a = 0; a < 3; ++a) { ix.grid.min[a] = mn[a]; ix.grid.dims[a] = grid.dims[a]; }
+    ix.grid.inv = grid.inv;
+    hipStream_t st = c->stream;
+    PairSort& so = ix.sort;
+    const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    HIP_TRY(c, hipMemsetAsync(so.grp, 0, static_cast<size_t>(passes) * gw * 4, st));
+    prof_mark(c, "k_cl_keys");
+    cmk_cl_keys(st, c->out, n, ix.grid, passes, ix.state, so.keys_a, so.hist, so.grp, nt);
+    radix_sort_pairs(c, ix.state, so.pairs(gw), passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
+    prof_mark(c, "k_cl_gather");
+    cmk_cl_gather(st, c->out, ix.state, so.vals_a, so.vals_b, n, ix.pts, ix.aux, ix.aux + n_slots, ix.aux + 2 * static_cast<size_t>(n_slots));
+    prof_mark(c, "cl_rows");
+    cmk_sorted_rows(st, nullptr, ix.state, so.keys_a, so.vals_a, so.keys_b, so.vals_b, ix.pts, ix.rows, n_slots, true);
+    return CM_OK;
+}
+
+}  // namespace
+
+// Euclidean cluster extraction on the last result (cm_kernels_cluster.hip): labels, cluster table and member lists into the
+// cl buffers. Reads `out` — what cm_result_copy reads — and out_cnt where the context keeps it. Two host round trips: the
+// bounds of the centroids (the search grid is decided on the host, cluster_grid) and the cluster count (the second sort's
+// passes, the table's size). Under CM_FLAG_PROFILE the stage times of the call replace the frame's in cm_get_stage_times.
+int clusters(cm_ctx* c, const cm_cluster_params& q) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    c->cl_n_clusters = 0;
+    c->cl_n_clustered = 0;
+    c->cl_indices = nullptr;
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
+    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
+    SearchIndex& ix = c->cl;
+    if (const int e = reserve_search_index(c, ix, 2, "cannot allocate the cluster extraction's buffers",
+                                           "cannot allocate the cluster extraction's state")) return e;
+    if (n_slots > c->cl_cap_tables) {
+        dev_free(c->cl_root); dev_free(c->cl_num); dev_free(c->cl_labels); dev_free(c->cl_tile_sums);
+        c->cl_cap_tables = 0;
+        bool ok = true;
+        for (uint32_t** b : {&c->cl_root, &c->cl_num, &c->cl_labels}) ok = ok && dev_alloc(b, static_cast<size_t>(n_slots) * 4);
+        ok = ok && dev_alloc(&c->cl_tile_sums, static_cast<size_t>(nt) * 8);
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's buffers");
+        c->cl_cap_tables = n_slots;
+    }
+    if (!c->cl_words && !dev_alloc(&c->cl_words, 2 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's state");
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->cl_words;
+    c->prof_used = 0;
+
+    // the search grid: over the centroids' own bounds
+    float mn[3], mx[3];
+    if (const int e = result_bounds(c, ix.bounds, mn, mx)) return e;
+    const ClusterGrid grid = cluster_grid(q.tolerance, mn, mx, CM_ROW_TABLE_CAP);
+    if (const int e = build_search_index(c, ix, grid, mn, "cannot allocate the cluster extraction's row table")) return e;
+    PairSort& so = ix.sort;
+    CmFrameState* st_cell = ix.state;
+    CmFrameState* st_num = ix.state + 1;
+    uint32_t *parent = ix.aux, *size = ix.aux + n_slots, *npts = ix.aux + 2 * static_cast<size_t>(n_slots);
+
+    // connected components, sizes, the roots the size filter keeps
+    const float tol2 = q.tolerance * q.tolerance;
+    prof_mark(c, "k_cl_hook");
+    cmk_cl_hook(st, st_cell, so.keys_a, so.keys_b, ix.pts, ix.rows, n, tol2, parent);
+    prof_mark(c, "k_cl_roots");
+    cmk_cl_roots(st, parent, (c->flags & CM_FLAG_OCCUPANCY) ? c->out_cnt : nullptr, n, c->cl_root, size, npts);
+    prof_mark(c, "k_cl_count");
+    cmk_cl_count(st, c->cl_root, size, n, q.min_cluster_size, q.max_cluster_size, c->cl_tile_sums, w, nt);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t counts[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    const uint32_t n_clusters = counts[0];
+    if (!grow_table(&c->cl_clusters, &c->cl_cap_clusters, n_clusters, sizeof(cm_cluster)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the cluster table");
+
+    // numbers, labels, AABB, and the member lists: (cluster number, voxel index) sorted by cluster number, stable
+    const uint32_t passes_num = (key_width(n_clusters ? n_clusters : 1u) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
+    prof_mark(c, "k_cl_number");
+    cmk_cl_number(st, c->cl_root, size, npts, c->cl_tile_sums, n, q.min_cluster_size, q.max_cluster_size, c->cl_num, c->cl_clusters, nt);
+    HIP_TRY(c, hipMemsetAsync(so.grp, 0, static_cast<size_t>(passes_num) * gw * 4, st));
+    prof_mark(c, "k_cl_labels");
+    cmk_cl_labels(st, c->out, c->cl_root, c->cl_num, n, passes_num, st_num, c->cl_labels, so.keys_a, so.hist, so.grp, c->cl_clusters, nt);
+    if (n_clusters) {
+        radix_sort_pairs(c, st_num, so.pairs(gw), passes_num, nt, n_slots, false, nullptr, "k_scatter(lists)");
+        prof_mark(c, "k_cl_decode");
+        cmk_cl_decode(st, c->cl_clusters, n_clusters);
+    }
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->cl_n_clusters = n_clusters;
+    c->cl_n_clustered = counts[1];
+    c->cl_indices = (passes_num & 1u) ? so.vals_b : so.vals_a;
+    return CM_OK;
+}
+
+// Normals and curvature of the last result (cm_kernels_normals.hip): one cm_voxel_normal per result record into nrm_entries.
+// The search index over a grid decided on the host (normals_grid), then the exact k-nearest-neighbour search in two launches.
+// Reads `out`. Two host round trips: the bounds of the centroids and the length of the second launch's list (an empty list
+// costs no launch). Under CM_FLAG_PROFILE the stage times of the call replace the frame's in cm_get_stage_times; the second
+// launch's stage is named "k_nrm_rings n=<centroids it took>".
+int normals(cm_ctx* c, const cm_normal_params& q) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    c->nrm_n_listed = 0;
+    c->nrm_have = false;
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t n_slots = round_up(n, CM_TILE);
+    SearchIndex& ix = c->nrm;
+    if (const int e = reserve_search_index(c, ix, 1, "cannot allocate the normal estimation's buffers",
+                                           "cannot allocate the normal estimation's state")) return e;
+    if (n_slots > c->nrm_cap_tables) {
+        dev_free(c->nrm_list); dev_free(c->nrm_entries);
+        c->nrm_cap_tables = 0;
+        if (!dev_alloc(&c->nrm_list, static_cast<size_t>(n_slots) * 8) || !dev_alloc(&c->nrm_entries, static_cast<size_t>(n_slots) * sizeof(cm_voxel_normal)))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's buffers");
+        c->nrm_cap_tables = n_slots;
+    }
+    if (!c->nrm_words && !dev_alloc(&c->nrm_words, 2 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's state");
+    hipStream_t st = c->stream;
+    uint32_t* const w = c->nrm_words;
+    c->prof_used = 0;
+
+    // the list count of the first search launch, cleared ahead of result_bounds' stage mark on purpose: the same order of
+    // device work as with the clear behind the mark, only its few bytes are no longer timed as "k_cl_bounds"
+    HIP_TRY(c, hipMemsetAsync(w, 0, 8, st));
+    // the search grid: over the centroids' own bounds
+    float mn[3], mx[3];
+    if (const int e = result_bounds(c, ix.bounds, mn, mx)) return e;
+    const ClusterGrid grid = normals_grid(q.search_cell, c->plan.params.leaf, q.k, mn, mx, CM_ROW_TABLE_CAP);
+    if (const int e = build_search_index(c, ix, grid, mn, "cannot allocate the normal estimation's row table")) return e;
+    const PairSort& so = ix.sort;
+
+    // the neighbourhoods and the planes: the 3x3x3 cells first, then whoever needs more, ring by ring
+    prof_mark(c, "k_nrm_knn(block)");
+    cmk_nrm_knn(st, ix.state, so.keys_a, so.keys_b, ix.pts, ix.rows, c->out, ix.grid, n, q.k, q.viewpoint, c->nrm_entries, c->nrm_list, w,
+                n, true);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t listed = 0;
+    HIP_TRY(c, hipMemcpyAsync(&listed, w, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (listed > n) return fail(c, CM_INTERNAL, "normals: the first search launch listed more centroids than the result holds");
+    if (listed) {
+        char name[24];                                    // (the stage's name carries the length of its list: 24 bytes with the NUL)
+        std::snprintf(name, sizeof name, "k_nrm_rings n=%u", listed);
+        prof_mark(c, name);
+        cmk_nrm_knn(st, ix.state, so.keys_a, so.keys_b, ix.pts, ix.rows, c->out, ix.grid, n, q.k, q.viewpoint, c->nrm_entries, c->nrm_list,
+                    w, listed, false);
+    }
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->nrm_n_listed = listed;
+    c->nrm_have = true;
+    c->nrm_k = q.k;
+    return CM_OK;
+}
+
+namespace {
+
+// What align's and ndt's parameters share, and what their outcomes share.
+struct FitParams {
+    uint32_t max_iterations, min_correspondences;
+    double rot_eps, trans_eps;
+};
+struct FitOutcome {
+    double s[CM_ALIGN_SUMS];             // H (21), g (6), the error sum, then the bits of n_corr: the final evaluation's
+    uint64_t n_corr;
+    uint32_t iterations, flags;          // flags: CM_ALIGN_*, whose four meanings are CM_NDT_*'s (cm_api.cpp asserts it)
+};
+
+// The Gauss-Newton loop of a registration: up to max_iterations times evaluate, solve, update `pose` about `pivot`
+// (cm_align_solve.hpp), then one evaluation at the final pose, whose sums *o holds. launch(P) enqueues one evaluation of the
+// n_src source records at the pose P: the correspondences into fit.corr, the per-block sums into fit.part; k_aln_sum and one
+// host round trip of 28 doubles and a count follow (readback: that stage's name). Under CM_FLAG_PROFILE the stage times of
+// the call replace the frame's, one entry per name, summed over the evaluations.
+template <class Launch>
+int fit_pose(cm_ctx* c, PoseFit& fit, const FitParams& q, uint32_t n_src, double pose[12], const double pivot[3], Launch&& launch,
+             const char* readback, FitOutcome* o) {
+    hipStream_t st = c->stream;
+    const uint32_t n_blocks = (n_src + CM_BLOCK - 1) / CM_BLOCK;
+    double* const s = o->s;
+    auto evaluate = [&]() -> int {
+        CmAlignPoseDev P;
+        std::memcpy(P.m, pose, sizeof P.m);
+        std::memcpy(P.p0, pivot, sizeof P.p0);
+        launch(P);
+        prof_mark(c, "k_aln_sum");
+        cmk_aln_sum(st, fit.part, n_blocks, fit.sums);
+        prof_mark(c, readback);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(s, fit.sums, sizeof o->s, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        std::memcpy(&o->n_corr, &s[CM_ALIGN_TERMS], 8);
+        return CM_OK;
+    };
+    uint32_t flags = 0, it = 0;
+    for (; it < q.max_iterations; ++it) {
+        if (const int e = evaluate()) return e;
+        if (o->n_corr < q.min_correspondences) break;
+        double x[6];
+        if (!cm_align_solve(s, s + 21, x)) { flags |= CM_ALIGN_SINGULAR; break; }
+        cm_align_update(pose, x, pivot);
+        if (cm_align_norm3(x) < q.rot_eps && cm_align_norm3(x + 3) < q.trans_eps) { flags |= CM_ALIGN_CONVERGED; ++it; break; }
+    }
+    o->iterations = it;
+    if (q.max_iterations && it == q.max_iterations && !(flags & CM_ALIGN_CONVERGED)) flags |= CM_ALIGN_MAX_ITER_HIT;
+    if (const int e = evaluate()) return e;
+    prof_mark(c, "end");
+    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times_by_name(c);
+    if (o->n_corr < q.min_correspondences) flags |= CM_ALIGN_FEW;
+    o->flags = flags;
+    fit.have = true;
+    fit.n_src = n_src;
+    return CM_OK;
+}
+
+}  // namespace
+
+// Point-to-plane registration of a source cloud against the last result (cm_kernels_align.hip; the semantics are in
+// include/cloudmerge.h). The normals table first: the one the context holds for this result at normals_k, else normals()
+// with viewpoint 0 and search_cell 0. Then the search index over cluster_grid of the matching radius, once per call; the
+// bounds also give the pivot. Then the loop (fit_pose), per evaluation k_aln_eval. Reads `out` and nrm_entries. The stage
+// times are without those of a normals call it made; "aln_readback" is the round trip with the host's solve.
+int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src64, cm_align_result* out) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    const uint32_t n_src = static_cast<uint32_t>(n_src64);
+    SearchIndex& ix = c->aln;
+    PoseFit& fit = c->aln_fit;
+    fit.have = false;
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(out->pose, q.guess, sizeof out->pose);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n && !(c->nrm_have && c->nrm_k == q.normals_k)) {
+        cm_normal_params np{};
+        np.k = q.normals_k;
+        if (const int e = normals(c, np)) return e;
+    }
+    if (const int e = reserve_search_index(c, ix, 1, "cannot allocate the registration's search buffers",
+                                           "cannot allocate the registration's state")) return e;
+    if (const int e = fit.reserve(c, n_src64, sizeof(cm_align_corr), "cannot allocate the registration's state",
+                                  "cannot allocate the registration's correspondence table")) return e;
+    c->prof_used = 0;
+
+    CmClusterGridDev gd{};
+    if (n) {
+        // the search grid: over the centroids' own bounds, whose midpoint is the pivot
+        float mn[3], mx[3];
+        if (const int e = result_bounds(c, ix.bounds, mn, mx)) return e;
+        bounds_midpoint(mn, mx, out->pivot);
+        const ClusterGrid grid = cluster_grid(q.max_corr_dist, mn, mx, CM_ROW_TABLE_CAP);
+        if (const int e = build_search_index(c, ix, grid, mn, "cannot allocate the registration's row table")) return e;
+        HIP_TRY(c, hipGetLastError());
+        gd = ix.grid;
+    }
+
+    const float r2 = q.max_corr_dist * q.max_corr_dist;
+    const PairSort& so = ix.sort;
+    FitOutcome o{};
+    const int e = fit_pose(c, fit, {q.max_iterations, q.min_correspondences, q.rot_eps, q.trans_eps}, n_src, out->pose, out->pivot,
+                           [&](const CmAlignPoseDev& P) {
+                               prof_mark(c, "k_aln_eval");
+                               cmk_aln_eval(c->stream, ix.state, so.keys_a, so.keys_b, ix.pts, ix.rows, c->out, c->nrm_entries, src_dev,
+                                            n_src, n, gd, r2, P, fit.corr, fit.part);
+                           },
+                           "aln_readback", &o);
+    out->iterations = o.iterations;          // (an evaluation that failed leaves the updates applied so far)
+    if (e != CM_OK) return e;
+    std::memcpy(out->H, o.s, sizeof out->H);
+    std::memcpy(out->g, o.s + 21, sizeof out->g);
+    out->sse = o.s[27];
+    out->rms = o.n_corr ? std::sqrt(o.s[27] / static_cast<double>(o.n_corr)) : 0.0;
+    out->n_corr = o.n_corr;
+    out->flags = o.flags;
+    return CM_OK;
+}
+
+// NDT registration of a source cloud against the last result's covariance table (cm_kernels_ndt.hip; the semantics are in
+// include/cloudmerge.h). The table first: the one the context holds for this result at these parameters, else voxel_cov().
+// Then k_cl_bounds on the result for the pivot, one round trip per call. Then align()'s loop (fit_pose), per evaluation
+// k_ndt_eval. Reads `out`, out_key and cov_entries. Among the stage times "voxel_cov" is the covariance call it made (absent
+// when the table was held), "ndt_readback" the round trip with the host's solve.
+int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void* src_dev, uint64_t n_src64, cm_ndt_result* out) {
+    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    const uint32_t n_src = static_cast<uint32_t>(n_src64);
+    PoseFit& fit = c->ndt_fit;
+    fit.have = false;
+    // the constants of the score, PCL's gauss_d1 / gauss_d2 at the frame's voxel volume
+    const CmFrameDev& f = c->frame;
+    const float* const leaf = c->plan.params.leaf;
+    const double res3 = (static_cast<double>(leaf[0]) * static_cast<double>(leaf[1])) * static_cast<double>(leaf[2]);
+    const double p = static_cast<double>(q.outlier_ratio);
+    const double c1 = 10.0 * (1.0 - p), c2 = p / res3;
+    const double d3 = -std::log(c2);
+    const double d1 = -std::log(c1 + c2) - d3;
+    const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+    if (!(std::isfinite(d2) && d2 > 0.0)) return fail(c, CM_BAD_ARG, "the score's d2 is not finite and > 0 at this outlier_ratio and leaf");
+    const double d2h = d2 * 0.5;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->prof_used = 0;
+    if (n && !(c->cov_have && c->cov_min_points == cov.min_points && c->cov_eig_mult == cov.eig_mult)) {
+        prof_mark(c, "voxel_cov");                   // (there only when the call computed the table)
+        if (const int e = voxel_cov(c, cov)) return e;
+    }
+    if (const int e = fit.reserve(c, n_src64, sizeof(cm_ndt_corr), "cannot allocate the NDT registration's state",
+                                  "cannot allocate the NDT registration's correspondence table")) return e;
+    if (!c->ndt_bounds && !dev_alloc(&c->ndt_bounds, 6 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's state");
+    // nothing is refused from here on: a refused call leaves *out as it was
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(out->pose, q.guess, sizeof out->pose);
+    out->gauss_d1 = d1;
+    out->gauss_d2 = d2;
+
+    CmCovGridDev g{};
+    if (n) {
+        // the pivot: the midpoint of the centroids' own bounds
+        float mn[3], mx[3];
+        if (const int e = result_bounds(c, c->ndt_bounds, mn, mx)) return e;
+        bounds_midpoint(mn, mx, out->pivot);
+        // the grid of out_key, as voxel_cov hands it to k_cov_keys
+        for (int a = 0; a < 3; ++a) {
+            g.inv[a] = f.inv_leaf[a];
+            g.min_b[a] = c->cell_min_b[a];
+            g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
+        }
+    }
+
+    FitOutcome o{};
+    const int e = fit_pose(c, fit, {q.max_iterations, q.min_correspondences, q.rot_eps, q.trans_eps}, n_src, out->pose, out->pivot,
+                           [&](const CmAlignPoseDev& P) {
+                               prof_mark(c, "k_ndt_eval");
+                               cmk_ndt_eval(c->stream, c->out_key, n, c->cov_entries, src_dev, n_src, g, q.neighborhood, d2h, P, fit.corr,
+                                            fit.part);
+                           },
+                           "ndt_readback", &o);
+    out->iterations = o.iterations;          // (an evaluation that failed leaves the updates applied so far)
+    if (e != CM_OK) return e;
+    std::memcpy(out->H, o.s, sizeof out->H);
+    std::memcpy(out->g, o.s + 21, sizeof out->g);
+    out->score = o.s[27];
+    out->n_corr = o.n_corr;
+    out->flags = o.flags;
+    return CM_OK;
+}

@@ -1,5 +1,6 @@
 // cm_ctx.hpp — the context behind the C-ABI handle, shared by the host translation units (cm_api.cpp: entry points and
-// their argument checks; cm_launch.cpp: frame assembly and launch sequences; cm_route.cpp: the route policy).
+// their argument checks; cm_launch.cpp: frame assembly and the frame's launch sequences; cm_byproducts.cpp: the tables computed
+// from a result on request; cm_route.cpp: the route policy).
 //
 // Owns the HBM layout and the launch sequence; no arithmetic on points happens on the host. There is no
 // CPU fallback of any kind: without a gfx950 device cm_create fails.
@@ -51,6 +52,59 @@ struct Slot {
     uint64_t active_bytes_h2d = 0;
     uint64_t gen = 0, active_gen = 0;    // accepted submits so far; the one `active` came from
     uint32_t time_off = 0, time_type = CM_TIME_NONE;   // per-point time field (cm_set_sensor_time_field)
+};
+
+struct cm_ctx;
+
+// Buffers of an LSD radix sort of (key, value) pairs over nt tiles: ping-pong a -> b -> a ...; pass 0 reads the group totals
+// in grp0 (filled by the launch that made the keys), pass p > 0 those at grp_rest + (p - 1) * gw.
+struct SortPairs {
+    uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *hist, *totals, *grp0, *grp_rest;
+};
+
+// The HBM of one by-product's radix sort, grown with what it sorts (cm_byproducts.cpp).
+struct PairSort {
+    uint32_t cap_slots = 0;              // words of each keys / vals buffer (a multiple of CM_TILE)
+    uint32_t *keys_a = nullptr, *keys_b = nullptr, *vals_a = nullptr, *vals_b = nullptr;
+    uint32_t *hist = nullptr, *grp = nullptr;    // (cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
+    uint32_t* totals = nullptr;          // CM_RADIX digit totals (k_gscan)
+    // Room for n_slots pairs: beyond cap_slots everything is freed and allocated anew (`what`: the error text of a failure).
+    int reserve(cm_ctx* c, uint32_t n_slots, const char* what);
+    void release();
+    // gw: words of one pass's group totals in the sort at hand.
+    SortPairs pairs(uint32_t gw) const { return {keys_a, keys_b, vals_a, vals_b, hist, totals, grp, grp + gw}; }
+};
+
+// A result's centroids in the order of a search grid over their own bounds (k_cl_bounds, k_cl_keys, the radix passes,
+// k_cl_gather, cmk_sorted_rows): what the cluster extraction, the normals and the registration search in. The sorted keys lie
+// in sort.keys_a / keys_b (state says which), the grid is the caller's choice (cm_byproducts.cpp build_search_index).
+struct SearchIndex {
+    PairSort sort;
+    CmFrameState* state = nullptr;       // the sort's state record (the cluster call keeps a second one behind it)
+    uint32_t* bounds = nullptr;          // six order-images: min x, y, z, max x, y, z of the centroids
+    void* pts = nullptr;                 // the centroids in search-grid order (x, y, z, result index)
+    uint32_t* aux = nullptr;             // room for 3 x sort.cap_slots words: the three arrays k_cl_gather initialises for the
+                                         // cluster call, laid out at the n_slots of the build at hand (aux, aux + n_slots,
+                                         // aux + 2 n_slots), not at cap_slots
+    void* rows = nullptr;                // (y,z)-row ranges of the search grid
+    uint64_t cap_rows = 0;
+    CmClusterGridDev grid{};             // the grid of the last build, as the search kernels take it
+    void release();
+};
+
+// The state of a registration's Gauss-Newton loop (cm_byproducts.cpp fit_pose): align's and ndt's.
+struct PoseFit {
+    uint64_t cap_src = 0;                // source records corr and part are sized for
+    void* corr = nullptr;                // one correspondence per source record: the last evaluation's
+    double* part = nullptr;              // CM_ALIGN_STRIDE doubles per block of 256 source records
+    double* sums = nullptr;              // CM_ALIGN_SUMS doubles: what the host reads back per evaluation
+    void* src = nullptr;                 // the device copy of a host source (cap_src_host records of 16 bytes)
+    uint64_t cap_src_host = 0;
+    bool have = false;                   // corr holds the table of a call since the last merge, n_src entries
+    uint64_t n_src = 0;
+    // Room for n_src records of corr_bytes each (what_state, what_table: the error texts of a failure).
+    int reserve(cm_ctx* c, uint64_t n_src, size_t corr_bytes, const char* what_state, const char* what_table);
+    void release();
 };
 
 struct cm_ctx {
@@ -161,11 +215,9 @@ struct cm_ctx {
     // per-voxel covariance of the result (cm_kernels_cov.hip), on request after a frame: buffers of its own — no frame reads
     // them — allocated by the first request and grown with the frames. (The merged records go to `merged`, which
     // cm_merged_copy fills with the same bytes and which no frame reads either.)
-    uint32_t cov_cap_slots = 0;          // words of each keys / vals buffer
-    uint32_t *cov_keys_a = nullptr, *cov_keys_b = nullptr, *cov_vals_a = nullptr, *cov_vals_b = nullptr;
-    uint32_t *cov_hist = nullptr, *cov_grp = nullptr;    // (cov_cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
+    PairSort cov;                        // (voxel number, record index), cap_slots = the frame's padded points
     uint32_t* cov_tile_counts = nullptr; // cap_tiles words: cmk_merged's per-tile offsets
-    uint32_t* cov_words = nullptr;       // [0] merged records, [1] error word of k_cov_reduce, [2..257] digit totals (k_gscan)
+    uint32_t* cov_words = nullptr;       // [0] merged records, [1] error word of k_cov_reduce
     CmFrameState* cov_state = nullptr;   // the sort's state record
     void* cov_entries = nullptr;         // the table: cm_voxel_cov per voxel
     uint64_t cov_cap_entries = 0;
@@ -175,71 +227,39 @@ struct cm_ctx {
 
     // Euclidean cluster extraction on the result (cm_kernels_cluster.hip), on request after a frame: buffers of its own — no
     // frame reads them — allocated by the first request and grown with the results. It reads `out` (and out_cnt).
-    uint32_t cl_cap_slots = 0;           // words of each per-voxel buffer (a multiple of CM_TILE)
-    uint32_t *cl_keys_a = nullptr, *cl_keys_b = nullptr, *cl_vals_a = nullptr, *cl_vals_b = nullptr;
-    uint32_t *cl_hist = nullptr, *cl_grp = nullptr;      // (cl_cap_slots / CM_TILE) rows; CM_MAX_PASSES x groups rows
-    uint32_t *cl_parent = nullptr, *cl_root = nullptr, *cl_size = nullptr, *cl_npts = nullptr, *cl_num = nullptr;
+    SearchIndex cl;                      // two state records: the sort by cell, the sort by cluster number; its aux words are
+                                         // the union-find's parent, size and point count per voxel
+    uint32_t cl_cap_tables = 0;          // voxels the four tables below are sized for (a multiple of CM_TILE)
+    uint32_t *cl_root = nullptr, *cl_num = nullptr;
     uint32_t* cl_labels = nullptr;       // the label table
-    void* cl_pts = nullptr;              // the centroids in search-grid order (x, y, z, result index)
     void* cl_tile_sums = nullptr;        // per tile: kept roots and their voxels, then their exclusive prefixes
-    void* cl_rows = nullptr;             // (y,z)-row ranges of the search grid
-    uint64_t cl_cap_rows = 0;
-    uint32_t* cl_words = nullptr;        // [0] clusters, [1] clustered voxels, [2..7] bounds images, [8..263] digit totals (k_gscan)
-    CmFrameState* cl_state = nullptr;    // two records: the sort by cell, the sort by cluster number
+    uint32_t* cl_words = nullptr;        // [0] clusters, [1] clustered voxels
     void* cl_clusters = nullptr;         // the cluster table: cm_cluster per cluster
     uint64_t cl_cap_clusters = 0;
-    const uint32_t* cl_indices = nullptr;   // the member lists of the last call (one of cl_vals_a / cl_vals_b)
+    const uint32_t* cl_indices = nullptr;   // the member lists of the last call (one of cl.sort.vals_a / vals_b)
     uint64_t cl_n_clusters = 0, cl_n_clustered = 0;
 
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
-    uint32_t nrm_cap_slots = 0;          // words of each per-voxel buffer (a multiple of CM_TILE)
-    uint32_t *nrm_keys_a = nullptr, *nrm_keys_b = nullptr, *nrm_vals_a = nullptr, *nrm_vals_b = nullptr;
-    uint32_t *nrm_hist = nullptr, *nrm_grp = nullptr;
-    uint32_t* nrm_aux = nullptr;         // 3 x nrm_cap_slots words: what k_cl_gather initialises for the cluster call (unused here)
-    void* nrm_pts = nullptr;             // the centroids in search-grid order (x, y, z, result index)
-    void* nrm_list = nullptr;            // nrm_cap_slots x 8 B: the centroids the first search launch could not finish
-    void* nrm_rows = nullptr;            // (y,z)-row ranges of the search grid
-    uint64_t nrm_cap_rows = 0;
-    uint32_t* nrm_words = nullptr;       // [0] list count, [2..7] bounds images, [8..263] digit totals (k_gscan)
-    CmFrameState* nrm_state = nullptr;   // the sort's state record
-    void* nrm_entries = nullptr;         // the table: cm_voxel_normal per voxel (nrm_cap_slots entries)
+    SearchIndex nrm;
+    uint32_t nrm_cap_tables = 0;         // voxels the list and the table are sized for (a multiple of CM_TILE)
+    void* nrm_list = nullptr;            // 8 B per voxel: the centroids the first search launch could not finish
+    uint32_t* nrm_words = nullptr;       // [0] list count, [1] unused
+    void* nrm_entries = nullptr;         // the table: cm_voxel_normal per voxel
     uint32_t nrm_n_listed = 0;           // centroids the last call's second launch took
     bool nrm_have = false;               // nrm_entries holds the table of the result at rest, computed with k = nrm_k:
     uint32_t nrm_k = 0;                  // set by normals(), cleared where a merge invalidates the result
 
     // Registration of a source cloud against the result (cm_kernels_align.hip), on request after a frame: the cluster call's
-    // front end on buffers and a state record of its own, as the normals' — no frame reads them — allocated by the first
-    // request and grown with the results and the sources. It reads `out` and nrm_entries.
-    uint32_t aln_cap_slots = 0;          // words of each per-voxel buffer (a multiple of CM_TILE)
-    uint32_t *aln_keys_a = nullptr, *aln_keys_b = nullptr, *aln_vals_a = nullptr, *aln_vals_b = nullptr;
-    uint32_t *aln_hist = nullptr, *aln_grp = nullptr;
-    uint32_t* aln_aux = nullptr;         // 3 x aln_cap_slots words: what k_cl_gather initialises for the cluster call (unused here)
-    void* aln_pts = nullptr;             // the centroids in search-grid order (x, y, z, result index)
-    void* aln_rows = nullptr;            // (y,z)-row ranges of the search grid
-    uint64_t aln_cap_rows = 0;
-    uint32_t* aln_words = nullptr;       // [2..7] bounds images, [8..263] digit totals (k_gscan)
-    CmFrameState* aln_state = nullptr;   // the sort's state record
-    uint64_t aln_cap_src = 0;            // source records aln_corr and aln_part are sized for
-    void* aln_corr = nullptr;            // cm_align_corr per source record: the last evaluation's
-    double* aln_part = nullptr;          // CM_ALIGN_STRIDE doubles per block of 256 source records
-    double* aln_sums = nullptr;          // CM_ALIGN_SUMS doubles: what the host reads back per evaluation
-    void* aln_src = nullptr;             // cm_result_align's device copy of a host source (aln_cap_src_host records)
-    uint64_t aln_cap_src_host = 0;
-    bool aln_have = false;               // aln_corr holds the table of a call since the last merge, aln_n_src entries
-    uint64_t aln_n_src = 0;
+    // front end on an index of its own — no frame reads it — allocated by the first request and grown with the results and
+    // the sources. It reads `out` and nrm_entries.
+    SearchIndex aln;
+    PoseFit aln_fit;                     // cm_align_corr per source record
 
     // NDT registration of a source cloud against the covariance table (cm_kernels_ndt.hip), on request after a frame: reads
     // out, out_key and cov_entries; these buffers are the call's own.
-    uint64_t ndt_cap_src = 0;            // source records ndt_corr and ndt_part are sized for
-    void* ndt_corr = nullptr;            // cm_ndt_corr per source record: the last evaluation's
-    double* ndt_part = nullptr;          // CM_ALIGN_STRIDE doubles per block of 256 source records
-    double* ndt_sums = nullptr;          // CM_ALIGN_SUMS doubles: what the host reads back per evaluation
-    uint32_t* ndt_words = nullptr;       // [2..7] bounds images (k_cl_bounds)
-    void* ndt_src = nullptr;             // cm_result_ndt_align's device copy of a host source (ndt_cap_src_host records)
-    uint64_t ndt_cap_src_host = 0;
-    bool ndt_have = false;               // ndt_corr holds the table of a call since the last merge, ndt_n_src entries
-    uint64_t ndt_n_src = 0;
+    PoseFit ndt_fit;                     // cm_ndt_corr per source record
+    uint32_t* ndt_bounds = nullptr;      // six bounds images (k_cl_bounds)
 
     // statistical outlier removal (cm_kernels_sor.hip): sorts by the outlier stage's grid (sorted_pts, rows, d_state_o) and
     // leaves its keep-mask in `mask`; its own buffers are allocated by the first cm_set_statistical_outlier
@@ -291,13 +311,22 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode = 0, const float* bounds = n
 int wait_frame(cm_ctx* c, cm_result* res);
 int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_entries, uint32_t n_tables, const cm_params* p,
                  cm_result* res);
+void prof_mark(cm_ctx* c, const char* name);
+// scatter_mark: the prof_mark name of the scatter (the histogram and scan passes get theirs); nullptr: no marks.
+void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t n_pass, uint32_t nt, uint32_t n_slots,
+                      bool lds_rank, uint32_t* tile_kept, const char* scatter_mark);
+
+// cm_byproducts.cpp: the tables computed from the last result on request. Called with merge_mu held.
+// The tables of the last result go with it (where a merge replaces the result).
+inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = false; }
+// The covariance table of the last result (cov_entries, n_out entries).
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 // The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
 int clusters(cm_ctx* c, const cm_cluster_params& q);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
-// Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_corr.
+// Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.
 int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src, cm_align_result* out);
 // NDT registration of the n_src source records at src_dev against the last result's covariance table at cov (resolved, never
-// {0, 0}): *out, and the correspondences in ndt_corr.
+// {0, 0}): *out, and the correspondences in ndt_fit.corr.
 int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void* src_dev, uint64_t n_src, cm_ndt_result* out);

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(64) void k_aln_sum(const double* __restrict__ parti
 #define CM_LAUNCH(kernel, grid, block, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
-// cm_launch.cpp align. corr: n_src entries of 8 bytes; partials: ceil(n_src / 256) * CM_ALIGN_STRIDE doubles; sums:
+// cm_byproducts.cpp align. corr: n_src entries of 8 bytes; partials: ceil(n_src / 256) * CM_ALIGN_STRIDE doubles; sums:
 // CM_ALIGN_SUMS doubles. n_src 0: no launch of k_aln_eval, and the sums are those of no block (zeros).
 void cmk_aln_eval(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
                   const void* rows, const void* recs, const void* normals, const void* src, uint32_t n_src, uint32_t n_tgt,

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_ndt_eval(const uint32_t* __restric
 
 }  // namespace
 
-// cm_launch.cpp ndt. corr: n_src entries of 16 bytes; partials: ceil(n_src / 256) * CM_ALIGN_STRIDE doubles, summed by
+// cm_byproducts.cpp ndt. corr: n_src entries of 16 bytes; partials: ceil(n_src / 256) * CM_ALIGN_STRIDE doubles, summed by
 // cmk_aln_sum. n_src 0: no launch. n_out 0: nothing is looked up, and out_key and cov are not read.
 void cmk_ndt_eval(hipStream_t s, const uint32_t* out_key, uint32_t n_out, const void* cov, const void* src, uint32_t n_src,
                   const CmCovGridDev& g, uint32_t neighborhood, double d2h, const CmAlignPoseDev& pose, void* corr,

@@ -248,7 +248,7 @@ __global__ __launch_bounds__(LANES) void k_nrm_knn(const CmFrameState* __restric
 #define CM_LAUNCH(kernel, grid, block, stream, ...) \
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
-// cm_launch.cpp normals: *list_n zeroed before the first launch; list = n uint2; out = n entries of 32 bytes. n_items: the
+// cm_byproducts.cpp normals: *list_n zeroed before the first launch; list = n uint2; out = n entries of 32 bytes. n_items: the
 // centroids (first) or the length of the list the first launch left.
 void cmk_nrm_knn(hipStream_t s, const CmFrameState* st, const uint32_t* keys_a, const uint32_t* keys_b, const void* pts,
                  const void* rows, const void* recs, const CmClusterGridDev& g, uint32_t n, uint32_t k, const float viewpoint[3],

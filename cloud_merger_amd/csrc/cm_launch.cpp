@@ -1,17 +1,14 @@
-// cm_launch.cpp — frame assembly and the launch sequences: the general path (cm_kernels.hip, with the ground and outlier
-// pre-stages), the bucket path's fixed-grid and quantile passes (cm_kernels_v2/v3/v4.hip), the replays of a frame the bucket
-// path hands back, the table merge, the covariance sort and the cluster extraction. Which route a frame takes is decided in cm_route.cpp: everything
-// here reads c->plan.
+// cm_launch.cpp — frame assembly and the frame's launch sequences: the general path (cm_kernels.hip, with the ground and
+// outlier pre-stages), the bucket path's fixed-grid and quantile passes (cm_kernels_v2/v3/v4.hip), the replays of a frame the
+// bucket path hands back, and the table merge. Which route a frame takes is decided in cm_route.cpp: everything here reads
+// c->plan. What is computed from a result afterwards, on request, is cm_byproducts.cpp's.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 
-#include "cm_align_solve.hpp"
 #include "cm_ctx.hpp"
-
-namespace {
 
 void prof_mark(cm_ctx* c, const char* name) {
     if (!(c->flags & CM_FLAG_PROFILE)) return;
@@ -25,6 +22,8 @@ void prof_mark(cm_ctx* c, const char* name) {
     (void)hipEventRecord(c->prof_ev[c->prof_used], c->stream);
     ++c->prof_used;
 }
+
+namespace {
 
 // Records c->frame as the descriptor HBM holds. true: it differs from the one uploaded last, and the caller uploads it (or
 // hands do_setup to a first pass that does).
@@ -62,13 +61,8 @@ int end_frame(cm_ctx* c) {
     return CM_OK;
 }
 
-// Buffers of an LSD radix sort of (key, value) pairs over nt tiles: ping-pong a -> b -> a ...; pass 0 reads the group totals
-// in grp0 (filled by the launch that made the keys), pass p > 0 those at grp_rest + (p - 1) * gw.
-struct SortPairs {
-    uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *hist, *totals, *grp0, *grp_rest;
-};
+}  // namespace
 
-// scatter_mark: the prof_mark name of the scatter (the histogram and scan passes get theirs); nullptr: no marks.
 void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t n_pass, uint32_t nt, uint32_t n_slots,
                       bool lds_rank, uint32_t* tile_kept, const char* scatter_mark) {
     const uint32_t n_groups = (nt + CM_GROUP - 1) / CM_GROUP, gw = n_groups * CM_RADIX;
@@ -88,6 +82,8 @@ void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t 
                     lds_rank, tile_kept);
     }
 }
+
+namespace {
 
 // The record passes of the bucket kernels behind k2_hist0 — the voxel stage, or the outlier stage's sort by the radius
 // grid: pass p scatters by the key bits low + 8 p; the passes behind the first run over grids of nt_later tiles. The
@@ -686,10 +682,7 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
         f.outlier_min_nb = o_min_nb;
     }
     c->have_result = false;
-    c->nrm_have = false;                             // (the tables of the last result go with it)
-    c->aln_have = false;
-    c->cov_have = false;
-    c->ndt_have = false;
+    invalidate_result_tables(c);
     c->last_mode = mode;
     c->bytes_d2h = 0;
     if (c->pub_pending[0]) {
@@ -900,10 +893,7 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     r.n_sensors = n_tables;
     r.n_in = total;
     c->have_result = false;
-    c->nrm_have = false;
-    c->aln_have = false;
-    c->cov_have = false;
-    c->ndt_have = false;
+    invalidate_result_tables(c);
     c->last_mode = 2;
     c->prof_used = 0;
     if (f.n_padded == 0) {
@@ -954,607 +944,4 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     c->have_result = true;
     if (res) *res = r;
     return r.status;
-}
-
-// The per-voxel covariance table of the last result into c->cov_entries (cm_kernels_cov.hip). Launches on the context's
-// stream, reads what the frame left (descriptor, mask, out_key / out_cnt, cell grid) and writes only the cov_* buffers and
-// `merged`: nothing a later frame reads.
-int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
-    const uint64_t n_out = c->result.n_out;
-    c->cov_have = false;
-    if (n_out == 0) return CM_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
-    if (n_out > c->cov_cap_entries) {
-        if (c->cov_entries) { (void)hipFree(c->cov_entries); c->cov_entries = nullptr; c->cov_cap_entries = 0; }
-        if (!A(&c->cov_entries, n_out * sizeof(cm_voxel_cov))) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance table");
-        c->cov_cap_entries = n_out;
-    }
-    const CmFrameDev& f = c->frame;
-    const uint32_t nt = f.n_tiles, n_slots = f.n_padded;
-    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
-    if (n_slots > c->cov_cap_slots) {
-        uint32_t** bufs[] = {&c->cov_keys_a, &c->cov_keys_b, &c->cov_vals_a, &c->cov_vals_b, &c->cov_hist, &c->cov_grp};
-        for (uint32_t** b : bufs) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        c->cov_cap_slots = 0;
-        const size_t tiles = n_slots / CM_TILE, groups = (tiles + CM_GROUP - 1) / CM_GROUP;
-        bool ok = true;
-        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(bufs[k]), static_cast<size_t>(n_slots) * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->cov_hist), tiles * CM_RADIX * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->cov_grp), CM_MAX_PASSES * groups * CM_RADIX * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's buffers");
-        c->cov_cap_slots = n_slots;
-    }
-    if (!c->cov_state) {
-        bool ok = A(reinterpret_cast<void**>(&c->cov_state), sizeof(CmFrameState)) &&
-                  A(reinterpret_cast<void**>(&c->cov_tile_counts), static_cast<size_t>(c->cap_tiles) * 4) &&
-                  A(reinterpret_cast<void**>(&c->cov_words), (2 + CM_RADIX) * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's state");
-    }
-    if (!c->merged) HIP_TRY(c, hipMalloc(&c->merged, static_cast<size_t>(c->cap_padded) * 16));
-    hipStream_t st = c->stream;
-    // the kept points in (sensor, point) order, as cm_merged_copy returns them
-    cmk_merged(st, c->d_frame, c->cov_tile_counts, c->cov_words, c->merged, nt, c->frame_mask);
-    // (voxel number, record index) pairs, sorted by voxel number: as many 8-bit passes as the numbers need
-    const uint32_t passes = (key_width(n_out) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
-    CmCovGridDev g;
-    for (int a = 0; a < 3; ++a) {
-        g.inv[a] = f.inv_leaf[a];
-        g.min_b[a] = c->cell_min_b[a];
-        g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
-    }
-    HIP_TRY(c, hipMemsetAsync(c->cov_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
-    HIP_TRY(c, hipMemsetAsync(c->cov_words + 1, 0, 4, st));
-    cmk_cov_keys(st, c->merged, c->cov_words, g, c->out_key, static_cast<uint32_t>(n_out), passes, c->cov_state, c->cov_keys_a,
-                 c->cov_hist, c->cov_grp, nt);
-    // ballot ranking whatever the context's probe found: stable by construction, the sums' order depends on it
-    radix_sort_pairs(c, c->cov_state, {c->cov_keys_a, c->cov_keys_b, c->cov_vals_a, c->cov_vals_b, c->cov_hist, c->cov_words + 2,
-                                       c->cov_grp, c->cov_grp + gw}, passes, nt, n_slots, false, nullptr, nullptr);
-    cmk_cov_reduce(st, c->merged, c->cov_state, c->cov_keys_a, c->cov_vals_a, c->cov_keys_b, c->cov_vals_b, c->out_cnt,
-                   static_cast<uint32_t>(n_out), q.min_points, q.eig_mult, c->cov_entries, c->cov_words + 1);
-    HIP_TRY(c, hipGetLastError());
-    uint32_t err = 0;
-    HIP_TRY(c, hipMemcpyAsync(&err, c->cov_words + 1, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (err) return fail(c, CM_INTERNAL, "covariance: a voxel's points did not match its count in the result");
-    c->cov_have = true;                              // (what ndt() may reuse)
-    c->cov_min_points = q.min_points;
-    c->cov_eig_mult = q.eig_mult;
-    return CM_OK;
-}
-
-namespace {
-
-// Host inverse of the kernels' order-preserving float image (k_cl_bounds).
-float ord_to_float(uint32_t o) {
-    const uint32_t b = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
-
-// The stages a by-product marked (prof_mark) into c->stage_times, as wait_frame does for a frame's.
-void collect_stage_times(cm_ctx* c) {
-    if (!(c->flags & CM_FLAG_PROFILE)) return;
-    cm_stage_times& t = c->stage_times;
-    std::memset(&t, 0, sizeof t);
-    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
-    for (size_t i = 0; i < n && i < CM_MAX_STAGES; ++i) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
-        std::snprintf(t.name[i], sizeof t.name[i], "%s", c->prof_names[i].c_str());
-        t.ms[i] = ms;
-        t.n_stages = static_cast<uint32_t>(i + 1);
-    }
-}
-
-}  // namespace
-
-// Euclidean cluster extraction on the last result (cm_kernels_cluster.hip): labels, cluster table and member lists into the
-// cl_* buffers. Launches on the context's stream, reads `out` — what cm_result_copy reads — and out_cnt where the context
-// keeps it, and writes only the cl_* buffers: nothing a later frame reads. Two host round trips: the bounds of the
-// centroids (the search grid is decided on the host, cluster_grid) and the cluster count (the second sort's passes, the
-// table's size). Under CM_FLAG_PROFILE the stage times of the call replace the frame's in cm_get_stage_times.
-int clusters(cm_ctx* c, const cm_cluster_params& q) {
-    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
-    c->cl_n_clusters = 0;
-    c->cl_n_clustered = 0;
-    c->cl_indices = nullptr;
-    if (n == 0) return CM_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
-    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
-    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
-    if (n_slots > c->cl_cap_slots) {
-        uint32_t** words[] = {&c->cl_keys_a, &c->cl_keys_b, &c->cl_vals_a, &c->cl_vals_b, &c->cl_parent, &c->cl_root,
-                              &c->cl_size,   &c->cl_npts,   &c->cl_num,    &c->cl_labels, &c->cl_hist,   &c->cl_grp};
-        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        if (c->cl_pts) { (void)hipFree(c->cl_pts); c->cl_pts = nullptr; }
-        if (c->cl_tile_sums) { (void)hipFree(c->cl_tile_sums); c->cl_tile_sums = nullptr; }
-        c->cl_cap_slots = 0;
-        bool ok = true;
-        for (int k = 0; k < 10; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->cl_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->cl_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
-        ok = ok && A(&c->cl_pts, static_cast<size_t>(n_slots) * 16);
-        ok = ok && A(&c->cl_tile_sums, static_cast<size_t>(nt) * 8);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's buffers");
-        c->cl_cap_slots = n_slots;
-    }
-    if (!c->cl_state) {
-        bool ok = A(reinterpret_cast<void**>(&c->cl_state), 2 * sizeof(CmFrameState)) &&
-                  A(reinterpret_cast<void**>(&c->cl_words), (8 + CM_RADIX) * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's state");
-    }
-    hipStream_t st = c->stream;
-    uint32_t* const w = c->cl_words;
-    SortPairs sp = {c->cl_keys_a, c->cl_keys_b, c->cl_vals_a, c->cl_vals_b, c->cl_hist, w + 8, c->cl_grp, c->cl_grp + gw};
-    c->prof_used = 0;
-
-    // the search grid: over the centroids' own bounds
-    prof_mark(c, "k_cl_bounds");
-    HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
-    HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
-    cmk_cl_bounds(st, c->out, n, w + 2);
-    uint32_t img[6];
-    HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
-    const ClusterGrid grid = cluster_grid(q.tolerance, mn, mx, CM_ROW_TABLE_CAP);
-    const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
-    if (n_rows > c->cl_cap_rows) {
-        if (c->cl_rows) { (void)hipFree(c->cl_rows); c->cl_rows = nullptr; c->cl_cap_rows = 0; }
-        if (!A(&c->cl_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's row table");
-        c->cl_cap_rows = n_rows;
-    }
-    CmClusterGridDev gd;
-    for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
-    gd.inv = grid.inv;
-
-    // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
-    CmFrameState* st_cell = c->cl_state;
-    CmFrameState* st_num = c->cl_state + 1;
-    const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
-    HIP_TRY(c, hipMemsetAsync(c->cl_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
-    prof_mark(c, "k_cl_keys");
-    cmk_cl_keys(st, c->out, n, gd, passes, st_cell, c->cl_keys_a, c->cl_hist, c->cl_grp, nt);
-    radix_sort_pairs(c, st_cell, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
-    prof_mark(c, "k_cl_gather");
-    cmk_cl_gather(st, c->out, st_cell, c->cl_vals_a, c->cl_vals_b, n, c->cl_pts, c->cl_parent, c->cl_size, c->cl_npts);
-    prof_mark(c, "cl_rows");
-    cmk_sorted_rows(st, nullptr, st_cell, c->cl_keys_a, c->cl_vals_a, c->cl_keys_b, c->cl_vals_b, c->cl_pts, c->cl_rows, n_slots, true);
-
-    // connected components, sizes, the roots the size filter keeps
-    const float tol2 = q.tolerance * q.tolerance;
-    prof_mark(c, "k_cl_hook");
-    cmk_cl_hook(st, st_cell, c->cl_keys_a, c->cl_keys_b, c->cl_pts, c->cl_rows, n, tol2, c->cl_parent);
-    prof_mark(c, "k_cl_roots");
-    cmk_cl_roots(st, c->cl_parent, (c->flags & CM_FLAG_OCCUPANCY) ? c->out_cnt : nullptr, n, c->cl_root, c->cl_size, c->cl_npts);
-    prof_mark(c, "k_cl_count");
-    cmk_cl_count(st, c->cl_root, c->cl_size, n, q.min_cluster_size, q.max_cluster_size, c->cl_tile_sums, w, nt);
-    HIP_TRY(c, hipGetLastError());
-    uint32_t counts[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    const uint32_t n_clusters = counts[0];
-    if (n_clusters > c->cl_cap_clusters) {
-        if (c->cl_clusters) { (void)hipFree(c->cl_clusters); c->cl_clusters = nullptr; c->cl_cap_clusters = 0; }
-        if (!A(&c->cl_clusters, static_cast<size_t>(n_clusters) * sizeof(cm_cluster))) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster table");
-        c->cl_cap_clusters = n_clusters;
-    }
-
-    // numbers, labels, AABB, and the member lists: (cluster number, voxel index) sorted by cluster number, stable
-    const uint32_t passes_num = (key_width(n_clusters ? n_clusters : 1u) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
-    prof_mark(c, "k_cl_number");
-    cmk_cl_number(st, c->cl_root, c->cl_size, c->cl_npts, c->cl_tile_sums, n, q.min_cluster_size, q.max_cluster_size, c->cl_num,
-                  c->cl_clusters, nt);
-    HIP_TRY(c, hipMemsetAsync(c->cl_grp, 0, static_cast<size_t>(passes_num) * gw * 4, st));
-    prof_mark(c, "k_cl_labels");
-    cmk_cl_labels(st, c->out, c->cl_root, c->cl_num, n, passes_num, st_num, c->cl_labels, c->cl_keys_a, c->cl_hist, c->cl_grp,
-                  c->cl_clusters, nt);
-    if (n_clusters) {
-        radix_sort_pairs(c, st_num, sp, passes_num, nt, n_slots, false, nullptr, "k_scatter(lists)");
-        prof_mark(c, "k_cl_decode");
-        cmk_cl_decode(st, c->cl_clusters, n_clusters);
-    }
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    c->cl_n_clusters = n_clusters;
-    c->cl_n_clustered = counts[1];
-    c->cl_indices = (passes_num & 1u) ? c->cl_vals_b : c->cl_vals_a;
-    return CM_OK;
-}
-
-// Normals and curvature of the last result (cm_kernels_normals.hip): one cm_voxel_normal per result record into nrm_entries.
-// The cluster call's front end — bounds, the search grid decided on the host (normals_grid), keys, radix passes, gather, row
-// table — on buffers and a state record of this call's own, then the exact k-nearest-neighbour search in two launches. Reads
-// `out` and writes only the nrm_* buffers: nothing a later frame reads. Two host round trips: the bounds of the centroids
-// and the length of the second launch's list (an empty list costs no launch). Under CM_FLAG_PROFILE the stage times of the
-// call replace the frame's in cm_get_stage_times; the second launch's stage is named "k_nrm_rings n=<centroids it took>".
-int normals(cm_ctx* c, const cm_normal_params& q) {
-    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
-    c->nrm_n_listed = 0;
-    c->nrm_have = false;
-    if (n == 0) return CM_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
-    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
-    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
-    if (n_slots > c->nrm_cap_slots) {
-        uint32_t** words[] = {&c->nrm_keys_a, &c->nrm_keys_b, &c->nrm_vals_a, &c->nrm_vals_b, &c->nrm_hist, &c->nrm_grp, &c->nrm_aux};
-        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        void** blocks[] = {&c->nrm_pts, &c->nrm_list, &c->nrm_entries};
-        for (void** b : blocks) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        c->nrm_cap_slots = 0;
-        bool ok = true;
-        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->nrm_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->nrm_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->nrm_aux), static_cast<size_t>(n_slots) * 12);
-        ok = ok && A(&c->nrm_pts, static_cast<size_t>(n_slots) * 16);
-        ok = ok && A(&c->nrm_list, static_cast<size_t>(n_slots) * 8);
-        ok = ok && A(&c->nrm_entries, static_cast<size_t>(n_slots) * sizeof(cm_voxel_normal));
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's buffers");
-        c->nrm_cap_slots = n_slots;
-    }
-    if (!c->nrm_state) {
-        bool ok = A(reinterpret_cast<void**>(&c->nrm_state), sizeof(CmFrameState)) &&
-                  A(reinterpret_cast<void**>(&c->nrm_words), (8 + CM_RADIX) * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's state");
-    }
-    hipStream_t st = c->stream;
-    uint32_t* const w = c->nrm_words;
-    SortPairs sp = {c->nrm_keys_a, c->nrm_keys_b, c->nrm_vals_a, c->nrm_vals_b, c->nrm_hist, w + 8, c->nrm_grp, c->nrm_grp + gw};
-    c->prof_used = 0;
-
-    // the search grid: over the centroids' own bounds
-    prof_mark(c, "k_cl_bounds");
-    HIP_TRY(c, hipMemsetAsync(w, 0, 8, st));
-    HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
-    HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
-    cmk_cl_bounds(st, c->out, n, w + 2);
-    uint32_t img[6];
-    HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    float mn[3], mx[3];
-    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
-    const ClusterGrid grid = normals_grid(q.search_cell, c->plan.params.leaf, q.k, mn, mx, CM_ROW_TABLE_CAP);
-    const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
-    if (n_rows > c->nrm_cap_rows) {
-        if (c->nrm_rows) { (void)hipFree(c->nrm_rows); c->nrm_rows = nullptr; c->nrm_cap_rows = 0; }
-        if (!A(&c->nrm_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's row table");
-        c->nrm_cap_rows = n_rows;
-    }
-    CmClusterGridDev gd;
-    for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
-    gd.inv = grid.inv;
-
-    // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
-    const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
-    HIP_TRY(c, hipMemsetAsync(c->nrm_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
-    prof_mark(c, "k_cl_keys");
-    cmk_cl_keys(st, c->out, n, gd, passes, c->nrm_state, c->nrm_keys_a, c->nrm_hist, c->nrm_grp, nt);
-    radix_sort_pairs(c, c->nrm_state, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
-    prof_mark(c, "k_cl_gather");
-    cmk_cl_gather(st, c->out, c->nrm_state, c->nrm_vals_a, c->nrm_vals_b, n, c->nrm_pts, c->nrm_aux, c->nrm_aux + n_slots,
-                  c->nrm_aux + 2 * static_cast<size_t>(n_slots));
-    prof_mark(c, "cl_rows");
-    cmk_sorted_rows(st, nullptr, c->nrm_state, c->nrm_keys_a, c->nrm_vals_a, c->nrm_keys_b, c->nrm_vals_b, c->nrm_pts, c->nrm_rows,
-                    n_slots, true);
-
-    // the neighbourhoods and the planes: the 3x3x3 cells first, then whoever needs more, ring by ring
-    prof_mark(c, "k_nrm_knn(block)");
-    cmk_nrm_knn(st, c->nrm_state, c->nrm_keys_a, c->nrm_keys_b, c->nrm_pts, c->nrm_rows, c->out, gd, n, q.k, q.viewpoint,
-                c->nrm_entries, c->nrm_list, w, n, true);
-    HIP_TRY(c, hipGetLastError());
-    uint32_t listed = 0;
-    HIP_TRY(c, hipMemcpyAsync(&listed, w, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    if (listed > n) return fail(c, CM_INTERNAL, "normals: the first search launch listed more centroids than the result holds");
-    if (listed) {
-        char name[24];                                    // (the stage's name carries the length of its list: 24 bytes with the NUL)
-        std::snprintf(name, sizeof name, "k_nrm_rings n=%u", listed);
-        prof_mark(c, name);
-        cmk_nrm_knn(st, c->nrm_state, c->nrm_keys_a, c->nrm_keys_b, c->nrm_pts, c->nrm_rows, c->out, gd, n, q.k, q.viewpoint,
-                    c->nrm_entries, c->nrm_list, w, listed, false);
-    }
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    c->nrm_n_listed = listed;
-    c->nrm_have = true;
-    c->nrm_k = q.k;
-    return CM_OK;
-}
-
-namespace {
-
-// The stages an iterated by-product marked, one entry per name in order of first appearance, the milliseconds of equally
-// named stages added up (collect_stage_times lists every launch; a registration has up to 65 evaluations).
-void collect_stage_times_by_name(cm_ctx* c) {
-    if (!(c->flags & CM_FLAG_PROFILE)) return;
-    cm_stage_times& t = c->stage_times;
-    std::memset(&t, 0, sizeof t);
-    const size_t n = c->prof_used ? c->prof_used - 1 : 0;
-    for (size_t i = 0; i < n; ++i) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->prof_ev[i], c->prof_ev[i + 1]);
-        char name[sizeof t.name[0]];
-        std::snprintf(name, sizeof name, "%s", c->prof_names[i].c_str());
-        uint32_t k = 0;
-        while (k < t.n_stages && std::strcmp(t.name[k], name) != 0) ++k;
-        if (k == CM_MAX_STAGES) continue;
-        if (k == t.n_stages) { std::memcpy(t.name[k], name, sizeof name); ++t.n_stages; }
-        t.ms[k] += ms;
-    }
-}
-
-}  // namespace
-
-// Point-to-plane registration of a source cloud against the last result (cm_kernels_align.hip; the semantics are in
-// include/cloudmerge.h). The normals table first: the one the context holds for this result at normals_k, else normals()
-// with viewpoint 0 and search_cell 0. Then the cluster call's front end — bounds, the search grid decided on the host
-// (cluster_grid of the matching radius), keys, radix passes, gather, row table — on buffers and a state record of this
-// call's own, once per call; the bounds also give the pivot. Then the loop: per evaluation k_aln_eval, k_aln_sum and one
-// host round trip of 28 doubles and a count; the solve and the pose update are cm_align_solve.hpp's. Reads `out` and
-// nrm_entries and writes only the aln_* buffers: nothing a later frame reads. Under CM_FLAG_PROFILE the stage times of the
-// call (without those of a normals call it made) replace the frame's, one entry per name, summed over the evaluations;
-// "aln_readback" is the round trip with the host's solve.
-int align(cm_ctx* c, const cm_align_params& q, const void* src_dev, uint64_t n_src64, cm_align_result* out) {
-    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
-    const uint32_t n_src = static_cast<uint32_t>(n_src64);
-    c->aln_have = false;
-    std::memset(out, 0, sizeof *out);
-    std::memcpy(out->pose, q.guess, sizeof out->pose);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (n && !(c->nrm_have && c->nrm_k == q.normals_k)) {
-        cm_normal_params np{};
-        np.k = q.normals_k;
-        if (const int e = normals(c, np)) return e;
-    }
-    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
-    const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
-    const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
-    if (n_slots > c->aln_cap_slots) {
-        uint32_t** words[] = {&c->aln_keys_a, &c->aln_keys_b, &c->aln_vals_a, &c->aln_vals_b, &c->aln_hist, &c->aln_grp, &c->aln_aux};
-        for (uint32_t** b : words) if (*b) { (void)hipFree(*b); *b = nullptr; }
-        if (c->aln_pts) { (void)hipFree(c->aln_pts); c->aln_pts = nullptr; }
-        c->aln_cap_slots = 0;
-        bool ok = true;
-        for (int k = 0; k < 4; ++k) ok = ok && A(reinterpret_cast<void**>(words[k]), static_cast<size_t>(n_slots) * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->aln_hist), static_cast<size_t>(nt) * CM_RADIX * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->aln_grp), static_cast<size_t>(CM_MAX_PASSES) * gw * 4);
-        ok = ok && A(reinterpret_cast<void**>(&c->aln_aux), static_cast<size_t>(n_slots) * 12);
-        ok = ok && A(&c->aln_pts, static_cast<size_t>(n_slots) * 16);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's search buffers");
-        c->aln_cap_slots = n_slots;
-    }
-    if (!c->aln_state) {
-        bool ok = A(reinterpret_cast<void**>(&c->aln_state), sizeof(CmFrameState)) &&
-                  A(reinterpret_cast<void**>(&c->aln_words), (8 + CM_RADIX) * 4) &&
-                  A(reinterpret_cast<void**>(&c->aln_sums), CM_ALIGN_SUMS * sizeof(double));
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's state");
-    }
-    const uint32_t n_blocks = (n_src + CM_BLOCK - 1) / CM_BLOCK;
-    if (n_src64 > c->aln_cap_src) {
-        if (c->aln_corr) { (void)hipFree(c->aln_corr); c->aln_corr = nullptr; }
-        if (c->aln_part) { (void)hipFree(c->aln_part); c->aln_part = nullptr; }
-        c->aln_cap_src = 0;
-        bool ok = A(&c->aln_corr, static_cast<size_t>(n_src) * sizeof(cm_align_corr)) &&
-                  A(reinterpret_cast<void**>(&c->aln_part), static_cast<size_t>(n_blocks) * CM_ALIGN_STRIDE * sizeof(double));
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's correspondence table");
-        c->aln_cap_src = n_src64;
-    }
-    hipStream_t st = c->stream;
-    uint32_t* const w = c->aln_words;
-    c->prof_used = 0;
-
-    CmClusterGridDev gd{};
-    if (n) {
-        SortPairs sp = {c->aln_keys_a, c->aln_keys_b, c->aln_vals_a, c->aln_vals_b, c->aln_hist, w + 8, c->aln_grp, c->aln_grp + gw};
-        // the search grid: over the centroids' own bounds, whose midpoint is the pivot
-        prof_mark(c, "k_cl_bounds");
-        HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
-        HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
-        cmk_cl_bounds(st, c->out, n, w + 2);
-        uint32_t img[6];
-        HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        float mn[3], mx[3];
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]);
-            out->pivot[a] = static_cast<double>(mn[a]) + (static_cast<double>(mx[a]) - static_cast<double>(mn[a])) * 0.5;
-        }
-        const ClusterGrid grid = cluster_grid(q.max_corr_dist, mn, mx, CM_ROW_TABLE_CAP);
-        const uint64_t n_rows = static_cast<uint64_t>(grid.dims[1]) * grid.dims[2];
-        if (n_rows > c->aln_cap_rows) {
-            if (c->aln_rows) { (void)hipFree(c->aln_rows); c->aln_rows = nullptr; c->aln_cap_rows = 0; }
-            if (!A(&c->aln_rows, n_rows * 8)) return fail(c, CM_HIP_ERROR, "cannot allocate the registration's row table");
-            c->aln_cap_rows = n_rows;
-        }
-        for (int a = 0; a < 3; ++a) { gd.min[a] = mn[a]; gd.dims[a] = grid.dims[a]; }
-        gd.inv = grid.inv;
-
-        // (cell key, result index), sorted by cell key; ballot ranking whatever the context's probe found
-        const uint32_t passes = (grid.key_bits + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
-        HIP_TRY(c, hipMemsetAsync(c->aln_grp, 0, static_cast<size_t>(passes) * gw * 4, st));
-        prof_mark(c, "k_cl_keys");
-        cmk_cl_keys(st, c->out, n, gd, passes, c->aln_state, c->aln_keys_a, c->aln_hist, c->aln_grp, nt);
-        radix_sort_pairs(c, c->aln_state, sp, passes, nt, n_slots, false, nullptr, "k_scatter(cells)");
-        prof_mark(c, "k_cl_gather");
-        cmk_cl_gather(st, c->out, c->aln_state, c->aln_vals_a, c->aln_vals_b, n, c->aln_pts, c->aln_aux, c->aln_aux + n_slots,
-                      c->aln_aux + 2 * static_cast<size_t>(n_slots));
-        prof_mark(c, "cl_rows");
-        cmk_sorted_rows(st, nullptr, c->aln_state, c->aln_keys_a, c->aln_vals_a, c->aln_keys_b, c->aln_vals_b, c->aln_pts,
-                        c->aln_rows, n_slots, true);
-        HIP_TRY(c, hipGetLastError());
-    }
-
-    // one evaluation at out->pose: the correspondences into aln_corr, the sums and the count into s[]
-    const float r2 = q.max_corr_dist * q.max_corr_dist;
-    double s[CM_ALIGN_SUMS];
-    uint64_t n_corr = 0;
-    auto evaluate = [&]() -> int {
-        CmAlignPoseDev P;
-        std::memcpy(P.m, out->pose, sizeof P.m);
-        std::memcpy(P.p0, out->pivot, sizeof P.p0);
-        prof_mark(c, "k_aln_eval");
-        cmk_aln_eval(st, c->aln_state, c->aln_keys_a, c->aln_keys_b, c->aln_pts, c->aln_rows, c->out, c->nrm_entries, src_dev,
-                     n_src, n, gd, r2, P, c->aln_corr, c->aln_part);
-        prof_mark(c, "k_aln_sum");
-        cmk_aln_sum(st, c->aln_part, n_blocks, c->aln_sums);
-        prof_mark(c, "aln_readback");
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(s, c->aln_sums, sizeof s, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        std::memcpy(&n_corr, &s[CM_ALIGN_TERMS], 8);
-        return CM_OK;
-    };
-    uint32_t flags = 0, it = 0;
-    for (; it < q.max_iterations; ++it) {
-        if (const int e = evaluate()) return e;
-        if (n_corr < q.min_correspondences) break;
-        double x[6];
-        if (!cm_align_solve(s, s + 21, x)) { flags |= CM_ALIGN_SINGULAR; break; }
-        cm_align_update(out->pose, x, out->pivot);
-        if (cm_align_norm3(x) < q.rot_eps && cm_align_norm3(x + 3) < q.trans_eps) { flags |= CM_ALIGN_CONVERGED; ++it; break; }
-    }
-    out->iterations = it;
-    if (q.max_iterations && it == q.max_iterations && !(flags & CM_ALIGN_CONVERGED)) flags |= CM_ALIGN_MAX_ITER_HIT;
-    if (const int e = evaluate()) return e;
-    prof_mark(c, "end");
-    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times_by_name(c);
-    if (n_corr < q.min_correspondences) flags |= CM_ALIGN_FEW;
-    std::memcpy(out->H, s, sizeof out->H);
-    std::memcpy(out->g, s + 21, sizeof out->g);
-    out->sse = s[27];
-    out->rms = n_corr ? std::sqrt(s[27] / static_cast<double>(n_corr)) : 0.0;
-    out->n_corr = n_corr;
-    out->flags = flags;
-    c->aln_have = true;
-    c->aln_n_src = n_src64;
-    return CM_OK;
-}
-
-// NDT registration of a source cloud against the last result's covariance table (cm_kernels_ndt.hip; the semantics are in
-// include/cloudmerge.h). The table first: the one the context holds for this result at these parameters, else voxel_cov().
-// Then k_cl_bounds on the result for the pivot, one round trip per call. Then align()'s loop: per evaluation k_ndt_eval,
-// k_aln_sum and one host round trip of 28 doubles and a count; the solve and the pose update are cm_align_solve.hpp's. Reads
-// `out`, out_key and cov_entries and writes only the ndt_* buffers: nothing a later frame reads. Under CM_FLAG_PROFILE the
-// stage times of the call replace the frame's, one entry per name, summed over the evaluations: "voxel_cov" is the covariance
-// call it made (absent when the table was held), "ndt_readback" the round trip with the host's solve.
-int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void* src_dev, uint64_t n_src64, cm_ndt_result* out) {
-    const uint32_t n = static_cast<uint32_t>(c->result.n_out);
-    const uint32_t n_src = static_cast<uint32_t>(n_src64);
-    c->ndt_have = false;
-    // the constants of the score, PCL's gauss_d1 / gauss_d2 at the frame's voxel volume
-    const CmFrameDev& f = c->frame;
-    const float* const leaf = c->plan.params.leaf;
-    const double res3 = (static_cast<double>(leaf[0]) * static_cast<double>(leaf[1])) * static_cast<double>(leaf[2]);
-    const double p = static_cast<double>(q.outlier_ratio);
-    const double c1 = 10.0 * (1.0 - p), c2 = p / res3;
-    const double d3 = -std::log(c2);
-    const double d1 = -std::log(c1 + c2) - d3;
-    const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
-    if (!(std::isfinite(d2) && d2 > 0.0)) return fail(c, CM_BAD_ARG, "the score's d2 is not finite and > 0 at this outlier_ratio and leaf");
-    const double d2h = d2 * 0.5;
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->prof_used = 0;
-    if (n && !(c->cov_have && c->cov_min_points == cov.min_points && c->cov_eig_mult == cov.eig_mult)) {
-        prof_mark(c, "voxel_cov");                   // (there only when the call computed the table)
-        if (const int e = voxel_cov(c, cov)) return e;
-    }
-    auto A = [](void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; };
-    if (!c->ndt_sums) {
-        bool ok = A(reinterpret_cast<void**>(&c->ndt_sums), CM_ALIGN_SUMS * sizeof(double)) &&
-                  A(reinterpret_cast<void**>(&c->ndt_words), 8 * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's state");
-    }
-    const uint32_t n_blocks = (n_src + CM_BLOCK - 1) / CM_BLOCK;
-    if (n_src64 > c->ndt_cap_src) {
-        if (c->ndt_corr) { (void)hipFree(c->ndt_corr); c->ndt_corr = nullptr; }
-        if (c->ndt_part) { (void)hipFree(c->ndt_part); c->ndt_part = nullptr; }
-        c->ndt_cap_src = 0;
-        bool ok = A(&c->ndt_corr, static_cast<size_t>(n_src) * sizeof(cm_ndt_corr)) &&
-                  A(reinterpret_cast<void**>(&c->ndt_part), static_cast<size_t>(n_blocks) * CM_ALIGN_STRIDE * sizeof(double));
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's correspondence table");
-        c->ndt_cap_src = n_src64;
-    }
-    hipStream_t st = c->stream;
-    uint32_t* const w = c->ndt_words;
-    // nothing is refused from here on: a refused call leaves *out as it was
-    std::memset(out, 0, sizeof *out);
-    std::memcpy(out->pose, q.guess, sizeof out->pose);
-    out->gauss_d1 = d1;
-    out->gauss_d2 = d2;
-
-    CmCovGridDev g{};
-    if (n) {
-        // the pivot: the midpoint of the centroids' own bounds
-        prof_mark(c, "k_cl_bounds");
-        HIP_TRY(c, hipMemsetAsync(w + 2, 0xFF, 12, st));
-        HIP_TRY(c, hipMemsetAsync(w + 5, 0, 12, st));
-        cmk_cl_bounds(st, c->out, n, w + 2);
-        uint32_t img[6];
-        HIP_TRY(c, hipMemcpyAsync(img, w + 2, sizeof img, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        for (int a = 0; a < 3; ++a) {
-            const float mn = ord_to_float(img[a]), mx = ord_to_float(img[3 + a]);
-            out->pivot[a] = static_cast<double>(mn) + (static_cast<double>(mx) - static_cast<double>(mn)) * 0.5;
-        }
-        // the grid of out_key, as voxel_cov hands it to k_cov_keys
-        for (int a = 0; a < 3; ++a) {
-            g.inv[a] = f.inv_leaf[a];
-            g.min_b[a] = c->cell_min_b[a];
-            g.div_b[a] = static_cast<uint32_t>(c->cell_div_b[a]);
-        }
-    }
-
-    // one evaluation at out->pose: the correspondences into ndt_corr, the sums and the count into s[]
-    double s[CM_ALIGN_SUMS];
-    uint64_t n_corr = 0;
-    auto evaluate = [&]() -> int {
-        CmAlignPoseDev P;
-        std::memcpy(P.m, out->pose, sizeof P.m);
-        std::memcpy(P.p0, out->pivot, sizeof P.p0);
-        prof_mark(c, "k_ndt_eval");
-        cmk_ndt_eval(st, c->out_key, n, c->cov_entries, src_dev, n_src, g, q.neighborhood, d2h, P, c->ndt_corr, c->ndt_part);
-        prof_mark(c, "k_aln_sum");
-        cmk_aln_sum(st, c->ndt_part, n_blocks, c->ndt_sums);
-        prof_mark(c, "ndt_readback");
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(s, c->ndt_sums, sizeof s, hipMemcpyDeviceToHost, st));
-        HIP_TRY(c, hipStreamSynchronize(st));
-        std::memcpy(&n_corr, &s[CM_ALIGN_TERMS], 8);
-        return CM_OK;
-    };
-    uint32_t flags = 0, it = 0;
-    for (; it < q.max_iterations; ++it) {
-        if (const int e = evaluate()) return e;
-        if (n_corr < q.min_correspondences) break;
-        double x[6];
-        if (!cm_align_solve(s, s + 21, x)) { flags |= CM_NDT_SINGULAR; break; }
-        cm_align_update(out->pose, x, out->pivot);
-        if (cm_align_norm3(x) < q.rot_eps && cm_align_norm3(x + 3) < q.trans_eps) { flags |= CM_NDT_CONVERGED; ++it; break; }
-    }
-    out->iterations = it;
-    if (q.max_iterations && it == q.max_iterations && !(flags & CM_NDT_CONVERGED)) flags |= CM_NDT_MAX_ITER_HIT;
-    if (const int e = evaluate()) return e;
-    prof_mark(c, "end");
-    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times_by_name(c);
-    if (n_corr < q.min_correspondences) flags |= CM_NDT_FEW;
-    std::memcpy(out->H, s, sizeof out->H);
-    std::memcpy(out->g, s + 21, sizeof out->g);
-    out->score = s[27];
-    out->n_corr = n_corr;
-    out->flags = flags;
-    c->ndt_have = true;
-    c->ndt_n_src = n_src64;
-    return CM_OK;
 }

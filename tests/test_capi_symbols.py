@@ -42,8 +42,8 @@ def test_no_oracle_or_cpu_path_in_product():
     assert sorted(exported) == sorted(capi.SYMBOLS), "only the C-ABI is exported (no weak template symbols either)"
     ldd = subprocess.run(["ldd", capi.LIB_PATH], capture_output=True, text=True).stdout
     assert "cm_oracle" not in ldd and "libamdhip64" in ldd
-    for f in ("cm_api.cpp", "cm_launch.cpp", "cm_route.cpp", "cm_ctx.hpp", "cm_route.hpp", "cm_kernels.hip", "cm_kernels.h",
-              "cm_device.h"):
+    for f in ("cm_api.cpp", "cm_launch.cpp", "cm_byproducts.cpp", "cm_route.cpp", "cm_ctx.hpp", "cm_route.hpp", "cm_kernels.hip",
+              "cm_kernels.h", "cm_device.h"):
         src = open(os.path.join(ROOT, "cloud_merger_amd", "csrc", f)).read()
         assert "oracle" not in src.lower().replace("oracle/", "")
 
