@@ -44,6 +44,7 @@ SYMBOLS = [
     "cm_result_voxel_cov", "cm_result_voxel_cov_device",
     "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
     "cm_result_clusters", "cm_result_clusters_device",
+    "cm_box_directions", "cm_result_cluster_boxes", "cm_result_cluster_boxes_device",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -163,6 +164,27 @@ class Cluster(C.Structure):
 CLUSTER_DTYPE = np.dtype([("first", "<u4"), ("n_voxels", "<u4"), ("n_points", "<u4"), ("_pad", "<u4"),
                           ("min", "<f4", (3,)), ("max", "<f4", (3,))])
 assert CLUSTER_DTYPE.itemsize == C.sizeof(Cluster) == 40 and C.sizeof(ClusterParams) == 16
+
+# oriented boxes of the clusters (cm_result_cluster_boxes)
+BOX_MAX_ANGLES, BOX_CHUNK, BOX_MAX_EXTENT = 180, 256, 1.0e6
+BOX_AREA, BOX_CLOSENESS = 0, 1
+BOX_VALID = 1
+
+
+class BoxParams(C.Structure):
+    _fields_ = [("cluster", ClusterParams), ("n_angles", C.c_uint32), ("criterion", C.c_uint32), ("d_min", C.c_float),
+                ("_pad", C.c_uint32)]
+
+
+class ClusterBox(C.Structure):
+    """cm_cluster_box (48 bytes): entry k belongs to cluster k; size along the heading, across it, height."""
+    _fields_ = [("center", C.c_float * 3), ("size", C.c_float * 3), ("yaw", C.c_float), ("angle", C.c_uint32),
+                ("score", C.c_double), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+BOX_DTYPE = np.dtype([("center", "<f4", (3,)), ("size", "<f4", (3,)), ("yaw", "<f4"), ("angle", "<u4"), ("score", "<f8"),
+                      ("flags", "<u4"), ("_pad", "<u4")])
+assert BOX_DTYPE.itemsize == C.sizeof(ClusterBox) == 48 and C.sizeof(BoxParams) == 32
 
 
 # normals and curvature of the result (cm_result_normals)
@@ -338,6 +360,9 @@ def load():
     L.cm_result_clusters.argtypes = [vp, C.POINTER(ClusterParams), vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.cm_result_clusters_device.argtypes = [vp, C.POINTER(ClusterParams), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                             C.POINTER(u64), C.POINTER(u64)]
+    L.cm_box_directions.argtypes = [u32, vp, u64]
+    L.cm_result_cluster_boxes.argtypes = [vp, C.POINTER(BoxParams), vp, u64, C.POINTER(u64)]
+    L.cm_result_cluster_boxes_device.argtypes = [vp, C.POINTER(BoxParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -352,6 +377,15 @@ def load():
             fn.restype = C.c_int
     _lib = L
     return L
+
+
+def box_directions(n):
+    """(n, 2) float32: (cos, sin) of the n headings a box call tries — the table it uploads (cm_box_directions)."""
+    out = np.empty((max(int(n), 1), 2), dtype=np.float32)
+    st = load().cm_box_directions(int(n), out.ctypes.data, out.shape[0])
+    if st != OK:
+        raise CloudMergeError(st, "cm_box_directions")
+    return out[: int(n)]
 
 
 def status_string(status):
@@ -652,6 +686,32 @@ class CloudMerger:
         self._check(self._lib.cm_result_clusters_device(self._ctx, C.byref(p), C.byref(lp), C.byref(cp), C.byref(ip), C.byref(nc),
                                                         C.byref(nm)), "cm_result_clusters_device")
         return lp.value, cp.value, ip.value, nc.value, nm.value
+
+    # ---- oriented boxes of the last result's clusters (cm_result_cluster_boxes) ----
+    @staticmethod
+    def box_params(tolerance, min_size=1, max_size=2**32 - 1, n_angles=90, criterion=BOX_CLOSENESS, d_min=0.01):
+        return BoxParams(ClusterParams(float(tolerance), int(min_size), int(max_size), 0), int(n_angles), int(criterion),
+                         float(d_min), 0)
+
+    def cluster_boxes(self, tolerance, min_size=1, max_size=2**32 - 1, n_angles=90, criterion=BOX_CLOSENESS, d_min=0.01):
+        """(n_clusters,) BOX_DTYPE array: entry k is the oriented box of cluster k of clusters(tolerance, min_size, max_size) —
+        the best of n_angles headings in [0, 90 deg) under the criterion. The context then holds those cluster tables."""
+        p = self.box_params(tolerance, min_size, max_size, n_angles, criterion, d_min)
+        _, n_out = self.result_device()
+        out = np.empty(max(int(n_out), 1), dtype=BOX_DTYPE)
+        n = C.c_uint64()
+        self._check(self._lib.cm_result_cluster_boxes(self._ctx, C.byref(p), out.ctypes.data, out.shape[0], C.byref(n)),
+                    "cm_result_cluster_boxes")
+        return out[: n.value].copy()
+
+    def cluster_boxes_device(self, tolerance, min_size=1, max_size=2**32 - 1, n_angles=90, criterion=BOX_CLOSENESS, d_min=0.01):
+        """(device pointer, entries) of the same table, owned by the context and valid until the next merge or the next cluster
+        or box call."""
+        p = self.box_params(tolerance, min_size, max_size, n_angles, criterion, d_min)
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self._check(self._lib.cm_result_cluster_boxes_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)),
+                    "cm_result_cluster_boxes_device")
+        return ptr.value, n.value
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

@@ -2,6 +2,7 @@
 // assembled and launched in cm_launch.cpp, routed in cm_route.cpp; the tables computed from a result on request are
 // cm_byproducts.cpp's; the context is cm_ctx.hpp.
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -50,6 +51,7 @@ void free_all(cm_ctx* c) {
     F(c->out_other); F(c->out32_other); F(c->motion_buf);
     c->cov.release(); F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
     c->cl.release(); F(c->cl_root); F(c->cl_num); F(c->cl_labels); F(c->cl_tile_sums); F(c->cl_words); F(c->cl_clusters);
+    F(c->box_entries); F(c->box_dirs); F(c->box_words); F(c->box_list); F(c->box_ext); F(c->box_work); F(c->box_sums);
     c->nrm.release(); F(c->nrm_list); F(c->nrm_words); F(c->nrm_entries);
     c->aln.release(); c->aln_fit.release();
     c->ndt_fit.release(); F(c->ndt_bounds);
@@ -148,6 +150,17 @@ int clusters_check(cm_ctx* c, const cm_cluster_params* p) {
     if (!std::isfinite(t2) || !(t2 > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 square of the tolerance must be finite and > 0");
     if (p->min_cluster_size == 0) return fail(c, CM_BAD_ARG, "min_cluster_size must be at least 1");
     if (p->min_cluster_size > p->max_cluster_size) return fail(c, CM_BAD_ARG, "min_cluster_size exceeds max_cluster_size");
+    return CM_OK;
+}
+
+// The refusals of cm_result_cluster_boxes*: CM_OK when the last result's clusters can be fitted with *p.
+int boxes_check(cm_ctx* c, const cm_box_params* p) {
+    if (!p) return fail(c, CM_BAD_ARG, "no box parameters");
+    if (const int e = clusters_check(c, &p->cluster)) return e;
+    if (p->n_angles == 0 || p->n_angles > CM_BOX_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_angles must be in 1..CM_BOX_MAX_ANGLES");
+    if (p->criterion != CM_BOX_AREA && p->criterion != CM_BOX_CLOSENESS) return fail(c, CM_BAD_ARG, "unknown box criterion");
+    if (p->criterion == CM_BOX_CLOSENESS && (!std::isfinite(p->d_min) || !(p->d_min > 0.0f)))
+        return fail(c, CM_BAD_ARG, "d_min must be finite and > 0");
     return CM_OK;
 }
 
@@ -368,6 +381,12 @@ int cm_create(cm_ctx** out, int device, const cm_limits* lim) {
     if (const char* qm = getenv("CM_QUANT")) rt.quant_never = qm[0] == '0';     // CM_QUANT=0: fixed-grid passes only
     if (const char* qs = getenv("CM_QUANT_SUB")) rt.quant_sub = qs[0] != '0';
     rt.verbose = getenv("CM_VERBOSE") != nullptr;
+    // CM_BOX_SPLIT=<members>: where the box fit hands a cluster to the chunk-wise launches (a measurement's switch; the
+    // table is the same bytes at every value)
+    if (const char* bs = getenv("CM_BOX_SPLIT")) {
+        const unsigned long v = std::strtoul(bs, nullptr, 10);
+        if (v >= 1 && v < 0xFFFFFFFFul) c->box_split = static_cast<uint32_t>(v);
+    }
     if (!ok) {
         free_all(c);
         delete c;
@@ -711,6 +730,53 @@ int cm_result_clusters_device(cm_ctx* c, const cm_cluster_params* p, const void*
     *indices = c->cl_n_clustered ? c->cl_indices : nullptr;
     *n_clusters = c->cl_n_clusters;
     *n_clustered = c->cl_n_clustered;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_cluster_box) == 48 && sizeof(CmBoxDev) == sizeof(cm_cluster_box) && sizeof(cm_box_params) == 32,
+              "cm_cluster_box is 48 bytes, its parameters 32");
+static_assert(offsetof(cm_cluster_box, score) == offsetof(CmBoxDev, score) && offsetof(cm_cluster_box, flags) == offsetof(CmBoxDev, flags),
+              "the kernels' entry");
+static_assert(CM_BOX_CHUNK == CM_BOX_CHUNK_DEV && CM_BOX_MAX_ANGLES == CM_BOX_MAX_ANGLES_DEV && CM_BOX_MAX_EXTENT == CM_BOX_MAX_EXTENT_DEV &&
+                  CM_BOX_CLOSENESS == CM_BOX_CLOSENESS_DEV && CM_BOX_VALID == CM_BOX_VALID_DEV,
+              "the kernels' constants");
+
+int cm_box_directions(uint32_t n_angles, float* cos_sin, uint64_t capacity_pairs) {
+    if (!cos_sin || n_angles == 0 || n_angles > CM_BOX_MAX_ANGLES) return CM_BAD_ARG;
+    if (capacity_pairs < n_angles) return CM_CAPACITY;
+    box_direction_table(n_angles, cos_sin);
+    return CM_OK;
+}
+
+int cm_result_cluster_boxes(cm_ctx* c, const cm_box_params* p, cm_cluster_box* host_dst, uint64_t capacity, uint64_t* n_boxes) {
+    if (!c || !n_boxes) return CM_BAD_ARG;
+    *n_boxes = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = boxes_check(c, p);
+    if (e != CM_OK) return e;
+    if (!host_dst && capacity) return fail(c, CM_BAD_ARG, "a destination with a capacity but no pointer");
+    e = cluster_boxes(c, *p);
+    if (e != CM_OK) return e;
+    const uint64_t n = c->box_n;
+    *n_boxes = n;
+    if (n > capacity) return fail(c, CM_CAPACITY, "boxes destination too small");
+    if (n == 0) return CM_OK;
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->box_entries, n * sizeof(cm_cluster_box), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_cluster_box);
+    return CM_OK;
+}
+
+int cm_result_cluster_boxes_device(cm_ctx* c, const cm_box_params* p, const void** dev_ptr, uint64_t* n_boxes) {
+    if (!c || !dev_ptr || !n_boxes) return CM_BAD_ARG;
+    *dev_ptr = nullptr;
+    *n_boxes = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = boxes_check(c, p);
+    if (e == CM_OK) e = cluster_boxes(c, *p);
+    if (e != CM_OK) return e;
+    *dev_ptr = c->box_n ? c->box_entries : nullptr;
+    *n_boxes = c->box_n;
     return CM_OK;
 }
 

@@ -1,5 +1,5 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
-// (voxel_cov), the cluster extraction (clusters), normals and curvature (normals), and the two registrations of a source cloud
+// (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), and the two registrations of a source cloud
 // (align, ndt). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
@@ -235,8 +235,9 @@ int build_search_index(cm_ctx* c, SearchIndex& ix, const ClusterGrid& grid, cons
 // cl buffers. Reads `out` — what cm_result_copy reads — and out_cnt where the context keeps it. Two host round trips: the
 // bounds of the centroids (the search grid is decided on the host, cluster_grid) and the cluster count (the second sort's
 // passes, the table's size). Under CM_FLAG_PROFILE the stage times of the call replace the frame's in cm_get_stage_times.
-int clusters(cm_ctx* c, const cm_cluster_params& q) {
+int clusters(cm_ctx* c, const cm_cluster_params& q, bool more_stages) {
     const uint32_t n = static_cast<uint32_t>(c->result.n_out);
+    c->box_n = 0;
     c->cl_n_clusters = 0;
     c->cl_n_clustered = 0;
     c->cl_indices = nullptr;
@@ -299,13 +300,95 @@ int clusters(cm_ctx* c, const cm_cluster_params& q) {
         prof_mark(c, "k_cl_decode");
         cmk_cl_decode(st, c->cl_clusters, n_clusters);
     }
+    HIP_TRY(c, hipGetLastError());
+    if (!more_stages) {
+        prof_mark(c, "end");
+        HIP_TRY(c, hipStreamSynchronize(st));
+        collect_stage_times(c);
+    }
+    c->cl_n_clusters = n_clusters;
+    c->cl_n_clustered = counts[1];
+    c->cl_indices = (passes_num & 1u) ? so.vals_b : so.vals_a;
+    return CM_OK;
+}
+
+void box_direction_table(uint32_t n_angles, float* cos_sin) {
+    const double step = 1.5707963267948966 / static_cast<double>(n_angles);
+    for (uint32_t a = 0; a < n_angles; ++a) {
+        const double th = static_cast<double>(a) * step;
+        cos_sin[2 * a] = static_cast<float>(std::cos(th));
+        cos_sin[2 * a + 1] = static_cast<float>(std::sin(th));
+    }
+}
+
+// Oriented boxes of the last result's clusters (cm_kernels_box.hip; the semantics are in include/cloudmerge.h). The cluster
+// call first, its stream left running: no host round trip of its own. k_box_fit takes every cluster, and fits the ones of
+// up to box_split members itself; the larger ones it lists, and three launches take them chunk by chunk. The host does not
+// know how many were listed: the three grids are sized for the most there can be among n_clustered voxels, and none is
+// launched where n_clustered <= box_split. Under CM_FLAG_PROFILE the stage times are the cluster call's, then these.
+int cluster_boxes(cm_ctx* c, const cm_box_params& q) {
+    if (const int e = clusters(c, q.cluster, true)) return e;
+    const uint64_t n_clusters = c->cl_n_clusters, n_clustered = c->cl_n_clustered;
+    hipStream_t st = c->stream;
+    if (n_clusters == 0) {                           // (an empty result marked nothing)
+        if (c->result.n_out) {
+            prof_mark(c, "end");
+            HIP_TRY(c, hipStreamSynchronize(st));
+            collect_stage_times(c);
+        }
+        return CM_OK;
+    }
+    if (!grow_table(&c->box_entries, &c->box_cap_entries, n_clusters, sizeof(cm_cluster_box)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the box table");
+    if (!c->box_dirs && !(dev_alloc(&c->box_dirs, sizeof c->box_dirs_host) && dev_alloc(&c->box_words, 2 * 4)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's state");
+    const uint64_t split = c->box_split;
+    const uint64_t max_large = n_clustered / (split + 1u);
+    const uint64_t max_chunks = max_large ? n_clustered / CM_BOX_CHUNK + max_large : 0u;
+    if (max_large > c->box_cap_large) {
+        dev_free(c->box_list); dev_free(c->box_ext);
+        c->box_cap_large = 0;
+        if (!dev_alloc(&c->box_list, max_large * 8) || !dev_alloc(&c->box_ext, max_large * CM_BOX_MAX_ANGLES * 16))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's buffers");
+        c->box_cap_large = max_large;
+    }
+    if (max_chunks > c->box_cap_chunks) {
+        dev_free(c->box_work); dev_free(c->box_sums);
+        c->box_cap_chunks = 0;
+        if (!dev_alloc(&c->box_work, max_chunks * 8) || !dev_alloc(&c->box_sums, max_chunks * CM_BOX_MAX_ANGLES * sizeof(double)))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's buffers");
+        c->box_cap_chunks = max_chunks;
+    }
+    if (c->box_dirs_n != q.n_angles) {
+        // (box_dirs_host is read by no copy in flight: every box call ends with the stream at rest)
+        box_direction_table(q.n_angles, c->box_dirs_host);
+        HIP_TRY(c, hipMemcpyAsync(c->box_dirs, c->box_dirs_host, static_cast<size_t>(q.n_angles) * 8, hipMemcpyHostToDevice, st));
+        c->box_dirs_n = q.n_angles;
+    }
+    const double step = 1.5707963267948966 / static_cast<double>(q.n_angles);
+    const uint32_t nk = static_cast<uint32_t>(n_clusters), na = q.n_angles;
+    HIP_TRY(c, hipMemsetAsync(c->box_words, 0, 8, st));
+    prof_mark(c, "k_box_fit");
+    cmk_box_fit(st, c->out, c->cl_clusters, c->cl_indices, nk, c->box_dirs, na, step, q.criterion, q.d_min,
+                static_cast<uint32_t>(split), c->box_entries, c->box_words, c->box_list, c->box_work, c->box_ext);
+    if (max_large) {
+        const uint32_t ml = static_cast<uint32_t>(max_large), mc = static_cast<uint32_t>(max_chunks);
+        prof_mark(c, "k_box_extremes");
+        cmk_box_extremes(st, c->out, c->cl_clusters, c->cl_indices, c->box_dirs, na, c->box_words, c->box_list, c->box_work, c->box_ext, mc);
+        if (q.criterion == CM_BOX_CLOSENESS) {
+            prof_mark(c, "k_box_sums");
+            cmk_box_sums(st, c->out, c->cl_clusters, c->cl_indices, c->box_dirs, na, q.d_min, c->box_words, c->box_list, c->box_work,
+                         c->box_ext, c->box_sums, mc);
+        }
+        prof_mark(c, "k_box_choose");
+        cmk_box_choose(st, c->cl_clusters, c->box_dirs, na, step, q.criterion, c->box_words, c->box_list, c->box_ext, c->box_sums,
+                       c->box_entries, ml);
+    }
     prof_mark(c, "end");
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
     collect_stage_times(c);
-    c->cl_n_clusters = n_clusters;
-    c->cl_n_clustered = counts[1];
-    c->cl_indices = (passes_num & 1u) ? so.vals_b : so.vals_a;
+    c->box_n = n_clusters;
     return CM_OK;
 }
 

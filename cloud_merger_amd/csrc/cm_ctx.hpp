@@ -239,6 +239,22 @@ struct cm_ctx {
     const uint32_t* cl_indices = nullptr;   // the member lists of the last call (one of cl.sort.vals_a / vals_b)
     uint64_t cl_n_clusters = 0, cl_n_clustered = 0;
 
+    // Oriented boxes of the clusters (cm_kernels_box.hip), on request after a frame: the cluster call, then the fit. Buffers of
+    // its own — no frame reads them — allocated by the first request and grown with the results.
+    void* box_entries = nullptr;         // the table: cm_cluster_box per cluster
+    uint64_t box_cap_entries = 0;
+    uint64_t box_n = 0;                  // its entries: the clusters of the last box call (0 after a cluster call)
+    void* box_dirs = nullptr;            // CM_BOX_MAX_ANGLES (cos, sin) pairs: the direction table at box_dirs_n headings
+    uint32_t box_dirs_n = 0;
+    float box_dirs_host[2 * CM_BOX_MAX_ANGLES];   // what the upload reads
+    uint32_t* box_words = nullptr;       // [0] listed (large) clusters, [1] their chunks
+    void *box_list = nullptr, *box_ext = nullptr;    // per listed cluster: (cluster, first chunk row); the extremes' images
+    uint64_t box_cap_large = 0;
+    void* box_work = nullptr;            // per listed chunk: (slot, chunk)
+    double* box_sums = nullptr;          // per listed chunk: CM_BOX_MAX_ANGLES sums
+    uint64_t box_cap_chunks = 0;
+    uint32_t box_split = CM_BOX_SPLIT;   // (CM_BOX_SPLIT in the environment: the measurement of scripts/box_cost.py)
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -322,7 +338,12 @@ inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c-
 // The covariance table of the last result (cov_entries, n_out entries).
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 // The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
-int clusters(cm_ctx* c, const cm_cluster_params& q);
+// more_stages: the caller goes on launching and closes the stage list itself.
+int clusters(cm_ctx* c, const cm_cluster_params& q, bool more_stages = false);
+// The box table of the last result's clusters at q.cluster (box_entries, box_n entries), behind the cluster tables.
+int cluster_boxes(cm_ctx* c, const cm_box_params& q);
+// The direction table of n_angles headings (1..CM_BOX_MAX_ANGLES): 2 * n_angles floats.
+void box_direction_table(uint32_t n_angles, float* cos_sin);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

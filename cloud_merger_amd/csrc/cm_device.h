@@ -256,3 +256,19 @@ struct CmAlignPoseDev {
 // CmAlignPoseDev, the block partials k_aln_eval's (the 28th sum is the score); a correspondence (== cm_ndt_corr, 16 bytes:
 // idx, n_used, the score's 8 bytes) is one uint4.
 #define CM_NDT_NONE_DEV 0xFFFFFFFFu
+
+// Oriented boxes of the clusters (cm_kernels_box.hip): the constants of include/cloudmerge.h the kernels need (cm_api.cpp
+// asserts that they agree) and one table entry (== cm_cluster_box, 48 bytes). CM_BOX_SPLIT: a cluster of more members is
+// not walked by one workgroup but chunk by chunk across workgroups (DESIGN.md §19 says why 1024).
+#define CM_BOX_CHUNK_DEV 256
+#define CM_BOX_MAX_ANGLES_DEV 180
+#define CM_BOX_MAX_EXTENT_DEV 1.0e6f
+#define CM_BOX_CLOSENESS_DEV 1u
+#define CM_BOX_VALID_DEV 1u
+#define CM_BOX_SPLIT 1024u
+struct CmBoxDev {
+    float center[3], size[3], yaw;
+    uint32_t angle;
+    double score;
+    uint32_t flags, _pad;
+};

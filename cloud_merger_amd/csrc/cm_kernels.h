@@ -207,3 +207,21 @@ void cmk_aln_sum(hipStream_t s, const double* partials, uint32_t n_blocks, doubl
 void cmk_ndt_eval(hipStream_t s, const uint32_t* out_key, uint32_t n_out, const void* cov, const void* src, uint32_t n_src,
                   const CmCovGridDev& g, uint32_t neighborhood, double d2h, const CmAlignPoseDev& pose, void* corr,
                   double* partials);
+
+// ---- oriented boxes of the clusters (cm_kernels_box.hip) --------------------------------------------------------------------
+// After the cluster call (clusters: its decoded table of n_clusters entries, indices: its member lists, recs: the result
+// records): one cm_cluster_box per cluster into boxes. dirs: n_angles (cos, sin) pairs; step: the angle between two headings.
+// A cluster of more than `split` members is listed instead of fitted: words[0] / [1] (zeroed before) count the listed
+// clusters and their chunks, list / work / ext take one entry per listed cluster / chunk / (cluster, angle). The three
+// launches behind it take the listed ones, with grids for the most there can be (max_chunks, max_large; 0: no launch);
+// sums: n_angles doubles per listed chunk (cmk_box_sums is CLOSENESS's alone).
+void cmk_box_fit(hipStream_t s, const void* recs, const void* clusters, const uint32_t* indices, uint32_t n_clusters,
+                 const void* dirs, uint32_t n_angles, double step, uint32_t criterion, float d_min, uint32_t split, void* boxes,
+                 uint32_t* words, void* list, void* work, void* ext);
+void cmk_box_extremes(hipStream_t s, const void* recs, const void* clusters, const uint32_t* indices, const void* dirs,
+                      uint32_t n_angles, const uint32_t* words, const void* list, const void* work, void* ext, uint32_t max_chunks);
+void cmk_box_sums(hipStream_t s, const void* recs, const void* clusters, const uint32_t* indices, const void* dirs, uint32_t n_angles,
+                  float d_min, const uint32_t* words, const void* list, const void* work, const void* ext, double* sums,
+                  uint32_t max_chunks);
+void cmk_box_choose(hipStream_t s, const void* clusters, const void* dirs, uint32_t n_angles, double step, uint32_t criterion,
+                    const uint32_t* words, const void* list, const void* ext, const double* sums, void* boxes, uint32_t max_large);

@@ -148,6 +148,13 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "cluster_tolerance") ok = static_cast<bool>(is >> c.cluster_tolerance) && c.cluster_tolerance >= 0.0f && std::isfinite(c.cluster_tolerance);
         else if (key == "cluster_min_size") ok = static_cast<bool>(is >> c.cluster_min_size) && c.cluster_min_size >= 1;
         else if (key == "cluster_max_size") ok = static_cast<bool>(is >> c.cluster_max_size) && c.cluster_max_size >= 1;
+        else if (key == "cluster_box_angles") ok = static_cast<bool>(is >> c.cluster_box_angles) && c.cluster_box_angles <= CM_BOX_MAX_ANGLES;
+        else if (key == "cluster_box_criterion") {
+            std::string v;
+            ok = static_cast<bool>(is >> v) && (v == "area" || v == "closeness");
+            c.cluster_box_criterion = v == "area" ? CM_BOX_AREA : CM_BOX_CLOSENESS;
+        }
+        else if (key == "cluster_box_d_min") ok = static_cast<bool>(is >> c.cluster_box_d_min) && c.cluster_box_d_min > 0.0f && std::isfinite(c.cluster_box_d_min);
         else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "align_prev") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.align_prev = v == 1; }
         else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
@@ -288,6 +295,7 @@ int CloudMergerNode::enqueue_frame(bool wait, cm_result* r) {
 int CloudMergerNode::clusters_of_frame(const cm_result& r) {
     n_clusters_ = 0;
     cluster_labels_.clear();
+    cluster_boxes_.clear();
     if (!(cfg_.cluster_tolerance > 0.0f) || r.status != CM_OK) return CM_OK;
     const cm_cluster_params q{cfg_.cluster_tolerance, cfg_.cluster_min_size, cfg_.cluster_max_size, 0};
     cluster_labels_.resize(r.n_out);
@@ -296,6 +304,16 @@ int CloudMergerNode::clusters_of_frame(const cm_result& r) {
                                       &n_clusters, &n_clustered);
     if (st != CM_OK) { cluster_labels_.clear(); set_error(cm_last_error(ctx_)); return st; }
     n_clusters_ = n_clusters;
+    if (cfg_.cluster_box_angles == 0) return CM_OK;
+    const cm_box_params b{q, cfg_.cluster_box_angles, cfg_.cluster_box_criterion, cfg_.cluster_box_d_min, 0};
+    cluster_boxes_.resize(n_clusters);
+    uint64_t n_boxes = 0;
+    const int sb = cm_result_cluster_boxes(ctx_, &b, cluster_boxes_.data(), cluster_boxes_.size(), &n_boxes);
+    if (sb != CM_OK || n_boxes != n_clusters) {
+        cluster_boxes_.clear();
+        set_error(sb != CM_OK ? cm_last_error(ctx_) : "the box table does not match the cluster table");
+        return sb != CM_OK ? sb : CM_INTERNAL;
+    }
     return CM_OK;
 }
 

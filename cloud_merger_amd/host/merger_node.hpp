@@ -80,6 +80,12 @@ struct NodeConfig {
     // the cluster count, until the next frame (cluster_count(), cluster_labels()).
     float cluster_tolerance = 0.0f;
     uint32_t cluster_min_size = 1, cluster_max_size = 0xFFFFFFFFu;
+    // Oriented boxes of those clusters (cm_result_cluster_boxes; search-based L-shape fitting). Off by default (angles 0) and
+    // without cluster_tolerance. On: the node asks for the box table behind the labels and keeps it until the next frame
+    // (cluster_boxes(): entry k belongs to cluster k). The call extracts the clusters a second time.
+    uint32_t cluster_box_angles = 0;
+    uint32_t cluster_box_criterion = CM_BOX_CLOSENESS;
+    float cluster_box_d_min = 0.01f;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -112,6 +118,8 @@ struct NodeConfig {
 //   u32ns: nanoseconds, relative to the cloud's header stamp)
 //   statistical_outlier <mean_k> <std_mul> [search_cell]   (pcl::StatisticalOutlierRemoval before the voxel grid)
 //   cluster_tolerance <metres> | cluster_min_size <n> | cluster_max_size <n>   (clusters of every voxel cloud; 0: off)
+//   cluster_box_angles <n> | cluster_box_criterion <area|closeness> | cluster_box_d_min <metres>   (oriented boxes of those
+//   clusters from n headings, 1..180; 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -184,6 +192,8 @@ public:
     // in no cluster), in the order of the published cloud. Read from the thread that calls spin_once.
     uint64_t cluster_count() const { return n_clusters_; }
     const std::vector<uint32_t>& cluster_labels() const { return cluster_labels_; }
+    // cluster_box_angles > 0 as well: the oriented box of each of those clusters, cluster_count() entries.
+    const std::vector<cm_cluster_box>& cluster_boxes() const { return cluster_boxes_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -233,7 +243,8 @@ private:
     uint64_t motion_t_ref_ = 0;
     uint64_t n_clusters_ = 0;
     std::vector<uint32_t> cluster_labels_;
-    int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters when the config asks for it
+    std::vector<cm_cluster_box> cluster_boxes_;
+    int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters (and the boxes) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     bool has_alignment_ = false;

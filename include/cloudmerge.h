@@ -456,6 +456,67 @@ CM_API int cm_result_clusters(cm_ctx* ctx, const cm_cluster_params* p, uint32_t*
 CM_API int cm_result_clusters_device(cm_ctx* ctx, const cm_cluster_params* p, const void** labels, const void** clusters,
                                      const void** indices, uint64_t* n_clusters, uint64_t* n_clustered);
 
+/* ---- oriented bounding boxes of the clusters (search-based L-shape fitting; an extension) ------------------------------
+ * A centre, a length, a width, a height and a heading per cluster, computed on request after a frame: every
+ * heading in [0, pi/2) is tried, the rectangle it implies is scored, the best is kept (Zhang, Xu et al., IV 2017). The table
+ * is a function of the result, the parameters and the direction table alone, bit for bit. All fp32 and fp64 operations are
+ * rounded one at a time, round-to-nearest, no contraction.
+ *   0. Directions. theta_a = double(a) * (1.5707963267948966 / double(n_angles)), a = 0 .. n_angles - 1;
+ *      (ca, sa) = (float(cos theta_a), float(sin theta_a)), std::cos / std::sin on the host. cm_box_directions returns exactly
+ *      the table the call uploads; that table is the definition. Entry 0 is (1, 0).
+ *   1. Clusters. The call first computes the cluster tables at `cluster`, as cm_result_clusters does; afterwards the context
+ *      holds those labels, indices and clusters. Cluster k has the members j_0 < j_1 < ... < j_{m-1} (its slice of indices)
+ *      and the box min / max of the cluster table.
+ *   2. Validity. ex = max[0] - min[0], ey = max[1] - min[1], fp32. The box is valid iff ex, ey and max[2] - min[2] are
+ *      finite and ex, ey < CM_BOX_MAX_EXTENT. Otherwise flags = 0, angle = 0, every float field and score NaN. In a valid
+ *      cluster nothing below overflows or becomes NaN.
+ *   3. Projection of member j at angle a: dx = x_j - min[0], dy = y_j - min[1]; u = (dx*ca) + (dy*sa), v = (dy*ca) - (dx*sa).
+ *      u0, u1, v0, v1: the minima and maxima of u and v over the members.
+ *   4. Score. CM_BOX_AREA: score_a = -double((u1 - u0) * (v1 - v0)), the product in fp32. CM_BOX_CLOSENESS: per member
+ *      d = max(min(min(u1 - u, u - u0), min(v1 - v, v - v0)), d_min) in fp32 and term = 1.0 / double(d). Member p of the
+ *      cluster's list belongs to chunk p / CM_BOX_CHUNK; a chunk's terms are added one after the other from 0.0 in list
+ *      order, the chunk sums one after the other from 0.0 in ascending chunk order; score_a is that total.
+ *   5. Choice. a* is the smallest a with the largest score_a.
+ *   6. Outputs, (ca, sa) and the extremes at a*: size = (u1 - u0, v1 - v0, max[2] - min[2]); uc = u0 + (u1 - u0) * 0.5f, vc
+ *      likewise; center = (min[0] + ((uc*ca) - (vc*sa)), min[1] + ((uc*sa) + (vc*ca)), min[2] + (max[2] - min[2]) * 0.5f);
+ *      yaw = float(theta_a*); angle = a*; score = score_a*.
+ * Refused with CM_BAD_ARG (cm_last_error says why): everything cm_result_clusters refuses, n_angles 0 or above
+ * CM_BOX_MAX_ANGLES, an unknown criterion, with CM_BOX_CLOSENESS a d_min that is not finite and > 0. Zero clusters: CM_OK
+ * with zero boxes. The table is owned by the context and valid until the next merge or the next cluster or box call. No
+ * later frame depends on whether it was asked for; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists the stages of
+ * the cluster call followed by this call's own (k_box_*). */
+#define CM_BOX_MAX_ANGLES 180
+#define CM_BOX_CHUNK      256          /* members per partial sum, part of the semantics */
+#define CM_BOX_MAX_EXTENT 1.0e6f       /* metres; a cluster wider than this in x or y gets no box */
+#define CM_BOX_AREA       0u
+#define CM_BOX_CLOSENESS  1u
+#define CM_BOX_VALID      1u
+typedef struct cm_box_params {         /* 32 bytes */
+    cm_cluster_params cluster;         /* the clusters the boxes are fitted to (cm_result_clusters) */
+    uint32_t n_angles;                 /* 1..CM_BOX_MAX_ANGLES headings in [0, pi/2) */
+    uint32_t criterion;                /* CM_BOX_AREA | CM_BOX_CLOSENESS */
+    float d_min;                       /* closeness: distances below it count as it; finite, > 0 (ignored for AREA) */
+    uint32_t _pad;
+} cm_box_params;
+typedef struct cm_cluster_box {        /* 48 bytes, entry k belongs to cm_cluster k */
+    float center[3];
+    float size[3];                     /* along the heading, across it, height */
+    float yaw;
+    uint32_t angle;                    /* index of the chosen heading */
+    double score;                      /* of the chosen heading */
+    uint32_t flags;                    /* CM_BOX_VALID */
+    uint32_t _pad;
+} cm_cluster_box;
+/* The direction table of n_angles headings: 2 floats (cos, sin) per heading into cos_sin. Host only, no context. CM_BAD_ARG:
+ * NULL, n_angles 0 or above CM_BOX_MAX_ANGLES; CM_CAPACITY: capacity_pairs < n_angles (nothing is written). */
+CM_API int cm_box_directions(uint32_t n_angles, float* cos_sin, uint64_t capacity_pairs);
+/* Host copy; capacity in entries. *n_boxes is always written (0 when the call is refused); a destination that is too small:
+ * CM_CAPACITY (nothing is copied; the table stays in the context, *n_boxes says how many entries it has). */
+CM_API int cm_result_cluster_boxes(cm_ctx* ctx, const cm_box_params* p, cm_cluster_box* host_dst, uint64_t capacity,
+                                   uint64_t* n_boxes);
+/* The same table left in device memory owned by the context (*n_boxes entries of 48 bytes; NULL where there is none). */
+CM_API int cm_result_cluster_boxes_device(cm_ctx* ctx, const cm_box_params* p, const void** dev_ptr, uint64_t* n_boxes);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
