@@ -45,6 +45,7 @@ SYMBOLS = [
     "cm_set_statistical_outlier", "cm_get_sor_stats", "cm_sor_distances_copy",
     "cm_result_clusters", "cm_result_clusters_device",
     "cm_box_directions", "cm_result_cluster_boxes", "cm_result_cluster_boxes_device",
+    "cm_result_grid_map", "cm_result_grid_map_device", "cm_grid_occupancy_copy",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -185,6 +186,26 @@ class ClusterBox(C.Structure):
 BOX_DTYPE = np.dtype([("center", "<f4", (3,)), ("size", "<f4", (3,)), ("yaw", "<f4"), ("angle", "<u4"), ("score", "<f8"),
                       ("flags", "<u4"), ("_pad", "<u4")])
 assert BOX_DTYPE.itemsize == C.sizeof(ClusterBox) == 48 and C.sizeof(BoxParams) == 32
+
+# 2-D grid map of the frame (cm_result_grid_map)
+GRID_MAX_CELLS = 1 << 22
+GRID_UNKNOWN, GRID_FREE, GRID_OCCUPIED = 0, 1, 2
+
+
+class GridParams(C.Structure):
+    _fields_ = [("origin", C.c_float * 2), ("cell", C.c_float), ("nx", C.c_uint32), ("ny", C.c_uint32), ("z_min", C.c_float),
+                ("z_max", C.c_float), ("obstacle_height", C.c_float), ("min_points", C.c_uint32)]
+
+
+class GridCell(C.Structure):
+    """cm_grid_cell (32 bytes): cell (ix, iy) is entry ix + iy * nx."""
+    _fields_ = [("n", C.c_uint32), ("n_ground", C.c_uint32), ("z_lo", C.c_float), ("z_hi", C.c_float), ("g_lo", C.c_float),
+                ("g_hi", C.c_float), ("i_max", C.c_float), ("state", C.c_uint32)]
+
+
+GRID_DTYPE = np.dtype([("n", "<u4"), ("n_ground", "<u4"), ("z_lo", "<f4"), ("z_hi", "<f4"), ("g_lo", "<f4"), ("g_hi", "<f4"),
+                       ("i_max", "<f4"), ("state", "<u4")])
+assert GRID_DTYPE.itemsize == C.sizeof(GridCell) == 32 and C.sizeof(GridParams) == 36
 
 
 # normals and curvature of the result (cm_result_normals)
@@ -363,6 +384,9 @@ def load():
     L.cm_box_directions.argtypes = [u32, vp, u64]
     L.cm_result_cluster_boxes.argtypes = [vp, C.POINTER(BoxParams), vp, u64, C.POINTER(u64)]
     L.cm_result_cluster_boxes_device.argtypes = [vp, C.POINTER(BoxParams), C.POINTER(vp), C.POINTER(u64)]
+    L.cm_result_grid_map.argtypes = [vp, C.POINTER(GridParams), vp, u64]
+    L.cm_result_grid_map_device.argtypes = [vp, C.POINTER(GridParams), C.POINTER(vp), C.POINTER(u64)]
+    L.cm_grid_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -712,6 +736,43 @@ class CloudMerger:
         self._check(self._lib.cm_result_cluster_boxes_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)),
                     "cm_result_cluster_boxes_device")
         return ptr.value, n.value
+
+    # ---- 2-D grid map of the last frame (cm_result_grid_map) ----
+    @staticmethod
+    def grid_params(origin, cell, nx, ny, z_band=(-np.inf, np.inf), obstacle_height=0.3, min_points=1):
+        return GridParams((C.c_float * 2)(float(origin[0]), float(origin[1])), float(cell), int(nx), int(ny), float(z_band[0]),
+                          float(z_band[1]), float(obstacle_height), int(min_points))
+
+    def grid_map(self, origin, cell, nx, ny, z_band=(-np.inf, np.inf), obstacle_height=0.3, min_points=1):
+        """(ny, nx) GRID_DTYPE array: per cell of the grid whose cell (0, 0) has its corner at origin the counts of the frame's
+        kept and ground points inside z_band, their lowest and highest z, the largest intensity and the state
+        (GRID_UNKNOWN / GRID_FREE / GRID_OCCUPIED). Row iy, column ix."""
+        p = self.grid_params(origin, cell, nx, ny, z_band, obstacle_height, min_points)
+        n = int(nx) * int(ny)
+        out = np.empty(n if 0 < n <= GRID_MAX_CELLS else 1, dtype=GRID_DTYPE)     # (a grid the library refuses: one entry)
+        self._check(self._lib.cm_result_grid_map(self._ctx, C.byref(p), out.ctypes.data, out.shape[0]), "cm_result_grid_map")
+        self._grid_shape = (int(ny), int(nx))
+        return out.reshape(int(ny), int(nx))
+
+    def grid_map_device(self, origin, cell, nx, ny, z_band=(-np.inf, np.inf), obstacle_height=0.3, min_points=1):
+        """(device pointer, cells) of the same table, owned by the context and valid until the next merge or the next grid call."""
+        p = self.grid_params(origin, cell, nx, ny, z_band, obstacle_height, min_points)
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self._check(self._lib.cm_result_grid_map_device(self._ctx, C.byref(p), C.byref(ptr), C.byref(n)), "cm_result_grid_map_device")
+        self._grid_shape = (int(ny), int(nx))
+        return ptr.value, n.value
+
+    def grid_occupancy(self):
+        """(ny, nx) int8 image of the last grid call since the last merge: -1 unknown, 0 free, 100 occupied
+        (nav_msgs/OccupancyGrid::data, row-major)."""
+        n = C.c_uint64()
+        st = self._lib.cm_grid_occupancy_copy(self._ctx, None, 0, C.byref(n))
+        if st != CAPACITY:
+            self._check(st, "cm_grid_occupancy_copy")
+        out = np.empty(max(n.value, 1), dtype=np.int8)
+        self._check(self._lib.cm_grid_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_grid_occupancy_copy")
+        ny, nx = self._grid_shape
+        return out[: n.value].reshape(ny, nx)
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

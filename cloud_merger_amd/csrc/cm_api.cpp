@@ -52,6 +52,7 @@ void free_all(cm_ctx* c) {
     c->cov.release(); F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
     c->cl.release(); F(c->cl_root); F(c->cl_num); F(c->cl_labels); F(c->cl_tile_sums); F(c->cl_words); F(c->cl_clusters);
     F(c->box_entries); F(c->box_dirs); F(c->box_words); F(c->box_list); F(c->box_ext); F(c->box_work); F(c->box_sums);
+    F(c->grid_cells); F(c->grid_image);
     c->nrm.release(); F(c->nrm_list); F(c->nrm_words); F(c->nrm_entries);
     c->aln.release(); c->aln_fit.release();
     c->ndt_fit.release(); F(c->ndt_bounds);
@@ -161,6 +162,23 @@ int boxes_check(cm_ctx* c, const cm_box_params* p) {
     if (p->criterion != CM_BOX_AREA && p->criterion != CM_BOX_CLOSENESS) return fail(c, CM_BAD_ARG, "unknown box criterion");
     if (p->criterion == CM_BOX_CLOSENESS && (!std::isfinite(p->d_min) || !(p->d_min > 0.0f)))
         return fail(c, CM_BAD_ARG, "d_min must be finite and > 0");
+    return CM_OK;
+}
+
+// The refusals of cm_result_grid_map*: CM_OK when the last frame's grid map can be computed with *p.
+int grid_check(cm_ctx* c, const cm_grid_params* p) {
+    if (!p) return fail(c, CM_BAD_ARG, "no grid parameters");
+    if (const int e = centroid_result_check(c)) return e;
+    if (!std::isfinite(p->origin[0]) || !std::isfinite(p->origin[1])) return fail(c, CM_BAD_ARG, "the origin must be finite");
+    if (!std::isfinite(p->cell) || !(p->cell > 0.0f)) return fail(c, CM_BAD_ARG, "cell must be finite and > 0");
+    const float inv = 1.0f / p->cell;
+    if (!std::isfinite(inv) || !(inv > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 inverse of cell must be finite and > 0");
+    if (p->nx == 0 || p->ny == 0) return fail(c, CM_BAD_ARG, "nx and ny must be at least 1");
+    if (static_cast<uint64_t>(p->nx) * p->ny > CM_GRID_MAX_CELLS) return fail(c, CM_BAD_ARG, "nx * ny exceeds CM_GRID_MAX_CELLS");
+    if (std::isnan(p->z_min) || std::isnan(p->z_max)) return fail(c, CM_BAD_ARG, "a band limit is NaN");
+    if (p->z_min > p->z_max) return fail(c, CM_BAD_ARG, "z_min exceeds z_max");
+    if (!std::isfinite(p->obstacle_height) || !(p->obstacle_height >= 0.0f)) return fail(c, CM_BAD_ARG, "obstacle_height must be finite and >= 0");
+    if (p->min_points == 0) return fail(c, CM_BAD_ARG, "min_points must be at least 1");
     return CM_OK;
 }
 
@@ -777,6 +795,61 @@ int cm_result_cluster_boxes_device(cm_ctx* c, const cm_box_params* p, const void
     if (e != CM_OK) return e;
     *dev_ptr = c->box_n ? c->box_entries : nullptr;
     *n_boxes = c->box_n;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_grid_cell) == 32 && sizeof(cm_grid_cell) == CM_GRID_WORDS * 4 && sizeof(cm_grid_params) == 36 &&
+                  sizeof(CmGridDev) == sizeof(cm_grid_params),
+              "cm_grid_cell is 32 bytes, its parameters 36");
+static_assert(offsetof(cm_grid_cell, z_lo) == 8 && offsetof(cm_grid_cell, g_lo) == 16 && offsetof(cm_grid_cell, i_max) == 24 &&
+                  offsetof(cm_grid_cell, state) == 28,
+              "the kernels' record");
+static_assert(CM_GRID_UNKNOWN == CM_GRID_UNKNOWN_DEV && CM_GRID_FREE == CM_GRID_FREE_DEV && CM_GRID_OCCUPIED == CM_GRID_OCCUPIED_DEV,
+              "the kernels' states");
+
+int cm_result_grid_map(cm_ctx* c, const cm_grid_params* p, cm_grid_cell* host_dst, uint64_t capacity_cells) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = grid_check(c, p);
+    if (e != CM_OK) return e;
+    e = grid_map(c, *p);
+    if (e != CM_OK) return e;
+    const uint64_t n = c->grid_n;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "grid destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->grid_cells, n * sizeof(cm_grid_cell), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_grid_cell);
+    return CM_OK;
+}
+
+int cm_result_grid_map_device(cm_ctx* c, const cm_grid_params* p, const void** dev_ptr, uint64_t* n_cells) {
+    if (!c || !dev_ptr || !n_cells) return CM_BAD_ARG;
+    *dev_ptr = nullptr;
+    *n_cells = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    int e = grid_check(c, p);
+    if (e == CM_OK) e = grid_map(c, *p);
+    if (e != CM_OK) return e;
+    *dev_ptr = c->grid_cells;
+    *n_cells = c->grid_n;
+    return CM_OK;
+}
+
+int cm_grid_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells) {
+    if (!c || !n_cells) return CM_BAD_ARG;
+    *n_cells = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->grid_have) return fail(c, CM_BAD_ARG, "no grid map of the last result (cm_result_grid_map first)");
+    const uint64_t n = c->grid_n;
+    *n_cells = n;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "occupancy destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->grid_image, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n;
     return CM_OK;
 }
 

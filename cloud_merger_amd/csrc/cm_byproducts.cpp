@@ -1,6 +1,6 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
-// (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), and the two registrations of a source cloud
-// (align, ndt). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
+// (align, ndt), and the one table computed from the frame's points rather than its result, the 2-D grid map (grid_map). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's.
@@ -389,6 +389,50 @@ int cluster_boxes(cm_ctx* c, const cm_box_params& q) {
     HIP_TRY(c, hipStreamSynchronize(st));
     collect_stage_times(c);
     c->box_n = n_clusters;
+    return CM_OK;
+}
+
+// The 2-D grid map of the last frame (cm_kernels_grid.hip; the semantics are in include/cloudmerge.h): nx * ny cm_grid_cell
+// records into grid_cells and as many occupancy bytes into grid_image. One clear, one pass over the frame's raw points in
+// place (the descriptor in HBM, the keep-mask behind cm_merged_copy, the ground mask behind cm_ground_copy), one pass over the
+// cells; no host round trip but the wait at the end. A steady-state call allocates nothing. Under CM_FLAG_PROFILE the stage
+// times of the call replace the frame's in cm_get_stage_times.
+int grid_map(cm_ctx* c, const cm_grid_params& q) {
+    c->grid_have = false;
+    const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_cells > c->grid_cap_cells) {
+        dev_free(c->grid_cells); dev_free(c->grid_image);
+        c->grid_cap_cells = 0;
+        if (!dev_alloc(&c->grid_cells, n_cells * sizeof(cm_grid_cell)) || !dev_alloc(&c->grid_image, n_cells))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the grid map");
+        c->grid_cap_cells = n_cells;
+    }
+    CmGridDev g;
+    g.origin[0] = q.origin[0];
+    g.origin[1] = q.origin[1];
+    g.inv = 1.0f / q.cell;
+    g.nx = q.nx;
+    g.ny = q.ny;
+    g.z_min = q.z_min;
+    g.z_max = q.z_max;
+    g.obstacle_height = q.obstacle_height;
+    g.min_points = q.min_points;
+    hipStream_t st = c->stream;
+    c->prof_used = 0;
+    prof_mark(c, "grid_clear");
+    HIP_TRY(c, hipMemsetAsync(c->grid_cells, 0, n_cells * sizeof(cm_grid_cell), st));
+    prof_mark(c, "k_grid_bin");
+    // (an empty frame has no tiles and, on a fresh context, no descriptor in HBM: nothing is launched)
+    cmk_grid_bin(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->grid_cells, c->frame.n_tiles);
+    prof_mark(c, "k_grid_finish");
+    cmk_grid_finish(st, c->grid_cells, c->grid_image, static_cast<uint32_t>(n_cells), q.obstacle_height, q.min_points);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->grid_n = n_cells;
+    c->grid_have = true;
     return CM_OK;
 }
 

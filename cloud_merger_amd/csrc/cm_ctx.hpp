@@ -255,6 +255,15 @@ struct cm_ctx {
     uint64_t box_cap_chunks = 0;
     uint32_t box_split = CM_BOX_SPLIT;   // (CM_BOX_SPLIT in the environment: the measurement of scripts/box_cost.py)
 
+    // 2-D grid map of the frame (cm_kernels_grid.hip), on request after a frame: it reads the frame's clouds in place (d_frame,
+    // frame_mask, gmask) and writes a table and an image of its own — no frame reads them — allocated by the first request and
+    // grown with the grids asked for.
+    void* grid_cells = nullptr;          // the table: cm_grid_cell per cell
+    void* grid_image = nullptr;          // the occupancy image: one byte per cell
+    uint64_t grid_cap_cells = 0;         // cells both are sized for
+    uint64_t grid_n = 0;                 // cells of the last grid call
+    bool grid_have = false;              // the two hold the grid of the result at rest (cleared where a merge replaces it)
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -334,7 +343,7 @@ void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t 
 
 // cm_byproducts.cpp: the tables computed from the last result on request. Called with merge_mu held.
 // The tables of the last result go with it (where a merge replaces the result).
-inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = false; }
+inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = c->grid_have = false; }
 // The covariance table of the last result (cov_entries, n_out entries).
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 // The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
@@ -344,6 +353,8 @@ int clusters(cm_ctx* c, const cm_cluster_params& q, bool more_stages = false);
 int cluster_boxes(cm_ctx* c, const cm_box_params& q);
 // The direction table of n_angles headings (1..CM_BOX_MAX_ANGLES): 2 * n_angles floats.
 void box_direction_table(uint32_t n_angles, float* cos_sin);
+// The grid map of the last frame at q (grid_cells and grid_image, grid_n = q.nx * q.ny cells).
+int grid_map(cm_ctx* c, const cm_grid_params& q);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

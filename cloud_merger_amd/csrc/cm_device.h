@@ -272,3 +272,23 @@ struct CmBoxDev {
     double score;
     uint32_t flags, _pad;
 };
+
+// 2-D grid map of the frame (cm_kernels_grid.hip): what the kernels take of cm_grid_params (inv = 1.0f / cell, formed on the
+// host) and the states of include/cloudmerge.h (cm_api.cpp asserts that they agree). A cell's record is 8 words, kept as
+// images whose zero means "nothing yet" until k_grid_finish: n, n_ground, ~ord(z_lo), ord(z_hi), ~ord(g_lo), ord(g_hi),
+// ord(i_max), 0 — ord the order-preserving image of a float, never 0 and never 0xFFFFFFFF for a number that is not NaN, so
+// that every field grows by an add or a max from a table cleared to zero bytes.
+#define CM_GRID_UNKNOWN_DEV 0u
+#define CM_GRID_FREE_DEV 1u
+#define CM_GRID_OCCUPIED_DEV 2u
+#define CM_GRID_WORDS 8
+#define CM_GRID_HASH 1024         // slots of k_grid_bin's LDS table of a tile's distinct cells (a power of two)
+#define CM_GRID_PROBES 8          // slots a point tries before it goes to the table in HBM itself
+struct CmGridDev {
+    float origin[2];
+    float inv;
+    uint32_t nx, ny;
+    float z_min, z_max;
+    float obstacle_height;
+    uint32_t min_points;
+};

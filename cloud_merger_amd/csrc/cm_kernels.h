@@ -225,3 +225,11 @@ void cmk_box_sums(hipStream_t s, const void* recs, const void* clusters, const u
                   uint32_t max_chunks);
 void cmk_box_choose(hipStream_t s, const void* clusters, const void* dirs, uint32_t n_angles, double step, uint32_t criterion,
                     const uint32_t* words, const void* list, const void* ext, const double* sums, void* boxes, uint32_t max_large);
+
+// ---- 2-D grid map of the frame (cm_kernels_grid.hip) ------------------------------------------------------------------------
+// table: nx * ny records of CM_GRID_WORDS words, zero bytes before cmk_grid_bin. cmk_grid_bin adds the frame's points (fd: the
+// uploaded descriptor; keep: the frame's keep-mask or nullptr for "every valid point"; ground: its ground mask or nullptr for
+// none) as images; cmk_grid_finish turns them into cm_grid_cell records in place and writes the occupancy bytes into image.
+void cmk_grid_bin(hipStream_t s, const CmFrameDev* fd, const CmGridDev& g, const unsigned char* keep, const unsigned char* ground,
+                  void* table, uint32_t n_tiles);
+void cmk_grid_finish(hipStream_t s, void* table, void* image, uint32_t n_cells, float obstacle_height, uint32_t min_points);

@@ -155,6 +155,14 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             c.cluster_box_criterion = v == "area" ? CM_BOX_AREA : CM_BOX_CLOSENESS;
         }
         else if (key == "cluster_box_d_min") ok = static_cast<bool>(is >> c.cluster_box_d_min) && c.cluster_box_d_min > 0.0f && std::isfinite(c.cluster_box_d_min);
+        else if (key == "grid_cell") ok = static_cast<bool>(is >> c.grid_cell) && std::isfinite(c.grid_cell) && c.grid_cell >= 0.0f &&
+                                          (c.grid_cell == 0.0f || std::isfinite(1.0f / c.grid_cell));
+        else if (key == "grid_origin") ok = static_cast<bool>(is >> c.grid_origin[0] >> c.grid_origin[1]) && std::isfinite(c.grid_origin[0]) && std::isfinite(c.grid_origin[1]);
+        else if (key == "grid_size") ok = static_cast<bool>(is >> c.grid_nx >> c.grid_ny) && c.grid_nx >= 1 && c.grid_ny >= 1 &&
+                                          static_cast<uint64_t>(c.grid_nx) * c.grid_ny <= CM_GRID_MAX_CELLS;
+        else if (key == "grid_z_band") ok = static_cast<bool>(is >> c.grid_z_band[0] >> c.grid_z_band[1]) && c.grid_z_band[0] <= c.grid_z_band[1];
+        else if (key == "grid_obstacle_height") ok = static_cast<bool>(is >> c.grid_obstacle_height) && std::isfinite(c.grid_obstacle_height) && c.grid_obstacle_height >= 0.0f;
+        else if (key == "grid_min_points") ok = static_cast<bool>(is >> c.grid_min_points) && c.grid_min_points >= 1;
         else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "align_prev") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.align_prev = v == 1; }
         else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
@@ -317,6 +325,27 @@ int CloudMergerNode::clusters_of_frame(const cm_result& r) {
     return CM_OK;
 }
 
+int CloudMergerNode::grid_of_frame(const cm_result& r) {
+    grid_cells_.clear();
+    grid_occupancy_.clear();
+    if (!(cfg_.grid_cell > 0.0f) || r.status != CM_OK) return CM_OK;
+    const cm_grid_params q{{cfg_.grid_origin[0], cfg_.grid_origin[1]}, cfg_.grid_cell, cfg_.grid_nx, cfg_.grid_ny,
+                           cfg_.grid_z_band[0], cfg_.grid_z_band[1], cfg_.grid_obstacle_height, cfg_.grid_min_points};
+    const size_t n = static_cast<size_t>(q.nx) * q.ny;
+    grid_cells_.resize(n);
+    grid_occupancy_.resize(n);
+    uint64_t n_cells = 0;
+    int st = cm_result_grid_map(ctx_, &q, grid_cells_.data(), n);
+    if (st == CM_OK) st = cm_grid_occupancy_copy(ctx_, grid_occupancy_.data(), n, &n_cells);
+    if (st != CM_OK || n_cells != n) {
+        grid_cells_.clear();
+        grid_occupancy_.clear();
+        set_error(st != CM_OK ? cm_last_error(ctx_) : "the occupancy image does not match the grid");
+        return st != CM_OK ? st : CM_INTERNAL;
+    }
+    return CM_OK;
+}
+
 int CloudMergerNode::normals_of_frame(const cm_result& r) {
     normals_.clear();
     if (cfg_.normals_k == 0 || r.status != CM_OK) return CM_OK;
@@ -454,6 +483,7 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
+    { const int gs = grid_of_frame(r); if (gs != CM_OK) return gs; }
     { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
     { const int as = align_of_frame(r); if (as != CM_OK) return as; }
     {
@@ -557,6 +587,7 @@ int CloudMergerNode::spin_once(cm_result* res) {
     if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
+    { const int gs = grid_of_frame(r); if (gs != CM_OK) return gs; }
     { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
     { const int as = align_of_frame(r); if (as != CM_OK) return as; }
     {

@@ -9,6 +9,7 @@
 #include <atomic>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -86,6 +87,16 @@ struct NodeConfig {
     uint32_t cluster_box_angles = 0;
     uint32_t cluster_box_criterion = CM_BOX_CLOSENESS;
     float cluster_box_d_min = 0.01f;
+    // 2-D grid map of every frame (cm_result_grid_map: per-cell counts, lowest and highest return, occupancy; the image is
+    // nav_msgs/OccupancyGrid::data). Off by default (grid_cell 0). On: after the frame has been waited for the node asks for
+    // the table and the image and keeps them until the next frame (grid_cells(), grid_occupancy()). The origin is the corner of
+    // cell (0, 0) in the base frame.
+    float grid_cell = 0.0f;
+    float grid_origin[2] = {0.0f, 0.0f};
+    uint32_t grid_nx = 1, grid_ny = 1;
+    float grid_z_band[2] = {-std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity()};
+    float grid_obstacle_height = 0.3f;
+    uint32_t grid_min_points = 1;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -120,6 +131,8 @@ struct NodeConfig {
 //   cluster_tolerance <metres> | cluster_min_size <n> | cluster_max_size <n>   (clusters of every voxel cloud; 0: off)
 //   cluster_box_angles <n> | cluster_box_criterion <area|closeness> | cluster_box_d_min <metres>   (oriented boxes of those
 //   clusters from n headings, 1..180; 0: off)
+//   grid_cell <metres> | grid_origin <x> <y> | grid_size <nx> <ny> | grid_z_band <lo> <hi> | grid_obstacle_height <metres> |
+//   grid_min_points <n>   (the 2-D grid map of every frame; grid_cell 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -194,6 +207,10 @@ public:
     const std::vector<uint32_t>& cluster_labels() const { return cluster_labels_; }
     // cluster_box_angles > 0 as well: the oriented box of each of those clusters, cluster_count() entries.
     const std::vector<cm_cluster_box>& cluster_boxes() const { return cluster_boxes_; }
+    // grid_cell > 0: the grid map of the frame waited for last, grid_nx * grid_ny entries, cell (ix, iy) at ix + iy * grid_nx, and
+    // its occupancy image (-1 unknown, 0 free, 100 occupied); both empty where the frame has no voxel grid.
+    const std::vector<cm_grid_cell>& grid_cells() const { return grid_cells_; }
+    const std::vector<int8_t>& grid_occupancy() const { return grid_occupancy_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -245,6 +262,9 @@ private:
     std::vector<uint32_t> cluster_labels_;
     std::vector<cm_cluster_box> cluster_boxes_;
     int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters (and the boxes) when the config asks for it
+    std::vector<cm_grid_cell> grid_cells_;
+    std::vector<int8_t> grid_occupancy_;
+    int grid_of_frame(const cm_result& r);         // after cm_wait: cm_result_grid_map and the image when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     bool has_alignment_ = false;

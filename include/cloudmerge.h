@@ -517,6 +517,70 @@ CM_API int cm_result_cluster_boxes(cm_ctx* ctx, const cm_box_params* p, cm_clust
 /* The same table left in device memory owned by the context (*n_boxes entries of 48 bytes; NULL where there is none). */
 CM_API int cm_result_cluster_boxes_device(cm_ctx* ctx, const cm_box_params* p, const void** dev_ptr, uint64_t* n_boxes);
 
+/* ---- 2-D grid map of the frame: per-cell counts, heights, occupancy (an extension) -------------------------------------
+ * What a planner takes instead of a cloud: a grid in the common frame that says per cell "nothing seen", "seen and
+ * drivable" or "obstacle", with the cell's lowest and highest return beside it (a costmap / elevation-map layer; the image
+ * of step 5 is nav_msgs/OccupancyGrid::data). Computed on request after a frame. Every quantity is
+ * order-free — integer counts, minima, maxima — so the table is a function of the frame and the parameters alone, bit for
+ * bit. All fp32 operations are rounded one at a time, round-to-nearest, no contraction.
+ * Inputs, of the last frame: A, the cloud cm_merged_copy returns (the points that entered the voxel grid: after transform,
+ * crop, non-finite drop, deskew, the outlier stages' masks, and ground removal where it is on), and G, the cloud
+ * cm_ground_copy returns when the frame ran with ground removal (otherwise G is empty). A point is in at most one of the
+ * two. A record is (x, y, z, intensity). The call reads the frame's clouds in place: they stay valid until the next frame is
+ * enqueued, as for cm_result_voxel_cov.
+ *   1. Cell of a point. inv = 1.0f / cell (an fp32 division). Per axis a in {x, y}: t = (p_a - origin_a) * inv (the
+ *      subtraction rounded, then the product), c = floorf(t). The point is in the grid iff c >= 0.0f && c < float(n_a) on
+ *      both axes, tested in float: a t of +-inf or NaN fails, -0.0f passes as cell 0. Then i_a = (int)c and the cell's index
+ *      is ix + iy * nx: x is fastest, the row-major order of nav_msgs/OccupancyGrid.
+ *   2. Band. A point in the grid is counted iff z_min <= z && z <= z_max (fp32 compares; infinite limits are allowed). The
+ *      band applies to A and G alike.
+ *   3. Per cell the record cm_grid_cell: n / n_ground count the counted points of A / G; z_lo, z_hi are the minimum and
+ *      maximum z of A's counted points, g_lo, g_hi of G's; i_max is the largest intensity among the counted points of both
+ *      clouds whose intensity is not NaN. Minima and maxima are taken in the order-preserving integer image of the float
+ *      (bits b: b ^ 0xFFFFFFFF when the sign is set, else b ^ 0x80000000; the image of the cluster table's bounds): of two
+ *      zeros of either sign the minimum is -0 and the maximum +0. A field with nothing to take an extreme of is the canonical
+ *      quiet NaN 0x7FC00000.
+ *   4. State. m = n + n_ground. m < min_points: CM_GRID_UNKNOWN. Otherwise n == 0: CM_GRID_FREE. Otherwise lo = z_lo when
+ *      n_ground == 0, else the smaller of z_lo and g_lo in the same integer order; the cell is CM_GRID_OCCUPIED iff
+ *      (z_hi - lo) >= obstacle_height, the subtraction in fp32, else CM_GRID_FREE. So with ground removal on and
+ *      obstacle_height 0 any non-ground return occupies its cell; without ground removal the rule is the classic
+ *      height-difference map.
+ *   5. Occupancy image. One int8_t per cell in the same order: -1 UNKNOWN, 0 FREE, 100 OCCUPIED.
+ * Refused with CM_BAD_ARG (cm_last_error says why): everything cm_result_clusters refuses about the result (a frame in
+ * flight, no result, a result of cm_merge_partial / cm_merge_tables, a last status other than CM_OK); NULL parameters; an
+ * origin that is not finite; a cell that is not finite and > 0, or whose inv is not finite and > 0; nx or ny 0, or
+ * nx * ny > CM_GRID_MAX_CELLS; a NaN band limit or z_min > z_max; an obstacle_height that is not finite and >= 0; min_points
+ * 0. The table and the image are owned by the context and valid until the next merge or the next grid call. No later frame
+ * depends on whether they were asked for; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists this call's stages
+ * (k_grid_bin, k_grid_finish). */
+#define CM_GRID_MAX_CELLS (1u << 22)
+#define CM_GRID_UNKNOWN   0u
+#define CM_GRID_FREE      1u
+#define CM_GRID_OCCUPIED  2u
+typedef struct cm_grid_params {        /* 36 bytes, no padding */
+    float origin[2];                   /* the corner of cell (0, 0), common frame; finite */
+    float cell;                        /* edge of a cell (m); finite, > 0 */
+    uint32_t nx, ny;                   /* cells along x and y; nx * ny <= CM_GRID_MAX_CELLS */
+    float z_min, z_max;                /* closed height band; infinities allowed */
+    float obstacle_height;             /* finite, >= 0 */
+    uint32_t min_points;               /* >= 1 */
+} cm_grid_params;
+typedef struct cm_grid_cell {          /* 32 bytes, cell (ix, iy) is entry ix + iy * nx */
+    uint32_t n;                        /* counted points of A */
+    uint32_t n_ground;                 /* counted points of G */
+    float z_lo, z_hi;                  /* of A's counted points; NaN when n == 0 */
+    float g_lo, g_hi;                  /* of G's counted points; NaN when n_ground == 0 */
+    float i_max;                       /* NaN when no counted point has an intensity that is not NaN */
+    uint32_t state;                    /* CM_GRID_* */
+} cm_grid_cell;
+/* Host copy; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied; the table stays in the context). */
+CM_API int cm_result_grid_map(cm_ctx* ctx, const cm_grid_params* p, cm_grid_cell* host_dst, uint64_t capacity_cells);
+/* The same table left in device memory owned by the context (*n_cells entries of 32 bytes). */
+CM_API int cm_result_grid_map_device(cm_ctx* ctx, const cm_grid_params* p, const void** dev_ptr, uint64_t* n_cells);
+/* The occupancy image of the last grid call since the last merge; capacity in cells. *n_cells is always written (0 when
+ * there is no such call: CM_BAD_ARG); a destination that is too small: CM_CAPACITY (nothing is copied). */
+CM_API int cm_grid_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
