@@ -25,6 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
@@ -90,6 +92,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
     constexpr int WB = SUB ? 9 : 10, BINS = 1 << WB, HWORDS = BINS / 2;          // two 16-bit counters per LDS word
     constexpr uint32_t MAXJ = LWAVES * HWORDS * 4 / sizeof(Job3);                  // jobs that fit where the counters were
     static_assert(LT == 4 * LBLOCK && LCAP <= 0x7FFE && HWORDS <= LBLOCK && LWAVES * HWORDS * 2 >= LCAP, "tile geometry");
+    static_assert(LITEMS % 4 == 0 && HWORDS >= 64, "the returning adds go out in groups of four; a slot without a record adds to word `lane`");
     __shared__ uint32_t sk[LCAP];                      // key of every slot
     __shared__ uint16_t si[LCAP];                      // slots in sorted order
     __shared__ uint32_t whist[LWAVES][HWORDS];         // digit counts per wave
@@ -128,6 +131,7 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
     const uint32_t bin = SUB ? tile >> sub_shift : tile;
     uint32_t base = QUANT ? SCAL(bofs[bin]) : tile * LT;
     const uint32_t rbase = base;                                 // slot s is record rbase + s (SUB: rbase + sp[s])
+    const float4* __restrict__ recb = rec + rbase;               // (a scalar base: the slot is a 32-bit offset of the load)
     const uint32_t q_end = QUANT ? SCAL(bofs[bin + 1]) : 0u;
     bool q_big = QUANT && !SUB && (q_end - base) > static_cast<uint32_t>(LCAP);
     if (QUANT && q_big && !big_list && (q_end - base) <= CM4_CAP_BIG) return;     // (the large shape's launch takes this bucket)
@@ -178,18 +182,37 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && nom <= static_cast<uint32_t>(HALF * LBLOCK)) break;     // (uniform)
             float4 r4[HALF];
+            // (a wave whose slots of the half's last round all hold a record — one scalar compare — runs the half straight
+            // through: no test per lane, the loads and then the stores one behind the other)
+            if ((h * HALF + HALF - 1) * LBLOCK + w * 64u + 64u <= nom) {
+                uint32_t pl[HALF];
 #pragma unroll
-            for (int r = 0; r < HALF; ++r) {
-                const uint32_t q = (h * HALF + r) * LBLOCK + threadIdx.x;
-                r4[r] = (q < nom) ? rec[rbase + (SUB ? sp[q < nom ? q : 0u] : q)] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+                for (int r = 0; r < HALF; ++r) {
+                    const uint32_t q = (h * HALF + r) * LBLOCK + threadIdx.x;
+                    pl[r] = SUB ? sp[q] : q;
+                }
 #pragma unroll
-            for (int r = 0; r < HALF; ++r) {
-                const uint32_t q = (h * HALF + r) * LBLOCK + threadIdx.x;
-                if (q < nom) {
+                for (int r = 0; r < HALF; ++r) r4[r] = recb[pl[r]];
+#pragma unroll
+                for (int r = 0; r < HALF; ++r) {
                     const uint32_t k = key_of(b, r4[r]);
-                    sk[q] = k;
-                    q_bad = q_bad || k < q_lo || k >= q_hi;      // (the scatter put a record into a bucket that is not its own)
+                    sk[(h * HALF + r) * LBLOCK + threadIdx.x] = k;
+                    q_bad = q_bad | (k < q_lo) | (k >= q_hi);    // (the scatter put a record into a bucket that is not its own)
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < HALF; ++r) {
+                    const uint32_t q = (h * HALF + r) * LBLOCK + threadIdx.x;
+                    r4[r] = (q < nom) ? rec[rbase + (SUB ? sp[q < nom ? q : 0u] : q)] : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+#pragma unroll
+                for (int r = 0; r < HALF; ++r) {
+                    const uint32_t q = (h * HALF + r) * LBLOCK + threadIdx.x;
+                    if (q < nom) {
+                        const uint32_t k = key_of(b, r4[r]);
+                        sk[q] = k;
+                        q_bad = q_bad || k < q_lo || k >= q_hi;
+                    }
                 }
             }
         }
@@ -286,76 +309,125 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
         const uint32_t width = nb ? (nb + npass - 1u) / npass : 0u;
         const uint32_t dmask = (1u << width) - 1u;
         const uint32_t rounds = (m + LBLOCK - 1) / LBLOCK;
-        for (uint32_t p = 0; p < npass; ++p) {
-            const uint32_t wp = nb > p * width ? min(width, nb - p * width) : 0u;     // bits this pass really sorts
-            const uint32_t words = wp ? ((1u << wp) + 1u) / 2u : 1u;
-            uint32_t dg[LITEMS], rk[LITEMS];
-            uint16_t ei[LITEMS];
+        // Wave w ranks the positions [w * 64 * rounds, (w + 1) * 64 * rounds): round r, lane l is position e0 + r * 64 + l and
+        // holds a record while r * 64 + l < cnt_w. The passes are compiled for R = 4 and R = LITEMS rounds (a bucket of the
+        // usual size takes four) as straight-line code: a thread's reads of si, then of sk, then its returning adds — in
+        // ascending r: the order of a lane's own records on one counter IS their stable rank — go out one behind the other
+        // and are waited for once. A wave whose R rounds are all full (a scalar compare) tests nothing per lane; in any
+        // other wave a slot without a record reads a clamped position and adds zero to a word of its own lane (the LDS
+        // serialises the adds of a wave that meet on one word).
+        const uint32_t e0 = w * (64u * rounds);
+        const uint32_t cnt_w = e0 < m ? min(m - e0, 64u * rounds) : 0u;
+        auto sort_passes = [&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            const bool all_full = R < LITEMS && cnt_w == 64u * R;             // (uniform; the long form always tests)
+            for (uint32_t p = 0; p < npass; ++p) {
+                const uint32_t wp = nb > p * width ? min(width, nb - p * width) : 0u;     // bits this pass really sorts
+                const uint32_t words = wp ? ((1u << wp) + 1u) / 2u : 1u;
+                uint32_t ed[R], rk[R];                     // slot (16 bits) | digit << 16; rank among the wave's records of the digit
+                auto digits = [&](auto fc) {
+                    constexpr bool FULL = decltype(fc)::value;
+                    uint32_t kk[R];
+                    uint32_t ln = lane;                            // (opaque: what depends on the lane alone is formed in every pass —
+                    asm volatile("" : "+v"(ln));                   //  hoisted out of the pass loop it stays live across it and spills)
+                    // (these opaque copies, here and in the two phases below, only steer LLVM's hoisting and register
+                    // allocation: after any change of the toolchain check scripts/kernel_resources.sh again — 64 VGPRs, no scratch)
+                    if (p == 0) {
 #pragma unroll
-            for (int r = 0; r < LITEMS; ++r) {
-                const uint32_t e = w * (64 * rounds) + r * 64 + lane;
-                ei[r] = 0; dg[r] = 0;
-                if (static_cast<uint32_t>(r) >= rounds) break;         // (uniform)
-                if (e < m) {
-                    ei[r] = (p == 0) ? static_cast<uint16_t>(a + e) : si[e];
-                    dg[r] = ((sk[ei[r]] - kbase) >> (p * width)) & dmask;
+                        for (int r = 0; r < R; ++r) ed[r] = a + (FULL ? e0 + r * 64 + ln : min(e0 + r * 64 + ln, m - 1u));
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < R; ++r) ed[r] = si[FULL ? e0 + r * 64 + ln : min(e0 + r * 64 + ln, m - 1u)];
+                    }
+#pragma unroll
+                    for (int r = 0; r < R; ++r) kk[r] = sk[ed[r]];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) ed[r] |= (((kk[r] - kbase) >> (p * width)) & dmask) << 16;
+                };
+                if (all_full) digits(std::true_type{}); else digits(std::false_type{});
+#pragma unroll
+                for (int q = 0; q < LWAVES * HWORDS / LBLOCK; ++q) {
+                    const uint32_t flat = q * LBLOCK + threadIdx.x;       // row = flat / HWORDS, column = flat % HWORDS
+                    if ((flat & (HWORDS - 1)) < words) (&whist[0][0])[flat] = 0;
                 }
-            }
-#pragma unroll
-            for (int q = 0; q < LWAVES * HWORDS / LBLOCK; ++q) {
-                const uint32_t flat = q * LBLOCK + threadIdx.x;       // row = flat / HWORDS, column = flat % HWORDS
-                if ((flat & (HWORDS - 1)) < words) (&whist[0][0])[flat] = 0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < LITEMS; ++r) {
-                const uint32_t e = w * (64 * rounds) + r * 64 + lane;
-                const uint32_t sh = (dg[r] & 1u) * 16u;
-                rk[r] = 0;
-                if (static_cast<uint32_t>(r) >= rounds) break;         // (uniform)
-                if (BALLOT) rk[r] = wave_rank_ballot(whist[w], dg[r], wp, e < m, lane);        // (cm_common.hpp: no returning adds)
-                else if (e < m) rk[r] = (atomicAdd(&whist[w][dg[r] >> 1], 1u << sh) >> sh) & 0xFFFFu;
-            }
-            __syncthreads();
-            // thread t < words: digits 2t and 2t+1. Totals over the waves, exclusive prefix over the digits (one barrier: the
-            // wave totals alternate between two sets of words from pass to pass), then every wave's counter becomes the
-            // first sorted position of its items of that digit — 16 bits each, positions stay below LCAP.
-            uint32_t cw[LWAVES], t0 = 0, t1 = 0;
-            if (threadIdx.x < words) {
-#pragma unroll
-                for (int q = 0; q < LWAVES; ++q) { cw[q] = whist[q][threadIdx.x]; t0 += cw[q] & 0xFFFFu; t1 += cw[q] >> 16; }
-            }
-            uint32_t db;
-            {
-                uint32_t* wl = lds + (p & 1u) * LWAVES;
-                const uint32_t incl = wave_incl_scan_u32(t0 + t1, lane);
-                if (lane == 63) wl[w] = incl;
                 __syncthreads();
-                uint32_t woff = 0;
+                auto ranks = [&](auto fc) {
+                    constexpr bool FULL = decltype(fc)::value;
+                    uint32_t ln = lane;
+                    asm volatile("" : "+v"(ln));
+                    if (BALLOT) {
 #pragma unroll
-                for (int q = 0; q < LWAVES; ++q) woff += (q < w) ? wl[q] : 0u;
-                db = woff + incl - (t0 + t1);
-            }
-            if (threadIdx.x < words) {
-                uint32_t r0 = db, r1 = db + t0;
+                        for (int r = 0; r < R; ++r) {                      // (cm_common.hpp: no returning adds; one record after the other)
+                            rk[r] = wave_rank_ballot(whist[w], ed[r] >> 16, wp, FULL || r * 64 + ln < cnt_w, static_cast<int>(ln));
+                            asm volatile("" : "+v"(rk[r]));
+                        }
+                    } else {
 #pragma unroll
-                for (int q = 0; q < LWAVES; ++q) {
-                    whist[q][threadIdx.x] = r0 | (r1 << 16);
-                    r0 += cw[q] & 0xFFFFu; r1 += cw[q] >> 16;
+                        for (int r0 = 0; r0 < R; r0 += 4) {                // (four returns in flight, as k4_scatter)
+                            uint32_t got[4];
+#pragma unroll
+                            for (int r = r0; r < r0 + 4; ++r) {
+                                const bool has = FULL || r * 64 + ln < cnt_w;
+                                got[r - r0] = atomicAdd(&whist[w][has ? ed[r] >> 17 : ln], (has ? 1u : 0u) << (ed[r] & 0x10000u ? 16u : 0u));
+                            }
+                            asm volatile("" : "+v"(got[0]), "+v"(got[1]), "+v"(got[2]), "+v"(got[3]));     // (all four asked for before one is used)
+#pragma unroll
+                            for (int r = r0; r < r0 + 4; ++r) {
+                                rk[r] = (got[r - r0] >> (ed[r] & 0x10000u ? 16u : 0u)) & 0xFFFFu;
+                                asm volatile("" : "+v"(rk[r]));          // (formed here: the raw returns need not stay alive)
+                            }
+                        }
+                    }
+                };
+                if (all_full) ranks(std::true_type{}); else ranks(std::false_type{});
+                __syncthreads();
+                // thread t < words: digits 2t and 2t+1. Totals over the waves, exclusive prefix over the digits (one barrier: the
+                // wave totals alternate between two sets of words from pass to pass), then every wave's counter becomes the
+                // first sorted position of its items of that digit — 16 bits each, positions stay below LCAP.
+                uint32_t cw[LWAVES], t0 = 0, t1 = 0;
+                if (threadIdx.x < words) {
+#pragma unroll
+                    for (int q = 0; q < LWAVES; ++q) { cw[q] = whist[q][threadIdx.x]; t0 += cw[q] & 0xFFFFu; t1 += cw[q] >> 16; }
                 }
-            }
-            __syncthreads();
+                uint32_t db;
+                {
+                    uint32_t* wl = lds + (p & 1u) * LWAVES;
+                    const uint32_t incl = wave_incl_scan_u32(t0 + t1, lane);
+                    if (lane == 63) wl[w] = incl;
+                    __syncthreads();
+                    uint32_t woff = 0;
 #pragma unroll
-            for (int r = 0; r < LITEMS; ++r) {
-                const uint32_t e = w * (64 * rounds) + r * 64 + lane;
-                if (static_cast<uint32_t>(r) >= rounds) break;         // (uniform)
-                if (e < m) {
-                    const uint32_t pos = ((whist[w][dg[r] >> 1] >> ((dg[r] & 1u) * 16u)) & 0xFFFFu) + rk[r];
-                    si[pos] = ei[r];
+                    for (int q = 0; q < LWAVES; ++q) woff += (q < w) ? wl[q] : 0u;
+                    db = woff + incl - (t0 + t1);
                 }
+                if (threadIdx.x < words) {
+                    uint32_t r0 = db, r1 = db + t0;
+#pragma unroll
+                    for (int q = 0; q < LWAVES; ++q) {
+                        whist[q][threadIdx.x] = r0 | (r1 << 16);
+                        r0 += cw[q] & 0xFFFFu; r1 += cw[q] >> 16;
+                    }
+                }
+                __syncthreads();
+                auto place = [&](auto fc) {
+                    constexpr bool FULL = decltype(fc)::value;
+                    uint32_t first[R];
+                    uint32_t ln = lane;
+                    asm volatile("" : "+v"(ln));
+#pragma unroll
+                    for (int r = 0; r < R; ++r) first[r] = whist[w][ed[r] >> 17];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const uint32_t pos = ((first[r] >> (ed[r] & 0x10000u ? 16u : 0u)) & 0xFFFFu) + rk[r];
+                        if (FULL || r * 64 + ln < cnt_w) si[pos] = static_cast<uint16_t>(ed[r]);
+                    }
+                };
+                if (all_full) place(std::true_type{}); else place(std::false_type{});
+                __syncthreads();
             }
-            __syncthreads();
-        }
+        };
+        if (LITEMS > 4 && rounds <= 4u) sort_passes(std::integral_constant<int, 4>{});
+        else sort_passes(std::integral_constant<int, LITEMS>{});
     }
     if (s_bad && threadIdx.x == 0) host_state[offsetof(CmFrameState, err) / 4] = CM_DEV_ERR_UNSORTED;
     PH(g_phase_k3, 2);
@@ -400,49 +472,6 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
     {
         const uint32_t per = (m + LBLOCK - 1) / LBLOCK;        // sorted positions per thread (<= LITEMS)
         const uint32_t i0 = threadIdx.x * per;
-        uint32_t k[LITEMS];
-        uint16_t sl[LITEMS];
-        uint32_t heads = 0, kheads = 0;
-        const uint32_t kp = (i0 > 0 && i0 < m) ? sk[si[i0 - 1]] : 0u;
-#pragma unroll
-        for (int j = 0; j < LITEMS; ++j) { k[j] = 0; sl[j] = 0; }
-#pragma unroll
-        for (int j = 0; j < LITEMS; ++j) {
-            if (static_cast<uint32_t>(j) >= per) break;        // (uniform)
-            if (i0 + j < m) { sl[j] = si[i0 + j]; k[j] = sk[sl[j]]; }
-        }
-#pragma unroll
-        for (int j = 0; j < LITEMS; ++j) {
-            if (static_cast<uint32_t>(j) >= per) break;        // (uniform)
-            if (i0 + j < m) {
-                const uint32_t prev = j ? k[j ? j - 1 : 0] : kp;
-                if (i0 + j == 0 || k[j] != prev) {
-                    heads |= 1u << j;
-                    bool keep = true;
-                    if (min_pts > 1) keep = (min_pts - 1u) < (m - (i0 + j)) && sk[si[i0 + j + min_pts - 1u]] == k[j];
-                    if (keep) kheads |= 1u << j;
-                }
-            }
-        }
-        // which of the block's positions belong to a kept voxel with its head in the block: those records are loaded
-        uint32_t ldm = 0;
-        {
-            bool on = false;
-#pragma unroll
-            for (int j = 0; j < LITEMS; ++j) {
-                if (static_cast<uint32_t>(j) >= per) break;    // (uniform)
-                if ((heads >> j) & 1u) on = (kheads >> j) & 1u;
-                if (on && i0 + j < m) ldm |= 1u << j;
-            }
-        }
-        float4 r4[LITEMS];
-#pragma unroll
-        for (int j = 0; j < LITEMS; ++j) {
-            if (static_cast<uint32_t>(j) >= per) break;        // (uniform)
-            if ((ldm >> j) & 1u) r4[j] = rec[rbase + (SUB ? sp[sl[j]] : sl[j])];
-        }
-        const uint32_t kid0 = block_excl_scan<LWAVES>(static_cast<uint32_t>(__builtin_popcount(kheads)), lds, &c_t);
-
         auto emit = [&](uint32_t kid, uint32_t key, float sx, float sy, float sz, float sw, uint32_t cn) {
             const size_t o = static_cast<size_t>(base) + a + kid;
             if (PARTIAL) {                                     // cm_partial_entry: key, count, sx, sy | sz, si, 0, 0
@@ -454,22 +483,82 @@ __global__ __launch_bounds__(LBLOCK, WPS) void k3_local(const CmFrameDev* __rest
                 if (stage_key) stage_key[o] = key;
             }
         };
-        uint32_t kid = kid0, cn = 0, ckey = 0;
+        uint32_t kid = 0, cn = 0, ckey = 0;
         float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
         bool on = false;
+        // Compiled for R = 4 and R = LITEMS positions per thread, as the sort: the slots and keys of a block (and the key before
+        // it) are fetched together, heads, keep and the load mask are bit arithmetic on those registers, and the records of
+        // the kept voxels are asked for one behind the other. A thread holds nv of its R positions (all of them in a wave
+        // whose whole range lies below m: a scalar compare, and then nothing is clamped or tested); position nv counts as a
+        // head, so a run of the block ends there. min_pts: a head at j is kept when the d = min_pts - 1 positions behind it are
+        // in the block and none of them is a head; only the block's LAST head can run on past the block, and only for that
+        // one the key d positions on is looked up in LDS (the keys are sorted: it is the head's key iff all between are).
+        auto voxels = [&](auto rc) {
+            constexpr int R = decltype(rc)::value;
+            const bool all_full = R < LITEMS && per == static_cast<uint32_t>(R) && (w * 64u + 64u) * R <= m;   // (uniform)
+            uint32_t k[R], sl[R];
+            uint32_t heads = 0, kheads = 0, ldm = 0;
+            float4 r4[R];
+            auto front = [&](auto fc) {
+                constexpr bool FULL = decltype(fc)::value;
+                const uint32_t nv = FULL ? static_cast<uint32_t>(R) : (i0 < m ? min(m - i0, per) : 0u);
+                const uint32_t slp = si[i0 ? min(i0 - 1u, m - 1u) : 0u];
 #pragma unroll
-        for (int j = 0; j < LITEMS; ++j) {
-            if (static_cast<uint32_t>(j) >= per) break;        // (uniform)
-            if ((heads >> j) & 1u) {
-                if (on) emit(kid++, ckey, sx, sy, sz, sw, cn);
-                on = (kheads >> j) & 1u;
-                sx = sy = sz = sw = 0.f; cn = 0; ckey = sk[sl[j]];       // (read again: keeping the eight keys alive costs registers)
+                for (int j = 0; j < R; ++j) sl[j] = si[FULL ? i0 + j : min(i0 + j, m - 1u)];
+                const uint32_t kp = sk[slp];
+#pragma unroll
+                for (int j = 0; j < R; ++j) k[j] = sk[sl[j]];
+                uint32_t klast = 0;
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const bool hd = (FULL || static_cast<uint32_t>(j) < nv) && (j ? k[j] != k[j ? j - 1 : 0] : (i0 == 0 || k[0] != kp));
+                    heads |= (hd ? 1u : 0u) << j;
+                    klast = hd ? k[j] : klast;
+                }
+                kheads = heads;
+                if (min_pts > 1) {                             // (uniform)
+                    const uint32_t d = min_pts - 1u;
+                    const uint32_t hb = heads | (1u << nv), dm = d >= 16u ? 0xFFFFu : (1u << d) - 1u;
+                    kheads = 0;
+#pragma unroll
+                    for (int j = 0; j < R; ++j) kheads |= (((heads >> j) & 1u) && ((hb >> (j + 1)) & dm) == 0u ? 1u : 0u) << j;
+                    const uint32_t jl = heads ? 31u - static_cast<uint32_t>(__builtin_clz(heads)) : 0u;
+                    const bool look = heads && !((kheads >> jl) & 1u) && d < m - (i0 + jl);
+                    const uint32_t kd = sk[si[look ? i0 + jl + d : 0u]];
+                    kheads |= (look && kd == klast ? 1u : 0u) << jl;
+                }
+                // which of the block's positions belong to a kept voxel with its head in the block: those records are loaded
+                uint32_t on_ = 0;
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    on_ = ((heads >> j) & 1u) ? (kheads >> j) & 1u : on_;
+                    ldm |= ((FULL || static_cast<uint32_t>(j) < nv) ? on_ : 0u) << j;
+                }
+                uint32_t pl[R];
+#pragma unroll
+                for (int j = 0; j < R; ++j) pl[j] = SUB ? sp[sl[j]] : sl[j];
+#pragma unroll
+                for (int j = 0; j < R; ++j)
+                    if ((ldm >> j) & 1u) r4[j] = recb[pl[j]];
+            };
+            if (m) { if (all_full) front(std::true_type{}); else front(std::false_type{}); }
+            kid = block_excl_scan<LWAVES>(static_cast<uint32_t>(__builtin_popcount(kheads)), lds, &c_t);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                if ((heads >> j) & 1u) {
+                    if (on) emit(kid++, ckey, sx, sy, sz, sw, cn);
+                    on = (kheads >> j) & 1u;
+                    sx = sy = sz = sw = 0.f; cn = 0;
+                    ckey = R <= 4 ? k[j] : sk[si[i0 + j]];     // (the long form reads it again: eight keys or slots kept alive cost registers)
+                }
+                if ((ldm >> j) & 1u) {
+                    sx = __fadd_rn(sx, r4[j].x); sy = __fadd_rn(sy, r4[j].y); sz = __fadd_rn(sz, r4[j].z); sw = __fadd_rn(sw, r4[j].w);
+                    ++cn;
+                }
             }
-            if ((ldm >> j) & 1u) {
-                sx = __fadd_rn(sx, r4[j].x); sy = __fadd_rn(sy, r4[j].y); sz = __fadd_rn(sz, r4[j].z); sw = __fadd_rn(sw, r4[j].w);
-                ++cn;
-            }
-        }
+        };
+        if (LITEMS > 4 && per <= 4u) voxels(std::integral_constant<int, 4>{});
+        else voxels(std::integral_constant<int, LITEMS>{});
         PH(g_phase_k3, 3);
         if (on) {
             // the last voxel may go on past the block: four positions at a time, loads first — up to CM3_EXT_SEQ positions
