@@ -10,6 +10,7 @@
 
 #include "cm_align_solve.hpp"
 #include "cm_ctx.hpp"
+#include "cm_search.hpp"
 
 namespace {
 
@@ -124,14 +125,6 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
 
 namespace {
 
-// Host inverse of the kernels' order-preserving float image (k_cl_bounds).
-float ord_to_float(uint32_t o) {
-    const uint32_t b = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
-    float f;
-    std::memcpy(&f, &b, 4);
-    return f;
-}
-
 // The stages a by-product marked (prof_mark) into c->stage_times, as wait_frame does for a frame's.
 void collect_stage_times(cm_ctx* c) {
     if (!(c->flags & CM_FLAG_PROFILE)) return;
@@ -178,7 +171,7 @@ int result_bounds(cm_ctx* c, uint32_t* words, float mn[3], float mx[3]) {
     uint32_t img[6];
     HIP_TRY(c, hipMemcpyAsync(img, words, sizeof img, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    for (int a = 0; a < 3; ++a) { mn[a] = ord_to_float(img[a]); mx[a] = ord_to_float(img[3 + a]); }
+    for (int a = 0; a < 3; ++a) { mn[a] = ord2f(img[a]); mx[a] = ord2f(img[3 + a]); }
     return CM_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
 
@@ -896,7 +897,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_table_finish(const float4* __restr
 // my_cloud_fusion/src/CloudFusionNode.h:74-85, applied before voxelgrid at cloud_fusion_node.cpp:72;
 // live node outlierRemoval pc_preprocessing_main.cpp:184-192). pcl::RadiusOutlierRemoval keeps a
 // point iff k > min_neighbors, k = points (itself included) with fp32 squared distance
-// ((dx*dx + dy*dy) + dz*dz) < float(r*r).
+// ((dx*dx + dy*dy) + dz*dz) < float(r*r) (d2_of, cm_search.hpp: the by-products' distance too).
 // Candidates come from a grid a little wider than the radius: the fused cloud is sorted by that
 // grid's linear cell index with the same radix sort, the points are gathered once into sorted
 // order (so the cells of a row are contiguous), a (y,z)-row table gives each row's range, and one
@@ -1001,8 +1002,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_neighbors_row(const CmFrameDev* __
         const uint32_t lo_key = jk * dx + (i ? i - 1 : 0u), hi_key = jk * dx + ((i + 1 < dx) ? i + 1 : dx - 1);
         const uint32_t my_cls = cls ? cls[__float_as_uint(me.w)] : 0u;
         auto test = [&](const float4& pt) {
-            const float ex = __fsub_rn(me.x, pt.x), ey = __fsub_rn(me.y, pt.y), ez = __fsub_rn(me.z, pt.z);
-            const bool near = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)) < r2;
+            const bool near = d2_of(me, pt) < r2;
             return near && (!cls || cls[__float_as_uint(pt.w)] == my_cls);
         };
         uint32_t cnt = 1;                                      // the point itself (distance 0)
@@ -1071,8 +1071,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_neighbors(const CmFrameDev* __rest
         // band on its own, like the reference's per-slab outlierRemoval call)
         const uint32_t my_cls = cls ? cls[__float_as_uint(me.w)] : 0u;
         auto test = [&](const float4& pt) {
-            const float ex = __fsub_rn(me.x, pt.x), ey = __fsub_rn(me.y, pt.y), ez = __fsub_rn(me.z, pt.z);
-            const bool near = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)) < r2;
+            const bool near = d2_of(me, pt) < r2;
             return near && (!cls || cls[__float_as_uint(pt.w)] == my_cls);
         };
         // Own row first, outward from the point's own sorted position: the points of its own cell
@@ -1245,9 +1244,6 @@ __global__ __launch_bounds__(256) void k_to_pcl32(const float4* __restrict__ in,
 // ------------------------------------------------------------------------------------------------
 // launch wrappers (called from cm_launch.cpp)
 // ------------------------------------------------------------------------------------------------
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
-
 void cmk_setup(hipStream_t s, const CmFrameDev& f, CmFrameDev* d_frame, CmTileDev* d_tiles) {
     CM_LAUNCH(k_setup, d_tiles ? (f.n_tiles + 255) / 256 + (f.n_tiles == 0) : 1, d_tiles ? 256 : 64, s, f, d_frame, d_tiles);
 }

@@ -8,8 +8,8 @@
 //
 //   k_aln_eval   one lane per source point, one workgroup per aligned block of 256 source indices.
 //                Transform: q64 = ((r00 x + r01 y) + r02 z) + t0 ... in fp64, qf = float(q64). Match: the 9 rows x 3 cells
-//                around qf's cell, each row entered by the binary search k_cl_hook uses, the smallest (d2, result index)
-//                pair with d2 < r2 kept; its 8-byte correspondence is written at the source index. Terms: the matched
+//                around qf's cell (grid_cell, for_row_cells, d2_of: cm_search.hpp, the cell, the search and
+//                the distance of k_cl_hook), the smallest (d2, result index) pair with d2 < r2 kept; its 8-byte correspondence is written at the source index. Terms: the matched
 //                centroid and its normal gathered by result index, the 28 fp64 products about the pivot. Reduction: inside
 //                a wave v[l] += v[l + s] for s = 32 .. 1 by shuffles, the four wave sums through LDS as ((w0 + w1) + w2) + w3,
 //                and one vector store of the block's 28 sums and its count (29 lanes, 8 bytes each).
@@ -17,7 +17,7 @@
 //
 // No floating-point atomics anywhere: the sums depend on the inputs alone, not on the launch or on timing.
 //
-// Why the 27 cells are enough, also for a point outside the grid. The cell of a coordinate is
+// Why the 27 cells are enough, also for a point outside the grid. The cell of a coordinate (grid_cell) is
 // clamp(floor(fl(fl(x - min) * inv)), 0, dims - 1): every step is monotone in x, so the whole is. A centroid c with
 // d2(qf, c) < r2 is within r (1 + 2^-22) of qf along every axis, and two coordinates that close are never two cells apart
 // (cell >= 1.0039 r; tests/test_cluster.py checks that premise in this arithmetic) — before the clamp, and the clamp, being
@@ -31,18 +31,9 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
-
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-
-// k_cl_keys' cell of a coordinate (cm_kernels_cluster.hip cl_cell), the clamp included.
-__device__ __forceinline__ uint32_t aln_cell(float x, float mn, float inv, uint32_t dim) {
-    const float v = floorf(__fmul_rn(__fsub_rn(x, mn), inv));
-    return static_cast<uint32_t>(fminf(fmaxf(v, 0.0f), static_cast<float>(dim - 1u)));
-}
 
 __global__ __launch_bounds__(CM_BLOCK) void k_aln_eval(const CmFrameState* __restrict__ st, const uint32_t* __restrict__ keys_a,
                                                        const uint32_t* __restrict__ keys_b, const float4* __restrict__ pts,
@@ -73,33 +64,27 @@ __global__ __launch_bounds__(CM_BLOCK) void k_aln_eval(const CmFrameState* __res
     if (has && n_tgt != 0u && isfinite(f0) && isfinite(f1) && isfinite(f2) && st->status == CM_DEV_OK) {
         const uint32_t* __restrict__ keys = pick(st, keys_a, keys_b);
         const uint32_t dx = g.dims[0], dy = g.dims[1], dz = g.dims[2];
-        const uint32_t cx = aln_cell(f0, g.min[0], g.inv, dx), cy = aln_cell(f1, g.min[1], g.inv, dy),
-                       cz = aln_cell(f2, g.min[2], g.inv, dz);
+        const uint32_t cx = grid_cell(f0, g.min[0], g.inv, dx), cy = grid_cell(f1, g.min[1], g.inv, dy),
+                       cz = grid_cell(f2, g.min[2], g.inv, dz);
         const uint32_t x_lo = cx ? cx - 1u : 0u, x_hi = (cx + 1u < dx) ? cx + 1u : dx - 1u;
+        const float4 qf = make_float4(f0, f1, f2, 0.0f);
+        // (the 3 x 3 rows in for_rows_3x3's order, in this kernel's own rolled loop: through the template the kernel measured
+        // 1 % slower per iteration at a 50 cm leaf, profiles/device_helpers_cost.txt)
 #pragma unroll 1
         for (int q = 0; q < 9; ++q) {
             const int oz = q / 3 - 1, oy = q % 3 - 1;
             if ((oz < 0 && cz == 0u) || (oz > 0 && cz + 1u >= dz) || (oy < 0 && cy == 0u) || (oy > 0 && cy + 1u >= dy)) continue;
             const uint32_t r = (cy + static_cast<uint32_t>(oy)) + dy * (cz + static_cast<uint32_t>(oz));
             const uint2 rg = rows[r];
-            const uint32_t k_lo = r * dx + x_lo, k_hi = r * dx + x_hi;
-            uint32_t lo = rg.x, hi = rg.y;
-            if (lo >= hi) continue;
-            while (lo < hi) {                                   // first candidate of the three cells
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                if (keys[mid] < k_lo) lo = mid + 1u; else hi = mid;
-            }
-            for (uint32_t t = lo; t < rg.y; ++t) {
-                if (keys[t] > k_hi) break;
+            for_row_cells(keys, rg.x, rg.y, r, dx, x_lo, x_hi, [&](uint32_t t) {
                 const float4 p = pts[t];
-                const float ex = __fsub_rn(f0, p.x), ey = __fsub_rn(f1, p.y), ez = __fsub_rn(f2, p.z);
-                const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+                const float d2 = d2_of(qf, p);
                 const uint32_t j = __float_as_uint(p.w);
                 if (d2 < r2 && (best_j == CM_ALIGN_NONE_DEV || d2 < best_d || (d2 == best_d && j < best_j))) {
                     best_d = d2;
                     best_j = j;
                 }
-            }
+            });
         }
     }
     if (has) corr[i] = make_uint2(best_j, __float_as_uint(best_d));
@@ -178,9 +163,6 @@ __global__ __launch_bounds__(64) void k_aln_sum(const double* __restrict__ parti
 }
 
 }  // namespace
-
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
 // cm_byproducts.cpp align. corr: n_src entries of 8 bytes; partials: ceil(n_src / 256) * CM_ALIGN_STRIDE doubles; sums:
 // CM_ALIGN_SUMS doubles. n_src 0: no launch of k_aln_eval, and the sums are those of no block (zeros).

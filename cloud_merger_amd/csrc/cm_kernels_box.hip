@@ -13,7 +13,7 @@
 //                   choice. A larger one is listed instead: a slot (atomic counter), a run of chunk rows (second counter),
 //                   one work item per chunk, and the empty images of its extremes.
 //   k_box_extremes  one workgroup per listed chunk: the chunk's extremes per angle into the cluster's images (atomicMin /
-//                   atomicMax on order-preserving integer images: order-free).
+//                   atomicMax on order-preserving integer images, f2ord / ord2f of cm_search.hpp: order-free).
 //   k_box_sums      one workgroup per listed chunk (CLOSENESS only): the chunk's sum per angle into the chunk's row.
 //   k_box_choose    one workgroup per listed cluster: the rows added in ascending chunk order, then the choice.
 //
@@ -27,17 +27,9 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
-
-// Order-preserving image of a float and back (as in cm_kernels_cluster.hip).
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
 
 // The cluster table after k_cl_decode: cm_cluster.
 struct BoxCluster {
@@ -294,9 +286,6 @@ __global__ __launch_bounds__(CM_BLOCK) void k_box_choose(const BoxCluster* __res
 }
 
 }  // namespace
-
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
 // One thread per heading, whole waves: CM_BOX_MAX_ANGLES_DEV <= CM_BLOCK.
 static uint32_t box_block(uint32_t n_angles) { return (n_angles + 63u) / 64u * 64u; }

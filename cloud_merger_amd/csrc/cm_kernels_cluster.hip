@@ -24,6 +24,9 @@
 // with that older parent and the smaller root, so no link is ever dropped; parents only decrease, so every walk ends. Loads
 // of parent words inside the launch bypass the CU's L1 (relaxed agent-scope atomic loads); a value that is stale all the
 // same is an older ancestor of the same tree and only costs steps, because the atomicMin that follows sees the truth.
+//
+// From cm_search.hpp: the integer images (f2ord / ord2f), the guarded atomics (ld_agent, min_into, max_into), the cell of a
+// coordinate (grid_cell), the walk of a row's cells (for_row_cells) and the predicate's d2 (d2_of).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -31,25 +34,9 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
-
-// Order-preserving image of a float (-inf < ... < -0 < +0 < ... < +inf) and back.
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// atomicMin / atomicMax that skip the atomic when the word already holds a value at least as good (the word only moves
-// one way, so a stale read can only cost an atomic, never lose one).
-__device__ __forceinline__ void min_into(uint32_t* p, uint32_t v) { if (v < ld_agent(p)) atomicMin(p, v); }
-__device__ __forceinline__ void max_into(uint32_t* p, uint32_t v) { if (v > ld_agent(p)) atomicMax(p, v); }
 
 // bounds: [0..2] min images (set to 0xFFFFFFFF), [3..5] max images (set to 0)
 __global__ __launch_bounds__(CM_BLOCK) void k_cl_bounds(const float4* __restrict__ recs, uint32_t n, uint32_t* __restrict__ bounds) {
@@ -68,12 +55,6 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_bounds(const float4* __restrict
     __syncthreads();
     if (threadIdx.x < 3) atomicMin(&bounds[threadIdx.x], sb[threadIdx.x]);
     else if (threadIdx.x < 6) atomicMax(&bounds[threadIdx.x], sb[threadIdx.x]);
-}
-
-__device__ __forceinline__ uint32_t cl_cell(float x, float mn, float inv, uint32_t dim) {
-    // (fmaxf drops a NaN — an infinite offset times the zero inverse of the one-cell grid — onto cell 0)
-    const float v = floorf(__fmul_rn(__fsub_rn(x, mn), inv));
-    return static_cast<uint32_t>(fminf(fmaxf(v, 0.0f), static_cast<float>(dim - 1u)));
 }
 
 __global__ __launch_bounds__(CM_BLOCK) void k_cl_keys(const float4* __restrict__ recs, uint32_t n, CmClusterGridDev g,
@@ -98,9 +79,9 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_keys(const float4* __restrict__
         uint32_t key = CM_INVALID_KEY;
         if (i < n) {
             const float4 p = recs[i];
-            const uint32_t c0 = cl_cell(p.x, g.min[0], g.inv, g.dims[0]);
-            const uint32_t c1 = cl_cell(p.y, g.min[1], g.inv, g.dims[1]);
-            const uint32_t c2 = cl_cell(p.z, g.min[2], g.inv, g.dims[2]);
+            const uint32_t c0 = grid_cell(p.x, g.min[0], g.inv, g.dims[0]);
+            const uint32_t c1 = grid_cell(p.y, g.min[1], g.inv, g.dims[1]);
+            const uint32_t c2 = grid_cell(p.z, g.min[2], g.inv, g.dims[2]);
             key = c0 + g.dims[0] * (c1 + g.dims[1] * c2);
             atomicAdd(&lh[key & (CM_RADIX - 1)], 1u);
         }
@@ -172,21 +153,10 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_hook(const CmFrameState* __rest
         if ((oz < 0 && cz == 0u) || (oy < 0 && cy == 0u) || (oy > 0 && cy + 1u >= dy)) continue;
         const uint32_t r = (cy + static_cast<uint32_t>(oy)) + dy * (cz + static_cast<uint32_t>(oz));
         const uint2 rg = rows[r];
-        const uint32_t end = q == 4 ? s : rg.y;
-        const uint32_t k_lo = r * dx + x_lo, k_hi = r * dx + x_hi;
-        uint32_t lo = rg.x, hi = end;
-        if (lo >= hi) continue;
-        while (lo < hi) {                                   // first candidate of the three cells
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (keys[mid] < k_lo) lo = mid + 1u; else hi = mid;
-        }
-        for (uint32_t t = lo; t < end; ++t) {
-            if (keys[t] > k_hi) break;
+        for_row_cells(keys, rg.x, q == 4 ? s : rg.y, r, dx, x_lo, x_hi, [&](uint32_t t) {
             const float4 p = pts[t];
-            const float ex = __fsub_rn(me.x, p.x), ey = __fsub_rn(me.y, p.y), ez = __fsub_rn(me.z, p.z);
-            if (__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez)) < tol2)
-                cl_unite(parent, my, __float_as_uint(p.w));
-        }
+            if (d2_of(me, p) < tol2) cl_unite(parent, my, __float_as_uint(p.w));
+        });
     }
 }
 
@@ -371,9 +341,6 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cl_decode(CmClusterDev* __restrict
 }
 
 }  // namespace
-
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
 void cmk_cl_bounds(hipStream_t s, const void* recs, uint32_t n, uint32_t* bounds) {
     const uint32_t blocks = (n + CM_TILE - 1) / CM_TILE;

@@ -13,7 +13,8 @@
 //   k_cov_reduce  one lane per voxel: finds the voxel's run by binary search, checks its length against out_cnt, adds the
 //                 fp64 moments point after point in sorted (= merged) order, then the covariance, its eigen-decomposition
 //                 (jacobi3), the inflation and the inverse                          [16 B/rec gather, 80 B/voxel write]
-// Arithmetic: fp64, every operation rounded on its own (-ffp-contract=off and the _rn intrinsics), in the order of the header.
+// Arithmetic: fp64, every operation rounded on its own (-ffp-contract=off and the _rn intrinsics: dadd, dsub, dmul, ddiv of
+// cm_search.hpp), in the order of the header. The binary search is cm_search.hpp's lower_bound_u32.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -21,18 +22,9 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
-
-// First index in keys[0, n) whose value is >= v.
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ keys, uint32_t n, uint32_t v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(CM_BLOCK) void k_cov_keys(const float4* __restrict__ recs, const uint32_t* __restrict__ total,
                                                        CmCovGridDev g, const uint32_t* __restrict__ out_key, uint32_t n_out,
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cov_keys(const float4* __restrict_
             const bool inside = static_cast<uint32_t>(c0) < g.div_b[0] && static_cast<uint32_t>(c1) < g.div_b[1] &&
                                 static_cast<uint32_t>(c2) < g.div_b[2];
             const uint32_t key = static_cast<uint32_t>(c0) + static_cast<uint32_t>(c1) * mul1 + static_cast<uint32_t>(c2) * mul2;
-            const uint32_t k = lower_bound_u32(out_key, n_out, key);
+            const uint32_t k = lower_bound_u32(out_key, 0u, n_out, key);
             if (inside && k < n_out && out_key[k] == key) {
                 v = k;
                 atomicAdd(&lh[v & (CM_RADIX - 1)], 1u);
@@ -79,11 +71,6 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cov_keys(const float4* __restrict_
     if (c) atomicAdd(&grp[static_cast<size_t>(tile / CM_GROUP) * CM_RADIX + threadIdx.x], c);
 }
 
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
-
 __global__ __launch_bounds__(CM_BLOCK) void k_cov_reduce(const float4* __restrict__ recs, const CmFrameState* __restrict__ st_sort,
                                                          const uint32_t* __restrict__ keys_a, const uint32_t* __restrict__ vals_a,
                                                          const uint32_t* __restrict__ keys_b, const uint32_t* __restrict__ vals_b,
@@ -96,7 +83,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_cov_reduce(const float4* __restric
     const uint32_t* __restrict__ vals = odd ? vals_b : vals_a;
     const uint32_t n_sorted = st_sort->n_valid;
     const uint32_t cnt = out_cnt[v];
-    const uint32_t lo = lower_bound_u32(keys, n_sorted, v);
+    const uint32_t lo = lower_bound_u32(keys, 0u, n_sorted, v);
     const uint32_t hi = lo + cnt;
     // the run of voxel v must hold exactly the points the frame counted for it
     if (cnt == 0 || hi > n_sorted || hi < lo || keys[hi - 1] != v || (hi < n_sorted && keys[hi] == v)) {

@@ -10,7 +10,8 @@
 //                  into a table cleared to zero bytes, in any order. A flat stretch of road puts tens of points of one tile
 //                  into one cell, so the tile's distinct cells are first gathered in an LDS hash table (CM_GRID_HASH slots,
 //                  LDS atomics) and flushed once per cell and tile; a point that finds no slot within CM_GRID_PROBES goes to
-//                  the table in HBM itself. Either way a maximum that a plain read shows cannot move the word is skipped.
+//                  the table in HBM itself. Either way a maximum that a plain read shows cannot move the word is skipped
+//                  (max_into; it, ld_agent and the images f2ord / ord2f are cm_search.hpp's).
 //   k_grid_finish  one thread per cell: the images back to floats (nothing -> the canonical NaN), the state in place, the
 //                  occupancy byte.
 //
@@ -22,23 +23,12 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
 
-// Order-preserving image of a float (-inf < ... < -0 < +0 < ... < +inf) and back (k_cl_bounds' image).
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-
-__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// A word of the table in HBM only grows: a stale read can cost an atomic, never lose one. v == 0 (nothing) never goes.
-__device__ __forceinline__ void max_into(uint32_t* p, uint32_t v) { if (v > ld_agent(p)) atomicMax(p, v); }
+// A word of the table in HBM only grows, so max_into (cm_search.hpp) may skip the atomic on a stale read. v == 0 (nothing)
+// never goes.
 __device__ __forceinline__ void add_into(uint32_t* p, uint32_t v) { if (v) atomicAdd(p, v); }
 // A word of the tile's LDS table as other lanes' atomics left it (or a moment earlier: the same argument).
 __device__ __forceinline__ uint32_t ld_lds(const uint32_t* p) {

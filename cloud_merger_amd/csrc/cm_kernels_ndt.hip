@@ -7,7 +7,8 @@
 //   k_ndt_eval   one lane per source point, one workgroup per aligned block of 256 source indices.
 //                Transform: k_aln_eval's, q64 in fp64 and qf = float(q64). Voxels: qf's cell in the grid of out_key with
 //                k_cov_keys' fp32 arithmetic, then the cell and (neighbourhood 7) its six face neighbours, each tested per
-//                axis as integers against the grid and looked up in out_key by binary search — no search grid of its own.
+//                axis as integers against the grid and looked up in out_key by binary search (lower_bound_u32,
+//                cm_search.hpp: k_cov_keys' search) — no search grid of its own.
 //                Terms: per used voxel the Mahalanobis form m, the weight w = cm_exp_neg(d2h * m) (cm_ndt_math.hpp) and the
 //                28 products, added over the point's voxels in candidate order into 28 registers; the voxel loop stays
 //                rolled. The 16-byte correspondence goes out in one store. Reduction: k_aln_eval's — shuffles inside a
@@ -23,6 +24,7 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 // the rounded fp64 operations: cm_ndt_math.hpp's macros, the one spelling of this file too
 #define CM_NDT_FN __device__ __forceinline__
@@ -40,16 +42,6 @@ __device__ __forceinline__ double dot3(double x0, double x1, double x2, double y
 // x0 y0 + x1 y1: the three-term form with an exact zero left out
 __device__ __forceinline__ double dot2(double x0, double x1, double y0, double y1) {
     return CM_NDT_ADD(CM_NDT_MUL(x0, y0), CM_NDT_MUL(x1, y1));
-}
-
-// First index in keys[0, n) whose value is >= v (k_cov_keys' search).
-__device__ __forceinline__ uint32_t ndt_lower_bound(const uint32_t* __restrict__ keys, uint32_t n, uint32_t v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 __global__ __launch_bounds__(CM_BLOCK) void k_ndt_eval(const uint32_t* __restrict__ out_key, uint32_t n_out,
@@ -100,7 +92,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_ndt_eval(const uint32_t* __restric
                 continue;
             const uint32_t key = static_cast<uint32_t>(e0) + static_cast<uint32_t>(e1) * g.div_b[0] +
                                  static_cast<uint32_t>(e2) * (g.div_b[0] * g.div_b[1]);
-            const uint32_t k = ndt_lower_bound(out_key, n_out, key);
+            const uint32_t k = lower_bound_u32(out_key, 0u, n_out, key);
             if (k >= n_out || out_key[k] != key) continue;
             const CmVoxelCovDev* __restrict__ e = cov + k;
             if (!(e->flags & CM_COV_VALID_DEV)) continue;

@@ -24,7 +24,13 @@
 // The geometry of the grid (cm_device.h CmClusterGridDev): cell = floor(fl(fl(p - min) * inv)), at most 4096 cells per axis
 // (normals_grid, cm_route.cpp). The two roundings move a centroid by less than 4096 * 2^-23 = 2^-11 of a cell, so two centroids
 // whose cell indices differ by D >= 2 along an axis are more than (D - 1 - 2^-10) cells apart along it; cell_gap takes
-// (D - 1 - 2^-8), and kRel below covers the rounding of 1 / inv, of the products and of the fp32 d2 itself.
+// (D - 1 - 2^-8), and kRel (cm_search.hpp) covers the rounding of 1 / inv, of the products and of the fp32 d2 itself.
+//
+// d2_of, kRel and the fp64 operations (dadd ...) are cm_search.hpp's. The walk is NOT: scan_row, the 3 x 3 rows and the ring
+// loop below are this kernel's own copy of for_row_cells / for_rows_3x3 / for_row_ring, line for line in the visiting order.
+// Through the shared templates the kernel compiled to two to four instructions more (the same registers, LDS and occupancy) and
+// measured 2 - 4 % slower at a 50 cm leaf, k = 30, in two sessions (profiles/device_helpers_cost.txt), so its text stays
+// byte for byte what it was. A change to the walk in cm_search.hpp is a change here too.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -32,15 +38,9 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 
 namespace {
-
-constexpr float kRel = 1.0f - 1.0f / (1 << 20);        // margin of every pruning bound against fp32 rounding
-
-__device__ __forceinline__ float d2_of(const float4& a, const float4& b) {
-    const float ex = __fsub_rn(a.x, b.x), ey = __fsub_rn(a.y, b.y), ez = __fsub_rn(a.z, b.z);
-    return __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-}
 
 // A lower bound (m) on the distance along one axis between two centroids whose cell indices differ by D or more.
 __device__ __forceinline__ float cell_gap(int D, float cell) {
@@ -50,11 +50,6 @@ __device__ __forceinline__ float cell_gap(int D, float cell) {
 __device__ __forceinline__ bool pair_less(float d2a, uint32_t ja, float d2b, uint32_t jb) {
     return d2a < d2b || (d2a == d2b && ja < jb);
 }
-
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
 
 // The entry of centroid `me` (result index me.w) from its kk nearest others, lj[q * LANES] in ascending (d2, index) order.
 template <int LANES>
@@ -244,9 +239,6 @@ __global__ __launch_bounds__(LANES) void k_nrm_knn(const CmFrameState* __restric
 }
 
 }  // namespace
-
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
 // cm_byproducts.cpp normals: *list_n zeroed before the first launch; list = n uint2; out = n entries of 32 bytes. n_items: the
 // centroids (first) or the length of the list the first launch left.

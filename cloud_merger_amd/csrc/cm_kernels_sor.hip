@@ -14,6 +14,8 @@
 //   k_sor_threshold         one lane: the exact sums (cm_sor_sum.hpp), mean, stddev, threshold -> the stats record
 //   k_sor_mask              keep-mask: double(d_i) > threshold removes the point
 // Every kernel leaves at once when the sort's state is not CM_DEV_OK.
+// The walks (for_row_cells, for_rows_3x3, for_row_ring), d2_of and kRel are cm_search.hpp's, shared with k_nrm_knn; the
+// pruning bounds (axis_gap), x_range, the list and the "finished after the first launch" test are this kernel's own.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -21,20 +23,14 @@
 #include "cm_common.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 #include "cm_sor_sum.hpp"
 
 namespace {
 
-constexpr float kRel = 1.0f - 1.0f / (1 << 20);        // margin of every pruning bound against fp32 rounding
-
 // sqrtf correctly rounded: the fp64 root of an fp32 value rounded to fp32 (53 >= 2 * 24 + 2 bits: no double-rounding error).
 // (HIP's __fsqrt_rn is the 1-ulp hardware root unless OCML's rounded operations are enabled.)
 __device__ __forceinline__ float sqrt_rn(float x) { return static_cast<float>(__dsqrt_rn(static_cast<double>(x))); }
-
-__device__ __forceinline__ float d2_of(const float4& a, const float4& b) {
-    const float ex = __fsub_rn(a.x, b.x), ey = __fsub_rn(a.y, b.y), ez = __fsub_rn(a.z, b.z);
-    return __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-}
 
 // A lower bound (m) on the distance from the point to any point s or more cells away along one axis: the cell
 // assignment floor(x * inv) may round either way by |x| 2^-23.
@@ -89,17 +85,9 @@ __global__ __launch_bounds__(CM_BLOCK) void k_sor_knn(const CmFrameDev* __restri
         // one row: the points of cells il..ih (clipped to the grid), the point itself left out
         auto scan_row = [&](uint32_t row, uint32_t il, uint32_t ih) {
             const uint2 r = rows[row];
-            if (r.x >= r.y) return;
-            const uint32_t lo_key = row * dx + il, hi_key = row * dx + ih;
-            uint32_t a = r.x, b = r.y;
-            while (a < b) {
-                const uint32_t mid = (a + b) >> 1;
-                if (keys[mid] < lo_key) a = mid + 1; else b = mid;
-            }
-            for (uint32_t q = a; q < r.y; ++q) {
-                if (keys[q] > hi_key) break;
+            for_row_cells(keys, r.x, r.y, row, dx, il, ih, [&](uint32_t q) {
                 if (q != p) offer(d2_of(me, pts[q]));
-            }
+            });
         };
         // the cells of a row within the current bound in x (the whole row while there is none)
         auto x_range = [&](uint32_t& il, uint32_t& ih) {
@@ -115,11 +103,7 @@ __global__ __launch_bounds__(CM_BLOCK) void k_sor_knn(const CmFrameDev* __restri
         bool done = false;
         if (first) {
             const uint32_t il = i ? i - 1 : 0u, ih = i + 1 < dx ? i + 1 : dx - 1;
-            for (int o = 0; o < 9; ++o) {
-                const int jj = static_cast<int>(j) + (o % 3) - 1, kz = static_cast<int>(kk) + (o / 3) - 1;
-                if (jj < 0 || jj >= static_cast<int>(dy) || kz < 0 || kz >= static_cast<int>(dz)) continue;
-                scan_row(static_cast<uint32_t>(jj) + static_cast<uint32_t>(kz) * dy, il, ih);
-            }
+            for_rows_3x3(j, kk, dy, dz, [&](uint32_t row) { scan_row(row, il, ih); });
             if (cnt == k) {
                 // the nearest face of the 3x3x3 block, per axis (an axis the block covers whole has none)
                 float g = inf;
@@ -142,27 +126,18 @@ __global__ __launch_bounds__(CM_BLOCK) void k_sor_knn(const CmFrameDev* __restri
                     const float g = fminf(axis_gap(sf, cy, me.y), axis_gap(sf, cz, me.z));
                     if (my[(k - 1) * CM_BLOCK] <= __fmul_rn(__fmul_rn(g, g), kRel)) break;
                 }
-                const int si = static_cast<int>(s);
-                for (int dk = -si; dk <= si; ++dk) {
-                    const int kz = static_cast<int>(kk) + dk;
-                    if (kz < 0 || kz >= static_cast<int>(dz)) continue;
-                    const bool edge_k = dk == -si || dk == si;
-                    const int step = (edge_k || si == 0) ? 1 : 2 * si;
-                    for (int dj = -si; dj <= si; dj += step) {
-                        const int jj = static_cast<int>(j) + dj;
-                        if (jj < 0 || jj >= static_cast<int>(dy)) continue;
-                        // skip a row wholly beyond the bound: every point of it is (|dj|-1, |dk|-1) cells away at least
-                        const float e = eff();
-                        if (e != inf) {
-                            const float gy = axis_gap(static_cast<float>(max(abs(dj) - 1, 0)), cy, me.y);
-                            const float gz = axis_gap(static_cast<float>(max(abs(dk) - 1, 0)), cz, me.z);
-                            if (e < __fmul_rn(__fadd_rn(__fmul_rn(gy, gy), __fmul_rn(gz, gz)), kRel)) continue;
-                        }
-                        uint32_t il, ih;
-                        x_range(il, ih);
-                        scan_row(static_cast<uint32_t>(jj) + static_cast<uint32_t>(kz) * dy, il, ih);
+                for_row_ring(s, j, kk, dy, dz, [&](uint32_t row, int dj, int dk) {
+                    // skip a row wholly beyond the bound: every point of it is (|dj|-1, |dk|-1) cells away at least
+                    const float e = eff();
+                    if (e != inf) {
+                        const float gy = axis_gap(static_cast<float>(max(abs(dj) - 1, 0)), cy, me.y);
+                        const float gz = axis_gap(static_cast<float>(max(abs(dk) - 1, 0)), cz, me.z);
+                        if (e < __fmul_rn(__fadd_rn(__fmul_rn(gy, gy), __fmul_rn(gz, gz)), kRel)) return;
                     }
-                }
+                    uint32_t il, ih;
+                    x_range(il, ih);
+                    scan_row(row, il, ih);
+                });
             }
         }
         // d_i: the square roots, correctly rounded, added in ascending order in fp64 from 0, divided by k, rounded to fp32
@@ -236,9 +211,6 @@ __global__ __launch_bounds__(CM_BLOCK) void k_sor_mask(const CmFrameState* __res
 }
 
 }  // namespace
-
-#define CM_LAUNCH(kernel, grid, block, stream, ...) \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, __VA_ARGS__)
 
 // cm_launch.cpp sor_filter: words = CM_SOR_WORDS u64 (bins, list count, stats record), zeroed up to CM_SOR_WORD_STATS before
 // the first launch; dist = n_padded floats set to 0xFFFFFFFF before it; list = n_padded uint2.

@@ -2,7 +2,10 @@
 # Prints VGPR / scratch / occupancy / LDS per kernel of every kernel file (hipcc -Rpass-analysis=kernel-resource-usage);
 # cross-compiles, needs no GPU. usage: bash scripts/kernel_resources.sh > profiles/rN_kernel_resources.txt
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-for f in cm_kernels cm_kernels_v2 cm_kernels_v3 cm_kernels_v4 cm_kernels_ground cm_kernels_sor cm_kernels_cluster cm_kernels_normals cm_kernels_align cm_kernels_ndt cm_kernels_cov cm_kernels_motion; do
+# (every cm_kernels*.hip of csrc/, or the files named: bash scripts/kernel_resources.sh cm_kernels_sor cm_kernels_box)
+FILES=${*:-$(cd $ROOT/cloud_merger_amd/csrc && ls cm_kernels*.hip)}
+for f in $FILES; do
+  f=${f%.hip}
   echo "== $f.hip"
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math \
     -I $ROOT/cloud_merger_amd/csrc -c $ROOT/cloud_merger_amd/csrc/$f.hip -o /tmp/k_$f.o \
