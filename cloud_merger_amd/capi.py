@@ -46,6 +46,7 @@ SYMBOLS = [
     "cm_result_clusters", "cm_result_clusters_device",
     "cm_box_directions", "cm_result_cluster_boxes", "cm_result_cluster_boxes_device",
     "cm_result_grid_map", "cm_result_grid_map_device", "cm_grid_occupancy_copy",
+    "cm_result_grid_rays", "cm_result_grid_rays_device", "cm_grid_ray_occupancy_copy",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -206,6 +207,21 @@ class GridCell(C.Structure):
 GRID_DTYPE = np.dtype([("n", "<u4"), ("n_ground", "<u4"), ("z_lo", "<f4"), ("z_hi", "<f4"), ("g_lo", "<f4"), ("g_hi", "<f4"),
                        ("i_max", "<f4"), ("state", "<u4")])
 assert GRID_DTYPE.itemsize == C.sizeof(GridCell) == 32 and C.sizeof(GridParams) == 36
+
+
+# free-space ray casting over the grid map (cm_result_grid_rays)
+class RayParams(C.Structure):
+    """cm_ray_params: min_pass (>= 1), max_range_cells (0: to the end cell)."""
+    _fields_ = [("min_pass", C.c_uint32), ("max_range_cells", C.c_uint32)]
+
+
+class GridRayCell(C.Structure):
+    """cm_grid_ray_cell (8 bytes): cell (ix, iy) is entry ix + iy * nx."""
+    _fields_ = [("n_pass", C.c_uint32), ("n_end", C.c_uint32)]
+
+
+RAY_DTYPE = np.dtype([("n_pass", "<u4"), ("n_end", "<u4")])
+assert RAY_DTYPE.itemsize == C.sizeof(GridRayCell) == 8 and C.sizeof(RayParams) == 8
 
 
 # normals and curvature of the result (cm_result_normals)
@@ -387,6 +403,9 @@ def load():
     L.cm_result_grid_map.argtypes = [vp, C.POINTER(GridParams), vp, u64]
     L.cm_result_grid_map_device.argtypes = [vp, C.POINTER(GridParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_grid_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.cm_result_grid_rays.argtypes = [vp, C.POINTER(GridParams), C.POINTER(RayParams), vp, u64]
+    L.cm_result_grid_rays_device.argtypes = [vp, C.POINTER(GridParams), C.POINTER(RayParams), C.POINTER(vp), C.POINTER(u64)]
+    L.cm_grid_ray_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -771,6 +790,45 @@ class CloudMerger:
             self._check(st, "cm_grid_occupancy_copy")
         out = np.empty(max(n.value, 1), dtype=np.int8)
         self._check(self._lib.cm_grid_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_grid_occupancy_copy")
+        ny, nx = self._grid_shape
+        return out[: n.value].reshape(ny, nx)
+
+    # ---- free-space ray casting over the grid map of the last frame (cm_result_grid_rays) ----
+    def grid_rays(self, origin, cell, nx, ny, z_band=(-np.inf, np.inf), obstacle_height=0.3, min_points=1, min_pass=1,
+                  max_range_cells=0):
+        """(ny, nx) RAY_DTYPE array: per cell the rays that cross it (n_pass) and that end in it (n_end), a ray being an
+        integer line from a sensor's cell to a distinct cell that holds one of that sensor's counted points. The grid map of
+        the same parameters is computed first (grid_occupancy() returns its image); grid_ray_occupancy() returns the image in
+        which an unknown cell crossed by at least min_pass rays is free."""
+        p = self.grid_params(origin, cell, nx, ny, z_band, obstacle_height, min_points)
+        r = RayParams(int(min_pass), int(max_range_cells))
+        n = int(nx) * int(ny)
+        out = np.empty(n if 0 < n <= GRID_MAX_CELLS else 1, dtype=RAY_DTYPE)      # (a grid the library refuses: one entry)
+        self._check(self._lib.cm_result_grid_rays(self._ctx, C.byref(p), C.byref(r), out.ctypes.data, out.shape[0]),
+                    "cm_result_grid_rays")
+        self._grid_shape = (int(ny), int(nx))
+        return out.reshape(int(ny), int(nx))
+
+    def grid_rays_device(self, origin, cell, nx, ny, z_band=(-np.inf, np.inf), obstacle_height=0.3, min_points=1, min_pass=1,
+                         max_range_cells=0):
+        """(device pointer, cells) of the same table, owned by the context and valid until the next merge, grid or ray call."""
+        p = self.grid_params(origin, cell, nx, ny, z_band, obstacle_height, min_points)
+        r = RayParams(int(min_pass), int(max_range_cells))
+        ptr, n = C.c_void_p(), C.c_uint64()
+        self._check(self._lib.cm_result_grid_rays_device(self._ctx, C.byref(p), C.byref(r), C.byref(ptr), C.byref(n)),
+                    "cm_result_grid_rays_device")
+        self._grid_shape = (int(ny), int(nx))
+        return ptr.value, n.value
+
+    def grid_ray_occupancy(self):
+        """(ny, nx) int8 cleared image of the last ray call since the last merge or grid call: -1 unknown, 0 free, 100 occupied."""
+        n = C.c_uint64()
+        st = self._lib.cm_grid_ray_occupancy_copy(self._ctx, None, 0, C.byref(n))
+        if st != CAPACITY:
+            self._check(st, "cm_grid_ray_occupancy_copy")
+        out = np.empty(max(n.value, 1), dtype=np.int8)
+        self._check(self._lib.cm_grid_ray_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)),
+                    "cm_grid_ray_occupancy_copy")
         ny, nx = self._grid_shape
         return out[: n.value].reshape(ny, nx)
 

@@ -53,6 +53,7 @@ void free_all(cm_ctx* c) {
     c->cl.release(); F(c->cl_root); F(c->cl_num); F(c->cl_labels); F(c->cl_tile_sums); F(c->cl_words); F(c->cl_clusters);
     F(c->box_entries); F(c->box_dirs); F(c->box_words); F(c->box_list); F(c->box_ext); F(c->box_work); F(c->box_sums);
     F(c->grid_cells); F(c->grid_image);
+    F(c->ray_bits); F(c->ray_cells); F(c->ray_image);
     c->nrm.release(); F(c->nrm_list); F(c->nrm_words); F(c->nrm_entries);
     c->aln.release(); c->aln_fit.release();
     c->ndt_fit.release(); F(c->ndt_bounds);
@@ -848,6 +849,65 @@ int cm_grid_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells,
     if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipMemcpyAsync(host_dst, c->grid_image, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_grid_ray_cell) == 8 && offsetof(cm_grid_ray_cell, n_end) == 4 && sizeof(cm_ray_params) == 8,
+              "cm_grid_ray_cell is 8 bytes (the kernels' two words), its parameters 8");
+
+// The refusals of cm_result_grid_rays*: grid_check's, and a min_pass of 0. *r: the parameters in force (NULL: {1, 0}).
+static int rays_check(cm_ctx* c, const cm_grid_params* p, const cm_ray_params* in, cm_ray_params* r) {
+    if (const int e = grid_check(c, p)) return e;
+    *r = in ? *in : cm_ray_params{1u, 0u};
+    if (r->min_pass == 0) return fail(c, CM_BAD_ARG, "min_pass must be at least 1");
+    return CM_OK;
+}
+
+int cm_result_grid_rays(cm_ctx* c, const cm_grid_params* p, const cm_ray_params* r, cm_grid_ray_cell* host_dst, uint64_t capacity_cells) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_ray_params rr;
+    int e = rays_check(c, p, r, &rr);
+    if (e != CM_OK) return e;
+    e = grid_rays(c, *p, rr);
+    if (e != CM_OK) return e;
+    const uint64_t n = c->ray_n;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "ray destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ray_cells, n * sizeof(cm_grid_ray_cell), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_grid_ray_cell);
+    return CM_OK;
+}
+
+int cm_result_grid_rays_device(cm_ctx* c, const cm_grid_params* p, const cm_ray_params* r, const void** dev_ptr, uint64_t* n_cells) {
+    if (!c || !dev_ptr || !n_cells) return CM_BAD_ARG;
+    *dev_ptr = nullptr;
+    *n_cells = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    cm_ray_params rr;
+    int e = rays_check(c, p, r, &rr);
+    if (e == CM_OK) e = grid_rays(c, *p, rr);
+    if (e != CM_OK) return e;
+    *dev_ptr = c->ray_cells;
+    *n_cells = c->ray_n;
+    return CM_OK;
+}
+
+int cm_grid_ray_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells) {
+    if (!c || !n_cells) return CM_BAD_ARG;
+    *n_cells = 0;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->ray_have) return fail(c, CM_BAD_ARG, "no rays of the last result (cm_result_grid_rays first)");
+    const uint64_t n = c->ray_n;
+    *n_cells = n;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "cleared occupancy destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ray_image, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bytes_d2h += n;
     return CM_OK;

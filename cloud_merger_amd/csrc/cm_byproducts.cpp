@@ -1,6 +1,6 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
-// (align, ndt), and the one table computed from the frame's points rather than its result, the 2-D grid map (grid_map). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's.
@@ -26,6 +26,21 @@ bool grow_table(void** ptr, uint64_t* cap, uint64_t need, size_t bytes) {
     if (!dev_alloc(ptr, need * bytes)) return false;
     *cap = need;
     return true;
+}
+
+// What the grid kernels take of cm_grid_params: inv = 1.0f / cell, the fp32 division of step 1.
+CmGridDev grid_dev(const cm_grid_params& q) {
+    CmGridDev g;
+    g.origin[0] = q.origin[0];
+    g.origin[1] = q.origin[1];
+    g.inv = 1.0f / q.cell;
+    g.nx = q.nx;
+    g.ny = q.ny;
+    g.z_min = q.z_min;
+    g.z_max = q.z_max;
+    g.obstacle_height = q.obstacle_height;
+    g.min_points = q.min_points;
+    return g;
 }
 
 }  // namespace
@@ -390,8 +405,8 @@ int cluster_boxes(cm_ctx* c, const cm_box_params& q) {
 // place (the descriptor in HBM, the keep-mask behind cm_merged_copy, the ground mask behind cm_ground_copy), one pass over the
 // cells; no host round trip but the wait at the end. A steady-state call allocates nothing. Under CM_FLAG_PROFILE the stage
 // times of the call replace the frame's in cm_get_stage_times.
-int grid_map(cm_ctx* c, const cm_grid_params& q) {
-    c->grid_have = false;
+int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages) {
+    c->grid_have = c->ray_have = false;           // (a ray table goes with the grid it was cast over)
     const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
     HIP_TRY(c, hipSetDevice(c->device));
     if (n_cells > c->grid_cap_cells) {
@@ -401,16 +416,7 @@ int grid_map(cm_ctx* c, const cm_grid_params& q) {
             return fail(c, CM_HIP_ERROR, "cannot allocate the grid map");
         c->grid_cap_cells = n_cells;
     }
-    CmGridDev g;
-    g.origin[0] = q.origin[0];
-    g.origin[1] = q.origin[1];
-    g.inv = 1.0f / q.cell;
-    g.nx = q.nx;
-    g.ny = q.ny;
-    g.z_min = q.z_min;
-    g.z_max = q.z_max;
-    g.obstacle_height = q.obstacle_height;
-    g.min_points = q.min_points;
+    const CmGridDev g = grid_dev(q);
     hipStream_t st = c->stream;
     c->prof_used = 0;
     prof_mark(c, "grid_clear");
@@ -420,12 +426,66 @@ int grid_map(cm_ctx* c, const cm_grid_params& q) {
     cmk_grid_bin(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->grid_cells, c->frame.n_tiles);
     prof_mark(c, "k_grid_finish");
     cmk_grid_finish(st, c->grid_cells, c->grid_image, static_cast<uint32_t>(n_cells), q.obstacle_height, q.min_points);
+    HIP_TRY(c, hipGetLastError());
+    c->grid_n = n_cells;
+    if (more_stages) return CM_OK;                // (grid_rays: it waits, and says then that the grid is there)
+    prof_mark(c, "end");
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->grid_have = true;
+    return CM_OK;
+}
+
+// Free-space ray casting over the grid map of the last frame (cm_kernels_rays.hip; the semantics are in include/cloudmerge.h):
+// the grid map at q as grid_map leaves it, then nx * ny cm_grid_ray_cell records into ray_cells and as many cleared occupancy
+// bytes into ray_image. The origin cells are the grid's step 1 applied on the host to the translations the frame was built
+// with (frame_origin). One clear, a second pass over the frame's raw points in place (the end cells' bitmaps), the walk, one
+// pass over the cells; no host round trip but the wait at the end. A steady-state call allocates nothing.
+int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r) {
+    const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n_cells > c->ray_cap_cells) {
+        dev_free(c->ray_bits); dev_free(c->ray_cells); dev_free(c->ray_image);
+        c->ray_cap_cells = 0;
+        if (!dev_alloc(&c->ray_bits, static_cast<size_t>(c->max_sensors) * ((n_cells + 31) / 32) * 4) ||
+            !dev_alloc(&c->ray_cells, n_cells * sizeof(cm_grid_ray_cell)) || !dev_alloc(&c->ray_image, n_cells))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the ray tables");
+        c->ray_cap_cells = n_cells;
+    }
+    if (const int e = grid_map(c, q, true)) return e;
+    const uint32_t words = static_cast<uint32_t>((n_cells + 31) / 32);
+    const uint32_t n_sensors = c->frame.n_tiles ? c->frame.n_sensors : 0u;
+    const CmGridDev g = grid_dev(q);
+    CmRayDev rd;
+    std::memset(&rd, 0, sizeof rd);
+    rd.nx = q.nx;
+    rd.max_range = r.max_range_cells;
+    for (uint32_t s = 0; s < n_sensors; ++s) {
+        // step 1 of the grid on the host: the same subtraction, product and floorf, each rounded to fp32 on its own
+        const float cx = std::floor(static_cast<float>(static_cast<float>(c->frame_origin[s][0] - g.origin[0]) * g.inv));
+        const float cy = std::floor(static_cast<float>(static_cast<float>(c->frame_origin[s][1] - g.origin[1]) * g.inv));
+        if (!(cx >= 0.0f && cx < static_cast<float>(q.nx) && cy >= 0.0f && cy < static_cast<float>(q.ny))) continue;
+        rd.ox[s] = static_cast<int>(cx);
+        rd.oy[s] = static_cast<int>(cy);
+        rd.has[s] = 1u;
+    }
+    hipStream_t st = c->stream;
+    prof_mark(c, "ray_clear");
+    if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->ray_bits, 0, static_cast<size_t>(n_sensors) * words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->ray_cells, 0, n_cells * sizeof(cm_grid_ray_cell), st));
+    prof_mark(c, "k_ray_mark");
+    cmk_ray_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->ray_bits, words, c->frame.n_tiles);
+    prof_mark(c, "k_ray_cast");
+    cmk_ray_cast(st, c->ray_bits, words, rd, n_sensors, c->ray_cells);
+    prof_mark(c, "k_ray_finish");
+    cmk_ray_finish(st, c->grid_cells, c->ray_cells, c->ray_image, static_cast<uint32_t>(n_cells), r.min_pass);
     prof_mark(c, "end");
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
     collect_stage_times(c);
-    c->grid_n = n_cells;
     c->grid_have = true;
+    c->ray_n = n_cells;
+    c->ray_have = true;
     return CM_OK;
 }
 

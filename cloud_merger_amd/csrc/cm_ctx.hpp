@@ -264,6 +264,19 @@ struct cm_ctx {
     uint64_t grid_n = 0;                 // cells of the last grid call
     bool grid_have = false;              // the two hold the grid of the result at rest (cleared where a merge replaces it)
 
+    // Free-space ray casting over the grid map (cm_kernels_rays.hip), on request after a frame, behind the grid map of the
+    // same call: the per-sensor bitmaps of end cells, the table and the cleared image — no frame reads them — allocated by the
+    // first request and grown together.
+    float frame_origin[CM_MAX_SENSORS][2] = {};   // per descriptor sensor the (x, y) translation of the matrix the last frame
+                                                  // was built with (build_frame; under deskew the descriptor's own is the
+                                                  // identity). Read by grid_rays and by nothing else.
+    uint32_t* ray_bits = nullptr;        // max_sensors bitmaps of ceil(ray_cap_cells / 32) words
+    void* ray_cells = nullptr;           // the table: cm_grid_ray_cell per cell
+    void* ray_image = nullptr;           // the cleared occupancy image: one byte per cell
+    uint64_t ray_cap_cells = 0;          // cells all three are sized for
+    uint64_t ray_n = 0;                  // cells of the last ray call
+    bool ray_have = false;               // they hold the rays of the result at rest (cleared by a merge and by a grid call)
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -343,7 +356,7 @@ void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t 
 
 // cm_byproducts.cpp: the tables computed from the last result on request. Called with merge_mu held.
 // The tables of the last result go with it (where a merge replaces the result).
-inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = c->grid_have = false; }
+inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = c->grid_have = c->ray_have = false; }
 // The covariance table of the last result (cov_entries, n_out entries).
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
 // The cluster tables of the last result (cl_labels, cl_clusters, cl_indices, cl_n_clusters, cl_n_clustered).
@@ -354,7 +367,10 @@ int cluster_boxes(cm_ctx* c, const cm_box_params& q);
 // The direction table of n_angles headings (1..CM_BOX_MAX_ANGLES): 2 * n_angles floats.
 void box_direction_table(uint32_t n_angles, float* cos_sin);
 // The grid map of the last frame at q (grid_cells and grid_image, grid_n = q.nx * q.ny cells).
-int grid_map(cm_ctx* c, const cm_grid_params& q);
+// more_stages: the caller goes on launching and closes the stage list itself.
+int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages = false);
+// The grid map at q and behind it the rays of the last frame at r (ray_cells and ray_image, ray_n = q.nx * q.ny cells).
+int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

@@ -292,3 +292,17 @@ struct CmGridDev {
     float obstacle_height;
     uint32_t min_points;
 };
+
+// Free-space ray casting over the grid map (cm_kernels_rays.hip): per descriptor sensor the origin cell the host computed
+// with the grid's step 1 (has: 0 where the origin is outside the grid or not finite — the sensor casts nothing), the grid's
+// width and the range limit (0: none). A ray cell's record is (n_pass, n_end), two words.
+#define CM_RAY_RUN 32             // bitmap words (1024 end cells) of one sensor a k_ray_cast workgroup takes
+#define CM_RAY_HASH_BITS 12
+#define CM_RAY_HASH (1u << CM_RAY_HASH_BITS)   // slots of its LDS table of crossed cells: 32 KiB of (cell, count), four workgroups per CU
+#define CM_RAY_PROBES 8           // slots a step tries before it goes to the table in HBM itself
+struct CmRayDev {
+    int32_t ox[CM_DEV_MAX_SENSORS], oy[CM_DEV_MAX_SENSORS];
+    uint32_t has[CM_DEV_MAX_SENSORS];
+    uint32_t nx;
+    uint32_t max_range;
+};

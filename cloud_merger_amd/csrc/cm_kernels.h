@@ -233,3 +233,13 @@ void cmk_box_choose(hipStream_t s, const void* clusters, const void* dirs, uint3
 void cmk_grid_bin(hipStream_t s, const CmFrameDev* fd, const CmGridDev& g, const unsigned char* keep, const unsigned char* ground,
                   void* table, uint32_t n_tiles);
 void cmk_grid_finish(hipStream_t s, void* table, void* image, uint32_t n_cells, float obstacle_height, uint32_t min_points);
+
+// ---- free-space ray casting over the grid map (cm_kernels_rays.hip) ---------------------------------------------------------
+// bits: per descriptor sensor a bitmap of `words` = ceil(nx * ny / 32) words, zero bytes before cmk_ray_mark, which sets the
+// bit of every (sensor, cell) that holds a point cmk_grid_bin counts. rays: nx * ny records of (n_pass, n_end), zero bytes
+// before cmk_ray_cast, which walks the set bits' rays from rd's origin cells. cmk_ray_finish writes the cleared bytes from
+// the finished grid table (cmk_grid_finish's) and the ray table.
+void cmk_ray_mark(hipStream_t s, const CmFrameDev* fd, const CmGridDev& g, const unsigned char* keep, const unsigned char* ground,
+                  uint32_t* bits, uint32_t words, uint32_t n_tiles);
+void cmk_ray_cast(hipStream_t s, const uint32_t* bits, uint32_t words, const CmRayDev& rd, uint32_t n_sensors, void* rays);
+void cmk_ray_finish(hipStream_t s, const void* grid, const void* rays, void* image, uint32_t n_cells, uint32_t min_pass);

@@ -44,14 +44,7 @@ __device__ __forceinline__ void flush_cell(uint32_t* __restrict__ table, uint32_
     for (int k = 2; k < 7; ++k) max_into(g + k, w[k]);
 }
 
-// The cell coordinate of step 1 on one axis: false when the point is outside the grid (a t of +-inf or NaN included).
-__device__ __forceinline__ bool grid_axis(float p, float origin, float inv, uint32_t n, uint32_t* i) {
-    const float c = floorf(__fmul_rn(__fsub_rn(p, origin), inv));
-    if (!(c >= 0.0f && c < static_cast<float>(n))) return false;
-    *i = static_cast<uint32_t>(static_cast<int>(c));
-    return true;
-}
-
+// (the cell coordinate of step 1, grid_axis, is cm_search.hpp's: k_ray_mark takes the same one)
 #define CM_GRID_EMPTY 0xFFFFFFFFu
 
 __global__ __launch_bounds__(CM_BLOCK) void k_grid_bin(const CmFrameDev* __restrict__ fd, CmGridDev g,

@@ -518,6 +518,8 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
         std::memcpy(d.m, sl.m, sizeof d.m);
         n_in += sc.n;
         if (consume) {
+            c->frame_origin[k][0] = sl.m[3];         // what the frame is built with, whatever deskew does to d.m below
+            c->frame_origin[k][1] = sl.m[7];
             c->stats_sensor[k] = s; c->stats_n[k] = sc.n;
             c->stats_fresh[k] = sl.fresh ? 1u : 0u;
             c->stats_bytes[k] = sl.fresh ? sl.active_bytes_h2d : 0u;

@@ -1,4 +1,4 @@
-// cm_search.hpp — device helpers shared by the by-product kernel files (cm_kernels_cluster / box / grid / sor / normals /
+// cm_search.hpp — device helpers shared by the by-product kernel files (cm_kernels_cluster / box / grid / rays / sor / normals /
 // align / cov / ndt .hip): the order-preserving image of a float, the guarded one-way atomics, the uncontracted fp64
 // operations, the fp32 squared distance in its one operation order, the lower bound in a sorted key array, the cell of a
 // coordinate in a search grid, and the three walks over a search grid's sorted cells. The frame path's
@@ -68,6 +68,15 @@ __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__
 __device__ __forceinline__ uint32_t grid_cell(float x, float mn, float inv, uint32_t dim) {
     const float v = floorf(__fmul_rn(__fsub_rn(x, mn), inv));
     return static_cast<uint32_t>(fminf(fmaxf(v, 0.0f), static_cast<float>(dim - 1u)));
+}
+
+// The cell coordinate of the 2-D grid map's step 1 on one axis (include/cloudmerge.h): false when the point is outside the
+// grid (a t of +-inf or NaN included). The one membership test of k_grid_bin and k_ray_mark.
+__device__ __forceinline__ bool grid_axis(float p, float origin, float inv, uint32_t n, uint32_t* i) {
+    const float c = floorf(__fmul_rn(__fsub_rn(p, origin), inv));
+    if (!(c >= 0.0f && c < static_cast<float>(n))) return false;
+    *i = static_cast<uint32_t>(static_cast<int>(c));
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -163,6 +163,9 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "grid_z_band") ok = static_cast<bool>(is >> c.grid_z_band[0] >> c.grid_z_band[1]) && c.grid_z_band[0] <= c.grid_z_band[1];
         else if (key == "grid_obstacle_height") ok = static_cast<bool>(is >> c.grid_obstacle_height) && std::isfinite(c.grid_obstacle_height) && c.grid_obstacle_height >= 0.0f;
         else if (key == "grid_min_points") ok = static_cast<bool>(is >> c.grid_min_points) && c.grid_min_points >= 1;
+        else if (key == "grid_raycast") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.grid_raycast = v == 1; }
+        else if (key == "grid_min_pass") ok = static_cast<bool>(is >> c.grid_min_pass) && c.grid_min_pass >= 1;
+        else if (key == "grid_ray_range") ok = static_cast<bool>(is >> c.grid_ray_range);
         else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "align_prev") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.align_prev = v == 1; }
         else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
@@ -189,6 +192,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         if (!ok) { if (err) *err = path + ":" + std::to_string(lineno) + ": bad line"; return false; }
     }
     if (c.sensors.empty() || c.sensors.size() > CM_MAX_SENSORS) { if (err) *err = "sensor count must be 1..16"; return false; }
+    if (c.grid_raycast && !(c.grid_cell > 0.0f)) { if (err) *err = "grid_raycast needs grid_cell > 0"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
     return true;
@@ -211,6 +215,10 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     }
     if (cfg_.align_prev && cfg_.align_method == "ndt" && !(cfg_.flags & CM_FLAG_OCCUPANCY)) {
         error_ = "align_method ndt needs CM_FLAG_OCCUPANCY (the voxel covariance table)";
+        return;
+    }
+    if (cfg_.grid_raycast && (!(cfg_.grid_cell > 0.0f) || cfg_.grid_min_pass == 0)) {
+        error_ = "grid_raycast needs grid_cell > 0 and grid_min_pass >= 1";
         return;
     }
     uint32_t mask = 0;
@@ -328,6 +336,8 @@ int CloudMergerNode::clusters_of_frame(const cm_result& r) {
 int CloudMergerNode::grid_of_frame(const cm_result& r) {
     grid_cells_.clear();
     grid_occupancy_.clear();
+    grid_ray_cells_.clear();
+    grid_cleared_.clear();
     if (!(cfg_.grid_cell > 0.0f) || r.status != CM_OK) return CM_OK;
     const cm_grid_params q{{cfg_.grid_origin[0], cfg_.grid_origin[1]}, cfg_.grid_cell, cfg_.grid_nx, cfg_.grid_ny,
                            cfg_.grid_z_band[0], cfg_.grid_z_band[1], cfg_.grid_obstacle_height, cfg_.grid_min_points};
@@ -341,6 +351,19 @@ int CloudMergerNode::grid_of_frame(const cm_result& r) {
         grid_cells_.clear();
         grid_occupancy_.clear();
         set_error(st != CM_OK ? cm_last_error(ctx_) : "the occupancy image does not match the grid");
+        return st != CM_OK ? st : CM_INTERNAL;
+    }
+    if (!cfg_.grid_raycast) return CM_OK;
+    // (the ray call computes the same grid map again: the two copies above are those of its base map)
+    const cm_ray_params rp{cfg_.grid_min_pass, cfg_.grid_ray_range};
+    grid_ray_cells_.resize(n);
+    grid_cleared_.resize(n);
+    st = cm_result_grid_rays(ctx_, &q, &rp, grid_ray_cells_.data(), n);
+    if (st == CM_OK) st = cm_grid_ray_occupancy_copy(ctx_, grid_cleared_.data(), n, &n_cells);
+    if (st != CM_OK || n_cells != n) {
+        grid_ray_cells_.clear();
+        grid_cleared_.clear();
+        set_error(st != CM_OK ? cm_last_error(ctx_) : "the cleared image does not match the grid");
         return st != CM_OK ? st : CM_INTERNAL;
     }
     return CM_OK;

@@ -97,6 +97,13 @@ struct NodeConfig {
     float grid_z_band[2] = {-std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity()};
     float grid_obstacle_height = 0.3f;
     uint32_t grid_min_points = 1;
+    // Free-space ray casting over that grid map (cm_result_grid_rays: per cell the rays that cross it and that end in it, and the
+    // image in which an unknown cell crossed by grid_min_pass rays is free). Off by default (grid_raycast 0); on, it needs
+    // grid_cell > 0. The node then asks for the ray table and the cleared image as well and keeps them until the next frame
+    // (grid_ray_cells(), grid_cleared()). grid_ray_range: steps of a ray from its sensor that count, 0 = to the return.
+    bool grid_raycast = false;
+    uint32_t grid_min_pass = 1;
+    uint32_t grid_ray_range = 0;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -133,6 +140,8 @@ struct NodeConfig {
 //   clusters from n headings, 1..180; 0: off)
 //   grid_cell <metres> | grid_origin <x> <y> | grid_size <nx> <ny> | grid_z_band <lo> <hi> | grid_obstacle_height <metres> |
 //   grid_min_points <n>   (the 2-D grid map of every frame; grid_cell 0: off)
+//   grid_raycast <0|1> | grid_min_pass <n> | grid_ray_range <cells>   (free-space ray casting over that grid map; it needs
+//   grid_cell > 0; grid_ray_range 0: to the return)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -211,6 +220,10 @@ public:
     // its occupancy image (-1 unknown, 0 free, 100 occupied); both empty where the frame has no voxel grid.
     const std::vector<cm_grid_cell>& grid_cells() const { return grid_cells_; }
     const std::vector<int8_t>& grid_occupancy() const { return grid_occupancy_; }
+    // grid_raycast as well: the ray table of that frame and the cleared image, laid out like the two above; both empty where
+    // the frame has no voxel grid.
+    const std::vector<cm_grid_ray_cell>& grid_ray_cells() const { return grid_ray_cells_; }
+    const std::vector<int8_t>& grid_cleared() const { return grid_cleared_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -264,6 +277,8 @@ private:
     int clusters_of_frame(const cm_result& r);     // after cm_wait: cm_result_clusters (and the boxes) when the config asks for it
     std::vector<cm_grid_cell> grid_cells_;
     std::vector<int8_t> grid_occupancy_;
+    std::vector<cm_grid_ray_cell> grid_ray_cells_;
+    std::vector<int8_t> grid_cleared_;
     int grid_of_frame(const cm_result& r);         // after cm_wait: cm_result_grid_map and the image when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

@@ -581,6 +581,60 @@ CM_API int cm_result_grid_map_device(cm_ctx* ctx, const cm_grid_params* p, const
  * there is no such call: CM_BAD_ARG); a destination that is too small: CM_CAPACITY (nothing is copied). */
 CM_API int cm_grid_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells);
 
+/* ---- free-space ray casting over the grid map: per-cell pass counts, the cleared image (an extension) -------------------
+ * The grid map calls a cell FREE only where returns landed; every cell a beam flew through on its way to a return stays
+ * UNKNOWN. This call clears them, as costmap_2d's obstacle layer and octomap's insertPointCloud do: per sensor it walks an
+ * integer line from the sensor's cell to every distinct cell that holds one of that sensor's counted points, counts per cell
+ * the rays that crossed it and the rays that ended in it, and emits a second occupancy image in which an UNKNOWN cell crossed
+ * by enough rays is FREE. Computed on request after a frame; it never changes a frame. Every quantity is an
+ * integer count over a set of distinct rays, so the tables are a function of the frame and the parameters alone, bit for bit.
+ *   1. Base map. The call first computes the grid map of p exactly as cm_result_grid_map(ctx, p, ...) does: afterwards the
+ *      context's grid table and image are those of p, and cm_grid_occupancy_copy returns them.
+ *   2. Counted points: exactly the points the grid map counts — in A or G, inside the grid on both axes (step 1 of the
+ *      grid), inside the band (its step 2). The cell of such a point of sensor s is an end cell of s. A sensor is an entry
+ *      of the frame's descriptor: the sensors that have a cloud, in ascending order of their number.
+ *   3. Origin cell. For sensor s, (x, y) is the fp32 translation of the matrix the frame transformed that sensor's cloud with
+ *      (cm_set_sensor_transform's t, rounded per component), as it stood when the frame was assembled. Its cell is the grid's
+ *      step 1 applied to that (x, y): the same fp32 subtraction, product and floorf, membership tested in float (-0.0f
+ *      passes as cell 0). A sensor whose origin is outside the grid or not finite casts no rays. Under ego-motion
+ *      compensation the origin is still that translation: the sensor's position at the cloud's own instant, not moved to
+ *      t_ref — an approximation (at 20 m/s and 50 ms, 1 m).
+ *   4. Ray set: the set of distinct pairs (s, end cell e of s) over the sensors that have an origin cell. Two points of one
+ *      sensor in one cell are one ray; one cell reached by two sensors is two rays.
+ *   5. Walk. For origin cell o and end cell e: dx = ex - ox, dy = ey - oy, L = max(|dx|, |dy|), K = L when max_range_cells
+ *      is 0, else min(L, max_range_cells). For k = 0 .. K - 1 the ray crosses the cell
+ *      (ox + rdiv(k * dx, L), oy + rdiv(k * dy, L)), where rdiv(a, L) = sign(a) * ((2 |a| + L) div 2 L) is the integer
+ *      quotient rounded to nearest, a half away from zero. The origin cell is crossed (k = 0), the end cell is not, L = 0
+ *      crosses nothing. Every crossed cell lies inside the grid and no ray crosses a cell twice (DESIGN.md §21 proves both).
+ *      The rule is symmetric under mirroring either axis and under swapping them.
+ *   6. Per cell the record cm_grid_ray_cell: n_pass, the rays of the set that cross the cell; n_end, the rays of the set
+ *      whose end cell it is (whatever max_range_cells).
+ *   7. Cleared image. One int8_t per cell, laid out like the grid's: base OCCUPIED gives 100 (a hit wins over any number of
+ *      passes), base FREE gives 0, base UNKNOWN gives 0 iff n_pass >= min_pass, else -1.
+ * NULL ray parameters mean {1, 0}. Refused with CM_BAD_ARG: everything cm_result_grid_map refuses, and min_pass 0. The
+ * bitmaps of end cells (the frame's sensors x nx * ny bits, at most 8 MiB), the table and the cleared image are owned by the
+ * context and valid until the next merge, the next grid call or the next ray call. No later frame depends on whether they
+ * were asked for; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists this call's stages (the grid's, then ray_clear,
+ * k_ray_mark, k_ray_cast, k_ray_finish). Not modelled: the height of a beam over a cell (2-D casting clears under an
+ * overhang), accumulation over frames, rays of points outside the grid or the band. */
+typedef struct cm_ray_params {         /* 8 bytes */
+    uint32_t min_pass;                 /* rays that must cross an UNKNOWN cell to clear it; >= 1 */
+    uint32_t max_range_cells;          /* steps of a ray from its origin that count; 0 = to the end cell */
+} cm_ray_params;
+typedef struct cm_grid_ray_cell {      /* 8 bytes, cell (ix, iy) is entry ix + iy * nx */
+    uint32_t n_pass;                   /* rays that cross the cell */
+    uint32_t n_end;                    /* rays that end in it */
+} cm_grid_ray_cell;
+/* Host copy; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied; the tables stay in the context). */
+CM_API int cm_result_grid_rays(cm_ctx* ctx, const cm_grid_params* p, const cm_ray_params* r, cm_grid_ray_cell* host_dst,
+                               uint64_t capacity_cells);
+/* The same table left in device memory owned by the context (*n_cells entries of 8 bytes). */
+CM_API int cm_result_grid_rays_device(cm_ctx* ctx, const cm_grid_params* p, const cm_ray_params* r, const void** dev_ptr,
+                                      uint64_t* n_cells);
+/* The cleared image of the last ray call since the last merge or grid call; capacity in cells. *n_cells is always written (0
+ * when there is no such call: CM_BAD_ARG); a destination that is too small: CM_CAPACITY (nothing is copied). */
+CM_API int cm_grid_ray_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
