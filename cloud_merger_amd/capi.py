@@ -418,8 +418,21 @@ def load():
         fn = getattr(L, name)
         if name not in ("cm_status_string", "cm_last_error"):
             fn.restype = C.c_int
+    if hasattr(L, "cm_test_device_allocations"):             # the test build only: not in SYMBOLS, the shipped library has no such symbol
+        L.cm_test_device_allocations.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+        L.cm_test_device_allocations.restype = C.c_int
     _lib = L
     return L
+
+
+def device_allocations():
+    """(live, total): allocations of the library's contexts alive in this process, and made so far. The test build only
+    (CM_LIB_VARIANT=testhooks); the shipped library does not count."""
+    live, total = C.c_uint64(), C.c_uint64()
+    st = load().cm_test_device_allocations(C.byref(live), C.byref(total))
+    if st != OK:
+        raise CloudMergeError(st, "cm_test_device_allocations")
+    return live.value, total.value
 
 
 def box_directions(n):

@@ -1,6 +1,6 @@
 // cm_api.cpp — the C-ABI declared in include/cloudmerge.h: entry points and their argument checks. Frames are
 // assembled and launched in cm_launch.cpp, routed in cm_route.cpp; the tables computed from a result on request are
-// cm_byproducts.cpp's; the context is cm_ctx.hpp.
+// cm_byproducts.cpp's; the context is cm_ctx.hpp, whose buffers own their memory (cm_devbuf.hpp): cm_destroy is `delete`.
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
@@ -42,37 +42,21 @@ void quat_to_rows(const double q[4], const double t[3], float m[12]) {
     m[8] = txz - twy;          m[9] = tyz + twx;          m[10] = 1.0f - (txx + tyy); m[11] = static_cast<float>(t[2]);
 }
 
-void free_all(cm_ctx* c) {
-    auto F = [](void* p) { if (p) (void)hipFree(p); };
-    F(c->keys_a); F(c->keys_b); F(c->vals_a); F(c->vals_b); F(c->hist); F(c->totals);
-    F(c->seg_counts); F(c->seg_tile_counts); F(c->seg_groups); F(c->grp); F(c->partials); F(c->out_key); F(c->out_cnt); F(c->merged_total); F(c->out); F(c->merged); F(c->partial); F(c->table_entries); F(c->mask); F(c->sorted_pts); F(c->rows); F(c->d_state_o);
-    F(c->stage32); F(c->out32); F(c->rec_a); F(c->rec_b); F(c->dig); F(c->tile_state); F(c->wave_cnt); F(c->records);
-    F(c->spl[0]); F(c->spl[1]); F(c->qcnt); F(c->qtot); F(c->qbofs); F(c->qbid); F(c->qbig);
-    F(c->out_other); F(c->out32_other); F(c->motion_buf);
-    c->cov.release(); F(c->cov_tile_counts); F(c->cov_words); F(c->cov_state); F(c->cov_entries);
-    c->cl.release(); F(c->cl_root); F(c->cl_num); F(c->cl_labels); F(c->cl_tile_sums); F(c->cl_words); F(c->cl_clusters);
-    F(c->box_entries); F(c->box_dirs); F(c->box_words); F(c->box_list); F(c->box_ext); F(c->box_work); F(c->box_sums);
-    F(c->grid_cells); F(c->grid_image);
-    F(c->ray_bits); F(c->ray_cells); F(c->ray_image);
-    c->nrm.release(); F(c->nrm_list); F(c->nrm_words); F(c->nrm_entries);
-    c->aln.release(); c->aln_fit.release();
-    c->ndt_fit.release(); F(c->ndt_bounds);
-    F(c->sor_d); F(c->sor_list); F(c->sor_words);
-    if (c->pub_stream) (void)hipStreamDestroy(c->pub_stream);
-    for (auto e : c->ev_pub) if (e) (void)hipEventDestroy(e);
-    F(c->d_ground); F(c->d_state_g); F(c->gmask); F(c->zone_off); F(c->d_planes); F(c->hyp0); F(c->valid0); F(c->counts0); F(c->chunk_sums); F(c->bmask); F(c->zcode);
-    F(c->d_frame); F(c->d_tiles); F(c->d_state[0]); F(c->d_state[1]);
-    if (c->h_state) (void)hipHostFree(c->h_state);
-    if (c->h_tile_kept) (void)hipHostFree(c->h_tile_kept);
-    for (auto& s : c->slots) {
-        F(s.buf[0]); F(s.buf[1]);
+}  // namespace
+
+cm_ctx::~cm_ctx() {
+    for (auto& s : slots) {
         if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
         if (s.ev_copy) (void)hipEventDestroy(s.ev_copy);
     }
-    for (auto e : c->prof_ev) (void)hipEventDestroy(e);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    if (pub_stream) (void)hipStreamDestroy(pub_stream);
+    for (auto e : ev_pub) if (e) (void)hipEventDestroy(e);
+    for (auto e : prof_ev) (void)hipEventDestroy(e);
+    if (ev_done) (void)hipEventDestroy(ev_done);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
 }
+
+namespace {
 
 int set_slot_cloud(cm_ctx* c, uint32_t sensor, const void* data, bool on_device, uint32_t n,
                    uint32_t step, uint32_t ox, uint32_t oy, uint32_t oz, uint32_t oi, bool wait_copy = true) {
@@ -96,13 +80,8 @@ int set_slot_cloud(cm_ctx* c, uint32_t sensor, const void* data, bool on_device,
     } else {
         // the buffer no enqueued frame reads (a replaced staged cloud lived there too: same copy stream, in order)
         const int w = s.active_buf == 0 ? 1 : 0;
-        if (bytes > s.cap[w]) {
-            if (s.buf[w]) HIP_TRY(c, hipFree(s.buf[w]));
-            s.buf[w] = nullptr; s.cap[w] = 0;
-            const size_t cap = bytes + bytes / 4 + 256;
-            HIP_TRY(c, hipMalloc(&s.buf[w], cap));
-            s.cap[w] = cap;
-        }
+        if (bytes > s.buf[w].capacity() && !s.buf[w].reserve(bytes + bytes / 4 + 256))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the sensor's staging buffer");
         if (bytes) {
             HIP_TRY(c, hipMemcpyAsync(s.buf[w], data, bytes, hipMemcpyHostToDevice, s.copy_stream));
             if (wait_copy) {
@@ -238,11 +217,7 @@ int ndt_check(cm_ctx* c, const cm_ndt_params* p, const void* src, uint64_t n_src
 // what: the error text of a failure to grow.
 int stage_source(cm_ctx* c, PoseFit& fit, const void* src_host, uint64_t n_src, const char* what, const void** src_dev) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n_src > fit.cap_src_host) {
-        if (fit.src) { (void)hipFree(fit.src); fit.src = nullptr; fit.cap_src_host = 0; }
-        if (hipMalloc(&fit.src, n_src * 16) != hipSuccess) return fail(c, CM_HIP_ERROR, what);
-        fit.cap_src_host = n_src;
-    }
+    if (!fit.src.reserve(n_src * 16)) return fail(c, CM_HIP_ERROR, what);
     if (n_src) {
         HIP_TRY(c, hipMemcpyAsync(fit.src, src_host, n_src * 16, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -270,7 +245,7 @@ int copy_correspondences(cm_ctx* c, const PoseFit& fit, size_t bytes, const char
 int copy_fused(cm_ctx* c, const unsigned char* mask, void* host_dst, uint64_t capacity, uint64_t* n_points, bool counted) {
     if (c->frame.n_padded == 0) return CM_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->merged) HIP_TRY(c, hipMalloc(&c->merged, static_cast<size_t>(c->cap_padded) * 16));
+    if (!ensure_merged(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the fused cloud's buffer");
     // (seg_counts holds this frame's output offsets in its first cap_seg_tiles words: the tail takes the tile counts)
     uint32_t total = 0;
     const int e = fuse_points(c, c->seg_counts + c->cap_seg_tiles, c->merged, mask, &total);
@@ -336,36 +311,25 @@ int cm_create(cm_ctx** out, int device, const cm_limits* lim) {
     c->cap_tiles = c->cap_padded / CM_TILE;
     c->cap_seg_tiles = c->cap_padded / CM_SEG_TILE;
 
-    auto A = [&](void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess; };
-    const size_t n4 = static_cast<size_t>(c->cap_padded) * 4;
+    const size_t npad = c->cap_padded, nt = c->cap_tiles, nseg = c->cap_seg_tiles;
     bool ok = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) == hipSuccess;
     c->stream = c->own_stream;
     ok = ok && hipEventCreate(&c->ev_done) == hipSuccess;
-    ok = ok && A(reinterpret_cast<void**>(&c->keys_a), n4) && A(reinterpret_cast<void**>(&c->keys_b), n4);
-    ok = ok && A(reinterpret_cast<void**>(&c->vals_a), n4) && A(reinterpret_cast<void**>(&c->vals_b), n4);
-    ok = ok && A(reinterpret_cast<void**>(&c->hist), static_cast<size_t>(c->cap_tiles) * CM_RADIX * 4);
+    ok = ok && c->keys_a.once(npad) && c->keys_b.once(npad) && c->vals_a.once(npad) && c->vals_b.once(npad);
+    ok = ok && c->hist.once(nt * CM_RADIX);
     c->cap_groups = (c->cap_tiles + CM_GROUP - 1) / CM_GROUP;
     {
-        const size_t gbytes = static_cast<size_t>(c->cap_groups) * CM_RADIX * 4 * 5;
-        ok = ok && A(reinterpret_cast<void**>(&c->grp), gbytes);
-        ok = ok && hipMemset(c->grp, 0, gbytes) == hipSuccess;
+        const size_t gwords = static_cast<size_t>(c->cap_groups) * CM_RADIX * 5;
+        ok = ok && c->grp.once(gwords) && hipMemset(c->grp, 0, gwords * 4) == hipSuccess;
     }
-    ok = ok && A(reinterpret_cast<void**>(&c->seg_tile_counts), static_cast<size_t>(c->cap_seg_tiles + 1) * 4);
-    ok = ok && A(reinterpret_cast<void**>(&c->seg_groups), static_cast<size_t>(c->cap_seg_tiles / CM_SEG_GROUP + 2) * 32 * 4);
-    ok = ok && A(reinterpret_cast<void**>(&c->partials), CM_MINMAX_BLOCKS * 8 * sizeof(float));
-    ok = ok && A(reinterpret_cast<void**>(&c->totals), CM_RADIX * 4);
-    ok = ok && A(reinterpret_cast<void**>(&c->seg_counts), static_cast<size_t>(c->cap_seg_tiles + c->cap_tiles) * 4);
-    ok = ok && A(reinterpret_cast<void**>(&c->merged_total), 256);
-    ok = ok && A(&c->out, static_cast<size_t>(c->cap_padded) * 16);
-    if (c->flags & CM_FLAG_OCCUPANCY)
-        ok = ok && A(reinterpret_cast<void**>(&c->out_key), n4) && A(reinterpret_cast<void**>(&c->out_cnt), n4);
-    ok = ok && A(reinterpret_cast<void**>(&c->d_frame), sizeof(CmFrameDev));
-    ok = ok && A(reinterpret_cast<void**>(&c->d_tiles), static_cast<size_t>(c->cap_tiles) * sizeof(CmTileDev));
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_tile_kept), static_cast<size_t>(c->cap_tiles) * 4, hipHostMallocDefault) == hipSuccess;
+    ok = ok && c->seg_tile_counts.once(nseg + 1) && c->seg_groups.once((nseg / CM_SEG_GROUP + 2) * 32);
+    ok = ok && c->partials.once(CM_MINMAX_BLOCKS * 8) && c->totals.once(CM_RADIX) && c->seg_counts.once(nseg + nt);
+    ok = ok && c->merged_total.once(256 / 4) && c->out.once(npad * 16);
+    if (c->flags & CM_FLAG_OCCUPANCY) ok = ok && c->out_key.once(npad) && c->out_cnt.once(npad);
+    ok = ok && c->d_frame.once(1) && c->d_tiles.once(nt);
+    ok = ok && c->h_tile_kept.once(nt);
     ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_tile_kept), c->h_tile_kept, 0) == hipSuccess;
-    ok = ok && A(reinterpret_cast<void**>(&c->d_state[0]), sizeof(CmFrameState));
-    ok = ok && A(reinterpret_cast<void**>(&c->d_state[1]), sizeof(CmFrameState));
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&c->h_state), sizeof(CmFrameState), hipHostMallocDefault) == hipSuccess;
+    ok = ok && c->d_state[0].once(1) && c->d_state[1].once(1) && c->h_state.once(1);
     ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&c->h_state_dev), c->h_state, 0) == hipSuccess;
     for (uint32_t s = 0; ok && s < c->max_sensors; ++s)
         ok = hipStreamCreateWithFlags(&c->slots[s].copy_stream, hipStreamNonBlocking) == hipSuccess &&
@@ -407,7 +371,6 @@ int cm_create(cm_ctx** out, int device, const cm_limits* lim) {
         if (v >= 1 && v < 0xFFFFFFFFul) c->box_split = static_cast<uint32_t>(v);
     }
     if (!ok) {
-        free_all(c);
         delete c;
         return CM_HIP_ERROR;
     }
@@ -421,7 +384,6 @@ int cm_destroy(cm_ctx* c) {
     if (!c) return CM_BAD_ARG;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    free_all(c);
     delete c;
     return CM_OK;
 }
@@ -523,7 +485,7 @@ int cm_result_copy(cm_ctx* c, void* host_dst, uint64_t capacity_points, uint32_t
         return CM_OK;
     }
     // pcl::PointXYZI images (A.0) are laid out on the device and cross PCIe as they go on the wire
-    if (!c->out32) HIP_TRY(c, hipMalloc(&c->out32, static_cast<size_t>(c->cap_padded) * 32));
+    if (!ensure_out32(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the 32-byte result buffers");
     cmk_to_pcl32(c->stream, c->out, c->out32, static_cast<uint32_t>(n));
     HIP_TRY(c, hipMemcpyAsync(host_dst, c->out32, n * 32, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -560,15 +522,15 @@ int cm_result_publish_async(cm_ctx* c, void* host_dst, uint64_t capacity_points,
     if (!c->pub_stream) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->pub_stream, hipStreamNonBlocking));
         for (auto& e : c->ev_pub) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIP_TRY(c, hipMalloc(&c->out_other, static_cast<size_t>(c->cap_padded) * 16));
+        if (!c->out_other.once(static_cast<size_t>(c->cap_padded) * 16)) return fail(c, CM_HIP_ERROR, "cannot allocate the second result buffer");
     }
     // (the frame has been waited for — cm_wait returned its counts — so its result is complete; an overflow fallback's
     // merged cloud was written on c->stream and synchronised as well)
     if (step_out == 16) {
         HIP_TRY(c, hipMemcpyAsync(host_dst, c->out, n * 16, hipMemcpyDeviceToHost, c->pub_stream));
     } else {
-        if (!c->out32) HIP_TRY(c, hipMalloc(&c->out32, static_cast<size_t>(c->cap_padded) * 32));
-        if (!c->out32_other) HIP_TRY(c, hipMalloc(&c->out32_other, static_cast<size_t>(c->cap_padded) * 32));
+        if (!ensure_out32(c) || !c->out32_other.once(static_cast<size_t>(c->cap_padded) * 32))
+            return fail(c, CM_HIP_ERROR, "cannot allocate the 32-byte result buffers");
         cmk_to_pcl32(c->pub_stream, c->out, c->out32, static_cast<uint32_t>(n));
         HIP_TRY(c, hipMemcpyAsync(host_dst, c->out32, n * 32, hipMemcpyDeviceToHost, c->pub_stream));
     }
@@ -1150,11 +1112,8 @@ int cm_set_ego_motion(cm_ctx* c, const cm_motion* m) {
         if (!std::isfinite(m->v[a]) || !std::isfinite(m->w[a])) return fail(c, CM_BAD_ARG, "ego velocity must be finite");
     if (!c->motion_buf) {
         HIP_TRY(c, hipSetDevice(c->device));
-        if (hipMalloc(&c->motion_buf, static_cast<size_t>(c->cap_padded) * 16) != hipSuccess) {
-            c->motion_buf = nullptr;
-            (void)hipGetLastError();
+        if (!c->motion_buf.once(static_cast<size_t>(c->cap_padded) * 16))
             return fail(c, CM_HIP_ERROR, "could not allocate the compensated clouds' buffer");
-        }
     }
     c->motion = *m;
     c->motion_on = true;
@@ -1170,18 +1129,8 @@ int cm_set_statistical_outlier(cm_ctx* c, const cm_sor_params* p) {
     if (!(p->search_cell >= 0.0f) || !std::isfinite(p->search_cell)) return fail(c, CM_BAD_ARG, "search_cell must be finite and >= 0");
     const size_t npad = c->cap_padded;
     HIP_TRY(c, hipSetDevice(c->device));
-    auto grab = [&](void** ptr, size_t bytes) {
-        if (*ptr) return true;
-        if (hipMalloc(ptr, bytes) == hipSuccess) return true;
-        *ptr = nullptr;
-        (void)hipGetLastError();
-        return false;
-    };
-    bool ok = grab(reinterpret_cast<void**>(&c->sor_d), npad * 4) && grab(&c->sor_list, npad * 8) &&
-              grab(reinterpret_cast<void**>(&c->sor_words), CM_SOR_WORDS * 8) && grab(reinterpret_cast<void**>(&c->mask), npad) &&
-              grab(&c->sorted_pts, npad * 16) && grab(&c->rows, static_cast<size_t>(CM_ROW_TABLE_CAP) * 8) &&
-              grab(reinterpret_cast<void**>(&c->d_state_o), sizeof(CmFrameState));
-    if (!ok) return fail(c, CM_HIP_ERROR, "could not allocate the statistical outlier stage's buffers");
+    if (!(c->sor_d.once(npad) && c->sor_list.once(npad * 8) && c->sor_words.once(CM_SOR_WORDS) && ensure_mask(c) && ensure_cell_sort(c)))
+        return fail(c, CM_HIP_ERROR, "could not allocate the statistical outlier stage's buffers");
     c->sor = *p;
     c->sor_on = true;
     return CM_OK;
@@ -1225,6 +1174,15 @@ int cm_get_stage_times(cm_ctx* c, cm_stage_times* out) {
     *out = c->stage_times;
     return CM_OK;
 }
+
+#ifdef CM_TEST_HOOKS                     // (the test build only: cm_devbuf.hpp's counts of the process)
+CM_API int cm_test_device_allocations(uint64_t* live, uint64_t* total) {
+    if (!live || !total) return CM_BAD_ARG;
+    *live = cm_allocations_live.load();
+    *total = cm_allocations_total.load();
+    return CM_OK;
+}
+#endif
 
 int cm_host_alloc(void** ptr, size_t bytes) {
     if (!ptr) return CM_BAD_ARG;

@@ -3,7 +3,8 @@
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
-// Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's.
+// Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
+// (cm_devbuf.hpp) that grow on demand and go with the context, so a call here states what it needs and frees nothing.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -13,20 +14,6 @@
 #include "cm_search.hpp"
 
 namespace {
-
-bool dev_alloc(void** ptr, size_t bytes) { return hipMalloc(ptr, bytes) == hipSuccess; }
-template <class T> bool dev_alloc(T** ptr, size_t bytes) { return dev_alloc(reinterpret_cast<void**>(ptr), bytes); }
-template <class T> void dev_free(T*& ptr) { if (ptr) { (void)hipFree(ptr); ptr = nullptr; } }
-
-// One table of `need` entries of `bytes` each: beyond *cap it is freed and allocated anew. false: out of memory, *cap is 0.
-bool grow_table(void** ptr, uint64_t* cap, uint64_t need, size_t bytes) {
-    if (need <= *cap) return true;
-    dev_free(*ptr);
-    *cap = 0;
-    if (!dev_alloc(ptr, need * bytes)) return false;
-    *cap = need;
-    return true;
-}
 
 // What the grid kernels take of cm_grid_params: inv = 1.0f / cell, the fp32 division of step 1.
 CmGridDev grid_dev(const cm_grid_params& q) {
@@ -46,45 +33,19 @@ CmGridDev grid_dev(const cm_grid_params& q) {
 }  // namespace
 
 int PairSort::reserve(cm_ctx* c, uint32_t n_slots, const char* what) {
-    if (n_slots <= cap_slots) return CM_OK;
-    release();
+    if (n_slots == 0) return CM_OK;
     const size_t tiles = n_slots / CM_TILE, groups = (tiles + CM_GROUP - 1) / CM_GROUP;
     bool ok = true;
-    for (uint32_t** b : {&keys_a, &keys_b, &vals_a, &vals_b}) ok = ok && dev_alloc(b, static_cast<size_t>(n_slots) * 4);
-    ok = ok && dev_alloc(&hist, tiles * CM_RADIX * 4);
-    ok = ok && dev_alloc(&grp, CM_MAX_PASSES * groups * CM_RADIX * 4);
-    ok = ok && dev_alloc(&totals, CM_RADIX * 4);
-    if (!ok) return fail(c, CM_HIP_ERROR, what);
-    cap_slots = n_slots;
-    return CM_OK;
-}
-
-void PairSort::release() {
-    for (uint32_t** b : {&keys_a, &keys_b, &vals_a, &vals_b, &hist, &grp, &totals}) dev_free(*b);
-    cap_slots = 0;
-}
-
-void SearchIndex::release() {
-    sort.release();
-    dev_free(state); dev_free(bounds); dev_free(pts); dev_free(aux); dev_free(rows);
-    cap_rows = 0;
+    for (DevBuf<uint32_t>* b : {&keys_a, &keys_b, &vals_a, &vals_b}) ok = ok && b->reserve(n_slots);
+    ok = ok && hist.reserve(tiles * CM_RADIX) && grp.reserve(CM_MAX_PASSES * groups * CM_RADIX) && totals.once(CM_RADIX);
+    return ok ? CM_OK : fail(c, CM_HIP_ERROR, what);
 }
 
 int PoseFit::reserve(cm_ctx* c, uint64_t n, size_t corr_bytes, const char* what_state, const char* what_table) {
-    if (!sums && !dev_alloc(&sums, CM_ALIGN_SUMS * sizeof(double))) return fail(c, CM_HIP_ERROR, what_state);
-    if (n <= cap_src) return CM_OK;
-    dev_free(corr); dev_free(part);
-    cap_src = 0;
+    if (!sums.once(CM_ALIGN_SUMS)) return fail(c, CM_HIP_ERROR, what_state);
     const size_t n_blocks = (n + CM_BLOCK - 1) / CM_BLOCK;
-    if (!dev_alloc(&corr, n * corr_bytes) || !dev_alloc(&part, n_blocks * CM_ALIGN_STRIDE * sizeof(double)))
-        return fail(c, CM_HIP_ERROR, what_table);
-    cap_src = n;
+    if (!corr.reserve(n * corr_bytes) || !part.reserve(n_blocks * CM_ALIGN_STRIDE)) return fail(c, CM_HIP_ERROR, what_table);
     return CM_OK;
-}
-
-void PoseFit::release() {
-    dev_free(corr); dev_free(part); dev_free(sums); dev_free(src);
-    cap_src = cap_src_host = 0;
 }
 
 // The per-voxel covariance table of the last result into c->cov_entries (cm_kernels_cov.hip). Launches on the context's
@@ -95,19 +56,15 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
     c->cov_have = false;
     if (n_out == 0) return CM_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!grow_table(&c->cov_entries, &c->cov_cap_entries, n_out, sizeof(cm_voxel_cov)))
-        return fail(c, CM_HIP_ERROR, "cannot allocate the covariance table");
+    if (!c->cov_entries.reserve(n_out * sizeof(cm_voxel_cov))) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance table");
     const CmFrameDev& f = c->frame;
     const uint32_t nt = f.n_tiles, n_slots = f.n_padded;
     const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
     PairSort& so = c->cov;
     if (const int e = so.reserve(c, n_slots, "cannot allocate the covariance sort's buffers")) return e;
-    if (!c->cov_state) {
-        bool ok = dev_alloc(&c->cov_state, sizeof(CmFrameState)) && dev_alloc(&c->cov_tile_counts, static_cast<size_t>(c->cap_tiles) * 4) &&
-                  dev_alloc(&c->cov_words, 2 * 4);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's state");
-    }
-    if (!c->merged) HIP_TRY(c, hipMalloc(&c->merged, static_cast<size_t>(c->cap_padded) * 16));
+    if (!c->cov_state.once(1) || !c->cov_tile_counts.once(c->cap_tiles) || !c->cov_words.once(2))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the covariance sort's state");
+    if (!ensure_merged(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the fused cloud's buffer");
     hipStream_t st = c->stream;
     // the kept points in (sensor, point) order, as cm_merged_copy returns them
     cmk_merged(st, c->d_frame, c->cov_tile_counts, c->cov_words, c->merged, nt, c->frame_mask);
@@ -199,16 +156,10 @@ void bounds_midpoint(const float mn[3], const float mx[3], double pivot[3]) {
 // sort's buffers, the points and the aux words grown with the result. what_buffers, what_state: the error texts.
 int reserve_search_index(cm_ctx* c, SearchIndex& ix, uint32_t n_states, const char* what_buffers, const char* what_state) {
     const uint32_t n_slots = round_up(static_cast<uint32_t>(c->result.n_out), CM_TILE);
-    if (n_slots > ix.sort.cap_slots) {
-        dev_free(ix.pts); dev_free(ix.aux);
-        if (const int e = ix.sort.reserve(c, n_slots, what_buffers)) return e;
-        if (!dev_alloc(&ix.pts, static_cast<size_t>(n_slots) * 16) || !dev_alloc(&ix.aux, static_cast<size_t>(n_slots) * 12)) {
-            ix.sort.release();                       // (the next call grows all of it again)
-            return fail(c, CM_HIP_ERROR, what_buffers);
-        }
-    }
-    if (!ix.state && !(dev_alloc(&ix.state, n_states * sizeof(CmFrameState)) && dev_alloc(&ix.bounds, 6 * 4)))
-        return fail(c, CM_HIP_ERROR, what_state);
+    if (const int e = ix.sort.reserve(c, n_slots, what_buffers)) return e;
+    if (!ix.pts.reserve(static_cast<size_t>(n_slots) * 16) || !ix.aux.reserve(static_cast<size_t>(n_slots) * 3))
+        return fail(c, CM_HIP_ERROR, what_buffers);
+    if (!ix.state.once(n_states) || !ix.bounds.once(6)) return fail(c, CM_HIP_ERROR, what_state);
     return CM_OK;
 }
 
@@ -220,7 +171,7 @@ int build_search_index(cm_ctx* c, SearchIndex& ix, const ClusterGrid& grid, cons
     const uint32_t n = static_cast<uint32_t>(c->result.n_out);
     const uint32_t n_slots = round_up(n, CM_TILE), nt = n_slots / CM_TILE;
     const uint32_t gw = (nt + CM_GROUP - 1) / CM_GROUP * CM_RADIX;
-    if (!grow_table(&ix.rows, &ix.cap_rows, static_cast<uint64_t>(grid.dims[1]) * grid.dims[2], 8)) return fail(c, CM_HIP_ERROR, what);
+    if (!ix.rows.reserve(static_cast<size_t>(grid.dims[1]) * grid.dims[2] * 8)) return fail(c, CM_HIP_ERROR, what);
     for (int a = 0; a < 3; ++a) { ix.grid.min[a] = mn[a]; ix.grid.dims[a] = grid.dims[a]; }
     ix.grid.inv = grid.inv;
     hipStream_t st = c->stream;
@@ -256,16 +207,10 @@ int clusters(cm_ctx* c, const cm_cluster_params& q, bool more_stages) {
     SearchIndex& ix = c->cl;
     if (const int e = reserve_search_index(c, ix, 2, "cannot allocate the cluster extraction's buffers",
                                            "cannot allocate the cluster extraction's state")) return e;
-    if (n_slots > c->cl_cap_tables) {
-        dev_free(c->cl_root); dev_free(c->cl_num); dev_free(c->cl_labels); dev_free(c->cl_tile_sums);
-        c->cl_cap_tables = 0;
-        bool ok = true;
-        for (uint32_t** b : {&c->cl_root, &c->cl_num, &c->cl_labels}) ok = ok && dev_alloc(b, static_cast<size_t>(n_slots) * 4);
-        ok = ok && dev_alloc(&c->cl_tile_sums, static_cast<size_t>(nt) * 8);
-        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's buffers");
-        c->cl_cap_tables = n_slots;
-    }
-    if (!c->cl_words && !dev_alloc(&c->cl_words, 2 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's state");
+    if (!c->cl_root.reserve(n_slots) || !c->cl_num.reserve(n_slots) || !c->cl_labels.reserve(n_slots) ||
+        !c->cl_tile_sums.reserve(static_cast<size_t>(nt) * 8))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's buffers");
+    if (!c->cl_words.once(2)) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster extraction's state");
     hipStream_t st = c->stream;
     uint32_t* const w = c->cl_words;
     c->prof_used = 0;
@@ -293,8 +238,7 @@ int clusters(cm_ctx* c, const cm_cluster_params& q, bool more_stages) {
     HIP_TRY(c, hipMemcpyAsync(counts, w, sizeof counts, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     const uint32_t n_clusters = counts[0];
-    if (!grow_table(&c->cl_clusters, &c->cl_cap_clusters, n_clusters, sizeof(cm_cluster)))
-        return fail(c, CM_HIP_ERROR, "cannot allocate the cluster table");
+    if (!c->cl_clusters.reserve(n_clusters * sizeof(cm_cluster))) return fail(c, CM_HIP_ERROR, "cannot allocate the cluster table");
 
     // numbers, labels, AABB, and the member lists: (cluster number, voxel index) sorted by cluster number, stable
     const uint32_t passes_num = (key_width(n_clusters ? n_clusters : 1u) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
@@ -346,27 +290,14 @@ int cluster_boxes(cm_ctx* c, const cm_box_params& q) {
         }
         return CM_OK;
     }
-    if (!grow_table(&c->box_entries, &c->box_cap_entries, n_clusters, sizeof(cm_cluster_box)))
-        return fail(c, CM_HIP_ERROR, "cannot allocate the box table");
-    if (!c->box_dirs && !(dev_alloc(&c->box_dirs, sizeof c->box_dirs_host) && dev_alloc(&c->box_words, 2 * 4)))
-        return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's state");
+    if (!c->box_entries.reserve(n_clusters * sizeof(cm_cluster_box))) return fail(c, CM_HIP_ERROR, "cannot allocate the box table");
+    if (!c->box_dirs.once(sizeof c->box_dirs_host) || !c->box_words.once(2)) return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's state");
     const uint64_t split = c->box_split;
     const uint64_t max_large = n_clustered / (split + 1u);
     const uint64_t max_chunks = max_large ? n_clustered / CM_BOX_CHUNK + max_large : 0u;
-    if (max_large > c->box_cap_large) {
-        dev_free(c->box_list); dev_free(c->box_ext);
-        c->box_cap_large = 0;
-        if (!dev_alloc(&c->box_list, max_large * 8) || !dev_alloc(&c->box_ext, max_large * CM_BOX_MAX_ANGLES * 16))
-            return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's buffers");
-        c->box_cap_large = max_large;
-    }
-    if (max_chunks > c->box_cap_chunks) {
-        dev_free(c->box_work); dev_free(c->box_sums);
-        c->box_cap_chunks = 0;
-        if (!dev_alloc(&c->box_work, max_chunks * 8) || !dev_alloc(&c->box_sums, max_chunks * CM_BOX_MAX_ANGLES * sizeof(double)))
-            return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's buffers");
-        c->box_cap_chunks = max_chunks;
-    }
+    if (!c->box_list.reserve(max_large * 8) || !c->box_ext.reserve(max_large * CM_BOX_MAX_ANGLES * 16) ||
+        !c->box_work.reserve(max_chunks * 8) || !c->box_sums.reserve(max_chunks * CM_BOX_MAX_ANGLES))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the box fit's buffers");
     if (c->box_dirs_n != q.n_angles) {
         // (box_dirs_host is read by no copy in flight: every box call ends with the stream at rest)
         box_direction_table(q.n_angles, c->box_dirs_host);
@@ -409,13 +340,8 @@ int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages) {
     c->grid_have = c->ray_have = false;           // (a ray table goes with the grid it was cast over)
     const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n_cells > c->grid_cap_cells) {
-        dev_free(c->grid_cells); dev_free(c->grid_image);
-        c->grid_cap_cells = 0;
-        if (!dev_alloc(&c->grid_cells, n_cells * sizeof(cm_grid_cell)) || !dev_alloc(&c->grid_image, n_cells))
-            return fail(c, CM_HIP_ERROR, "cannot allocate the grid map");
-        c->grid_cap_cells = n_cells;
-    }
+    if (!c->grid_cells.reserve(n_cells * sizeof(cm_grid_cell)) || !c->grid_image.reserve(n_cells))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the grid map");
     const CmGridDev g = grid_dev(q);
     hipStream_t st = c->stream;
     c->prof_used = 0;
@@ -444,14 +370,9 @@ int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages) {
 int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r) {
     const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
     HIP_TRY(c, hipSetDevice(c->device));
-    if (n_cells > c->ray_cap_cells) {
-        dev_free(c->ray_bits); dev_free(c->ray_cells); dev_free(c->ray_image);
-        c->ray_cap_cells = 0;
-        if (!dev_alloc(&c->ray_bits, static_cast<size_t>(c->max_sensors) * ((n_cells + 31) / 32) * 4) ||
-            !dev_alloc(&c->ray_cells, n_cells * sizeof(cm_grid_ray_cell)) || !dev_alloc(&c->ray_image, n_cells))
-            return fail(c, CM_HIP_ERROR, "cannot allocate the ray tables");
-        c->ray_cap_cells = n_cells;
-    }
+    if (!c->ray_bits.reserve(static_cast<size_t>(c->max_sensors) * ((n_cells + 31) / 32)) ||
+        !c->ray_cells.reserve(n_cells * sizeof(cm_grid_ray_cell)) || !c->ray_image.reserve(n_cells))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the ray tables");
     if (const int e = grid_map(c, q, true)) return e;
     const uint32_t words = static_cast<uint32_t>((n_cells + 31) / 32);
     const uint32_t n_sensors = c->frame.n_tiles ? c->frame.n_sensors : 0u;
@@ -504,14 +425,9 @@ int normals(cm_ctx* c, const cm_normal_params& q) {
     SearchIndex& ix = c->nrm;
     if (const int e = reserve_search_index(c, ix, 1, "cannot allocate the normal estimation's buffers",
                                            "cannot allocate the normal estimation's state")) return e;
-    if (n_slots > c->nrm_cap_tables) {
-        dev_free(c->nrm_list); dev_free(c->nrm_entries);
-        c->nrm_cap_tables = 0;
-        if (!dev_alloc(&c->nrm_list, static_cast<size_t>(n_slots) * 8) || !dev_alloc(&c->nrm_entries, static_cast<size_t>(n_slots) * sizeof(cm_voxel_normal)))
-            return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's buffers");
-        c->nrm_cap_tables = n_slots;
-    }
-    if (!c->nrm_words && !dev_alloc(&c->nrm_words, 2 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's state");
+    if (!c->nrm_list.reserve(static_cast<size_t>(n_slots) * 8) || !c->nrm_entries.reserve(static_cast<size_t>(n_slots) * sizeof(cm_voxel_normal)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's buffers");
+    if (!c->nrm_words.once(2)) return fail(c, CM_HIP_ERROR, "cannot allocate the normal estimation's state");
     hipStream_t st = c->stream;
     uint32_t* const w = c->nrm_words;
     c->prof_used = 0;
@@ -701,7 +617,7 @@ int ndt(cm_ctx* c, const cm_ndt_params& q, const cm_cov_params& cov, const void*
     }
     if (const int e = fit.reserve(c, n_src64, sizeof(cm_ndt_corr), "cannot allocate the NDT registration's state",
                                   "cannot allocate the NDT registration's correspondence table")) return e;
-    if (!c->ndt_bounds && !dev_alloc(&c->ndt_bounds, 6 * 4)) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's state");
+    if (!c->ndt_bounds.once(6)) return fail(c, CM_HIP_ERROR, "cannot allocate the NDT registration's state");
     // nothing is refused from here on: a refused call leaves *out as it was
     std::memset(out, 0, sizeof *out);
     std::memcpy(out->pose, q.guess, sizeof out->pose);

@@ -123,21 +123,13 @@ int bootstrap_box(cm_ctx* c) {
 }
 
 int bucket_buffers(cm_ctx* c) {
-    const size_t npad = c->cap_padded;
-    if (!c->rec_a) HIP_TRY(c, hipMalloc(&c->rec_a, npad * 16));
-    if (!c->rec_b) HIP_TRY(c, hipMalloc(&c->rec_b, npad * 16));
-    if (!c->dig) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->dig), npad));
-    if (!c->tile_state) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->tile_state), (npad / 1024 + 2) * 8));
-    if (!c->records) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->records), static_cast<size_t>(c->cap_tiles) * 32));
-    if (!c->wave_cnt) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->wave_cnt), static_cast<size_t>(c->cap_tiles) * CM2_WAVES * 4));
-    for (auto& p : c->spl)
-        if (!p) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&p), (CM4_MAX_BUCKETS + 4) * 4));
-    if (!c->qcnt) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->qcnt), static_cast<size_t>(std::min<uint32_t>(c->cap_tiles, CM4_MAX_TILES)) * (CM4_BINS / 2) * 4));
-    if (!c->qtot) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->qtot), CM4_BINS * 4));
-    if (!c->qbid) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->qbid), static_cast<size_t>(std::min<uint32_t>(c->cap_tiles, CM4_MAX_TILES)) * CM_TILE * 2));
-    if (!c->qbofs) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->qbofs), (CM4_BINS + 4) * 4));
-    if (!c->qbig) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->qbig), (CM4_MAX_BIG + 4) * 4));
-    return CM_OK;
+    const size_t npad = c->cap_padded, nt = c->cap_tiles, nt4 = std::min<uint32_t>(c->cap_tiles, CM4_MAX_TILES);
+    const bool ok = c->rec_a.once(npad * 16) && c->rec_b.once(npad * 16) && c->dig.once(npad) && c->tile_state.once(npad / 1024 + 2) &&
+                    c->records.once(nt * 8) && c->wave_cnt.once(nt * CM2_WAVES) &&
+                    // the quantile passes'
+                    c->spl[0].once(CM4_MAX_BUCKETS + 4) && c->spl[1].once(CM4_MAX_BUCKETS + 4) && c->qcnt.once(nt4 * (CM4_BINS / 2)) &&
+                    c->qtot.once(CM4_BINS) && c->qbid.once(nt4 * CM_TILE) && c->qbofs.once(CM4_BINS + 4) && c->qbig.once(CM4_MAX_BIG + 4);
+    return ok ? CM_OK : fail(c, CM_HIP_ERROR, "cannot allocate the bucket path's buffers");
 }
 
 // The bucket path's voxel stage for the frame in c->frame as c->plan has it: the quantile passes, or pl.g fixed-grid 8-bit
@@ -188,7 +180,7 @@ int launch_bucket(cm_ctx* c, const unsigned char* mask, const CmFrameState* st_o
                      c->out_cnt, false, 0u, nb);
         return end_frame(c);
     }
-    if (pl.mode == 1 && !c->partial) HIP_TRY(c, hipMalloc(&c->partial, static_cast<size_t>(c->cap_padded) * 32));
+    if (pl.mode == 1 && !ensure_partial(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the partial table");
     const GrpArrays g = next_grp(c);
     prof_mark(c, "k2_hist0");
     cmk2_hist0(st, f, c->d_frame, c->d_tiles, do_setup, state, c->hist, g.p0, g.p0_next, g.rest, g.gw, g.stride, c->tile_state,
@@ -203,7 +195,7 @@ int launch_bucket(cm_ctx* c, const unsigned char* mask, const CmFrameState* st_o
         // path's key / value arrays, which the bucket path does not use.
         void* stage = ((pl.g - 1) & 1u) ? c->rec_a : c->rec_b;
         if (pl.mode == 1) {
-            if (!c->stage32) HIP_TRY(c, hipMalloc(&c->stage32, static_cast<size_t>(c->cap_padded) * 32));
+            if (!c->stage32.once(static_cast<size_t>(c->cap_padded) * 32)) return fail(c, CM_HIP_ERROR, "cannot allocate the partial table's staging");
             stage = c->stage32;
         }
         uint32_t* grp_cnt = reinterpret_cast<uint32_t*>(c->tile_state + f.n_padded / 2048);
@@ -246,9 +238,7 @@ int cell_sort(cm_ctx* c, const unsigned char* in, bool* gathered) {
     const FramePlan& pl = c->plan;
     const CmFrameDev& f = c->frame;
     hipStream_t st = c->stream;
-    if (!c->sorted_pts) HIP_TRY(c, hipMalloc(&c->sorted_pts, static_cast<size_t>(c->cap_padded) * 16));
-    if (!c->rows) HIP_TRY(c, hipMalloc(&c->rows, static_cast<size_t>(CM_ROW_TABLE_CAP) * 8));
-    if (!c->d_state_o) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_state_o), sizeof(CmFrameState)));
+    if (!ensure_cell_sort(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the outlier stage's buffers");
     HIP_TRY(c, hipMemsetAsync(c->d_state_o, 0, sizeof(CmFrameState), st));
     const uint32_t nt = f.n_tiles, g = pl.g_o;
     if (g) {
@@ -337,22 +327,12 @@ int launch_classic(cm_ctx* c) {
     if (c->ground_on && pl.mode == 0) {
         // Zone-wise ground removal first (per sensor, before the fuse): it leaves a keep-mask for the voxel
         // grid and the fused no-ground cloud, and a ground mask for the fused ground cloud.
-        if (!c->mask) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->mask), c->cap_padded));
-        if (!c->gmask) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->gmask), c->cap_padded));
-        if (!c->sorted_pts) HIP_TRY(c, hipMalloc(&c->sorted_pts, static_cast<size_t>(c->cap_padded) * 16));
-        if (!c->d_ground) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_ground), sizeof(CmGroundDev)));
-        if (!c->d_state_g) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_state_g), sizeof(CmFrameState)));
-        if (!c->zone_off) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->zone_off), (CM_DEV_MAX_SENSORS * CM_DEV_MAX_ZONES + 1) * 4));
-        if (!c->d_planes) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_planes), CM_DEV_MAX_SENSORS * CM_DEV_MAX_ZONES * sizeof(CmGroundPlaneDev)));
-        const size_t nh = static_cast<size_t>(CM_DEV_MAX_SENSORS) * CM_DEV_MAX_ZONES * CM_GROUND_BATCH;
-        if (!c->hyp0) HIP_TRY(c, hipMalloc(&c->hyp0, nh * 16));
-        if (!c->valid0) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->valid0), nh * 4));
-        if (!c->counts0) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->counts0), nh * 4));
-        if (!c->chunk_sums) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->chunk_sums), (static_cast<size_t>(c->cap_padded) / CM_GROUND_CHUNK + CM_DEV_MAX_SENSORS * CM_DEV_MAX_ZONES + 1) * 10 * sizeof(double)));
-        if (ground_outl) {
-            if (!c->bmask) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->bmask), c->cap_padded));
-            if (!c->zcode) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->zcode), c->cap_padded));
-        }
+        const size_t npad = c->cap_padded, nz = CM_DEV_MAX_SENSORS * CM_DEV_MAX_ZONES, nh = nz * CM_GROUND_BATCH;
+        const bool ok = ensure_mask(c) && c->gmask.once(npad) && ensure_sorted_pts(c) && c->d_ground.once(1) && c->d_state_g.once(1) &&
+                        c->zone_off.once(nz + 1) && c->d_planes.once(nz) && c->hyp0.once(nh * 16) && c->valid0.once(nh) &&
+                        c->counts0.once(nh) && c->chunk_sums.once((npad / CM_GROUND_CHUNK + nz + 1) * 10) &&
+                        (!ground_outl || (c->bmask.once(npad) && c->zcode.once(npad)));
+        if (!ok) return fail(c, CM_HIP_ERROR, "cannot allocate the ground stage's buffers");
         if (!c->ground_uploaded) { cmkg_setup(st, c->ground, c->d_ground); c->ground_uploaded = true; }
         // (masks and the slab sort's state cleared by ONE launch: they were five hipMemsetAsync calls per tick)
         prof_mark(c, "kg_clear");
@@ -378,7 +358,7 @@ int launch_classic(cm_ctx* c) {
     }
     if (pl.outl) {
         // Radius outlier removal first: it decides which points the voxel grid sees at all.
-        if (!c->mask) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->mask), c->cap_padded));
+        if (!ensure_mask(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the outlier stage's buffers");
         HIP_TRY(c, hipMemsetAsync(c->mask, 0, f.n_padded, st));
         const int e = radius_filter(c, nullptr, nullptr, c->mask);
         if (e != CM_OK) return e;
@@ -403,7 +383,7 @@ int launch_classic(cm_ctx* c) {
     uint32_t* seg_groups = nseg > CM_SEG_DIRECT_TILES ? c->seg_groups : nullptr;
     cmk_seg_count(st, state, c->keys_a, c->keys_b, c->seg_tile_counts, seg_groups, pl.mode == 1 ? 1u : f.min_pts, nseg);
     prof_mark(c, "k_seg_reduce");
-    if (pl.mode == 1 && !c->partial) HIP_TRY(c, hipMalloc(&c->partial, static_cast<size_t>(c->cap_padded) * 32));
+    if (pl.mode == 1 && !ensure_partial(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the partial table");
     cmk_seg_reduce(st, pl.mode, c->d_frame, state, state_next, c->h_state_dev, c->keys_a, c->vals_a, c->keys_b,
                    c->vals_b, c->seg_tile_counts, seg_groups, pl.mode == 1 ? c->partial : c->out, c->out_key,
                    c->out_cnt, nseg);
@@ -558,7 +538,7 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
         static const float identity[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
         for (uint32_t j = 0; j < k; ++j) {
             CmSensorDev& d = f.s[j];
-            d.data = static_cast<const unsigned char*>(c->motion_buf) + static_cast<size_t>(d.base) * 16;
+            d.data = c->motion_buf + static_cast<size_t>(d.base) * 16;
             d.point_step = 16;
             d.off_x = 0; d.off_y = 4; d.off_z = 8; d.off_i = 12;
             d.layout = CM_LAYOUT_XYZI16;
@@ -912,7 +892,7 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     CmFrameState* state_next = c->d_state[c->cur ^ 1];
     const uint32_t nt = f.n_tiles, nseg = f.n_padded / CM_SEG_TILE;
     const GrpArrays g = next_grp(c);
-    if (!c->table_entries) HIP_TRY(c, hipMalloc(&c->table_entries, static_cast<size_t>(c->cap_padded) * 32));
+    if (!c->table_entries.once(static_cast<size_t>(c->cap_padded) * 32)) return fail(c, CM_HIP_ERROR, "cannot allocate the merged table");
     cmk_table_keys(st, c->d_frame, state, c->keys_a, c->hist, g.p0, g.p0_next, g.rest, g.gw, g.stride, c->seg_groups,
                    (nseg + CM_SEG_GROUP - 1) / CM_SEG_GROUP + 1, 32u, nt);
     radix_sort_pairs(c, state, {c->keys_a, c->keys_b, c->vals_a, c->vals_b, c->hist, c->totals, g.p0, g.rest}, CM_MAX_PASSES, nt,
