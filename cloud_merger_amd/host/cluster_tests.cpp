@@ -1,24 +1,11 @@
 // cluster_tests.cpp — the host shell's cluster extraction: NodeConfig keys (CPU) and, with "gpu", one node whose voxel
 // cloud holds three separated groups of points and a loose one, checked against the known partition.
 //   cluster_tests <tmpdir> [gpu]
-#include <cstdio>
-#include <cstring>
-#include <fstream>
 #include <map>
-#include <string>
-#include <vector>
 
-#include "merger_node.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
-
-static bool load_text(const std::string& path, const std::string& text, NodeConfig* c, std::string* err) {
-    std::ofstream(path) << text;
-    return load_config(path, c, err);
-}
 
 static void test_config_keys(const char* tmpdir) {
     const std::string path = std::string(tmpdir) + "/cluster.cfg";
@@ -40,13 +27,7 @@ static void test_config_keys(const char* tmpdir) {
 }
 
 static void test_node_on_gpu() {
-    NodeConfig c = reference_config();
-    c.sensors = {{"a", "/a", "a_link", true}};
-    c.params.crop_enable = 0;
-    c.params.min_points_per_voxel = 0;
-    c.params.leaf[0] = c.params.leaf[1] = c.params.leaf[2] = 0.125f;
-    c.publish_pcl_layout = false;
-    c.max_points_total = 1000;
+    NodeConfig c = single_sensor_config(0.125f, 1000);
     c.cluster_tolerance = 0.6f;
     c.cluster_min_size = 2;
     CloudMergerNode node(c);
@@ -62,8 +43,7 @@ static void test_node_on_gpu() {
     const float loose[4] = {40.0f, 40.0f, 0.25f, 1.0f};
     pts.insert(pts.end(), loose, loose + 4);
     const int n = static_cast<int>(pts.size() / 4);
-    PointCloud2 m = make_xyzi16_message(n);
-    std::memcpy(m.data.data(), pts.data(), pts.size() * 4);
+    PointCloud2 m = xyzi_message(pts);
     std::vector<float> out;
     node.set_publisher([&](const std::string&, const PointCloud2& o) {
         out.resize(o.num_points() * 4);
@@ -95,11 +75,4 @@ static void test_node_on_gpu() {
     CHECK(node.cluster_count() == 3);
 }
 
-int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_config_keys(tmpdir);
-    if (gpu) test_node_on_gpu();
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
-}
+int main(int argc, char** argv) { return run_tests(argc, argv, test_config_keys, test_node_on_gpu); }

@@ -3,18 +3,12 @@
 // (no fallback) when no MI355X is present. Exit code 0 = all passed. Run by tests/test_host_shell.py.
 #include <atomic>
 #include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
 #include <thread>
 
-#include "merger_node.hpp"
 #include "pcd_io.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
 
 static void test_find_xyzi() {
     PointCloud2 m = make_pcl_xyzi_message(3);
@@ -171,6 +165,42 @@ static void test_load_config(const char* tmpdir) {
     CHECK(!load_config(std::string(tmpdir) + "/nope.cfg", &c, &err));
 }
 
+// Every key load_config knows, line for line in the order of the grammar comment in merger_node.hpp, each with a minimal valid
+// line: behind a sensor line it loads, and without its last `drop` tokens (one, unless said) it is the bad line 2.
+static void test_every_config_key(const char* tmpdir) {
+    struct Row { const char* line; int drop = 1; };
+    static const Row rows[] = {
+        {"sensor b /b b_link optional"},
+        {"base_frame base_link"}, {"voxel_topic /voxels"}, {"rate_hz 20"}, {"leaf 0.05"}, {"min_points_per_voxel 3"},
+        {"crop -1 -2 -3 4 5 6"}, {"no_crop", 0} /* takes no value */, {"outlier 0.2 2"}, {"stamp_from_inputs 1"} /* one integer, any */,
+        {"max_points_total 123456"}, {"device 0"}, {"max_stamp_spread_ms 25"},
+        {"ground 500 0.2 0.9"}, {"zone a 0 10 0.5"},
+        {"ground_outlier 0.15 1"},
+        {"motion_compensation 1"}, {"time_field a 16 f32"},
+        {"statistical_outlier 8 1.5 0.25", 2} /* the third value is optional */,
+        {"cluster_tolerance 0.35"}, {"cluster_min_size 10"}, {"cluster_max_size 25000"},
+        {"cluster_box_angles 90"}, {"cluster_box_criterion area"}, {"cluster_box_d_min 0.05"},
+        {"grid_cell 0.25"}, {"grid_origin -20 -10.5"}, {"grid_size 160 84"}, {"grid_z_band -0.5 2.5"}, {"grid_obstacle_height 0.2"},
+        {"grid_min_points 3"},
+        {"grid_raycast 0"}, {"grid_min_pass 3"}, {"grid_ray_range 120"} /* one integer, any */,
+        {"normals_k 12"}, {"normals_viewpoint 1.5 -2 0.25"},
+        {"align_prev 1"}, {"align_max_corr 0.25"}, {"align_normals_k 12"}, {"align_max_iterations 5"},
+        {"align_method ndt"},
+    };
+    const std::string path = std::string(tmpdir) + "/keys.cfg", head = "sensor a /a a_link required\n";
+    NodeConfig c;
+    std::string err;
+    for (const Row& row : rows) {
+        std::string line = row.line;
+        CHECK(load_text(path, head + line + "\n", &c, &err));
+        if (row.drop == 0) continue;
+        for (int k = 0; k < row.drop; ++k) line.resize(line.rfind(' '));
+        CHECK(!load_text(path, head + line + "\n", &c, &err) && err.find(":2:") != std::string::npos);
+        if (err.find(":2:") == std::string::npos) std::printf("  '%s': %s\n", line.c_str(), err.c_str());
+    }
+    CHECK(!load_text(path, head + "no_such_key 1\n", &c, &err) && err.find(":2:") != std::string::npos);
+}
+
 static void test_node_without_gpu_fails_loudly(bool expect_gpu) {
     NodeConfig c = reference_config();
     c.max_points_total = 1000;
@@ -321,13 +351,13 @@ static void test_node_without_gpu_fails_loudly(bool expect_gpu) {
 }
 
 int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool expect_gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_find_xyzi();
-    test_pcd_roundtrip(tmpdir);
-    test_reference_config();
-    test_load_config(tmpdir);
-    test_node_without_gpu_fails_loudly(expect_gpu);
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
+    const bool expect_gpu = gpu_mode(argc, argv);
+    return run_tests(argc, argv, [expect_gpu](const char* tmpdir) {
+        test_find_xyzi();
+        test_pcd_roundtrip(tmpdir);
+        test_reference_config();
+        test_load_config(tmpdir);
+        test_every_config_key(tmpdir);
+        test_node_without_gpu_fails_loudly(expect_gpu);                    // (in both modes: without a GPU the node must say so)
+    }, [] {});
 }

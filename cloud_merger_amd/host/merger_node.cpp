@@ -89,10 +89,45 @@ NodeConfig fusion_config() {
     return c;
 }
 
+namespace {
+
+// load_config's line helpers. read: whether every value was extracted (what follows them on the line is ignored).
+template <class... T>
+bool read(std::istream& is, T&... v) { return static_cast<bool>((is >> ... >> v)); }
+
+bool read_flag(std::istream& is, bool* flag) {                          // the strict 0|1 keys
+    int v = 0;
+    if (!read(is, v) || (v != 0 && v != 1)) return false;
+    *flag = v == 1;
+    return true;
+}
+
+// the sensor of that name (the last one, should several carry it); c.sensors.size(): none
+size_t sensor_index(const NodeConfig& c, const std::string& name) {
+    size_t idx = c.sensors.size();
+    for (size_t q = 0; q < c.sensors.size(); ++q) if (c.sensors[q].name == name) idx = q;
+    return idx;
+}
+
+// CM_NODE_TRACE (a debugging aid): which of two calls of a slow tick took the time, written when the timer goes out of scope.
+struct SlowTick {
+    const char *first, *second;
+    double ms[2] = {0, 0};
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(int k) { const auto t1 = std::chrono::steady_clock::now(); ms[k] = std::chrono::duration<double, std::milli>(t1 - t0).count(); t0 = t1; }
+    ~SlowTick() {
+        static const bool trace = std::getenv("CM_NODE_TRACE") != nullptr;
+        if (trace && (ms[0] > 3 || ms[1] > 3)) std::fprintf(stderr, "[node] slow tick: %s %.2f %s %.2f ms\n", first, ms[0], second, ms[1]);
+    }
+};
+
+}  // namespace
+
 bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     std::ifstream f(path);
     if (!f) { if (err) *err = "cannot open " + path; return false; }
     NodeConfig c = reference_config();
+    cm_params& p = c.params;
     bool own_sensors = false, ground_z_from_crop = false;
     int lineno = 0;
     for (std::string line; std::getline(f, line);) {
@@ -106,88 +141,83 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         if (key == "sensor") {
             SensorSpec s;
             std::string req;
-            ok = static_cast<bool>(is >> s.name >> s.topic >> s.frame >> req) && (req == "required" || req == "optional");
+            ok = read(is, s.name, s.topic, s.frame, req) && (req == "required" || req == "optional");
             s.required = req == "required";
             if (ok) { if (!own_sensors) { c.sensors.clear(); own_sensors = true; } c.sensors.push_back(s); }
-        } else if (key == "base_frame") ok = static_cast<bool>(is >> c.base_frame);
-        else if (key == "voxel_topic") ok = static_cast<bool>(is >> c.voxel_topic);
-        else if (key == "rate_hz") ok = static_cast<bool>(is >> c.rate_hz) && c.rate_hz > 0;
-        else if (key == "leaf") { float v; ok = static_cast<bool>(is >> v) && v > 0; if (ok) c.params.leaf[0] = c.params.leaf[1] = c.params.leaf[2] = v; }
-        else if (key == "min_points_per_voxel") ok = static_cast<bool>(is >> c.params.min_points_per_voxel);
+        } else if (key == "base_frame") ok = read(is, c.base_frame);
+        else if (key == "voxel_topic") ok = read(is, c.voxel_topic);
+        else if (key == "rate_hz") ok = read(is, c.rate_hz) && c.rate_hz > 0;
+        else if (key == "leaf") { float v = 0; ok = read(is, v) && v > 0; if (ok) p.leaf[0] = p.leaf[1] = p.leaf[2] = v; }
+        else if (key == "min_points_per_voxel") ok = read(is, p.min_points_per_voxel);
         else if (key == "crop") {
-            ok = static_cast<bool>(is >> c.params.crop_min[0] >> c.params.crop_min[1] >> c.params.crop_min[2] >>
-                                   c.params.crop_max[0] >> c.params.crop_max[1] >> c.params.crop_max[2]);
-            c.params.crop_enable = 1;
-        } else if (key == "no_crop") c.params.crop_enable = 0;
-        else if (key == "outlier") { ok = static_cast<bool>(is >> c.params.outlier_radius >> c.params.outlier_min_neighbors); c.params.outlier_enable = 1; }
-        else if (key == "stamp_from_inputs") { int v; ok = static_cast<bool>(is >> v); c.stamp_from_inputs = v != 0; }
-        else if (key == "max_stamp_spread_ms") { double v; ok = static_cast<bool>(is >> v) && v >= 0; c.max_stamp_spread_ns = static_cast<uint64_t>(v * 1e6); }
+            ok = read(is, p.crop_min[0], p.crop_min[1], p.crop_min[2], p.crop_max[0], p.crop_max[1], p.crop_max[2]);
+            p.crop_enable = 1;
+        } else if (key == "no_crop") p.crop_enable = 0;
+        else if (key == "outlier") { ok = read(is, p.outlier_radius, p.outlier_min_neighbors); p.outlier_enable = 1; }
+        else if (key == "stamp_from_inputs") { int v = 0; ok = read(is, v); c.stamp_from_inputs = v != 0; }   // (any integer: not read_flag)
+        else if (key == "max_stamp_spread_ms") { double v = 0; ok = read(is, v) && v >= 0; if (ok) c.max_stamp_spread_ns = static_cast<uint64_t>(v * 1e6); }
         else if (key == "ground") {
-            ok = static_cast<bool>(is >> c.ground.max_iterations >> c.ground.distance_threshold >> c.ground.probability);
+            ok = read(is, c.ground.max_iterations, c.ground.distance_threshold, c.ground.probability);
             c.ground.optimize_coefficients = 1; c.ground.seed = 12345;
             ground_z_from_crop = true;                 // roi_z_max: taken from the crop box once the whole file is read
             c.ground_enable = true;
-        } else if (key == "ground_outlier") {
-            ok = static_cast<bool>(is >> c.ground.outlier_radius >> c.ground.outlier_min_neighbors) && c.ground.outlier_radius >= 0.0f;
-        } else if (key == "zone") {
+        } else if (key == "ground_outlier") ok = read(is, c.ground.outlier_radius, c.ground.outlier_min_neighbors) && c.ground.outlier_radius >= 0.0f;
+        else if (key == "zone") {
             std::string name; cm_zone z{};
-            ok = static_cast<bool>(is >> name >> z.x_min >> z.x_length >> z.z_max_ground);
-            size_t sidx = c.sensors.size();
-            for (size_t q = 0; q < c.sensors.size(); ++q) if (c.sensors[q].name == name) sidx = q;
+            ok = read(is, name, z.x_min, z.x_length, z.z_max_ground);
+            const size_t sidx = sensor_index(c, name);
             ok = ok && sidx < c.sensors.size() && c.ground.n_zones[sidx] < CM_MAX_ZONES;
             if (ok) c.ground.zones[sidx][c.ground.n_zones[sidx]++] = z;
-        }
-        else if (key == "statistical_outlier") {
+        } else if (key == "statistical_outlier") {
             cm_sor_params q{};
-            ok = static_cast<bool>(is >> q.mean_k >> q.std_mul) && q.mean_k >= 1 && q.mean_k <= CM_SOR_MAX_K;
+            ok = read(is, q.mean_k, q.std_mul) && q.mean_k >= 1 && q.mean_k <= CM_SOR_MAX_K;
             float cell = 0.0f;
-            if (ok && (is >> cell)) q.search_cell = cell;
+            if (ok && read(is, cell)) q.search_cell = cell;                 // (optional: a third token that is no number is ignored)
             ok = ok && q.search_cell >= 0.0f;
             if (ok) { c.sor = q; c.sor_enable = true; }
         }
-        else if (key == "cluster_tolerance") ok = static_cast<bool>(is >> c.cluster_tolerance) && c.cluster_tolerance >= 0.0f && std::isfinite(c.cluster_tolerance);
-        else if (key == "cluster_min_size") ok = static_cast<bool>(is >> c.cluster_min_size) && c.cluster_min_size >= 1;
-        else if (key == "cluster_max_size") ok = static_cast<bool>(is >> c.cluster_max_size) && c.cluster_max_size >= 1;
-        else if (key == "cluster_box_angles") ok = static_cast<bool>(is >> c.cluster_box_angles) && c.cluster_box_angles <= CM_BOX_MAX_ANGLES;
+        else if (key == "cluster_tolerance") ok = read(is, c.cluster_tolerance) && c.cluster_tolerance >= 0.0f && std::isfinite(c.cluster_tolerance);
+        else if (key == "cluster_min_size") ok = read(is, c.cluster_min_size) && c.cluster_min_size >= 1;
+        else if (key == "cluster_max_size") ok = read(is, c.cluster_max_size) && c.cluster_max_size >= 1;
+        else if (key == "cluster_box_angles") ok = read(is, c.cluster_box_angles) && c.cluster_box_angles <= CM_BOX_MAX_ANGLES;
         else if (key == "cluster_box_criterion") {
             std::string v;
-            ok = static_cast<bool>(is >> v) && (v == "area" || v == "closeness");
+            ok = read(is, v) && (v == "area" || v == "closeness");
             c.cluster_box_criterion = v == "area" ? CM_BOX_AREA : CM_BOX_CLOSENESS;
         }
-        else if (key == "cluster_box_d_min") ok = static_cast<bool>(is >> c.cluster_box_d_min) && c.cluster_box_d_min > 0.0f && std::isfinite(c.cluster_box_d_min);
-        else if (key == "grid_cell") ok = static_cast<bool>(is >> c.grid_cell) && std::isfinite(c.grid_cell) && c.grid_cell >= 0.0f &&
+        else if (key == "cluster_box_d_min") ok = read(is, c.cluster_box_d_min) && c.cluster_box_d_min > 0.0f && std::isfinite(c.cluster_box_d_min);
+        else if (key == "grid_cell") ok = read(is, c.grid_cell) && std::isfinite(c.grid_cell) && c.grid_cell >= 0.0f &&
                                           (c.grid_cell == 0.0f || std::isfinite(1.0f / c.grid_cell));
-        else if (key == "grid_origin") ok = static_cast<bool>(is >> c.grid_origin[0] >> c.grid_origin[1]) && std::isfinite(c.grid_origin[0]) && std::isfinite(c.grid_origin[1]);
-        else if (key == "grid_size") ok = static_cast<bool>(is >> c.grid_nx >> c.grid_ny) && c.grid_nx >= 1 && c.grid_ny >= 1 &&
+        else if (key == "grid_origin") ok = read(is, c.grid_origin[0], c.grid_origin[1]) && std::isfinite(c.grid_origin[0]) && std::isfinite(c.grid_origin[1]);
+        else if (key == "grid_size") ok = read(is, c.grid_nx, c.grid_ny) && c.grid_nx >= 1 && c.grid_ny >= 1 &&
                                           static_cast<uint64_t>(c.grid_nx) * c.grid_ny <= CM_GRID_MAX_CELLS;
-        else if (key == "grid_z_band") ok = static_cast<bool>(is >> c.grid_z_band[0] >> c.grid_z_band[1]) && c.grid_z_band[0] <= c.grid_z_band[1];
-        else if (key == "grid_obstacle_height") ok = static_cast<bool>(is >> c.grid_obstacle_height) && std::isfinite(c.grid_obstacle_height) && c.grid_obstacle_height >= 0.0f;
-        else if (key == "grid_min_points") ok = static_cast<bool>(is >> c.grid_min_points) && c.grid_min_points >= 1;
-        else if (key == "grid_raycast") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.grid_raycast = v == 1; }
-        else if (key == "grid_min_pass") ok = static_cast<bool>(is >> c.grid_min_pass) && c.grid_min_pass >= 1;
-        else if (key == "grid_ray_range") ok = static_cast<bool>(is >> c.grid_ray_range);
-        else if (key == "normals_k") ok = static_cast<bool>(is >> c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
-        else if (key == "align_prev") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.align_prev = v == 1; }
-        else if (key == "align_max_corr") ok = static_cast<bool>(is >> c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
-        else if (key == "align_normals_k") ok = static_cast<bool>(is >> c.align_normals_k) && c.align_normals_k >= 3 && c.align_normals_k <= CM_NORMAL_MAX_K;
-        else if (key == "align_max_iterations") ok = static_cast<bool>(is >> c.align_max_iterations) && c.align_max_iterations <= CM_ALIGN_MAX_ITER;
-        else if (key == "align_method") ok = static_cast<bool>(is >> c.align_method) && (c.align_method == "icp" || c.align_method == "ndt");
+        else if (key == "grid_z_band") ok = read(is, c.grid_z_band[0], c.grid_z_band[1]) && c.grid_z_band[0] <= c.grid_z_band[1];
+        else if (key == "grid_obstacle_height") ok = read(is, c.grid_obstacle_height) && std::isfinite(c.grid_obstacle_height) && c.grid_obstacle_height >= 0.0f;
+        else if (key == "grid_min_points") ok = read(is, c.grid_min_points) && c.grid_min_points >= 1;
+        else if (key == "grid_raycast") ok = read_flag(is, &c.grid_raycast);
+        else if (key == "grid_min_pass") ok = read(is, c.grid_min_pass) && c.grid_min_pass >= 1;
+        else if (key == "grid_ray_range") ok = read(is, c.grid_ray_range);
+        else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
-            ok = static_cast<bool>(is >> v[0] >> v[1] >> v[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
+            ok = read(is, v[0], v[1], v[2]) && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]);
         }
-        else if (key == "motion_compensation") { int v; ok = static_cast<bool>(is >> v) && (v == 0 || v == 1); c.motion_compensation = v == 1; }
+        else if (key == "align_prev") ok = read_flag(is, &c.align_prev);
+        else if (key == "align_max_corr") ok = read(is, c.align_max_corr) && c.align_max_corr > 0.0f && std::isfinite(c.align_max_corr);
+        else if (key == "align_normals_k") ok = read(is, c.align_normals_k) && c.align_normals_k >= 3 && c.align_normals_k <= CM_NORMAL_MAX_K;
+        else if (key == "align_max_iterations") ok = read(is, c.align_max_iterations) && c.align_max_iterations <= CM_ALIGN_MAX_ITER;
+        else if (key == "align_method") ok = read(is, c.align_method) && (c.align_method == "icp" || c.align_method == "ndt");
+        else if (key == "motion_compensation") ok = read_flag(is, &c.motion_compensation);
         else if (key == "time_field") {
             std::string name, type;
             uint32_t off = 0;
-            ok = static_cast<bool>(is >> name >> off >> type) && (type == "f32" || type == "u32ns");
-            size_t sidx = c.sensors.size();
-            for (size_t q = 0; q < c.sensors.size(); ++q) if (c.sensors[q].name == name) sidx = q;
+            ok = read(is, name, off, type) && (type == "f32" || type == "u32ns");
+            const size_t sidx = sensor_index(c, name);
             ok = ok && sidx < c.sensors.size();
             if (ok) c.time_field[sidx] = NodeConfig::TimeField{off, type == "f32" ? CM_TIME_F32_S : CM_TIME_U32_NS};
         }
-        else if (key == "max_points_total") ok = static_cast<bool>(is >> c.max_points_total);
-        else if (key == "device") ok = static_cast<bool>(is >> c.device);
+        else if (key == "max_points_total") ok = read(is, c.max_points_total);
+        else if (key == "device") ok = read(is, c.device);
         else ok = false;
         if (!ok) { if (err) *err = path + ":" + std::to_string(lineno) + ": bad line"; return false; }
     }
@@ -229,34 +259,20 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     lim.max_sensors = static_cast<uint32_t>(cfg_.sensors.size());
     lim.flags = cfg_.flags;
     lim.max_points_total = cfg_.max_points_total;
+    auto refuse = [this](const char* what) {                            // a set-up call failed: its reason, and no context
+        error_ = std::string(what) + ": " + cm_last_error(ctx_);
+        cm_destroy(ctx_);
+        ctx_ = nullptr;
+    };
     const int st = cm_create(&ctx_, cfg_.device, &lim);
     if (st != CM_OK) {
         ctx_ = nullptr;
         error_ = std::string("cm_create: ") + cm_status_string(st);
-    } else if (cfg_.ground_enable) {
-        const int gs = cm_set_ground_removal(ctx_, &cfg_.ground);
-        if (gs != CM_OK) {
-            error_ = std::string("cm_set_ground_removal: ") + cm_last_error(ctx_);
-            cm_destroy(ctx_);
-            ctx_ = nullptr;
-        }
-    }
-    if (ctx_ && cfg_.sor_enable) {
-        const int ss = cm_set_statistical_outlier(ctx_, &cfg_.sor);
-        if (ss != CM_OK) {
-            error_ = std::string("cm_set_statistical_outlier: ") + cm_last_error(ctx_);
-            cm_destroy(ctx_);
-            ctx_ = nullptr;
-        }
-    }
-    for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s) {
-        const int ts = cm_set_sensor_time_field(ctx_, static_cast<uint32_t>(s), cfg_.time_field[s].offset, cfg_.time_field[s].type);
-        if (ts != CM_OK) {
-            error_ = std::string("cm_set_sensor_time_field: ") + cm_last_error(ctx_);
-            cm_destroy(ctx_);
-            ctx_ = nullptr;
-        }
-    }
+    } else if (cfg_.ground_enable && cm_set_ground_removal(ctx_, &cfg_.ground) != CM_OK) refuse("cm_set_ground_removal");
+    if (ctx_ && cfg_.sor_enable && cm_set_statistical_outlier(ctx_, &cfg_.sor) != CM_OK) refuse("cm_set_statistical_outlier");
+    for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s)
+        if (cm_set_sensor_time_field(ctx_, static_cast<uint32_t>(s), cfg_.time_field[s].offset, cfg_.time_field[s].type) != CM_OK)
+            refuse("cm_set_sensor_time_field");
     clock_ = [] {
         return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(
             std::chrono::system_clock::now().time_since_epoch()).count());
@@ -385,14 +401,17 @@ int CloudMergerNode::align_of_frame(const cm_result& r) {
     has_alignment_ = false;
     if (!cfg_.align_prev) return CM_OK;
     if (r.status != CM_OK) { prev_records_.clear(); return CM_OK; }
-    if (!prev_records_.empty() && cfg_.align_method == "ndt") {
-        cm_ndt_params q{};
-        q.outlier_ratio = 0.55f;
-        q.neighborhood = 7;
+    auto common = [this](auto& q) {                                     // what both matchers take; the guess is the identity
         q.max_iterations = cfg_.align_max_iterations;
         q.min_correspondences = 6;
         q.trans_eps = q.rot_eps = 1e-6;
         q.guess[0] = q.guess[5] = q.guess[10] = 1.0;
+    };
+    if (!prev_records_.empty() && cfg_.align_method == "ndt") {
+        cm_ndt_params q{};
+        q.outlier_ratio = 0.55f;
+        q.neighborhood = 7;
+        common(q);
         const int st = cm_result_ndt_align(ctx_, &q, prev_records_.data(), prev_records_.size() / 4, &ndt_alignment_);
         if (st != CM_OK) { set_error(cm_last_error(ctx_)); return st; }
         const cm_ndt_result& n = ndt_alignment_;
@@ -408,11 +427,8 @@ int CloudMergerNode::align_of_frame(const cm_result& r) {
     } else if (!prev_records_.empty()) {
         cm_align_params q{};
         q.max_corr_dist = cfg_.align_max_corr;
-        q.max_iterations = cfg_.align_max_iterations;
         q.normals_k = cfg_.align_normals_k;
-        q.min_correspondences = 6;
-        q.trans_eps = q.rot_eps = 1e-6;
-        q.guess[0] = q.guess[5] = q.guess[10] = 1.0;
+        common(q);
         const int st = cm_result_align(ctx_, &q, prev_records_.data(), prev_records_.size() / 4, &alignment_);
         if (st != CM_OK) { set_error(cm_last_error(ctx_)); return st; }
         has_alignment_ = true;
@@ -438,29 +454,66 @@ void CloudMergerNode::flush_published() {
     frames_.fetch_add(1);
 }
 
-void CloudMergerNode::flush() {
-    if (frame_pending_ && ctx_) {                                       // deferred_wait: the frame enqueued by the last spin_once
-        flush_published();
-        frame_pending_ = false;
-        (void)collect_and_publish_async(nullptr);
-    }
+// deferred_wait: the frame enqueued by the last spin_once, if any — the one before it goes out, this one is waited for.
+int CloudMergerNode::collect_pending(cm_result* res) {
+    if (!frame_pending_ || !ctx_) return CM_OK;
     flush_published();
+    frame_pending_ = false;
+    return collect_and_publish_async(res);
+}
+
+void CloudMergerNode::flush() {
+    (void)collect_pending(nullptr);
+    flush_published();
+}
+
+// After a successful wait, on either path: the path counters, the by-products (the first to fail ends the tick), the generations.
+int CloudMergerNode::after_wait(const cm_result& r) {
+    if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
+    if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
+    int st = clusters_of_frame(r);
+    if (st == CM_OK) st = grid_of_frame(r);
+    if (st == CM_OK) st = normals_of_frame(r);
+    if (st == CM_OK) st = align_of_frame(r);
+    if (st != CM_OK) return st;
+    // flag reset, :151-157 — for exactly the clouds this fuse read: a callback may have delivered the next one since
+    cm_frame_stats fs;
+    if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
+        for (uint32_t k = 0; k < fs.n_sensors; ++k)
+            if (fs.sensor[k] < consumed_.size()) consumed_[fs.sensor[k]].store(fs.generation[k]);
+    return CM_OK;
+}
+
+// publishPointcloud, voxel leg (:215-219): the configured layout and the frame's shape; the payload is the caller's to fill.
+void CloudMergerNode::shape_message(PointCloud2& msg, const cm_result& r, int st) {
+    const bool pcl = cfg_.publish_pcl_layout;
+    if (msg.fields.empty() || msg.point_step != (pcl ? 32u : 16u)) msg = pcl ? make_pcl_xyzi_message(0) : make_xyzi16_message(0);
+    msg.height = 1; msg.width = static_cast<uint32_t>(r.n_out);
+    msg.row_step = msg.point_step * msg.width;
+    msg.data.resize(static_cast<size_t>(r.n_out) * msg.point_step);    // (capacity is kept: no zero-fill in steady state)
+    if (st == CM_EMPTY_INPUT) { msg.width = 0; msg.height = 0; msg.row_step = 0; }   // A.4 step 1
+}
+
+// ... its header (:217-218). input_stamp: the newest stamp among the clouds the frame fused — each path reads it at its own moment.
+void CloudMergerNode::stamp_message(PointCloud2& msg, uint64_t input_stamp) {
+    msg.header.seq = seq_++;
+    msg.header.stamp_ns = cfg_.motion_compensation ? motion_t_ref_ : (cfg_.stamp_from_inputs && input_stamp) ? input_stamp : clock_();
+    msg.header.frame_id = cfg_.base_frame;
 }
 
 // spin_once with NodeConfig::pipelined_publish: enqueue frame n; while it computes, finish and publish frame n - 1; wait
 // for frame n; start its copy-out (cm_result_publish_async: a stream of its own, double-buffered result) and return.
 int CloudMergerNode::spin_once_pipelined(cm_result* res) {
-    static const bool trace = std::getenv("CM_NODE_TRACE") != nullptr;  // (debugging aid: which call of a slow tick took the time)
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(now() - t0).count(); };
-    auto t0 = now();
-    const uint64_t stamp_enq = newest_stamp();                          // (of the clouds this fuse reads: a callback may deliver the next ones before the wait)
-    const int eq = enqueue_frame(false, nullptr);                       // fusePointclouds + voxelgrid, enqueued
-    if (eq == CM_OK) enq_stamp_ = stamp_enq;
-    const double t_enq = since(t0); t0 = now();
-    flush_published();                                                  // frame n - 1 goes out while frame n runs
-    const double t_flush = since(t0);
-    if (trace && (t_enq > 3 || t_flush > 3)) std::fprintf(stderr, "[node] slow tick: enqueue %.2f flush %.2f ms\n", t_enq, t_flush);
+    int eq;
+    {
+        SlowTick tick{"enqueue", "flush"};
+        const uint64_t stamp_enq = newest_stamp();                      // (of the clouds this fuse reads: a callback may deliver the next ones before the wait)
+        eq = enqueue_frame(false, nullptr);                             // fusePointclouds + voxelgrid, enqueued
+        if (eq == CM_OK) enq_stamp_ = stamp_enq;
+        tick.lap(0);
+        flush_published();                                              // frame n - 1 goes out while frame n runs
+        tick.lap(1);
+    }
     if (res) *res = cm_result{};
     if (eq == CM_NOT_READY) return eq;                                  // :575 — nothing fused this tick
     if (eq < 0) { set_error(cm_last_error(ctx_)); return eq; }
@@ -474,13 +527,8 @@ int CloudMergerNode::spin_once_pipelined(cm_result* res) {
 // CM_NOT_READY, as always); `res` is the PREVIOUS frame's result (zero when there was none to wait for).
 int CloudMergerNode::spin_once_deferred(cm_result* res) {
     if (res) *res = cm_result{};
-    int st_prev = CM_OK;
-    if (frame_pending_) {
-        flush_published();                                              // frame n - 2 goes out
-        frame_pending_ = false;
-        st_prev = collect_and_publish_async(res);                       // frame n - 1: waited for, copy-out started
-        if (st_prev < 0) return st_prev;
-    }
+    const int st_prev = collect_pending(res);                           // frame n - 2 goes out; frame n - 1: waited for, copy-out started
+    if (st_prev < 0) return st_prev;
     const uint64_t stamp_enq = newest_stamp();
     const int eq = enqueue_frame(false, nullptr);                       // frame n: enqueued, not waited for
     if (eq == CM_OK) { frame_pending_ = true; enq_stamp_ = stamp_enq; }
@@ -488,36 +536,17 @@ int CloudMergerNode::spin_once_deferred(cm_result* res) {
     return eq;                                                          // CM_OK: a frame was fused this tick; CM_NOT_READY: none (:575)
 }
 
-// The frame in flight on the context: cm_wait, the consumed generations, its message, the start of its copy-out.
+// The frame in flight on the context: cm_wait, the by-products, its message, the start of its copy-out.
 int CloudMergerNode::collect_and_publish_async(cm_result* res) {
-    static const bool trace = std::getenv("CM_NODE_TRACE") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(now() - t0).count(); };
-    auto t0 = now();
-    struct Report { bool on; double* w; double* p;
-                    ~Report() { if (on && (*w > 3 || *p > 3)) std::fprintf(stderr, "[node] slow tick: wait %.2f publish %.2f ms\n", *w, *p); } };
-    double t_wait = 0, t_pub = 0;
-    Report rep{trace, &t_wait, &t_pub};
+    SlowTick tick{"wait", "publish"};
     cm_result r{};
     const int st = cm_wait(ctx_, &r);
-    t_wait = since(t0); t0 = now();
+    tick.lap(0);
     if (res) *res = r;
     if (st < 0) { set_error(cm_last_error(ctx_)); return st; }
-    if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
-    if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
-    { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
-    { const int gs = grid_of_frame(r); if (gs != CM_OK) return gs; }
-    { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
-    { const int as = align_of_frame(r); if (as != CM_OK) return as; }
-    {
-        cm_frame_stats fs;
-        if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
-            for (uint32_t k = 0; k < fs.n_sensors; ++k)
-                if (fs.sensor[k] < consumed_.size()) consumed_[fs.sensor[k]].store(fs.generation[k]);
-    }
+    { const int bs = after_wait(r); if (bs != CM_OK) return bs; }
     PointCloud2& msg = pipe_msg_[pipe_cur_];
-    const bool pcl = cfg_.publish_pcl_layout;
-    if (msg.fields.empty() || msg.point_step != (pcl ? 32u : 16u)) msg = pcl ? make_pcl_xyzi_message(0) : make_xyzi16_message(0);
+    shape_message(msg, r, st);
     // The payload buffer is reserved once at the largest cloud the context can produce and made DMA-able: the copy-out
     // then is a true asynchronous transfer straight into the message that goes on the wire.
     const size_t cap_bytes = static_cast<size_t>(cfg_.max_points_total) * msg.point_step;
@@ -526,21 +555,16 @@ int CloudMergerNode::collect_and_publish_async(cm_result* res) {
         msg.data.resize(cap_bytes);                                     // (every page touched once before it is pinned)
         msg.data.resize(1);                                             // (capacity stays; data() of an empty vector need not be its buffer)
         if (cm_host_register(msg.data.data(), cap_bytes) == CM_OK) pipe_registered_[pipe_cur_] = msg.data.data();
+        msg.data.resize(static_cast<size_t>(r.n_out) * msg.point_step); // (the frame's size again, within the reserved capacity: the buffer stays put)
     }
-    msg.height = 1; msg.width = static_cast<uint32_t>(r.n_out);
-    msg.row_step = msg.point_step * msg.width;
-    msg.data.resize(static_cast<size_t>(r.n_out) * msg.point_step);    // (within the reserved capacity: the buffer stays put)
-    if (st == CM_EMPTY_INPUT) { msg.width = 0; msg.height = 0; msg.row_step = 0; }   // A.4 step 1
     if (r.n_out) {
         const int cs = cm_result_publish_async(ctx_, msg.data.data(), r.n_out, msg.point_step);
         if (cs != CM_OK) { set_error(cm_last_error(ctx_)); return cs; }
     }
-    msg.header.seq = seq_++;
-    msg.header.stamp_ns = cfg_.motion_compensation ? motion_t_ref_ : (cfg_.stamp_from_inputs && enq_stamp_) ? enq_stamp_ : clock_();
-    msg.header.frame_id = cfg_.base_frame;
+    stamp_message(msg, enq_stamp_);                                     // (read at enqueue: a callback may have delivered since)
     pipe_in_flight_ = true;
     pipe_cur_ ^= 1;
-    t_pub = since(t0);
+    tick.lap(1);
     return st;
 }
 
@@ -607,38 +631,13 @@ int CloudMergerNode::spin_once(cm_result* res) {
     if (res) *res = r;
     if (st == CM_NOT_READY) return st;                              // :575 — nothing fused this tick
     if (st < 0) { set_error(cm_last_error(ctx_)); return st; }
-    if (r.path_flags & CM_PATH_QUANTILE) n_quantile_.fetch_add(1);
-    if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
-    { const int cs = clusters_of_frame(r); if (cs != CM_OK) return cs; }
-    { const int gs = grid_of_frame(r); if (gs != CM_OK) return gs; }
-    { const int ns = normals_of_frame(r); if (ns != CM_OK) return ns; }
-    { const int as = align_of_frame(r); if (as != CM_OK) return as; }
-    {
-        // flag reset, :151-157 — for exactly the clouds this fuse read: a callback may have delivered the next one since
-        cm_frame_stats fs;
-        if (cm_get_frame_stats(ctx_, &fs) == CM_OK)
-            for (uint32_t k = 0; k < fs.n_sensors; ++k)
-                if (fs.sensor[k] < consumed_.size()) consumed_[fs.sensor[k]].store(fs.generation[k]);
-    }
-    // publishPointcloud, voxel leg (:215-219): PCL layout, stamp = now, frame = base_footprint.
-    PointCloud2& msg = out_msg_;
-    {
-        const bool pcl = cfg_.publish_pcl_layout;
-        if (msg.fields.empty() || msg.point_step != (pcl ? 32u : 16u)) msg = pcl ? make_pcl_xyzi_message(0) : make_xyzi16_message(0);
-        msg.height = 1; msg.width = static_cast<uint32_t>(r.n_out);
-        msg.row_step = msg.point_step * msg.width;
-        msg.data.resize(static_cast<size_t>(r.n_out) * msg.point_step);    // (capacity is kept: no zero-fill in steady state)
-    }
-    if (st == CM_EMPTY_INPUT) { msg.width = 0; msg.height = 0; msg.row_step = 0; }   // A.4 step 1
+    { const int bs = after_wait(r); if (bs != CM_OK) return bs; }
+    shape_message(out_msg_, r, st);
     if (r.n_out) {
-        const int cs = cm_result_copy(ctx_, msg.data.data(), r.n_out, msg.point_step);
+        const int cs = cm_result_copy(ctx_, out_msg_.data.data(), r.n_out, out_msg_.point_step);
         if (cs != CM_OK) { set_error(cm_last_error(ctx_)); return cs; }
     }
-    msg.header.seq = seq_++;
-    uint64_t newest = 0;
-    for (const auto& t : stamp_ns_) newest = std::max(newest, t.load());
-    msg.header.stamp_ns = cfg_.motion_compensation ? motion_t_ref_ : (cfg_.stamp_from_inputs && newest) ? newest : clock_();
-    msg.header.frame_id = cfg_.base_frame;
+    stamp_message(out_msg_, newest_stamp());                             // (read after the wait: stamp = now without stamp_from_inputs, :217)
     if (cfg_.ground_enable && publish_ && st != CM_EMPTY_INPUT) {
         // publishPointcloud's other two legs (:203-213): the fused no-ground and ground clouds
         for (int leg = 0; leg < 2; ++leg) {
@@ -650,11 +649,11 @@ int CloudMergerNode::spin_once(cm_result* res) {
             if (cs != CM_OK) { set_error(cm_last_error(ctx_)); return cs; }
             m2.width = static_cast<uint32_t>(n); m2.height = n ? 1 : 0; m2.row_step = static_cast<uint32_t>(n) * m2.point_step;
             m2.data.resize(static_cast<size_t>(n) * m2.point_step);
-            m2.header = msg.header;
+            m2.header = out_msg_.header;
             publish_(leg == 0 ? cfg_.no_ground_topic : cfg_.ground_topic, m2);
         }
     }
-    if (publish_) publish_(cfg_.voxel_topic, msg);
+    if (publish_) publish_(cfg_.voxel_topic, out_msg_);
     frames_.fetch_add(1);
     return st;
 }

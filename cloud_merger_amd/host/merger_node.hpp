@@ -128,7 +128,7 @@ struct NodeConfig {
 // of the reference's string literals). Lines, '#' comments allowed:
 //   sensor <name> <topic> <tf_frame> <required|optional>
 //   base_frame <id> | voxel_topic <topic> | rate_hz <v> | leaf <v> | min_points_per_voxel <n>
-//   crop <x0> <y0> <z0> <x1> <y1> <z1> | outlier <radius> <min_neighbors> | stamp_from_inputs <0|1>
+//   crop <x0> <y0> <z0> <x1> <y1> <z1> | no_crop | outlier <radius> <min_neighbors> | stamp_from_inputs <0|1>
 //   max_points_total <n> | device <n> | max_stamp_spread_ms <v>
 //   ground <max_iterations> <distance_threshold> <probability> | zone <sensor_name> <x_min> <x_length> <z_max_ground>
 //   ground_outlier <radius> <min_neighbors>   (removeGround's outlierRemoval on every slab's band points, :119)
@@ -256,8 +256,13 @@ private:
     uint64_t newest_stamp() const;
     void flush_published();
     int spin_once_deferred(cm_result* res);
+    int collect_pending(cm_result* res);
     int collect_and_publish_async(cm_result* res);
     int spin_once_pipelined(cm_result* res);
+    // what both paths do once a frame has been waited for, and to its message
+    int after_wait(const cm_result& r);
+    void shape_message(PointCloud2& msg, const cm_result& r, int st);
+    void stamp_message(PointCloud2& msg, uint64_t input_stamp);
     std::vector<std::atomic<uint64_t>> stamp_ns_;   // stamp of the cloud each sensor slot currently holds
     // A slot holds a cloud no fuse has consumed yet when more submits were accepted for it than the last fuse had seen
     // (cm_frame_stats.generation): exact, whichever way a callback and the fuse interleave.

@@ -3,24 +3,10 @@
 //   motion_tests <tmpdir> [gpu]
 #include <algorithm>
 #include <array>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
 
-#include "merger_node.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
-
-static bool load_text(const std::string& path, const std::string& text, NodeConfig* c, std::string* err) {
-    std::ofstream(path) << text;
-    return load_config(path, c, err);
-}
 
 static void test_config_keys(const char* tmpdir) {
     const std::string path = std::string(tmpdir) + "/motion.cfg";
@@ -117,11 +103,4 @@ static void test_node_on_gpu() {
     CHECK(got.size() == want.size() && std::memcmp(got.data(), want.data(), want.size() * 16) == 0);   // one point per voxel
 }
 
-int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_config_keys(tmpdir);
-    if (gpu) test_node_on_gpu();
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
-}
+int main(int argc, char** argv) { return run_tests(argc, argv, test_config_keys, test_node_on_gpu); }

@@ -2,24 +2,9 @@
 // start-up refusal (CPU) and, with "gpu", one node that sees a three-plane corner twice, the second time moved by a known
 // rigid motion, and reports that motion.
 //   ndt_tests <tmpdir> [gpu]
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "merger_node.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
-
-static bool load_text(const std::string& path, const std::string& text, NodeConfig* c, std::string* err) {
-    std::ofstream(path) << text;
-    return load_config(path, c, err);
-}
 
 static void test_config_keys(const char* tmpdir) {
     const std::string path = std::string(tmpdir) + "/ndt.cfg";
@@ -54,33 +39,8 @@ static void test_config_keys(const char* tmpdir) {
     }
 }
 
-// The corner x = 0, y = 0, z = 0 over [0, 4]^2 on a lattice of `step`, phase `ph`, each plane rippled by 1 cm (a perfectly
-// flat voxel has lambda_0 = 0 up to rounding, and the covariance table calls the ones that round below 0 invalid), moved by
-// the rotation `rz` (radians about z through (2, 2, 2)) and the shift (sx, sy, sz).
-static std::vector<float> corner(double step, double ph, double rz, double sx, double sy, double sz) {
-    std::vector<float> pts;
-    const double c = std::cos(rz), s = std::sin(rz);
-    for (int axis = 0; axis < 3; ++axis)
-        for (double u = ph; u < 4.0; u += step)
-            for (double v = ph; v < 4.0; v += step) {
-                double p[3];
-                p[axis] = 0.01 * std::sin(13.7 * u + 7.1 * v + axis); p[(axis + 1) % 3] = u; p[(axis + 2) % 3] = v;
-                const double x = p[0] - 2.0, y = p[1] - 2.0;
-                const float q[4] = {static_cast<float>(c * x - s * y + 2.0 + sx), static_cast<float>(s * x + c * y + 2.0 + sy),
-                                    static_cast<float>(p[2] + sz), 1.0f};
-                pts.insert(pts.end(), q, q + 4);
-            }
-    return pts;
-}
-
 static void test_node_on_gpu() {
-    NodeConfig c = reference_config();
-    c.sensors = {{"a", "/a", "a_link", true}};
-    c.params.crop_enable = 0;
-    c.params.min_points_per_voxel = 0;
-    c.params.leaf[0] = c.params.leaf[1] = c.params.leaf[2] = 0.5f;
-    c.publish_pcl_layout = false;
-    c.max_points_total = 40000;
+    NodeConfig c = single_sensor_config(0.5f, 40000);
     c.align_prev = true;
     c.align_method = "ndt";
     c.flags |= CM_FLAG_OCCUPANCY;
@@ -93,9 +53,8 @@ static void test_node_on_gpu() {
     const double rz = 0.03, sh[3] = {0.06, -0.04, 0.05};
     cm_result r{};
     for (int frame = 0; frame < 2; ++frame) {
-        const std::vector<float> pts = frame == 0 ? corner(0.037, 0.011, 0.0, 0.0, 0.0, 0.0) : corner(0.041, 0.017, rz, sh[0], sh[1], sh[2]);
-        PointCloud2 m = make_xyzi16_message(static_cast<int>(pts.size() / 4));
-        std::memcpy(m.data.data(), pts.data(), pts.size() * 4);
+        const std::vector<float> pts = frame == 0 ? corner(0.037, 0.011, 0.0, 0.0, 0.0, 0.0, 0.01) : corner(0.041, 0.017, rz, sh[0], sh[1], sh[2], 0.01);   // rippled by 1 cm
+        PointCloud2 m = xyzi_message(pts);
         CHECK(node.on_cloud(0, m) == CM_OK);
         CHECK(node.spin_once(&r) == CM_OK);
         CHECK(r.n_out > 150 && r.n_out < 400);
@@ -120,11 +79,4 @@ static void test_node_on_gpu() {
     CHECK(node.has_alignment());
 }
 
-int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_config_keys(tmpdir);
-    if (gpu) test_node_on_gpu();
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
-}
+int main(int argc, char** argv) { return run_tests(argc, argv, test_config_keys, test_node_on_gpu); }

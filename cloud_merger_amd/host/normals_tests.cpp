@@ -1,24 +1,9 @@
 // normals_tests.cpp — the host shell's normal estimation: NodeConfig keys (CPU) and, with "gpu", one node whose voxel cloud
 // is a tilted plane beside a short line, checked against the plane's known normal.
 //   normals_tests <tmpdir> [gpu]
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "merger_node.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
-
-static bool load_text(const std::string& path, const std::string& text, NodeConfig* c, std::string* err) {
-    std::ofstream(path) << text;
-    return load_config(path, c, err);
-}
 
 static void test_config_keys(const char* tmpdir) {
     const std::string path = std::string(tmpdir) + "/normals.cfg";
@@ -43,13 +28,7 @@ static void test_config_keys(const char* tmpdir) {
 }
 
 static void test_node_on_gpu() {
-    NodeConfig c = reference_config();
-    c.sensors = {{"a", "/a", "a_link", true}};
-    c.params.crop_enable = 0;
-    c.params.min_points_per_voxel = 0;
-    c.params.leaf[0] = c.params.leaf[1] = c.params.leaf[2] = 0.125f;
-    c.publish_pcl_layout = false;
-    c.max_points_total = 1000;
+    NodeConfig c = single_sensor_config(0.125f, 1000);
     c.normals_k = 9;
     c.normals_viewpoint[0] = 0.0f; c.normals_viewpoint[1] = 0.0f; c.normals_viewpoint[2] = 50.0f;
     CloudMergerNode node(c);
@@ -64,8 +43,7 @@ static void test_node_on_gpu() {
         for (int j = 0; j < 20; ++j) { const float p[4] = {0.5f * i, 0.5f * j, 0.25f * i, 1.0f}; pts.insert(pts.end(), p, p + 4); }
     for (int j = 0; j < 12; ++j) { const float p[4] = {100.0f, 0.5f * j, 0.0f, 1.0f}; pts.insert(pts.end(), p, p + 4); }
     const int n = static_cast<int>(pts.size() / 4);
-    PointCloud2 m = make_xyzi16_message(n);
-    std::memcpy(m.data.data(), pts.data(), pts.size() * 4);
+    PointCloud2 m = xyzi_message(pts);
     std::vector<float> out;
     node.set_publisher([&](const std::string&, const PointCloud2& o) {
         out.resize(o.num_points() * 4);
@@ -99,11 +77,4 @@ static void test_node_on_gpu() {
     CHECK(node.normals().size() == static_cast<size_t>(n));
 }
 
-int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_config_keys(tmpdir);
-    if (gpu) test_node_on_gpu();
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
-}
+int main(int argc, char** argv) { return run_tests(argc, argv, test_config_keys, test_node_on_gpu); }

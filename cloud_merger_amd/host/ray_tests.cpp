@@ -2,24 +2,9 @@
 // cell (0, 0) of a 6 x 4 grid and sees two poles and a lone point, checked against known cells and against what the library
 // returns for the same frame.
 //   ray_tests <tmpdir> [gpu]
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-#include "merger_node.hpp"
+#include "test_support.hpp"
 
 using namespace cloudmerge;
-
-static int failures = 0;
-#define CHECK(cond) do { if (!(cond)) { std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond); ++failures; } } while (0)
-
-static bool load_text(const std::string& path, const std::string& text, NodeConfig* c, std::string* err) {
-    std::ofstream(path) << text;
-    return load_config(path, c, err);
-}
 
 static void test_config_keys(const char* tmpdir) {
     const std::string path = std::string(tmpdir) + "/rays.cfg";
@@ -52,13 +37,7 @@ static void test_config_keys(const char* tmpdir) {
 }
 
 static void test_node_on_gpu() {
-    NodeConfig c = reference_config();
-    c.sensors = {{"a", "/a", "a_link", true}};
-    c.params.crop_enable = 0;
-    c.params.min_points_per_voxel = 0;
-    c.params.leaf[0] = c.params.leaf[1] = c.params.leaf[2] = 0.125f;
-    c.publish_pcl_layout = false;
-    c.max_points_total = 1000;
+    NodeConfig c = single_sensor_config(0.125f, 1000);
     c.grid_cell = 0.5f;
     c.grid_origin[0] = -1.0f;
     c.grid_origin[1] = -1.0f;
@@ -73,23 +52,9 @@ static void test_node_on_gpu() {
     // the sensor at (-0.75, -0.75): cell (0, 0)
     const double q[4] = {0, 0, 0, 1}, t[3] = {-0.75, -0.75, 0};
     node.set_transform(0, q, t);
-    // in the sensor's frame (the base frame is 0.75 less on x and y): a pole of 5 points in cell (4, 0), one of 3 points in cell
-    // (2, 0) on the way to it, a lone point in cell (2, 1), one point outside the grid
-    std::vector<float> pts;
-    for (int i = 0; i < 5; ++i) {
-        const float p[4] = {2.0f, 0.0f, 0.25f * static_cast<float>(i), 1.0f};
-        pts.insert(pts.end(), p, p + 4);
-    }
-    for (int i = 0; i < 3; ++i) {
-        const float p[4] = {1.0f, 0.0f, 0.5f * static_cast<float>(i), 2.0f};
-        pts.insert(pts.end(), p, p + 4);
-    }
-    const float lone[4] = {1.0f, 0.5f, 0.1f, 3.0f}, outside[4] = {3.0f, 0.0f, 0.5f, 4.0f};
-    pts.insert(pts.end(), lone, lone + 4);
-    pts.insert(pts.end(), outside, outside + 4);
+    const std::vector<float> pts = ray_scene();
     const int n = static_cast<int>(pts.size() / 4);
-    PointCloud2 m = make_xyzi16_message(n);
-    std::memcpy(m.data.data(), pts.data(), pts.size() * 4);
+    PointCloud2 m = xyzi_message(pts);
     CHECK(node.on_cloud(0, m) == CM_OK);
     cm_result r{};
     CHECK(node.spin_once(&r) == CM_OK);
@@ -140,11 +105,4 @@ static void test_node_on_gpu() {
     CHECK(node.grid_ray_cells().size() == 24 && node.grid_cleared().size() == 24);
 }
 
-int main(int argc, char** argv) {
-    const char* tmpdir = argc > 1 ? argv[1] : "/tmp";
-    const bool gpu = argc > 2 && std::strcmp(argv[2], "gpu") == 0;
-    test_config_keys(tmpdir);
-    if (gpu) test_node_on_gpu();
-    std::printf("%s (%d failures)\n", failures ? "FAILED" : "ok", failures);
-    return failures ? 1 : 0;
-}
+int main(int argc, char** argv) { return run_tests(argc, argv, test_config_keys, test_node_on_gpu); }
