@@ -47,6 +47,7 @@ SYMBOLS = [
     "cm_box_directions", "cm_result_cluster_boxes", "cm_result_cluster_boxes_device",
     "cm_result_grid_map", "cm_result_grid_map_device", "cm_grid_occupancy_copy",
     "cm_result_grid_rays", "cm_result_grid_rays_device", "cm_grid_ray_occupancy_copy",
+    "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -222,6 +223,33 @@ class GridRayCell(C.Structure):
 
 RAY_DTYPE = np.dtype([("n_pass", "<u4"), ("n_end", "<u4")])
 assert RAY_DTYPE.itemsize == C.sizeof(GridRayCell) == 8 and C.sizeof(RayParams) == 8
+
+
+# rolling log-odds occupancy map accumulated over frames (cm_map_configure, cm_map_integrate)
+MAP_MAX_LOGODDS = 1 << 20
+
+
+class MapParams(C.Structure):
+    """cm_map_params (48 bytes): the window, the height band (vehicle frame), the log-odds steps, clamps and image thresholds."""
+    _fields_ = [("cell", C.c_float), ("nx", C.c_uint32), ("ny", C.c_uint32), ("z_min", C.c_float), ("z_max", C.c_float),
+                ("l_hit", C.c_int32), ("l_miss", C.c_int32), ("l_min", C.c_int32), ("l_max", C.c_int32), ("l_free", C.c_int32),
+                ("l_occ", C.c_int32), ("max_range_cells", C.c_uint32)]
+
+
+class MapCell(C.Structure):
+    """cm_map_cell (8 bytes): window cell (ix, iy) is entry ix + iy * nx."""
+    _fields_ = [("logodds", C.c_int32), ("n_obs", C.c_uint32)]
+
+
+class MapInfo(C.Structure):
+    """cm_map_info (32 bytes): the window's anchor (absolute cell of window cell (0, 0)) and size, the integrations since the
+    configure call, the descriptor sensors that cast rays in the last one (a bit mask)."""
+    _fields_ = [("anchor", C.c_int32 * 2), ("nx", C.c_uint32), ("ny", C.c_uint32), ("n_frames", C.c_uint64),
+                ("sensors_cast", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+MAP_DTYPE = np.dtype([("logodds", "<i4"), ("n_obs", "<u4")])
+assert MAP_DTYPE.itemsize == C.sizeof(MapCell) == 8 and C.sizeof(MapParams) == 48 and C.sizeof(MapInfo) == 32
 
 
 # normals and curvature of the result (cm_result_normals)
@@ -406,6 +434,11 @@ def load():
     L.cm_result_grid_rays.argtypes = [vp, C.POINTER(GridParams), C.POINTER(RayParams), vp, u64]
     L.cm_result_grid_rays_device.argtypes = [vp, C.POINTER(GridParams), C.POINTER(RayParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_grid_ray_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.cm_map_configure.argtypes = [vp, C.POINTER(MapParams)]
+    L.cm_map_integrate.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(MapInfo)]
+    L.cm_map_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
+    L.cm_map_device.argtypes = [vp, C.POINTER(vp), C.POINTER(MapInfo)]
+    L.cm_map_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -844,6 +877,59 @@ class CloudMerger:
                     "cm_grid_ray_occupancy_copy")
         ny, nx = self._grid_shape
         return out[: n.value].reshape(ny, nx)
+
+    # ---- rolling log-odds occupancy map accumulated over frames (cm_map_configure / cm_map_integrate) ----
+    @staticmethod
+    def map_params(cell, nx, ny, z_band=(-np.inf, np.inf), l_hit=85, l_miss=40, l_min=-200, l_max=350, l_free=-40, l_occ=85,
+                   max_range_cells=0):
+        return MapParams(float(cell), int(nx), int(ny), float(z_band[0]), float(z_band[1]), int(l_hit), int(l_miss), int(l_min),
+                         int(l_max), int(l_free), int(l_occ), int(max_range_cells))
+
+    def map_configure(self, cell=None, nx=0, ny=0, z_band=(-np.inf, np.inf), l_hit=85, l_miss=40, l_min=-200, l_max=350, l_free=-40,
+                      l_occ=85, max_range_cells=0):
+        """Allocates and clears the occupancy map: a window of nx x ny cells of edge `cell` that scrolls with the vehicle over a
+        lattice fixed in the world frame. The log-odds are integers (the defaults are octomap's 0.85 / -0.4 / clamps -2 and 3.5,
+        times 100). cell None frees the map."""
+        if cell is None:
+            self._check(self._lib.cm_map_configure(self._ctx, None), "cm_map_configure")
+            return
+        p = self.map_params(cell, nx, ny, z_band, l_hit, l_miss, l_min, l_max, l_free, l_occ, max_range_cells)
+        self._check(self._lib.cm_map_configure(self._ctx, C.byref(p)), "cm_map_configure")
+
+    def map_integrate(self, pose=None):
+        """Integrates the last frame into the map: pose is the 3 x 4 matrix (fp32) that takes the vehicle frame at the frame's
+        reference instant into the world frame, None the identity. Each frame is integrated at most once. Returns the MapInfo."""
+        m = np.eye(3, 4, dtype=np.float32) if pose is None else np.asarray(pose, np.float32).reshape(3, 4)
+        mm = (C.c_float * 12)(*m.reshape(-1))
+        info = MapInfo()
+        self._check(self._lib.cm_map_integrate(self._ctx, mm, C.byref(info)), "cm_map_integrate")
+        return info
+
+    def map(self):
+        """((ny, nx) MAP_DTYPE array, MapInfo): the log-odds and observation count of every window cell."""
+        info = MapInfo()
+        st = self._lib.cm_map_copy(self._ctx, None, 0, C.byref(info))
+        if st != CAPACITY:
+            self._check(st, "cm_map_copy")
+        out = np.empty(info.nx * info.ny, dtype=MAP_DTYPE)
+        self._check(self._lib.cm_map_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_copy")
+        return out.reshape(info.ny, info.nx), info
+
+    def map_device(self):
+        """(device pointer, MapInfo) of the same table, owned by the context and valid until the next integrate or configure call."""
+        ptr, info = C.c_void_p(), MapInfo()
+        self._check(self._lib.cm_map_device(self._ctx, C.byref(ptr), C.byref(info)), "cm_map_device")
+        return ptr.value, info
+
+    def map_occupancy(self):
+        """((ny, nx) int8 image, MapInfo): -1 unknown, 0 free, 100 occupied (nav_msgs/OccupancyGrid::data, row-major)."""
+        info = MapInfo()
+        st = self._lib.cm_map_occupancy_copy(self._ctx, None, 0, C.byref(info))
+        if st != CAPACITY:
+            self._check(st, "cm_map_occupancy_copy")
+        out = np.empty(info.nx * info.ny, dtype=np.int8)
+        self._check(self._lib.cm_map_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_occupancy_copy")
+        return out.reshape(info.ny, info.nx), info
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

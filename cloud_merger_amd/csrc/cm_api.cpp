@@ -875,6 +875,100 @@ int cm_grid_ray_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_ce
     return CM_OK;
 }
 
+static_assert(sizeof(cm_map_params) == 48 && offsetof(cm_map_params, max_range_cells) == 44 && sizeof(cm_map_cell) == 8 &&
+                  offsetof(cm_map_cell, n_obs) == 4 && sizeof(cm_map_info) == 32 && offsetof(cm_map_info, n_frames) == 16,
+              "cm_map_params is 48 bytes, cm_map_cell 8 (the kernels' two words), cm_map_info 32");
+
+// The refusals of cm_map_configure about *p.
+static int map_params_check(cm_ctx* c, const cm_map_params* p) {
+    if (!std::isfinite(p->cell) || !(p->cell > 0.0f)) return fail(c, CM_BAD_ARG, "cell must be finite and > 0");
+    const float inv = 1.0f / p->cell;
+    if (!std::isfinite(inv) || !(inv > 0.0f)) return fail(c, CM_BAD_ARG, "the fp32 inverse of cell must be finite and > 0");
+    if (p->nx == 0 || p->ny == 0) return fail(c, CM_BAD_ARG, "nx and ny must be at least 1");
+    if (static_cast<uint64_t>(p->nx) * p->ny > CM_GRID_MAX_CELLS) return fail(c, CM_BAD_ARG, "nx * ny exceeds CM_GRID_MAX_CELLS");
+    if (std::isnan(p->z_min) || std::isnan(p->z_max)) return fail(c, CM_BAD_ARG, "a band limit is NaN");
+    if (p->z_min > p->z_max) return fail(c, CM_BAD_ARG, "z_min exceeds z_max");
+    if (p->l_hit < 1 || p->l_miss < 1) return fail(c, CM_BAD_ARG, "l_hit and l_miss must be at least 1");
+    for (const int32_t l : {p->l_hit, p->l_miss, p->l_min, p->l_max, p->l_free, p->l_occ})
+        if (l > CM_MAP_MAX_LOGODDS || l < -CM_MAP_MAX_LOGODDS) return fail(c, CM_BAD_ARG, "a log-odds parameter exceeds 2^20 in magnitude");
+    if (!(p->l_min <= p->l_free && p->l_free < p->l_occ && p->l_occ <= p->l_max))
+        return fail(c, CM_BAD_ARG, "the thresholds must satisfy l_min <= l_free < l_occ <= l_max");
+    if (!(p->l_min <= 0 && 0 <= p->l_max)) return fail(c, CM_BAD_ARG, "the clamp limits must satisfy l_min <= 0 <= l_max");
+    return CM_OK;
+}
+
+int cm_map_configure(cm_ctx* c, const cm_map_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (p)
+        if (const int e = map_params_check(c, p)) return e;
+    return map_configure(c, p);
+}
+
+int cm_map_integrate(cm_ctx* c, const float pose[12], cm_map_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = centroid_result_check(c)) return e;
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    int v[2];
+    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    if (c->map_serial == c->frame_serial) return fail(c, CM_BAD_ARG, "the last frame was already integrated");
+    if (const int e = map_integrate(c, pose, v)) return e;
+    if (out) *out = c->map_info;
+    return CM_OK;
+}
+
+// The refusals the three reads of the map share.
+static int map_read_check(cm_ctx* c) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    return CM_OK;
+}
+
+int cm_map_copy(cm_ctx* c, cm_map_cell* host_dst, uint64_t capacity_cells, cm_map_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = map_read_check(c)) return e;
+    if (info) *info = c->map_info;
+    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "map destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->map_state[c->map_cur], n * sizeof(cm_map_cell), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_map_cell);
+    return CM_OK;
+}
+
+int cm_map_device(cm_ctx* c, const void** dev_ptr, cm_map_info* info) {
+    if (!c || !dev_ptr) return CM_BAD_ARG;
+    *dev_ptr = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = map_read_check(c)) return e;
+    if (info) *info = c->map_info;
+    *dev_ptr = c->map_state[c->map_cur];
+    return CM_OK;
+}
+
+int cm_map_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = map_read_check(c)) return e;
+    if (info) *info = c->map_info;
+    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "map image destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->map_image, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");
 static_assert(CM_NORMAL_VALID == CM_NORMAL_VALID_DEV && CM_NORMAL_MAX_K == 64, "the kernels' flag and largest list");
 

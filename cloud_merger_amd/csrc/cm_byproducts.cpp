@@ -1,6 +1,7 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
-// (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
+// merge does not drop). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
@@ -407,6 +408,140 @@ int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r) {
     c->grid_have = true;
     c->ray_n = n_cells;
     c->ray_have = true;
+    return CM_OK;
+}
+
+namespace {
+
+// Step 1 of the occupancy map on the host, one axis: floorf(w * inv), the product rounded to fp32 on its own; false where the
+// cell does not exist.
+bool map_world_axis(float w, float inv, int* g) {
+    const float c = std::floor(static_cast<float>(w * inv));
+    if (!(c > -1073741824.0f && c < 1073741824.0f)) return false;
+    *g = static_cast<int>(c);
+    return true;
+}
+
+// xf_row on the host: ((m0 x + m1 y) + m2 z) + m3, every operation rounded to fp32 on its own.
+float map_row(const float* m, const float* t) {
+    const float a = static_cast<float>(static_cast<float>(m[0] * t[0]) + static_cast<float>(m[1] * t[1]));
+    return static_cast<float>(static_cast<float>(a + static_cast<float>(m[2] * t[2])) + m[3]);
+}
+
+}  // namespace
+
+// The occupancy map's memory, all of it: two state tables, the image, the bitmaps of every sensor the context can hold and
+// the scratch ray table, then cleared. nullptr gives it back.
+int map_configure(cm_ctx* c, const cm_map_params* q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->map_on = false;
+    c->map_serial = 0;
+    c->map_cur = 0;
+    std::memset(&c->map_info, 0, sizeof c->map_info);
+    if (!q) {
+        c->map_state[0].release();
+        c->map_state[1].release();
+        c->map_image.release();
+        c->map_bits.release();
+        c->map_rays.release();
+        return CM_OK;
+    }
+    const uint64_t n_cells = static_cast<uint64_t>(q->nx) * q->ny;
+    const size_t words = (n_cells + 31) / 32;
+    if (!c->map_state[0].reserve(n_cells * sizeof(cm_map_cell)) || !c->map_state[1].reserve(n_cells * sizeof(cm_map_cell)) ||
+        !c->map_image.reserve(n_cells) || !c->map_bits.reserve(2 * static_cast<size_t>(c->max_sensors) * words) ||
+        !c->map_rays.reserve(n_cells * sizeof(cm_grid_ray_cell)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the occupancy map");
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->map_state[0], 0, n_cells * sizeof(cm_map_cell), st));
+    HIP_TRY(c, hipMemsetAsync(c->map_image, 0xFF, n_cells, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->map_params = *q;
+    c->map_info.nx = q->nx;
+    c->map_info.ny = q->ny;
+    c->map_on = true;
+    return CM_OK;
+}
+
+bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]) {
+    const float inv = 1.0f / c->map_params.cell;
+    return map_world_axis(pose[3], inv, &v[0]) && map_world_axis(pose[7], inv, &v[1]);
+}
+
+// The last frame into the occupancy map (cm_kernels_map.hip; the semantics are in include/cloudmerge.h). The window's anchor
+// and the sensors' origin cells are step 1 on the host (fp32, explicit casts, as grid_rays does). One clear of the bitmaps
+// and the scratch ray table, a pass over the frame's raw points in place (the E and H bitmaps), k_ray_cast unchanged on the
+// E bitmaps, one pass over the cells that scrolls, updates and writes the image into the other state buffer; no host round
+// trip but the wait at the end, and no allocation: cm_map_configure made them all.
+int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
+    const cm_map_params& q = c->map_params;
+    const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
+    const uint32_t words = static_cast<uint32_t>((n_cells + 31) / 32);
+    const uint32_t n_sensors = c->frame.n_tiles ? c->frame.n_sensors : 0u;
+    HIP_TRY(c, hipSetDevice(c->device));
+    CmMapDev g;
+    std::memcpy(g.p, pose, sizeof g.p);
+    g.inv = 1.0f / q.cell;
+    g.ax = v[0] - static_cast<int>(q.nx / 2);          // (|v| < 2^30, nx / 2 <= 2^21: no overflow)
+    g.ay = v[1] - static_cast<int>(q.ny / 2);
+    g.nx = q.nx;
+    g.ny = q.ny;
+    g.z_min = q.z_min;
+    g.z_max = q.z_max;
+    CmRayDev rd;
+    std::memset(&rd, 0, sizeof rd);
+    rd.nx = q.nx;
+    rd.max_range = q.max_range_cells;
+    uint32_t cast = 0;
+    for (uint32_t s = 0; s < n_sensors; ++s) {
+        int o[2];
+        if (!map_world_axis(map_row(pose, c->frame_origin[s]), g.inv, &o[0]) ||
+            !map_world_axis(map_row(pose + 4, c->frame_origin[s]), g.inv, &o[1])) continue;
+        const int64_t ix = static_cast<int64_t>(o[0]) - g.ax, iy = static_cast<int64_t>(o[1]) - g.ay;
+        if (ix < 0 || ix >= static_cast<int64_t>(q.nx) || iy < 0 || iy >= static_cast<int64_t>(q.ny)) continue;
+        rd.ox[s] = static_cast<int>(ix);
+        rd.oy[s] = static_cast<int>(iy);
+        rd.has[s] = 1u;
+        cast |= 1u << s;
+    }
+    CmMapUpdateDev u;
+    u.nx = q.nx;
+    u.ny = q.ny;
+    // the shift anchor_new - anchor_old: a window that shares no cell with the old one (or has no old one) carries nothing
+    const int64_t sx = static_cast<int64_t>(g.ax) - c->map_info.anchor[0], sy = static_cast<int64_t>(g.ay) - c->map_info.anchor[1];
+    const bool carry = c->map_info.n_frames != 0 && sx > -static_cast<int64_t>(q.nx) && sx < static_cast<int64_t>(q.nx) &&
+                       sy > -static_cast<int64_t>(q.ny) && sy < static_cast<int64_t>(q.ny);
+    u.carry = carry ? 1u : 0u;
+    u.sx = carry ? static_cast<int32_t>(sx) : 0;
+    u.sy = carry ? static_cast<int32_t>(sy) : 0;
+    u.n_sensors = n_sensors;
+    u.l_hit = q.l_hit;
+    u.l_miss = q.l_miss;
+    u.l_min = q.l_min;
+    u.l_max = q.l_max;
+    u.l_free = q.l_free;
+    u.l_occ = q.l_occ;
+    hipStream_t st = c->stream;
+    c->prof_used = 0;
+    prof_mark(c, "map_clear");
+    if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->map_bits, 0, 2 * static_cast<size_t>(n_sensors) * words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->map_rays, 0, n_cells * sizeof(cm_grid_ray_cell), st));
+    prof_mark(c, "k_map_mark");
+    cmk_map_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->map_bits, words, n_sensors, c->frame.n_tiles);
+    prof_mark(c, "k_ray_cast");
+    cmk_ray_cast(st, c->map_bits, words, rd, n_sensors, c->map_rays);
+    prof_mark(c, "k_map_update");
+    cmk_map_update(st, c->map_state[c->map_cur], c->map_state[c->map_cur ^ 1], c->map_rays, c->map_bits, words, u, c->map_image);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->map_cur ^= 1;
+    c->map_info.anchor[0] = g.ax;
+    c->map_info.anchor[1] = g.ay;
+    ++c->map_info.n_frames;
+    c->map_info.sensors_cast = cast;
+    c->map_serial = c->frame_serial;
     return CM_OK;
 }
 

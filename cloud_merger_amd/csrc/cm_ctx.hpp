@@ -257,14 +257,28 @@ struct cm_ctx {
     // Free-space ray casting over the grid map (cm_kernels_rays.hip), on request after a frame, behind the grid map of the
     // same call: the per-sensor bitmaps of end cells, the table and the cleared image — no frame reads them — allocated by the
     // first request and grown together.
-    float frame_origin[CM_MAX_SENSORS][2] = {};   // per descriptor sensor the (x, y) translation of the matrix the last frame
+    float frame_origin[CM_MAX_SENSORS][3] = {};   // per descriptor sensor the (x, y, z) translation of the matrix the last frame
                                                   // was built with (build_frame; under deskew the descriptor's own is the
-                                                  // identity). Read by grid_rays and by nothing else.
+                                                  // identity). Read by grid_rays (x, y) and map_integrate, by nothing else.
     DevBuf<uint32_t> ray_bits;           // max_sensors bitmaps of ceil(cells / 32) words
     DevBuf<void> ray_cells;              // the table: cm_grid_ray_cell per cell
     DevBuf<void> ray_image;              // the cleared occupancy image: one byte per cell
     uint64_t ray_n = 0;                  // cells of the last ray call
     bool ray_have = false;               // they hold the rays of the result at rest (cleared by a merge and by a grid call)
+
+    // Rolling log-odds occupancy map (cm_kernels_map.hip), configured by cm_map_configure and fed by cm_map_integrate after a
+    // frame: the one by-product that survives merges (invalidate_result_tables leaves it alone). Buffers of its own — no frame
+    // and no other by-product reads them —, all allocated by the configure call, so an integrate call allocates nothing.
+    bool map_on = false;                 // a map is configured
+    cm_map_params map_params{};
+    DevBuf<void> map_state[2];           // cm_map_cell per window cell, twice: k_map_update reads one and writes the other
+    int map_cur = 0;                     // which of the two holds the map
+    DevBuf<void> map_image;              // the three-valued image: one byte per cell
+    DevBuf<uint32_t> map_bits;           // 2 * max_sensors bitmaps of ceil(cells / 32) words: the E bitmaps, then the H bitmaps
+    DevBuf<void> map_rays;               // k_ray_cast's scratch table: (n_pass, n_end) per cell
+    cm_map_info map_info{};              // anchor, size, integrations since the configure call, who cast in the last one
+    uint64_t frame_serial = 0;           // counts the frames enqueued (enqueue, merge_tables): the frame at rest is this one
+    uint64_t map_serial = 0;             // the frame integrated last (0: none since the configure call)
 
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
@@ -354,7 +368,8 @@ void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t 
                       bool lds_rank, uint32_t* tile_kept, const char* scatter_mark);
 
 // cm_byproducts.cpp: the tables computed from the last result on request. Called with merge_mu held.
-// The tables of the last result go with it (where a merge replaces the result).
+// The tables of the last result go with it (where a merge replaces the result). The occupancy map is not one of them: it
+// accumulates over the frames and stays.
 inline void invalidate_result_tables(cm_ctx* c) { c->cov_have = c->nrm_have = c->aln_fit.have = c->ndt_fit.have = c->grid_have = c->ray_have = false; }
 // The covariance table of the last result (cov_entries, n_out entries).
 int voxel_cov(cm_ctx* c, const cm_cov_params& q);
@@ -370,6 +385,12 @@ void box_direction_table(uint32_t n_angles, float* cos_sin);
 int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages = false);
 // The grid map at q and behind it the rays of the last frame at r (ray_cells and ray_image, ray_n = q.nx * q.ny cells).
 int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r);
+// The occupancy map. map_configure: room for q's window, cleared (nullptr: the buffers go). map_vehicle_cell: the absolute
+// cell of the pose's translation at the configured cell size, false where it does not exist. map_integrate: the last frame
+// under `pose` into the map, whose window is then anchored around the vehicle cell v.
+int map_configure(cm_ctx* c, const cm_map_params* q);
+bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]);
+int map_integrate(cm_ctx* c, const float pose[12], const int v[2]);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

@@ -306,3 +306,22 @@ struct CmRayDev {
     uint32_t nx;
     uint32_t max_range;
 };
+
+// Rolling log-odds occupancy map (cm_kernels_map.hip). What k_map_mark takes: rows x and y of the pose, inv = 1.0f / cell, the
+// window's anchor (the absolute cell of window cell (0, 0)) and size, the height band. What k_map_update takes: the window,
+// the shift anchor_new - anchor_old per axis (carry 0: the old window shares no cell with the new one, or there is none), the
+// frame's sensors and the eight log-odds parameters. A state record is (logodds, n_obs), two words.
+struct CmMapDev {
+    float p[8];
+    float inv;
+    int32_t ax, ay;
+    uint32_t nx, ny;
+    float z_min, z_max;
+};
+struct CmMapUpdateDev {
+    uint32_t nx, ny;
+    int32_t sx, sy;
+    uint32_t carry;
+    uint32_t n_sensors;
+    int32_t l_hit, l_miss, l_min, l_max, l_free, l_occ;
+};

@@ -243,3 +243,13 @@ void cmk_ray_mark(hipStream_t s, const CmFrameDev* fd, const CmGridDev& g, const
                   uint32_t* bits, uint32_t words, uint32_t n_tiles);
 void cmk_ray_cast(hipStream_t s, const uint32_t* bits, uint32_t words, const CmRayDev& rd, uint32_t n_sensors, void* rays);
 void cmk_ray_finish(hipStream_t s, const void* grid, const void* rays, void* image, uint32_t n_cells, uint32_t min_pass);
+
+// ---- rolling log-odds occupancy map (cm_kernels_map.hip) ---------------------------------------------------------------------
+// bits: 2 * n_sensors bitmaps of `words` = ceil(nx * ny / 32) words, zero bytes before cmk_map_mark: sensor s's E bitmap (the
+// window cells of its counted points of A and G) at s * words — what cmk_ray_cast takes —, its H bitmap (of A alone) at
+// (n_sensors + s) * words. cmk_map_update reads the old state (prev) at the shifted index, the ray table cmk_ray_cast left and
+// the bitmaps, and writes the new state (next, another buffer) and the image.
+void cmk_map_mark(hipStream_t s, const CmFrameDev* fd, const CmMapDev& g, const unsigned char* keep, const unsigned char* ground,
+                  uint32_t* bits, uint32_t words, uint32_t n_sensors, uint32_t n_tiles);
+void cmk_map_update(hipStream_t s, const void* prev, void* next, const void* rays, const uint32_t* bits, uint32_t words,
+                    const CmMapUpdateDev& u, void* image);

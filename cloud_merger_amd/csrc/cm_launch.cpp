@@ -500,6 +500,7 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
         if (consume) {
             c->frame_origin[k][0] = sl.m[3];         // what the frame is built with, whatever deskew does to d.m below
             c->frame_origin[k][1] = sl.m[7];
+            c->frame_origin[k][2] = sl.m[11];
             c->stats_sensor[k] = s; c->stats_n[k] = sc.n;
             c->stats_fresh[k] = sl.fresh ? 1u : 0u;
             c->stats_bytes[k] = sl.fresh ? sl.active_bytes_h2d : 0u;
@@ -665,6 +666,7 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
     }
     c->have_result = false;
     invalidate_result_tables(c);
+    ++c->frame_serial;
     c->last_mode = mode;
     c->bytes_d2h = 0;
     if (c->pub_pending[0]) {
@@ -876,6 +878,7 @@ int merge_tables(cm_ctx* c, const void* const* dev_tables, const uint64_t* n_ent
     r.n_in = total;
     c->have_result = false;
     invalidate_result_tables(c);
+    ++c->frame_serial;
     c->last_mode = 2;
     c->prof_used = 0;
     if (f.n_padded == 0) {

@@ -79,6 +79,16 @@ __device__ __forceinline__ bool grid_axis(float p, float origin, float inv, uint
     return true;
 }
 
+// The absolute cell of a world coordinate on one axis, the occupancy map's step 1 (include/cloudmerge.h): floorf(w * inv),
+// false when it is not strictly inside +-2^30 (a w of +-inf or NaN included). No origin is subtracted: the lattice never
+// moves. The one cell computation of k_map_mark.
+__device__ __forceinline__ bool world_axis(float w, float inv, int* g) {
+    const float c = floorf(__fmul_rn(w, inv));
+    if (!(c > -1073741824.0f && c < 1073741824.0f)) return false;
+    *g = static_cast<int>(c);
+    return true;
+}
+
 // ------------------------------------------------------------------------------------------------
 // walks over the sorted cells of a search grid: keys ascending, key = x + dx * row, row = y + dy * z; the (y,z)-row table
 // gives each row's range of sorted positions

@@ -197,6 +197,15 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "grid_raycast") ok = read_flag(is, &c.grid_raycast);
         else if (key == "grid_min_pass") ok = read(is, c.grid_min_pass) && c.grid_min_pass >= 1;
         else if (key == "grid_ray_range") ok = read(is, c.grid_ray_range);
+        else if (key == "map_cell") ok = read(is, c.map_cell) && std::isfinite(c.map_cell) && c.map_cell >= 0.0f &&
+                                         (c.map_cell == 0.0f || std::isfinite(1.0f / c.map_cell));
+        else if (key == "map_size") ok = read(is, c.map_nx, c.map_ny) && c.map_nx >= 1 && c.map_ny >= 1 &&
+                                         static_cast<uint64_t>(c.map_nx) * c.map_ny <= CM_GRID_MAX_CELLS;
+        else if (key == "map_z_band") ok = read(is, c.map_z_band[0], c.map_z_band[1]) && c.map_z_band[0] <= c.map_z_band[1];
+        else if (key == "map_logodds") ok = read(is, c.map_l_hit, c.map_l_miss, c.map_l_min, c.map_l_max) && c.map_l_hit >= 1 && c.map_l_miss >= 1 &&
+                                            c.map_l_min <= 0 && c.map_l_max >= 0;
+        else if (key == "map_thresholds") ok = read(is, c.map_l_free, c.map_l_occ) && c.map_l_free < c.map_l_occ;
+        else if (key == "map_ray_range") ok = read(is, c.map_ray_range);
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -270,6 +279,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
         error_ = std::string("cm_create: ") + cm_status_string(st);
     } else if (cfg_.ground_enable && cm_set_ground_removal(ctx_, &cfg_.ground) != CM_OK) refuse("cm_set_ground_removal");
     if (ctx_ && cfg_.sor_enable && cm_set_statistical_outlier(ctx_, &cfg_.sor) != CM_OK) refuse("cm_set_statistical_outlier");
+    if (ctx_ && cfg_.map_cell > 0.0f) {
+        const cm_map_params mp{cfg_.map_cell, cfg_.map_nx, cfg_.map_ny, cfg_.map_z_band[0], cfg_.map_z_band[1], cfg_.map_l_hit, cfg_.map_l_miss,
+                               cfg_.map_l_min, cfg_.map_l_max, cfg_.map_l_free, cfg_.map_l_occ, cfg_.map_ray_range};
+        if (cm_map_configure(ctx_, &mp) != CM_OK) refuse("cm_map_configure");
+    }
     for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s)
         if (cm_set_sensor_time_field(ctx_, static_cast<uint32_t>(s), cfg_.time_field[s].offset, cfg_.time_field[s].type) != CM_OK)
             refuse("cm_set_sensor_time_field");
@@ -385,6 +399,35 @@ int CloudMergerNode::grid_of_frame(const cm_result& r) {
     return CM_OK;
 }
 
+int CloudMergerNode::set_pose(const float pose[12]) {
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(pose_mu_);
+    std::memcpy(pose_, pose, sizeof pose_);
+    return CM_OK;
+}
+
+int CloudMergerNode::map_of_frame(const cm_result& r) {
+    if (!(cfg_.map_cell > 0.0f) || r.status != CM_OK) return CM_OK;     // (a frame without a voxel grid leaves the map as it is)
+    float pose[12];
+    {
+        std::lock_guard<std::mutex> lk(pose_mu_);
+        std::memcpy(pose, pose_, sizeof pose);
+    }
+    const size_t n = static_cast<size_t>(cfg_.map_nx) * cfg_.map_ny;
+    map_cells_.resize(n);
+    map_image_.resize(n);
+    int st = cm_map_integrate(ctx_, pose, &map_info_);
+    if (st == CM_OK) st = cm_map_copy(ctx_, map_cells_.data(), n, nullptr);
+    if (st == CM_OK) st = cm_map_occupancy_copy(ctx_, map_image_.data(), n, nullptr);
+    if (st != CM_OK) {
+        map_cells_.clear();
+        map_image_.clear();
+        set_error(cm_last_error(ctx_));
+    }
+    return st;
+}
+
 int CloudMergerNode::normals_of_frame(const cm_result& r) {
     normals_.clear();
     if (cfg_.normals_k == 0 || r.status != CM_OK) return CM_OK;
@@ -473,6 +516,7 @@ int CloudMergerNode::after_wait(const cm_result& r) {
     if (r.path_flags & CM_PATH_REDONE) n_redone_.fetch_add(1);
     int st = clusters_of_frame(r);
     if (st == CM_OK) st = grid_of_frame(r);
+    if (st == CM_OK) st = map_of_frame(r);
     if (st == CM_OK) st = normals_of_frame(r);
     if (st == CM_OK) st = align_of_frame(r);
     if (st != CM_OK) return st;

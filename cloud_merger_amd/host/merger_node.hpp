@@ -104,6 +104,17 @@ struct NodeConfig {
     bool grid_raycast = false;
     uint32_t grid_min_pass = 1;
     uint32_t grid_ray_range = 0;
+    // Rolling log-odds occupancy map accumulated over the frames (cm_map_configure, cm_map_integrate). Off by default
+    // (map_cell 0). On: the node configures a window of map_nx x map_ny cells that scrolls with the vehicle, and after every
+    // frame that has been waited for integrates it under the pose set_pose() last gave (the identity until then), then keeps
+    // the state table, the image and the info until the next frame (map_cells(), map_image(), map_info()). The log-odds are
+    // integers: the defaults are octomap's 0.85 / -0.4, clamps -2 and 3.5, thresholds -0.4 and 0.85, times 100.
+    float map_cell = 0.0f;
+    uint32_t map_nx = 1, map_ny = 1;
+    float map_z_band[2] = {-std::numeric_limits<float>::infinity(), std::numeric_limits<float>::infinity()};
+    int32_t map_l_hit = 85, map_l_miss = 40, map_l_min = -200, map_l_max = 350;
+    int32_t map_l_free = -40, map_l_occ = 85;
+    uint32_t map_ray_range = 0;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -142,6 +153,8 @@ struct NodeConfig {
 //   grid_min_points <n>   (the 2-D grid map of every frame; grid_cell 0: off)
 //   grid_raycast <0|1> | grid_min_pass <n> | grid_ray_range <cells>   (free-space ray casting over that grid map; it needs
 //   grid_cell > 0; grid_ray_range 0: to the return)
+//   map_cell <metres> | map_size <nx> <ny> | map_z_band <lo> <hi> | map_logodds <hit> <miss> <min> <max> |
+//   map_thresholds <free> <occ> | map_ray_range <cells>   (the occupancy map accumulated over the frames; map_cell 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -194,6 +207,11 @@ public:
     // finite).
     int set_ego_twist(const float v[3], const float w[3]);
 
+    // The pose the next integrated frame enters the occupancy map with (map_cell > 0): a row-major 3 x 4 matrix from the base
+    // frame at the frame's stamp into a fixed world frame, the identity until the first call. Callable from any thread.
+    // Returns a cm_status (CM_BAD_ARG: not finite).
+    int set_pose(const float pose[12]);
+
     void set_publisher(Publisher p) { publish_ = std::move(p); }
     void set_clock(Clock c) { clock_ = std::move(c); }
 
@@ -224,6 +242,12 @@ public:
     // the frame has no voxel grid.
     const std::vector<cm_grid_ray_cell>& grid_ray_cells() const { return grid_ray_cells_; }
     const std::vector<int8_t>& grid_cleared() const { return grid_cleared_; }
+    // map_cell > 0: the occupancy map after the frame waited for last, map_nx * map_ny entries, window cell (ix, iy) at
+    // ix + iy * map_nx, its image (-1 unknown, 0 free, 100 occupied) and its info (the window's anchor among them); the two
+    // tables are empty until the first frame with a voxel grid.
+    const std::vector<cm_map_cell>& map_cells() const { return map_cells_; }
+    const std::vector<int8_t>& map_image() const { return map_image_; }
+    const cm_map_info& map_info() const { return map_info_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -285,6 +309,12 @@ private:
     std::vector<cm_grid_ray_cell> grid_ray_cells_;
     std::vector<int8_t> grid_cleared_;
     int grid_of_frame(const cm_result& r);         // after cm_wait: cm_result_grid_map and the image when the config asks for it
+    std::mutex pose_mu_;
+    float pose_[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    std::vector<cm_map_cell> map_cells_;
+    std::vector<int8_t> map_image_;
+    cm_map_info map_info_{};
+    int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     bool has_alignment_ = false;

@@ -616,7 +616,8 @@ CM_API int cm_grid_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capaci
  * context and valid until the next merge, the next grid call or the next ray call. No later frame depends on whether they
  * were asked for; with CM_FLAG_PROFILE, cm_get_stage_times afterwards lists this call's stages (the grid's, then ray_clear,
  * k_ray_mark, k_ray_cast, k_ray_finish). Not modelled: the height of a beam over a cell (2-D casting clears under an
- * overhang), accumulation over frames, rays of points outside the grid or the band. */
+ * overhang), rays of points outside the grid or the band. Accumulation over frames is the occupancy map's (cm_map_integrate
+ * below), which casts the same rays. */
 typedef struct cm_ray_params {         /* 8 bytes */
     uint32_t min_pass;                 /* rays that must cross an UNKNOWN cell to clear it; >= 1 */
     uint32_t max_range_cells;          /* steps of a ray from its origin that count; 0 = to the end cell */
@@ -634,6 +635,83 @@ CM_API int cm_result_grid_rays_device(cm_ctx* ctx, const cm_grid_params* p, cons
 /* The cleared image of the last ray call since the last merge or grid call; capacity in cells. *n_cells is always written (0
  * when there is no such call: CM_BAD_ARG); a destination that is too small: CM_CAPACITY (nothing is copied). */
 CM_API int cm_grid_ray_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, uint64_t* n_cells);
+
+/* ---- rolling log-odds occupancy map accumulated over frames (an extension) ---------------------------------------------
+ * A single frame's clearing is noise to a planner. This is the persistent map of costmap_2d and octomap: every beam adds
+ * evidence for "free" along its path and for "occupied" at its end, per cell an integer log-odds that is clamped, and the
+ * map's window scrolls with the vehicle over a lattice fixed in a world frame. The caller passes the pose of every frame it
+ * integrates, for example the one cm_result_align or cm_result_ndt_align returned, chained. Everything is
+ * integer arithmetic over sets of distinct rays apart from the fp32 cell computation of step 1, every operation of which is
+ * rounded on its own: the map is a function of the frames, the poses and the parameters alone, bit for bit.
+ * Pose: a row-major 3 x 4 fp32 matrix P that takes the common (vehicle) frame at the frame's reference instant into a fixed
+ * world frame; all twelve entries finite.
+ *   1. World cell of a point. q = (x, y, z) is a point of the frame in the common frame, as the grid map sees it (after the
+ *      sensor transform, deskew and validity). wx = ((P0*x + P1*y) + P2*z) + P3, wy = ((P4*x + P5*y) + P6*z) + P7. With
+ *      inv = 1.0f / cell (an fp32 division), per axis c = floorf(w * inv), the product in fp32. The cell exists iff
+ *      c > -1073741824.0f && c < 1073741824.0f, tested in float (NaN and +-inf fail); then g = (int)c, an absolute cell. No
+ *      origin is subtracted: the lattice never moves.
+ *   2. Window. The vehicle cell (vx, vy) is step 1 applied to (P3, P7). The anchor is a = (vx - (int)(nx / 2),
+ *      vy - (int)(ny / 2)), the window ax <= gx < ax + nx and likewise in y; window cell (gx - ax, gy - ay) is entry
+ *      ix + iy * nx.
+ *   3. Counted points. A counted point lies in A (what cm_merged_copy returns) or G (what cm_ground_copy returns), has
+ *      z_min <= q.z && q.z <= z_max (the band is in the vehicle frame) and a world cell inside the window. E_s is the set of
+ *      distinct window cells of sensor s's counted points of A and G, H_s the same over A alone. A sensor is an entry of the
+ *      frame's descriptor, as for cm_result_grid_rays.
+ *   4. Origins. Sensor s's origin cell is step 1 applied to P times the full (x, y, z) translation of the matrix the frame
+ *      transformed that sensor's cloud with. A sensor whose origin cell does not exist or lies outside the window casts no
+ *      rays; its hits still count. Under ego-motion compensation the origin is still that translation, not moved to t_ref
+ *      (the approximation of cm_result_grid_rays' step 3), and P is the pose at t_ref.
+ *   5. Rays: those of cm_result_grid_rays' step 5, unchanged, over the window: from each origin cell to every cell of E_s,
+ *      with max_range_cells. n_pass(c) is the number of rays that cross c.
+ *   6. Evidence per window cell. n_hit = |{s : c in H_s}|, n_ground = |{s : c in E_s \ H_s}|, over all sensors of the frame.
+ *      n_hit > 0: d = l_hit * n_hit (a hit wins over any number of passes). Otherwise d = -l_miss * (n_pass + n_ground), in
+ *      int64.
+ *   7. State, cm_map_cell. A cell of the new window that was not in the previous window starts {0, 0}: every cell on the
+ *      first integration after cm_map_configure. A cell in both windows carries its state over. If d != 0,
+ *      logodds = clamp(logodds + d, l_min, l_max) in int64 and n_obs is incremented, saturating.
+ *   8. Image. One int8_t per window cell: n_obs == 0 gives -1, logodds >= l_occ gives 100, logodds <= l_free gives 0, anything
+ *      else -1.
+ * cm_map_configure refuses with CM_BAD_ARG (cm_last_error says why): a cell that is not finite and > 0, or whose inv is not
+ * finite and > 0; nx or ny 0, or nx * ny > CM_GRID_MAX_CELLS; a NaN band limit or z_min > z_max; l_hit < 1 or l_miss < 1;
+ * any of the six l_* above 2^20 in magnitude; anything that breaks l_min <= l_free < l_occ <= l_max and l_min <= 0 <= l_max;
+ * a frame in flight. cm_map_integrate refuses everything cm_result_grid_map refuses about the result, and: no configured
+ * map, a pose that is not finite, a vehicle cell that does not exist, and a frame that was already integrated into this map
+ * (each frame is integrated at most once). Unlike every other by-product the map survives merges: it lives until the next
+ * cm_map_configure or cm_destroy, uses buffers of its own (the grid map's and the rays' tables stay what they were), and no
+ * later frame depends on whether it exists. All of its memory is taken by cm_map_configure. With CM_FLAG_PROFILE,
+ * cm_get_stage_times after an integrate call lists map_clear, k_map_mark, k_ray_cast, k_map_update. Not modelled: 3-D
+ * occupancy and the height of a beam over a cell, probabilities beyond the three-valued image, origins moved under deskew. */
+#define CM_MAP_MAX_LOGODDS (1 << 20)
+typedef struct cm_map_params {         /* 48 bytes, no padding */
+    float cell;                        /* edge of a cell (m); finite, > 0 */
+    uint32_t nx, ny;                   /* the window in cells; nx * ny <= CM_GRID_MAX_CELLS */
+    float z_min, z_max;                /* closed height band in the vehicle frame; infinities allowed */
+    int32_t l_hit, l_miss;             /* log-odds added per sensor that hits, subtracted per pass; >= 1 */
+    int32_t l_min, l_max;              /* clamp limits; l_min <= 0 <= l_max */
+    int32_t l_free, l_occ;             /* image thresholds; l_min <= l_free < l_occ <= l_max */
+    uint32_t max_range_cells;          /* steps of a ray from its origin that count; 0 = to the end cell */
+} cm_map_params;
+typedef struct cm_map_cell {           /* 8 bytes, window cell (ix, iy) is entry ix + iy * nx */
+    int32_t logodds;
+    uint32_t n_obs;                    /* integrations that changed the cell's evidence (d != 0), saturating */
+} cm_map_cell;
+typedef struct cm_map_info {           /* 32 bytes */
+    int32_t anchor[2];                 /* the absolute cell of window cell (0, 0) at the last integration */
+    uint32_t nx, ny;
+    uint64_t n_frames;                 /* integrations since cm_map_configure */
+    uint32_t sensors_cast;             /* bit s: descriptor sensor s cast rays in the last integration */
+    uint32_t _pad;
+} cm_map_info;
+/* Non-NULL parameters allocate the map and clear it (every cell {0, 0}, the image -1, no frame integrated); NULL frees it. */
+CM_API int cm_map_configure(cm_ctx* ctx, const cm_map_params* p);
+/* Integrates the last frame under the pose; *out (may be NULL) is the map's info afterwards. */
+CM_API int cm_map_integrate(cm_ctx* ctx, const float pose[12], cm_map_info* out);
+/* Host copy of the state table; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied). *info may be NULL. */
+CM_API int cm_map_copy(cm_ctx* ctx, cm_map_cell* host_dst, uint64_t capacity_cells, cm_map_info* info);
+/* The same table in device memory owned by the context, valid until the next cm_map_integrate or cm_map_configure. */
+CM_API int cm_map_device(cm_ctx* ctx, const void** dev_ptr, cm_map_info* info);
+/* Host copy of the image; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied). *info may be NULL. */
+CM_API int cm_map_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, cm_map_info* info);
 
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
