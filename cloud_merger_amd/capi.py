@@ -48,6 +48,7 @@ SYMBOLS = [
     "cm_result_grid_map", "cm_result_grid_map_device", "cm_grid_occupancy_copy",
     "cm_result_grid_rays", "cm_result_grid_rays_device", "cm_grid_ray_occupancy_copy",
     "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy",
+    "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -251,6 +252,23 @@ class MapInfo(C.Structure):
 MAP_DTYPE = np.dtype([("logodds", "<i4"), ("n_obs", "<u4")])
 assert MAP_DTYPE.itemsize == C.sizeof(MapCell) == 8 and C.sizeof(MapParams) == 48 and C.sizeof(MapInfo) == 32
 
+# cost layer over the occupancy map: exact distance field and inflated costmap (cm_map_cost_configure, cm_map_cost_update)
+MAP_DIST_NONE = 0xFFFFFFFF
+COST_LETHAL = 254
+COST_INSCRIBED = 253
+COST_NO_INFORMATION = 255
+COST_INFLATE_UNKNOWN = 1
+COST_MAX_RADIUS_CELLS = 256
+COST_MAX_AXIS = 2048
+
+
+class CostParams(C.Structure):
+    """cm_cost_params (16 bytes): the two radii in metres, the decay per metre, CM_COST_INFLATE_UNKNOWN or 0."""
+    _fields_ = [("inscribed_radius", C.c_float), ("inflation_radius", C.c_float), ("cost_scaling", C.c_float), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(CostParams) == 16
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -439,6 +457,12 @@ def load():
     L.cm_map_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
     L.cm_map_device.argtypes = [vp, C.POINTER(vp), C.POINTER(MapInfo)]
     L.cm_map_occupancy_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
+    L.cm_map_cost_configure.argtypes = [vp, C.POINTER(CostParams)]
+    L.cm_map_cost_update.argtypes = [vp, C.POINTER(MapInfo)]
+    L.cm_map_cost_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
+    L.cm_map_dist_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
+    L.cm_map_cost_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(MapInfo)]
+    L.cm_map_cost_table_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -930,6 +954,53 @@ class CloudMerger:
         out = np.empty(info.nx * info.ny, dtype=np.int8)
         self._check(self._lib.cm_map_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_occupancy_copy")
         return out.reshape(info.ny, info.nx), info
+
+    # ---- cost layer over the occupancy map (cm_map_cost_configure / cm_map_cost_update) ----
+    def map_cost_configure(self, inscribed_radius=None, inflation_radius=0.0, cost_scaling=0.0, inflate_unknown=False):
+        """Allocates the cost layer behind the configured map and builds its table: costmap_2d's inflation layer (254 lethal, 253
+        within inscribed_radius, an exponential decay at cost_scaling per metre out to inflation_radius, 255 unknown) over the
+        exact distance field. inscribed_radius None frees the layer."""
+        if inscribed_radius is None:
+            self._check(self._lib.cm_map_cost_configure(self._ctx, None), "cm_map_cost_configure")
+            return
+        p = CostParams(float(inscribed_radius), float(inflation_radius), float(cost_scaling), COST_INFLATE_UNKNOWN if inflate_unknown else 0)
+        self._check(self._lib.cm_map_cost_configure(self._ctx, C.byref(p)), "cm_map_cost_configure")
+
+    def map_cost_update(self):
+        """Computes both tables from the map's current image. Returns the MapInfo."""
+        info = MapInfo()
+        self._check(self._lib.cm_map_cost_update(self._ctx, C.byref(info)), "cm_map_cost_update")
+        return info
+
+    def map_cost(self):
+        """((ny, nx) uint8 cost, (ny, nx) uint32 dist2, MapInfo) of the last update: the inflated cost and the squared distance
+        in cells to the nearest occupied cell of the window (MAP_DIST_NONE where the window holds none)."""
+        info = MapInfo()
+        st = self._lib.cm_map_cost_copy(self._ctx, None, 0, C.byref(info))
+        if st != CAPACITY:
+            self._check(st, "cm_map_cost_copy")
+        n = info.nx * info.ny
+        cost, dist2 = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
+        self._check(self._lib.cm_map_cost_copy(self._ctx, cost.ctypes.data, n, C.byref(info)), "cm_map_cost_copy")
+        self._check(self._lib.cm_map_dist_copy(self._ctx, dist2.ctypes.data, n, C.byref(info)), "cm_map_dist_copy")
+        return cost.reshape(info.ny, info.nx), dist2.reshape(info.ny, info.nx), info
+
+    def map_cost_device(self):
+        """(cost device pointer, dist2 device pointer, MapInfo) of the same tables, owned by the context and valid until the next
+        update, integrate or configure call."""
+        cost, dist2, info = C.c_void_p(), C.c_void_p(), MapInfo()
+        self._check(self._lib.cm_map_cost_device(self._ctx, C.byref(cost), C.byref(dist2), C.byref(info)), "cm_map_cost_device")
+        return cost.value, dist2.value, info
+
+    def map_cost_table(self):
+        """(R * R + 1,) uint8: the cost of a free cell by its squared distance in cells, as cm_map_cost_configure built it."""
+        n = C.c_uint64(0)
+        st = self._lib.cm_map_cost_table_copy(self._ctx, None, 0, C.byref(n))
+        if st != CAPACITY:
+            self._check(st, "cm_map_cost_table_copy")
+        out = np.empty(n.value, dtype=np.uint8)
+        self._check(self._lib.cm_map_cost_table_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_map_cost_table_copy")
+        return out
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

@@ -8,6 +8,7 @@
 #include <limits>
 #include <new>
 
+#include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 
 namespace {
@@ -966,6 +967,96 @@ int cm_map_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, 
     HIP_TRY(c, hipMemcpyAsync(host_dst, c->map_image, n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->bytes_d2h += n;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_cost_params) == 16 && offsetof(cm_cost_params, flags) == 12, "cm_cost_params is 16 bytes");
+static_assert(CM_COST_MAX_AXIS == CM_COST_MAX_AXIS_DEV && CM_COST_MAX_RADIUS_CELLS == 256, "the row pass's LDS row and the largest table");
+
+int cm_map_cost_configure(cm_ctx* c, const cm_cost_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    uint32_t R = 0;
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (const char* why = cm_cost_refusal(c->map_params.cell, p->inscribed_radius, p->inflation_radius, p->cost_scaling,
+                                              CM_COST_MAX_RADIUS_CELLS, &R))
+            return fail(c, CM_BAD_ARG, why);
+        if (p->flags & ~CM_COST_INFLATE_UNKNOWN) return fail(c, CM_BAD_ARG, "unknown flag bits");
+        if (c->map_info.nx > CM_COST_MAX_AXIS || c->map_info.ny > CM_COST_MAX_AXIS)
+            return fail(c, CM_BAD_ARG, "the map is wider or taller than CM_COST_MAX_AXIS cells");
+    }
+    return map_cost_configure(c, p, R);
+}
+
+// The refusals every call on a configured cost layer shares; the reads also refuse stale tables.
+static int cost_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (read && !c->cost_fresh)
+        return fail(c, CM_BAD_ARG, c->map_info.n_frames ? "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate"
+                                                        : "the cost tables are stale: no cm_map_cost_update since cm_map_cost_configure");
+    return CM_OK;
+}
+
+int cm_map_cost_update(cm_ctx* c, cm_map_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cost_check(c, false)) return e;
+    if (const int e = map_cost_update(c)) return e;
+    if (out) *out = c->map_info;
+    return CM_OK;
+}
+
+// One of the two tables to the host: `bytes` per cell from src.
+static int cost_table_to_host(cm_ctx* c, void* host_dst, const void* src, size_t bytes, uint64_t capacity_cells, cm_map_info* info, const char* what) {
+    if (const int e = cost_check(c, true)) return e;
+    if (info) *info = c->map_info;
+    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, what);
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, src, n * bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * bytes;
+    return CM_OK;
+}
+
+int cm_map_cost_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    return cost_table_to_host(c, host_dst, c->cost_cells, 1, capacity_cells, info, "cost destination too small");
+}
+
+int cm_map_dist_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    return cost_table_to_host(c, host_dst, c->cost_dist2, sizeof(uint32_t), capacity_cells, info, "distance destination too small");
+}
+
+int cm_map_cost_device(cm_ctx* c, const void** cost, const void** dist2, cm_map_info* info) {
+    if (!c) return CM_BAD_ARG;
+    if (cost) *cost = nullptr;
+    if (dist2) *dist2 = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cost_check(c, true)) return e;
+    if (info) *info = c->map_info;
+    if (cost) *cost = c->cost_cells;
+    if (dist2) *dist2 = c->cost_dist2;
+    return CM_OK;
+}
+
+int cm_map_cost_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cost_check(c, false)) return e;
+    const uint64_t n_lut = c->cost_lut_host.size();
+    if (n) *n = n_lut;
+    if (n_lut > capacity) return fail(c, CM_CAPACITY, "cost table destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    std::memcpy(host_dst, c->cost_lut_host.data(), n_lut);
     return CM_OK;
 }
 

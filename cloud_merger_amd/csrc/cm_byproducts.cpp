@@ -1,7 +1,7 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
-// merge does not drop). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "cm_align_solve.hpp"
+#include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 #include "cm_search.hpp"
 
@@ -434,6 +435,7 @@ float map_row(const float* m, const float* t) {
 // the scratch ray table, then cleared. nullptr gives it back.
 int map_configure(cm_ctx* c, const cm_map_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
+    if (const int e = map_cost_configure(c, nullptr, 0)) return e;     // the cost layer goes with the map it was sized for
     c->map_on = false;
     c->map_serial = 0;
     c->map_cur = 0;
@@ -542,6 +544,64 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     ++c->map_info.n_frames;
     c->map_info.sensors_cast = cast;
     c->map_serial = c->frame_serial;
+    c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
+    return CM_OK;
+}
+
+// The cost layer's memory, all of it: the two tables, the column pass's obstacle words and carries, the cost table, which is
+// built here (cm_cost_table.hpp) and uploaded. nullptr gives it back. The tables are stale until the first update.
+int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->cost_on = false;
+    c->cost_fresh = false;
+    if (!q) {
+        c->cost_cells.release();
+        c->cost_dist2.release();
+        c->cost_masks.release();
+        c->cost_lut.release();
+        c->cost_lut_host = std::vector<unsigned char>();
+        return CM_OK;
+    }
+    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    const size_t words = static_cast<size_t>((c->map_info.ny + CM_COST_ROWS - 1) / CM_COST_ROWS) * c->map_info.nx;
+    const size_t n_lut = static_cast<size_t>(R) * R + 1;
+    if (!c->cost_cells.reserve(n_cells) || !c->cost_dist2.reserve(n_cells) || !c->cost_masks.reserve(2 * words) || !c->cost_lut.reserve(n_lut))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the cost layer");
+    c->cost_lut_host.assign(n_lut, 0);
+    cm_cost_table(c->map_params.cell, q->inscribed_radius, q->inflation_radius, q->cost_scaling, R, c->cost_lut_host.data());
+    HIP_TRY(c, hipMemcpyAsync(c->cost_lut, c->cost_lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->cost_params = *q;
+    c->cost_radius = R;
+    c->cost_on = true;
+    return CM_OK;
+}
+
+// dist2 and cost of the map's current image (cm_kernels_cost.hip; the semantics are in include/cloudmerge.h): the obstacle
+// words of every column, the carries between their blocks, then one pass over the rows that writes both tables. No host
+// round trip but the wait at the end, and no allocation: cm_map_cost_configure made them all.
+int map_cost_update(cm_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    CmCostDev g;
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.r2 = c->cost_radius * c->cost_radius;
+    g.inflate_unknown = (c->cost_params.flags & CM_COST_INFLATE_UNKNOWN) ? 1u : 0u;
+    uint32_t* masks = c->cost_masks;
+    uint32_t* carry = masks + static_cast<size_t>((g.ny + CM_COST_ROWS - 1) / CM_COST_ROWS) * g.nx;
+    hipStream_t st = c->stream;
+    c->prof_used = 0;
+    prof_mark(c, "k_cost_colmask");
+    cmk_cost_colmask(st, c->map_image, g, masks);
+    prof_mark(c, "k_cost_colcarry");
+    cmk_cost_colcarry(st, masks, g, carry);
+    prof_mark(c, "k_cost_rows");
+    cmk_cost_rows(st, c->map_image, masks, carry, c->cost_lut, g, c->cost_dist2, c->cost_cells);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->cost_fresh = true;
     return CM_OK;
 }
 

@@ -280,6 +280,19 @@ struct cm_ctx {
     uint64_t frame_serial = 0;           // counts the frames enqueued (enqueue, merge_tables): the frame at rest is this one
     uint64_t map_serial = 0;             // the frame integrated last (0: none since the configure call)
 
+    // Cost layer over the occupancy map (cm_kernels_cost.hip), configured by cm_map_cost_configure behind the map and
+    // recomputed by cm_map_cost_update from map_image. Buffers of its own, all allocated by the configure call; it lives and
+    // goes with the map (map_configure frees it).
+    bool cost_on = false;                // a cost layer is configured
+    bool cost_fresh = false;             // the two tables are those of the map's current image (cleared by map_integrate)
+    cm_cost_params cost_params{};
+    uint32_t cost_radius = 0;            // R: the table has R * R + 1 entries
+    DevBuf<unsigned char> cost_cells;    // the inflated cost: one byte per cell
+    DevBuf<uint32_t> cost_dist2;         // the squared distance: one word per cell
+    DevBuf<uint32_t> cost_masks;         // the column pass: ceil(ny / CM_COST_ROWS) * nx obstacle words, then as many carry words
+    DevBuf<unsigned char> cost_lut;      // the table in HBM
+    std::vector<unsigned char> cost_lut_host;   // and as it was built
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -391,6 +404,10 @@ int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r);
 int map_configure(cm_ctx* c, const cm_map_params* q);
 bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]);
 int map_integrate(cm_ctx* c, const float pose[12], const int v[2]);
+// The cost layer over the occupancy map. map_cost_configure: room for the map's window and the table of q at radius R cells
+// (nullptr: the buffers go). map_cost_update: dist2 and cost of the map's current image.
+int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R);
+int map_cost_update(cm_ctx* c);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

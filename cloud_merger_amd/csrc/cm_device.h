@@ -325,3 +325,19 @@ struct CmMapUpdateDev {
     uint32_t n_sensors;
     int32_t l_hit, l_miss, l_min, l_max, l_free, l_occ;
 };
+
+// Cost layer over the occupancy map (cm_kernels_cost.hip). The column pass works on blocks of CM_COST_ROWS rows: one bit per
+// row says whether the cell is an obstacle, so a block of one column is one 32-bit word. The row pass gives a workgroup of
+// CM_COST_BLOCK threads one row, which it walks in strips of CM_COST_BLOCK cells, with the row's squared vertical distances in
+// LDS: CM_COST_MAX_AXIS words, the widest window a cost layer takes. CM_COST_FAR stands for "no obstacle in this column" in
+// LDS: adding any dx * dx of a window to it neither overflows nor comes below it.
+#define CM_COST_ROWS 32
+#define CM_COST_BLOCK 256
+#define CM_COST_MAX_AXIS_DEV 2048
+#define CM_COST_FAR 0xF0000000u
+#define CM_COST_NO_ROW 0xFFFFu
+struct CmCostDev {
+    uint32_t nx, ny;
+    uint32_t r2;                       // R * R: the table has r2 + 1 entries
+    uint32_t inflate_unknown;
+};

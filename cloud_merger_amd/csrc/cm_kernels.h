@@ -253,3 +253,14 @@ void cmk_map_mark(hipStream_t s, const CmFrameDev* fd, const CmMapDev& g, const 
                   uint32_t* bits, uint32_t words, uint32_t n_sensors, uint32_t n_tiles);
 void cmk_map_update(hipStream_t s, const void* prev, void* next, const void* rays, const uint32_t* bits, uint32_t words,
                     const CmMapUpdateDev& u, void* image);
+
+// ---- cost layer over the occupancy map (cm_kernels_cost.hip) -------------------------------------------------------------------
+// image: the map's three-valued image, ny rows of nx bytes. masks: ceil(ny / CM_COST_ROWS) * nx words, bit r of word
+// (b, x) set iff cell (x, b * CM_COST_ROWS + r) is an obstacle (cmk_cost_colmask). carry: as many words, the nearest obstacle
+// row of column x above block b in the low half and below it in the high half, CM_COST_NO_ROW where there is none
+// (cmk_cost_colcarry). cmk_cost_rows writes dist2 (a word per cell) and cost (a byte per cell); lut holds g.r2 + 1 bytes.
+// g.nx and g.ny are at most CM_COST_MAX_AXIS_DEV (a larger window is not launched).
+void cmk_cost_colmask(hipStream_t s, const void* image, const CmCostDev& g, uint32_t* masks);
+void cmk_cost_colcarry(hipStream_t s, const uint32_t* masks, const CmCostDev& g, uint32_t* carry);
+void cmk_cost_rows(hipStream_t s, const void* image, const uint32_t* masks, const uint32_t* carry, const unsigned char* lut,
+                   const CmCostDev& g, uint32_t* dist2, unsigned char* cost);

@@ -206,6 +206,11 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
                                             c.map_l_min <= 0 && c.map_l_max >= 0;
         else if (key == "map_thresholds") ok = read(is, c.map_l_free, c.map_l_occ) && c.map_l_free < c.map_l_occ;
         else if (key == "map_ray_range") ok = read(is, c.map_ray_range);
+        else if (key == "map_inflation") ok = read(is, c.map_inscribed_radius, c.map_inflation_radius, c.map_cost_scaling) &&
+                                              std::isfinite(c.map_inscribed_radius) && c.map_inscribed_radius >= 0.0f &&
+                                              std::isfinite(c.map_inflation_radius) && std::isfinite(c.map_cost_scaling) && c.map_cost_scaling >= 0.0f &&
+                                              (c.map_inflation_radius == 0.0f || c.map_inflation_radius >= c.map_inscribed_radius);
+        else if (key == "map_inflate_unknown") ok = read_flag(is, &c.map_inflate_unknown);
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -283,6 +288,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
         const cm_map_params mp{cfg_.map_cell, cfg_.map_nx, cfg_.map_ny, cfg_.map_z_band[0], cfg_.map_z_band[1], cfg_.map_l_hit, cfg_.map_l_miss,
                                cfg_.map_l_min, cfg_.map_l_max, cfg_.map_l_free, cfg_.map_l_occ, cfg_.map_ray_range};
         if (cm_map_configure(ctx_, &mp) != CM_OK) refuse("cm_map_configure");
+        if (ctx_ && cfg_.map_inflation_radius > 0.0f) {         // the cost layer behind the map
+            const cm_cost_params cp{cfg_.map_inscribed_radius, cfg_.map_inflation_radius, cfg_.map_cost_scaling,
+                                    cfg_.map_inflate_unknown ? CM_COST_INFLATE_UNKNOWN : 0u};
+            if (cm_map_cost_configure(ctx_, &cp) != CM_OK) refuse("cm_map_cost_configure");
+        }
     }
     for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s)
         if (cm_set_sensor_time_field(ctx_, static_cast<uint32_t>(s), cfg_.time_field[s].offset, cfg_.time_field[s].type) != CM_OK)
@@ -420,9 +430,18 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
     int st = cm_map_integrate(ctx_, pose, &map_info_);
     if (st == CM_OK) st = cm_map_copy(ctx_, map_cells_.data(), n, nullptr);
     if (st == CM_OK) st = cm_map_occupancy_copy(ctx_, map_image_.data(), n, nullptr);
+    if (cfg_.map_inflation_radius > 0.0f) {
+        map_cost_.resize(n);
+        map_dist2_.resize(n);
+        if (st == CM_OK) st = cm_map_cost_update(ctx_, nullptr);
+        if (st == CM_OK) st = cm_map_cost_copy(ctx_, map_cost_.data(), n, nullptr);
+        if (st == CM_OK) st = cm_map_dist_copy(ctx_, map_dist2_.data(), n, nullptr);
+    }
     if (st != CM_OK) {
         map_cells_.clear();
         map_image_.clear();
+        map_cost_.clear();
+        map_dist2_.clear();
         set_error(cm_last_error(ctx_));
     }
     return st;

@@ -115,6 +115,11 @@ struct NodeConfig {
     int32_t map_l_hit = 85, map_l_miss = 40, map_l_min = -200, map_l_max = 350;
     int32_t map_l_free = -40, map_l_occ = 85;
     uint32_t map_ray_range = 0;
+    // Cost layer over that map (cm_map_cost_configure, cm_map_cost_update): costmap_2d's inflation layer and the exact distance
+    // field under it. Off by default (an inflation radius of 0). On (it needs map_cell > 0): the node configures the layer
+    // behind the map, updates it behind every integration and keeps the two tables until the next frame (map_cost(), map_dist2()).
+    float map_inscribed_radius = 0.0f, map_inflation_radius = 0.0f, map_cost_scaling = 0.0f;
+    bool map_inflate_unknown = false;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -155,6 +160,8 @@ struct NodeConfig {
 //   grid_cell > 0; grid_ray_range 0: to the return)
 //   map_cell <metres> | map_size <nx> <ny> | map_z_band <lo> <hi> | map_logodds <hit> <miss> <min> <max> |
 //   map_thresholds <free> <occ> | map_ray_range <cells>   (the occupancy map accumulated over the frames; map_cell 0: off)
+//   map_inflation <inscribed> <inflation> <scaling> | map_inflate_unknown <0|1>   (the cost layer over that map: radii in metres,
+//   the decay per metre; an inflation radius of 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -248,6 +255,10 @@ public:
     const std::vector<cm_map_cell>& map_cells() const { return map_cells_; }
     const std::vector<int8_t>& map_image() const { return map_image_; }
     const cm_map_info& map_info() const { return map_info_; }
+    // map_inflation with a radius > 0: the inflated cost (254 lethal, 253 inscribed, 255 unknown) and the squared distance in
+    // cells to the nearest occupied cell (CM_MAP_DIST_NONE: none in the window) of the same window cells, after the same frame.
+    const std::vector<uint8_t>& map_cost() const { return map_cost_; }
+    const std::vector<uint32_t>& map_dist2() const { return map_dist2_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -314,7 +325,9 @@ private:
     std::vector<cm_map_cell> map_cells_;
     std::vector<int8_t> map_image_;
     cm_map_info map_info_{};
-    int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies when the config asks for it
+    std::vector<uint8_t> map_cost_;
+    std::vector<uint32_t> map_dist2_;
+    int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it
     bool has_alignment_ = false;

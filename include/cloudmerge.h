@@ -713,6 +713,66 @@ CM_API int cm_map_device(cm_ctx* ctx, const void** dev_ptr, cm_map_info* info);
 /* Host copy of the image; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied). *info may be NULL. */
 CM_API int cm_map_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, cm_map_info* info);
 
+/* ---- cost layer over the occupancy map: exact distance field and inflated costmap (an extension) -------------------------
+ * The map's image is costmap_2d's obstacle layer. A planner plans on the layer above it, the inflation layer, and clearance
+ * checks want the distance field under that. The cost layer is configured once behind the map and recomputed on request from
+ * the map's current image; it yields two tables per window cell, dist2 (uint32_t) and cost (uint8_t), entry ix + iy * nx
+ * (DESIGN.md §23). A squared distance in cells is an integer and the table of step 3 is built on the host from an exponential
+ * that is spelled out (cm_ndt_math.hpp), so both tables are bit for bit a function of the image and the parameters.
+ * Input: the map's image I as cm_map_occupancy_copy returns it (ny x nx, entry ix + iy * nx) and the map's `cell`.
+ *   1. Obstacles. O = { c : I(c) == 100 }. Only cells of the window count: what scrolled out is forgotten, as the map
+ *      forgets it.
+ *   2. Distance field. dist2(c) = min over o in O of (cx - ox)^2 + (cy - oy)^2, in integer arithmetic; O empty gives
+ *      CM_MAP_DIST_NONE in every cell. With nx, ny <= CM_COST_MAX_AXIS the largest value is 2 * 2047^2, so uint32_t holds it.
+ *      The field is not truncated at the inflation radius: it is the whole window's exact transform.
+ *   3. Cost table, built on the host in double from four fp32 values widened to double, the map's cell, inscribed_radius,
+ *      inflation_radius and cost_scaling. R = (uint32_t)ceil(inflation_radius / cell); the table has R * R + 1 entries.
+ *      lut[0] = 254. For d2 >= 1, m = sqrt((double)d2) * cell (each operation rounded once): m <= inscribed_radius gives 253,
+ *      m > inflation_radius gives 0, anything else (uint8_t)floor(252.0 * cm_exp_neg(cost_scaling * (m - inscribed_radius))).
+ *      A d2 beyond the table has cost 0 (sqrt(R * R + 1) lies far more than a rounding above R for R <= 256, so this agrees
+ *      with the formula). This is costmap_2d::InflationLayer::computeCost with the exponential replaced by cm_exp_neg.
+ *   4. Cost. infl = dist2 <= R * R ? lut[dist2] : 0. I == 100: 254. I == 0: infl. I == -1: infl if infl >= 253, else 255
+ *      (NO_INFORMATION); with CM_COST_INFLATE_UNKNOWN the condition is infl > 0 (costmap_2d's inflate_unknown).
+ * cm_map_cost_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured map; a radius or the scaling that is
+ * not finite or is negative; inflation_radius < inscribed_radius; R > CM_COST_MAX_RADIUS_CELLS; unknown flag bits; a map
+ * wider or taller than CM_COST_MAX_AXIS cells (step 2's bound; nx * ny alone admits a window of 1 x 2^22); a frame in flight.
+ * R = 0 (a table of one entry) is legal. All memory of the layer is taken by cm_map_cost_configure (cost, dist2, the column
+ * pass's two tables, the cost table): no update call allocates. cm_map_cost_update is allowed before any integration (the
+ * image is all -1: dist2 all CM_MAP_DIST_NONE, cost all 255). The tables are stale from cm_map_cost_configure and from every
+ * cm_map_integrate until the next cm_map_cost_update: the copies and cm_map_cost_device then refuse with CM_BAD_ARG.
+ * cm_map_configure, in either form, frees the layer; like the map it survives merges, and neither the map's state, image and
+ * info nor any frame depends on whether it exists. With CM_FLAG_PROFILE, cm_get_stage_times after an update lists
+ * k_cost_colmask, k_cost_colcarry, k_cost_rows. Not modelled: a signed distance (inside obstacles dist2 is 0), the index of
+ * the nearest obstacle, obstacles outside the window, a footprint other than the inscribed radius, unknown cells as
+ * obstacles. */
+#define CM_MAP_DIST_NONE 0xFFFFFFFFu
+#define CM_COST_LETHAL 254
+#define CM_COST_INSCRIBED 253
+#define CM_COST_NO_INFORMATION 255
+#define CM_COST_INFLATE_UNKNOWN 1u
+#define CM_COST_MAX_RADIUS_CELLS 256
+#define CM_COST_MAX_AXIS 2048
+typedef struct cm_cost_params {        /* 16 bytes, no padding */
+    float inscribed_radius;            /* metres; finite, >= 0 */
+    float inflation_radius;            /* metres; finite, >= inscribed_radius; at most CM_COST_MAX_RADIUS_CELLS cells */
+    float cost_scaling;                /* 1 / metres; finite, >= 0 */
+    uint32_t flags;                    /* CM_COST_INFLATE_UNKNOWN or 0 */
+} cm_cost_params;
+/* Non-NULL parameters allocate the layer and build the table (the tables are stale until the first update); NULL frees it. */
+CM_API int cm_map_cost_configure(cm_ctx* ctx, const cm_cost_params* p);
+/* Computes dist2 and cost from the map's current image; *out (may be NULL) is the map's info. */
+CM_API int cm_map_cost_update(cm_ctx* ctx, cm_map_info* out);
+/* Host copies of the two tables; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied; *info, which may be
+ * NULL, is still written). */
+CM_API int cm_map_cost_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capacity_cells, cm_map_info* info);
+CM_API int cm_map_dist_copy(cm_ctx* ctx, uint32_t* host_dst, uint64_t capacity_cells, cm_map_info* info);
+/* The same tables in device memory owned by the context, valid until the next cm_map_cost_update, cm_map_integrate,
+ * cm_map_cost_configure or cm_map_configure. Either pointer argument may be NULL. */
+CM_API int cm_map_cost_device(cm_ctx* ctx, const void** cost, const void** dist2, cm_map_info* info);
+/* Host copy of the R * R + 1 bytes of step 3; *n (may be NULL) is that count. Fewer than that: CM_CAPACITY (nothing is
+ * copied, *n is still written). The table exists from cm_map_cost_configure on: staleness does not concern it. */
+CM_API int cm_map_cost_table_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capacity, uint64_t* n);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
