@@ -49,6 +49,7 @@ SYMBOLS = [
     "cm_result_grid_rays", "cm_result_grid_rays_device", "cm_grid_ray_occupancy_copy",
     "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy",
     "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
+    "cm_map_plan_configure", "cm_map_plan_update", "cm_map_plan_copy", "cm_map_plan_device", "cm_map_plan_path",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -269,6 +270,34 @@ class CostParams(C.Structure):
 
 assert C.sizeof(CostParams) == 16
 
+# plan layer behind the cost layer: navigation function and path extraction (cm_map_plan_configure, cm_map_plan_update, cm_map_plan_path)
+PLAN_UNREACHABLE = 0xFFFFFFFF
+PLAN_ALLOW_UNKNOWN = 1
+PATH_FOUND = 0
+PATH_UNREACHABLE = 1
+PATH_TRUNCATED = 2
+
+
+class PlanParams(C.Structure):
+    """cm_plan_params (16 bytes): neutral 1..255, the cost byte's factor in 1/256 (0..256), CM_PLAN_ALLOW_UNKNOWN or 0, the longest
+    path in cells."""
+    _fields_ = [("neutral", C.c_uint32), ("cost_factor_q8", C.c_uint32), ("flags", C.c_uint32), ("max_path_cells", C.c_uint32)]
+
+
+class PlanInfo(C.Structure):
+    """cm_plan_info (16 bytes): the goal's window cell and the number of sweeps of the last update."""
+    _fields_ = [("goal", C.c_uint32 * 2), ("n_sweeps", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class PathInfo(C.Structure):
+    """cm_path_info (32 bytes): the start's and the goal's window cells, the cells written, PATH_FOUND / PATH_UNREACHABLE /
+    PATH_TRUNCATED, pot(start)."""
+    _fields_ = [("start", C.c_uint32 * 2), ("goal", C.c_uint32 * 2), ("n_cells", C.c_uint32), ("status", C.c_uint32),
+                ("pot_start", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(PlanParams) == 16 and C.sizeof(PlanInfo) == 16 and C.sizeof(PathInfo) == 32
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -463,6 +492,11 @@ def load():
     L.cm_map_dist_copy.argtypes = [vp, vp, u64, C.POINTER(MapInfo)]
     L.cm_map_cost_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(MapInfo)]
     L.cm_map_cost_table_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.cm_map_plan_configure.argtypes = [vp, C.POINTER(PlanParams)]
+    L.cm_map_plan_update.argtypes = [vp, C.c_float, C.c_float, C.POINTER(PlanInfo), C.POINTER(MapInfo)]
+    L.cm_map_plan_copy.argtypes = [vp, vp, u64, C.POINTER(PlanInfo), C.POINTER(MapInfo)]
+    L.cm_map_plan_device.argtypes = [vp, C.POINTER(vp), C.POINTER(PlanInfo), C.POINTER(MapInfo)]
+    L.cm_map_plan_path.argtypes = [vp, C.c_float, C.c_float, vp, u64, C.POINTER(PathInfo)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -1001,6 +1035,58 @@ class CloudMerger:
         out = np.empty(n.value, dtype=np.uint8)
         self._check(self._lib.cm_map_cost_table_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_map_cost_table_copy")
         return out
+
+    # ---- plan layer behind the cost layer (cm_map_plan_configure / cm_map_plan_update / cm_map_plan_path) ----
+    def map_plan_configure(self, neutral=50, cost_factor_q8=205, allow_unknown=False, max_path_cells=None):
+        """Allocates the plan layer behind the configured cost layer: the shortest-path potential to a goal over the cost table
+        (a cell weighs neutral + ((cost * cost_factor_q8) >> 8), 5 per straight and 7 per diagonal step, 253..255 impassable,
+        255 as 252 with allow_unknown) and paths of at most max_path_cells cells (None: nx * ny). neutral None frees the layer."""
+        if neutral is None:
+            self._check(self._lib.cm_map_plan_configure(self._ctx, None), "cm_map_plan_configure")
+            return
+        if max_path_cells is None:
+            info = MapInfo()
+            st = self._lib.cm_map_copy(self._ctx, None, 0, C.byref(info))
+            if st != CAPACITY:
+                self._check(st, "cm_map_copy")
+            max_path_cells = info.nx * info.ny
+        p = PlanParams(int(neutral), int(cost_factor_q8), PLAN_ALLOW_UNKNOWN if allow_unknown else 0, int(max_path_cells))
+        self._check(self._lib.cm_map_plan_configure(self._ctx, C.byref(p)), "cm_map_plan_configure")
+        self._plan_max_path_cells = p.max_path_cells
+
+    def map_plan_update(self, x, y):
+        """Computes the potential of every window cell to the goal at world (x, y) from the cost layer's fresh table. Returns the
+        PlanInfo."""
+        info = PlanInfo()
+        self._check(self._lib.cm_map_plan_update(self._ctx, float(x), float(y), C.byref(info), None), "cm_map_plan_update")
+        return info
+
+    def map_plan(self):
+        """((ny, nx) uint32 pot, PlanInfo) of the last update: the exact cost of the cheapest path to the goal (PLAN_UNREACHABLE
+        where there is none)."""
+        info, m = PlanInfo(), MapInfo()
+        st = self._lib.cm_map_plan_copy(self._ctx, None, 0, C.byref(info), C.byref(m))
+        if st != CAPACITY:
+            self._check(st, "cm_map_plan_copy")
+        n = m.nx * m.ny
+        pot = np.empty(n, dtype=np.uint32)
+        self._check(self._lib.cm_map_plan_copy(self._ctx, pot.ctypes.data, n, C.byref(info), C.byref(m)), "cm_map_plan_copy")
+        return pot.reshape(m.ny, m.nx), info
+
+    def map_plan_device(self):
+        """(pot device pointer, PlanInfo, MapInfo) of the same table, owned by the context and valid until the next update,
+        integrate or configure call."""
+        pot, info, m = C.c_void_p(), PlanInfo(), MapInfo()
+        self._check(self._lib.cm_map_plan_device(self._ctx, C.byref(pot), C.byref(info), C.byref(m)), "cm_map_plan_device")
+        return pot.value, info, m
+
+    def map_path(self, x, y):
+        """((n_cells,) uint32 window cell indices ix + iy * nx, PathInfo): the path by descent from world (x, y) to the goal of
+        the last update, start first; empty with PATH_UNREACHABLE, the first max_path_cells cells with PATH_TRUNCATED."""
+        info = PathInfo()
+        cells = np.empty(getattr(self, "_plan_max_path_cells", 0), dtype=np.uint32)      # (one walk: no path is longer)
+        self._check(self._lib.cm_map_plan_path(self._ctx, float(x), float(y), cells.ctypes.data, cells.shape[0], C.byref(info)), "cm_map_plan_path")
+        return cells[:info.n_cells].copy(), info
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

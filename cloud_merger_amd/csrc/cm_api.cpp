@@ -1060,6 +1060,97 @@ int cm_map_cost_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uint
     return CM_OK;
 }
 
+static_assert(sizeof(cm_plan_params) == 16 && sizeof(cm_plan_info) == 16 && sizeof(cm_path_info) == 32, "the plan layer's three structs");
+static_assert(CM_PATH_FOUND == CM_PLAN_PATH_FOUND_DEV && CM_PATH_UNREACHABLE == CM_PLAN_PATH_UNREACHABLE_DEV &&
+              CM_PATH_TRUNCATED == CM_PLAN_PATH_TRUNCATED_DEV, "k_plan_path writes cm_path_info's status values");
+
+int cm_map_plan_configure(cm_ctx* c, const cm_plan_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+        if (p->neutral < 1u || p->neutral > 255u) return fail(c, CM_BAD_ARG, "neutral must lie in 1..255");
+        if (p->cost_factor_q8 > 256u) return fail(c, CM_BAD_ARG, "cost_factor_q8 must lie in 0..256");
+        if (p->flags & ~CM_PLAN_ALLOW_UNKNOWN) return fail(c, CM_BAD_ARG, "unknown flag bits");
+        const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+        if (p->max_path_cells < 1u || p->max_path_cells > n) return fail(c, CM_BAD_ARG, "max_path_cells must lie in 1..nx * ny");
+        const uint64_t w_max = p->neutral + ((252u * p->cost_factor_q8) >> 8);
+        if (7u * w_max * (n - 1u) > 0xFFFFFFFEull)
+            return fail(c, CM_BAD_ARG, "the window is too large for these weights: 7 * w_max * (nx * ny - 1) exceeds 0xFFFFFFFE");
+    }
+    return map_plan_configure(c, p);
+}
+
+// The refusals every call on a configured plan layer shares; the reads also refuse a stale potential.
+static int plan_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
+    if (read && c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
+    return CM_OK;
+}
+
+int cm_map_plan_update(cm_ctx* c, float gx, float gy, cm_plan_info* out, cm_map_info* map) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = plan_check(c, false)) return e;
+    if (const int e = cost_check(c, true)) return e;
+    uint32_t goal[2];
+    if (!map_window_cell(c, gx, gy, goal)) return fail(c, CM_BAD_ARG, "the goal is not finite or lies outside the map's window");
+    if (const int e = map_plan_update(c, goal)) return e;
+    if (out) *out = c->plan_info;
+    if (map) *map = c->map_info;
+    return CM_OK;
+}
+
+int cm_map_plan_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_plan_info* info, cm_map_info* map) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = plan_check(c, true)) return e;
+    if (info) *info = c->plan_info;
+    if (map) *map = c->map_info;
+    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "potential destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->plan_pot, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(uint32_t);
+    return CM_OK;
+}
+
+int cm_map_plan_device(cm_ctx* c, const void** pot, cm_plan_info* info, cm_map_info* map) {
+    if (!c) return CM_BAD_ARG;
+    if (pot) *pot = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = plan_check(c, true)) return e;
+    if (info) *info = c->plan_info;
+    if (map) *map = c->map_info;
+    if (pot) *pot = c->plan_pot;
+    return CM_OK;
+}
+
+int cm_map_plan_path(cm_ctx* c, float sx, float sy, uint32_t* host_dst, uint64_t capacity, cm_path_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = plan_check(c, true)) return e;
+    uint32_t start[2], head[CM_PLAN_PATH_HEAD];
+    if (!map_window_cell(c, sx, sy, start)) return fail(c, CM_BAD_ARG, "the start is not finite or lies outside the map's window");
+    if (const int e = map_plan_path(c, start, head)) return e;
+    const uint64_t n = head[0];
+    if (info) *info = cm_path_info{{start[0], start[1]}, {c->plan_info.goal[0], c->plan_info.goal[1]}, head[0], head[1], head[2], 0u};
+    if (n > capacity) return fail(c, CM_CAPACITY, "path destination too small");
+    if (n == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->plan_path + CM_PLAN_PATH_HEAD, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(uint32_t);
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");
 static_assert(CM_NORMAL_VALID == CM_NORMAL_VALID_DEV && CM_NORMAL_MAX_K == 64, "the kernels' flag and largest list");
 

@@ -1,11 +1,12 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
-// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
 // (cm_devbuf.hpp) that grow on demand and go with the context, so a call here states what it needs and frees nothing.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -470,6 +471,17 @@ bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]) {
     return map_world_axis(pose[3], inv, &v[0]) && map_world_axis(pose[7], inv, &v[1]);
 }
 
+bool map_window_cell(const cm_ctx* c, float x, float y, uint32_t cell[2]) {
+    const float inv = 1.0f / c->map_params.cell;
+    int g[2];
+    if (!map_world_axis(x, inv, &g[0]) || !map_world_axis(y, inv, &g[1])) return false;
+    const int64_t ix = static_cast<int64_t>(g[0]) - c->map_info.anchor[0], iy = static_cast<int64_t>(g[1]) - c->map_info.anchor[1];
+    if (ix < 0 || ix >= static_cast<int64_t>(c->map_info.nx) || iy < 0 || iy >= static_cast<int64_t>(c->map_info.ny)) return false;
+    cell[0] = static_cast<uint32_t>(ix);
+    cell[1] = static_cast<uint32_t>(iy);
+    return true;
+}
+
 // The last frame into the occupancy map (cm_kernels_map.hip; the semantics are in include/cloudmerge.h). The window's anchor
 // and the sensors' origin cells are step 1 on the host (fp32, explicit casts, as grid_rays does). One clear of the bitmaps
 // and the scratch ray table, a pass over the frame's raw points in place (the E and H bitmaps), k_ray_cast unchanged on the
@@ -545,6 +557,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->map_info.sensors_cast = cast;
     c->map_serial = c->frame_serial;
     c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
+    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -552,6 +565,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
 // built here (cm_cost_table.hpp) and uploaded. nullptr gives it back. The tables are stale until the first update.
 int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
+    if (const int e = map_plan_configure(c, nullptr)) return e;        // the plan layer goes with the cost layer it reads
     c->cost_on = false;
     c->cost_fresh = false;
     if (!q) {
@@ -602,6 +616,113 @@ int map_cost_update(cm_ctx* c) {
     HIP_TRY(c, hipStreamSynchronize(st));
     collect_stage_times(c);
     c->cost_fresh = true;
+    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_cost_update";
+    return CM_OK;
+}
+
+// The plan layer's memory, all of it: the potential, the sweep counters and the two tile flag tables, the path buffer and
+// the page-locked words the host reads counters and a path's head from. nullptr gives it back. pot is stale until the first
+// update.
+int map_plan_configure(cm_ctx* c, const cm_plan_params* q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->plan_on = false;
+    c->plan_stale = "the potential is stale: no cm_map_plan_update since cm_map_plan_configure";
+    std::memset(&c->plan_info, 0, sizeof c->plan_info);
+    if (!q) {
+        c->plan_pot.release();
+        c->plan_words.release();
+        c->plan_path.release();
+        c->plan_host.release();
+        return CM_OK;
+    }
+    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    const size_t n_tiles = static_cast<size_t>((c->map_info.nx + CM_PLAN_TILE - 1) / CM_PLAN_TILE) * ((c->map_info.ny + CM_PLAN_TILE - 1) / CM_PLAN_TILE);
+    if (!c->plan_pot.reserve(n_cells) || !c->plan_words.reserve(CM_PLAN_BATCH + 2 * n_tiles) ||
+        !c->plan_path.reserve(CM_PLAN_PATH_HEAD + static_cast<size_t>(q->max_path_cells)) || !c->plan_host.reserve(std::max(CM_PLAN_BATCH, CM_PLAN_PATH_HEAD)))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the plan layer");
+    c->plan_params = *q;
+    c->plan_on = true;
+    return CM_OK;
+}
+
+namespace {
+
+CmPlanDev plan_dev(const cm_ctx* c, const uint32_t goal[2]) {
+    CmPlanDev g;
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.tiles_x = (g.nx + CM_PLAN_TILE - 1) / CM_PLAN_TILE;
+    g.tiles_y = (g.ny + CM_PLAN_TILE - 1) / CM_PLAN_TILE;
+    g.goal = goal[0] + goal[1] * g.nx;
+    g.neutral = c->plan_params.neutral;
+    g.factor_q8 = c->plan_params.cost_factor_q8;
+    g.allow_unknown = (c->plan_params.flags & CM_PLAN_ALLOW_UNKNOWN) ? 1u : 0u;
+    return g;
+}
+
+}  // namespace
+
+// pot of the cost layer's current table for one goal (cm_kernels_plan.hip; the semantics are in include/cloudmerge.h): the
+// fill, then sweeps over the dirty tiles until one reports that no tile changed. The sweeps go out CM_PLAN_BATCH at a time,
+// each with a counter of its own, and the host reads the batch's counters once: a sweep with no dirty tile costs a launch of
+// workgroups that leave at once, a read per sweep a round trip. The two flag tables swap roles per sweep. Every sweep but the
+// last fixes the final word of at least one more cell, so nx * ny sweeps suffice; reaching that bound is CM_INTERNAL. No
+// allocation: cm_map_plan_configure made them all.
+int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const CmPlanDev g = plan_dev(c, goal);
+    const size_t n_tiles = static_cast<size_t>(g.tiles_x) * g.tiles_y;
+    const uint64_t bound = static_cast<uint64_t>(g.nx) * g.ny;
+    uint32_t* counters = c->plan_words;
+    uint32_t* flags = counters + CM_PLAN_BATCH;
+    hipStream_t st = c->stream;
+    c->plan_stale = "the potential is stale: the last cm_map_plan_update failed";
+    c->prof_used = 0;
+    prof_mark(c, "k_plan_init");
+    cmk_plan_init(st, g, c->plan_pot, flags);
+    prof_mark(c, "k_plan_sweep");
+    uint64_t launched = 0, n_sweeps = 0;
+    while (!n_sweeps && launched < bound) {
+        const uint32_t batch = static_cast<uint32_t>(std::min<uint64_t>(CM_PLAN_BATCH, bound - launched));
+        HIP_TRY(c, hipMemsetAsync(counters, 0, CM_PLAN_BATCH * sizeof(uint32_t), st));
+        for (uint32_t b = 0; b < batch; ++b) {
+            const size_t cur = static_cast<size_t>((launched + b) & 1u) * n_tiles;
+            cmk_plan_sweep(st, c->cost_cells, g, c->plan_pot, flags + cur, flags + (n_tiles - cur), counters + b);
+        }
+        HIP_TRY(c, hipMemcpyAsync(c->plan_host, counters, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        for (uint32_t b = 0; b < batch && !n_sweeps; ++b)
+            if (c->plan_host[b] == 0u) n_sweeps = launched + b + 1;
+        launched += batch;
+    }
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));     // (the end mark only: the last batch was waited for)
+    collect_stage_times(c);
+    if (!n_sweeps) return fail(c, CM_INTERNAL, "the sweeps did not reach the fixed point within nx * ny launches");
+    c->plan_info.goal[0] = goal[0];
+    c->plan_info.goal[1] = goal[1];
+    c->plan_info.n_sweeps = static_cast<uint32_t>(n_sweeps);
+    c->plan_stale = nullptr;
+    return CM_OK;
+}
+
+// The walk of step 6 from the start's window cell into plan_path, and its head to the host: one launch, one copy of the head
+// and one wait here; cm_map_plan_path then copies the n_cells words the head announces and waits a second time.
+int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const CmPlanDev g = plan_dev(c, c->plan_info.goal);
+    hipStream_t st = c->stream;
+    c->prof_used = 0;
+    prof_mark(c, "k_plan_path");
+    cmk_plan_path(st, c->cost_cells, c->plan_pot, g, start[0] + start[1] * g.nx, c->plan_params.max_path_cells, c->plan_path);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->plan_host, c->plan_path, CM_PLAN_PATH_HEAD * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    std::memcpy(head, c->plan_host, CM_PLAN_PATH_HEAD * sizeof(uint32_t));
+    if (head[1] == CM_PLAN_PATH_BROKEN_DEV) return fail(c, CM_INTERNAL, "the potential is not a fixed point: a reachable cell has no step");
     return CM_OK;
 }
 

@@ -293,6 +293,18 @@ struct cm_ctx {
     DevBuf<unsigned char> cost_lut;      // the table in HBM
     std::vector<unsigned char> cost_lut_host;   // and as it was built
 
+    // Plan layer behind the cost layer (cm_kernels_plan.hip), configured by cm_map_plan_configure and recomputed by
+    // cm_map_plan_update from cost_cells. Buffers of its own, all allocated by the configure call; it lives and goes with the
+    // cost layer (map_cost_configure frees it).
+    bool plan_on = false;                // a plan layer is configured
+    const char* plan_stale = nullptr;    // why pot is not that of the current cost table and a goal; nullptr: it is
+    cm_plan_params plan_params{};
+    cm_plan_info plan_info{};
+    DevBuf<uint32_t> plan_pot;           // the potential: one word per cell
+    DevBuf<uint32_t> plan_words;         // CM_PLAN_BATCH sweep counters, then two tables of tile flags
+    DevBuf<uint32_t> plan_path;          // CM_PLAN_PATH_HEAD words, then max_path_cells cells
+    PinnedBuf<uint32_t> plan_host;       // what the host reads back: the counters of a batch, a path's head
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -403,11 +415,19 @@ int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r);
 // under `pose` into the map, whose window is then anchored around the vehicle cell v.
 int map_configure(cm_ctx* c, const cm_map_params* q);
 bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]);
+// The window cell of a world position (step 1 per axis, minus the anchor); false: not finite, no such cell, or outside the window.
+bool map_window_cell(const cm_ctx* c, float x, float y, uint32_t cell[2]);
 int map_integrate(cm_ctx* c, const float pose[12], const int v[2]);
 // The cost layer over the occupancy map. map_cost_configure: room for the map's window and the table of q at radius R cells
 // (nullptr: the buffers go). map_cost_update: dist2 and cost of the map's current image.
 int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R);
 int map_cost_update(cm_ctx* c);
+// The plan layer behind the cost layer. map_plan_configure: room for the map's window and q's longest path (nullptr: the
+// buffers go). map_plan_update: pot for the goal's window cell. map_plan_path: the walk from the start's window cell into
+// plan_path; head receives its CM_PLAN_PATH_HEAD words.
+int map_plan_configure(cm_ctx* c, const cm_plan_params* q);
+int map_plan_update(cm_ctx* c, const uint32_t goal[2]);
+int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

@@ -341,3 +341,25 @@ struct CmCostDev {
     uint32_t r2;                       // R * R: the table has r2 + 1 entries
     uint32_t inflate_unknown;
 };
+
+// Plan layer behind the cost layer (cm_kernels_plan.hip). A sweep gives a workgroup of CM_PLAN_BLOCK threads one tile of
+// CM_PLAN_TILE x CM_PLAN_TILE cells, one thread per cell, with the tile and one ring of cells around it in LDS. The host
+// launches CM_PLAN_BATCH sweeps between two reads of their changed-tile counters, and a thread relaxes its cell CM_PLAN_INNER
+// times between two barriers of its workgroup (both measured). k_plan_path's output begins with
+// CM_PLAN_PATH_HEAD words (n_cells, status, pot(start), 0); the status values are cm_path_info's, BROKEN is the kernel's own.
+#define CM_PLAN_TILE 32
+#define CM_PLAN_BLOCK 1024
+#define CM_PLAN_BATCH 8
+#define CM_PLAN_INNER 4
+#define CM_PLAN_PATH_HEAD 4
+#define CM_PLAN_PATH_FOUND_DEV 0u
+#define CM_PLAN_PATH_UNREACHABLE_DEV 1u
+#define CM_PLAN_PATH_TRUNCATED_DEV 2u
+#define CM_PLAN_PATH_BROKEN_DEV 0xFFFFFFFFu
+struct CmPlanDev {
+    uint32_t nx, ny;
+    uint32_t tiles_x, tiles_y;
+    uint32_t goal;                     // window cell ix + iy * nx
+    uint32_t neutral, factor_q8;
+    uint32_t allow_unknown;
+};

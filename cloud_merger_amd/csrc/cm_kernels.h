@@ -264,3 +264,14 @@ void cmk_cost_colmask(hipStream_t s, const void* image, const CmCostDev& g, uint
 void cmk_cost_colcarry(hipStream_t s, const uint32_t* masks, const CmCostDev& g, uint32_t* carry);
 void cmk_cost_rows(hipStream_t s, const void* image, const uint32_t* masks, const uint32_t* carry, const unsigned char* lut,
                    const CmCostDev& g, uint32_t* dist2, unsigned char* cost);
+
+// ---- plan layer behind the cost layer (cm_kernels_plan.hip) ----------------------------------------------------------------------
+// cost: the cost layer's table, ny rows of nx bytes. pot: a word per cell. flags: two tables of g.tiles_x * g.tiles_y words,
+// one per tile, not zero: dirty. cmk_plan_init fills pot and both tables (the first is the first sweep's `cur`).
+// cmk_plan_sweep relaxes the tiles that are dirty in cur, clears their words there, marks in next and adds the number of tiles
+// that changed to *counter. cmk_plan_path walks from `start` and writes CM_PLAN_PATH_HEAD words and at most max_cells cells to out.
+void cmk_plan_init(hipStream_t s, const CmPlanDev& g, uint32_t* pot, uint32_t* flags);
+void cmk_plan_sweep(hipStream_t s, const unsigned char* cost, const CmPlanDev& g, uint32_t* pot, uint32_t* cur, uint32_t* next,
+                    uint32_t* counter);
+void cmk_plan_path(hipStream_t s, const unsigned char* cost, const uint32_t* pot, const CmPlanDev& g, uint32_t start, uint32_t max_cells,
+                   uint32_t* out);

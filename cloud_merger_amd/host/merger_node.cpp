@@ -211,6 +211,9 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
                                               std::isfinite(c.map_inflation_radius) && std::isfinite(c.map_cost_scaling) && c.map_cost_scaling >= 0.0f &&
                                               (c.map_inflation_radius == 0.0f || c.map_inflation_radius >= c.map_inscribed_radius);
         else if (key == "map_inflate_unknown") ok = read_flag(is, &c.map_inflate_unknown);
+        else if (key == "map_plan") ok = read(is, c.map_plan_neutral, c.map_plan_factor_q8) && c.map_plan_neutral <= 255u && c.map_plan_factor_q8 <= 256u;
+        else if (key == "map_plan_allow_unknown") ok = read_flag(is, &c.map_plan_allow_unknown);
+        else if (key == "map_goal") { ok = read(is, c.map_goal[0], c.map_goal[1]) && std::isfinite(c.map_goal[0]) && std::isfinite(c.map_goal[1]); c.map_has_goal = ok; }
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -249,6 +252,9 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     for (auto& t : stamp_ns_) t.store(0);
     for (auto& f : submitted_) f.store(0);
     for (auto& f : consumed_) f.store(0);
+    goal_[0] = cfg_.map_goal[0];
+    goal_[1] = cfg_.map_goal[1];
+    has_goal_ = cfg_.map_has_goal;
     if (cfg_.sensors.empty() || cfg_.sensors.size() > CM_MAX_SENSORS) {
         error_ = "sensor count must be 1..CM_MAX_SENSORS";
         return;
@@ -292,6 +298,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
             const cm_cost_params cp{cfg_.map_inscribed_radius, cfg_.map_inflation_radius, cfg_.map_cost_scaling,
                                     cfg_.map_inflate_unknown ? CM_COST_INFLATE_UNKNOWN : 0u};
             if (cm_map_cost_configure(ctx_, &cp) != CM_OK) refuse("cm_map_cost_configure");
+            if (ctx_ && cfg_.map_plan_neutral > 0u) {              // the plan layer behind the cost layer
+                const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
+                                        cfg_.map_nx * cfg_.map_ny};
+                if (cm_map_plan_configure(ctx_, &pp) != CM_OK) refuse("cm_map_plan_configure");
+            }
         }
     }
     for (size_t s = 0; ctx_ && s < cfg_.sensors.size(); ++s)
@@ -417,6 +428,15 @@ int CloudMergerNode::set_pose(const float pose[12]) {
     return CM_OK;
 }
 
+int CloudMergerNode::set_goal(float x, float y) {
+    if (!std::isfinite(x) || !std::isfinite(y)) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(pose_mu_);
+    goal_[0] = x;
+    goal_[1] = y;
+    has_goal_ = true;
+    return CM_OK;
+}
+
 int CloudMergerNode::map_of_frame(const cm_result& r) {
     if (!(cfg_.map_cell > 0.0f) || r.status != CM_OK) return CM_OK;     // (a frame without a voxel grid leaves the map as it is)
     float pose[12];
@@ -437,14 +457,43 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
         if (st == CM_OK) st = cm_map_cost_copy(ctx_, map_cost_.data(), n, nullptr);
         if (st == CM_OK) st = cm_map_dist_copy(ctx_, map_dist2_.data(), n, nullptr);
     }
+    map_potential_.clear();
+    map_path_.clear();
+    map_path_info_ = cm_path_info{};
     if (st != CM_OK) {
         map_cells_.clear();
         map_image_.clear();
         map_cost_.clear();
         map_dist2_.clear();
         set_error(cm_last_error(ctx_));
+        return st;
     }
-    return st;
+    // The plan behind the cost update: the potential to the goal, then the path from the vehicle cell. A goal or a vehicle
+    // outside the window is the caller's to mend (the window has scrolled away from it): the frame stands, the plan is empty.
+    float goal[2];
+    bool has_goal;
+    {
+        std::lock_guard<std::mutex> lk(pose_mu_);
+        goal[0] = goal_[0];
+        goal[1] = goal_[1];
+        has_goal = has_goal_;
+    }
+    if (cfg_.map_inflation_radius > 0.0f && cfg_.map_plan_neutral > 0u && has_goal) {
+        map_potential_.resize(n);
+        map_path_.resize(n);
+        int ps = cm_map_plan_update(ctx_, goal[0], goal[1], &map_plan_info_, nullptr);
+        if (ps == CM_OK) ps = cm_map_plan_copy(ctx_, map_potential_.data(), n, nullptr, nullptr);
+        if (ps == CM_OK) ps = cm_map_plan_path(ctx_, pose[3], pose[7], map_path_.data(), n, &map_path_info_);
+        if (ps == CM_OK) map_path_.resize(map_path_info_.n_cells);
+        else {
+            map_potential_.clear();
+            map_path_.clear();
+            map_path_info_ = cm_path_info{};
+            set_error(cm_last_error(ctx_));
+            if (ps != CM_BAD_ARG) return ps;
+        }
+    }
+    return CM_OK;
 }
 
 int CloudMergerNode::normals_of_frame(const cm_result& r) {

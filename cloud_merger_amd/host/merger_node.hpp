@@ -120,6 +120,14 @@ struct NodeConfig {
     // behind the map, updates it behind every integration and keeps the two tables until the next frame (map_cost(), map_dist2()).
     float map_inscribed_radius = 0.0f, map_inflation_radius = 0.0f, map_cost_scaling = 0.0f;
     bool map_inflate_unknown = false;
+    // Plan layer behind that cost layer (cm_map_plan_configure, cm_map_plan_update, cm_map_plan_path): the shortest-path
+    // potential to a goal and the path from the vehicle cell. Off by default (neutral 0). On (it needs an inflation radius
+    // > 0): the node configures the layer behind the cost layer and, once a goal is known (map_goal, set_goal()), updates the
+    // potential behind every cost update and walks the path from the pose's cell (map_potential(), map_path()).
+    uint32_t map_plan_neutral = 0, map_plan_factor_q8 = 205;
+    bool map_plan_allow_unknown = false;
+    bool map_has_goal = false;
+    float map_goal[2] = {0.0f, 0.0f};                // world frame, metres
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -162,6 +170,8 @@ struct NodeConfig {
 //   map_thresholds <free> <occ> | map_ray_range <cells>   (the occupancy map accumulated over the frames; map_cell 0: off)
 //   map_inflation <inscribed> <inflation> <scaling> | map_inflate_unknown <0|1>   (the cost layer over that map: radii in metres,
 //   the decay per metre; an inflation radius of 0: off)
+//   map_plan <neutral> <factor_q8> | map_plan_allow_unknown <0|1> | map_goal <x> <y>   (the plan layer behind that cost layer:
+//   neutral 1..255 and the cost's factor in 1/256, 0..256; neutral 0: off; the goal in the world frame, metres)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -259,6 +269,15 @@ public:
     // cells to the nearest occupied cell (CM_MAP_DIST_NONE: none in the window) of the same window cells, after the same frame.
     const std::vector<uint8_t>& map_cost() const { return map_cost_; }
     const std::vector<uint32_t>& map_dist2() const { return map_dist2_; }
+    // map_plan with neutral > 0 and a goal: the potential of the same window cells to the goal (CM_PLAN_UNREACHABLE: none) and
+    // the path from the vehicle cell, window cell indices ix + iy * nx, start first (map_path_info(): its status and cost), after
+    // the same frame. Both empty while there is no goal, and after a frame whose goal or vehicle lay outside the window
+    // (error() says which). set_goal replaces the configured goal from the next tick on; CM_BAD_ARG if it is not finite.
+    int set_goal(float x, float y);
+    const std::vector<uint32_t>& map_potential() const { return map_potential_; }
+    const std::vector<uint32_t>& map_path() const { return map_path_; }
+    const cm_plan_info& map_plan_info() const { return map_plan_info_; }
+    const cm_path_info& map_path_info() const { return map_path_info_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -327,6 +346,11 @@ private:
     cm_map_info map_info_{};
     std::vector<uint8_t> map_cost_;
     std::vector<uint32_t> map_dist2_;
+    float goal_[2] = {0.0f, 0.0f};                 // (under pose_mu_)
+    bool has_goal_ = false;
+    std::vector<uint32_t> map_potential_, map_path_;
+    cm_plan_info map_plan_info_{};
+    cm_path_info map_path_info_{};
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

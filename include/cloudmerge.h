@@ -773,6 +773,88 @@ CM_API int cm_map_cost_device(cm_ctx* ctx, const void** cost, const void** dist2
  * copied, *n is still written). The table exists from cm_map_cost_configure on: staleness does not concern it. */
 CM_API int cm_map_cost_table_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capacity, uint64_t* n);
 
+/* ---- plan layer behind the cost layer: navigation function and path extraction (an extension) ---------------------------
+ * In a costmap_2d stack the step behind the inflation layer is navfn / global_planner: a potential over the costmap from a
+ * goal, then a path from any start by descent. The plan layer is configured once behind the cost layer and recomputed on
+ * request; it yields one table per window cell, pot (uint32_t, entry ix + iy * nx), and paths over it. Every
+ * step cost is a positive integer, so the Bellman equations of step 4 have exactly one solution: pot is bit for bit a
+ * function of the cost table, the parameters and the goal, whatever the order in which the device relaxes cells.
+ * Input: the cost layer's fresh cost table (ny x nx bytes, entry ix + iy * nx) and the map's info.
+ *   1. Traversal weight w(c). v is the cost byte of c. v == 255 (unknown): impassable; with CM_PLAN_ALLOW_UNKNOWN, v := 252
+ *      instead. v >= 253 (inscribed or lethal): impassable. Otherwise w = neutral + ((v * cost_factor_q8) >> 8) in integer
+ *      arithmetic, so w >= 1 for every passable cell. navfn's 50 and 0.8 are neutral 50 and cost_factor_q8 205.
+ *   2. Goal. (x, y) are fp32 world coordinates in the map's world frame. The absolute cell is step 1 of the map's semantics
+ *      per axis, floorf(x * inv) with the same existence test; the window cell is that cell minus the map's anchor. A goal
+ *      that is not finite, whose cell does not exist or that lies outside the window: CM_BAD_ARG. The goal cell has potential
+ *      0 whatever its cost byte, and counts as passable in step 3's corner rule.
+ *   3. Steps. Cells are 8-connected; direction d = 0..7 is (dx, dy) = (1,0), (1,1), (0,1), (-1,1), (-1,0), (-1,-1), (0,-1),
+ *      (1,-1). A step costs k * w(the cell left behind when walking towards the goal), k = 5 for a straight step and 7 for a
+ *      diagonal one. No corner cutting: a diagonal step between c and n exists only if both cells that share an edge with
+ *      both of them are passable.
+ *   4. Potential. pot(goal) = 0. For every other passable c, pot(c) is the minimum over the existing steps to a neighbour n
+ *      with pot(n) defined of pot(n) + k * w(c). Impassable and unreachable cells hold CM_PLAN_UNREACHABLE. This is the exact
+ *      shortest-path cost, and it is unique.
+ *   5. Range. A simple path has at most nx * ny - 1 steps. With w_max = neutral + ((252 * cost_factor_q8) >> 8),
+ *      cm_map_plan_configure refuses with CM_BAD_ARG if 7 * w_max * (nx * ny - 1) > 0xFFFFFFFE, evaluated in 64 bits: a
+ *      potential could then not be told from CM_PLAN_UNREACHABLE. With 50 / 205 this admits about 2.4 M cells: 1000 x 1000
+ *      passes, 2048 x 2048 needs a smaller neutral or factor.
+ *   6. Path. The start is given like the goal; outside the window or not finite: CM_BAD_ARG. pot(start) ==
+ *      CM_PLAN_UNREACHABLE: status CM_PATH_UNREACHABLE, zero cells. Otherwise c = start, and while c is not the goal the next
+ *      cell is the neighbour n over the existing steps with pot(n) defined that minimises pot(n) + k * w(c); ties go to the
+ *      lowest direction number. The output is the window cell indices ix + iy * nx, start first and goal last. By step 4 that
+ *      minimum equals pot(c): the path's step costs sum to pot(start), pot strictly decreases along it, and it ends. A path
+ *      longer than max_path_cells (1..nx * ny, given at configure time) writes its first max_path_cells cells with status
+ *      CM_PATH_TRUNCATED.
+ * cm_map_plan_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured cost layer; neutral outside 1..255;
+ * cost_factor_q8 above 256; unknown flag bits; max_path_cells 0 or above nx * ny; step 5's range rule; a frame in flight.
+ * All memory of the layer is taken by cm_map_plan_configure (pot, the tile flags and sweep counters, the path buffer and its
+ * page-locked host words): no update or path call allocates. pot is stale from cm_map_plan_configure and from every
+ * cm_map_integrate and cm_map_cost_update until the next cm_map_plan_update, which itself refuses a stale cost layer: the
+ * copies, cm_map_plan_device and cm_map_plan_path then refuse with CM_BAD_ARG. cm_map_cost_configure and cm_map_configure,
+ * in either form, free the layer; like the map it survives merges, and nothing else depends on whether it exists. With
+ * CM_FLAG_PROFILE, cm_get_stage_times after an update lists k_plan_init and k_plan_sweep (all sweeps and the reads of their
+ * counters as one stage), after a path call k_plan_path. Not modelled: navfn's quadratic interpolation and sub-cell gradient
+ * paths, A*, path smoothing, several goals per update, goals or paths outside the window. */
+#define CM_PLAN_UNREACHABLE 0xFFFFFFFFu
+#define CM_PLAN_ALLOW_UNKNOWN 1u
+/* cm_path_info.status (values, not bits; unrelated to cm_result.path_flags) */
+#define CM_PATH_FOUND 0u
+#define CM_PATH_UNREACHABLE 1u
+#define CM_PATH_TRUNCATED 2u
+typedef struct cm_plan_params {        /* 16 bytes, no padding */
+    uint32_t neutral;                  /* 1..255 */
+    uint32_t cost_factor_q8;           /* 0..256: the cost byte's factor in 1/256 */
+    uint32_t flags;                    /* CM_PLAN_ALLOW_UNKNOWN or 0 */
+    uint32_t max_path_cells;           /* 1..nx * ny: the longest path cm_map_plan_path writes */
+} cm_plan_params;
+typedef struct cm_plan_info {          /* 16 bytes */
+    uint32_t goal[2];                  /* the goal's window cell (ix, iy) */
+    uint32_t n_sweeps;                 /* launches of the sweep up to the first that changed nothing (not a function of the
+                                          input alone: tiles of one sweep may or may not see one another's words) */
+    uint32_t _pad;
+} cm_plan_info;
+typedef struct cm_path_info {          /* 32 bytes */
+    uint32_t start[2], goal[2];        /* window cells (ix, iy) */
+    uint32_t n_cells;                  /* cells of the path that were written (0: unreachable) */
+    uint32_t status;                   /* CM_PATH_FOUND, CM_PATH_UNREACHABLE or CM_PATH_TRUNCATED */
+    uint32_t pot_start;                /* pot(start) */
+    uint32_t _pad;
+} cm_path_info;
+/* Non-NULL parameters allocate the layer (pot is stale until the first update); NULL frees it. */
+CM_API int cm_map_plan_configure(cm_ctx* ctx, const cm_plan_params* p);
+/* Computes pot for the goal at world (gx, gy) from the cost layer's fresh table. *out and *map (either may be NULL) are the
+ * plan's and the map's info. CM_INTERNAL: nx * ny sweeps did not reach the fixed point (they provably do). */
+CM_API int cm_map_plan_update(cm_ctx* ctx, float gx, float gy, cm_plan_info* out, cm_map_info* map);
+/* Host copy of pot; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied; *info and *map, which may be
+ * NULL, are still written). */
+CM_API int cm_map_plan_copy(cm_ctx* ctx, uint32_t* host_dst, uint64_t capacity_cells, cm_plan_info* info, cm_map_info* map);
+/* The same table in device memory owned by the context, valid until the next cm_map_plan_update, cm_map_cost_update,
+ * cm_map_integrate or configure call of the three layers. */
+CM_API int cm_map_plan_device(cm_ctx* ctx, const void** pot, cm_plan_info* info, cm_map_info* map);
+/* The path of step 6 from world (sx, sy) to the goal of the last update; capacity in cells. A capacity below n_cells:
+ * CM_CAPACITY (nothing is copied, *info is still written). *info may be NULL. */
+CM_API int cm_map_plan_path(cm_ctx* ctx, float sx, float sy, uint32_t* host_dst, uint64_t capacity, cm_path_info* info);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
