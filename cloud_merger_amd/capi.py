@@ -50,6 +50,7 @@ SYMBOLS = [
     "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy",
     "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
     "cm_map_plan_configure", "cm_map_plan_update", "cm_map_plan_copy", "cm_map_plan_device", "cm_map_plan_path",
+    "cm_map_traj_configure", "cm_map_traj_evaluate", "cm_map_traj_copy", "cm_map_traj_device", "cm_traj_directions",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -298,6 +299,49 @@ class PathInfo(C.Structure):
 
 assert C.sizeof(PlanParams) == 16 and C.sizeof(PlanInfo) == 16 and C.sizeof(PathInfo) == 32
 
+# rollout layer behind the plan layer: sampled velocity commands scored over cost and pot (cm_map_traj_configure, cm_map_traj_evaluate)
+TRAJ_MAX_SAMPLES = 16384
+TRAJ_MAX_STEPS = 256
+TRAJ_MAX_FOOT = 256
+TRAJ_HEADINGS = 4096
+TRAJ_ALLOW_UNKNOWN = 1
+TRAJ_NONE = 0xFFFFFFFF
+TRAJ_VALID = 0
+TRAJ_COLLISION = 1
+TRAJ_OFF_MAP = 2
+TRAJ_NO_POTENTIAL = 3
+
+
+class TrajParams(C.Structure):
+    """cm_traj_params (24 bytes): the sample counts nv x nw (at most TRAJ_MAX_SAMPLES together), the steps of a rollout
+    (1..TRAJ_MAX_STEPS), the two weights of the total, CM_TRAJ_ALLOW_UNKNOWN or 0."""
+    _fields_ = [("nv", C.c_uint32), ("nw", C.c_uint32), ("n_steps", C.c_uint32), ("occ_scale", C.c_uint32), ("goal_scale", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class TrajWindow(C.Structure):
+    """cm_traj_window (32 bytes): the start pose (x, y, yaw), the velocity window v_lo..v_hi and w_lo..w_hi, dt per step."""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("yaw", C.c_float), ("v_lo", C.c_float), ("v_hi", C.c_float), ("w_lo", C.c_float),
+                ("w_hi", C.c_float), ("dt", C.c_float)]
+
+
+class TrajScore(C.Structure):
+    """cm_traj_score (32 bytes): TRAJ_VALID / TRAJ_COLLISION / TRAJ_OFF_MAP / TRAJ_NO_POTENTIAL, the pose that ended the
+    trajectory, the largest cost byte met, pot at the end, the total, the last (or the bad) pose's centre."""
+    _fields_ = [("status", C.c_uint32), ("bad_step", C.c_uint32), ("occ", C.c_uint32), ("pot_end", C.c_uint32), ("total", C.c_uint64),
+                ("end_x", C.c_float), ("end_y", C.c_float)]
+
+
+class TrajInfo(C.Structure):
+    """cm_traj_info (24 bytes): the best entry (TRAJ_NONE: no valid one), the number of valid entries, the best entry's
+    command, the start's window cell."""
+    _fields_ = [("best", C.c_uint32), ("n_valid", C.c_uint32), ("best_v", C.c_float), ("best_w", C.c_float), ("start", C.c_uint32 * 2)]
+
+
+TRAJ_SCORE_DTYPE = np.dtype([("status", "<u4"), ("bad_step", "<u4"), ("occ", "<u4"), ("pot_end", "<u4"), ("total", "<u8"),
+                             ("end_x", "<f4"), ("end_y", "<f4")])
+assert C.sizeof(TrajParams) == 24 and C.sizeof(TrajWindow) == 32 and C.sizeof(TrajScore) == 32 == TRAJ_SCORE_DTYPE.itemsize and C.sizeof(TrajInfo) == 24
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -497,6 +541,11 @@ def load():
     L.cm_map_plan_copy.argtypes = [vp, vp, u64, C.POINTER(PlanInfo), C.POINTER(MapInfo)]
     L.cm_map_plan_device.argtypes = [vp, C.POINTER(vp), C.POINTER(PlanInfo), C.POINTER(MapInfo)]
     L.cm_map_plan_path.argtypes = [vp, C.c_float, C.c_float, vp, u64, C.POINTER(PathInfo)]
+    L.cm_map_traj_configure.argtypes = [vp, C.POINTER(TrajParams), vp, u32]
+    L.cm_map_traj_evaluate.argtypes = [vp, C.POINTER(TrajWindow), C.POINTER(TrajInfo)]
+    L.cm_map_traj_copy.argtypes = [vp, vp, u64, C.POINTER(TrajInfo)]
+    L.cm_map_traj_device.argtypes = [vp, C.POINTER(vp), C.POINTER(TrajInfo)]
+    L.cm_traj_directions.argtypes = [vp, u64]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -533,6 +582,15 @@ def box_directions(n):
     if st != OK:
         raise CloudMergeError(st, "cm_box_directions")
     return out[: int(n)]
+
+
+def traj_directions():
+    """(TRAJ_HEADINGS, 2) float32: (cos, sin) of the rollout layer's binary headings — the table it uploads (cm_traj_directions)."""
+    out = np.empty((TRAJ_HEADINGS, 2), dtype=np.float32)
+    st = load().cm_traj_directions(out.ctypes.data, out.shape[0])
+    if st != OK:
+        raise CloudMergeError(st, "cm_traj_directions")
+    return out
 
 
 def status_string(status):
@@ -1087,6 +1145,41 @@ class CloudMerger:
         cells = np.empty(getattr(self, "_plan_max_path_cells", 0), dtype=np.uint32)      # (one walk: no path is longer)
         self._check(self._lib.cm_map_plan_path(self._ctx, float(x), float(y), cells.ctypes.data, cells.shape[0], C.byref(info)), "cm_map_plan_path")
         return cells[:info.n_cells].copy(), info
+
+    # ---- rollout layer behind the plan layer (cm_map_traj_configure / cm_map_traj_evaluate) ----
+    def map_traj_configure(self, nv=None, nw=1, n_steps=1, footprint=((0.0, 0.0),), occ_scale=1, goal_scale=1, allow_unknown=False):
+        """Allocates the rollout layer behind the configured plan layer: nv x nw velocity samples rolled n_steps forward, the
+        footprint ((n_foot, 2) body-frame points, x forward, y left, metres) checked against the cost table at every pose, a
+        survivor's total occ_scale * (largest cost byte met) + goal_scale * pot(end). nv None frees the layer."""
+        if nv is None:
+            self._check(self._lib.cm_map_traj_configure(self._ctx, None, None, 0), "cm_map_traj_configure")
+            return
+        foot = np.ascontiguousarray(footprint, dtype=np.float32).reshape(-1, 2)
+        p = TrajParams(int(nv), int(nw), int(n_steps), int(occ_scale), int(goal_scale), TRAJ_ALLOW_UNKNOWN if allow_unknown else 0)
+        self._check(self._lib.cm_map_traj_configure(self._ctx, C.byref(p), foot.ctypes.data, foot.shape[0]), "cm_map_traj_configure")
+        self._traj_n = p.nv * p.nw
+
+    def map_traj_evaluate(self, x, y, yaw, v=(0.0, 0.0), w=(0.0, 0.0), dt=0.1):
+        """Rolls and scores every sample from the pose (x, y, yaw) over the velocity window v = (lo, hi), w = (lo, hi) with steps
+        of dt seconds, from the fresh cost table and pot. Returns the TrajInfo."""
+        win = TrajWindow(float(x), float(y), float(yaw), float(v[0]), float(v[1]), float(w[0]), float(w[1]), float(dt))
+        info = TrajInfo()
+        self._check(self._lib.cm_map_traj_evaluate(self._ctx, C.byref(win), C.byref(info)), "cm_map_traj_evaluate")
+        return info
+
+    def map_traj(self):
+        """((nv * nw,) TRAJ_SCORE_DTYPE scores, TrajInfo) of the last evaluate; sample (i, j) is entry i * nw + j."""
+        info = TrajInfo()
+        out = np.empty(getattr(self, "_traj_n", 0), dtype=TRAJ_SCORE_DTYPE)
+        self._check(self._lib.cm_map_traj_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_traj_copy")
+        return out, info
+
+    def map_traj_device(self):
+        """(scores device pointer, TrajInfo) of the same table, owned by the context and valid until the next evaluate, update,
+        integrate or configure call."""
+        ptr, info = C.c_void_p(), TrajInfo()
+        self._check(self._lib.cm_map_traj_device(self._ctx, C.byref(ptr), C.byref(info)), "cm_map_traj_device")
+        return ptr.value, info
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

@@ -1151,6 +1151,106 @@ int cm_map_plan_path(cm_ctx* c, float sx, float sy, uint32_t* host_dst, uint64_t
     return CM_OK;
 }
 
+static_assert(sizeof(cm_traj_params) == 24 && sizeof(cm_traj_window) == 32 && sizeof(cm_traj_score) == 32 && sizeof(cm_traj_info) == 24,
+              "the rollout layer's four structs");
+static_assert(sizeof(CmTrajScoreDev) == sizeof(cm_traj_score) && offsetof(cm_traj_score, total) == offsetof(CmTrajScoreDev, total) &&
+                  offsetof(cm_traj_score, end_x) == offsetof(CmTrajScoreDev, end_x), "k_traj_roll writes cm_traj_score");
+static_assert(CM_TRAJ_VALID == CM_TRAJ_VALID_DEV && CM_TRAJ_COLLISION == CM_TRAJ_COLLISION_DEV && CM_TRAJ_OFF_MAP == CM_TRAJ_OFF_MAP_DEV &&
+                  CM_TRAJ_NO_POTENTIAL == CM_TRAJ_NO_POTENTIAL_DEV && CM_TRAJ_HEADINGS == CM_TRAJ_HEADINGS_DEV &&
+                  CM_TRAJ_MAX_SAMPLES == CM_TRAJ_MAX_SAMPLES_DEV && CM_TRAJ_MAX_STEPS == CM_TRAJ_MAX_STEPS_DEV && CM_TRAJ_MAX_FOOT == CM_TRAJ_MAX_FOOT_DEV,
+              "the kernels' constants");
+
+int cm_traj_directions(float* cos_sin, uint64_t capacity_pairs) {
+    if (!cos_sin) return CM_BAD_ARG;
+    if (capacity_pairs < CM_TRAJ_HEADINGS) return CM_CAPACITY;
+    std::memcpy(cos_sin, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float));
+    return CM_OK;
+}
+
+int cm_map_traj_configure(cm_ctx* c, const cm_traj_params* p, const float* foot_xy, uint32_t n_foot) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!p) return map_traj_configure(c, nullptr, nullptr, 0);
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
+    if (p->nv < 1u || p->nw < 1u || static_cast<uint64_t>(p->nv) * p->nw > CM_TRAJ_MAX_SAMPLES)
+        return fail(c, CM_BAD_ARG, "nv and nw must be at least 1 and nv * nw at most CM_TRAJ_MAX_SAMPLES");
+    if (p->n_steps < 1u || p->n_steps > CM_TRAJ_MAX_STEPS) return fail(c, CM_BAD_ARG, "n_steps must lie in 1..CM_TRAJ_MAX_STEPS");
+    if (p->flags & ~CM_TRAJ_ALLOW_UNKNOWN) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    if (n_foot < 1u || n_foot > CM_TRAJ_MAX_FOOT) return fail(c, CM_BAD_ARG, "n_foot must lie in 1..CM_TRAJ_MAX_FOOT");
+    if (!foot_xy) return fail(c, CM_BAD_ARG, "no footprint");
+    for (uint32_t i = 0; i < 2u * n_foot; ++i)
+        if (!std::isfinite(foot_xy[i])) return fail(c, CM_BAD_ARG, "a footprint coordinate is not finite");
+    return map_traj_configure(c, p, foot_xy, n_foot);
+}
+
+// The refusals every call on a configured rollout layer shares; the reads also refuse stale scores.
+static int traj_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
+    if (!c->traj_on) return fail(c, CM_BAD_ARG, "no rollout layer (cm_map_traj_configure first)");
+    if (read && c->traj_stale) return fail(c, CM_BAD_ARG, c->traj_stale);
+    return CM_OK;
+}
+
+int cm_map_traj_evaluate(cm_ctx* c, const cm_traj_window* w, cm_traj_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = traj_check(c, false)) return e;
+    if (c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
+    if (!w) return fail(c, CM_BAD_ARG, "no window");
+    for (const float v : {w->x, w->y, w->yaw, w->v_lo, w->v_hi, w->w_lo, w->w_hi, w->dt})
+        if (!std::isfinite(v)) return fail(c, CM_BAD_ARG, "a window value is not finite");
+    if (w->v_hi < w->v_lo) return fail(c, CM_BAD_ARG, "v_hi is below v_lo");
+    if (w->w_hi < w->w_lo) return fail(c, CM_BAD_ARG, "w_hi is below w_lo");
+    if (!(w->dt > 0.0f)) return fail(c, CM_BAD_ARG, "dt must be above 0");
+    if (std::fabs(w->yaw) > 1024.0f) return fail(c, CM_BAD_ARG, "|yaw| is above 1024");
+    uint32_t start[2];
+    if (!map_window_cell(c, w->x, w->y, start)) return fail(c, CM_BAD_ARG, "the start's cell does not exist or lies outside the map's window");
+    // (traj_info holds the last command by value: a refusal below leaves the fresh scores and their info alone)
+    std::vector<float>& sv = c->traj_v;
+    std::vector<float>& sw = c->traj_w;
+    traj_samples(w->v_lo, w->v_hi, c->traj_params.nv, sv.data());
+    traj_samples(w->w_lo, w->w_hi, c->traj_params.nw, sw.data());
+    for (const float v : sv)
+        if (!std::isfinite(v) || !std::isfinite(static_cast<float>(v * w->dt))) return fail(c, CM_BAD_ARG, "a sample or its step length is not finite");
+    for (const float wj : sw)
+        if (!std::isfinite(wj) || std::fabs(static_cast<double>(wj) * static_cast<double>(w->dt)) >= 3.141592653589793)
+            return fail(c, CM_BAD_ARG, "a turn of pi or more per step: |w_j * dt| must stay below pi");
+    if (const int e = map_traj_evaluate(c, *w, start)) return e;
+    if (out) *out = c->traj_info;
+    return CM_OK;
+}
+
+int cm_map_traj_copy(cm_ctx* c, cm_traj_score* host_dst, uint64_t capacity, cm_traj_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = traj_check(c, true)) return e;
+    if (info) *info = c->traj_info;
+    const uint64_t n = static_cast<uint64_t>(c->traj_params.nv) * c->traj_params.nw;
+    if (n > capacity) return fail(c, CM_CAPACITY, "score destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->traj_scores, n * sizeof(cm_traj_score), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_traj_score);
+    return CM_OK;
+}
+
+int cm_map_traj_device(cm_ctx* c, const void** scores, cm_traj_info* info) {
+    if (!c) return CM_BAD_ARG;
+    if (scores) *scores = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = traj_check(c, true)) return e;
+    if (info) *info = c->traj_info;
+    if (scores) *scores = c->traj_scores;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");
 static_assert(CM_NORMAL_VALID == CM_NORMAL_VALID_DEV && CM_NORMAL_MAX_K == 64, "the kernels' flag and largest list");
 

@@ -1,7 +1,7 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
-// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path) and the rollout layer behind the plan (map_traj_configure, map_traj_evaluate). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
@@ -558,6 +558,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->map_serial = c->frame_serial;
     c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_integrate";
+    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -617,6 +618,7 @@ int map_cost_update(cm_ctx* c) {
     collect_stage_times(c);
     c->cost_fresh = true;
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_cost_update";
+    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_cost_update";
     return CM_OK;
 }
 
@@ -625,6 +627,7 @@ int map_cost_update(cm_ctx* c) {
 // update.
 int map_plan_configure(cm_ctx* c, const cm_plan_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
+    if (const int e = map_traj_configure(c, nullptr, nullptr, 0)) return e;   // the rollout layer goes with the plan layer it reads
     c->plan_on = false;
     c->plan_stale = "the potential is stale: no cm_map_plan_update since cm_map_plan_configure";
     std::memset(&c->plan_info, 0, sizeof c->plan_info);
@@ -677,6 +680,7 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
     uint32_t* flags = counters + CM_PLAN_BATCH;
     hipStream_t st = c->stream;
     c->plan_stale = "the potential is stale: the last cm_map_plan_update failed";
+    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_plan_update";
     c->prof_used = 0;
     prof_mark(c, "k_plan_init");
     cmk_plan_init(st, g, c->plan_pot, flags);
@@ -723,6 +727,130 @@ int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]) {
     collect_stage_times(c);
     std::memcpy(head, c->plan_host, CM_PLAN_PATH_HEAD * sizeof(uint32_t));
     if (head[1] == CM_PLAN_PATH_BROKEN_DEV) return fail(c, CM_INTERNAL, "the potential is not a fixed point: a reachable cell has no step");
+    return CM_OK;
+}
+
+// Step 2 of the rollout layer: CM_TRAJ_HEADINGS (cos, sin) pairs as box_direction_table builds its own, with the four axes
+// set exactly. Built by the first caller and kept.
+const float* traj_direction_table() {
+    static const std::vector<float> table = [] {
+        std::vector<float> t(2 * CM_TRAJ_HEADINGS);
+        const double step = 6.283185307179586 / 4096.0;
+        for (uint32_t a = 0; a < CM_TRAJ_HEADINGS; ++a) {
+            const double th = static_cast<double>(a) * step;
+            t[2 * a] = static_cast<float>(std::cos(th));
+            t[2 * a + 1] = static_cast<float>(std::sin(th));
+        }
+        const float axes[4][2] = {{1.0f, 0.0f}, {0.0f, 1.0f}, {-1.0f, 0.0f}, {0.0f, -1.0f}};
+        for (uint32_t k = 0; k < 4; ++k) {
+            t[2 * (k * 1024u)] = axes[k][0];
+            t[2 * (k * 1024u) + 1] = axes[k][1];
+        }
+        return t;
+    }();
+    return table.data();
+}
+
+// Step 1's samples: lo + (float)i * ((hi - lo) / (float)(n - 1)), every operation rounded to fp32 on its own.
+void traj_samples(float lo, float hi, uint32_t n, float* out) {
+    out[0] = lo;
+    if (n == 1) return;
+    const float step = static_cast<float>(static_cast<float>(hi - lo) / static_cast<float>(n - 1u));
+    for (uint32_t i = 1; i < n; ++i) out[i] = static_cast<float>(lo + static_cast<float>(static_cast<float>(i) * step));
+}
+
+// The rollout layer's memory, all of it: the scores, the info words and the two sample tables, the heading table and the
+// footprint (both uploaded here), the page-locked words an evaluate uploads from and reads back into. nullptr gives it back.
+// The scores are stale until the first evaluate.
+int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->traj_on = false;
+    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since cm_map_traj_configure";
+    std::memset(&c->traj_info, 0, sizeof c->traj_info);
+    if (!q) {
+        c->traj_scores.release();
+        c->traj_words.release();
+        c->traj_const.release();
+        c->traj_host.release();
+        c->traj_v = std::vector<float>();
+        c->traj_w = std::vector<float>();
+        return CM_OK;
+    }
+    const size_t n = static_cast<size_t>(q->nv) * q->nw, n_tab = static_cast<size_t>(q->nv) + q->nw;
+    // (the page-locked words also stage the footprint for its upload below)
+    if (!c->traj_scores.reserve(n) || !c->traj_words.reserve(CM_TRAJ_INFO_WORDS + n_tab) || !c->traj_const.reserve(2 * CM_TRAJ_HEADINGS + 2 * static_cast<size_t>(n_foot)) ||
+        !c->traj_host.reserve(CM_TRAJ_INFO_WORDS + std::max(n_tab, 2 * static_cast<size_t>(n_foot))))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the rollout layer");
+    c->traj_v.assign(q->nv, 0.0f);
+    c->traj_w.assign(q->nw, 0.0f);
+    std::memcpy(c->traj_host + CM_TRAJ_INFO_WORDS, foot_xy, 2 * static_cast<size_t>(n_foot) * sizeof(float));
+    HIP_TRY(c, hipMemcpyAsync(c->traj_const, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->traj_const + 2 * CM_TRAJ_HEADINGS, c->traj_host + CM_TRAJ_INFO_WORDS, 2 * static_cast<size_t>(n_foot) * sizeof(float),
+                              hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->traj_params = *q;
+    c->traj_n_foot = n_foot;
+    c->traj_on = true;
+    return CM_OK;
+}
+
+// The scores of every sample of the window from the start's window cell (cm_kernels_traj.hip; the semantics are in
+// include/cloudmerge.h). Step 1 on the host: the samples, the step lengths and the heading increments, written into the
+// page-locked words. One upload, two launches, one copy of the info words back and one wait; no allocation:
+// cm_map_traj_configure made them all.
+int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_traj_params& q = c->traj_params;
+    const double K = 4294967296.0 / 6.283185307179586;
+    CmTrajDev g;
+    g.x = w.x;
+    g.y = w.y;
+    g.inv = 1.0f / c->map_params.cell;
+    g.ax = c->map_info.anchor[0];
+    g.ay = c->map_info.anchor[1];
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.h0 = static_cast<uint32_t>(static_cast<int64_t>(std::rint(static_cast<double>(w.yaw) * K)));
+    g.nv = q.nv;
+    g.nw = q.nw;
+    g.n_steps = q.n_steps;
+    g.n_foot = c->traj_n_foot;
+    g.occ_scale = q.occ_scale;
+    g.goal_scale = q.goal_scale;
+    g.allow_unknown = (q.flags & CM_TRAJ_ALLOW_UNKNOWN) ? 1u : 0u;
+    uint32_t* const up = c->traj_host + CM_TRAJ_INFO_WORDS;
+    for (uint32_t i = 0; i < q.nv; ++i) {
+        const float s = static_cast<float>(c->traj_v[i] * w.dt);
+        std::memcpy(up + i, &s, sizeof s);
+    }
+    for (uint32_t j = 0; j < q.nw; ++j)
+        up[q.nv + j] = static_cast<uint32_t>(static_cast<int64_t>(std::rint((static_cast<double>(c->traj_w[j]) * static_cast<double>(w.dt)) * K)));
+    uint32_t* const info = c->traj_words;
+    uint32_t* const tab = info + CM_TRAJ_INFO_WORDS;
+    const uint32_t n = q.nv * q.nw;
+    hipStream_t st = c->stream;
+    c->traj_stale = "the scores are stale: the last cm_map_traj_evaluate failed";
+    c->prof_used = 0;
+    HIP_TRY(c, hipMemcpyAsync(tab, up, (static_cast<size_t>(q.nv) + q.nw) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    prof_mark(c, "k_traj_roll");
+    cmk_traj_roll(st, c->cost_cells, c->plan_pot, g, reinterpret_cast<const float*>(tab), tab + q.nv, c->traj_const, c->traj_const + 2 * CM_TRAJ_HEADINGS,
+                  c->traj_scores);
+    prof_mark(c, "k_traj_best");
+    cmk_traj_best(st, c->traj_scores, n, info);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->traj_host, info, CM_TRAJ_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    const uint32_t best = c->traj_host[0];
+    if (best != CM_TRAJ_NONE && best >= n) return fail(c, CM_INTERNAL, "the best entry lies outside the table");
+    c->traj_info.best = best;
+    c->traj_info.n_valid = c->traj_host[1];
+    c->traj_info.best_v = best == CM_TRAJ_NONE ? 0.0f : c->traj_v[best / q.nw];
+    c->traj_info.best_w = best == CM_TRAJ_NONE ? 0.0f : c->traj_w[best % q.nw];
+    c->traj_info.start[0] = start[0];
+    c->traj_info.start[1] = start[1];
+    c->traj_stale = nullptr;
     return CM_OK;
 }
 

@@ -305,6 +305,20 @@ struct cm_ctx {
     DevBuf<uint32_t> plan_path;          // CM_PLAN_PATH_HEAD words, then max_path_cells cells
     PinnedBuf<uint32_t> plan_host;       // what the host reads back: the counters of a batch, a path's head
 
+    // Rollout layer behind the plan layer (cm_kernels_traj.hip), configured by cm_map_traj_configure and evaluated by
+    // cm_map_traj_evaluate from cost_cells and plan_pot. Buffers of its own, all allocated by the configure call; it lives and
+    // goes with the plan layer (map_plan_configure frees it).
+    bool traj_on = false;                // a rollout layer is configured
+    const char* traj_stale = nullptr;    // why the scores are not those of the current tables and a window; nullptr: they are
+    cm_traj_params traj_params{};
+    uint32_t traj_n_foot = 0;
+    cm_traj_info traj_info{};
+    DevBuf<CmTrajScoreDev> traj_scores;  // nv * nw records
+    DevBuf<uint32_t> traj_words;         // CM_TRAJ_INFO_WORDS info words, then nv step lengths (fp32) and nw heading increments
+    DevBuf<float> traj_const;            // the heading table (2 * CM_TRAJ_HEADINGS floats), then the footprint (2 * n_foot)
+    PinnedBuf<uint32_t> traj_host;       // CM_TRAJ_INFO_WORDS words read back, then the nv + nw words an evaluate uploads
+    std::vector<float> traj_v, traj_w;   // the samples of the last evaluate (nv and nw entries from the configure call on)
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -428,6 +442,14 @@ int map_cost_update(cm_ctx* c);
 int map_plan_configure(cm_ctx* c, const cm_plan_params* q);
 int map_plan_update(cm_ctx* c, const uint32_t goal[2]);
 int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]);
+// The rollout layer behind the plan layer. traj_direction_table: the 2 * CM_TRAJ_HEADINGS floats of step 2 (built once).
+// traj_samples: the n samples of step 1 between lo and hi. map_traj_configure: room for q's samples and the footprint, which
+// is uploaded with the heading table (nullptr: the buffers go). map_traj_evaluate: the scores and traj_info for a window that
+// cm_map_traj_evaluate has checked, from the start's window cell.
+const float* traj_direction_table();
+void traj_samples(float lo, float hi, uint32_t n, float* out);
+int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot);
+int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

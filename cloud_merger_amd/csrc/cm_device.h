@@ -363,3 +363,42 @@ struct CmPlanDev {
     uint32_t neutral, factor_q8;
     uint32_t allow_unknown;
 };
+
+// Rollout layer behind the plan layer (cm_kernels_traj.hip). k_traj_roll gives one wave one trajectory, CM_TRAJ_WAVES of them
+// to a workgroup; the wave issues the cost-byte loads of CM_TRAJ_STEP_BATCH poses before it reduces any of them, and reads the
+// heading table through the caches (CM_TRAJ_DIRS_LDS 1: every workgroup stages it in LDS first; both batch sizes and both
+// table routes were measured). k_traj_best reduces the records in one workgroup of CM_TRAJ_BEST_BLOCK threads
+// and writes CM_TRAJ_INFO_WORDS words (best, n_valid). The status values are cm_traj_score's.
+#ifndef CM_TRAJ_STEP_BATCH
+#define CM_TRAJ_STEP_BATCH 4
+#endif
+#ifndef CM_TRAJ_DIRS_LDS
+#define CM_TRAJ_DIRS_LDS 0
+#endif
+#define CM_TRAJ_WAVES 4
+#define CM_TRAJ_BEST_BLOCK 1024
+#define CM_TRAJ_INFO_WORDS 2
+#define CM_TRAJ_HEADINGS_DEV 4096
+#define CM_TRAJ_MAX_SAMPLES_DEV 16384
+#define CM_TRAJ_MAX_STEPS_DEV 256
+#define CM_TRAJ_MAX_FOOT_DEV 256
+#define CM_TRAJ_VALID_DEV 0u
+#define CM_TRAJ_COLLISION_DEV 1u
+#define CM_TRAJ_OFF_MAP_DEV 2u
+#define CM_TRAJ_NO_POTENTIAL_DEV 3u
+struct CmTrajDev {
+    float x, y;                        // the start
+    float inv;                         // 1.0f / cell
+    int32_t ax, ay;                    // the map's anchor
+    uint32_t nx, ny;
+    uint32_t h0;                       // the start heading, a binary angle
+    uint32_t nv, nw;
+    uint32_t n_steps, n_foot;
+    uint32_t occ_scale, goal_scale;
+    uint32_t allow_unknown;
+};
+struct CmTrajScoreDev {                // cm_traj_score
+    uint32_t status, bad_step, occ, pot_end;
+    unsigned long long total;
+    float end_x, end_y;
+};

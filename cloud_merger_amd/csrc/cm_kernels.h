@@ -275,3 +275,11 @@ void cmk_plan_sweep(hipStream_t s, const unsigned char* cost, const CmPlanDev& g
                     uint32_t* counter);
 void cmk_plan_path(hipStream_t s, const unsigned char* cost, const uint32_t* pot, const CmPlanDev& g, uint32_t start, uint32_t max_cells,
                    uint32_t* out);
+
+// ---- rollout layer behind the plan layer (cm_kernels_traj.hip) --------------------------------------------------------------------
+// cost, pot: the cost and the plan layer's tables. steps: g.nv step lengths s_i (fp32). dh: g.nw heading increments. dirs:
+// CM_TRAJ_HEADINGS_DEV (cos, sin) pairs. foot: g.n_foot (bx, by) pairs. cmk_traj_roll writes g.nv * g.nw records, entry
+// i * g.nw + j; cmk_traj_best reduces them to CM_TRAJ_INFO_WORDS words (best, n_valid).
+void cmk_traj_roll(hipStream_t s, const unsigned char* cost, const uint32_t* pot, const CmTrajDev& g, const float* steps, const uint32_t* dh,
+                   const float* dirs, const float* foot, CmTrajScoreDev* out);
+void cmk_traj_best(hipStream_t s, const CmTrajScoreDev* scores, uint32_t n, uint32_t* info);

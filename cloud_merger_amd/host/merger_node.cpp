@@ -13,6 +13,26 @@
 
 namespace cloudmerge {
 
+bool traj_footprint_lattice(float x_back, float x_front, float half_width, float cell, std::vector<float>* xy) {
+    const double h = 0.5 * static_cast<double>(cell), len = static_cast<double>(x_front) - x_back, wid = 2.0 * static_cast<double>(half_width);
+    uint64_t n_x = static_cast<uint64_t>(std::ceil(len / h)) + 1u, n_y = static_cast<uint64_t>(std::ceil(wid / h)) + 1u;
+    const bool coarsened = n_x * n_y > CM_TRAJ_MAX_FOOT;
+    if (coarsened) {
+        const double scale = std::sqrt(static_cast<double>(CM_TRAJ_MAX_FOOT) / (static_cast<double>(n_x) * static_cast<double>(n_y)));
+        n_x = std::max<uint64_t>(1u, static_cast<uint64_t>(static_cast<double>(n_x) * scale));
+        n_y = std::max<uint64_t>(1u, static_cast<uint64_t>(static_cast<double>(n_y) * scale));
+        n_x = std::min<uint64_t>(n_x, CM_TRAJ_MAX_FOOT);               // (one of the two was raised to 1: a strip)
+        n_y = std::min<uint64_t>(n_y, CM_TRAJ_MAX_FOOT / n_x);
+    }
+    xy->clear();
+    for (uint64_t i = 0; i < n_x; ++i)
+        for (uint64_t j = 0; j < n_y; ++j) {
+            xy->push_back(static_cast<float>(n_x == 1u ? x_back + 0.5 * len : x_back + len * static_cast<double>(i) / static_cast<double>(n_x - 1u)));
+            xy->push_back(static_cast<float>(n_y == 1u ? 0.0 : -static_cast<double>(half_width) + wid * static_cast<double>(j) / static_cast<double>(n_y - 1u)));
+        }
+    return coarsened;
+}
+
 NodeConfig reference_config() {
     NodeConfig c;
     // Topics :520-525, TF frames :556-561, fuse order :137-142, gate :134-136.
@@ -214,6 +234,20 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "map_plan") ok = read(is, c.map_plan_neutral, c.map_plan_factor_q8) && c.map_plan_neutral <= 255u && c.map_plan_factor_q8 <= 256u;
         else if (key == "map_plan_allow_unknown") ok = read_flag(is, &c.map_plan_allow_unknown);
         else if (key == "map_goal") { ok = read(is, c.map_goal[0], c.map_goal[1]) && std::isfinite(c.map_goal[0]) && std::isfinite(c.map_goal[1]); c.map_has_goal = ok; }
+        else if (key == "traj") ok = read(is, c.traj_nv, c.traj_nw, c.traj_steps, c.traj_dt) &&
+                                     (c.traj_nv == 0u || (c.traj_nw >= 1u && static_cast<uint64_t>(c.traj_nv) * c.traj_nw <= CM_TRAJ_MAX_SAMPLES &&
+                                                          c.traj_steps >= 1u && c.traj_steps <= CM_TRAJ_MAX_STEPS && std::isfinite(c.traj_dt) && c.traj_dt > 0.0f));
+        else if (key == "traj_limits") {
+            float* l = c.traj_limits;
+            ok = read(is, l[0], l[1], l[2], l[3]) && std::isfinite(l[0]) && std::isfinite(l[1]) && std::isfinite(l[2]) && std::isfinite(l[3]) &&
+                 l[0] <= l[1] && l[2] <= l[3];
+        }
+        else if (key == "traj_footprint") {
+            float* f = c.traj_footprint;
+            ok = read(is, f[0], f[1], f[2]) && std::isfinite(f[0]) && std::isfinite(f[1]) && std::isfinite(f[2]) && f[0] <= f[1] && f[2] >= 0.0f;
+        }
+        else if (key == "traj_scales") ok = read(is, c.traj_occ_scale, c.traj_goal_scale);
+        else if (key == "traj_allow_unknown") ok = read_flag(is, &c.traj_allow_unknown);
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -302,6 +336,14 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
                                         cfg_.map_nx * cfg_.map_ny};
                 if (cm_map_plan_configure(ctx_, &pp) != CM_OK) refuse("cm_map_plan_configure");
+                if (ctx_ && cfg_.traj_nv > 0u) {                   // the rollout layer behind the plan layer
+                    std::vector<float> foot;
+                    if (traj_footprint_lattice(cfg_.traj_footprint[0], cfg_.traj_footprint[1], cfg_.traj_footprint[2], cfg_.map_cell, &foot))
+                        set_error("traj_footprint: the lattice was coarsened to CM_TRAJ_MAX_FOOT points");
+                    const cm_traj_params tp{cfg_.traj_nv, cfg_.traj_nw, cfg_.traj_steps, cfg_.traj_occ_scale, cfg_.traj_goal_scale,
+                                            cfg_.traj_allow_unknown ? CM_TRAJ_ALLOW_UNKNOWN : 0u};
+                    if (cm_map_traj_configure(ctx_, &tp, foot.data(), static_cast<uint32_t>(foot.size() / 2)) != CM_OK) refuse("cm_map_traj_configure");
+                }
             }
         }
     }
@@ -437,6 +479,13 @@ int CloudMergerNode::set_goal(float x, float y) {
     return CM_OK;
 }
 
+bool CloudMergerNode::best_command(float* v, float* w) const {
+    if (traj_scores_.empty() || traj_info_.best == CM_TRAJ_NONE) return false;
+    if (v) *v = traj_info_.best_v;
+    if (w) *w = traj_info_.best_w;
+    return true;
+}
+
 int CloudMergerNode::map_of_frame(const cm_result& r) {
     if (!(cfg_.map_cell > 0.0f) || r.status != CM_OK) return CM_OK;     // (a frame without a voxel grid leaves the map as it is)
     float pose[12];
@@ -460,6 +509,8 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
     map_potential_.clear();
     map_path_.clear();
     map_path_info_ = cm_path_info{};
+    traj_scores_.clear();
+    traj_info_ = cm_traj_info{};
     if (st != CM_OK) {
         map_cells_.clear();
         map_image_.clear();
@@ -491,6 +542,21 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
             map_path_info_ = cm_path_info{};
             set_error(cm_last_error(ctx_));
             if (ps != CM_BAD_ARG) return ps;
+        }
+        // The rollout behind the plan: every velocity sample from the pose. Without a plan there is nothing to score against;
+        // a start the library refuses leaves the results empty like the path.
+        if (ps == CM_OK && cfg_.traj_nv > 0u) {
+            const cm_traj_window w{pose[3], pose[7], std::atan2(pose[4], pose[0]), cfg_.traj_limits[0], cfg_.traj_limits[1],
+                                   cfg_.traj_limits[2], cfg_.traj_limits[3], cfg_.traj_dt};
+            traj_scores_.resize(static_cast<size_t>(cfg_.traj_nv) * cfg_.traj_nw);
+            int ts = cm_map_traj_evaluate(ctx_, &w, &traj_info_);
+            if (ts == CM_OK) ts = cm_map_traj_copy(ctx_, traj_scores_.data(), traj_scores_.size(), nullptr);
+            if (ts != CM_OK) {
+                traj_scores_.clear();
+                traj_info_ = cm_traj_info{};
+                set_error(cm_last_error(ctx_));
+                if (ts != CM_BAD_ARG) return ts;
+            }
         }
     }
     return CM_OK;

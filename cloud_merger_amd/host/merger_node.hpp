@@ -128,6 +128,17 @@ struct NodeConfig {
     bool map_plan_allow_unknown = false;
     bool map_has_goal = false;
     float map_goal[2] = {0.0f, 0.0f};                // world frame, metres
+    // Rollout layer behind that plan layer (cm_map_traj_configure, cm_map_traj_evaluate): sampled velocity commands rolled
+    // forward from the pose and scored over the cost table and the potential. Off by default (traj_nv 0). On (it needs the plan
+    // layer): the node lays a filled lattice over the footprint rectangle (traj_footprint_lattice), configures the layer behind
+    // the plan layer and evaluates it behind every plan update, from the pose with yaw = atan2f(P[4], P[0]) (traj_scores(),
+    // traj_info(), best_command()).
+    uint32_t traj_nv = 0, traj_nw = 1, traj_steps = 1;
+    float traj_dt = 0.1f;                            // seconds per step
+    float traj_limits[4] = {0.0f, 1.0f, -1.0f, 1.0f};   // v_lo, v_hi (m/s), w_lo, w_hi (rad/s)
+    float traj_footprint[3] = {0.0f, 0.0f, 0.0f};    // x_back, x_front, half_width (metres, body frame): the one point (0, 0) by default
+    uint32_t traj_occ_scale = 1, traj_goal_scale = 1;
+    bool traj_allow_unknown = false;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -172,6 +183,9 @@ struct NodeConfig {
 //   the decay per metre; an inflation radius of 0: off)
 //   map_plan <neutral> <factor_q8> | map_plan_allow_unknown <0|1> | map_goal <x> <y>   (the plan layer behind that cost layer:
 //   neutral 1..255 and the cost's factor in 1/256, 0..256; neutral 0: off; the goal in the world frame, metres)
+//   traj <nv> <nw> <n_steps> <dt> | traj_limits <v_lo> <v_hi> <w_lo> <w_hi> | traj_footprint <x_back> <x_front> <half_width> |
+//   traj_scales <occ> <goal> | traj_allow_unknown <0|1>   (the rollout layer behind that plan layer: nv x nw velocity samples
+//   between the limits, n_steps steps of dt seconds, the footprint rectangle in the body frame; nv 0: off)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -181,6 +195,11 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err);
 
 // The reference's literals: six sensors in fuse order fr, fl, rr, rl, tm, livox (:137-142), ROI
 // crop (Parameter.h:31-35), leaf 0.1 m, min 2 points per voxel (Parameter.h:27-28).
+// The rollout layer's footprint: a filled lattice over [x_back, x_front] x [-half_width, half_width] at a spacing of at most
+// half a cell per axis, as (bx, by) pairs; a lattice of more than CM_TRAJ_MAX_FOOT points is laid again with both counts
+// scaled down by the same factor. Returns whether that cap coarsened it.
+bool traj_footprint_lattice(float x_back, float x_front, float half_width, float cell, std::vector<float>* xy);
+
 NodeConfig reference_config();
 // The live node as a whole (pcl_preprocessing): reference_config() plus the zone-wise ground removal of its
 // callbacks — proceedFront for the four corner Velodynes (:228-269, called at :326,:352,:378,:404; proceedRear
@@ -278,6 +297,12 @@ public:
     const std::vector<uint32_t>& map_path() const { return map_path_; }
     const cm_plan_info& map_plan_info() const { return map_plan_info_; }
     const cm_path_info& map_path_info() const { return map_path_info_; }
+    // traj with nv > 0, behind a plan: the score of every velocity sample from the pose of the same frame, entry i * nw + j, and
+    // the best of them. Empty (best_command false) while there is no plan, and after a frame whose goal or vehicle lay outside
+    // the window (error() says which).
+    const std::vector<cm_traj_score>& traj_scores() const { return traj_scores_; }
+    const cm_traj_info& traj_info() const { return traj_info_; }
+    bool best_command(float* v, float* w) const;
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -351,6 +376,8 @@ private:
     std::vector<uint32_t> map_potential_, map_path_;
     cm_plan_info map_plan_info_{};
     cm_path_info map_path_info_{};
+    std::vector<cm_traj_score> traj_scores_;
+    cm_traj_info traj_info_{};
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

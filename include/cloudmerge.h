@@ -855,6 +855,111 @@ CM_API int cm_map_plan_device(cm_ctx* ctx, const void** pot, cm_plan_info* info,
  * CM_CAPACITY (nothing is copied, *info is still written). *info may be NULL. */
 CM_API int cm_map_plan_path(cm_ctx* ctx, float sx, float sy, uint32_t* host_dst, uint64_t capacity, cm_path_info* info);
 
+/* ---- rollout layer behind the plan layer: sampled velocity commands scored over cost and pot (an extension) ----------------
+ * In a costmap_2d stack the consumer behind the global planner is the local planner (base_local_planner, dwa_local_planner):
+ * it samples velocity commands, rolls each forward, checks the robot's footprint against the costmap pose by pose, scores the
+ * survivors by cost and by distance to the goal and picks one. The rollout layer is configured once behind the plan layer and
+ * evaluated on request; it yields one cm_traj_score per sample and the best of them. The goal-distance grid
+ * base_local_planner builds with a wavefront of its own is the plan layer's pot. Positions are fp32 with every operation
+ * rounded on its own, headings are integers, scores are integers: the table is bit for bit a function of the cost table, pot,
+ * the map's info and cell, the parameters, the footprint and the window.
+ * Input: the cost layer's fresh cost table, the plan layer's fresh pot, the map's info; cm_traj_params and the footprint
+ * (n_foot body-frame points (bx, by), x forward, y left, metres) given at configure time; per evaluate a cm_traj_window
+ * (x, y, yaw, v_lo, v_hi, w_lo, w_hi, dt). Sample (i, j), 0 <= i < nv, 0 <= j < nw, is entry i * nw + j.
+ *   1. Samples. In fp32, every operation rounded on its own: nv == 1 gives v_0 = v_lo, otherwise
+ *      v_i = v_lo + (float)i * ((v_hi - v_lo) / (float)(nv - 1)); w_j likewise from w_lo, w_hi and nw. Step length
+ *      s_i = v_i * dt in fp32. Headings are binary angles, a uint32_t in which a full turn is 2^32. With
+ *      K = 4294967296.0 / 6.283185307179586, in double: dh_j = rint(((double)w_j * (double)dt) * K), an integer of magnitude
+ *      at most 2^31 by the refusal below, reduced mod 2^32 (so +2^31 and -2^31 are the same increment; this is the one place
+ *      that differs from a plain (int32_t) cast, which is undefined at +2^31). h0 = rint((double)yaw * K), reduced mod 2^32.
+ *   2. Heading table. CM_TRAJ_HEADINGS pairs (cos, sin) in fp32, built once on the host: th = (double)a *
+ *      (6.283185307179586 / 4096.0), cos and sin from libm, rounded to float; entries 0, 1024, 2048 and 3072 are set to the
+ *      exact axes (1, 0), (0, 1), (-1, 0), (0, -1), so that driving along an axis stays in its row or column.
+ *      cm_traj_directions returns the table. A heading H uses entry ((H + 0x80000) >> 20) & 4095, the sum wrapping.
+ *   3. Rollout, forward Euler as in base_local_planner. p_0 = (x, y), H_0 = h0. For k = 0 .. n_steps - 1, with (c, s) the
+ *      entry of H_k: x_{k+1} = x_k + s_i * c, y_{k+1} = y_k + s_i * s, H_{k+1} = H_k + dh_j (wrapping). One multiplication and
+ *      one addition, each rounded; nothing is fused. Poses k = 1 .. n_steps are checked; pose 0 is not.
+ *   4. Looked-up points of pose k. The centre (x_k, y_k), and per footprint point, with (c, s) the entry of H_k and every
+ *      operation rounded: wx = (x_k + c * bx) - s * by, wy = (y_k + s * bx) + c * by. A point's cell is step 1 of the map's
+ *      semantics per axis (floorf(w * inv), the same existence test) minus the map's anchor.
+ *   5. Classes. A point whose cell does not exist or lies outside the window is off map. Otherwise v is the cost byte of its
+ *      cell: v == 254 is a collision; v == 255 is a collision unless CM_TRAJ_ALLOW_UNKNOWN, and then contributes 0; at the
+ *      centre only, v == 253 is a collision too; anything else contributes v. The first pose with an off-map or collision
+ *      point ends the trajectory, bad_step = k; status is CM_TRAJ_OFF_MAP if any point of that pose is off map, else
+ *      CM_TRAJ_COLLISION (a priority by class, not by point order).
+ *   6. Score. Without a bad pose: occ = the largest contribution over all poses and points, (end_x, end_y) = p_{n_steps},
+ *      pot_end = pot at the centre's cell of the last pose. pot_end == CM_PLAN_UNREACHABLE: status CM_TRAJ_NO_POTENTIAL, with
+ *      bad_step = n_steps. Otherwise status CM_TRAJ_VALID, bad_step 0 and total = occ_scale * occ + goal_scale * pot_end in
+ *      uint64_t. Every other entry holds occ 0, pot_end CM_PLAN_UNREACHABLE, total UINT64_MAX and the (end_x, end_y) of its
+ *      bad pose.
+ *   7. Best. The valid entry with the smallest total, ties to the lowest entry index; none valid: CM_TRAJ_NONE. best_v, best_w
+ *      are v_i, w_j of that entry (0 when there is none), n_valid the number of valid entries.
+ * cm_map_traj_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured plan layer; nv or nw 0 or nv * nw above
+ * CM_TRAJ_MAX_SAMPLES; n_steps outside 1..CM_TRAJ_MAX_STEPS; unknown flag bits; n_foot outside 1..CM_TRAJ_MAX_FOOT; a NULL
+ * footprint or a coordinate that is not finite; a frame in flight. cm_map_traj_evaluate refuses: no rollout layer; a stale pot
+ * (or none yet); a window value that is not finite; v_hi < v_lo, w_hi < w_lo, dt <= 0; |yaw| > 1024; any
+ * |(double)w_j * (double)dt| >= 3.141592653589793; a sample or a step length s_i that is not finite (they overflow fp32); a
+ * start whose cell does not exist or lies outside the window; a frame in flight. All memory of the layer is taken by cm_map_traj_configure (the scores, the sample tables and info words, the heading
+ * table and the footprint, the page-locked host words): no evaluate or copy allocates. The scores are stale from
+ * cm_map_traj_configure and from every cm_map_integrate, cm_map_cost_update and cm_map_plan_update until the next
+ * cm_map_traj_evaluate: cm_map_traj_copy and cm_map_traj_device then refuse with CM_BAD_ARG and say since which call.
+ * cm_map_plan_configure, cm_map_cost_configure and cm_map_configure, in either form, free the layer; like the map it survives
+ * merges, and nothing else depends on whether it exists. With CM_FLAG_PROFILE, cm_get_stage_times after an evaluate lists
+ * k_traj_roll and k_traj_best. Not modelled: path-distance and heading-alignment terms, acceleration limits (the caller passes
+ * the dynamic window), holonomic vy, oscillation suppression, the poses of a trajectory as an output. A stationary sample
+ * (v = 0, dh = 0) is a valid trajectory like any other; a caller who does not want it sets v_lo > 0. */
+#define CM_TRAJ_MAX_SAMPLES 16384
+#define CM_TRAJ_MAX_STEPS 256
+#define CM_TRAJ_MAX_FOOT 256
+#define CM_TRAJ_HEADINGS 4096
+#define CM_TRAJ_ALLOW_UNKNOWN 1u
+#define CM_TRAJ_NONE 0xFFFFFFFFu
+/* cm_traj_score.status (values, not bits) */
+#define CM_TRAJ_VALID 0u
+#define CM_TRAJ_COLLISION 1u
+#define CM_TRAJ_OFF_MAP 2u
+#define CM_TRAJ_NO_POTENTIAL 3u
+typedef struct cm_traj_params {        /* 24 bytes, no padding */
+    uint32_t nv, nw;                   /* linear and angular sample counts; each >= 1, nv * nw <= CM_TRAJ_MAX_SAMPLES */
+    uint32_t n_steps;                  /* 1..CM_TRAJ_MAX_STEPS */
+    uint32_t occ_scale, goal_scale;    /* the weights of step 6 */
+    uint32_t flags;                    /* CM_TRAJ_ALLOW_UNKNOWN or 0 */
+} cm_traj_params;
+typedef struct cm_traj_window {        /* 32 bytes: 8 floats */
+    float x, y, yaw;                   /* the start pose in the map's world frame; yaw in radians, |yaw| <= 1024 */
+    float v_lo, v_hi;                  /* m/s; v_lo <= v_hi */
+    float w_lo, w_hi;                  /* rad/s; w_lo <= w_hi */
+    float dt;                          /* seconds per step; > 0 */
+} cm_traj_window;
+typedef struct cm_traj_score {         /* 32 bytes */
+    uint32_t status;                   /* CM_TRAJ_VALID, CM_TRAJ_COLLISION, CM_TRAJ_OFF_MAP or CM_TRAJ_NO_POTENTIAL */
+    uint32_t bad_step;                 /* the pose that ended the trajectory (0: valid) */
+    uint32_t occ;                      /* the largest cost byte under the footprint along the way */
+    uint32_t pot_end;                  /* pot at the last pose's centre */
+    uint64_t total;                    /* occ_scale * occ + goal_scale * pot_end; UINT64_MAX unless valid */
+    float end_x, end_y;                /* the last pose's centre, or the bad pose's */
+} cm_traj_score;
+typedef struct cm_traj_info {          /* 24 bytes */
+    uint32_t best;                     /* entry index of step 7, or CM_TRAJ_NONE */
+    uint32_t n_valid;                  /* entries with status CM_TRAJ_VALID */
+    float best_v, best_w;              /* the command of the best entry (0, 0 when there is none) */
+    uint32_t start[2];                 /* the start's window cell (ix, iy) */
+} cm_traj_info;
+/* Non-NULL parameters allocate the layer and take the footprint (the scores are stale until the first evaluate); NULL frees
+ * it (foot_xy and n_foot are then ignored). foot_xy: 2 * n_foot floats, (bx, by) per point. */
+CM_API int cm_map_traj_configure(cm_ctx* ctx, const cm_traj_params* p, const float* foot_xy, uint32_t n_foot);
+/* Rolls and scores every sample from the window's pose. *out may be NULL. */
+CM_API int cm_map_traj_evaluate(cm_ctx* ctx, const cm_traj_window* w, cm_traj_info* out);
+/* Host copy of the nv * nw scores; capacity in entries. Fewer than nv * nw: CM_CAPACITY (nothing is copied; *info, which may
+ * be NULL, is still written). */
+CM_API int cm_map_traj_copy(cm_ctx* ctx, cm_traj_score* host_dst, uint64_t capacity, cm_traj_info* info);
+/* The same table in device memory owned by the context, valid until the next cm_map_traj_evaluate, cm_map_plan_update,
+ * cm_map_cost_update, cm_map_integrate or configure call of the four layers. */
+CM_API int cm_map_traj_device(cm_ctx* ctx, const void** scores, cm_traj_info* info);
+/* The heading table of step 2: 2 * CM_TRAJ_HEADINGS floats. A host function: no context, no GPU. A capacity below
+ * CM_TRAJ_HEADINGS pairs: CM_CAPACITY. */
+CM_API int cm_traj_directions(float* cos_sin, uint64_t capacity_pairs);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
