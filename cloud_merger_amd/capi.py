@@ -51,6 +51,7 @@ SYMBOLS = [
     "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
     "cm_map_plan_configure", "cm_map_plan_update", "cm_map_plan_copy", "cm_map_plan_device", "cm_map_plan_path",
     "cm_map_traj_configure", "cm_map_traj_evaluate", "cm_map_traj_copy", "cm_map_traj_device", "cm_traj_directions",
+    "cm_map_match_configure", "cm_map_match_evaluate", "cm_map_match_copy", "cm_map_match_device", "cm_map_match_table_copy", "cm_match_table",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -342,6 +343,30 @@ TRAJ_SCORE_DTYPE = np.dtype([("status", "<u4"), ("bad_step", "<u4"), ("occ", "<u
                              ("end_x", "<f4"), ("end_y", "<f4")])
 assert C.sizeof(TrajParams) == 24 and C.sizeof(TrajWindow) == 32 and C.sizeof(TrajScore) == 32 == TRAJ_SCORE_DTYPE.itemsize and C.sizeof(TrajInfo) == 24
 
+# scan matching of the frame against the occupancy map, behind the cost layer (cm_map_match_configure, cm_map_match_evaluate)
+MATCH_MAX_RADIUS_CELLS = 64
+MATCH_MAX_SHIFT = 64
+MATCH_MAX_ANGLES = 127
+MATCH_MAX_CANDIDATES = 1 << 22
+MATCH_SUBCELL = 1
+
+
+class MatchParams(C.Structure):
+    """cm_match_params (28 bytes): the field's sigma and cut (metres), angle candidates -n_a..n_a at a_stride heading-table
+    entries, shifts -wx..wx and -wy..wy cells, MATCH_SUBCELL or 0."""
+    _fields_ = [("sigma", C.c_float), ("max_dist", C.c_float), ("n_a", C.c_uint32), ("a_stride", C.c_uint32), ("wx", C.c_uint32),
+                ("wy", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MatchResult(C.Structure):
+    """cm_match_result (96 bytes): the best entry, its angle candidate and shift, its score, the cells of that candidate and
+    255 times their number, the candidate's rotation, the sub-cell offsets, the matched pose (3 x 4, row-major)."""
+    _fields_ = [("best", C.c_uint32), ("k", C.c_int32), ("i", C.c_int32), ("j", C.c_int32), ("score", C.c_uint32), ("n_cells", C.c_uint32),
+                ("max_score", C.c_uint32), ("yaw", C.c_float), ("sub", C.c_double * 2), ("pose", C.c_float * 12)]
+
+
+assert C.sizeof(MatchParams) == 28 and C.sizeof(MatchResult) == 96 and MatchResult.sub.offset == 32 and MatchResult.pose.offset == 48
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -546,6 +571,12 @@ def load():
     L.cm_map_traj_copy.argtypes = [vp, vp, u64, C.POINTER(TrajInfo)]
     L.cm_map_traj_device.argtypes = [vp, C.POINTER(vp), C.POINTER(TrajInfo)]
     L.cm_traj_directions.argtypes = [vp, u64]
+    L.cm_map_match_configure.argtypes = [vp, C.POINTER(MatchParams)]
+    L.cm_map_match_evaluate.argtypes = [vp, vp, C.POINTER(MatchResult)]
+    L.cm_map_match_copy.argtypes = [vp, vp, u64, C.POINTER(MatchResult)]
+    L.cm_map_match_device.argtypes = [vp, C.POINTER(vp), C.POINTER(MatchResult)]
+    L.cm_map_match_table_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.cm_match_table.argtypes = [C.c_float, C.c_float, C.c_float, vp, u64, C.POINTER(u64)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -591,6 +622,16 @@ def traj_directions():
     if st != OK:
         raise CloudMergeError(st, "cm_traj_directions")
     return out
+
+
+def match_table(cell, sigma, max_dist):
+    """(R * R + 1,) uint8: the scan matching layer's field byte by squared distance in cells (cm_match_table)."""
+    out = np.empty(MATCH_MAX_RADIUS_CELLS * MATCH_MAX_RADIUS_CELLS + 1, dtype=np.uint8)
+    n = C.c_uint64(0)
+    st = load().cm_match_table(float(cell), float(sigma), float(max_dist), out.ctypes.data, out.shape[0], C.byref(n))
+    if st != OK:
+        raise CloudMergeError(st, "cm_match_table")
+    return out[: n.value].copy()
 
 
 def status_string(status):
@@ -1180,6 +1221,49 @@ class CloudMerger:
         ptr, info = C.c_void_p(), TrajInfo()
         self._check(self._lib.cm_map_traj_device(self._ctx, C.byref(ptr), C.byref(info)), "cm_map_traj_device")
         return ptr.value, info
+
+    # ---- scan matching of the frame against the map, behind the cost layer (cm_map_match_configure / cm_map_match_evaluate) ----
+    def map_match_configure(self, sigma=None, max_dist=0.5, n_a=0, a_stride=1, wx=0, wy=0, subcell=False):
+        """Allocates the matching layer behind the configured cost layer: a likelihood field of standard deviation sigma cut at
+        max_dist (metres), angle candidates -n_a..n_a at a_stride entries of the 4096-entry heading table, shifts -wx..wx and
+        -wy..wy cells, the sub-cell offset with subcell. sigma None frees the layer."""
+        if sigma is None:
+            self._check(self._lib.cm_map_match_configure(self._ctx, None), "cm_map_match_configure")
+            return
+        p = MatchParams(float(sigma), float(max_dist), int(n_a), int(a_stride), int(wx), int(wy), MATCH_SUBCELL if subcell else 0)
+        self._check(self._lib.cm_map_match_configure(self._ctx, C.byref(p)), "cm_map_match_configure")
+        self._match_shape = (2 * p.n_a + 1, 2 * p.wy + 1, 2 * p.wx + 1)
+
+    def map_match(self, pose):
+        """Matches the last frame against the map around the prior pose (3 x 4, row-major). Returns the MatchResult."""
+        p = np.ascontiguousarray(pose, dtype=np.float32).reshape(12)
+        out = MatchResult()
+        self._check(self._lib.cm_map_match_evaluate(self._ctx, p.ctypes.data, C.byref(out)), "cm_map_match_evaluate")
+        return out
+
+    def map_match_scores(self):
+        """((2 n_a + 1, 2 wy + 1, 2 wx + 1) uint32 scores, MatchResult) of the last match: entry [k + n_a, j + wy, i + wx]."""
+        res = MatchResult()
+        out = np.empty(getattr(self, "_match_shape", (0, 0, 0)), dtype=np.uint32)
+        self._check(self._lib.cm_map_match_copy(self._ctx, out.ctypes.data, out.size, C.byref(res)), "cm_map_match_copy")
+        return out, res
+
+    def map_match_device(self):
+        """(scores device pointer, MatchResult) of the same volume, owned by the context and valid until the next evaluate,
+        update, integrate, merge or configure call."""
+        ptr, res = C.c_void_p(), MatchResult()
+        self._check(self._lib.cm_map_match_device(self._ctx, C.byref(ptr), C.byref(res)), "cm_map_match_device")
+        return ptr.value, res
+
+    def map_match_table(self):
+        """(R * R + 1,) uint8: the field byte by squared distance in cells, as cm_map_match_configure built it."""
+        n = C.c_uint64(0)
+        st = self._lib.cm_map_match_table_copy(self._ctx, None, 0, C.byref(n))
+        if st != CAPACITY:
+            self._check(st, "cm_map_match_table_copy")
+        out = np.empty(n.value, dtype=np.uint8)
+        self._check(self._lib.cm_map_match_table_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_map_match_table_copy")
+        return out
 
     # ---- normals and curvature of the last result (cm_result_normals) ----
     def normals(self, k, viewpoint=(0.0, 0.0, 0.0), search_cell=0.0):

@@ -10,6 +10,7 @@
 
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
+#include "cm_match_table.hpp"
 
 namespace {
 
@@ -1248,6 +1249,111 @@ int cm_map_traj_device(cm_ctx* c, const void** scores, cm_traj_info* info) {
     if (const int e = traj_check(c, true)) return e;
     if (info) *info = c->traj_info;
     if (scores) *scores = c->traj_scores;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_match_params) == 28 && sizeof(cm_match_result) == 96 && offsetof(cm_match_result, sub) == 32 &&
+                  offsetof(cm_match_result, pose) == 48, "the matching layer's two structs");
+static_assert(CM_MATCH_MAX_SHIFT == CM_MATCH_MAX_SHIFT_DEV && 2 * CM_MATCH_MAX_ANGLES + 1 == CM_MATCH_MAX_ANGLES_DEV &&
+                  CM_MATCH_MAX_CANDIDATES == CM_GRID_MAX_CELLS, "the kernels' constants");
+
+int cm_match_table(float cell, float sigma, float max_dist, uint8_t* dst, uint64_t capacity, uint64_t* n) {
+    uint32_t R = 0;
+    if (!dst || cm_match_refusal(cell, sigma, max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return CM_BAD_ARG;
+    const uint64_t n_lut = static_cast<uint64_t>(R) * R + 1;
+    if (n) *n = n_lut;
+    if (n_lut > capacity) return CM_CAPACITY;
+    cm_match_table_build(cell, sigma, max_dist, R, dst);
+    return CM_OK;
+}
+
+int cm_map_match_configure(cm_ctx* c, const cm_match_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    uint32_t R = 0;
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
+        if (p->n_a > CM_MATCH_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_a exceeds CM_MATCH_MAX_ANGLES");
+        if (p->a_stride == 0u) return fail(c, CM_BAD_ARG, "a_stride must be at least 1");
+        if (static_cast<uint64_t>(p->n_a) * p->a_stride > 1024u) return fail(c, CM_BAD_ARG, "n_a * a_stride exceeds 1024 (a quarter turn)");
+        if (p->wx > CM_MATCH_MAX_SHIFT || p->wy > CM_MATCH_MAX_SHIFT) return fail(c, CM_BAD_ARG, "wx or wy exceeds CM_MATCH_MAX_SHIFT");
+        if ((2ull * p->n_a + 1u) * (2ull * p->wx + 1u) * (2ull * p->wy + 1u) > CM_MATCH_MAX_CANDIDATES)
+            return fail(c, CM_BAD_ARG, "more than CM_MATCH_MAX_CANDIDATES candidates");
+        if (p->flags & ~CM_MATCH_SUBCELL) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    }
+    return map_match_configure(c, p, R);
+}
+
+// The refusals every call on a configured matching layer shares; the reads also refuse a stale volume.
+static int match_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->match_on) return fail(c, CM_BAD_ARG, "no matching layer (cm_map_match_configure first)");
+    if (read && c->match_stale) return fail(c, CM_BAD_ARG, c->match_stale);
+    if (read && c->match_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the match is stale: no cm_map_match_evaluate since the last merge");
+    return CM_OK;
+}
+
+int cm_map_match_evaluate(cm_ctx* c, const float pose[12], cm_match_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = match_check(c, false)) return e;
+    if (const int e = centroid_result_check(c)) return e;
+    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
+    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    int v[2];
+    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    if (const int e = map_match_evaluate(c, pose)) return e;
+    if (out) *out = c->match_result;
+    return CM_OK;
+}
+
+static uint64_t match_entries(const cm_ctx* c) {
+    const cm_match_params& q = c->match_params;
+    return (2ull * q.n_a + 1u) * (2ull * q.wx + 1u) * (2ull * q.wy + 1u);
+}
+
+int cm_map_match_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity, cm_match_result* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = match_check(c, true)) return e;
+    if (out) *out = c->match_result;
+    const uint64_t n = match_entries(c);
+    if (n > capacity) return fail(c, CM_CAPACITY, "score destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->match_vol, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(uint32_t);
+    return CM_OK;
+}
+
+int cm_map_match_device(cm_ctx* c, const void** scores, cm_match_result* out) {
+    if (!c) return CM_BAD_ARG;
+    if (scores) *scores = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = match_check(c, true)) return e;
+    if (out) *out = c->match_result;
+    if (scores) *scores = c->match_vol;
+    return CM_OK;
+}
+
+int cm_map_match_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uint64_t* n) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = match_check(c, false)) return e;
+    const uint64_t n_lut = c->match_lut_host.size();
+    if (n) *n = n_lut;
+    if (n_lut > capacity) return fail(c, CM_CAPACITY, "field table destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    std::memcpy(host_dst, c->match_lut_host.data(), n_lut);
     return CM_OK;
 }
 

@@ -1,7 +1,7 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
-// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path) and the rollout layer behind the plan (map_traj_configure, map_traj_evaluate). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path) and the rollout layer behind the plan (map_traj_configure, map_traj_evaluate), and the scan matching of the frame against the map behind the cost layer (map_match_configure, map_match_evaluate). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
@@ -14,6 +14,7 @@
 #include "cm_align_solve.hpp"
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
+#include "cm_match_table.hpp"
 #include "cm_search.hpp"
 
 namespace {
@@ -559,6 +560,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_integrate";
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_integrate";
+    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -567,6 +569,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
 int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int e = map_plan_configure(c, nullptr)) return e;        // the plan layer goes with the cost layer it reads
+    if (const int e = map_match_configure(c, nullptr, 0)) return e;    // and so does the matching layer
     c->cost_on = false;
     c->cost_fresh = false;
     if (!q) {
@@ -619,6 +622,7 @@ int map_cost_update(cm_ctx* c) {
     c->cost_fresh = true;
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_cost_update";
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_cost_update";
+    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
     return CM_OK;
 }
 
@@ -851,6 +855,134 @@ int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2
     c->traj_info.start[0] = start[0];
     c->traj_info.start[1] = start[1];
     c->traj_stale = nullptr;
+    return CM_OK;
+}
+
+// The matching layer's memory, all of it: the field with the table behind it (built here, cm_match_table.hpp, and uploaded),
+// one bitmap per angle candidate, the volume with the info words behind it, the candidates' matrices and the page-locked words
+// an evaluate uploads from and reads back into. nullptr gives it back. Volume and result are stale until the first evaluate.
+int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->match_on = false;
+    c->match_stale = "the match is stale: no cm_map_match_evaluate since cm_map_match_configure";
+    std::memset(&c->match_result, 0, sizeof c->match_result);
+    if (!q) {
+        c->match_field.release();
+        c->match_bits.release();
+        c->match_vol.release();
+        c->match_q.release();
+        c->match_host.release();
+        c->match_lut_host = std::vector<unsigned char>();
+        return CM_OK;
+    }
+    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, words = (n_cells + 31) / 32;
+    const size_t n_k = 2 * static_cast<size_t>(q->n_a) + 1, n_vol = n_k * (2 * static_cast<size_t>(q->wx) + 1) * (2 * static_cast<size_t>(q->wy) + 1);
+    const size_t n_lut = static_cast<size_t>(R) * R + 1;
+    if (!c->match_field.reserve(n_cells + n_lut) || !c->match_bits.reserve(n_k * words) || !c->match_vol.reserve(n_vol + CM_MATCH_INFO_WORDS) ||
+        !c->match_q.reserve(6 * n_k) || !c->match_host.reserve(CM_MATCH_INFO_WORDS + 6 * n_k))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the matching layer");
+    c->match_lut_host.assign(n_lut, 0);
+    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, c->match_lut_host.data());
+    HIP_TRY(c, hipMemcpyAsync(c->match_field + n_cells, c->match_lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->match_params = *q;
+    c->match_radius = R;
+    c->match_on = true;
+    return CM_OK;
+}
+
+// The last frame against the map around a prior (cm_kernels_match.hip; the semantics are in include/cloudmerge.h). Step 3 on
+// the host: the candidates' matrices, written into the page-locked words. One upload, two clears, four launches, one copy of
+// the info words back and one wait; steps 7 and 8 on the host from those words. No allocation: cm_map_match_configure made
+// them all.
+int map_match_evaluate(cm_ctx* c, const float pose[12]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_match_params& q = c->match_params;
+    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny;
+    CmMatchDev g;
+    g.tx = pose[3];
+    g.ty = pose[7];
+    g.inv = 1.0f / c->map_params.cell;
+    g.ax = c->map_info.anchor[0];
+    g.ay = c->map_info.anchor[1];
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.z_min = c->map_params.z_min;
+    g.z_max = c->map_params.z_max;
+    g.n_a = q.n_a;
+    g.n_k = 2u * q.n_a + 1u;
+    g.wx = q.wx;
+    g.wy = q.wy;
+    g.words = static_cast<uint32_t>((n_cells + 31) / 32);
+    g.r2 = c->match_radius * c->match_radius;
+    const uint32_t sx = 2u * q.wx + 1u, sy = 2u * q.wy + 1u;
+    const size_t n_vol = static_cast<size_t>(g.n_k) * sx * sy;
+    const float* const dirs = traj_direction_table();
+    float* const up = reinterpret_cast<float*>(c->match_host + CM_MATCH_INFO_WORDS);
+    for (uint32_t kk = 0; kk < g.n_k; ++kk) {
+        const int k = static_cast<int>(kk) - static_cast<int>(q.n_a);
+        const uint32_t e = static_cast<uint32_t>(k * static_cast<int>(q.a_stride)) & (CM_TRAJ_HEADINGS - 1u);
+        const float cs = dirs[2 * e], sn = dirs[2 * e + 1];
+        for (int j = 0; j < 3; ++j) {
+            up[6 * kk + j] = static_cast<float>(static_cast<float>(cs * pose[j]) - static_cast<float>(sn * pose[4 + j]));
+            up[6 * kk + 3 + j] = static_cast<float>(static_cast<float>(sn * pose[j]) + static_cast<float>(cs * pose[4 + j]));
+        }
+    }
+    uint32_t* const info = c->match_vol + n_vol;
+    const uint32_t n_tiles = c->frame.n_tiles;
+    hipStream_t st = c->stream;
+    c->match_stale = "the match is stale: the last cm_map_match_evaluate failed";
+    c->prof_used = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->match_q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
+    prof_mark(c, "match_clear");
+    HIP_TRY(c, hipMemsetAsync(c->match_bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->match_vol, 0, n_vol * 4, st));
+    prof_mark(c, "k_match_field");
+    cmk_match_field(st, c->cost_dist2, c->match_field + n_cells, g.r2, static_cast<uint32_t>(n_cells), c->match_field);
+    prof_mark(c, "k_match_mark");
+    cmk_match_mark(st, c->d_frame, g, c->match_q, c->frame_mask, c->match_bits, n_tiles);
+    prof_mark(c, "k_match_score");
+    cmk_match_score(st, c->match_field, c->match_bits, g, c->match_vol);
+    prof_mark(c, "k_match_best");
+    cmk_match_best(st, c->match_vol, c->match_bits, g, info);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->match_host, info, CM_MATCH_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    const uint32_t* const h = c->match_host;
+    const uint32_t best = h[0];
+    if (best >= n_vol) return fail(c, CM_INTERNAL, "the best entry lies outside the volume");
+    cm_match_result& r = c->match_result;
+    r.best = best;
+    r.k = static_cast<int32_t>(best / (sx * sy)) - static_cast<int32_t>(q.n_a);
+    r.j = static_cast<int32_t>((best / sx) % sy) - static_cast<int32_t>(q.wy);
+    r.i = static_cast<int32_t>(best % sx) - static_cast<int32_t>(q.wx);
+    r.n_cells = h[1];
+    r.max_score = 255u * h[1];
+    r.score = h[2];
+    r.yaw = static_cast<float>(static_cast<double>(r.k * static_cast<int32_t>(q.a_stride)) * (6.283185307179586 / 4096.0));
+    // step 7: the vertex of the parabola through the best entry and its two neighbours, per axis
+    const auto sub = [&](bool both, uint32_t lo, uint32_t hi) {
+        if (!(q.flags & CM_MATCH_SUBCELL) || !both) return 0.0;
+        const int64_t den = static_cast<int64_t>(lo) - 2 * static_cast<int64_t>(h[2]) + static_cast<int64_t>(hi);
+        if (den >= 0) return 0.0;
+        const double v = 0.5 * static_cast<double>(static_cast<int64_t>(lo) - static_cast<int64_t>(hi)) / static_cast<double>(den);
+        return v < -0.5 ? -0.5 : v > 0.5 ? 0.5 : v;
+    };
+    r.sub[0] = sub(r.i > -static_cast<int32_t>(q.wx) && r.i < static_cast<int32_t>(q.wx), h[3], h[4]);
+    r.sub[1] = sub(r.j > -static_cast<int32_t>(q.wy) && r.j < static_cast<int32_t>(q.wy), h[5], h[6]);
+    const uint32_t bk = best / (sx * sy);
+    const double cell = static_cast<double>(c->map_params.cell);
+    for (int j = 0; j < 3; ++j) {
+        r.pose[j] = up[6 * bk + j];
+        r.pose[4 + j] = up[6 * bk + 3 + j];
+    }
+    r.pose[3] = static_cast<float>(pose[3] + static_cast<float>((static_cast<double>(r.i) + r.sub[0]) * cell));
+    r.pose[7] = static_cast<float>(pose[7] + static_cast<float>((static_cast<double>(r.j) + r.sub[1]) * cell));
+    for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
+    c->match_serial = c->frame_serial;
+    c->match_stale = nullptr;
     return CM_OK;
 }
 

@@ -319,6 +319,22 @@ struct cm_ctx {
     PinnedBuf<uint32_t> traj_host;       // CM_TRAJ_INFO_WORDS words read back, then the nv + nw words an evaluate uploads
     std::vector<float> traj_v, traj_w;   // the samples of the last evaluate (nv and nw entries from the configure call on)
 
+    // Scan matching layer behind the cost layer (cm_kernels_match.hip), configured by cm_map_match_configure and evaluated by
+    // cm_map_match_evaluate from the frame at rest, map_info and cost_dist2. Buffers of its own, all allocated by the
+    // configure call; it lives and goes with the cost layer (map_cost_configure frees it).
+    bool match_on = false;               // a matching layer is configured
+    const char* match_stale = nullptr;   // why volume and result are not those of the current tables and a prior; nullptr: they are
+    uint64_t match_serial = 0;           // the frame matched last: a merge since then makes them stale too
+    cm_match_params match_params{};
+    uint32_t match_radius = 0;           // R: the field table has R * R + 1 entries
+    cm_match_result match_result{};
+    DevBuf<unsigned char> match_field;   // nx * ny bytes L, then the field table
+    DevBuf<uint32_t> match_bits;         // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
+    DevBuf<uint32_t> match_vol;          // the volume, then CM_MATCH_INFO_WORDS info words
+    DevBuf<float> match_q;               // six floats per candidate
+    PinnedBuf<uint32_t> match_host;      // CM_MATCH_INFO_WORDS words read back, then the candidates' floats an evaluate uploads
+    std::vector<unsigned char> match_lut_host;
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -450,6 +466,11 @@ const float* traj_direction_table();
 void traj_samples(float lo, float hi, uint32_t n, float* out);
 int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot);
 int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]);
+// The scan matching layer behind the cost layer. map_match_configure: room for q's candidates over the map's window and the
+// field table at radius R cells, which is built and uploaded (nullptr: the buffers go). map_match_evaluate: the volume and
+// match_result for a prior that cm_map_match_evaluate has checked.
+int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R);
+int map_match_evaluate(cm_ctx* c, const float pose[12]);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

@@ -402,3 +402,28 @@ struct CmTrajScoreDev {                // cm_traj_score
     unsigned long long total;
     float end_x, end_y;
 };
+
+// Scan matching layer behind the cost layer (cm_kernels_match.hip). k_match_score gives a workgroup of CM_MATCH_BLOCK threads
+// one angle candidate and one tile of CM_MATCH_TILE x CM_MATCH_TILE window cells: the tile's field bytes with a halo of
+// (wx, wy) cells and the tile's marked cells are staged in LDS, every thread sums the bytes of its translations over the cell
+// list and adds the sums into the volume (integer atomicAdd: the order cannot show). k_match_best reduces the volume in one
+// workgroup of CM_MATCH_BEST_BLOCK threads and writes CM_MATCH_INFO_WORDS words: best, n_cells, score, then the scores of the
+// best entry's neighbours at i - 1, i + 1, j - 1, j + 1 (0 where there is none), one spare.
+#define CM_MATCH_TILE 32
+#define CM_MATCH_BLOCK 256
+#define CM_MATCH_BEST_BLOCK 1024
+#define CM_MATCH_INFO_WORDS 8
+#define CM_MATCH_MAX_SHIFT_DEV 64
+#define CM_MATCH_MAX_ANGLES_DEV 255
+struct CmMatchDev {
+    float tx, ty;                      // the prior's translation (P3, P7)
+    float inv;                         // 1.0f / cell
+    int32_t ax, ay;                    // the map's anchor
+    uint32_t nx, ny;
+    float z_min, z_max;
+    uint32_t n_k;                      // 2 * n_a + 1 candidates
+    uint32_t n_a;
+    uint32_t wx, wy;
+    uint32_t words;                    // bitmap words of one candidate
+    uint32_t r2;                       // the field table has r2 + 1 entries
+};

@@ -283,3 +283,13 @@ void cmk_plan_path(hipStream_t s, const unsigned char* cost, const uint32_t* pot
 void cmk_traj_roll(hipStream_t s, const unsigned char* cost, const uint32_t* pot, const CmTrajDev& g, const float* steps, const uint32_t* dh,
                    const float* dirs, const float* foot, CmTrajScoreDev* out);
 void cmk_traj_best(hipStream_t s, const CmTrajScoreDev* scores, uint32_t n, uint32_t* info);
+
+// ---- scan matching layer behind the cost layer (cm_kernels_match.hip) ---------------------------------------------------------------
+// dist2: the cost layer's table. lut: the field table, r2 + 1 bytes. field: one byte per window cell. q: six floats per
+// candidate (rows 0 and 1 of its linear part). bits: g.n_k bitmaps of g.words words, zero before cmk_match_mark. vol:
+// g.n_k * (2 wy + 1) * (2 wx + 1) words, zero before cmk_match_score. cmk_match_best writes CM_MATCH_INFO_WORDS words.
+void cmk_match_field(hipStream_t s, const uint32_t* dist2, const unsigned char* lut, uint32_t r2, uint32_t n_cells, unsigned char* field);
+void cmk_match_mark(hipStream_t s, const CmFrameDev* fd, const CmMatchDev& g, const float* q, const unsigned char* keep, uint32_t* bits,
+                    uint32_t n_tiles);
+void cmk_match_score(hipStream_t s, const unsigned char* field, const uint32_t* bits, const CmMatchDev& g, uint32_t* vol);
+void cmk_match_best(hipStream_t s, const uint32_t* vol, const uint32_t* bits, const CmMatchDev& g, uint32_t* info);

@@ -248,6 +248,13 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         }
         else if (key == "traj_scales") ok = read(is, c.traj_occ_scale, c.traj_goal_scale);
         else if (key == "traj_allow_unknown") ok = read_flag(is, &c.traj_allow_unknown);
+        else if (key == "match") ok = read_flag(is, &c.match_enable);
+        else if (key == "match_angles") ok = read(is, c.match_n_a, c.match_a_stride) && c.match_n_a <= CM_MATCH_MAX_ANGLES && c.match_a_stride >= 1u &&
+                                             static_cast<uint64_t>(c.match_n_a) * c.match_a_stride <= 1024u;
+        else if (key == "match_window") ok = read(is, c.match_wx, c.match_wy) && c.match_wx <= CM_MATCH_MAX_SHIFT && c.match_wy <= CM_MATCH_MAX_SHIFT;
+        else if (key == "match_field") ok = read(is, c.match_sigma, c.match_max_dist) && std::isfinite(c.match_sigma) && c.match_sigma > 0.0f &&
+                                            std::isfinite(c.match_max_dist) && c.match_max_dist > 0.0f;
+        else if (key == "match_subcell") ok = read_flag(is, &c.match_subcell);
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -332,6 +339,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
             const cm_cost_params cp{cfg_.map_inscribed_radius, cfg_.map_inflation_radius, cfg_.map_cost_scaling,
                                     cfg_.map_inflate_unknown ? CM_COST_INFLATE_UNKNOWN : 0u};
             if (cm_map_cost_configure(ctx_, &cp) != CM_OK) refuse("cm_map_cost_configure");
+            if (ctx_ && cfg_.match_enable) {                       // the matching layer behind the cost layer
+                const cm_match_params qp{cfg_.match_sigma, cfg_.match_max_dist, cfg_.match_n_a, cfg_.match_a_stride, cfg_.match_wx, cfg_.match_wy,
+                                         cfg_.match_subcell ? CM_MATCH_SUBCELL : 0u};
+                if (cm_map_match_configure(ctx_, &qp) != CM_OK) refuse("cm_map_match_configure");
+            }
             if (ctx_ && cfg_.map_plan_neutral > 0u) {              // the plan layer behind the cost layer
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
                                         cfg_.map_nx * cfg_.map_ny};
@@ -492,6 +504,24 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
     {
         std::lock_guard<std::mutex> lk(pose_mu_);
         std::memcpy(pose, pose_, sizeof pose);
+    }
+    // The match in front of the integration: once the map holds a frame, the frame against it with the given pose as the prior.
+    // A match the library refuses (a stale distance field after a failed epilogue) leaves the prior in place and says so.
+    if (cfg_.match_enable && cfg_.map_inflation_radius > 0.0f) {
+        matched_ = false;
+        match_result_ = cm_match_result{};
+        if (map_info_.n_frames > 0) {
+            const int ms = cm_map_match_evaluate(ctx_, pose, &match_result_);
+            if (ms == CM_OK) {
+                matched_ = true;
+                std::memcpy(pose, match_result_.pose, sizeof pose);
+            } else {
+                match_result_ = cm_match_result{};
+                set_error(cm_last_error(ctx_));
+                if (ms != CM_BAD_ARG) return ms;
+            }
+        }
+        std::memcpy(matched_pose_, pose, sizeof pose);
     }
     const size_t n = static_cast<size_t>(cfg_.map_nx) * cfg_.map_ny;
     map_cells_.resize(n);

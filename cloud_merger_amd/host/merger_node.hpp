@@ -139,6 +139,16 @@ struct NodeConfig {
     float traj_footprint[3] = {0.0f, 0.0f, 0.0f};    // x_back, x_front, half_width (metres, body frame): the one point (0, 0) by default
     uint32_t traj_occ_scale = 1, traj_goal_scale = 1;
     bool traj_allow_unknown = false;
+    // Scan matching of every frame against the map (cm_map_match_configure, cm_map_match_evaluate): a search over angle
+    // candidates and shifts around the pose set_pose() gave. Off by default. On (it needs the cost layer): once the map holds a
+    // frame and its distance field is fresh, the frame is matched with set_pose()'s pose as the prior and integrated under the
+    // matched pose (matched(), match_result(), matched_pose()); the first frame, and a frame the library refuses to match, is
+    // integrated under the prior.
+    bool match_enable = false;
+    uint32_t match_n_a = 10, match_a_stride = 2;     // angle candidates -n_a..n_a, a_stride entries of 2 pi / 4096 apart
+    uint32_t match_wx = 10, match_wy = 10;           // shifts in cells
+    float match_sigma = 0.1f, match_max_dist = 0.5f; // the likelihood field's standard deviation and cut (metres)
+    bool match_subcell = false;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -186,6 +196,9 @@ struct NodeConfig {
 //   traj <nv> <nw> <n_steps> <dt> | traj_limits <v_lo> <v_hi> <w_lo> <w_hi> | traj_footprint <x_back> <x_front> <half_width> |
 //   traj_scales <occ> <goal> | traj_allow_unknown <0|1>   (the rollout layer behind that plan layer: nv x nw velocity samples
 //   between the limits, n_steps steps of dt seconds, the footprint rectangle in the body frame; nv 0: off)
+//   match <0|1> | match_angles <n_a> <a_stride> | match_window <wx> <wy> | match_field <sigma> <max_dist> | match_subcell <0|1>
+//   (scan matching of every frame against the map, behind the cost layer: 2 n_a + 1 angles a_stride table entries apart,
+//   shifts of up to wx and wy cells, the field's standard deviation and cut in metres)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -303,6 +316,11 @@ public:
     const std::vector<cm_traj_score>& traj_scores() const { return traj_scores_; }
     const cm_traj_info& traj_info() const { return traj_info_; }
     bool best_command(float* v, float* w) const;
+    // match 1: whether the frame waited for last was matched against the map, the match and the pose it was integrated under
+    // (the prior where it was not matched).
+    bool matched() const { return matched_; }
+    const cm_match_result& match_result() const { return match_result_; }
+    const float* matched_pose() const { return matched_pose_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -378,6 +396,9 @@ private:
     cm_path_info map_path_info_{};
     std::vector<cm_traj_score> traj_scores_;
     cm_traj_info traj_info_{};
+    bool matched_ = false;
+    cm_match_result match_result_{};
+    float matched_pose_[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

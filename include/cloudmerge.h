@@ -960,6 +960,101 @@ CM_API int cm_map_traj_device(cm_ctx* ctx, const void** scores, cm_traj_info* in
  * CM_TRAJ_HEADINGS pairs: CM_CAPACITY. */
 CM_API int cm_traj_directions(float* cos_sin, uint64_t capacity_pairs);
 
+/* ---- correlative scan matching of a frame against the occupancy map (an extension) -----------------------------------------
+ * Every layer above takes the vehicle's pose from outside. This one finds it: the last frame is registered against the one
+ * thing accumulated over time, the map, by an exhaustive search over a window of (yaw, x, y) around a prior pose, every
+ * candidate scored by looking the frame's hit cells up in a likelihood field of the map (Olson's real-time correlative scan
+ * matching, cartographer's RealTimeCorrelativeScanMatcher). The layer is configured once behind the cost layer
+ * and evaluated on request. A score is an integer sum over a set of cells: the score volume is bit for bit a function of the
+ * frame, the prior, the map's info and cell, dist2 and the parameters, whatever the order of summation.
+ * Input: the last frame as cm_map_integrate sees it (the raw clouds in place, the keep and ground masks); the configured map
+ * with its cell, inv, height band and the info (anchor, nx, ny) of its last integration; the cost layer's fresh dist2;
+ * cm_match_params given at configure time; per evaluate a prior pose P, row-major 3 x 4 fp32 as for cm_map_integrate.
+ *   1. Field table, built on the host in double from three fp32 values widened to double, the map's cell, sigma and max_dist:
+ *      R = (uint32_t)ceil(max_dist / cell), the table has R * R + 1 bytes. lut[0] = 255. For d2 >= 1:
+ *      m = sqrt((double)d2) * cell; m > max_dist gives 0, anything else
+ *      (uint8_t)floor(255.0 * cm_exp_neg((m * m) / (2.0 * sigma * sigma))), every operation rounded once ((2.0 * sigma) *
+ *      sigma; cm_exp_neg is cm_ndt_math.hpp's). A d2 beyond the table, CM_MAP_DIST_NONE included, has field value 0.
+ *      cm_match_table returns the table of three values, cm_map_match_table_copy the configured layer's.
+ *   2. Field. L(c) = lut[dist2(c)] for every window cell c; a cell outside the window has L = 0.
+ *   3. Angle candidates k = -n_a .. n_a. Candidate k uses entry e_k = (k * a_stride) & 4095 of the CM_TRAJ_HEADINGS table
+ *      (cm_traj_directions), (c, s). Its linear part is the prior's rows 0 and 1 rotated about world z through the vehicle's
+ *      position: for j = 0..2, Q0j = c * P0j - s * P1j, Q1j = s * P0j + c * P1j in fp32, each product and the difference or
+ *      sum rounded on its own, nothing fused (P0j is P[j], P1j is P[4 + j]). The translation stays (P3, P7). For k = 0 the
+ *      entry is exactly (1, 0): Q equals P in value.
+ *   4. Cells of a candidate. A counted point is what the map's step 3 calls a counted point of A: in A, valid, inside the
+ *      closed height band. Its world cell under Q_k is the map's step 1 (wx = ((Q00*x + Q01*y) + Q02*z) + P3, wy likewise
+ *      with row 1 and P7, floorf(w * inv), the same existence test) minus the map's current anchor. D_k is the set of distinct
+ *      window cells of all sensors' counted points; a point whose cell does not exist or lies outside the window under Q_k is
+ *      dropped for that k only.
+ *   5. Score. For i = -wx .. wx, j = -wy .. wy: S(k, i, j) = sum over c in D_k of L(c + (i, j)) as uint32_t (with
+ *      nx * ny <= 2^22 and bytes it cannot overflow); shifted cells outside the window contribute 0. The entry index is
+ *      ((k + n_a) * (2 wy + 1) + (j + wy)) * (2 wx + 1) + (i + wx).
+ *   6. Best. The entry with the largest S; ties go to the smallest i * i + j * j, then the smallest |k|, then the lowest
+ *      entry index. An empty map, or a frame without counted points, gives all zeros: the prior wins.
+ *   7. Sub-cell offset, with CM_MATCH_SUBCELL only, on the host in double from the volume, per axis (x along i, y along j):
+ *      S-, S+ are the scores of the best entry's two neighbours along that axis (same k, same other index), S0 its own. If
+ *      both neighbours exist and den = S- - 2 * S0 + S+ < 0 (in int64), sub = 0.5 * (double)(S- - S+) / (double)den, clamped
+ *      to [-0.5, 0.5]; otherwise sub = 0. Without the flag both are 0.
+ *   8. Result, cm_match_result: best (the entry index), k, i, j, score; n_cells = |D_k| of the best k and
+ *      max_score = 255 * n_cells; yaw = (float)((double)(k * a_stride) * (6.283185307179586 / 4096.0)); sub[2]; pose[12]: rows
+ *      0 and 1 are Q_k with pose[3] = P3 + (float)(((double)i + sub_x) * (double)cell), an fp32 addition, pose[7] likewise
+ *      from P7, j and sub_y; row 2 is P's. A point's cell under `pose` need not equal its shifted cell of step 5 in the last
+ *      bit (adding a rounded shift to the translation is not shifting the floor of the product): the score is defined by
+ *      step 5, not by `pose`.
+ * cm_map_match_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured cost layer; sigma or max_dist not
+ * finite and > 0; R > CM_MATCH_MAX_RADIUS_CELLS; n_a > 127, a_stride == 0 or n_a * a_stride > 1024; wx or wy above
+ * CM_MATCH_MAX_SHIFT; more than 2^22 candidates (2 n_a + 1)(2 wx + 1)(2 wy + 1); unknown flag bits; a frame in flight.
+ * cm_map_match_evaluate refuses: no matching layer; a stale dist2 (or none yet); a map with n_frames == 0; everything
+ * cm_map_integrate refuses about the result and the pose, except that matching a frame that was already integrated is legal.
+ * All memory of the layer is taken by cm_map_match_configure (the field, the candidates' bitmaps, the volume, the tables, the
+ * page-locked host words): no evaluate or copy allocates. The volume and the result are stale from cm_map_match_configure
+ * and from every cm_map_integrate, cm_map_cost_update and merge until the next cm_map_match_evaluate: cm_map_match_copy and
+ * cm_map_match_device then refuse with CM_BAD_ARG and say since which call. cm_map_cost_configure and cm_map_configure, in
+ * either form, free the layer. It reads the map and the cost layer and writes buffers of its own only: no other layer's
+ * tables or staleness change. With CM_FLAG_PROFILE, cm_get_stage_times after an evaluate lists match_clear, k_match_field,
+ * k_match_mark, k_match_score, k_match_best. Not modelled: branch-and-bound or multi-resolution search (the window is searched
+ * exhaustively), a covariance of the match, roll, pitch and z, weighting a cell by the number of its points. */
+#define CM_MATCH_MAX_RADIUS_CELLS 64
+#define CM_MATCH_MAX_SHIFT 64
+#define CM_MATCH_MAX_ANGLES 127
+#define CM_MATCH_MAX_CANDIDATES (1u << 22)
+#define CM_MATCH_SUBCELL 1u
+typedef struct cm_match_params {       /* 28 bytes, no padding */
+    float sigma;                       /* standard deviation of the field (m); finite, > 0 */
+    float max_dist;                    /* the field is 0 beyond it (m); finite, > 0, at most CM_MATCH_MAX_RADIUS_CELLS cells */
+    uint32_t n_a;                      /* angle candidates -n_a .. n_a; at most CM_MATCH_MAX_ANGLES */
+    uint32_t a_stride;                 /* heading-table entries between two candidates; >= 1, n_a * a_stride <= 1024 */
+    uint32_t wx, wy;                   /* shifts -wx .. wx and -wy .. wy cells; each at most CM_MATCH_MAX_SHIFT */
+    uint32_t flags;                    /* CM_MATCH_SUBCELL or 0 */
+} cm_match_params;
+typedef struct cm_match_result {       /* 96 bytes */
+    uint32_t best;                     /* entry index of step 6 */
+    int32_t k, i, j;                   /* its angle candidate and shift in cells */
+    uint32_t score;                    /* S of the best entry */
+    uint32_t n_cells;                  /* |D_k| of the best k */
+    uint32_t max_score;                /* 255 * n_cells */
+    float yaw;                         /* the best candidate's rotation (rad) */
+    double sub[2];                     /* step 7's offsets along x and y in cells; 0 without CM_MATCH_SUBCELL */
+    float pose[12];                    /* the matched pose, step 8 */
+} cm_match_result;
+/* Non-NULL parameters allocate the layer (volume and result are stale until the first evaluate); NULL frees it. */
+CM_API int cm_map_match_configure(cm_ctx* ctx, const cm_match_params* p);
+/* Matches the last frame against the map around the prior pose. *out may be NULL. */
+CM_API int cm_map_match_evaluate(cm_ctx* ctx, const float pose[12], cm_match_result* out);
+/* Host copy of the (2 n_a + 1)(2 wy + 1)(2 wx + 1) scores; capacity in entries. Fewer: CM_CAPACITY (nothing is copied; *out,
+ * which may be NULL, is still written). */
+CM_API int cm_map_match_copy(cm_ctx* ctx, uint32_t* host_dst, uint64_t capacity, cm_match_result* out);
+/* The same volume in device memory owned by the context, valid until the next cm_map_match_evaluate, cm_map_cost_update,
+ * cm_map_integrate, merge or configure call of the map, the cost layer or this layer. */
+CM_API int cm_map_match_device(cm_ctx* ctx, const void** scores, cm_match_result* out);
+/* The configured layer's field table; capacity in bytes, *n (may be NULL) its length R * R + 1. Too small: CM_CAPACITY. */
+CM_API int cm_map_match_table_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capacity, uint64_t* n);
+/* Step 1's table for a cell, sigma and max_dist. A host function: no context, no GPU. CM_BAD_ARG: a value that is not finite
+ * and > 0, R above CM_MATCH_MAX_RADIUS_CELLS, a NULL dst (nothing is written). Otherwise *n (may be NULL) = R * R + 1, and a
+ * capacity below it: CM_CAPACITY (dst is not written). */
+CM_API int cm_match_table(float cell, float sigma, float max_dist, uint8_t* dst, uint64_t capacity, uint64_t* n);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
