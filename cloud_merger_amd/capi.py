@@ -51,6 +51,7 @@ SYMBOLS = [
     "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
     "cm_map_plan_configure", "cm_map_plan_update", "cm_map_plan_copy", "cm_map_plan_device", "cm_map_plan_path",
     "cm_map_traj_configure", "cm_map_traj_evaluate", "cm_map_traj_copy", "cm_map_traj_device", "cm_traj_directions",
+    "cm_map_frontier_configure", "cm_map_frontier_update", "cm_map_frontier_copy", "cm_map_frontier_labels_copy", "cm_map_frontier_device",
     "cm_map_match_configure", "cm_map_match_evaluate", "cm_map_match_copy", "cm_map_match_device", "cm_map_match_table_copy", "cm_match_table",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
@@ -343,6 +344,37 @@ TRAJ_SCORE_DTYPE = np.dtype([("status", "<u4"), ("bad_step", "<u4"), ("occ", "<u
                              ("end_x", "<f4"), ("end_y", "<f4")])
 assert C.sizeof(TrajParams) == 24 and C.sizeof(TrajWindow) == 32 and C.sizeof(TrajScore) == 32 == TRAJ_SCORE_DTYPE.itemsize and C.sizeof(TrajInfo) == 24
 
+# frontier layer behind the plan layer: connected frontiers of the occupancy map (cm_map_frontier_configure, cm_map_frontier_update)
+FRONTIER_NONE = 0xFFFFFFFF
+FRONTIER_MAX_TABLE = 1 << 16
+
+
+class FrontierParams(C.Structure):
+    """cm_frontier_params (20 bytes): the smallest component that is a frontier (>= 1), the table's entries
+    (1..FRONTIER_MAX_TABLE), the largest cost byte of a frontier cell (0..252), the two weights of the score."""
+    _fields_ = [("min_cells", C.c_uint32), ("max_frontiers", C.c_uint32), ("max_cost", C.c_uint32), ("pot_scale", C.c_uint32),
+                ("gain_scale", C.c_uint32)]
+
+
+class Frontier(C.Structure):
+    """cm_frontier (40 bytes): the smallest cell and the cell count, the sums of ix and iy, the smallest pot and the lowest cell
+    that has it (PLAN_UNREACHABLE and FRONTIER_NONE: none reachable), the closed bounding box."""
+    _fields_ = [("first_cell", C.c_uint32), ("n_cells", C.c_uint32), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64),
+                ("min_pot", C.c_uint32), ("min_pot_cell", C.c_uint32), ("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16),
+                ("y1", C.c_uint16)]
+
+
+class FrontierInfo(C.Structure):
+    """cm_frontier_info (32 bytes): frontier cells, components, frontiers, table entries written, the best entry
+    (FRONTIER_NONE: none) and its score."""
+    _fields_ = [("n_frontier_cells", C.c_uint32), ("n_components", C.c_uint32), ("n_frontiers", C.c_uint32), ("n_written", C.c_uint32),
+                ("best", C.c_uint32), ("_pad", C.c_uint32), ("best_score", C.c_int64)]
+
+
+FRONTIER_DTYPE = np.dtype([("first_cell", "<u4"), ("n_cells", "<u4"), ("sum_x", "<u8"), ("sum_y", "<u8"), ("min_pot", "<u4"),
+                           ("min_pot_cell", "<u4"), ("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
+assert C.sizeof(FrontierParams) == 20 and C.sizeof(Frontier) == 40 == FRONTIER_DTYPE.itemsize and C.sizeof(FrontierInfo) == 32
+
 # scan matching of the frame against the occupancy map, behind the cost layer (cm_map_match_configure, cm_map_match_evaluate)
 MATCH_MAX_RADIUS_CELLS = 64
 MATCH_MAX_SHIFT = 64
@@ -571,6 +603,11 @@ def load():
     L.cm_map_traj_copy.argtypes = [vp, vp, u64, C.POINTER(TrajInfo)]
     L.cm_map_traj_device.argtypes = [vp, C.POINTER(vp), C.POINTER(TrajInfo)]
     L.cm_traj_directions.argtypes = [vp, u64]
+    L.cm_map_frontier_configure.argtypes = [vp, C.POINTER(FrontierParams)]
+    L.cm_map_frontier_update.argtypes = [vp, C.POINTER(FrontierInfo), C.POINTER(MapInfo)]
+    L.cm_map_frontier_copy.argtypes = [vp, vp, u64, C.POINTER(FrontierInfo)]
+    L.cm_map_frontier_labels_copy.argtypes = [vp, vp, u64, C.POINTER(FrontierInfo)]
+    L.cm_map_frontier_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(FrontierInfo)]
     L.cm_map_match_configure.argtypes = [vp, C.POINTER(MatchParams)]
     L.cm_map_match_evaluate.argtypes = [vp, vp, C.POINTER(MatchResult)]
     L.cm_map_match_copy.argtypes = [vp, vp, u64, C.POINTER(MatchResult)]
@@ -1221,6 +1258,52 @@ class CloudMerger:
         ptr, info = C.c_void_p(), TrajInfo()
         self._check(self._lib.cm_map_traj_device(self._ctx, C.byref(ptr), C.byref(info)), "cm_map_traj_device")
         return ptr.value, info
+
+    # ---- frontier layer behind the plan layer (cm_map_frontier_configure / cm_map_frontier_update) ----
+    def map_frontier_configure(self, min_cells=1, max_frontiers=FRONTIER_MAX_TABLE, max_cost=252, pot_scale=1, gain_scale=0):
+        """Allocates the frontier layer behind the configured plan layer: the free cells of the map's image with a cost byte of
+        at most max_cost and an unknown edge neighbour, 8-connected, the components of at least min_cells cells numbered by
+        their smallest cell, a table of at most max_frontiers of them and the one with the lowest pot_scale * min_pot -
+        gain_scale * n_cells. min_cells None frees the layer."""
+        if min_cells is None:
+            self._check(self._lib.cm_map_frontier_configure(self._ctx, None), "cm_map_frontier_configure")
+            return
+        p = FrontierParams(int(min_cells), int(max_frontiers), int(max_cost), int(pot_scale), int(gain_scale))
+        self._check(self._lib.cm_map_frontier_configure(self._ctx, C.byref(p)), "cm_map_frontier_configure")
+
+    def map_frontier_update(self):
+        """Computes labels, table and info from the map's image and the fresh cost table and pot. Returns the FrontierInfo."""
+        info = FrontierInfo()
+        self._check(self._lib.cm_map_frontier_update(self._ctx, C.byref(info), None), "cm_map_frontier_update")
+        return info
+
+    def map_frontiers(self):
+        """((n_written,) FRONTIER_DTYPE table, FrontierInfo) of the last update; entry k is frontier k."""
+        info = FrontierInfo()
+        st = self._lib.cm_map_frontier_copy(self._ctx, None, 0, C.byref(info))
+        if st != CAPACITY:
+            self._check(st, "cm_map_frontier_copy")
+        out = np.empty(info.n_written, dtype=FRONTIER_DTYPE)
+        self._check(self._lib.cm_map_frontier_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_frontier_copy")
+        return out, info
+
+    def map_frontier_labels(self):
+        """((ny, nx) uint32 labels, FrontierInfo) of the last update: a frontier's number, FRONTIER_NONE elsewhere."""
+        info, m = FrontierInfo(), MapInfo()
+        st = self._lib.cm_map_copy(self._ctx, None, 0, C.byref(m))
+        if st != CAPACITY:
+            self._check(st, "cm_map_copy")
+        n = m.nx * m.ny
+        out = np.empty(n, dtype=np.uint32)
+        self._check(self._lib.cm_map_frontier_labels_copy(self._ctx, out.ctypes.data, n, C.byref(info)), "cm_map_frontier_labels_copy")
+        return out.reshape(m.ny, m.nx), info
+
+    def map_frontier_device(self):
+        """(labels device pointer, table device pointer, FrontierInfo) of the same tables, owned by the context and valid until
+        the next update, integrate or configure call."""
+        labels, table, info = C.c_void_p(), C.c_void_p(), FrontierInfo()
+        self._check(self._lib.cm_map_frontier_device(self._ctx, C.byref(labels), C.byref(table), C.byref(info)), "cm_map_frontier_device")
+        return labels.value, table.value, info
 
     # ---- scan matching of the frame against the map, behind the cost layer (cm_map_match_configure / cm_map_match_evaluate) ----
     def map_match_configure(self, sigma=None, max_dist=0.5, n_a=0, a_stride=1, wx=0, wy=0, subcell=False):

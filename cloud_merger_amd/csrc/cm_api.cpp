@@ -1252,6 +1252,94 @@ int cm_map_traj_device(cm_ctx* c, const void** scores, cm_traj_info* info) {
     return CM_OK;
 }
 
+static_assert(sizeof(cm_frontier_params) == 20 && sizeof(cm_frontier) == 40 && sizeof(cm_frontier_info) == 32 && offsetof(cm_frontier_info, best_score) == 24,
+              "the frontier layer's three structs");
+static_assert(sizeof(CmFrontEntryDev) == sizeof(cm_frontier) && offsetof(cm_frontier, sum_x) == offsetof(CmFrontEntryDev, sum_x) &&
+                  offsetof(cm_frontier, min_pot) == offsetof(CmFrontEntryDev, key) && offsetof(cm_frontier, x0) == offsetof(CmFrontEntryDev, box01),
+              "k_front_best writes cm_frontier");
+static_assert(CM_FRONTIER_NONE == CM_FRONT_NONE_DEV && CM_FRONTIER_MAX_TABLE == CM_FRONT_MAX_TABLE_DEV && CM_FRONTIER_NONE == CM_PLAN_UNREACHABLE,
+              "the kernels' constants");
+
+int cm_map_frontier_configure(cm_ctx* c, const cm_frontier_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!p) return map_frontier_configure(c, nullptr);
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
+    if (p->min_cells < 1u) return fail(c, CM_BAD_ARG, "min_cells must be at least 1");
+    if (p->max_frontiers < 1u || p->max_frontiers > CM_FRONTIER_MAX_TABLE) return fail(c, CM_BAD_ARG, "max_frontiers must lie in 1..CM_FRONTIER_MAX_TABLE");
+    if (p->max_cost > 252u) return fail(c, CM_BAD_ARG, "max_cost must lie in 0..252");
+    if (c->map_info.nx > 0xFFFFu || c->map_info.ny > 0xFFFFu) return fail(c, CM_BAD_ARG, "the window is too large for a 16-bit box");
+    return map_frontier_configure(c, p);
+}
+
+// The refusals every call on a configured frontier layer shares; the reads also refuse stale frontiers.
+static int front_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
+    if (!c->front_on) return fail(c, CM_BAD_ARG, "no frontier layer (cm_map_frontier_configure first)");
+    if (read && c->front_stale) return fail(c, CM_BAD_ARG, c->front_stale);
+    return CM_OK;
+}
+
+int cm_map_frontier_update(cm_ctx* c, cm_frontier_info* out, cm_map_info* map) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = front_check(c, false)) return e;
+    if (c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
+    if (const int e = map_frontier_update(c)) return e;
+    if (out) *out = c->front_info;
+    if (map) *map = c->map_info;
+    return CM_OK;
+}
+
+int cm_map_frontier_copy(cm_ctx* c, cm_frontier* host_dst, uint64_t capacity, cm_frontier_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = front_check(c, true)) return e;
+    if (info) *info = c->front_info;
+    const uint64_t n = c->front_info.n_written;
+    if (n > capacity) return fail(c, CM_CAPACITY, "frontier destination too small");
+    if (n == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->front_table, n * sizeof(cm_frontier), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_frontier);
+    return CM_OK;
+}
+
+int cm_map_frontier_labels_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_frontier_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = front_check(c, true)) return e;
+    if (info) *info = c->front_info;
+    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    if (n > capacity_cells) return fail(c, CM_CAPACITY, "label destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->front_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(uint32_t);
+    return CM_OK;
+}
+
+int cm_map_frontier_device(cm_ctx* c, const void** labels, const void** table, cm_frontier_info* info) {
+    if (!c) return CM_BAD_ARG;
+    if (labels) *labels = nullptr;
+    if (table) *table = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = front_check(c, true)) return e;
+    if (info) *info = c->front_info;
+    if (labels) *labels = c->front_labels;
+    if (table) *table = c->front_table;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_match_params) == 28 && sizeof(cm_match_result) == 96 && offsetof(cm_match_result, sub) == 32 &&
                   offsetof(cm_match_result, pose) == 48, "the matching layer's two structs");
 static_assert(CM_MATCH_MAX_SHIFT == CM_MATCH_MAX_SHIFT_DEV && 2 * CM_MATCH_MAX_ANGLES + 1 == CM_MATCH_MAX_ANGLES_DEV &&

@@ -1,7 +1,7 @@
 // cm_byproducts.cpp — the tables computed from a frame's result on request, after the frame is done: the per-voxel covariance
 // (voxel_cov), the cluster extraction (clusters) and the boxes of its clusters (cluster_boxes), normals and curvature (normals), the two registrations of a source cloud
 // (align, ndt), and the tables computed from the frame's points rather than its result, the 2-D grid map (grid_map) and the rays cast over it (grid_rays), and the occupancy map those rays accumulate into over the frames (map_configure, map_integrate: the one table a
-// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path) and the rollout layer behind the plan (map_traj_configure, map_traj_evaluate), and the scan matching of the frame against the map behind the cost layer (map_match_configure, map_match_evaluate). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
+// merge does not drop) with the cost layer over its image (map_cost_configure, map_cost_update) and the plan layer behind that (map_plan_configure, map_plan_update, map_plan_path) and the rollout layer behind the plan (map_traj_configure, map_traj_evaluate) and the frontier layer behind it too (map_frontier_configure, map_frontier_update), and the scan matching of the frame against the map behind the cost layer (map_match_configure, map_match_evaluate). Each launches on the context's stream, reads what the frame left and writes only buffers of its own: nothing
 // a later frame reads. What they share lives here once: the buffers of a radix sort (PairSort), a result's centroids in
 // search-grid order (SearchIndex: result_bounds, then the caller's choice of grid, then build_search_index) and the
 // Gauss-Newton loop of a registration (PoseFit, fit_pose). The structs are cm_ctx.hpp's; their buffers are DevBufs
@@ -560,6 +560,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_integrate";
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_integrate";
+    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_integrate";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
     return CM_OK;
 }
@@ -622,6 +623,7 @@ int map_cost_update(cm_ctx* c) {
     c->cost_fresh = true;
     c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_cost_update";
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_cost_update";
+    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_cost_update";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
     return CM_OK;
 }
@@ -632,6 +634,7 @@ int map_cost_update(cm_ctx* c) {
 int map_plan_configure(cm_ctx* c, const cm_plan_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int e = map_traj_configure(c, nullptr, nullptr, 0)) return e;   // the rollout layer goes with the plan layer it reads
+    if (const int e = map_frontier_configure(c, nullptr)) return e;           // and so does the frontier layer
     c->plan_on = false;
     c->plan_stale = "the potential is stale: no cm_map_plan_update since cm_map_plan_configure";
     std::memset(&c->plan_info, 0, sizeof c->plan_info);
@@ -685,6 +688,7 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
     hipStream_t st = c->stream;
     c->plan_stale = "the potential is stale: the last cm_map_plan_update failed";
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_plan_update";
+    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_plan_update";
     c->prof_used = 0;
     prof_mark(c, "k_plan_init");
     cmk_plan_init(st, g, c->plan_pot, flags);
@@ -731,6 +735,92 @@ int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]) {
     collect_stage_times(c);
     std::memcpy(head, c->plan_host, CM_PLAN_PATH_HEAD * sizeof(uint32_t));
     if (head[1] == CM_PLAN_PATH_BROKEN_DEV) return fail(c, CM_INTERNAL, "the potential is not a fixed point: a reachable cell has no step");
+    return CM_OK;
+}
+
+// The frontier layer's memory, all of it: the labels, a size word per cell with the scan's counts and the info words behind
+// them, the table with its box scratch, and the page-locked words the host reads the info from. nullptr gives it back. The
+// layer is stale until the first update.
+int map_frontier_configure(cm_ctx* c, const cm_frontier_params* q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->front_on = false;
+    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since cm_map_frontier_configure";
+    std::memset(&c->front_info, 0, sizeof c->front_info);
+    if (!q) {
+        c->front_labels.release();
+        c->front_words.release();
+        c->front_table.release();
+        c->front_box.release();
+        c->front_host.release();
+        return CM_OK;
+    }
+    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    const size_t n_blocks = static_cast<size_t>((n_cells + CM_FRONT_BLOCK - 1) / CM_FRONT_BLOCK);
+    if (!c->front_labels.reserve(n_cells) || !c->front_words.reserve(n_cells + n_blocks + CM_FRONT_INFO_WORDS) ||
+        !c->front_table.reserve(q->max_frontiers) || !c->front_box.reserve(4 * static_cast<size_t>(q->max_frontiers)) ||
+        !c->front_host.reserve(CM_FRONT_INFO_WORDS))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the frontier layer");
+    c->front_params = *q;
+    c->front_on = true;
+    return CM_OK;
+}
+
+// Labels, table and info of the current image, cost table and pot (cm_kernels_front.hip; the semantics are in
+// include/cloudmerge.h): eight launches in a fixed order behind one clear of the info words, one copy of those words and one
+// wait. No loop on the host, and no allocation: cm_map_frontier_configure made them all.
+int map_frontier_update(cm_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_frontier_params& q = c->front_params;
+    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    CmFrontDev g;
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.tiles_x = (g.nx + CM_FRONT_TILE - 1) / CM_FRONT_TILE;
+    g.tiles_y = (g.ny + CM_FRONT_TILE - 1) / CM_FRONT_TILE;
+    g.n_blocks = static_cast<uint32_t>((n_cells + CM_FRONT_BLOCK - 1) / CM_FRONT_BLOCK);
+    g.min_cells = q.min_cells;
+    g.max_frontiers = q.max_frontiers;
+    g.max_cost = q.max_cost;
+    g.pot_scale = q.pot_scale;
+    g.gain_scale = q.gain_scale;
+    uint32_t* labels = c->front_labels;
+    uint32_t* size = c->front_words;
+    uint32_t* counts = size + n_cells;
+    uint32_t* info = counts + g.n_blocks;
+    hipStream_t st = c->stream;
+    c->front_stale = "the frontiers are stale: the last cm_map_frontier_update failed";
+    c->prof_used = 0;
+    HIP_TRY(c, hipMemsetAsync(info, 0, CM_FRONT_INFO_WORDS * sizeof(uint32_t), st));
+    prof_mark(c, "k_front_local");
+    cmk_front_local(st, c->map_image, c->cost_cells, g, labels, size, info);
+    prof_mark(c, "k_front_merge");
+    cmk_front_merge(st, g, labels);
+    prof_mark(c, "k_front_flatten");
+    cmk_front_flatten(st, g, labels, size);
+    prof_mark(c, "k_front_count");
+    cmk_front_count(st, g, labels, size, counts, info);
+    prof_mark(c, "k_front_scan");
+    cmk_front_scan(st, g, counts, info);
+    prof_mark(c, "k_front_number");
+    cmk_front_number(st, g, labels, size, counts, c->front_table, c->front_box);
+    prof_mark(c, "k_front_table");
+    cmk_front_table(st, g, c->plan_pot, labels, size, c->front_table, c->front_box);
+    prof_mark(c, "k_front_best");
+    cmk_front_best(st, g, c->front_table, c->front_box, info);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->front_host, info, CM_FRONT_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    const uint32_t* h = c->front_host;
+    c->front_info.n_frontier_cells = h[0];
+    c->front_info.n_components = h[1];
+    c->front_info.n_frontiers = h[2];
+    c->front_info.n_written = h[3];
+    c->front_info.best = h[4];
+    c->front_info._pad = 0u;
+    c->front_info.best_score = static_cast<int64_t>(static_cast<uint64_t>(h[6]) | (static_cast<uint64_t>(h[7]) << 32));
+    c->front_stale = nullptr;
     return CM_OK;
 }
 

@@ -319,6 +319,19 @@ struct cm_ctx {
     PinnedBuf<uint32_t> traj_host;       // CM_TRAJ_INFO_WORDS words read back, then the nv + nw words an evaluate uploads
     std::vector<float> traj_v, traj_w;   // the samples of the last evaluate (nv and nw entries from the configure call on)
 
+    // Frontier layer behind the plan layer (cm_kernels_front.hip), configured by cm_map_frontier_configure and recomputed by
+    // cm_map_frontier_update from map_image, cost_cells and plan_pot. Buffers of its own, all allocated by the configure call;
+    // it lives and goes with the plan layer (map_plan_configure frees it).
+    bool front_on = false;               // a frontier layer is configured
+    const char* front_stale = nullptr;   // why labels and table are not those of the current tables; nullptr: they are
+    cm_frontier_params front_params{};
+    cm_frontier_info front_info{};
+    DevBuf<uint32_t> front_labels;       // a word per cell: parents, then roots, then the frontier numbers
+    DevBuf<uint32_t> front_words;        // a size word per cell, the counts of the scan (one per CM_FRONT_BLOCK cells), CM_FRONT_INFO_WORDS info words
+    DevBuf<CmFrontEntryDev> front_table; // max_frontiers entries
+    DevBuf<uint32_t> front_box;          // four words per entry: the box while it is reduced
+    PinnedBuf<uint32_t> front_host;      // CM_FRONT_INFO_WORDS words read back
+
     // Scan matching layer behind the cost layer (cm_kernels_match.hip), configured by cm_map_match_configure and evaluated by
     // cm_map_match_evaluate from the frame at rest, map_info and cost_dist2. Buffers of its own, all allocated by the
     // configure call; it lives and goes with the cost layer (map_cost_configure frees it).
@@ -466,6 +479,10 @@ const float* traj_direction_table();
 void traj_samples(float lo, float hi, uint32_t n, float* out);
 int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot);
 int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]);
+// The frontier layer behind the plan layer. map_frontier_configure: room for the map's window and q's table (nullptr: the
+// buffers go). map_frontier_update: labels, table and front_info of the current image, cost table and pot.
+int map_frontier_configure(cm_ctx* c, const cm_frontier_params* q);
+int map_frontier_update(cm_ctx* c);
 // The scan matching layer behind the cost layer. map_match_configure: room for q's candidates over the map's window and the
 // field table at radius R cells, which is built and uploaded (nullptr: the buffers go). map_match_evaluate: the volume and
 // match_result for a prior that cm_map_match_evaluate has checked.

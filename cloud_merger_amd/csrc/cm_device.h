@@ -427,3 +427,31 @@ struct CmMatchDev {
     uint32_t words;                    // bitmap words of one candidate
     uint32_t r2;                       // the field table has r2 + 1 entries
 };
+
+// Frontier layer behind the plan layer (cm_kernels_front.hip). k_front_local gives a workgroup of CM_FRONT_BLOCK threads one
+// tile of CM_FRONT_TILE x CM_FRONT_TILE cells, one thread per cell, with the image bytes of the tile and one ring of cells
+// around it in LDS. The cell passes (merge, flatten, count, number, table) run CM_FRONT_BLOCK cells per workgroup, and the
+// scan of their counts and k_front_best are one workgroup each. The info words the host reads back: the frontier cells, the
+// components, the frontiers, the entries written, best, one spare, then the score's low and high word. A table entry on the
+// device is cm_frontier with min_pot and min_pot_cell as one 64-bit key (pot << 32 | cell: an atomicMin keeps the smallest
+// pot and the lowest cell that has it) and the box in a scratch table of four words per entry, since there is no 16-bit
+// atomic; k_front_best puts both into cm_frontier's form.
+#define CM_FRONT_TILE 32
+#define CM_FRONT_BLOCK 1024
+#define CM_FRONT_INFO_WORDS 8
+#define CM_FRONT_SLOTS 32              // per workgroup of k_front_flatten and k_front_table: keys whose waves combine in LDS first
+#define CM_FRONT_NONE_DEV 0xFFFFFFFFu
+#define CM_FRONT_MAX_TABLE_DEV 65536u
+struct CmFrontDev {
+    uint32_t nx, ny;
+    uint32_t tiles_x, tiles_y;
+    uint32_t n_blocks;                 // (nx * ny + CM_FRONT_BLOCK - 1) / CM_FRONT_BLOCK
+    uint32_t min_cells, max_frontiers, max_cost;
+    uint32_t pot_scale, gain_scale;
+};
+struct CmFrontEntryDev {               // cm_frontier
+    uint32_t first_cell, n_cells;
+    unsigned long long sum_x, sum_y;
+    unsigned long long key;            // until k_front_best: pot << 32 | cell; then min_pot (low word) and min_pot_cell
+    uint32_t box01, box23;             // x0 | y0 << 16, x1 | y1 << 16 (written by k_front_best)
+};

@@ -293,3 +293,20 @@ void cmk_match_mark(hipStream_t s, const CmFrameDev* fd, const CmMatchDev& g, co
                     uint32_t n_tiles);
 void cmk_match_score(hipStream_t s, const unsigned char* field, const uint32_t* bits, const CmMatchDev& g, uint32_t* vol);
 void cmk_match_best(hipStream_t s, const uint32_t* vol, const uint32_t* bits, const CmMatchDev& g, uint32_t* info);
+
+// ---- frontier layer behind the plan layer (cm_kernels_front.hip) -------------------------------------------------------------------
+// image, cost, pot: the map's image, the cost and the plan layer's tables. labels: a word per cell (parents, then roots, then
+// frontier numbers). size: a word per cell (a root's cell count, then its number). counts: g.n_blocks words. info:
+// CM_FRONT_INFO_WORDS words, zero before cmk_front_local. table: g.max_frontiers entries; box: four words per entry.
+// The calls run in this order; every one is a single launch.
+void cmk_front_local(hipStream_t s, const void* image, const unsigned char* cost, const CmFrontDev& g, uint32_t* labels, uint32_t* size,
+                     uint32_t* info);
+void cmk_front_merge(hipStream_t s, const CmFrontDev& g, uint32_t* labels);
+void cmk_front_flatten(hipStream_t s, const CmFrontDev& g, uint32_t* labels, uint32_t* size);
+void cmk_front_count(hipStream_t s, const CmFrontDev& g, const uint32_t* labels, const uint32_t* size, uint32_t* counts, uint32_t* info);
+void cmk_front_scan(hipStream_t s, const CmFrontDev& g, uint32_t* counts, uint32_t* info);
+void cmk_front_number(hipStream_t s, const CmFrontDev& g, const uint32_t* labels, uint32_t* size, const uint32_t* counts,
+                      CmFrontEntryDev* table, uint32_t* box);
+void cmk_front_table(hipStream_t s, const CmFrontDev& g, const uint32_t* pot, uint32_t* labels, const uint32_t* size,
+                     CmFrontEntryDev* table, uint32_t* box);
+void cmk_front_best(hipStream_t s, const CmFrontDev& g, CmFrontEntryDev* table, const uint32_t* box, uint32_t* info);

@@ -233,6 +233,10 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "map_inflate_unknown") ok = read_flag(is, &c.map_inflate_unknown);
         else if (key == "map_plan") ok = read(is, c.map_plan_neutral, c.map_plan_factor_q8) && c.map_plan_neutral <= 255u && c.map_plan_factor_q8 <= 256u;
         else if (key == "map_plan_allow_unknown") ok = read_flag(is, &c.map_plan_allow_unknown);
+        else if (key == "map_frontier") ok = read(is, c.map_frontier_min_cells, c.map_frontier_max) && c.map_frontier_max >= 1u && c.map_frontier_max <= CM_FRONTIER_MAX_TABLE;
+        else if (key == "map_frontier_max_cost") ok = read(is, c.map_frontier_max_cost) && c.map_frontier_max_cost <= 252u;
+        else if (key == "map_frontier_scales") ok = read(is, c.map_frontier_pot_scale, c.map_frontier_gain_scale);
+        else if (key == "map_goal_vehicle") ok = read_flag(is, &c.map_goal_vehicle);
         else if (key == "map_goal") { ok = read(is, c.map_goal[0], c.map_goal[1]) && std::isfinite(c.map_goal[0]) && std::isfinite(c.map_goal[1]); c.map_has_goal = ok; }
         else if (key == "traj") ok = read(is, c.traj_nv, c.traj_nw, c.traj_steps, c.traj_dt) &&
                                      (c.traj_nv == 0u || (c.traj_nw >= 1u && static_cast<uint64_t>(c.traj_nv) * c.traj_nw <= CM_TRAJ_MAX_SAMPLES &&
@@ -348,6 +352,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
                                         cfg_.map_nx * cfg_.map_ny};
                 if (cm_map_plan_configure(ctx_, &pp) != CM_OK) refuse("cm_map_plan_configure");
+                if (ctx_ && cfg_.map_frontier_min_cells > 0u) {    // the frontier layer behind the plan layer
+                    const cm_frontier_params fp{cfg_.map_frontier_min_cells, cfg_.map_frontier_max, cfg_.map_frontier_max_cost,
+                                                cfg_.map_frontier_pot_scale, cfg_.map_frontier_gain_scale};
+                    if (cm_map_frontier_configure(ctx_, &fp) != CM_OK) refuse("cm_map_frontier_configure");
+                }
                 if (ctx_ && cfg_.traj_nv > 0u) {                   // the rollout layer behind the plan layer
                     std::vector<float> foot;
                     if (traj_footprint_lattice(cfg_.traj_footprint[0], cfg_.traj_footprint[1], cfg_.traj_footprint[2], cfg_.map_cell, &foot))
@@ -491,6 +500,14 @@ int CloudMergerNode::set_goal(float x, float y) {
     return CM_OK;
 }
 
+bool CloudMergerNode::explore_goal(float* x, float* y) const {
+    if (frontier_info_.best == CM_FRONTIER_NONE || frontier_info_.best >= frontiers_.size()) return false;
+    const uint32_t c = frontiers_[frontier_info_.best].min_pot_cell;
+    if (x) *x = (static_cast<float>(map_info_.anchor[0] + static_cast<int32_t>(c % map_info_.nx)) + 0.5f) * cfg_.map_cell;
+    if (y) *y = (static_cast<float>(map_info_.anchor[1] + static_cast<int32_t>(c / map_info_.nx)) + 0.5f) * cfg_.map_cell;
+    return true;
+}
+
 bool CloudMergerNode::best_command(float* v, float* w) const {
     if (traj_scores_.empty() || traj_info_.best == CM_TRAJ_NONE) return false;
     if (v) *v = traj_info_.best_v;
@@ -541,6 +558,9 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
     map_path_info_ = cm_path_info{};
     traj_scores_.clear();
     traj_info_ = cm_traj_info{};
+    frontiers_.clear();
+    frontier_info_ = cm_frontier_info{};
+    frontier_info_.best = CM_FRONTIER_NONE;
     if (st != CM_OK) {
         map_cells_.clear();
         map_image_.clear();
@@ -559,6 +579,11 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
         goal[1] = goal_[1];
         has_goal = has_goal_;
     }
+    if (cfg_.map_goal_vehicle) {                       // exploration: the goal is where the vehicle is
+        goal[0] = pose[3];
+        goal[1] = pose[7];
+        has_goal = true;
+    }
     if (cfg_.map_inflation_radius > 0.0f && cfg_.map_plan_neutral > 0u && has_goal) {
         map_potential_.resize(n);
         map_path_.resize(n);
@@ -572,6 +597,24 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
             map_path_info_ = cm_path_info{};
             set_error(cm_last_error(ctx_));
             if (ps != CM_BAD_ARG) return ps;
+        }
+        // The frontiers behind the plan: the table, and the choice among its entries. No frontier with a reachable cell is an
+        // answer, not a failure: explore_goal() is empty and error() says so.
+        if (ps == CM_OK && cfg_.map_frontier_min_cells > 0u) {
+            int fs = cm_map_frontier_update(ctx_, &frontier_info_, nullptr);
+            if (fs == CM_OK) {
+                frontiers_.resize(frontier_info_.n_written);
+                fs = cm_map_frontier_copy(ctx_, frontiers_.data(), frontiers_.size(), nullptr);
+            }
+            if (fs != CM_OK) {
+                frontiers_.clear();
+                frontier_info_ = cm_frontier_info{};
+                frontier_info_.best = CM_FRONTIER_NONE;
+                set_error(cm_last_error(ctx_));
+                if (fs != CM_BAD_ARG) return fs;
+            } else if (frontier_info_.best == CM_FRONTIER_NONE) {
+                set_error("no frontier with a reachable cell: nothing to explore");
+            }
         }
         // The rollout behind the plan: every velocity sample from the pose. Without a plan there is nothing to score against;
         // a start the library refuses leaves the results empty like the path.

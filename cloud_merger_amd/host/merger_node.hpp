@@ -128,6 +128,14 @@ struct NodeConfig {
     bool map_plan_allow_unknown = false;
     bool map_has_goal = false;
     float map_goal[2] = {0.0f, 0.0f};                // world frame, metres
+    // Frontier layer behind that plan layer (cm_map_frontier_configure, cm_map_frontier_update): the connected frontiers of
+    // the map's image and the one to explore next. Off by default (min_cells 0). On (it needs map_plan): the node configures
+    // the layer behind the plan layer and updates it behind every plan update (frontiers(), frontier_info(), explore_goal()).
+    // map_goal_vehicle makes the plan's goal of every frame the pose's cell instead of map_goal, which is what exploration
+    // wants: pot is then the cost of the walk between a cell and the vehicle.
+    uint32_t map_frontier_min_cells = 0, map_frontier_max = 256, map_frontier_max_cost = 252;
+    uint32_t map_frontier_pot_scale = 1, map_frontier_gain_scale = 0;
+    bool map_goal_vehicle = false;
     // Rollout layer behind that plan layer (cm_map_traj_configure, cm_map_traj_evaluate): sampled velocity commands rolled
     // forward from the pose and scored over the cost table and the potential. Off by default (traj_nv 0). On (it needs the plan
     // layer): the node lays a filled lattice over the footprint rectangle (traj_footprint_lattice), configures the layer behind
@@ -191,6 +199,9 @@ struct NodeConfig {
 //   map_thresholds <free> <occ> | map_ray_range <cells>   (the occupancy map accumulated over the frames; map_cell 0: off)
 //   map_inflation <inscribed> <inflation> <scaling> | map_inflate_unknown <0|1>   (the cost layer over that map: radii in metres,
 //   the decay per metre; an inflation radius of 0: off)
+//   map_frontier <min_cells> <max_frontiers> | map_frontier_max_cost <0..252> | map_frontier_scales <pot> <gain> |
+//   map_goal_vehicle <0|1>   (the frontier layer behind the plan layer: min_cells 0: off, at most 65536 table entries; with
+//   map_goal_vehicle the plan's goal of every frame is the pose's cell)
 //   map_plan <neutral> <factor_q8> | map_plan_allow_unknown <0|1> | map_goal <x> <y>   (the plan layer behind that cost layer:
 //   neutral 1..255 and the cost's factor in 1/256, 0..256; neutral 0: off; the goal in the world frame, metres)
 //   traj <nv> <nw> <n_steps> <dt> | traj_limits <v_lo> <v_hi> <w_lo> <w_hi> | traj_footprint <x_back> <x_front> <half_width> |
@@ -310,6 +321,12 @@ public:
     const std::vector<uint32_t>& map_path() const { return map_path_; }
     const cm_plan_info& map_plan_info() const { return map_plan_info_; }
     const cm_path_info& map_path_info() const { return map_path_info_; }
+    // map_frontier with min_cells > 0 and a plan: the table of the frontiers of the same window after the same frame, its info,
+    // and the world centre of the best frontier's min_pot_cell, the place to drive to next. Empty (explore_goal false) while
+    // there is no plan and after a frame that left no frontier with a reachable cell (error() says so; the frame stands).
+    const std::vector<cm_frontier>& frontiers() const { return frontiers_; }
+    const cm_frontier_info& frontier_info() const { return frontier_info_; }
+    bool explore_goal(float* x, float* y) const;
     // traj with nv > 0, behind a plan: the score of every velocity sample from the pose of the same frame, entry i * nw + j, and
     // the best of them. Empty (best_command false) while there is no plan, and after a frame whose goal or vehicle lay outside
     // the window (error() says which).
@@ -394,6 +411,8 @@ private:
     std::vector<uint32_t> map_potential_, map_path_;
     cm_plan_info map_plan_info_{};
     cm_path_info map_path_info_{};
+    std::vector<cm_frontier> frontiers_;
+    cm_frontier_info frontier_info_{};
     std::vector<cm_traj_score> traj_scores_;
     cm_traj_info traj_info_{};
     bool matched_ = false;

@@ -1055,6 +1055,88 @@ CM_API int cm_map_match_table_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capa
  * capacity below it: CM_CAPACITY (dst is not written). */
 CM_API int cm_match_table(float cell, float sigma, float max_dist, uint8_t* dst, uint64_t capacity, uint64_t* n);
 
+/* ---- frontier layer behind the plan layer: connected frontiers of the occupancy map (an extension) ------------------------
+ * Where to go when nobody gives a goal: every exploration stack over an occupancy grid (Yamauchi's frontiers,
+ * frontier_exploration, explore_lite) takes the cells where known free space meets the unknown, groups them into connected
+ * frontiers and ranks those by their size and the cost of getting there. The frontier layer is configured once behind the
+ * plan layer and recomputed on request. Every quantity below is an integer and every reduction commutative
+ * (count, sum, min, max), and a component is named by its smallest cell: labels, table and info are bit for bit a function
+ * of the three input tables and the parameters, whatever the order in which the device works.
+ * Input: the map's image I (int8_t, entry ix + iy * nx: -1 unknown, 0 free, 100 occupied), the cost layer's fresh cost table,
+ * the plan layer's fresh pot, and the map's info. In exploration the caller sets the plan's goal to the vehicle's position
+ * (cm_map_plan_update with the pose's x and y): pot(c) is then the exact cost of the cheapest walk between c and the vehicle
+ * by the plan layer's steps 3 and 4, where a step charges k times the weight of the cell left behind when walking towards
+ * the goal, that is, of the cell farther from the vehicle.
+ *   1. Frontier cell. c is a frontier cell iff I(c) == 0, cost(c) <= max_cost, and at least one of its four edge neighbours
+ *      inside the window has I == -1. A cell outside the window is not unknown: what scrolled out is forgotten.
+ *   2. Components. Frontier cells are 8-connected, with no corner rule: a diagonal pair is connected. A component's
+ *      first_cell is its smallest cell index ix + iy * nx.
+ *   3. Frontiers. A component with n_cells >= min_cells is a frontier. Frontiers are numbered from 0 in ascending order of
+ *      first_cell.
+ *   4. Labels. One uint32_t per window cell (entry ix + iy * nx): the frontier's number for the cells of a frontier,
+ *      CM_FRONTIER_NONE for every other cell, the frontier cells of components below min_cells among them. Numbers at or
+ *      above max_frontiers still appear in the labels.
+ *   5. Table. cm_frontier, entry k = frontier k, the first n_written = min(n_frontiers, max_frontiers) of them: first_cell,
+ *      n_cells; sum_x, sum_y, the sums of ix and of iy over the frontier's cells (the centroid is the caller's division; 64
+ *      bits, since 4 M cells times 2047 do not fit 32); min_pot, the smallest pot over the frontier's cells, and
+ *      min_pot_cell, the lowest cell index that has it (every cell CM_PLAN_UNREACHABLE: CM_PLAN_UNREACHABLE and
+ *      CM_FRONTIER_NONE; min_pot is then "not defined"); x0, y0, x1, y1, the closed bounding box in window cells.
+ *   6. Choice. For a table entry with min_pot defined, score = pot_scale * min_pot - gain_scale * n_cells as an integer
+ *      (explore_lite's cost in integers); both products fit 64 unsigned bits, the difference is exact, and a score above
+ *      INT64_MAX is stored and compared as INT64_MAX: nothing wraps. best is the entry with the lowest score, ties go to
+ *      the lowest number. No entry with min_pot defined: best is CM_FRONTIER_NONE and best_score 0.
+ *   7. Info. cm_frontier_info: n_frontier_cells (step 1), n_components (step 2), n_frontiers (step 3), n_written (step 5),
+ *      best and best_score (step 6).
+ * cm_map_frontier_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured plan layer (or none of its
+ * parents); min_cells 0; max_frontiers 0 or above CM_FRONTIER_MAX_TABLE; max_cost above 252; a frame in flight. All memory of
+ * the layer is taken by cm_map_frontier_configure (the labels, a size word per cell, the counts of the numbering scan, the
+ * table and its box scratch, the page-locked info words): no update allocates, and nothing is kept per cell but those two
+ * words. The layer is stale from cm_map_frontier_configure and from every cm_map_integrate, cm_map_cost_update and
+ * cm_map_plan_update until the next cm_map_frontier_update, which itself refuses a stale plan layer: the copies and
+ * cm_map_frontier_device then refuse with CM_BAD_ARG and say since which call. cm_map_plan_configure, cm_map_cost_configure
+ * and cm_map_configure, in either form, free the layer; like the map it survives merges, and nothing else depends on whether
+ * it exists: not a frame, the map, or any other layer's bytes. With CM_FLAG_PROFILE, cm_get_stage_times after an update
+ * lists k_front_local, k_front_merge, k_front_flatten, k_front_count, k_front_scan, k_front_number, k_front_table and
+ * k_front_best. Not modelled: 4-connectivity, frontiers of unknown cells as explore_lite defines them (its frontier cells are
+ * the unknown cells beside free ones), a blacklist of frontiers, a "middle" cell, frontiers outside the window. */
+#define CM_FRONTIER_NONE 0xFFFFFFFFu
+#define CM_FRONTIER_MAX_TABLE 65536u
+typedef struct cm_frontier_params {    /* 20 bytes, no padding */
+    uint32_t min_cells;                /* >= 1: the smallest component that is a frontier */
+    uint32_t max_frontiers;            /* 1..CM_FRONTIER_MAX_TABLE: entries of the table */
+    uint32_t max_cost;                 /* 0..252: the largest cost byte of a frontier cell; 252 admits every passable cell */
+    uint32_t pot_scale;                /* step 6 */
+    uint32_t gain_scale;
+} cm_frontier_params;
+typedef struct cm_frontier {           /* 40 bytes */
+    uint32_t first_cell, n_cells;
+    uint64_t sum_x, sum_y;
+    uint32_t min_pot, min_pot_cell;
+    uint16_t x0, y0, x1, y1;
+} cm_frontier;
+typedef struct cm_frontier_info {      /* 32 bytes */
+    uint32_t n_frontier_cells;
+    uint32_t n_components;
+    uint32_t n_frontiers;
+    uint32_t n_written;
+    uint32_t best;                     /* a table entry, or CM_FRONTIER_NONE */
+    uint32_t _pad;
+    int64_t best_score;
+} cm_frontier_info;
+/* Non-NULL parameters allocate the layer (it is stale until the first update); NULL frees it. */
+CM_API int cm_map_frontier_configure(cm_ctx* ctx, const cm_frontier_params* p);
+/* Computes labels, table and info from the map's image and the fresh cost and plan layers. *out and *map (either may be
+ * NULL) are the layer's and the map's info. */
+CM_API int cm_map_frontier_update(cm_ctx* ctx, cm_frontier_info* out, cm_map_info* map);
+/* Host copy of the table's n_written entries; capacity in entries. Fewer: CM_CAPACITY (nothing is copied; *info, which may
+ * be NULL, is still written). */
+CM_API int cm_map_frontier_copy(cm_ctx* ctx, cm_frontier* host_dst, uint64_t capacity, cm_frontier_info* info);
+/* Host copy of the labels; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied; *info is still written). */
+CM_API int cm_map_frontier_labels_copy(cm_ctx* ctx, uint32_t* host_dst, uint64_t capacity_cells, cm_frontier_info* info);
+/* Both in device memory owned by the context (nx * ny words; n_written entries of cm_frontier), valid until the next
+ * cm_map_frontier_update, cm_map_plan_update, cm_map_cost_update, cm_map_integrate or configure call of the four layers. */
+CM_API int cm_map_frontier_device(cm_ctx* ctx, const void** labels, const void** table, cm_frontier_info* info);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
