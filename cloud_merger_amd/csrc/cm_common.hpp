@@ -679,7 +679,8 @@ __device__ __forceinline__ Acc acc_shfl_down(const Acc& a, int d) {
 
 // Eigen-decomposition of a symmetric 3x3 matrix in fp64 by cyclic Jacobi rotations, 12 sweeps, every operation rounded on
 // its own: `a` ends diagonal (the eigenvalues, unsorted), the columns of `v` are the eigenvectors. Used by the ground stage's
-// plane refit (cm_kernels_ground.hip) and the per-voxel covariance (cm_kernels_cov.hip).
+// plane refit (cm_kernels_ground.hip), the per-voxel covariance (cm_kernels_cov.hip) and the normals' plane fit
+// (nrm_plane, cm_kernels_normals.hip); tests/jacobi_ref.py restates it and the three are pinned to that bit for bit.
 __device__ void jacobi3(double a[3][3], double v[3][3]) {
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) v[i][j] = (i == j) ? 1.0 : 0.0;
     const int P[3] = {0, 0, 1}, Q[3] = {1, 2, 2};

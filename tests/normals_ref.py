@@ -4,8 +4,12 @@ neighbours_brute is the definition: the fp32 d2 of every pair, np.lexsort on (j,
 is the same answer for large inputs: a kd-tree's k + 8 nearest in fp64, their d2 recomputed in fp32, the lexicographic m - 1 of
 them — and brute force for every point whose (k + 8)-th fp64 distance does not clear its chosen last d2 by a relative 1e-5
 (the candidate set might then miss a tie). planes() restates steps 3 to 5 on those neighbourhoods: the sequential fp64 sums,
-the covariance, and — the reference the device's normals are compared with — numpy.linalg.eigh of it."""
+the covariance, and numpy.linalg.eigh of it: the independent cross-check of the device's normals, within tolerances and away
+from small eigenvalue gaps. planes_exact() restates nrm_plane (cm_kernels_normals.hip) in the kernel's own order with the shared
+Jacobi (tests/jacobi_ref.py): normal, curvature and flags of every entry bit for bit, degenerate and invalid ones included."""
 import numpy as np
+
+from tests import jacobi_ref
 
 F32 = np.float32
 VALID = 1
@@ -109,9 +113,69 @@ def planes(xyz, idx, viewpoint=(0.0, 0.0, 0.0)):
     return dict(C=Cm, evals=w, normal=normal, curvature=curv, valid=valid, to_viewpoint=vp)
 
 
-def table(xyz, k, viewpoint=(0.0, 0.0, 0.0), tree=True, stats=None):
+QNAN = np.uint32(0x7FC00000)
+
+
+def planes_exact(xyz, idx, viewpoint=(0.0, 0.0, 0.0)):
+    """nrm_plane on the neighbourhoods idx (n, m - 1) in list order, every step one rounded fp64 operation in the kernel's
+    order: the differences double(p) - double(c) and their sequential sums; mu = s / m, C = S / m - mu mu^T; jacobi3; the
+    select chain for the smallest eigenvalue (strict <: the first of equals keeps its column); hi = max; the eigenvector
+    divided by sqrt((e0^2 + e1^2) + e2^2); cv = |lo / ((l0 + l1) + l2)|; the flip when ((e0 wx + e1 wy) + e2 wz) < 0 with
+    w = double(viewpoint) - double(c); valid iff m >= 3, hi > 0 and hi, lo, e, cv finite; the quiet NaN 0x7FC00000 in
+    normal and curvature where not. Returns a dict: normal (n, 3) and curvature (n,) float32, flags uint32 — the bits of
+    the table — and diag (n, 3: the eigenvalues as jacobi3 left them), dot (the flip's sum), w."""
+    xyz = np.ascontiguousarray(xyz, F32)
+    n = len(xyz)
+    kk = idx.shape[1]
+    m = kk + 1
+    normal = np.full((n, 3), QNAN, np.uint32).view(F32)
+    curv = np.full(n, QNAN, np.uint32).view(F32)
+    flags = np.zeros(n, np.uint32)
+    out = dict(normal=normal, curvature=curv, flags=flags, diag=np.zeros((n, 3)), dot=np.zeros(n), w=np.zeros((n, 3)))
+    if m < 3 or n == 0:
+        return out
+    p = xyz.astype(np.float64)
+    with np.errstate(all="ignore"):
+        s = np.zeros((n, 3))
+        S = {ab: np.zeros(n) for ab in ((0, 0), (1, 0), (2, 0), (1, 1), (2, 1), (2, 2))}
+        for q in range(kk):
+            e = p[idx[:, q]] - p
+            s = s + e
+            for (a, b) in S:
+                S[(a, b)] = S[(a, b)] + e[:, a] * e[:, b]
+        dm = float(m)
+        mu = s / dm
+        Cm = np.empty((n, 3, 3))
+        for (a, b), v in S.items():
+            Cm[:, a, b] = v / dm - mu[:, a] * mu[:, b]
+            Cm[:, b, a] = Cm[:, a, b]
+        A, V = jacobi_ref.jacobi3(Cm)
+        l0, l1, l2 = A[:, 0, 0], A[:, 1, 1], A[:, 2, 2]
+        z1 = l1 < l0
+        lo = np.where(z1, l1, l0)
+        ev = np.where(z1[:, None], V[:, :, 1], V[:, :, 0])
+        z2 = l2 < lo
+        lo = np.where(z2, l2, lo)
+        ev = np.where(z2[:, None], V[:, :, 2], ev)
+        hi = np.fmax(np.fmax(l0, l1), l2)
+        ln = np.sqrt((ev[:, 0] * ev[:, 0] + ev[:, 1] * ev[:, 1]) + ev[:, 2] * ev[:, 2])
+        ev = ev / ln[:, None]
+        cv = np.abs(lo / ((l0 + l1) + l2))
+        w = np.asarray(viewpoint, F32).astype(np.float64) - p
+        dot = (ev[:, 0] * w[:, 0] + ev[:, 1] * w[:, 1]) + ev[:, 2] * w[:, 2]
+        ev = np.where((dot < 0.0)[:, None], -ev, ev)
+        ok = (hi > 0.0) & np.isfinite(hi) & np.isfinite(lo) & np.isfinite(ev).all(axis=1) & np.isfinite(cv)
+        normal[ok] = ev[ok].astype(F32)
+        curv[ok] = cv[ok].astype(F32)
+    flags[ok] = VALID
+    out.update(diag=np.stack([l0, l1, l2], axis=1), dot=dot, w=w, column=np.where(z2, 2, np.where(z1, 1, 0)))
+    return out
+
+
+def table(xyz, k, viewpoint=(0.0, 0.0, 0.0), tree=True, stats=None, exact=True):
     """(entries, planes): the table as cm_result_normals defines it — normal and curvature from eigh, rounded to fp32, so
-    only n_neighbors, r2_k, last and flags are meant for bit comparison — and the fp64 figures behind it."""
+    only n_neighbors, r2_k, last and flags are meant for bit comparison — and the fp64 figures behind it; with exact, also
+    planes["exact"]: planes_exact() of the same neighbourhoods, whose normal, curvature and flags are the table's bits."""
     xyz = np.ascontiguousarray(xyz, F32)
     n = len(xyz)
     out = np.zeros(n, VOXEL_NORMAL_DTYPE)
@@ -128,4 +192,6 @@ def table(xyz, k, viewpoint=(0.0, 0.0, 0.0), tree=True, stats=None):
     out["normal"] = np.where(ok[:, None], pl["normal"], np.nan).astype(F32)
     out["curvature"] = np.where(ok, pl["curvature"], np.nan).astype(F32)
     pl["idx"], pl["d2"] = idx, d2
+    if exact:
+        pl["exact"] = planes_exact(xyz, idx, viewpoint)
     return out, pl

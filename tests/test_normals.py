@@ -6,7 +6,9 @@ result — they pin the neighbourhood, ties included, and need no tolerance. Nor
 the restated covariance: every component within 1e-6, |curv - ref| <= 1e-6 ref + 1e-9, for the valid entries whose reference
 gap (l1 - l0) >= 1e-3 l2 (fp64 Jacobi moves the eigenvector by about 2^-52 l2 / gap <= 3e-13; rounding a unit vector to fp32
 moves a component by 6e-8), which must be all but 1 % of the valid ones; for every valid entry whatever its gap the residual
-|C n - l0 n| <= 1e-5 l2, and the normal must not point away from the viewpoint."""
+|C n - l0 n| <= 1e-5 l2, and the normal must not point away from the viewpoint. That is the independent cross-check (eigh
+is another algorithm). Beside it normal, curvature and flags of EVERY entry — the ones the gap rule leaves out and the invalid
+ones included — equal the kernel-order restatement normals_ref.planes_exact bit for bit (all tests but the full-size frame)."""
 import ctypes as C
 import os
 import re
@@ -112,6 +114,80 @@ def test_known_planes_in_the_restatement():
     assert t["last"].tolist() == [1, 0] and t["r2_k"].tolist() == [1.0, 1.0]
     t, _ = nr.table(xyz[:1], 9, tree=False)
     assert t["last"].tolist() == [0] and t["r2_k"].tolist() == [0] and t["n_neighbors"].tolist() == [1]
+
+
+# ---- CPU: designed neighbourhoods -----------------------------------------------------------------------------------------
+DESIGNED_VIEW_IN_PLANE = (42.0, 41.0, 3.0)               # a centroid of plane_z: in the fitted plane of all of them
+
+
+def designed_cloud():
+    """A few hundred centroids in groups 20 m apart, so that with k <= 8 a neighbourhood stays inside its group: exactly
+    collinear along each axis and along a diagonal, exactly coplanar normal to each axis, and a generic blob. Returns
+    (xyz, group name per point)."""
+    rng = np.random.default_rng(31)
+    g = np.arange(9, dtype=F32)
+    z9 = np.zeros(9, F32)
+    q = np.stack(np.meshgrid(np.arange(5, dtype=F32), np.arange(5, dtype=F32), indexing="ij"), axis=-1).reshape(-1, 2)
+    c25 = np.zeros((25, 1), F32)
+    parts = {"blob": own_voxels(rng.uniform(-3, 3, (150, 3)).astype(F32), 0.25),
+             "line_x": np.stack([g, z9, z9], axis=1) + F32([20, 0, 0]),
+             "line_y": np.stack([z9, g, z9], axis=1) + F32([0, 20, 0]),
+             "line_z": np.stack([z9, z9, g], axis=1) + F32([0, 0, 20]),
+             "line_d": np.stack([g, g, g], axis=1) * F32(0.5) - F32([30, 30, 30]),
+             "plane_z": np.concatenate([q, c25], axis=1) + F32([40, 40, 3]),
+             "plane_x": np.concatenate([c25, q], axis=1) + F32([-40, 40, 10]),
+             "plane_y": np.concatenate([q[:, :1], c25, q[:, 1:]], axis=1) + F32([40, -40, 10])}
+    xyz = np.concatenate(list(parts.values())).astype(F32)
+    group = np.concatenate([np.full(len(v), k) for k, v in parts.items()])
+    perm = rng.permutation(len(xyz))
+    return xyz[perm], group[perm]
+
+
+def group_of(xyz):
+    """the group of every centroid of a result made from designed_cloud(), whatever its order"""
+    src, group = designed_cloud()
+    lut = {p.tobytes(): g for p, g in zip(src, group)}
+    return np.array([lut[p.tobytes()] for p in np.ascontiguousarray(xyz, F32)])
+
+
+def designed_neighbourhoods(xyz, k, viewpoint, pl):
+    """What the designed cloud is for, asserted on the neighbourhoods the restatement found (pl: nr.table's planes)."""
+    ex, group = pl["exact"], group_of(xyz)
+    zeros = (ex["diag"] == 0).sum(axis=1)
+    assert (pl["idx"].shape[1] + 1) == k                                    # m == k: m == 3 at k = 3
+    for name, column in (("line_x", 1), ("line_y", 0), ("line_z", 0)):       # l = (a, 0, 0): the first of the equal zeros
+        sel = group == name
+        assert sel.sum() == 9 and (zeros[sel] == 2).all() and (ex["column"][sel] == column).all() and (ex["flags"][sel] == 1).all()
+    assert (ex["flags"][group == "line_d"] == 1).all() and (ex["curvature"][group == "line_d"] < 1e-12).all()
+    for name, axis in (("plane_x", 0), ("plane_y", 1), ("plane_z", 2)):
+        sel = group == name
+        assert sel.sum() == 25 and (ex["diag"][sel, axis] == 0).all() and (ex["flags"][sel] == 1).all()
+        if k == 8:
+            assert (zeros[sel] == 1).all() and (ex["column"][sel] == axis).all()
+    at_view = (ex["w"] == 0).all(axis=1)
+    assert at_view.sum() == 1 and ex["dot"][at_view] == 0                   # the viewpoint is a centroid
+    if tuple(viewpoint) == DESIGNED_VIEW_IN_PLANE and k == 8:               # (three grid points are collinear as well)
+        sel = group == "plane_z"
+        assert (ex["dot"][sel] == 0).all() and at_view[sel].sum() == 1      # the viewpoint lies in the fitted plane: no flip
+        assert ex["normal"][sel].tobytes() == np.tile(F32([0, 0, 1]), (25, 1)).tobytes()
+    return int((zeros == 2).sum()), int((ex["dot"] == 0).sum())
+
+
+def test_designed_neighbourhoods_are_in_the_restatement():
+    xyz, group = designed_cloud()
+    assert 200 <= len(xyz) <= 400 and len(own_voxels(xyz, 0.25)) == len(xyz)
+    blob_point = tuple(float(v) for v in xyz[group == "blob"][0])
+    for k in (3, 8):
+        for vp in (DESIGNED_VIEW_IN_PLANE, blob_point):
+            t, pl = nr.table(xyz, k, vp, tree=False)
+            collinear, zero_dots = designed_neighbourhoods(xyz, k, vp, pl)
+            print(f"k {k} viewpoint {vp}: two zero eigenvalues {collinear}, flip sum exactly zero {zero_dots}")
+            ex = pl["exact"]
+            assert t["flags"].tobytes() == ex["flags"].tobytes()
+    t, pl = nr.table(xyz[:2], 8, tree=False)                                 # m == 2: not valid, the quiet NaN
+    ex = pl["exact"]
+    assert (ex["flags"] == 0).all() and (ex["normal"].view(np.uint32) == 0x7FC00000).all()
+    assert (ex["curvature"].view(np.uint32) == 0x7FC00000).all()
 
 
 # ---- CPU: the search grid (normals_grid, cm_route.cpp) --------------------------------------------------------------------
@@ -238,6 +314,17 @@ def result_xyz(cm, res):
     return np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(F32)
 
 
+def compare_exact(got, ex, label=""):
+    """normal, curvature and flags of every entry against planes_exact, bit for bit"""
+    for f in ("flags", "normal", "curvature"):
+        g, w = got[f].view(np.uint32), ex[f].view(np.uint32)
+        if g.tobytes() != w.tobytes():
+            bad = np.nonzero((g != w).reshape(len(g), -1).any(axis=1))[0]
+            k = bad[0]
+            raise AssertionError(f"{label}{f} differs from the kernel-order restatement in {len(bad)} of {len(g)} entries, first "
+                                 f"at {k}: got {got[f][k]!r} want {ex[f][k]!r} (eigenvalues {ex['diag'][k]}, flip sum {ex['dot'][k]})")
+
+
 def compare(got, want, pl, viewpoint, normals=True, label=""):
     """The bar of the module's docstring. Returns the number of valid entries."""
     n = len(want)
@@ -247,6 +334,8 @@ def compare(got, want, pl, viewpoint, normals=True, label=""):
             bad = np.nonzero(got[f].view(np.uint32) != want[f].view(np.uint32))[0]
             raise AssertionError(f"{label}{f}: {len(bad)} of {n} entries differ, first at {bad[:5]}: got {got[f][bad[:5]]} "
                                  f"want {want[f][bad[:5]]}")
+    if "exact" in pl:                                     # (the neighbourhoods are the same: the bits above)
+        compare_exact(got, pl["exact"], label)
     ok = want["flags"] == nr.VALID
     assert np.isnan(got["normal"][~ok]).all() and np.isnan(got["curvature"][~ok]).all()
     if not ok.any():
@@ -432,6 +521,26 @@ def test_fewer_voxels_than_k():
                 assert np.abs(got["normal"].astype(np.float64) @ line.astype(np.float64)).max() < 1e-6
             if n == 5:
                 assert (got["flags"] == 1).all()
+
+
+@pytest.mark.gpu
+def test_designed_neighbourhoods():
+    """m == 3, exactly collinear and exactly coplanar centroids (equal smallest eigenvalues: the select chain's column), a
+    viewpoint in the fitted plane (the flip's sum is exactly zero) and at a centroid: every entry bit for bit. k = 2 is
+    refused by the call, so m == 2 comes from a result of two centroids."""
+    xyz, group = designed_cloud()
+    blob_point = tuple(float(v) for v in xyz[group == "blob"][0])
+    with capi.CloudMerger(max_points_total=len(xyz), max_sensors=1) as cm:
+        res = submit_as_voxels(cm, xyz, 0.25, 0)
+        for k in (3, 8):
+            for vp in (DESIGNED_VIEW_IN_PLANE, blob_point):
+                got, want, pl = check(cm, res, k, vp, tree=False, normals=False)
+                designed_neighbourhoods(result_xyz(cm, res), k, vp, pl)
+    with capi.CloudMerger(max_points_total=2, max_sensors=1) as cm:
+        res = submit_as_voxels(cm, xyz[:2], 0.25, 0)
+        got, want, pl = check(cm, res, 8, DESIGNED_VIEW_IN_PLANE, tree=False, normals=False)
+        assert (got["n_neighbors"] == 2).all() and (got["flags"] == 0).all()
+        assert (got["normal"].view(np.uint32) == 0x7FC00000).all() and (got["curvature"].view(np.uint32) == 0x7FC00000).all()
 
 
 @pytest.mark.gpu
@@ -673,8 +782,8 @@ def test_full_size_frame():
         assert res.n_out > 1_000_000
         xyz = result_xyz(cm, res)
         t0 = time.perf_counter()
-        want, pl = nr.table(xyz, 10)
-        host_s = time.perf_counter() - t0
+        want, pl = nr.table(xyz, 10, exact=False)        # (the exact restatement is left out here: jacobi3 in numpy over a
+        host_s = time.perf_counter() - t0                #  million matrices would double this test; every other test has it)
         t0 = time.perf_counter()
         got = cm.normals(10)
         print(f"n_out {res.n_out}: host restatement {host_s:.1f} s, cm_result_normals with its copy {time.perf_counter() - t0:.3f} s")

@@ -4,7 +4,9 @@
 The bar: count and mean bit for bit against the numpy restatement (tests/voxel_cov_ref.py) fed with the frame's own merged
 cloud and cells, and so is the covariance of every voxel that was not inflated; what goes through an eigen-decomposition
 (inflated covariance, eigenvalues, inverse) within tolerances. On every route, with the pre-stages, and without any effect
-on later frames."""
+on later frames. eigh is another algorithm than the kernel's Jacobi, which makes this the independent cross-check and
+makes it look away at the zero-eigenvalue boundary; tests/test_voxel_cov_edges.py compares whole entries byte for byte
+with the kernel-order restatement (tests/voxel_cov_exact.py) on frames designed to live at that boundary."""
 import ctypes as C
 import os
 import re

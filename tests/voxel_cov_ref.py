@@ -10,10 +10,10 @@ from cloud_merger_amd.capi import COV_INFLATED, COV_VALID, VOXEL_COV_DTYPE
 TRI = ((0, 0), (1, 0), (2, 0), (1, 1), (2, 1), (2, 2))      # cm_voxel_cov's order of the lower triangle
 
 
-def voxel_stats(xyz, vox, n_vox, min_points=6, eig_mult=0.01):
+def moments(xyz, vox, n_vox):
     """xyz: (n, 3) float32 points in their order; vox: (n,) voxel number of every point (-1: in no voxel).
-    Returns (table, lam): the VOXEL_COV_DTYPE table of the n_vox voxels and the eigenvalues eigh found before inflation
-    ((n_vox, 3) float64, zero below min_points) — what tolerances near zero are judged by."""
+    Returns (cnt, s, S): points per voxel (int64), the fp64 sums of the coordinates (n_vox, 3) and of their products
+    (n_vox, 6, in TRI's order), each taken one point after the other from 0 in the points' order."""
     xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
     vox = np.asarray(vox, dtype=np.int64)
     keep = vox >= 0
@@ -35,7 +35,14 @@ def voxel_stats(xyz, vox, n_vox, min_points=6, eig_mult=0.01):
         s[vv] = s[vv] + pp
         for q, (i, j) in enumerate(TRI):
             S[vv, q] = S[vv, q] + pp[:, i] * pp[:, j]
+    return cnt, s, S
 
+
+def voxel_stats(xyz, vox, n_vox, min_points=6, eig_mult=0.01):
+    """xyz: (n, 3) float32 points in their order; vox: (n,) voxel number of every point (-1: in no voxel).
+    Returns (table, lam): the VOXEL_COV_DTYPE table of the n_vox voxels and the eigenvalues eigh found before inflation
+    ((n_vox, 3) float64, zero below min_points) — what tolerances near zero are judged by."""
+    cnt, s, S = moments(xyz, vox, n_vox)
     out = np.zeros(n_vox, dtype=VOXEL_COV_DTYPE)
     lam_out = np.zeros((n_vox, 3))
     out["count"] = cnt
@@ -90,9 +97,9 @@ def cell_keys(ijk):
     return ijk[:, 0] + (ijk[:, 1] << 21) + (ijk[:, 2] << 42)
 
 
-def voxel_cov(merged, cells, counts, leaf, min_points=6, eig_mult=0.01):
-    """The table for a frame: merged — cm_merged_copy's records (XYZI structured array, (sensor, point) order); cells /
-    counts — cm_result_copy_cells of the same frame; leaf — the voxel size (x, y, z). Returns (table, lam)."""
+def voxel_of(merged, cells, leaf):
+    """(xyz, vox): the merged records' coordinates (n, 3) float32 and, for each, the number of the result voxel (row of
+    cells) that holds it, -1 for a point whose cell is not in the result."""
     xyz = np.stack([merged["x"], merged["y"], merged["z"]], axis=1).astype(np.float32)
     inv = np.float32(1.0) / np.asarray(leaf, dtype=np.float32)
     pc = np.floor(xyz * inv[None, :]).astype(np.int64)      # PCL's cell: floor(p * (1 / leaf)) in fp32
@@ -103,6 +110,13 @@ def voxel_cov(merged, cells, counts, leaf, min_points=6, eig_mult=0.01):
         pk = cell_keys(pc)
         pos = np.minimum(np.searchsorted(ck[order], pk), len(ck) - 1)
         vox = np.where(ck[order][pos] == pk, order[pos], -1)
+    return xyz, vox
+
+
+def voxel_cov(merged, cells, counts, leaf, min_points=6, eig_mult=0.01):
+    """The table for a frame: merged — cm_merged_copy's records (XYZI structured array, (sensor, point) order); cells /
+    counts — cm_result_copy_cells of the same frame; leaf — the voxel size (x, y, z). Returns (table, lam)."""
+    xyz, vox = voxel_of(merged, cells, leaf)
     table, lam = voxel_stats(xyz, vox, len(cells), min_points, eig_mult)
     assert np.array_equal(table["count"], np.asarray(counts, dtype=np.uint32)), "points per voxel differ from the result's counts"
     return table, lam
