@@ -53,6 +53,7 @@ SYMBOLS = [
     "cm_map_traj_configure", "cm_map_traj_evaluate", "cm_map_traj_copy", "cm_map_traj_device", "cm_traj_directions",
     "cm_map_frontier_configure", "cm_map_frontier_update", "cm_map_frontier_copy", "cm_map_frontier_labels_copy", "cm_map_frontier_device",
     "cm_map_match_configure", "cm_map_match_evaluate", "cm_map_match_copy", "cm_map_match_device", "cm_map_match_table_copy", "cm_match_table",
+    "cm_map_match_search_configure", "cm_map_match_search", "cm_map_match_search_result", "cm_map_match_search_level_copy",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -399,6 +400,30 @@ class MatchResult(C.Structure):
 
 assert C.sizeof(MatchParams) == 28 and C.sizeof(MatchResult) == 96 and MatchResult.sub.offset == 32 and MatchResult.pose.offset == 48
 
+# branch-and-bound scan matching over wide windows, the search layer behind the cost layer (cm_map_match_search_configure, cm_map_match_search)
+MATCH_SEARCH_MAX_SHIFT = 1024
+MATCH_SEARCH_MAX_DEPTH = 7
+MATCH_SEARCH_MAX_NODES = 1 << 22
+MATCH_SEARCH_OVERFLOW_CELLS = -2
+
+
+class MatchSearchParams(C.Structure):
+    """cm_match_search_params (40 bytes): MatchParams' sigma, max_dist, n_a, a_stride, shifts -wx..wx and -wy..wy cells of up to
+    MATCH_SEARCH_MAX_SHIFT, the roots' level, the room of a level's node list and of a candidate's cell list, MATCH_SUBCELL or 0."""
+    _fields_ = [("sigma", C.c_float), ("max_dist", C.c_float), ("n_a", C.c_uint32), ("a_stride", C.c_uint32), ("wx", C.c_uint32),
+                ("wy", C.c_uint32), ("depth", C.c_uint32), ("max_nodes", C.c_uint32), ("max_cells", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class MatchSearchInfo(C.Structure):
+    """cm_match_search_info (84 bytes): depth, the number of roots, the bound B, per level the nodes scored in the level loop and
+    those kept, the nodes scored for B beyond the roots, and the level whose node list overflowed (-1: none,
+    MATCH_SEARCH_OVERFLOW_CELLS: a candidate's cell list)."""
+    _fields_ = [("depth", C.c_uint32), ("n_roots", C.c_uint32), ("bound", C.c_uint32), ("scored", C.c_uint32 * 8), ("live", C.c_uint32 * 8),
+                ("n_probe", C.c_uint32), ("overflow_level", C.c_int32)]
+
+
+assert C.sizeof(MatchSearchParams) == 40 and C.sizeof(MatchSearchInfo) == 84
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -614,6 +639,10 @@ def load():
     L.cm_map_match_device.argtypes = [vp, C.POINTER(vp), C.POINTER(MatchResult)]
     L.cm_map_match_table_copy.argtypes = [vp, vp, u64, C.POINTER(u64)]
     L.cm_match_table.argtypes = [C.c_float, C.c_float, C.c_float, vp, u64, C.POINTER(u64)]
+    L.cm_map_match_search_configure.argtypes = [vp, C.POINTER(MatchSearchParams)]
+    L.cm_map_match_search.argtypes = [vp, vp, C.POINTER(MatchResult), C.POINTER(MatchSearchInfo)]
+    L.cm_map_match_search_result.argtypes = [vp, C.POINTER(MatchResult), C.POINTER(MatchSearchInfo)]
+    L.cm_map_match_search_level_copy.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(C.c_uint32 * 2)]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -1346,6 +1375,49 @@ class CloudMerger:
             self._check(st, "cm_map_match_table_copy")
         out = np.empty(n.value, dtype=np.uint8)
         self._check(self._lib.cm_map_match_table_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_map_match_table_copy")
+        return out
+
+    # ---- branch-and-bound scan matching over wide windows, behind the cost layer (cm_map_match_search_configure / cm_map_match_search) ----
+    def map_match_search_configure(self, sigma=None, max_dist=0.5, n_a=0, a_stride=1, wx=0, wy=0, depth=0, max_nodes=1 << 16, max_cells=1 << 16,
+                                   subcell=False):
+        """Allocates the search layer behind the configured cost layer: map_match_configure's field and angle candidates, shifts
+        -wx..wx and -wy..wy cells of up to MATCH_SEARCH_MAX_SHIFT, roots at level depth, room for max_nodes nodes per level and
+        max_cells cells per candidate. sigma None frees the layer."""
+        if sigma is None:
+            self._check(self._lib.cm_map_match_search_configure(self._ctx, None), "cm_map_match_search_configure")
+            return
+        p = MatchSearchParams(float(sigma), float(max_dist), int(n_a), int(a_stride), int(wx), int(wy), int(depth), int(max_nodes), int(max_cells),
+                              MATCH_SUBCELL if subcell else 0)
+        self._check(self._lib.cm_map_match_search_configure(self._ctx, C.byref(p)), "cm_map_match_search_configure")
+
+    def map_match_search(self, pose):
+        """Matches the last frame against the map around the prior pose (3 x 4, row-major) by branch and bound. Returns
+        (MatchResult, MatchSearchInfo). A capacity overflow raises CloudMergeError with status CAPACITY and the info as its
+        `info` attribute."""
+        p = np.ascontiguousarray(pose, dtype=np.float32).reshape(12)
+        out, info = MatchResult(), MatchSearchInfo()
+        try:
+            self._check(self._lib.cm_map_match_search(self._ctx, p.ctypes.data, C.byref(out), C.byref(info)), "cm_map_match_search")
+        except CloudMergeError as e:
+            e.info = info if e.status == CAPACITY else None
+            raise
+        return out, info
+
+    def map_match_search_result(self):
+        """(MatchResult, MatchSearchInfo) of the last search again."""
+        out, info = MatchResult(), MatchSearchInfo()
+        self._check(self._lib.cm_map_match_search_result(self._ctx, C.byref(out), C.byref(info)), "cm_map_match_search_result")
+        return out, info
+
+    def map_match_search_level(self, h):
+        """(ny + 2^h - 1, nx + 2^h - 1) uint8: level h of the last search's pyramid; entry [y + 2^h - 1, x + 2^h - 1] is the
+        largest field byte of the 2^h x 2^h cells from (x, y) on."""
+        dims = (C.c_uint32 * 2)()
+        st = self._lib.cm_map_match_search_level_copy(self._ctx, int(h), None, 0, C.byref(dims))
+        if st != CAPACITY:
+            self._check(st, "cm_map_match_search_level_copy")
+        out = np.empty((dims[1], dims[0]), dtype=np.uint8)
+        self._check(self._lib.cm_map_match_search_level_copy(self._ctx, int(h), out.ctypes.data, out.size, C.byref(dims)), "cm_map_match_search_level_copy")
         return out
 
     # ---- normals and curvature of the last result (cm_result_normals) ----

@@ -1445,6 +1445,96 @@ int cm_map_match_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uin
     return CM_OK;
 }
 
+static_assert(sizeof(cm_match_search_params) == 40 && sizeof(cm_match_search_info) == 84 && offsetof(cm_match_search_info, scored) == 12 &&
+                  offsetof(cm_match_search_info, live) == 44 && offsetof(cm_match_search_info, overflow_level) == 80, "the search layer's two structs");
+static_assert(CM_MATCH_SEARCH_MAX_SHIFT == CM_MSEARCH_MAX_SHIFT_DEV && CM_MATCH_SEARCH_MAX_DEPTH == CM_MSEARCH_MAX_DEPTH_DEV &&
+                  2 * CM_MATCH_SEARCH_MAX_SHIFT < 4096 && 2 * CM_MATCH_MAX_ANGLES + 1 < 256 && CM_MATCH_SEARCH_MAX_NODES == CM_GRID_MAX_CELLS,
+              "the kernels' constants; a node is 8 + 12 + 12 bits");
+
+int cm_map_match_search_configure(cm_ctx* c, const cm_match_search_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    uint32_t R = 0;
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
+        if (p->n_a > CM_MATCH_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_a exceeds CM_MATCH_MAX_ANGLES");
+        if (p->a_stride == 0u) return fail(c, CM_BAD_ARG, "a_stride must be at least 1");
+        if (static_cast<uint64_t>(p->n_a) * p->a_stride > 1024u) return fail(c, CM_BAD_ARG, "n_a * a_stride exceeds 1024 (a quarter turn)");
+        if (p->wx > CM_MATCH_SEARCH_MAX_SHIFT || p->wy > CM_MATCH_SEARCH_MAX_SHIFT) return fail(c, CM_BAD_ARG, "wx or wy exceeds CM_MATCH_SEARCH_MAX_SHIFT");
+        if (p->depth > CM_MATCH_SEARCH_MAX_DEPTH) return fail(c, CM_BAD_ARG, "depth exceeds CM_MATCH_SEARCH_MAX_DEPTH");
+        if (p->max_nodes == 0u || p->max_nodes > CM_MATCH_SEARCH_MAX_NODES) return fail(c, CM_BAD_ARG, "max_nodes must be 1 .. CM_MATCH_SEARCH_MAX_NODES");
+        if (p->max_cells == 0u || p->max_cells > CM_MATCH_SEARCH_MAX_NODES) return fail(c, CM_BAD_ARG, "max_cells must be 1 .. CM_MATCH_SEARCH_MAX_NODES");
+        const uint64_t rx = (2ull * p->wx + (1ull << p->depth)) >> p->depth, ry = (2ull * p->wy + (1ull << p->depth)) >> p->depth;
+        if ((2ull * p->n_a + 1u) * rx * ry > p->max_nodes) return fail(c, CM_BAD_ARG, "more roots than max_nodes");
+        if (c->map_info.nx > 65535u || c->map_info.ny > 65535u) return fail(c, CM_BAD_ARG, "the map's window has more than 65535 cells along an axis");
+        if (p->flags & ~CM_MATCH_SUBCELL) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    }
+    return map_msearch_configure(c, p, R);
+}
+
+// The refusals every call on a configured search layer shares; the reads also refuse a stale result.
+static int msearch_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->msearch_on) return fail(c, CM_BAD_ARG, "no search layer (cm_map_match_search_configure first)");
+    if (read && c->msearch_stale) return fail(c, CM_BAD_ARG, c->msearch_stale);
+    if (read && c->msearch_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the search is stale: no cm_map_match_search since the last merge");
+    return CM_OK;
+}
+
+int cm_map_match_search(cm_ctx* c, const float pose[12], cm_match_result* out, cm_match_search_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = msearch_check(c, false)) return e;
+    if (const int e = centroid_result_check(c)) return e;
+    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
+    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    int v[2];
+    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    const int e = map_msearch_evaluate(c, pose);
+    if (e == CM_CAPACITY && info) *info = c->msearch_info;
+    if (e) return e;
+    if (out) *out = c->msearch_result;
+    if (info) *info = c->msearch_info;
+    return CM_OK;
+}
+
+int cm_map_match_search_result(cm_ctx* c, cm_match_result* out, cm_match_search_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = msearch_check(c, true)) return e;
+    if (out) *out = c->msearch_result;
+    if (info) *info = c->msearch_info;
+    return CM_OK;
+}
+
+int cm_map_match_search_level_copy(cm_ctx* c, uint32_t h, uint8_t* host_dst, uint64_t capacity, uint32_t dims[2]) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = msearch_check(c, true)) return e;
+    if (h > c->msearch_params.depth) return fail(c, CM_BAD_ARG, "no such level (h exceeds depth)");
+    const uint32_t pw = c->map_info.nx + (1u << h) - 1u, ph = c->map_info.ny + (1u << h) - 1u;
+    if (dims) {
+        dims[0] = pw;
+        dims[1] = ph;
+    }
+    const uint64_t n = static_cast<uint64_t>(pw) * ph;
+    if (n > capacity) return fail(c, CM_CAPACITY, "level destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->msearch_pyr + msearch_level_offset(c->map_info.nx, c->map_info.ny, h), n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");
 static_assert(CM_NORMAL_VALID == CM_NORMAL_VALID_DEV && CM_NORMAL_MAX_K == 64, "the kernels' flag and largest list");
 

@@ -562,6 +562,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_integrate";
     c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_integrate";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
+    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -571,6 +572,7 @@ int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (const int e = map_plan_configure(c, nullptr)) return e;        // the plan layer goes with the cost layer it reads
     if (const int e = map_match_configure(c, nullptr, 0)) return e;    // and so does the matching layer
+    if (const int e = map_msearch_configure(c, nullptr, 0)) return e;  // and the search layer
     c->cost_on = false;
     c->cost_fresh = false;
     if (!q) {
@@ -625,6 +627,7 @@ int map_cost_update(cm_ctx* c) {
     c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_cost_update";
     c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_cost_update";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
+    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_cost_update";
     return CM_OK;
 }
 
@@ -1073,6 +1076,275 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
     c->match_serial = c->frame_serial;
     c->match_stale = nullptr;
+    return CM_OK;
+}
+
+size_t msearch_level_offset(uint32_t nx, uint32_t ny, uint32_t h) {
+    size_t off = 0;
+    for (uint32_t l = 0; l < h; ++l) off += static_cast<size_t>(nx + (1u << l) - 1u) * (ny + (1u << l) - 1u);
+    return off;
+}
+
+namespace {
+
+uint32_t msearch_roots_along(uint32_t w, uint32_t depth) { return (2u * w + (1u << depth)) >> depth; }     // ceil((2 w + 1) / 2^depth)
+
+// Where the parts of msearch_nodes and msearch_host start.
+struct MSearchLayout {
+    size_t roots, list[2], u, words;   // msearch_nodes
+    size_t h_counts, h_init, h_q;      // msearch_host (the words read back start at 0)
+};
+MSearchLayout msearch_layout(const cm_match_search_params& q, uint32_t n_roots) {
+    MSearchLayout l;
+    l.roots = 0;
+    l.list[0] = n_roots;
+    l.list[1] = l.list[0] + q.max_nodes;
+    l.u = l.list[1] + q.max_nodes;
+    l.words = l.u + q.max_nodes;
+    l.h_counts = CM_MSEARCH_WORDS;
+    l.h_init = l.h_counts + 256;
+    l.h_q = l.h_init + CM_MSEARCH_WORDS;
+    return l;
+}
+
+}  // namespace
+
+// The search layer's memory, all of it: the pyramid with the field table behind it, one bitmap and one cell list per angle
+// candidate with the counts behind them, the roots (built here and uploaded), two node lists, the scores and the info words,
+// the candidates' matrices and the page-locked words. nullptr gives it back. Everything is stale until the first evaluate.
+int map_msearch_configure(cm_ctx* c, const cm_match_search_params* q, uint32_t R) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->msearch_on = false;
+    c->msearch_stale = "the search is stale: no cm_map_match_search since cm_map_match_search_configure";
+    std::memset(&c->msearch_result, 0, sizeof c->msearch_result);
+    std::memset(&c->msearch_info, 0, sizeof c->msearch_info);
+    if (!q) {
+        c->msearch_pyr.release();
+        c->msearch_bits.release();
+        c->msearch_cells.release();
+        c->msearch_nodes.release();
+        c->msearch_q.release();
+        c->msearch_host.release();
+        return CM_OK;
+    }
+    const uint32_t nx = c->map_info.nx, ny = c->map_info.ny;
+    const size_t n_cells = static_cast<size_t>(nx) * ny, words = (n_cells + 31) / 32;
+    const size_t n_k = 2 * static_cast<size_t>(q->n_a) + 1, n_lut = static_cast<size_t>(R) * R + 1;
+    const uint32_t rx = msearch_roots_along(q->wx, q->depth), ry = msearch_roots_along(q->wy, q->depth);
+    const uint32_t n_roots = static_cast<uint32_t>(n_k) * rx * ry;
+    const MSearchLayout l = msearch_layout(*q, n_roots);
+    const size_t n_pyr = msearch_level_offset(nx, ny, q->depth + 1u);
+    if (!c->msearch_pyr.reserve(n_pyr + n_lut) || !c->msearch_bits.reserve(n_k * words) || !c->msearch_cells.reserve(n_k * q->max_cells + n_k) ||
+        !c->msearch_nodes.reserve(l.words + CM_MSEARCH_WORDS) || !c->msearch_q.reserve(6 * n_k) ||
+        !c->msearch_host.reserve(std::max(l.h_q + 6 * n_k, static_cast<size_t>(n_roots))))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the search layer");
+    std::vector<unsigned char> lut(n_lut, 0);
+    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, lut.data());
+    uint32_t* const roots = c->msearch_host;           // (the page-locked words are free until the first evaluate)
+    size_t r = 0;
+    for (uint32_t kk = 0; kk < n_k; ++kk)
+        for (uint32_t b = 0; b < ry; ++b)
+            for (uint32_t a = 0; a < rx; ++a) roots[r++] = (kk << 24) | ((b << q->depth) << 12) | (a << q->depth);
+    HIP_TRY(c, hipMemcpyAsync(c->msearch_pyr + n_pyr, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->msearch_nodes + l.roots, roots, static_cast<size_t>(n_roots) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->msearch_params = *q;
+    c->msearch_radius = R;
+    c->msearch_n_roots = n_roots;
+    c->msearch_on = true;
+    return CM_OK;
+}
+
+// The last frame against the map around a prior, by branch and bound (cm_kernels_msearch.hip; the semantics are in
+// include/cloudmerge.h). The candidates' matrices and the info words' initial values go up from the page-locked words; field,
+// pyramid, bitmaps and cell lists are made; the prior's leaf and the roots are scored and the descent for B runs on the
+// device, each score launch reading its list's length from the info words. Then one host round trip per level: the live nodes
+// and their children, which size the next launch and decide an overflow. The leaves' best entry, its four neighbours as leaves,
+// one last copy; steps 7 and 8 on the host. No allocation: cm_map_match_search_configure made them all.
+int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_match_search_params& q = c->msearch_params;
+    const uint32_t nx = c->map_info.nx, ny = c->map_info.ny, n_roots = c->msearch_n_roots;
+    const size_t n_cells = static_cast<size_t>(nx) * ny;
+    const MSearchLayout l = msearch_layout(q, n_roots);
+    CmMatchDev g{};                                    // (for the exhaustive layer's mark kernel: no shifts)
+    g.tx = pose[3];
+    g.ty = pose[7];
+    g.inv = 1.0f / c->map_params.cell;
+    g.ax = c->map_info.anchor[0];
+    g.ay = c->map_info.anchor[1];
+    g.nx = nx;
+    g.ny = ny;
+    g.z_min = c->map_params.z_min;
+    g.z_max = c->map_params.z_max;
+    g.n_a = q.n_a;
+    g.n_k = 2u * q.n_a + 1u;
+    g.wx = 0;
+    g.wy = 0;
+    g.words = static_cast<uint32_t>((n_cells + 31) / 32);
+    g.r2 = c->msearch_radius * c->msearch_radius;
+    const CmMSearchDev m{nx, ny, g.n_k, q.n_a, q.wx, q.wy, q.max_cells};
+    const float* const dirs = traj_direction_table();
+    uint32_t* const hw = c->msearch_host;              // the info words read back
+    uint32_t* const hcounts = c->msearch_host + l.h_counts;
+    uint32_t* const init = c->msearch_host + l.h_init;
+    float* const up = reinterpret_cast<float*>(c->msearch_host + l.h_q);
+    for (uint32_t kk = 0; kk < g.n_k; ++kk) {
+        const int k = static_cast<int>(kk) - static_cast<int>(q.n_a);
+        const uint32_t e = static_cast<uint32_t>(k * static_cast<int>(q.a_stride)) & (CM_TRAJ_HEADINGS - 1u);
+        const float cs = dirs[2 * e], sn = dirs[2 * e + 1];
+        for (int j = 0; j < 3; ++j) {
+            up[6 * kk + j] = static_cast<float>(static_cast<float>(cs * pose[j]) - static_cast<float>(sn * pose[4 + j]));
+            up[6 * kk + 3 + j] = static_cast<float>(static_cast<float>(sn * pose[j]) + static_cast<float>(cs * pose[4 + j]));
+        }
+    }
+    std::memset(init, 0, CM_MSEARCH_WORDS * sizeof(uint32_t));
+    init[CM_MSEARCH_W_PROBE] = 1u;                     // the prior's leaf
+    init[CM_MSEARCH_W_PRIOR] = (q.n_a << 24) | (q.wy << 12) | q.wx;
+    init[CM_MSEARCH_W_ONE] = 1u;
+    init[CM_MSEARCH_W_FOUR] = 4u;
+    init[CM_MSEARCH_W_NROOTS] = n_roots;
+    unsigned char* const pyr = c->msearch_pyr;
+    const unsigned char* const lut = pyr + msearch_level_offset(nx, ny, q.depth + 1u);
+    const auto level = [&](uint32_t h) { return pyr + msearch_level_offset(nx, ny, h); };
+    uint32_t* const cells = c->msearch_cells;
+    uint32_t* const counts = cells + static_cast<size_t>(g.n_k) * q.max_cells;
+    uint32_t* const nodes = c->msearch_nodes;
+    uint32_t* const words = nodes + l.words;
+    uint32_t* const U = nodes + l.u;
+    hipStream_t st = c->stream;
+    cm_match_search_info& info = c->msearch_info;
+    std::memset(&info, 0, sizeof info);
+    info.depth = q.depth;
+    info.n_roots = n_roots;
+    info.overflow_level = -1;
+    c->msearch_stale = "the search is stale: the last cm_map_match_search failed";
+    c->prof_used = 0;
+    HIP_TRY(c, hipMemcpyAsync(c->msearch_q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
+    prof_mark(c, "msearch_clear");
+    HIP_TRY(c, hipMemcpyAsync(words, init, CM_MSEARCH_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->msearch_bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(counts, 0, static_cast<size_t>(g.n_k) * 4, st));
+    prof_mark(c, "k_match_field");
+    cmk_match_field(st, c->cost_dist2, lut, g.r2, static_cast<uint32_t>(n_cells), pyr);
+    prof_mark(c, "k_msearch_pyramid");
+    for (uint32_t h = 1; h <= q.depth; ++h) cmk_msearch_pyramid(st, level(h - 1u), level(h), nx, ny, h);
+    prof_mark(c, "k_match_mark");
+    cmk_match_mark(st, c->d_frame, g, c->msearch_q, c->frame_mask, c->msearch_bits, c->frame.n_tiles);
+    prof_mark(c, "k_msearch_list");
+    cmk_msearch_list(st, c->msearch_bits, m, g.words, cells, counts);
+    // A list's nodes times `splits` stripes of cells are the workgroups of a score launch: about 4096, no stripe under 1024
+    // cells of room. More than one stripe adds into the scores, which are zero before: the info words' by their upload and by
+    // k_msearch_pick, U by a clear.
+    const auto splits_of = [&](uint32_t n) { return std::max(1u, std::min({4096u / n, (q.max_cells + 1023u) / 1024u, 64u})); };
+    const auto score = [&](const uint32_t* list, const uint32_t* n_ptr, uint32_t n, uint32_t h, uint32_t* out) -> int {
+        const uint32_t sp = splits_of(n);
+        if (sp > 1u && out == U) HIP_TRY(c, hipMemsetAsync(U, 0, static_cast<size_t>(n) * sizeof(uint32_t), st));
+        cmk_msearch_score(st, list, n_ptr, n, m, level(h), h, cells, counts, sp, out);
+        return CM_OK;
+    };
+    // the bound B: the prior's leaf, the roots, the descent
+    prof_mark(c, "k_msearch_score");
+    if (const int e = score(words + CM_MSEARCH_W_PRIOR, words + CM_MSEARCH_W_ONE, 1, 0, words + CM_MSEARCH_W_PRIOR_U)) return e;
+    if (const int e = score(nodes + l.roots, words + CM_MSEARCH_W_NROOTS, n_roots, q.depth, U)) return e;
+    prof_mark(c, "k_msearch_pick");
+    cmk_msearch_pick(st, nodes + l.roots, U, words + CM_MSEARCH_W_NROOTS, n_roots, m, q.depth, words);
+    for (uint32_t h = q.depth; h-- > 0u;) {
+        prof_mark(c, "k_msearch_score");
+        if (const int e = score(words + CM_MSEARCH_W_TINY, words + CM_MSEARCH_W_TN, 4, h, words + CM_MSEARCH_W_TINY_U)) return e;
+        prof_mark(c, "k_msearch_pick");
+        cmk_msearch_pick(st, words + CM_MSEARCH_W_TINY, words + CM_MSEARCH_W_TINY_U, words + CM_MSEARCH_W_TN, 4, m, h, words);
+    }
+    // the level loop
+    const uint32_t* cur = nodes + l.roots;
+    uint32_t n_cur = n_roots;
+    info.scored[q.depth] = n_roots;
+    bool first = true;
+    const auto fetch = [&]() -> int {                  // the info words (and once the counts) back, and a wait
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(hw, words, CM_MSEARCH_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (first) {
+            HIP_TRY(c, hipMemcpyAsync(hcounts, counts, static_cast<size_t>(g.n_k) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(c, hipStreamSynchronize(st));
+        if (first) {
+            first = false;
+            for (uint32_t kk = 0; kk < g.n_k; ++kk)
+                if (hcounts[kk] > q.max_cells) {
+                    info.overflow_level = CM_MATCH_SEARCH_OVERFLOW_CELLS;
+                    info.scored[q.depth] = 0u;
+                    return fail(c, CM_CAPACITY, "a candidate has more cells than max_cells");
+                }
+        }
+        return CM_OK;
+    };
+    for (uint32_t h = q.depth; h >= 1u; --h) {
+        uint32_t* const next = nodes + l.list[h & 1u];
+        prof_mark(c, "k_msearch_select");
+        cmk_msearch_select(st, cur, U, n_cur, m, h, words + CM_MSEARCH_W_B, next, q.max_nodes, words + CM_MSEARCH_W_LEVEL + 2u * h);
+        if (const int e = fetch()) { prof_mark(c, "end"); collect_stage_times_by_name(c); return e; }
+        info.bound = hw[CM_MSEARCH_W_B];
+        info.n_probe = hw[CM_MSEARCH_W_PROBE];
+        info.live[h] = hw[CM_MSEARCH_W_LEVEL + 2u * h];
+        info.scored[h - 1u] = hw[CM_MSEARCH_W_LEVEL + 2u * h + 1u];
+        if (info.scored[h - 1u] > q.max_nodes) {
+            info.overflow_level = static_cast<int32_t>(h - 1u);
+            prof_mark(c, "end");
+            collect_stage_times_by_name(c);
+            return fail(c, CM_CAPACITY, "a level has more nodes than max_nodes");
+        }
+        if (info.scored[h - 1u] == 0u) return fail(c, CM_INTERNAL, "no live node at a level");
+        cur = next;
+        n_cur = info.scored[h - 1u];
+        HIP_TRY(c, hipMemcpyAsync(words + CM_MSEARCH_W_TN, hw + CM_MSEARCH_W_LEVEL + 2u * h + 1u, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        prof_mark(c, "k_msearch_score");
+        if (const int e = score(cur, words + CM_MSEARCH_W_TN, n_cur, h - 1u, U)) return e;
+    }
+    prof_mark(c, "k_msearch_best");
+    cmk_msearch_best(st, cur, U, n_cur, m, counts, words);
+    prof_mark(c, "k_msearch_score");
+    if (const int e = score(words + CM_MSEARCH_W_NEIGH, words + CM_MSEARCH_W_FOUR, 4, 0, words + CM_MSEARCH_W_NEIGH_U)) return e;
+    prof_mark(c, "end");
+    const int fe = fetch();
+    collect_stage_times_by_name(c);
+    if (fe) return fe;
+    info.bound = hw[CM_MSEARCH_W_B];
+    info.n_probe = hw[CM_MSEARCH_W_PROBE];
+    info.live[0] = hw[CM_MSEARCH_W_LIVE0];
+    const uint32_t node = hw[CM_MSEARCH_W_BEST];
+    const uint32_t sx = 2u * q.wx + 1u, sy = 2u * q.wy + 1u;
+    const uint32_t bk = node >> 24, bj = (node >> 12) & 4095u, bi = node & 4095u;
+    if (bk >= g.n_k || bj >= sy || bi >= sx) return fail(c, CM_INTERNAL, "the best entry lies outside the range");
+    cm_match_result& r = c->msearch_result;
+    r.best = (bk * sy + bj) * sx + bi;
+    r.k = static_cast<int32_t>(bk) - static_cast<int32_t>(q.n_a);
+    r.j = static_cast<int32_t>(bj) - static_cast<int32_t>(q.wy);
+    r.i = static_cast<int32_t>(bi) - static_cast<int32_t>(q.wx);
+    r.n_cells = hw[CM_MSEARCH_W_NCELLS];
+    r.max_score = 255u * r.n_cells;
+    r.score = hw[CM_MSEARCH_W_SCORE];
+    r.yaw = static_cast<float>(static_cast<double>(r.k * static_cast<int32_t>(q.a_stride)) * (6.283185307179586 / 4096.0));
+    // step 7: the vertex of the parabola through the best entry and its two neighbours, per axis
+    const auto sub = [&](bool both, uint32_t lo, uint32_t hi) {
+        if (!(q.flags & CM_MATCH_SUBCELL) || !both) return 0.0;
+        const int64_t den = static_cast<int64_t>(lo) - 2 * static_cast<int64_t>(r.score) + static_cast<int64_t>(hi);
+        if (den >= 0) return 0.0;
+        const double v = 0.5 * static_cast<double>(static_cast<int64_t>(lo) - static_cast<int64_t>(hi)) / static_cast<double>(den);
+        return v < -0.5 ? -0.5 : v > 0.5 ? 0.5 : v;
+    };
+    const uint32_t* const nu = hw + CM_MSEARCH_W_NEIGH_U;
+    r.sub[0] = sub(bi > 0u && bi + 1u < sx, nu[0], nu[1]);
+    r.sub[1] = sub(bj > 0u && bj + 1u < sy, nu[2], nu[3]);
+    const double cell = static_cast<double>(c->map_params.cell);
+    for (int j = 0; j < 3; ++j) {
+        r.pose[j] = up[6 * bk + j];
+        r.pose[4 + j] = up[6 * bk + 3 + j];
+    }
+    r.pose[3] = static_cast<float>(pose[3] + static_cast<float>((static_cast<double>(r.i) + r.sub[0]) * cell));
+    r.pose[7] = static_cast<float>(pose[7] + static_cast<float>((static_cast<double>(r.j) + r.sub[1]) * cell));
+    for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
+    c->msearch_serial = c->frame_serial;
+    c->msearch_stale = nullptr;
     return CM_OK;
 }
 

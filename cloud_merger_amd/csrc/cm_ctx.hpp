@@ -348,6 +348,24 @@ struct cm_ctx {
     PinnedBuf<uint32_t> match_host;      // CM_MATCH_INFO_WORDS words read back, then the candidates' floats an evaluate uploads
     std::vector<unsigned char> match_lut_host;
 
+    // Search layer behind the cost layer (cm_kernels_msearch.hip): branch-and-bound scan matching over wide windows,
+    // configured by cm_map_match_search_configure and evaluated by cm_map_match_search from the same inputs as the layer
+    // above. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer too.
+    bool msearch_on = false;
+    const char* msearch_stale = nullptr; // why result, info and pyramid are not those of the current tables and a prior; nullptr: they are
+    uint64_t msearch_serial = 0;         // the frame matched last
+    cm_match_search_params msearch_params{};
+    uint32_t msearch_radius = 0;         // R: the field table has R * R + 1 entries
+    uint32_t msearch_n_roots = 0;
+    cm_match_result msearch_result{};
+    cm_match_search_info msearch_info{};
+    DevBuf<unsigned char> msearch_pyr;   // levels 0 .. depth (msearch_level_offset), then the field table
+    DevBuf<uint32_t> msearch_bits;       // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
+    DevBuf<uint32_t> msearch_cells;      // 2 * n_a + 1 cell lists of max_cells words, then as many counts
+    DevBuf<uint32_t> msearch_nodes;      // the roots, two node lists of max_nodes words, the scores of max_nodes words, CM_MSEARCH_WORDS info words
+    DevBuf<float> msearch_q;             // six floats per candidate
+    PinnedBuf<uint32_t> msearch_host;    // CM_MSEARCH_WORDS words read back, 256 counts, CM_MSEARCH_WORDS words an evaluate uploads, then the candidates' floats
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -488,6 +506,13 @@ int map_frontier_update(cm_ctx* c);
 // match_result for a prior that cm_map_match_evaluate has checked.
 int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R);
 int map_match_evaluate(cm_ctx* c, const float pose[12]);
+// The search layer behind the cost layer. map_msearch_configure: room for q over the map's window, the field table at radius
+// R cells built and uploaded, the roots built and uploaded (nullptr: the buffers go). map_msearch_evaluate: msearch_result and
+// msearch_info for a prior that cm_map_match_search has checked; CM_CAPACITY leaves the result stale and the info written.
+// msearch_level_offset: where level h starts in msearch_pyr.
+int map_msearch_configure(cm_ctx* c, const cm_match_search_params* q, uint32_t R);
+int map_msearch_evaluate(cm_ctx* c, const float pose[12]);
+size_t msearch_level_offset(uint32_t nx, uint32_t ny, uint32_t h);
 // The normal table of the last result (nrm_entries, n_out entries).
 int normals(cm_ctx* c, const cm_normal_params& q);
 // Registration of the n_src source records at src_dev against the last result: *out, and the correspondences in aln_fit.corr.

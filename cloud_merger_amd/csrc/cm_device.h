@@ -455,3 +455,40 @@ struct CmFrontEntryDev {               // cm_frontier
     unsigned long long key;            // until k_front_best: pot << 32 | cell; then min_pot (low word) and min_pot_cell
     uint32_t box01, box23;             // x0 | y0 << 16, x1 | y1 << 16 (written by k_front_best)
 };
+
+// Search layer behind the cost layer (cm_kernels_msearch.hip): branch-and-bound scan matching over wide windows. A node is one
+// word, (k + n_a) << 24 | (j0 + wy) << 12 | (i0 + wx); a cell of a candidate's list is x | y << 16. k_msearch_score gives a
+// workgroup of CM_MSEARCH_BLOCK threads one node; k_msearch_pick and k_msearch_best are one workgroup of CM_MSEARCH_ONE_BLOCK
+// threads. The layer's CM_MSEARCH_WORDS info words on the device: the bound B, the nodes scored for it, the best leaf with
+// its score and cell count, the live leaves, the length of the tiny list of the descent, the score of the prior's leaf, the
+// four neighbours of step 7 and their scores, per level h the live nodes and their children at CM_MSEARCH_W_LEVEL + 2 h, the
+// tiny list and its scores, the prior's leaf, and three list lengths the host writes (1, 4, the number of roots).
+#define CM_MSEARCH_BLOCK 256
+#define CM_MSEARCH_ONE_BLOCK 1024
+#define CM_MSEARCH_MAX_SHIFT_DEV 1024
+#define CM_MSEARCH_MAX_DEPTH_DEV 7
+#define CM_MSEARCH_W_B 0
+#define CM_MSEARCH_W_PROBE 1
+#define CM_MSEARCH_W_BEST 2
+#define CM_MSEARCH_W_SCORE 3
+#define CM_MSEARCH_W_NCELLS 4
+#define CM_MSEARCH_W_LIVE0 5
+#define CM_MSEARCH_W_TN 6
+#define CM_MSEARCH_W_PRIOR_U 7
+#define CM_MSEARCH_W_NEIGH 8
+#define CM_MSEARCH_W_NEIGH_U 12
+#define CM_MSEARCH_W_LEVEL 16
+#define CM_MSEARCH_W_TINY 32
+#define CM_MSEARCH_W_TINY_U 36
+#define CM_MSEARCH_W_PRIOR 40
+#define CM_MSEARCH_W_ONE 41
+#define CM_MSEARCH_W_FOUR 42
+#define CM_MSEARCH_W_NROOTS 43
+#define CM_MSEARCH_WORDS 48
+struct CmMSearchDev {
+    uint32_t nx, ny;
+    uint32_t n_k;                      // 2 * n_a + 1 candidates
+    uint32_t n_a;
+    uint32_t wx, wy;
+    uint32_t max_cells;                // room of one candidate's cell list
+};

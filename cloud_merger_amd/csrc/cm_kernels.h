@@ -310,3 +310,20 @@ void cmk_front_number(hipStream_t s, const CmFrontDev& g, const uint32_t* labels
 void cmk_front_table(hipStream_t s, const CmFrontDev& g, const uint32_t* pot, uint32_t* labels, const uint32_t* size,
                      CmFrontEntryDev* table, uint32_t* box);
 void cmk_front_best(hipStream_t s, const CmFrontDev& g, CmFrontEntryDev* table, const uint32_t* box, uint32_t* info);
+
+// ---- search layer behind the cost layer (cm_kernels_msearch.hip) ---------------------------------------------------------------------
+// Level h of the pyramid is (ny + 2^h - 1) rows of (nx + 2^h - 1) bytes; cmk_msearch_pyramid makes level h >= 1 (dst) from
+// level h - 1 (src). bits: the g.n_k bitmaps cmk_match_mark filled; cells: g.n_k lists of g.max_cells words; counts: g.n_k
+// words, zero before cmk_msearch_list. list / n_ptr / n_max: nodes, their number in device memory, and the host's bound on
+// it (the grid). U: one score per node of the list; with splits > 1 a node's cells are spread over that many workgroups, which
+// add into U, zero before the launch. words: the CM_MSEARCH_WORDS info words. cmk_msearch_select adds the live
+// nodes of the n-node list at level h >= 1 to counters[0] and their children to counters[1] and writes at most cap of them.
+void cmk_msearch_pyramid(hipStream_t s, const unsigned char* src, unsigned char* dst, uint32_t nx, uint32_t ny, uint32_t h);
+void cmk_msearch_list(hipStream_t s, const uint32_t* bits, const CmMSearchDev& g, uint32_t words, uint32_t* cells, uint32_t* counts);
+void cmk_msearch_score(hipStream_t s, const uint32_t* list, const uint32_t* n_ptr, uint32_t n_max, const CmMSearchDev& g, const unsigned char* tab,
+                       uint32_t h, const uint32_t* cells, const uint32_t* counts, uint32_t splits, uint32_t* U);
+void cmk_msearch_pick(hipStream_t s, const uint32_t* list, const uint32_t* U, const uint32_t* n_ptr, uint32_t n_max, const CmMSearchDev& g, uint32_t h,
+                      uint32_t* words);
+void cmk_msearch_select(hipStream_t s, const uint32_t* list, const uint32_t* U, uint32_t n, const CmMSearchDev& g, uint32_t h, const uint32_t* bound,
+                        uint32_t* next, uint32_t cap, uint32_t* counters);
+void cmk_msearch_best(hipStream_t s, const uint32_t* list, const uint32_t* U, uint32_t n, const CmMSearchDev& g, const uint32_t* counts, uint32_t* words);

@@ -259,6 +259,13 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "match_field") ok = read(is, c.match_sigma, c.match_max_dist) && std::isfinite(c.match_sigma) && c.match_sigma > 0.0f &&
                                             std::isfinite(c.match_max_dist) && c.match_max_dist > 0.0f;
         else if (key == "match_subcell") ok = read_flag(is, &c.match_subcell);
+        else if (key == "match_search") ok = read_flag(is, &c.match_search_enable);
+        else if (key == "match_search_window") ok = read(is, c.match_search_wx, c.match_search_wy) && c.match_search_wx <= CM_MATCH_SEARCH_MAX_SHIFT &&
+                                                    c.match_search_wy <= CM_MATCH_SEARCH_MAX_SHIFT;
+        else if (key == "match_search_depth") ok = read(is, c.match_search_depth) && c.match_search_depth <= CM_MATCH_SEARCH_MAX_DEPTH;
+        else if (key == "match_search_capacity") ok = read(is, c.match_search_max_nodes, c.match_search_max_cells) && c.match_search_max_nodes >= 1u &&
+                                                      c.match_search_max_nodes <= CM_MATCH_SEARCH_MAX_NODES && c.match_search_max_cells >= 1u &&
+                                                      c.match_search_max_cells <= CM_MATCH_SEARCH_MAX_NODES;
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -285,6 +292,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     }
     if (c.sensors.empty() || c.sensors.size() > CM_MAX_SENSORS) { if (err) *err = "sensor count must be 1..16"; return false; }
     if (c.grid_raycast && !(c.grid_cell > 0.0f)) { if (err) *err = "grid_raycast needs grid_cell > 0"; return false; }
+    if (c.match_enable && c.match_search_enable) { if (err) *err = "match and match_search exclude each other"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
     return true;
@@ -347,6 +355,12 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                 const cm_match_params qp{cfg_.match_sigma, cfg_.match_max_dist, cfg_.match_n_a, cfg_.match_a_stride, cfg_.match_wx, cfg_.match_wy,
                                          cfg_.match_subcell ? CM_MATCH_SUBCELL : 0u};
                 if (cm_map_match_configure(ctx_, &qp) != CM_OK) refuse("cm_map_match_configure");
+            }
+            if (ctx_ && cfg_.match_search_enable) {                // the search layer behind the cost layer, in the matching layer's place
+                const cm_match_search_params sp{cfg_.match_sigma, cfg_.match_max_dist, cfg_.match_n_a, cfg_.match_a_stride, cfg_.match_search_wx,
+                                                cfg_.match_search_wy, cfg_.match_search_depth, cfg_.match_search_max_nodes, cfg_.match_search_max_cells,
+                                                cfg_.match_subcell ? CM_MATCH_SUBCELL : 0u};
+                if (cm_map_match_search_configure(ctx_, &sp) != CM_OK) refuse("cm_map_match_search_configure");
             }
             if (ctx_ && cfg_.map_plan_neutral > 0u) {              // the plan layer behind the cost layer
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
@@ -524,14 +538,20 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
     }
     // The match in front of the integration: once the map holds a frame, the frame against it with the given pose as the prior.
     // A match the library refuses (a stale distance field after a failed epilogue) leaves the prior in place and says so.
-    if (cfg_.match_enable && cfg_.map_inflation_radius > 0.0f) {
+    // match_search 1: the search layer in the exhaustive layer's place; a capacity overflow is such a refusal too.
+    if ((cfg_.match_enable || cfg_.match_search_enable) && cfg_.map_inflation_radius > 0.0f) {
         matched_ = false;
         match_result_ = cm_match_result{};
+        match_search_info_ = cm_match_search_info{};
         if (map_info_.n_frames > 0) {
-            const int ms = cm_map_match_evaluate(ctx_, pose, &match_result_);
+            const int ms = cfg_.match_search_enable ? cm_map_match_search(ctx_, pose, &match_result_, &match_search_info_)
+                                                    : cm_map_match_evaluate(ctx_, pose, &match_result_);
             if (ms == CM_OK) {
                 matched_ = true;
                 std::memcpy(pose, match_result_.pose, sizeof pose);
+            } else if (ms == CM_CAPACITY && cfg_.match_search_enable) {
+                match_result_ = cm_match_result{};
+                set_error(cm_last_error(ctx_));
             } else {
                 match_result_ = cm_match_result{};
                 set_error(cm_last_error(ctx_));

@@ -157,6 +157,15 @@ struct NodeConfig {
     uint32_t match_wx = 10, match_wy = 10;           // shifts in cells
     float match_sigma = 0.1f, match_max_dist = 0.5f; // the likelihood field's standard deviation and cut (metres)
     bool match_subcell = false;
+    // match_search 1: the same match by the search layer (cm_map_match_search_configure, cm_map_match_search): branch and
+    // bound over shifts of up to CM_MATCH_SEARCH_MAX_SHIFT cells, with match_angles, match_field and match_subcell as above and
+    // a window, a depth and capacities of its own. Off by default; `match` and `match_search` together is a config error.
+    // matched() / match_result() / matched_pose() as above, and match_search_info(). A frame whose search overflows a
+    // capacity is integrated under the prior, as a refused one is.
+    bool match_search_enable = false;
+    uint32_t match_search_wx = 128, match_search_wy = 128;
+    uint32_t match_search_depth = 5;
+    uint32_t match_search_max_nodes = 1u << 18, match_search_max_cells = 1u << 17;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -210,6 +219,8 @@ struct NodeConfig {
 //   match <0|1> | match_angles <n_a> <a_stride> | match_window <wx> <wy> | match_field <sigma> <max_dist> | match_subcell <0|1>
 //   (scan matching of every frame against the map, behind the cost layer: 2 n_a + 1 angles a_stride table entries apart,
 //   shifts of up to wx and wy cells, the field's standard deviation and cut in metres)
+//   match_search <0|1> | match_search_window <wx> <wy> | match_search_depth <h> | match_search_capacity <max_nodes> <max_cells>
+//   (the same match by branch and bound over shifts of up to 1024 cells, in the place of `match`: both on is an error)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -338,6 +349,9 @@ public:
     bool matched() const { return matched_; }
     const cm_match_result& match_result() const { return match_result_; }
     const float* matched_pose() const { return matched_pose_; }
+    // match_search 1: the statistics of the search behind match_result() (zeros where the frame was not matched, the overflow
+    // where a capacity was exceeded).
+    const cm_match_search_info& match_search_info() const { return match_search_info_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -417,6 +431,7 @@ private:
     cm_traj_info traj_info_{};
     bool matched_ = false;
     cm_match_result match_result_{};
+    cm_match_search_info match_search_info_{};
     float matched_pose_[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;

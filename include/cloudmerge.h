@@ -1055,6 +1055,98 @@ CM_API int cm_map_match_table_copy(cm_ctx* ctx, uint8_t* host_dst, uint64_t capa
  * capacity below it: CM_CAPACITY (dst is not written). */
 CM_API int cm_match_table(float cell, float sigma, float max_dist, uint8_t* dst, uint64_t capacity, uint64_t* n);
 
+/* ---- branch-and-bound scan matching over wide windows of the map: the search layer (an extension) ----------------------------
+ * The layer above searches its window exhaustively and is capped at CM_MATCH_MAX_SHIFT cells. This one returns the best entry
+ * of the same definition over shifts of up to CM_MATCH_SEARCH_MAX_SHIFT cells without computing the volume: a pyramid of
+ * block maxima of the field bounds whole blocks of shifts from above, and a block whose bound lies below a score already
+ * found is dropped (cartographer's FastCorrelativeScanMatcher, with integer bounds: DESIGN.md §28). The bounds are sound, so
+ * the result is exactly step 6's over the whole range; the way there is specified too, so that the statistics in
+ * cm_match_search_info are a function of the inputs as well. A second layer behind the cost layer with buffers of its own: it
+ * may be configured beside the layer above, and neither changes the other.
+ * Input: as for cm_map_match_evaluate, with cm_match_search_params in the place of cm_match_params.
+ *   1-4. Field table, field L, angle candidates Q_k and cell sets D_k: steps 1 to 4 above, word for word.
+ *   5. Score. S(k, i, j) as in step 5 above over i = -wx .. wx, j = -wy .. wy, with the entry index
+ *      ((k + n_a) * (2 wy + 1) + (j + wy)) * (2 wx + 1) + (i + wx) (it fits uint32_t: at most 255 * 2049 * 2049). The volume
+ *      is never materialised.
+ *   6. Best. As step 6 above: the largest S, ties to the smallest i * i + j * j, then the smallest |k|, then the lowest entry
+ *      index. How it is found:
+ *      a. Pyramid. L_0 = L; L_h(x, y) = max over 0 <= a, b < 2^h of L(x + a, y + b) for all integer (x, y), L being 0
+ *         outside the window. Level h is stored as (ny + 2^h - 1) rows of (nx + 2^h - 1) bytes, entry
+ *         [y + 2^h - 1][x + 2^h - 1] holding L_h(x, y); outside that storage L_h is 0. cm_map_match_search_level_copy
+ *         returns a level.
+ *      b. A node (h, k, i0, j0) stands for the entries of k with i0 <= i < i0 + 2^h, j0 <= j < j0 + 2^h that lie in the
+ *         range. Its bound is U = sum over c in D_k of L_h(c + (i0, j0)) as uint32_t: U >= S of each of its entries, and at
+ *         h = 0, U = S(k, i0, j0). Node order is ascending (k + n_a, j0, i0).
+ *      c. Roots: h = depth, i0 = -wx + a * 2^depth for a = 0 .. ceil((2 wx + 1) / 2^depth) - 1, j0 likewise with wy, for
+ *         every k; n_roots is their number. The children of a node at h > 0 are those of the four nodes
+ *         (h - 1, k, i0 + a * 2^(h-1), j0 + b * 2^(h-1)), a, b in {0, 1}, with i0' <= wx and j0' <= wy.
+ *      d. Bound B. All roots are scored. From the root of the largest U (ties: the first in node order) the search descends
+ *         at every level to the child of the largest U (the same tie rule) down to a leaf (h = 0);
+ *         B = max(S(that leaf), S(0, 0, 0)). B is not raised afterwards. n_probe counts the children scored on the way down
+ *         plus one for the prior's entry (the roots are not counted: 1 at depth 0).
+ *      e. Level loop. live_depth = the roots with U >= B; for h = depth .. 1 all children of live_h are scored and
+ *         live_(h-1) = those with U >= B. scored[h] and live[h] are the numbers of nodes scored and kept at level h
+ *         (scored[depth] = n_roots), 0 above depth. A node is dropped only if U < B, so every entry with S = max S has all
+ *         its ancestors live and is in live_0, and step 6's rule over live_0 is step 6 over the whole volume.
+ *      f. Capacities. If some |D_k| exceeds max_cells the evaluate returns CM_CAPACITY with
+ *         overflow_level = CM_MATCH_SEARCH_OVERFLOW_CELLS and depth and n_roots set, everything else 0. If the live nodes of
+ *         level h + 1 have more than max_nodes children it returns CM_CAPACITY with overflow_level = h, scored[h] their
+ *         number, live[h] and everything below 0, and bound and n_probe set. Either way the result stays stale (the info is
+ *         still written to *info). overflow_level is -1 otherwise. Both conditions are functions of the inputs.
+ *   7. Sub-cell offset, with CM_MATCH_SUBCELL: step 7 above; the four neighbours' scores are computed directly as leaves, a
+ *      neighbour outside [-wx, wx] or [-wy, wy] does not exist.
+ *   8. Result: step 8 above, the same cm_match_result.
+ * cm_map_match_search_configure refuses with CM_BAD_ARG: no configured cost layer; sigma or max_dist not finite and > 0;
+ * R > CM_MATCH_MAX_RADIUS_CELLS; n_a > 127, a_stride == 0 or n_a * a_stride > 1024; wx or wy above
+ * CM_MATCH_SEARCH_MAX_SHIFT; depth above CM_MATCH_SEARCH_MAX_DEPTH; max_nodes or max_cells 0 or above
+ * CM_MATCH_SEARCH_MAX_NODES; more roots than max_nodes; a map window with nx or ny above 65535; unknown flag bits; a frame in
+ * flight. cm_map_match_search refuses what cm_map_match_evaluate refuses, with this layer in the place of that one. All
+ * memory of the layer is taken by cm_map_match_search_configure (the pyramid with the table behind it, the candidates'
+ * bitmaps and cell lists of max_cells words each, two node lists and one score list of max_nodes words, the roots, the
+ * page-locked host words): no evaluate or copy allocates. Result, info and pyramid are stale from
+ * cm_map_match_search_configure and from every cm_map_integrate, cm_map_cost_update and merge until the next successful
+ * cm_map_match_search: cm_map_match_search_result and cm_map_match_search_level_copy then refuse with CM_BAD_ARG and say
+ * since which call. cm_map_cost_configure and cm_map_configure, in either form, free the layer. It reads the map and the
+ * cost layer and writes buffers of its own only: no other layer's tables or staleness change, the exhaustive layer's
+ * included. With CM_FLAG_PROFILE, cm_get_stage_times after an evaluate lists msearch_clear, k_match_field,
+ * k_msearch_pyramid, k_match_mark, k_msearch_list, k_msearch_score, k_msearch_pick, k_msearch_select, k_msearch_best, equally
+ * named launches added up (the host's waits for a level's counts fall to k_msearch_select). Not modelled: raising B during
+ * the level loop or a best-first order, a covariance of the match, roll, pitch and z, cell weights. */
+#define CM_MATCH_SEARCH_MAX_SHIFT 1024
+#define CM_MATCH_SEARCH_MAX_DEPTH 7
+#define CM_MATCH_SEARCH_MAX_NODES (1u << 22)
+#define CM_MATCH_SEARCH_OVERFLOW_CELLS (-2)
+typedef struct cm_match_search_params { /* 40 bytes (ten words), no padding */
+    float sigma;                       /* as cm_match_params */
+    float max_dist;
+    uint32_t n_a;
+    uint32_t a_stride;
+    uint32_t wx, wy;                   /* shifts -wx .. wx and -wy .. wy cells; each at most CM_MATCH_SEARCH_MAX_SHIFT */
+    uint32_t depth;                    /* the roots' level; at most CM_MATCH_SEARCH_MAX_DEPTH */
+    uint32_t max_nodes;                /* room of a level's node list; 1 .. CM_MATCH_SEARCH_MAX_NODES, at least n_roots */
+    uint32_t max_cells;                /* room of a candidate's cell list; 1 .. CM_MATCH_SEARCH_MAX_NODES */
+    uint32_t flags;                    /* CM_MATCH_SUBCELL or 0 */
+} cm_match_search_params;
+typedef struct cm_match_search_info {  /* 84 bytes */
+    uint32_t depth;
+    uint32_t n_roots;
+    uint32_t bound;                    /* B */
+    uint32_t scored[8];                /* nodes scored in the level loop, by level */
+    uint32_t live[8];                  /* those with U >= B */
+    uint32_t n_probe;                  /* nodes scored for B beyond the roots */
+    int32_t overflow_level;            /* -1: none; h: the children at level h; CM_MATCH_SEARCH_OVERFLOW_CELLS */
+} cm_match_search_info;
+/* Non-NULL parameters allocate the layer (result, info and pyramid are stale until the first evaluate); NULL frees it. */
+CM_API int cm_map_match_search_configure(cm_ctx* ctx, const cm_match_search_params* p);
+/* Matches the last frame against the map around the prior pose. *out and *info may be NULL. CM_CAPACITY: step 6f (*info is
+ * written, *out is not). */
+CM_API int cm_map_match_search(cm_ctx* ctx, const float pose[12], cm_match_result* out, cm_match_search_info* info);
+/* The last result and info again; either may be NULL. */
+CM_API int cm_map_match_search_result(cm_ctx* ctx, cm_match_result* out, cm_match_search_info* info);
+/* Host copy of level h <= depth of the last evaluate's pyramid; capacity in bytes; dims (may be NULL) = {columns, rows} =
+ * {nx + 2^h - 1, ny + 2^h - 1}. Too small: CM_CAPACITY (nothing is copied; dims is still written). */
+CM_API int cm_map_match_search_level_copy(cm_ctx* ctx, uint32_t h, uint8_t* host_dst, uint64_t capacity, uint32_t dims[2]);
+
 /* ---- frontier layer behind the plan layer: connected frontiers of the occupancy map (an extension) ------------------------
  * Where to go when nobody gives a goal: every exploration stack over an occupancy grid (Yamauchi's frontiers,
  * frontier_exploration, explore_lite) takes the cells where known free space meets the unknown, groups them into connected
