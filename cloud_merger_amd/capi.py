@@ -47,13 +47,15 @@ SYMBOLS = [
     "cm_box_directions", "cm_result_cluster_boxes", "cm_result_cluster_boxes_device",
     "cm_result_grid_map", "cm_result_grid_map_device", "cm_grid_occupancy_copy",
     "cm_result_grid_rays", "cm_result_grid_rays_device", "cm_grid_ray_occupancy_copy",
-    "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy",
+    "cm_map_configure", "cm_map_integrate", "cm_map_copy", "cm_map_device", "cm_map_occupancy_copy", "cm_map_load",
     "cm_map_cost_configure", "cm_map_cost_update", "cm_map_cost_copy", "cm_map_dist_copy", "cm_map_cost_device", "cm_map_cost_table_copy",
     "cm_map_plan_configure", "cm_map_plan_update", "cm_map_plan_copy", "cm_map_plan_device", "cm_map_plan_path",
     "cm_map_traj_configure", "cm_map_traj_evaluate", "cm_map_traj_copy", "cm_map_traj_device", "cm_traj_directions",
     "cm_map_frontier_configure", "cm_map_frontier_update", "cm_map_frontier_copy", "cm_map_frontier_labels_copy", "cm_map_frontier_device",
     "cm_map_match_configure", "cm_map_match_evaluate", "cm_map_match_copy", "cm_map_match_device", "cm_map_match_table_copy", "cm_match_table",
     "cm_map_match_search_configure", "cm_map_match_search", "cm_map_match_search_result", "cm_map_match_search_level_copy",
+    "cm_map_mcl_configure", "cm_map_mcl_init_pose", "cm_map_mcl_init_uniform", "cm_map_mcl_predict", "cm_map_mcl_update", "cm_map_mcl_copy",
+    "cm_map_mcl_weights_copy", "cm_map_mcl_device", "cm_mcl_draws",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -424,6 +426,39 @@ class MatchSearchInfo(C.Structure):
 
 assert C.sizeof(MatchSearchParams) == 40 and C.sizeof(MatchSearchInfo) == 84
 
+# the localisation layer: a particle filter against the occupancy map, behind the cost layer (cm_map_mcl_configure, cm_map_mcl_update)
+MCL_MAX_PARTICLES = 65536
+MCL_MAX_BEAMS = 8192
+MCL_MAX_RANGE_CELLS = 1024
+MCL_WEIGHT_ONE = 65536
+MCL_RESAMPLE_ALWAYS = 1
+
+
+class MclParams(C.Structure):
+    """cm_mcl_params (40 bytes): the particles, the most beams of an update and the reach of a beam in body cells, the field's
+    sigma and cut (metres) as MatchParams', the temperature of the weights, the fraction of n_particles below which n_eff
+    triggers resampling, MCL_RESAMPLE_ALWAYS or 0, the seed of the draws."""
+    _fields_ = [("n_particles", C.c_uint32), ("max_beams", C.c_uint32), ("range_cells", C.c_uint32), ("sigma", C.c_float), ("max_dist", C.c_float),
+                ("tau", C.c_float), ("resample_frac", C.c_float), ("flags", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class MclInfo(C.Structure):
+    """cm_mcl_info (176 bytes): the particles, the distinct body cells, the stride and the beams of the update, its gen, whether
+    it resampled, the best particle and its pose before resampling, the exact integer sums, n_eff, the weighted means and the
+    three spread terms (m^2)."""
+    _fields_ = [("n_particles", C.c_uint32), ("n_cells", C.c_uint32), ("stride", C.c_uint32), ("n_beams", C.c_uint32), ("gen", C.c_uint64),
+                ("resampled", C.c_uint32), ("best", C.c_uint32), ("best_x", C.c_float), ("best_y", C.c_float), ("best_h", C.c_uint32),
+                ("_pad", C.c_uint32), ("sum_w", C.c_uint64), ("sum_w2", C.c_uint64), ("sum_wqx", C.c_int64), ("sum_wqy", C.c_int64),
+                ("sum_wc", C.c_int64), ("sum_ws", C.c_int64), ("sum_wdxx", C.c_int64), ("sum_wdyy", C.c_int64), ("sum_wdxy", C.c_int64),
+                ("n_eff", C.c_double), ("mean_x", C.c_double), ("mean_y", C.c_double), ("mean_yaw", C.c_double), ("var_xx", C.c_double),
+                ("var_yy", C.c_double), ("var_xy", C.c_double)]
+
+
+MCL_PARTICLE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("h", "<u4"), ("parent", "<u4"), ("acc", "<u8")])
+MCL_WEIGHT_DTYPE = np.dtype([("score", "<u4"), ("weight", "<u4")])
+assert C.sizeof(MclParams) == 40 and MclParams.seed.offset == 32 and C.sizeof(MclInfo) == 176 and MclInfo.sum_w.offset == 48
+assert MclInfo.n_eff.offset == 120 and MCL_PARTICLE_DTYPE.itemsize == 24 and MCL_WEIGHT_DTYPE.itemsize == 8
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -643,6 +678,16 @@ def load():
     L.cm_map_match_search.argtypes = [vp, vp, C.POINTER(MatchResult), C.POINTER(MatchSearchInfo)]
     L.cm_map_match_search_result.argtypes = [vp, C.POINTER(MatchResult), C.POINTER(MatchSearchInfo)]
     L.cm_map_match_search_level_copy.argtypes = [vp, C.c_uint32, vp, u64, C.POINTER(C.c_uint32 * 2)]
+    L.cm_map_load.argtypes = [vp, vp, u64, C.POINTER(C.c_int32 * 2), C.POINTER(MapInfo)]
+    L.cm_map_mcl_configure.argtypes = [vp, C.POINTER(MclParams)]
+    L.cm_map_mcl_init_pose.argtypes = [vp] + [C.c_float] * 6
+    L.cm_map_mcl_init_uniform.argtypes = [vp]
+    L.cm_map_mcl_predict.argtypes = [vp] + [C.c_float] * 6
+    L.cm_map_mcl_update.argtypes = [vp, C.POINTER(MclInfo)]
+    L.cm_map_mcl_copy.argtypes = [vp, vp, u64]
+    L.cm_map_mcl_weights_copy.argtypes = [vp, vp, u64, C.POINTER(MclInfo)]
+    L.cm_map_mcl_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(MclInfo)]
+    L.cm_mcl_draws.argtypes = [u64, u64, u32, u32, u32, vp]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -698,6 +743,15 @@ def match_table(cell, sigma, max_dist):
     if st != OK:
         raise CloudMergeError(st, "cm_match_table")
     return out[: n.value].copy()
+
+
+def mcl_draws(seed, gen, first_p, n_p, i):
+    """(n_p,) uint64: the localisation layer's draw(p, i) for p = first_p .. first_p + n_p - 1 of the call gen (cm_mcl_draws)."""
+    out = np.empty(int(n_p), dtype=np.uint64)
+    st = load().cm_mcl_draws(int(seed) & (2**64 - 1), int(gen) & (2**64 - 1), int(first_p), int(n_p), int(i), out.ctypes.data if n_p else None)
+    if st != OK and n_p:
+        raise CloudMergeError(st, "cm_mcl_draws")
+    return out
 
 
 def status_string(status):
@@ -1154,6 +1208,15 @@ class CloudMerger:
         self._check(self._lib.cm_map_occupancy_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_occupancy_copy")
         return out.reshape(info.ny, info.nx), info
 
+    def map_load(self, table, anchor):
+        """Puts a recorded map back: table is what map() returned ((ny, nx) MAP_DTYPE), anchor its MapInfo's anchor. The layers
+        behind go stale as after an integration. Returns the MapInfo."""
+        t = np.ascontiguousarray(table, dtype=MAP_DTYPE).reshape(-1)
+        a = (C.c_int32 * 2)(int(anchor[0]), int(anchor[1]))
+        info = MapInfo()
+        self._check(self._lib.cm_map_load(self._ctx, t.ctypes.data, t.shape[0], C.byref(a), C.byref(info)), "cm_map_load")
+        return info
+
     # ---- cost layer over the occupancy map (cm_map_cost_configure / cm_map_cost_update) ----
     def map_cost_configure(self, inscribed_radius=None, inflation_radius=0.0, cost_scaling=0.0, inflate_unknown=False):
         """Allocates the cost layer behind the configured map and builds its table: costmap_2d's inflation layer (254 lethal, 253
@@ -1376,6 +1439,59 @@ class CloudMerger:
         out = np.empty(n.value, dtype=np.uint8)
         self._check(self._lib.cm_map_match_table_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(n)), "cm_map_match_table_copy")
         return out
+
+    # ---- the localisation layer: a particle filter against the map, behind the cost layer (cm_map_mcl_configure / cm_map_mcl_update) ----
+    def map_mcl_configure(self, n_particles=None, max_beams=256, range_cells=256, sigma=0.1, max_dist=0.5, tau=8.0, resample_frac=0.5,
+                          always=False, seed=0):
+        """Allocates the localisation layer behind the configured cost layer: n_particles particles scored with at most max_beams
+        beams (the frame's distinct body cells within range_cells, thinned by a stride) against map_match_configure's field of
+        sigma and max_dist; weights exp(-(A - acc) / (255 tau)); resampling when n_eff < resample_frac * n_particles, or after
+        every update with always. n_particles None frees the layer."""
+        if n_particles is None:
+            self._check(self._lib.cm_map_mcl_configure(self._ctx, None), "cm_map_mcl_configure")
+            return
+        p = MclParams(int(n_particles), int(max_beams), int(range_cells), float(sigma), float(max_dist), float(tau), float(resample_frac),
+                      MCL_RESAMPLE_ALWAYS if always else 0, int(seed) & (2**64 - 1))
+        self._check(self._lib.cm_map_mcl_configure(self._ctx, C.byref(p)), "cm_map_mcl_configure")
+        self._mcl_n = p.n_particles
+
+    def map_mcl_init_pose(self, x, y, yaw, sd_x=0.0, sd_y=0.0, sd_yaw=0.0):
+        """Draws the particles around a pose of the map's world frame with the three standard deviations (metres, radians)."""
+        self._check(self._lib.cm_map_mcl_init_pose(self._ctx, x, y, yaw, sd_x, sd_y, sd_yaw), "cm_map_mcl_init_pose")
+
+    def map_mcl_init_uniform(self):
+        """Draws the particles uniformly over the free cells of the map's image, headings uniform over the turn."""
+        self._check(self._lib.cm_map_mcl_init_uniform(self._ctx), "cm_map_mcl_init_uniform")
+
+    def map_mcl_predict(self, d_fwd, d_left, d_yaw, sd_fwd=0.0, sd_left=0.0, sd_yaw=0.0):
+        """Moves every particle by the vehicle-frame motion since the last predict, with noise of the three standard deviations."""
+        self._check(self._lib.cm_map_mcl_predict(self._ctx, d_fwd, d_left, d_yaw, sd_fwd, sd_left, sd_yaw), "cm_map_mcl_predict")
+
+    def map_mcl_update(self):
+        """Scores the particles with the last frame, weighs them, estimates and resamples where due. Returns the MclInfo."""
+        info = MclInfo()
+        self._check(self._lib.cm_map_mcl_update(self._ctx, C.byref(info)), "cm_map_mcl_update")
+        return info
+
+    def map_mcl_particles(self):
+        """(n_particles,) MCL_PARTICLE_DTYPE: the particles after the last call of the layer."""
+        out = np.empty(getattr(self, "_mcl_n", 0), dtype=MCL_PARTICLE_DTYPE)
+        self._check(self._lib.cm_map_mcl_copy(self._ctx, out.ctypes.data, out.shape[0]), "cm_map_mcl_copy")
+        return out
+
+    def map_mcl_weights(self):
+        """((n_particles,) MCL_WEIGHT_DTYPE, MclInfo) of the last update, in the order of the particles it found."""
+        info = MclInfo()
+        out = np.empty(getattr(self, "_mcl_n", 0), dtype=MCL_WEIGHT_DTYPE)
+        self._check(self._lib.cm_map_mcl_weights_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_mcl_weights_copy")
+        return out, info
+
+    def map_mcl_device(self):
+        """(particles device pointer, weights device pointer, MclInfo), owned by the context and valid until the next call of the
+        layer or configure call."""
+        parts, wts, info = C.c_void_p(), C.c_void_p(), MclInfo()
+        self._check(self._lib.cm_map_mcl_device(self._ctx, C.byref(parts), C.byref(wts), C.byref(info)), "cm_map_mcl_device")
+        return parts.value, wts.value, info
 
     # ---- branch-and-bound scan matching over wide windows, behind the cost layer (cm_map_match_search_configure / cm_map_match_search) ----
     def map_match_search_configure(self, sigma=None, max_dist=0.5, n_a=0, a_stride=1, wx=0, wy=0, depth=0, max_nodes=1 << 16, max_cells=1 << 16,

@@ -11,6 +11,7 @@
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 #include "cm_match_table.hpp"
+#include "cm_mcl_math.hpp"
 
 namespace {
 
@@ -971,6 +972,23 @@ int cm_map_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, 
     return CM_OK;
 }
 
+int cm_map_load(cm_ctx* c, const cm_map_cell* host_src, uint64_t n_cells, const int32_t anchor[2], cm_map_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = map_read_check(c)) return e;
+    if (!host_src) return fail(c, CM_BAD_ARG, "no state table");
+    if (!anchor) return fail(c, CM_BAD_ARG, "no anchor");
+    if (n_cells != static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny) return fail(c, CM_BAD_ARG, "n_cells is not nx * ny");
+    for (int k = 0; k < 2; ++k)
+        if (anchor[k] <= -(1 << 30) || anchor[k] >= (1 << 30)) return fail(c, CM_BAD_ARG, "the anchor lies 2^30 cells or more from the world origin");
+    for (uint64_t i = 0; i < n_cells; ++i)
+        if (host_src[i].logodds < c->map_params.l_min || host_src[i].logodds > c->map_params.l_max)
+            return fail(c, CM_BAD_ARG, "a logodds lies outside [l_min, l_max]");
+    if (const int e = map_load(c, host_src, anchor)) return e;
+    if (out) *out = c->map_info;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_cost_params) == 16 && offsetof(cm_cost_params, flags) == 12, "cm_cost_params is 16 bytes");
 static_assert(CM_COST_MAX_AXIS == CM_COST_MAX_AXIS_DEV && CM_COST_MAX_RADIUS_CELLS == 256, "the row pass's LDS row and the largest table");
 
@@ -1442,6 +1460,148 @@ int cm_map_match_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uin
     if (n_lut > capacity) return fail(c, CM_CAPACITY, "field table destination too small");
     if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
     std::memcpy(host_dst, c->match_lut_host.data(), n_lut);
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_mcl_params) == 40 && offsetof(cm_mcl_params, seed) == 32 && sizeof(cm_mcl_particle) == 24 && sizeof(cm_mcl_weight) == 8 &&
+                  sizeof(cm_mcl_info) == 176 && offsetof(cm_mcl_info, gen) == 16 && offsetof(cm_mcl_info, sum_w) == 48 && offsetof(cm_mcl_info, n_eff) == 120,
+              "the localisation layer's four structs");
+static_assert(sizeof(CmMclParticleDev) == sizeof(cm_mcl_particle) && offsetof(cm_mcl_particle, acc) == offsetof(CmMclParticleDev, acc) &&
+                  offsetof(cm_mcl_particle, parent) == offsetof(CmMclParticleDev, parent) && sizeof(CmMclWeightDev) == sizeof(cm_mcl_weight) &&
+                  offsetof(cm_mcl_weight, weight) == offsetof(CmMclWeightDev, weight),
+              "the kernels write cm_mcl_particle and cm_mcl_weight");
+static_assert(CM_MCL_MAX_PARTICLES == CM_MCL_MAX_PARTICLES_DEV && CM_MCL_MAX_BEAMS == CM_MCL_MAX_BEAMS_DEV && CM_MCL_MAX_RANGE_CELLS == CM_MCL_MAX_RANGE_DEV &&
+                  CM_MCL_MAX_BEAMS * 8 <= 65536 && CM_MCL_MAX_PARTICLES <= 64 * CM_MCL_ONE_BLOCK &&
+                  ((2ull * CM_MCL_MAX_RANGE_CELLS + 1) * (2ull * CM_MCL_MAX_RANGE_CELLS + 1) + 31) / 32 <= 1ull * CM_MCL_BLOCK * CM_MCL_ONE_BLOCK &&
+                  (CM_GRID_MAX_CELLS + 31) / 32 <= CM_MCL_BLOCK * CM_MCL_ONE_BLOCK,
+              "the kernels' constants; the staged beams fit 64 KiB of LDS; a bitmap's block counts fit one workgroup's scan");
+
+int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t n_p, uint32_t i, uint64_t* dst) {
+    if (!dst || i >= 256u || static_cast<uint64_t>(first_p) + n_p > (1ull << 32)) return CM_BAD_ARG;
+    const unsigned long long base = cm_mcl_base(seed, gen);
+    for (uint32_t k = 0; k < n_p; ++k) dst[k] = cm_mcl_draw(base, first_p + k, i);
+    return CM_OK;
+}
+
+int cm_map_mcl_configure(cm_ctx* c, const cm_mcl_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    uint32_t R = 0;
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+        if (p->n_particles < 1u || p->n_particles > CM_MCL_MAX_PARTICLES) return fail(c, CM_BAD_ARG, "n_particles must lie in 1..CM_MCL_MAX_PARTICLES");
+        if (p->max_beams < 1u || p->max_beams > CM_MCL_MAX_BEAMS) return fail(c, CM_BAD_ARG, "max_beams must lie in 1..CM_MCL_MAX_BEAMS");
+        if (p->range_cells < 1u || p->range_cells > CM_MCL_MAX_RANGE_CELLS) return fail(c, CM_BAD_ARG, "range_cells must lie in 1..CM_MCL_MAX_RANGE_CELLS");
+        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
+        if (!std::isfinite(p->tau) || !(p->tau > 0.0f)) return fail(c, CM_BAD_ARG, "tau must be finite and > 0");
+        if (!std::isfinite(p->resample_frac) || !(p->resample_frac >= 0.0f && p->resample_frac <= 1.0f))
+            return fail(c, CM_BAD_ARG, "resample_frac must be finite and lie in 0..1");
+        if (p->flags & ~CM_MCL_RESAMPLE_ALWAYS) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    }
+    return map_mcl_configure(c, p, R);
+}
+
+// The refusals every call on a configured localisation layer shares.
+static int mcl_check(cm_ctx* c, bool need_particles, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->mcl_on) return fail(c, CM_BAD_ARG, "no localisation layer (cm_map_mcl_configure first)");
+    if (need_particles && !c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
+    if (read && c->mcl_stale) return fail(c, CM_BAD_ARG, c->mcl_stale);
+    if (read && c->mcl_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the weights are stale: no cm_map_mcl_update since the last merge");
+    return CM_OK;
+}
+
+// A centre or a motion (x, y, yaw) and its three standard deviations: what init_pose and predict refuse about them.
+static int mcl_values_check(cm_ctx* c, const float v[6]) {
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(v[k])) return fail(c, CM_BAD_ARG, "a value is not finite");
+    if (std::fabs(v[2]) > 1024.0f) return fail(c, CM_BAD_ARG, "|yaw| is above 1024");
+    for (int k = 3; k < 6; ++k)
+        if (v[k] < 0.0f || v[k] > 1024.0f) return fail(c, CM_BAD_ARG, "a standard deviation must lie in 0..1024");
+    return CM_OK;
+}
+
+int cm_map_mcl_init_pose(cm_ctx* c, float x0, float y0, float yaw0, float sd_x, float sd_y, float sd_yaw) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, false, false)) return e;
+    const float v[6] = {x0, y0, yaw0, sd_x, sd_y, sd_yaw};
+    if (const int e = mcl_values_check(c, v)) return e;
+    return map_mcl_init_pose(c, v);
+}
+
+int cm_map_mcl_init_uniform(cm_ctx* c) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, false, false)) return e;
+    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate or cm_map_load first)");
+    return map_mcl_init_uniform(c);
+}
+
+int cm_map_mcl_predict(cm_ctx* c, float d_fwd, float d_left, float d_yaw, float sd_fwd, float sd_left, float sd_yaw) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, false)) return e;
+    const float v[6] = {d_fwd, d_left, d_yaw, sd_fwd, sd_left, sd_yaw};
+    if (const int e = mcl_values_check(c, v)) return e;
+    return map_mcl_predict(c, v);
+}
+
+int cm_map_mcl_update(cm_ctx* c, cm_mcl_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, false, false)) return e;
+    if (const int e = centroid_result_check(c)) return e;
+    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
+    if (!c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
+    if (const int e = map_mcl_update(c)) return e;
+    if (out) *out = c->mcl_info;
+    return CM_OK;
+}
+
+int cm_map_mcl_copy(cm_ctx* c, cm_mcl_particle* host_dst, uint64_t capacity) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, false)) return e;
+    const uint64_t n = c->mcl_params.n_particles;
+    if (n > capacity) return fail(c, CM_CAPACITY, "particle destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->mcl_parts[c->mcl_cur], n * sizeof(cm_mcl_particle), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_mcl_particle);
+    return CM_OK;
+}
+
+int cm_map_mcl_weights_copy(cm_ctx* c, cm_mcl_weight* host_dst, uint64_t capacity, cm_mcl_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, true)) return e;
+    if (info) *info = c->mcl_info;
+    const uint64_t n = c->mcl_params.n_particles;
+    if (n > capacity) return fail(c, CM_CAPACITY, "weight destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->mcl_wts, n * sizeof(cm_mcl_weight), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_mcl_weight);
+    return CM_OK;
+}
+
+int cm_map_mcl_device(cm_ctx* c, const void** particles, const void** weights, cm_mcl_info* info) {
+    if (!c) return CM_BAD_ARG;
+    if (particles) *particles = nullptr;
+    if (weights) *weights = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, true)) return e;
+    if (info) *info = c->mcl_info;
+    if (particles) *particles = c->mcl_parts[c->mcl_cur];
+    if (weights) *weights = c->mcl_wts;
     return CM_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 #include "cm_match_table.hpp"
+#include "cm_mcl_math.hpp"
 #include "cm_search.hpp"
 
 namespace {
@@ -563,6 +564,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_integrate";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
     c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_integrate";
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -573,6 +575,7 @@ int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     if (const int e = map_plan_configure(c, nullptr)) return e;        // the plan layer goes with the cost layer it reads
     if (const int e = map_match_configure(c, nullptr, 0)) return e;    // and so does the matching layer
     if (const int e = map_msearch_configure(c, nullptr, 0)) return e;  // and the search layer
+    if (const int e = map_mcl_configure(c, nullptr, 0)) return e;      // and the localisation layer
     c->cost_on = false;
     c->cost_fresh = false;
     if (!q) {
@@ -628,6 +631,7 @@ int map_cost_update(cm_ctx* c) {
     c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_cost_update";
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
     c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_cost_update";
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_cost_update";
     return CM_OK;
 }
 
@@ -1076,6 +1080,261 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
     c->match_serial = c->frame_serial;
     c->match_stale = nullptr;
+    return CM_OK;
+}
+
+// The localisation layer's memory, all of it: two particle buffers, the weight table, the prefix sums with the info words
+// behind them, the field with its table behind it (built here, cm_match_table.hpp, and uploaded), the one bitmap and the one
+// list (behind the block counts) that serve the body cells and the free cells, the heading table and the page-locked words an
+// update reads back. nullptr gives it back. No particles, gen = 0, weights and info stale until the first update.
+int map_mcl_configure(cm_ctx* c, const cm_mcl_params* q, uint32_t R) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->mcl_on = false;
+    c->mcl_init = false;
+    c->mcl_gen = 0;
+    c->mcl_cur = 0;
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since cm_map_mcl_configure";
+    std::memset(&c->mcl_info, 0, sizeof c->mcl_info);
+    if (!q) {
+        c->mcl_parts[0].release();
+        c->mcl_parts[1].release();
+        c->mcl_wts.release();
+        c->mcl_cum.release();
+        c->mcl_field.release();
+        c->mcl_bits.release();
+        c->mcl_list.release();
+        c->mcl_dirs.release();
+        c->mcl_host.release();
+        return CM_OK;
+    }
+    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, side = 2 * static_cast<size_t>(q->range_cells) + 1;
+    const size_t words = std::max((n_cells + 31) / 32, (side * side + 31) / 32);
+    const size_t n_lut = static_cast<size_t>(R) * R + 1, n = q->n_particles;
+    if (!c->mcl_parts[0].reserve(n) || !c->mcl_parts[1].reserve(n) || !c->mcl_wts.reserve(n) || !c->mcl_cum.reserve(n + CM_MCL_WORDS) ||
+        !c->mcl_field.reserve(n_cells + n_lut) || !c->mcl_bits.reserve(words) ||
+        !c->mcl_list.reserve(CM_MCL_ONE_BLOCK + std::max(static_cast<size_t>(q->max_beams), n_cells)) || !c->mcl_dirs.reserve(2 * CM_TRAJ_HEADINGS) ||
+        !c->mcl_host.reserve(CM_MCL_WORDS))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the localisation layer");
+    std::vector<unsigned char> lut(n_lut, 0);
+    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, lut.data());
+    HIP_TRY(c, hipMemcpyAsync(c->mcl_field + n_cells, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->mcl_dirs, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->mcl_params = *q;
+    c->mcl_radius = R;
+    c->mcl_on = true;
+    return CM_OK;
+}
+
+namespace {
+
+CmMclDev mcl_dev(const cm_ctx* c) {
+    const cm_mcl_params& q = c->mcl_params;
+    CmMclDev g;
+    g.inv = 1.0f / c->map_params.cell;
+    g.cell = c->map_params.cell;
+    g.ax = c->map_info.anchor[0];
+    g.ay = c->map_info.anchor[1];
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.z_min = c->map_params.z_min;
+    g.z_max = c->map_params.z_max;
+    g.n = q.n_particles;
+    g.max_beams = q.max_beams;
+    g.range = q.range_cells;
+    g.side = 2u * q.range_cells + 1u;
+    return g;
+}
+
+// Step 2's scale of a standard deviation: (float)((double)sd * K1).
+float mcl_scale(float sd) { return static_cast<float>(static_cast<double>(sd) * std::sqrt(3.0 / 4294967295.0)); }
+
+// What an init_pose or predict call adds to a particle, and the call's gen taken.
+CmMclMoveDev mcl_move(cm_ctx* c, const float v[6]) {
+    CmMclMoveDev m;
+    m.a = v[0];
+    m.b = v[1];
+    m.yaw = static_cast<double>(v[2]);
+    m.sc_a = mcl_scale(v[3]);
+    m.sc_b = mcl_scale(v[4]);
+    m.sc_yaw = mcl_scale(v[5]);
+    m.base = cm_mcl_base(c->mcl_params.seed, c->mcl_gen++);
+    return m;
+}
+
+}  // namespace
+
+int map_mcl_init_pose(cm_ctx* c, const float v[6]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->mcl_init = false;
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_init_pose";
+    c->mcl_cur = 0;
+    c->prof_used = 0;
+    prof_mark(c, "k_mcl_init_pose");
+    cmk_mcl_init_pose(c->stream, mcl_move(c, v), c->mcl_params.n_particles, c->mcl_parts[0]);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    collect_stage_times(c);
+    c->mcl_init = true;
+    return CM_OK;
+}
+
+// The free cells by the ordered compaction of the image's bitmap; their number comes back to the host, which refuses an
+// image without one before any particle is written.
+int map_mcl_init_uniform(cm_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const CmMclDev g = mcl_dev(c);
+    const uint32_t n_cells = g.nx * g.ny, n_words = (n_cells + 31u) / 32u;
+    unsigned long long* const words = c->mcl_cum + g.n;
+    uint32_t* const counts = c->mcl_list;
+    uint32_t* const list = c->mcl_list + CM_MCL_ONE_BLOCK;
+    hipStream_t st = c->stream;
+    c->prof_used = 0;
+    prof_mark(c, "k_mcl_free_bits");
+    cmk_mcl_free_bits(st, c->map_image, n_cells, c->mcl_bits);
+    prof_mark(c, "k_mcl_compact");
+    cmk_mcl_compact(st, c->mcl_bits, n_words, n_cells, counts, list, words);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->mcl_host, words, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (c->mcl_host[CM_MCL_W_NCELLS] == 0) return fail(c, CM_BAD_ARG, "the map's image holds no free cell");
+    c->mcl_init = false;
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_init_uniform";
+    c->mcl_cur = 0;
+    prof_mark(c, "k_mcl_init_uniform");
+    cmk_mcl_init_uniform(st, g, cm_mcl_base(c->mcl_params.seed, c->mcl_gen++), list, words, c->mcl_parts[0]);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    c->mcl_init = true;
+    return CM_OK;
+}
+
+int map_mcl_predict(cm_ctx* c, const float v[6]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_predict";
+    c->prof_used = 0;
+    prof_mark(c, "k_mcl_predict");
+    cmk_mcl_predict(c->stream, mcl_move(c, v), c->mcl_params.n_particles, c->mcl_dirs, c->mcl_parts[c->mcl_cur]);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    collect_stage_times(c);
+    return CM_OK;
+}
+
+// Steps 6 to 11 (cm_kernels_mcl.hip; the semantics are in include/cloudmerge.h). Two clears, the field, the mark pass, the
+// compaction, the score, the best particle, the weights with their sums, the spread, the prefix sums with the resampling
+// decision, which is taken on the device, and the gather; then one copy of the info words back and one wait, the only host
+// round trip. The host learns from the words whether the particles now live in the other buffer. No allocation.
+int map_mcl_update(cm_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_mcl_params& q = c->mcl_params;
+    const CmMclDev g = mcl_dev(c);
+    const size_t n_cells = static_cast<size_t>(g.nx) * g.ny;
+    const uint32_t body_words = static_cast<uint32_t>((static_cast<uint64_t>(g.side) * g.side + 31u) / 32u);
+    const uint32_t r2 = c->mcl_radius * c->mcl_radius;
+    unsigned long long* const words = c->mcl_cum + g.n;
+    uint32_t* const counts = c->mcl_list;
+    uint32_t* const list = c->mcl_list + CM_MCL_ONE_BLOCK;
+    CmMclParticleDev* const src = c->mcl_parts[c->mcl_cur];
+    CmMclParticleDev* const dst = c->mcl_parts[c->mcl_cur ^ 1];
+    const uint64_t gen = c->mcl_gen++;
+    const unsigned long long base = cm_mcl_base(q.seed, gen);
+    const double beta = 1.0 / (255.0 * static_cast<double>(q.tau));
+    const double thr = static_cast<double>(q.resample_frac) * static_cast<double>(q.n_particles);
+    hipStream_t st = c->stream;
+    c->mcl_stale = "the weights are stale: the last cm_map_mcl_update failed";
+    c->prof_used = 0;
+    prof_mark(c, "mcl_clear");
+    HIP_TRY(c, hipMemsetAsync(c->mcl_bits, 0, static_cast<size_t>(body_words) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(words, 0, CM_MCL_WORDS * sizeof(unsigned long long), st));
+    prof_mark(c, "k_match_field");
+    cmk_match_field(st, c->cost_dist2, c->mcl_field + n_cells, r2, static_cast<uint32_t>(n_cells), c->mcl_field);
+    prof_mark(c, "k_mcl_mark");
+    cmk_mcl_mark(st, c->d_frame, g, c->frame_mask, c->mcl_bits, c->frame.n_tiles);
+    prof_mark(c, "k_mcl_compact");
+    cmk_mcl_compact(st, c->mcl_bits, body_words, q.max_beams, counts, list, words);
+    prof_mark(c, "k_mcl_score");
+    cmk_mcl_score(st, c->mcl_field, g, list, words, c->mcl_dirs, src, c->mcl_wts);
+    prof_mark(c, "k_mcl_best");
+    cmk_mcl_best(st, src, g.n, words);
+    prof_mark(c, "k_mcl_weights");
+    cmk_mcl_weights(st, src, g.n, beta, c->mcl_dirs, c->mcl_wts, words);
+    prof_mark(c, "k_mcl_spread");
+    cmk_mcl_spread(st, src, g.n, c->mcl_wts, words);
+    prof_mark(c, "k_mcl_resample");
+    cmk_mcl_resample(st, src, dst, g.n, c->mcl_wts, c->mcl_cum, cm_mcl_splitmix64(base ^ (1ull << 63)), thr,
+                     (q.flags & CM_MCL_RESAMPLE_ALWAYS) ? 1u : 0u, words);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->mcl_host, words, CM_MCL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    const unsigned long long* const h = c->mcl_host;
+    if (h[CM_MCL_W_BEST] >= g.n || h[CM_MCL_W_SW] < CM_MCL_WEIGHT_ONE || h[CM_MCL_W_SW2] == 0) return fail(c, CM_INTERNAL, "the info words of the update are not a result");
+    if (h[CM_MCL_W_RESAMPLED]) c->mcl_cur ^= 1;
+    cm_mcl_info& r = c->mcl_info;
+    std::memset(&r, 0, sizeof r);
+    r.n_particles = g.n;
+    r.n_cells = static_cast<uint32_t>(h[CM_MCL_W_NCELLS]);
+    r.stride = static_cast<uint32_t>(h[CM_MCL_W_STRIDE]);
+    r.n_beams = static_cast<uint32_t>(h[CM_MCL_W_NBEAMS]);
+    r.gen = gen;
+    r.resampled = static_cast<uint32_t>(h[CM_MCL_W_RESAMPLED]);
+    r.best = static_cast<uint32_t>(h[CM_MCL_W_BEST]);
+    const uint32_t bx = static_cast<uint32_t>(h[CM_MCL_W_BEST_X]), by = static_cast<uint32_t>(h[CM_MCL_W_BEST_Y]);
+    std::memcpy(&r.best_x, &bx, 4);
+    std::memcpy(&r.best_y, &by, 4);
+    r.best_h = static_cast<uint32_t>(h[CM_MCL_W_BEST_H]);
+    r.sum_w = h[CM_MCL_W_SW];
+    r.sum_w2 = h[CM_MCL_W_SW2];
+    r.sum_wqx = static_cast<int64_t>(h[CM_MCL_W_SWQX]);
+    r.sum_wqy = static_cast<int64_t>(h[CM_MCL_W_SWQY]);
+    r.sum_wc = static_cast<int64_t>(h[CM_MCL_W_SWC]);
+    r.sum_ws = static_cast<int64_t>(h[CM_MCL_W_SWS]);
+    r.sum_wdxx = static_cast<int64_t>(h[CM_MCL_W_SWDXX]);
+    r.sum_wdyy = static_cast<int64_t>(h[CM_MCL_W_SWDYY]);
+    r.sum_wdxy = static_cast<int64_t>(h[CM_MCL_W_SWDXY]);
+    const double sw = static_cast<double>(r.sum_w);
+    r.n_eff = (sw * sw) / static_cast<double>(r.sum_w2);
+    r.mean_x = (static_cast<double>(r.sum_wqx) / sw) / 1024.0;
+    r.mean_y = (static_cast<double>(r.sum_wqy) / sw) / 1024.0;
+    r.mean_yaw = std::atan2(static_cast<double>(r.sum_ws), static_cast<double>(r.sum_wc));
+    const double den = sw * 1048576.0;
+    r.var_xx = static_cast<double>(r.sum_wdxx) / den;
+    r.var_yy = static_cast<double>(r.sum_wdyy) / den;
+    r.var_xy = static_cast<double>(r.sum_wdxy) / den;
+    c->mcl_serial = c->frame_serial;
+    c->mcl_stale = nullptr;
+    return CM_OK;
+}
+
+// A recorded state table into the map: the table into the current state buffer, the image by step 8, the anchor; the layers
+// behind go stale exactly as after an integration, and the frame at rest counts as not yet integrated.
+int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_map_params& q = c->map_params;
+    const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(c->map_state[c->map_cur], src, n_cells * sizeof(cm_map_cell), hipMemcpyHostToDevice, st));
+    cmk_map_image(st, c->map_state[c->map_cur], static_cast<uint32_t>(n_cells), q.l_free, q.l_occ, c->map_image);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(st));
+    c->map_info.anchor[0] = anchor[0];
+    c->map_info.anchor[1] = anchor[1];
+    c->map_info.n_frames = 1;
+    c->map_info.sensors_cast = 0;
+    c->map_serial = 0;
+    c->cost_fresh = false;
+    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_load";
+    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_load";
+    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_load";
+    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_load";
+    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_load";
+    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_load";
     return CM_OK;
 }
 

@@ -366,6 +366,27 @@ struct cm_ctx {
     DevBuf<float> msearch_q;             // six floats per candidate
     PinnedBuf<uint32_t> msearch_host;    // CM_MSEARCH_WORDS words read back, 256 counts, CM_MSEARCH_WORDS words an evaluate uploads, then the candidates' floats
 
+    // Localisation layer behind the cost layer (cm_kernels_mcl.hip): a particle filter against the matching layer's field,
+    // configured by cm_map_mcl_configure and driven by cm_map_mcl_init_* / _predict / _update from the frame at rest, map_info,
+    // map_image and cost_dist2. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
+    bool mcl_on = false;
+    bool mcl_init = false;               // the particles are initialised (an init call since the configure call)
+    const char* mcl_stale = nullptr;     // why weights and info are not those of the current tables and particles; nullptr: they are
+    uint64_t mcl_serial = 0;             // the frame of the last update: a merge since then makes them stale too
+    uint64_t mcl_gen = 0;                // init, predict and update calls since the configure call
+    cm_mcl_params mcl_params{};
+    uint32_t mcl_radius = 0;             // R: the field table has R * R + 1 entries
+    cm_mcl_info mcl_info{};
+    DevBuf<CmMclParticleDev> mcl_parts[2];      // n_particles each: the resampling gathers from one into the other
+    int mcl_cur = 0;                     // which of the two holds the particles
+    DevBuf<CmMclWeightDev> mcl_wts;      // n_particles records
+    DevBuf<unsigned long long> mcl_cum;  // n_particles prefix sums, then CM_MCL_WORDS info words
+    DevBuf<unsigned char> mcl_field;     // nx * ny bytes L, then the field table
+    DevBuf<uint32_t> mcl_bits;           // one bitmap: the body cells ((2 range_cells + 1)^2 bits) or the free cells (nx * ny bits)
+    DevBuf<uint32_t> mcl_list;           // CM_MCL_ONE_BLOCK block counts, then max(max_beams, nx * ny) list entries
+    DevBuf<float> mcl_dirs;              // the heading table (2 * CM_TRAJ_HEADINGS floats)
+    PinnedBuf<unsigned long long> mcl_host;     // CM_MCL_WORDS words read back
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -506,6 +527,17 @@ int map_frontier_update(cm_ctx* c);
 // match_result for a prior that cm_map_match_evaluate has checked.
 int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R);
 int map_match_evaluate(cm_ctx* c, const float pose[12]);
+// The localisation layer behind the cost layer. map_mcl_configure: room for q's particles and beams over the map's window and
+// the field table at radius R cells (nullptr: the buffers go). The other four run a call that cm_api.cpp has checked: v holds
+// the centre or the motion (x, y, yaw) and its three standard deviations. map_mcl_init_uniform refuses an image without a
+// free cell itself (it learns the number from the device).
+int map_mcl_configure(cm_ctx* c, const cm_mcl_params* q, uint32_t R);
+int map_mcl_init_pose(cm_ctx* c, const float v[6]);
+int map_mcl_init_uniform(cm_ctx* c);
+int map_mcl_predict(cm_ctx* c, const float v[6]);
+int map_mcl_update(cm_ctx* c);
+// A recorded state table into the configured map (cm_map_load has checked it): state, image, anchor, staleness.
+int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]);
 // The search layer behind the cost layer. map_msearch_configure: room for q over the map's window, the field table at radius
 // R cells built and uploaded, the roots built and uploaded (nullptr: the buffers go). map_msearch_evaluate: msearch_result and
 // msearch_info for a prior that cm_map_match_search has checked; CM_CAPACITY leaves the result stale and the info written.

@@ -492,3 +492,67 @@ struct CmMSearchDev {
     uint32_t wx, wy;
     uint32_t max_cells;                // room of one candidate's cell list
 };
+
+// Localisation layer behind the cost layer (cm_kernels_mcl.hip): a particle filter against the matching layer's likelihood
+// field. k_mcl_score gives one wave one particle at a time, CM_MCL_WAVES waves to a workgroup, the grid sized to the device
+// with a stride over the particles; the beams are staged once per workgroup in LDS as float2, and a lane issues the field
+// loads of CM_MCL_BEAM_BATCH beams before it adds any. The cell passes and the particle passes run CM_MCL_BLOCK threads per
+// workgroup, the scans of block counts, the best particle and the prefix sum of the weights are one workgroup of
+// CM_MCL_ONE_BLOCK threads. The layer's CM_MCL_WORDS 64-bit info words on the device, zero before an update: the distinct
+// body cells, the stride and the beams of the ordered compaction (the free cells of cm_map_mcl_init_uniform land in the same
+// three), the largest acc, the best particle with its x, y (bit patterns) and h, the nine sums of step 9 and the resampling
+// decision.
+#ifndef CM_MCL_BEAM_BATCH
+#define CM_MCL_BEAM_BATCH 4
+#endif
+#define CM_MCL_WAVES 4
+#define CM_MCL_BLOCK 256
+#define CM_MCL_ONE_BLOCK 1024
+#define CM_MCL_MAX_PARTICLES_DEV 65536u
+#define CM_MCL_MAX_BEAMS_DEV 8192u
+#define CM_MCL_MAX_RANGE_DEV 1024u
+#define CM_MCL_W_NCELLS 0
+#define CM_MCL_W_STRIDE 1
+#define CM_MCL_W_NBEAMS 2
+#define CM_MCL_W_AMAX 3
+#define CM_MCL_W_BEST 4
+#define CM_MCL_W_BEST_X 5
+#define CM_MCL_W_BEST_Y 6
+#define CM_MCL_W_BEST_H 7
+#define CM_MCL_W_SW 8
+#define CM_MCL_W_SW2 9
+#define CM_MCL_W_SWQX 10
+#define CM_MCL_W_SWQY 11
+#define CM_MCL_W_SWC 12
+#define CM_MCL_W_SWS 13
+#define CM_MCL_W_SWDXX 14
+#define CM_MCL_W_SWDYY 15
+#define CM_MCL_W_SWDXY 16
+#define CM_MCL_W_RESAMPLED 17
+#define CM_MCL_WORDS 24
+struct CmMclDev {
+    float inv, cell;                   // 1.0f / cell, and the map's cell
+    int32_t ax, ay;                    // the map's anchor
+    uint32_t nx, ny;
+    float z_min, z_max;
+    uint32_t n;                        // particles
+    uint32_t max_beams;
+    uint32_t range;                    // range_cells: the body bitmap is side x side bits, side = 2 * range + 1
+    uint32_t side;
+};
+struct CmMclParticleDev {              // cm_mcl_particle
+    float x, y;
+    uint32_t h, parent;
+    unsigned long long acc;
+};
+struct CmMclWeightDev {                // cm_mcl_weight
+    uint32_t score, weight;
+};
+// What one init or predict call adds to a particle: the centre (init) or the motion (predict), the three noise scales sc and
+// the base of the call's draws.
+struct CmMclMoveDev {
+    float a, b;                        // x0, y0 or d_fwd, d_left
+    double yaw;                        // yaw0 or d_yaw, widened
+    float sc_a, sc_b, sc_yaw;
+    unsigned long long base;
+};

@@ -294,6 +294,33 @@ void cmk_match_mark(hipStream_t s, const CmFrameDev* fd, const CmMatchDev& g, co
 void cmk_match_score(hipStream_t s, const unsigned char* field, const uint32_t* bits, const CmMatchDev& g, uint32_t* vol);
 void cmk_match_best(hipStream_t s, const uint32_t* vol, const uint32_t* bits, const CmMatchDev& g, uint32_t* info);
 
+// ---- localisation layer behind the cost layer (cm_kernels_mcl.hip) -------------------------------------------------------------------
+// parts: g.n particles; wts: g.n records; words: the CM_MCL_WORDS info words. bits: a bitmap of n_words words (the body bitmap,
+// zero before cmk_mcl_mark, or the free-cell bitmap cmk_mcl_free_bits writes); counts: one word per CM_MCL_BLOCK bitmap words, at
+// most CM_MCL_ONE_BLOCK of them. cmk_mcl_compact is the ordered compaction of a bitmap, three launches: the set bits in
+// ascending order, every stride-th of them into list (at most max_out, the stride chosen on the device), their numbers into
+// words[CM_MCL_W_NCELLS .. CM_MCL_W_NBEAMS]. cmk_mcl_score reads the beams from list and words. dirs: the heading table. cum: g.n
+// 64-bit prefix sums. cmk_mcl_resample writes the decision into words and, where it falls, the new particles into dst;
+// otherwise it sets src's parents. r_draw: splitmix64(base ^ 1 << 63). thr: resample_frac * n_particles, always: the flag.
+void cmk_mcl_mark(hipStream_t s, const CmFrameDev* fd, const CmMclDev& g, const unsigned char* keep, uint32_t* bits, uint32_t n_tiles);
+void cmk_mcl_free_bits(hipStream_t s, const void* image, uint32_t n_cells, uint32_t* bits);
+void cmk_mcl_compact(hipStream_t s, const uint32_t* bits, uint32_t n_words, uint32_t max_out, uint32_t* counts, uint32_t* list,
+                     unsigned long long* words);
+void cmk_mcl_init_pose(hipStream_t s, const CmMclMoveDev& m, uint32_t n, CmMclParticleDev* parts);
+void cmk_mcl_init_uniform(hipStream_t s, const CmMclDev& g, unsigned long long base, const uint32_t* list, const unsigned long long* words,
+                          CmMclParticleDev* parts);
+void cmk_mcl_predict(hipStream_t s, const CmMclMoveDev& m, uint32_t n, const float* dirs, CmMclParticleDev* parts);
+void cmk_mcl_score(hipStream_t s, const unsigned char* field, const CmMclDev& g, const uint32_t* list, const unsigned long long* words,
+                   const float* dirs, CmMclParticleDev* parts, CmMclWeightDev* wts);
+void cmk_mcl_best(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, unsigned long long* words);
+void cmk_mcl_weights(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, double beta, const float* dirs, CmMclWeightDev* wts,
+                     unsigned long long* words);
+void cmk_mcl_spread(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, const CmMclWeightDev* wts, unsigned long long* words);
+void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, uint32_t n, const CmMclWeightDev* wts, unsigned long long* cum,
+                      unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words);
+// The image of a state table (the map's step 8), for cm_map_load: (logodds, n_obs) per cell into one byte per cell.
+void cmk_map_image(hipStream_t s, const void* state, uint32_t n_cells, int l_free, int l_occ, void* image);
+
 // ---- frontier layer behind the plan layer (cm_kernels_front.hip) -------------------------------------------------------------------
 // image, cost, pot: the map's image, the cost and the plan layer's tables. labels: a word per cell (parents, then roots, then
 // frontier numbers). size: a word per cell (a root's cell count, then its number). counts: g.n_blocks words. info:

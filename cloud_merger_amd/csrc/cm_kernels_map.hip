@@ -105,7 +105,25 @@ __global__ __launch_bounds__(256) void k_map_update(const uint2* __restrict__ pr
     image[c] = v;
 }
 
+// Step 8 alone, for a state table that was loaded (cm_map_load): k_map_update's last three lines.
+__global__ __launch_bounds__(256) void k_map_image(const uint2* __restrict__ state, uint32_t n_cells, int l_free, int l_occ,
+                                                   signed char* __restrict__ image) {
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= n_cells) return;
+    const uint2 st = state[c];
+    const int logodds = static_cast<int>(st.x);
+    signed char v = -1;
+    if (st.y) v = logodds >= l_occ ? 100 : logodds <= l_free ? 0 : -1;
+    image[c] = v;
+}
+
 }  // namespace
+
+void cmk_map_image(hipStream_t s, const void* state, uint32_t n_cells, int l_free, int l_occ, void* image) {
+    if (n_cells)
+        hipLaunchKernelGGL(k_map_image, dim3((n_cells + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint2*>(state), n_cells, l_free, l_occ,
+                           reinterpret_cast<signed char*>(image));
+}
 
 void cmk_map_mark(hipStream_t s, const CmFrameDev* fd, const CmMapDev& g, const unsigned char* keep, const unsigned char* ground,
                   uint32_t* bits, uint32_t words, uint32_t n_sensors, uint32_t n_tiles) {

@@ -1,0 +1,513 @@
+// cm_kernels_mcl.hip — the localisation layer behind the cost layer: a particle filter of the vehicle's pose against the
+// likelihood field of the occupancy map (amcl's Monte Carlo localisation against a likelihood field), for gfx950 (wave64).
+//
+// Computed on request (cm_map_mcl_init_pose / _init_uniform / _predict / _update) from the frame's clouds in place exactly as
+// k_match_mark reads them, the map's info and image and the cost layer's dist2; it writes buffers of the localisation layer
+// only (the semantics are in include/cloudmerge.h). Scores and weights are integers, positions are fp32 with
+// every operation rounded on its own (the _rn intrinsics: nothing contracts), the noise is an integer sum of fields of a
+// counter-based draw (cm_mcl_math.hpp) and the resampling is integer systematic resampling, so neither the lanes, the order of
+// the atomics nor the grid can show in a table.
+//
+//   k_mcl_mark       one workgroup per tile of 4096 raw points: k_match_mark's front end and masks without candidates. A
+//                    counted point's body cell (floorf(x * inv), floorf(y * inv)) within range_cells sets its bit in the body
+//                    bitmap, side x side bits in (b_y, b_x) order, the atomicOr skipped where a plain read shows the bit.
+//   k_mcl_free_bits  one thread per word: the bitmap of the window cells whose image byte is 0.
+//   k_mcl_count, k_mcl_scan, k_mcl_emit   the ordered compaction of a bitmap by a popcount scan: per CM_MCL_BLOCK words their
+//                    set bits, the exclusive scan of those counts in one workgroup, which also picks the stride
+//                    max(1, ceil(n / max_out)), then every set bit's rank from its block's base and a scan inside the block;
+//                    rank r with r % stride == 0 writes its bit index to list[r / stride]. It serves the beams (with their
+//                    stride) and the free cells of cm_map_mcl_init_uniform (stride 1).
+//   k_mcl_init_pose, k_mcl_init_uniform, k_mcl_predict   one thread per particle.
+//   k_mcl_score      one wave per particle, CM_MCL_WAVES waves per workgroup, the grid sized to the device with a stride over
+//                    the particles. The workgroup stages the beams once in LDS as float2 (the centre of a list entry's body
+//                    cell). A lane takes beams lane, lane + 64, ... and issues the field loads of CM_MCL_BEAM_BATCH of them
+//                    before it adds any: the loads do not depend on one another. An integer wave reduction; lane 0 stores S_p
+//                    and the new acc_p by plain vector stores.
+//   k_mcl_best       one workgroup: the largest acc, ties to the lowest index; the best particle's x, y, h.
+//   k_mcl_weights    one thread per particle: W_p through cm_exp_neg (cm_ndt_math.hpp with the _rn macros), and the six sums
+//                    of step 9 combined per wave by shuffles and per workgroup in LDS before one 64-bit integer atomicAdd per
+//                    sum and workgroup.
+//   k_mcl_spread     the same shape for the three spread sums about the integer means.
+//   k_mcl_cum        one workgroup: the inclusive prefix sum of W in particle order, and the resampling decision, taken here
+//                    on the device from the sums: n_eff in double with the host's three operations.
+//   k_mcl_gather     one thread per new particle: a binary search in the prefix sums, the copy into the second buffer; without
+//                    resampling it sets the parents of the first.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "cm_common.hpp"
+#include "cm_device.h"
+#include "cm_kernels.h"
+#include "cm_search.hpp"
+
+// the rounded fp64 operations of cm_ndt_math.hpp, as cm_kernels_ndt.hip sets them
+#define CM_NDT_FN __device__ __forceinline__
+#define CM_NDT_MUL(a, b) __dmul_rn((a), (b))
+#define CM_NDT_ADD(a, b) __dadd_rn((a), (b))
+#define CM_NDT_SUB(a, b) __dsub_rn((a), (b))
+#include "cm_ndt_math.hpp"
+#define CM_MCL_FN __device__ __forceinline__
+#include "cm_mcl_math.hpp"
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr double kTurn = 4294967296.0 / 6.283185307179586;     // K: binary angle units per radian (the rollout layer's)
+
+// The rollout layer's step 2: the table entry of a heading.
+__device__ __forceinline__ uint32_t heading_entry(uint32_t h) { return ((h + 0x80000u) >> 20) & (CM_TRAJ_HEADINGS_DEV - 1u); }
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+    for (int m = 1; m < 64; m <<= 1) v += static_cast<uint32_t>(__shfl_xor(static_cast<int>(v), m));
+    return v;
+}
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// Inclusive scan of v over the WAVES * 64 threads of a workgroup (all of them call it); s_w: WAVES words of LDS.
+template <int WAVES, class T>
+__device__ __forceinline__ T block_scan(T v, T* s_w) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(v, d);
+        if (lane >= static_cast<uint32_t>(d)) v += o;
+    }
+    __syncthreads();                                   // (s_w may still be read from an earlier call)
+    if (lane == 63u) s_w[wave] = v;
+    __syncthreads();
+    T before = 0;
+    for (uint32_t w = 0; w < wave; ++w) before += s_w[w];
+    return v + before;
+}
+
+// ---- the front end and the ordered compaction ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(CM_BLOCK) void k_mcl_mark(const CmFrameDev* __restrict__ fd, CmMclDev g, const unsigned char* __restrict__ keep,
+                                                       uint32_t* __restrict__ bits) {
+    const uint32_t tile = blockIdx.x;
+    const uint32_t s = sensor_of_tile(fd, tile);
+    const CmSensorDev& sd = fd->s[s];
+    const uint32_t first = tile * CM_TILE - sd.base;
+    const int R = static_cast<int>(g.range);
+    for (int r = 0; r < CM_ITEMS; ++r) {
+        const uint32_t i = first + r * CM_BLOCK + threadIdx.x;
+        if (i >= sd.n) continue;
+        const Pt p = load_point(sd.data, sd.layout, sd.point_step, sd.off_x, sd.off_y, sd.off_z, sd.off_i, i);
+        float x, y, z;
+        xf_point(sd.m, p, x, y, z);
+        if (!point_valid(x, y, z, fd->crop_enable, fd->crop_min, fd->crop_max)) continue;
+        const uint32_t slot = tile * CM_TILE + r * CM_BLOCK + threadIdx.x;
+        if (keep && !keep[slot]) continue;             // (a counted point of A)
+        if (!(g.z_min <= z && z <= g.z_max)) continue;
+        int bx, by;
+        if (!world_axis(x, g.inv, &bx) || !world_axis(y, g.inv, &by)) continue;
+        if (bx < -R || bx > R || by < -R || by > R) continue;
+        const uint32_t cell = static_cast<uint32_t>(bx + R) + static_cast<uint32_t>(by + R) * g.side;      // (< side * side)
+        const uint32_t b = 1u << (cell & 31u);
+        uint32_t* w = bits + (cell >> 5);
+        if (!(ld_agent(w) & b)) atomicOr(w, b);
+    }
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_free_bits(const signed char* __restrict__ image, uint32_t n_cells, uint32_t n_words,
+                                                                uint32_t* __restrict__ bits) {
+    const uint32_t w = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (w >= n_words) return;
+    uint32_t m = 0u;
+    for (uint32_t b = 0; b < 32u; ++b) {
+        const uint32_t c = w * 32u + b;
+        if (c < n_cells && image[c] == 0) m |= 1u << b;
+    }
+    bits[w] = m;
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_count(const uint32_t* __restrict__ bits, uint32_t n_words, uint32_t* __restrict__ counts) {
+    __shared__ uint32_t s_w[CM_MCL_BLOCK / 64];
+    const uint32_t w = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    const uint32_t v = wave_sum(w < n_words ? static_cast<uint32_t>(__popc(bits[w])) : 0u);
+    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t t = 0u;
+        for (uint32_t k = 0; k < CM_MCL_BLOCK / 64; ++k) t += s_w[k];
+        counts[blockIdx.x] = t;
+    }
+}
+
+// n_blocks <= CM_MCL_ONE_BLOCK: one count per thread.
+__global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_scan(uint32_t* __restrict__ counts, uint32_t n_blocks, uint32_t max_out, u64* __restrict__ words) {
+    __shared__ uint32_t s_w[CM_MCL_ONE_BLOCK / 64];
+    const uint32_t t = threadIdx.x;
+    const uint32_t v = t < n_blocks ? counts[t] : 0u;
+    const uint32_t incl = block_scan<CM_MCL_ONE_BLOCK / 64>(v, s_w);
+    if (t < n_blocks) counts[t] = incl - v;
+    if (t == CM_MCL_ONE_BLOCK - 1u) {
+        const uint32_t n = incl;
+        const uint32_t stride = n > max_out ? (n + max_out - 1u) / max_out : 1u;
+        words[CM_MCL_W_NCELLS] = n;
+        words[CM_MCL_W_STRIDE] = stride;
+        words[CM_MCL_W_NBEAMS] = (n + stride - 1u) / stride;
+    }
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_emit(const uint32_t* __restrict__ bits, uint32_t n_words, const uint32_t* __restrict__ counts,
+                                                           const u64* __restrict__ words, uint32_t max_out, uint32_t* __restrict__ list) {
+    __shared__ uint32_t s_w[CM_MCL_BLOCK / 64];
+    const uint32_t w = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    uint32_t m = w < n_words ? bits[w] : 0u;
+    const uint32_t v = static_cast<uint32_t>(__popc(m));
+    uint32_t r = counts[blockIdx.x] + block_scan<CM_MCL_BLOCK / 64>(v, s_w) - v;
+    const uint32_t stride = static_cast<uint32_t>(words[CM_MCL_W_STRIDE]);
+    while (m) {
+        const uint32_t b = static_cast<uint32_t>(__ffs(static_cast<int>(m))) - 1u;
+        m &= m - 1u;
+        if (r % stride == 0u) {
+            const uint32_t o = r / stride;
+            if (o < max_out) list[o] = w * 32u + b;
+        }
+        ++r;
+    }
+}
+
+// ---- the particles -------------------------------------------------------------------------------------------------------------
+// The low 32 bits of (int64)rint(((double)yaw + (double)nz) * K): steps 3 and 5.
+__device__ __forceinline__ uint32_t turn_of(double yaw, float nz) {
+    return static_cast<uint32_t>(static_cast<long long>(rint(__dmul_rn(__dadd_rn(yaw, static_cast<double>(nz)), kTurn))));
+}
+__device__ __forceinline__ float noise_of(u64 base, uint32_t p, uint32_t i, float sc) {
+    return __fmul_rn(static_cast<float>(cm_mcl_noise(cm_mcl_draw(base, p, i))), sc);
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_pose(CmMclMoveDev m, uint32_t n, CmMclParticleDev* __restrict__ parts) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    CmMclParticleDev q;
+    q.x = __fadd_rn(m.a, noise_of(m.base, p, 0u, m.sc_a));
+    q.y = __fadd_rn(m.b, noise_of(m.base, p, 1u, m.sc_b));
+    q.h = turn_of(m.yaw, noise_of(m.base, p, 2u, m.sc_yaw));
+    q.parent = p;
+    q.acc = 0ull;
+    parts[p] = q;
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_uniform(CmMclDev g, u64 base, const uint32_t* __restrict__ list, const u64* __restrict__ words,
+                                                                   CmMclParticleDev* __restrict__ parts) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (p >= g.n) return;
+    const u64 n_free = words[CM_MCL_W_NCELLS];         // (>= 1: the host looked)
+    const uint32_t c = list[__umul64hi(cm_mcl_draw(base, p, 0u), n_free)];
+    const int ix = static_cast<int>(c % g.nx), iy = static_cast<int>(c / g.nx);
+    const float ux = __fmul_rn(static_cast<float>(cm_mcl_draw(base, p, 1u) >> 40), 0x1p-24f);
+    const float uy = __fmul_rn(static_cast<float>(cm_mcl_draw(base, p, 2u) >> 40), 0x1p-24f);
+    CmMclParticleDev q;
+    q.x = __fmul_rn(__fadd_rn(static_cast<float>(g.ax + ix), ux), g.cell);
+    q.y = __fmul_rn(__fadd_rn(static_cast<float>(g.ay + iy), uy), g.cell);
+    q.h = static_cast<uint32_t>(cm_mcl_draw(base, p, 3u) >> 32);
+    q.parent = p;
+    q.acc = 0ull;
+    parts[p] = q;
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_predict(CmMclMoveDev m, uint32_t n, const float2* __restrict__ dirs,
+                                                              CmMclParticleDev* __restrict__ parts) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (p >= n) return;
+    CmMclParticleDev q = parts[p];
+    const float2 e = dirs[heading_entry(q.h)];
+    const float a = __fadd_rn(m.a, noise_of(m.base, p, 0u, m.sc_a));
+    const float b = __fadd_rn(m.b, noise_of(m.base, p, 1u, m.sc_b));
+    q.x = __fsub_rn(__fadd_rn(q.x, __fmul_rn(e.x, a)), __fmul_rn(e.y, b));
+    q.y = __fadd_rn(__fadd_rn(q.y, __fmul_rn(e.y, a)), __fmul_rn(e.x, b));
+    q.h += turn_of(m.yaw, noise_of(m.base, p, 2u, m.sc_yaw));
+    parts[p] = q;
+}
+
+// ---- the score -----------------------------------------------------------------------------------------------------------------
+// Dynamic LDS: g.max_beams float2.
+__global__ __launch_bounds__(CM_MCL_WAVES * 64) void k_mcl_score(const unsigned char* __restrict__ field, CmMclDev g, const uint32_t* __restrict__ list,
+                                                                 const u64* __restrict__ words, const float2* __restrict__ dirs,
+                                                                 CmMclParticleDev* __restrict__ parts, CmMclWeightDev* __restrict__ wts) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    float2* const s_beam = reinterpret_cast<float2*>(s_mem);
+    const uint32_t n_words = static_cast<uint32_t>(words[CM_MCL_W_NBEAMS]);
+    const uint32_t n_beams = n_words < g.max_beams ? n_words : g.max_beams;       // (it is at most max_beams: the room of s_beam)
+    for (uint32_t i = threadIdx.x; i < n_beams; i += CM_MCL_WAVES * 64) {
+        const uint32_t c = list[i];
+        const int bx = static_cast<int>(c % g.side) - static_cast<int>(g.range), by = static_cast<int>(c / g.side) - static_cast<int>(g.range);
+        s_beam[i] = make_float2(__fmul_rn(__fadd_rn(static_cast<float>(bx), 0.5f), g.cell), __fmul_rn(__fadd_rn(static_cast<float>(by), 0.5f), g.cell));
+    }
+    __syncthreads();                                   // (the only barrier: the waves part ways below)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    for (uint32_t p = blockIdx.x * CM_MCL_WAVES + wave; p < g.n; p += gridDim.x * CM_MCL_WAVES) {
+        const CmMclParticleDev q = parts[p];
+        const float2 e = dirs[heading_entry(q.h)];
+        uint32_t sum = 0u;
+        for (uint32_t b0 = lane; b0 < n_beams; b0 += 64u * CM_MCL_BEAM_BATCH) {
+            uint32_t v[CM_MCL_BEAM_BATCH];
+#pragma unroll
+            for (int k = 0; k < CM_MCL_BEAM_BATCH; ++k) {
+                const uint32_t b = b0 + 64u * static_cast<uint32_t>(k);
+                v[k] = 0u;
+                if (b < n_beams) {
+                    const float2 f = s_beam[b];
+                    const float wx = __fsub_rn(__fadd_rn(q.x, __fmul_rn(e.x, f.x)), __fmul_rn(e.y, f.y));
+                    const float wy = __fadd_rn(__fadd_rn(q.y, __fmul_rn(e.y, f.x)), __fmul_rn(e.x, f.y));
+                    int gx = 0, gy = 0;
+                    const bool exists = world_axis(wx, g.inv, &gx) & world_axis(wy, g.inv, &gy);
+                    // (|gx| < 2^30 and |ax| < 2^30 + 2^21: the wrapped difference is below nx only where the true one is)
+                    const uint32_t ix = static_cast<uint32_t>(gx) - static_cast<uint32_t>(g.ax), iy = static_cast<uint32_t>(gy) - static_cast<uint32_t>(g.ay);
+                    if (exists && ix < g.nx && iy < g.ny) v[k] = field[iy * g.nx + ix];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < CM_MCL_BEAM_BATCH; ++k) sum += v[k];
+        }
+        sum = wave_sum(sum);
+        if (lane == 0u) {
+            wts[p].score = sum;
+            parts[p].acc = q.acc + sum;
+        }
+    }
+}
+
+__global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_best(const CmMclParticleDev* __restrict__ parts, uint32_t n, u64* __restrict__ words) {
+    __shared__ u64 s_acc[CM_MCL_ONE_BLOCK / 64];
+    __shared__ uint32_t s_index[CM_MCL_ONE_BLOCK / 64];
+    u64 acc = 0ull;
+    uint32_t index = 0xFFFFFFFFu;
+    for (uint32_t i = threadIdx.x; i < n; i += CM_MCL_ONE_BLOCK) {        // (ascending i: a tie keeps the lower index)
+        const u64 v = parts[i].acc;
+        if (index == 0xFFFFFFFFu || v > acc) {
+            acc = v;
+            index = i;
+        }
+    }
+    const auto fold = [&](u64 oa, uint32_t oi) {
+        if (oi != 0xFFFFFFFFu && (index == 0xFFFFFFFFu || oa > acc || (oa == acc && oi < index))) {
+            acc = oa;
+            index = oi;
+        }
+    };
+    for (int m = 1; m < 64; m <<= 1) fold(__shfl_xor(acc, m), static_cast<uint32_t>(__shfl_xor(static_cast<int>(index), m)));
+    if ((threadIdx.x & 63u) == 0u) {
+        s_acc[threadIdx.x >> 6] = acc;
+        s_index[threadIdx.x >> 6] = index;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        for (uint32_t w = 1; w < CM_MCL_ONE_BLOCK / 64; ++w) fold(s_acc[w], s_index[w]);
+        const CmMclParticleDev q = parts[index];       // (n >= 1: there is one)
+        words[CM_MCL_W_AMAX] = acc;
+        words[CM_MCL_W_BEST] = index;
+        words[CM_MCL_W_BEST_X] = __builtin_bit_cast(uint32_t, q.x);
+        words[CM_MCL_W_BEST_Y] = __builtin_bit_cast(uint32_t, q.y);
+        words[CM_MCL_W_BEST_H] = q.h;
+    }
+}
+
+// Step 9's q(v): clamp(llrint(v * 1024), -2^30, 2^30), 0 for a v that is not finite. The clamp comes first, in double: the
+// limits are integers and rounding is monotone, so the result is the same and no conversion overflows.
+__device__ __forceinline__ long long quant_of(float v) {
+    if (!finite_f32(v)) return 0;
+    double x = __dmul_rn(static_cast<double>(v), 1024.0);
+    x = x < -1073741824.0 ? -1073741824.0 : x > 1073741824.0 ? 1073741824.0 : x;
+    return __double2ll_rn(x);
+}
+
+// floor(a / b) for 0 < b <= 2^32.
+__device__ __forceinline__ long long floor_div(long long a, u64 b) {
+    const long long d = static_cast<long long>(b);
+    long long q = a / d;
+    if (a % d < 0) --q;
+    return q;
+}
+
+// K sums of a workgroup of CM_MCL_BLOCK threads into words[first ...]: shuffles inside a wave, the wave sums through LDS, one
+// atomicAdd per non-zero sum (integers: the order cannot show).
+template <int K>
+__device__ __forceinline__ void block_add(u64 (&v)[K], u64* words, const int (&slot)[K]) {
+    __shared__ u64 s_sum[CM_MCL_BLOCK / 64][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+    if ((threadIdx.x & 63u) == 0u)
+        for (int k = 0; k < K; ++k) s_sum[threadIdx.x >> 6][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x < static_cast<uint32_t>(K)) {
+        u64 t = 0ull;
+        for (uint32_t w = 0; w < CM_MCL_BLOCK / 64; ++w) t += s_sum[w][threadIdx.x];
+        if (t) atomicAdd(words + slot[threadIdx.x], t);
+    }
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_weights(const CmMclParticleDev* __restrict__ parts, uint32_t n, double beta,
+                                                              const float2* __restrict__ dirs, CmMclWeightDev* __restrict__ wts, u64* __restrict__ words) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    u64 v[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    if (p < n) {
+        const CmMclParticleDev q = parts[p];
+        const u64 d = words[CM_MCL_W_AMAX] - q.acc;
+        const u64 w = static_cast<u64>(floor(__dmul_rn(65536.0, cm_exp_neg(__dmul_rn(__ull2double_rn(d), beta)))));
+        wts[p].weight = static_cast<uint32_t>(w);
+        const float2 e = dirs[heading_entry(q.h)];
+        const long long ci = static_cast<long long>(rintf(__fmul_rn(e.x, 32768.0f))), si = static_cast<long long>(rintf(__fmul_rn(e.y, 32768.0f)));
+        const long long sw = static_cast<long long>(w);
+        v[0] = w;
+        v[1] = w * w;
+        v[2] = static_cast<u64>(sw * quant_of(q.x));   // (signed sums wrap as two's complement: the total is exact, header)
+        v[3] = static_cast<u64>(sw * quant_of(q.y));
+        v[4] = static_cast<u64>(sw * ci);
+        v[5] = static_cast<u64>(sw * si);
+    }
+    const int slot[6] = {CM_MCL_W_SW, CM_MCL_W_SW2, CM_MCL_W_SWQX, CM_MCL_W_SWQY, CM_MCL_W_SWC, CM_MCL_W_SWS};
+    block_add<6>(v, words, slot);
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_spread(const CmMclParticleDev* __restrict__ parts, uint32_t n, const CmMclWeightDev* __restrict__ wts,
+                                                             u64* __restrict__ words) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    u64 v[3] = {0ull, 0ull, 0ull};
+    if (p < n) {
+        const u64 sum_w = words[CM_MCL_W_SW];          // (>= 65536: the best particle's weight)
+        const long long mx = floor_div(static_cast<long long>(words[CM_MCL_W_SWQX]), sum_w), my = floor_div(static_cast<long long>(words[CM_MCL_W_SWQY]), sum_w);
+        const auto clamp16 = [](long long d) { return d < -32768 ? -32768ll : d > 32767 ? 32767ll : d; };
+        const long long dx = clamp16(quant_of(parts[p].x) - mx), dy = clamp16(quant_of(parts[p].y) - my);
+        const long long w = wts[p].weight;
+        v[0] = static_cast<u64>(w * dx * dx);
+        v[1] = static_cast<u64>(w * dy * dy);
+        v[2] = static_cast<u64>(w * dx * dy);
+    }
+    const int slot[3] = {CM_MCL_W_SWDXX, CM_MCL_W_SWDYY, CM_MCL_W_SWDXY};
+    block_add<3>(v, words, slot);
+}
+
+// ---- resampling ----------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_cum(const CmMclWeightDev* __restrict__ wts, uint32_t n, double thr, uint32_t always,
+                                                              u64* __restrict__ cum, u64* __restrict__ words) {
+    __shared__ u64 s_w[CM_MCL_ONE_BLOCK / 64];
+    const uint32_t per = (n + CM_MCL_ONE_BLOCK - 1u) / CM_MCL_ONE_BLOCK;
+    const uint32_t lo = threadIdx.x * per < n ? threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
+    u64 own = 0ull;
+    for (uint32_t p = lo; p < hi; ++p) own += wts[p].weight;
+    u64 c = block_scan<CM_MCL_ONE_BLOCK / 64>(own, s_w) - own;
+    for (uint32_t p = lo; p < hi; ++p) {
+        c += wts[p].weight;
+        cum[p] = c;
+    }
+    if (threadIdx.x == 0u) {
+        const double sw = __ull2double_rn(words[CM_MCL_W_SW]), sw2 = __ull2double_rn(words[CM_MCL_W_SW2]);
+        const double n_eff = __ddiv_rn(__dmul_rn(sw, sw), sw2);
+        words[CM_MCL_W_RESAMPLED] = (always || n_eff < thr) ? 1ull : 0ull;
+    }
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_gather(CmMclParticleDev* __restrict__ src, CmMclParticleDev* __restrict__ dst, uint32_t n,
+                                                             const u64* __restrict__ cum, u64 r_draw, const u64* __restrict__ words) {
+    const uint32_t j = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (j >= n) return;
+    if (!words[CM_MCL_W_RESAMPLED]) {
+        src[j].parent = j;
+        return;
+    }
+    const u64 T = words[CM_MCL_W_SW];
+    const u64 t = (static_cast<u64>(j) * T + __umul64hi(r_draw, T)) / n;          // (< T = cum[n - 1]: there is a p)
+    uint32_t lo = 0u, hi = n - 1u;
+    while (lo < hi) {                                  // the smallest p with cum[p] > t
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (cum[mid] > t) hi = mid; else lo = mid + 1u;
+    }
+    const CmMclParticleDev q = src[lo];
+    CmMclParticleDev o;
+    o.x = q.x;
+    o.y = q.y;
+    o.h = q.h;
+    o.parent = lo;
+    o.acc = 0ull;
+    dst[j] = o;
+}
+
+bool mcl_ok(const CmMclDev& g) {
+    return g.nx >= 1 && g.ny >= 1 && static_cast<uint64_t>(g.nx) * g.ny <= (1u << 22) && g.n >= 1 && g.n <= CM_MCL_MAX_PARTICLES_DEV && g.max_beams >= 1 &&
+           g.max_beams <= CM_MCL_MAX_BEAMS_DEV && g.range >= 1 && g.range <= CM_MCL_MAX_RANGE_DEV && g.side == 2u * g.range + 1u;
+}
+
+// Workgroups of k_mcl_score: enough to fill the device a few times over, never more than the particles need.
+uint32_t score_grid(uint32_t n) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const uint32_t want = (n + CM_MCL_WAVES - 1) / CM_MCL_WAVES, cap = static_cast<uint32_t>(cus) * 8u;
+    return want < cap ? want : cap;
+}
+
+}  // namespace
+
+void cmk_mcl_mark(hipStream_t s, const CmFrameDev* fd, const CmMclDev& g, const unsigned char* keep, uint32_t* bits, uint32_t n_tiles) {
+    if (!mcl_ok(g)) return;
+    if (n_tiles) hipLaunchKernelGGL(k_mcl_mark, dim3(n_tiles), dim3(CM_BLOCK), 0, s, fd, g, keep, bits);
+}
+
+void cmk_mcl_free_bits(hipStream_t s, const void* image, uint32_t n_cells, uint32_t* bits) {
+    const uint32_t n_words = (n_cells + 31u) / 32u;
+    if (n_words)
+        hipLaunchKernelGGL(k_mcl_free_bits, dim3((n_words + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, static_cast<const signed char*>(image),
+                           n_cells, n_words, bits);
+}
+
+void cmk_mcl_compact(hipStream_t s, const uint32_t* bits, uint32_t n_words, uint32_t max_out, uint32_t* counts, uint32_t* list,
+                     unsigned long long* words) {
+    const uint32_t n_blocks = (n_words + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK;
+    if (n_blocks == 0 || n_blocks > CM_MCL_ONE_BLOCK || max_out == 0) return;
+    hipLaunchKernelGGL(k_mcl_count, dim3(n_blocks), dim3(CM_MCL_BLOCK), 0, s, bits, n_words, counts);
+    hipLaunchKernelGGL(k_mcl_scan, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, counts, n_blocks, max_out, words);
+    hipLaunchKernelGGL(k_mcl_emit, dim3(n_blocks), dim3(CM_MCL_BLOCK), 0, s, bits, n_words, counts, words, max_out, list);
+}
+
+void cmk_mcl_init_pose(hipStream_t s, const CmMclMoveDev& m, uint32_t n, CmMclParticleDev* parts) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_init_pose, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, m, n, parts);
+}
+
+void cmk_mcl_init_uniform(hipStream_t s, const CmMclDev& g, unsigned long long base, const uint32_t* list, const unsigned long long* words,
+                          CmMclParticleDev* parts) {
+    if (!mcl_ok(g)) return;
+    hipLaunchKernelGGL(k_mcl_init_uniform, dim3((g.n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, g, base, list, words, parts);
+}
+
+void cmk_mcl_predict(hipStream_t s, const CmMclMoveDev& m, uint32_t n, const float* dirs, CmMclParticleDev* parts) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_predict, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, m, n, reinterpret_cast<const float2*>(dirs), parts);
+}
+
+void cmk_mcl_score(hipStream_t s, const unsigned char* field, const CmMclDev& g, const uint32_t* list, const unsigned long long* words,
+                   const float* dirs, CmMclParticleDev* parts, CmMclWeightDev* wts) {
+    if (!mcl_ok(g)) return;
+    const size_t lds = static_cast<size_t>(g.max_beams) * sizeof(float2);          // (at most 64 KiB)
+    hipLaunchKernelGGL(k_mcl_score, dim3(score_grid(g.n)), dim3(CM_MCL_WAVES * 64), lds, s, field, g, list, words, reinterpret_cast<const float2*>(dirs),
+                       parts, wts);
+}
+
+void cmk_mcl_best(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, unsigned long long* words) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_best, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, parts, n, words);
+}
+
+void cmk_mcl_weights(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, double beta, const float* dirs, CmMclWeightDev* wts,
+                     unsigned long long* words) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_weights, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, n, beta,
+                       reinterpret_cast<const float2*>(dirs), wts, words);
+}
+
+void cmk_mcl_spread(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, const CmMclWeightDev* wts, unsigned long long* words) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_spread, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, n, wts, words);
+}
+
+void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, uint32_t n, const CmMclWeightDev* wts, unsigned long long* cum,
+                      unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words) {
+    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
+    hipLaunchKernelGGL(k_mcl_cum, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, wts, n, thr, always, cum, words);
+    hipLaunchKernelGGL(k_mcl_gather, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, src, dst, n, cum, r_draw, words);
+}

@@ -266,6 +266,31 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
         else if (key == "match_search_capacity") ok = read(is, c.match_search_max_nodes, c.match_search_max_cells) && c.match_search_max_nodes >= 1u &&
                                                       c.match_search_max_nodes <= CM_MATCH_SEARCH_MAX_NODES && c.match_search_max_cells >= 1u &&
                                                       c.match_search_max_cells <= CM_MATCH_SEARCH_MAX_NODES;
+        else if (key == "mcl") ok = read_flag(is, &c.mcl_enable);
+        else if (key == "mcl_particles") ok = read(is, c.mcl_particles) && c.mcl_particles >= 1u && c.mcl_particles <= CM_MCL_MAX_PARTICLES;
+        else if (key == "mcl_beams") ok = read(is, c.mcl_max_beams, c.mcl_range_cells) && c.mcl_max_beams >= 1u && c.mcl_max_beams <= CM_MCL_MAX_BEAMS &&
+                                          c.mcl_range_cells >= 1u && c.mcl_range_cells <= CM_MCL_MAX_RANGE_CELLS;
+        else if (key == "mcl_field") ok = read(is, c.mcl_sigma, c.mcl_max_dist) && std::isfinite(c.mcl_sigma) && c.mcl_sigma > 0.0f &&
+                                          std::isfinite(c.mcl_max_dist) && c.mcl_max_dist > 0.0f;
+        else if (key == "mcl_tau") ok = read(is, c.mcl_tau) && std::isfinite(c.mcl_tau) && c.mcl_tau > 0.0f;
+        else if (key == "mcl_resample") ok = read(is, c.mcl_resample_frac) && read_flag(is, &c.mcl_resample_always) && std::isfinite(c.mcl_resample_frac) &&
+                                             c.mcl_resample_frac >= 0.0f && c.mcl_resample_frac <= 1.0f;
+        else if (key == "mcl_seed") ok = read(is, c.mcl_seed);
+        else if (key == "mcl_init") {
+            std::string how;
+            ok = read(is, how) && (how == "pose" || how == "uniform");
+            if (ok && how == "pose") {
+                float* sd = c.mcl_init_sd;
+                ok = read(is, sd[0], sd[1], sd[2]);
+                for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(sd[k]) && sd[k] >= 0.0f && sd[k] <= 1024.0f;
+            }
+            if (ok) c.mcl_init_uniform = how == "uniform";
+        }
+        else if (key == "mcl_noise") {
+            float* sd = c.mcl_noise;
+            ok = read(is, sd[0], sd[1], sd[2]);
+            for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(sd[k]) && sd[k] >= 0.0f && sd[k] <= 1024.0f;
+        }
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -293,6 +318,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     if (c.sensors.empty() || c.sensors.size() > CM_MAX_SENSORS) { if (err) *err = "sensor count must be 1..16"; return false; }
     if (c.grid_raycast && !(c.grid_cell > 0.0f)) { if (err) *err = "grid_raycast needs grid_cell > 0"; return false; }
     if (c.match_enable && c.match_search_enable) { if (err) *err = "match and match_search exclude each other"; return false; }
+    if (c.mcl_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "mcl needs the cost layer (map and map_inflation)"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
     return true;
@@ -322,6 +348,10 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     }
     if (cfg_.grid_raycast && (!(cfg_.grid_cell > 0.0f) || cfg_.grid_min_pass == 0)) {
         error_ = "grid_raycast needs grid_cell > 0 and grid_min_pass >= 1";
+        return;
+    }
+    if (cfg_.mcl_enable && !(cfg_.map_cell > 0.0f && cfg_.map_inflation_radius > 0.0f)) {
+        error_ = "mcl needs the cost layer (map and map_inflation)";
         return;
     }
     uint32_t mask = 0;
@@ -361,6 +391,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                                                 cfg_.match_search_wy, cfg_.match_search_depth, cfg_.match_search_max_nodes, cfg_.match_search_max_cells,
                                                 cfg_.match_subcell ? CM_MATCH_SUBCELL : 0u};
                 if (cm_map_match_search_configure(ctx_, &sp) != CM_OK) refuse("cm_map_match_search_configure");
+            }
+            if (ctx_ && cfg_.mcl_enable) {                         // the localisation layer behind the cost layer
+                const cm_mcl_params lp{cfg_.mcl_particles, cfg_.mcl_max_beams, cfg_.mcl_range_cells, cfg_.mcl_sigma, cfg_.mcl_max_dist, cfg_.mcl_tau,
+                                       cfg_.mcl_resample_frac, cfg_.mcl_resample_always ? CM_MCL_RESAMPLE_ALWAYS : 0u, cfg_.mcl_seed};
+                if (cm_map_mcl_configure(ctx_, &lp) != CM_OK) refuse("cm_map_mcl_configure");
             }
             if (ctx_ && cfg_.map_plan_neutral > 0u) {              // the plan layer behind the cost layer
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
@@ -559,6 +594,40 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
             }
         }
         std::memcpy(matched_pose_, pose, sizeof pose);
+    }
+    // The localisation in front of the integration, from the pose that was set (a match does not move it): once the map holds a
+    // frame, the first frame initialises the particles, every later one predicts with the planar motion since and updates. A
+    // call the library refuses leaves the belief as it is and says so.
+    if (cfg_.mcl_enable && cfg_.map_inflation_radius > 0.0f && map_info_.n_frames > 0) {
+        float set[12];
+        {
+            std::lock_guard<std::mutex> lk(pose_mu_);
+            std::memcpy(set, pose_, sizeof set);
+        }
+        const float now[3] = {set[3], set[7], std::atan2(set[4], set[0])};
+        int ls = CM_OK;
+        if (!mcl_started_) {
+            ls = cfg_.mcl_init_uniform ? cm_map_mcl_init_uniform(ctx_)
+                                       : cm_map_mcl_init_pose(ctx_, now[0], now[1], now[2], cfg_.mcl_init_sd[0], cfg_.mcl_init_sd[1], cfg_.mcl_init_sd[2]);
+            mcl_started_ = ls == CM_OK;
+        } else {
+            const float dx = now[0] - mcl_prev_[0], dy = now[1] - mcl_prev_[1];
+            const float c = std::cos(mcl_prev_[2]), s = std::sin(mcl_prev_[2]);
+            float dyaw = now[2] - mcl_prev_[2];
+            if (dyaw > 3.14159265f) dyaw -= 6.28318531f;
+            if (dyaw < -3.14159265f) dyaw += 6.28318531f;
+            ls = cm_map_mcl_predict(ctx_, c * dx + s * dy, c * dy - s * dx, dyaw, cfg_.mcl_noise[0], cfg_.mcl_noise[1], cfg_.mcl_noise[2]);
+            if (ls == CM_OK) ls = cm_map_mcl_update(ctx_, &mcl_info_);
+        }
+        if (ls == CM_OK) {
+            std::memcpy(mcl_prev_, now, sizeof now);
+            mcl_particles_.resize(cfg_.mcl_particles);
+            ls = cm_map_mcl_copy(ctx_, mcl_particles_.data(), mcl_particles_.size());
+        }
+        if (ls != CM_OK) {
+            set_error(cm_last_error(ctx_));
+            if (ls != CM_BAD_ARG) return ls;
+        }
     }
     const size_t n = static_cast<size_t>(cfg_.map_nx) * cfg_.map_ny;
     map_cells_.resize(n);

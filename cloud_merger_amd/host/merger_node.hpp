@@ -166,6 +166,23 @@ struct NodeConfig {
     uint32_t match_search_wx = 128, match_search_wy = 128;
     uint32_t match_search_depth = 5;
     uint32_t match_search_max_nodes = 1u << 18, match_search_max_cells = 1u << 17;
+    // The localisation layer (cm_map_mcl_configure, cm_map_mcl_update): a particle filter of the pose against the map. Off by
+    // default. On (it needs the cost layer; without one load_config refuses the file and the node does not start): once the
+    // map holds a frame and its distance field is fresh, the first frame initialises the particles, around set_pose()'s pose
+    // (mcl_init pose) or over the map's free cells (mcl_init uniform); every later frame predicts with the planar motion between
+    // the previous and the current set_pose() pose and the noise of mcl_noise, then updates (mcl_info(), mcl_particles()). The
+    // pose a frame is integrated under does not change.
+    bool mcl_enable = false;
+    uint32_t mcl_particles = 2048;
+    uint32_t mcl_max_beams = 256, mcl_range_cells = 256;
+    float mcl_sigma = 0.1f, mcl_max_dist = 0.5f;     // the likelihood field, as match_field
+    float mcl_tau = 8.0f;
+    float mcl_resample_frac = 0.5f;
+    bool mcl_resample_always = false;
+    uint64_t mcl_seed = 1;
+    bool mcl_init_uniform = false;                   // mcl_init uniform; otherwise around the pose with mcl_init_sd
+    float mcl_init_sd[3] = {0.5f, 0.5f, 0.2f};       // sd_x, sd_y (metres), sd_yaw (radians)
+    float mcl_noise[3] = {0.05f, 0.05f, 0.02f};      // sd_fwd, sd_left (metres), sd_yaw (radians) of every predict
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -221,6 +238,9 @@ struct NodeConfig {
 //   shifts of up to wx and wy cells, the field's standard deviation and cut in metres)
 //   match_search <0|1> | match_search_window <wx> <wy> | match_search_depth <h> | match_search_capacity <max_nodes> <max_cells>
 //   (the same match by branch and bound over shifts of up to 1024 cells, in the place of `match`: both on is an error)
+//   mcl <0|1> | mcl_particles <n> | mcl_beams <max_beams> <range_cells> | mcl_field <sigma> <max_dist> | mcl_tau <tau> |
+//   mcl_resample <frac> <always 0|1> | mcl_seed <seed> | mcl_init <pose sd_x sd_y sd_yaw | uniform> | mcl_noise <sd_fwd sd_left sd_yaw>
+//   (the localisation layer behind the cost layer, which it needs: a file with mcl 1 and no map_inflation is refused)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -352,6 +372,11 @@ public:
     // match_search 1: the statistics of the search behind match_result() (zeros where the frame was not matched, the overflow
     // where a capacity was exceeded).
     const cm_match_search_info& match_search_info() const { return match_search_info_; }
+    // mcl 1: whether the particles are initialised, the info of the last update (zeros until the first) and the particles
+    // after the last call of the layer.
+    bool mcl_started() const { return mcl_started_; }
+    const cm_mcl_info& mcl_info() const { return mcl_info_; }
+    const std::vector<cm_mcl_particle>& mcl_particles() const { return mcl_particles_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -433,6 +458,10 @@ private:
     cm_match_result match_result_{};
     cm_match_search_info match_search_info_{};
     float matched_pose_[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    bool mcl_started_ = false;
+    float mcl_prev_[3] = {0.0f, 0.0f, 0.0f};         // x, y, yaw of the set pose at the last init or predict
+    cm_mcl_info mcl_info_{};
+    std::vector<cm_mcl_particle> mcl_particles_;
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

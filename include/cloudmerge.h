@@ -712,6 +712,13 @@ CM_API int cm_map_copy(cm_ctx* ctx, cm_map_cell* host_dst, uint64_t capacity_cel
 CM_API int cm_map_device(cm_ctx* ctx, const void** dev_ptr, cm_map_info* info);
 /* Host copy of the image; capacity in cells. Fewer than nx * ny: CM_CAPACITY (nothing is copied). *info may be NULL. */
 CM_API int cm_map_occupancy_copy(cm_ctx* ctx, int8_t* host_dst, uint64_t capacity_cells, cm_map_info* info);
+/* Puts a recorded map back (localisation in a map that was built earlier): host_src is a state table as cm_map_copy returned it,
+ * anchor the anchor it was recorded with. It replaces the state, recomputes the image by step 8, sets the anchor,
+ * n_frames = 1 and sensors_cast = 0, and makes the layers behind stale exactly as an integration does. A frame held at the time
+ * counts as not yet integrated. CM_BAD_ARG: no configured map, n_cells != nx * ny, a NULL table or anchor, a logodds outside
+ * [l_min, l_max], |anchor| >= 2^30 on an axis, a frame in flight (nothing changes). *out (may be NULL) is the info afterwards.
+ * No other function of the map changes. */
+CM_API int cm_map_load(cm_ctx* ctx, const cm_map_cell* host_src, uint64_t n_cells, const int32_t anchor[2], cm_map_info* out);
 
 /* ---- cost layer over the occupancy map: exact distance field and inflated costmap (an extension) -------------------------
  * The map's image is costmap_2d's obstacle layer. A planner plans on the layer above it, the inflation layer, and clearance
@@ -1228,6 +1235,147 @@ CM_API int cm_map_frontier_labels_copy(cm_ctx* ctx, uint32_t* host_dst, uint64_t
 /* Both in device memory owned by the context (nx * ny words; n_written entries of cm_frontier), valid until the next
  * cm_map_frontier_update, cm_map_plan_update, cm_map_cost_update, cm_map_integrate or configure call of the four layers. */
 CM_API int cm_map_frontier_device(cm_ctx* ctx, const void** labels, const void** table, cm_frontier_info* info);
+
+/* ---- the localisation layer: a particle filter against the occupancy map (an extension) -----------------------------------
+ * The matching layers return the single best entry of a lattice around one prior. This layer keeps a belief over poses: a set
+ * of particles that carries several hypotheses from frame to frame, takes odometry between frames and can start without a
+ * prior (Monte Carlo localisation against a likelihood field, amcl). It is configured once behind the cost
+ * layer; its calls are init, predict and update. Scores and weights are integers, positions are fp32 with every operation
+ * rounded on its own, noise is an integer sum of fields of a counter-based draw and resampling is integer systematic
+ * resampling: the particles, the weight table and the info are bit for bit a function of the frame, the map's info, cell and
+ * image, dist2, the parameters and the sequence of calls.
+ * Constants: W1 = 65536 (weight one); K = 4294967296.0 / 6.283185307179586 (the rollout layer's); K1 = sqrt(3.0 /
+ * 4294967295.0) in double; umul64hi(a, b) is the high 64 bits of the 128-bit product.
+ *   1. Particle, cm_mcl_particle (24 bytes): x, y (fp32) in the map's world frame; h, a binary angle, a full turn is 2^32,
+ *      whose direction (c, s) is entry ((h + 0x80000) >> 20) & 4095 of the CM_TRAJ_HEADINGS table (cm_traj_directions); parent;
+ *      acc (uint64_t).
+ *   2. Draws. gen counts the layer's init, predict and update calls since cm_map_mcl_configure that were not refused; the
+ *      first has gen = 0 (sharpened: a refused call draws nothing and does not count). base = splitmix64(seed + gen), wrapping.
+ *      draw(p, i) = splitmix64(base ^ ((uint64_t)p << 8) ^ i) for i < 256; splitmix64 is the ground stage's function
+ *      (x += 0x9E3779B97F4A7C15; z = x; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *      z ^ z >> 31). The noise integer n(u) of a draw u is the sum of its four 16-bit fields minus 131070, in
+ *      [-131070, 131070], of mean 0 and variance (2^32 - 1) / 3. A noise value for a standard deviation sd (fp32, >= 0) is
+ *      (float)n * sc with sc = (float)((double)sd * K1), computed once per call on the host: one fp32 product. cm_mcl_draws
+ *      returns draw(p, i) for a range of p.
+ *   3. Init around a pose (x0, y0, yaw0) with (sd_x, sd_y, sd_yaw): x_p = x0 + (float)n(draw(p, 0)) * sc_x, y_p likewise with
+ *      draw 1 and sc_y, h_p = the low 32 bits of (int64_t)rint(((double)yaw0 + (double)((float)n(draw(p, 2)) * sc_yaw)) * K);
+ *      acc = 0, parent = p.
+ *   4. Init over the free space. The free cells are the window cells whose image byte is 0, in ascending entry order, n_free of
+ *      them. Particle p takes the free cell of rank umul64hi(draw(p, 0), n_free), window cell (ix, iy). ux = (float)(draw(p, 1)
+ *      >> 40) * 0x1p-24f; x_p = ((float)(ax + ix) + ux) * cell: a conversion, a sum and a product, each rounded; y_p likewise
+ *      with draw 2 and ay + iy; h_p = (uint32_t)(draw(p, 3) >> 32); acc = 0, parent = p. Whether floorf(x_p * inv) lands in
+ *      that very cell is not promised and not needed.
+ *   5. Predict with the vehicle-frame motion since the last predict (d_fwd, d_left, d_yaw) and its standard deviations, which
+ *      the caller passes as the rollout takes its dynamic window from outside. With (c, s) of h_p before the turn:
+ *      a = d_fwd + (float)n(draw(p, 0)) * sc_fwd, b = d_left + (float)n(draw(p, 1)) * sc_left; x' = (x + c * a) - s * b,
+ *      y' = (y + s * a) + c * b, each operation rounded (the form of the rollout's step 4); h' = h + the low 32 bits of
+ *      (int64_t)rint(((double)d_yaw + (double)((float)n(draw(p, 2)) * sc_yaw)) * K), wrapping. acc and parent stay.
+ *   6. Beams of an update, from the last frame as cm_map_match_evaluate sees it. A counted point is a point of A that is valid
+ *      and inside the map's closed height band. Its (x, y) is taken in the common frame: no pose is applied, the body frame is
+ *      taken as level. Per axis the body cell is b = floorf(x * inv) with the map's existence test; a point is dropped where
+ *      either |b| > range_cells. D is the set of distinct body cells over all sensors, n_cells = |D|, ordered by (b_y, b_x)
+ *      ascending. stride = max(1, ceil(n_cells / max_beams)); the beams are the cells of rank 0, stride, 2 stride, ...:
+ *      n_beams = ceil(n_cells / stride). A beam's point is its cell's centre: fx = ((float)b_x + 0.5f) * cell, fy likewise.
+ *   7. Score. The field L is steps 1 and 2 of the matching layer, unchanged. For particle p and every beam:
+ *      wx = (x_p + c * fx) - s * fy, wy = (y_p + s * fx) + c * fy, each operation rounded; the cell of (wx, wy) is the map's
+ *      step 1 minus the anchor; it contributes L if it exists and lies in the window, otherwise 0. S_p is the sum as uint32_t
+ *      (at most 8192 * 255); acc_p += S_p.
+ *   8. Weights. A = max acc_p, d_p = A - acc_p, W_p = (uint32_t)floor(65536.0 * cm_exp_neg((double)d_p * beta)) with
+ *      beta = 1.0 / (255.0 * (double)tau) computed once on the host (cm_exp_neg is cm_ndt_math.hpp's). The best particle has
+ *      W = 65536, so sum_w >= 65536. cm_mcl_weight is {S_p, W_p}, in the order of the particles the update found.
+ *   9. Estimate, all sums int64 / uint64 and exact. q(v) = clamp(llrint((double)v * 1024.0), -2^30, 2^30), and 0 for a v that
+ *      is not finite. ci = (int)rint(c * 32768.0f), si likewise. sum_w = sum W, sum_w2 = sum W^2, sum_wqx = sum W q(x),
+ *      sum_wqy, sum_wc = sum W ci, sum_ws = sum W si. best is the particle with the largest acc, ties to the lowest index.
+ *      mq_x = floor(sum_wqx / sum_w) as integers, mq_y likewise; dq = clamp(q - mq, -32768, 32767) per axis; sum_wdxx, sum_wdyy
+ *      and sum_wdxy are the sums of W dq_x^2, W dq_y^2 and W dq_x dq_y. The arithmetic: W <= 2^16 and at most 2^16 particles,
+ *      so sum_w <= 2^32 and sum_w2 <= 2^48; |q| <= 2^30, so |sum_wq| <= 2^62; |ci| <= 2^15, so |sum_wc| <= 2^47;
+ *      |dq| <= 2^15, so the spread sums stay within 2^62: every sum is below 2^63. On the host in double:
+ *      mean_x = ((double)sum_wqx / (double)sum_w) / 1024.0, mean_y likewise; mean_yaw = atan2((double)sum_ws, (double)sum_wc);
+ *      var_xx = (double)sum_wdxx / ((double)sum_w * 1048576.0), var_yy and var_xy likewise (m^2, about the integer mean);
+ *      n_eff = ((double)sum_w * (double)sum_w) / (double)sum_w2.
+ *  10. Resampling happens iff CM_MCL_RESAMPLE_ALWAYS is set or n_eff < (double)resample_frac * (double)n_particles. T = sum_w,
+ *      r = umul64hi(splitmix64(base ^ (1ull << 63)), T), C the inclusive prefix sum of W in particle order. New particle j
+ *      copies (x, y, h) of the smallest p with C_p > (j * T + r) / N (integer division); its parent = p and its acc = 0.
+ *      Without resampling the particles stay and parent = own index.
+ *  11. cm_mcl_info: n_particles, n_cells, stride, n_beams, the gen of the update, resampled, best, the best particle's x, y, h
+ *      before resampling, every sum of step 9, n_eff, the means and the three spread terms.
+ * cm_map_mcl_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured cost layer; n_particles outside
+ * 1..CM_MCL_MAX_PARTICLES, max_beams outside 1..CM_MCL_MAX_BEAMS, range_cells outside 1..CM_MCL_MAX_RANGE_CELLS; sigma and
+ * max_dist as cm_map_match_configure refuses them; tau not finite and > 0; resample_frac not finite or outside 0..1; unknown
+ * flag bits; a frame in flight. cm_map_mcl_init_pose refuses a value that is not finite, a negative sd, |yaw0| > 1024 and an sd
+ * above 1024; cm_map_mcl_predict the same of its six values (|d_yaw| <= 1024), and particles that are not yet initialised.
+ * cm_map_mcl_init_uniform refuses a map with n_frames == 0 and an image without a free cell. cm_map_mcl_update refuses what
+ * cm_map_match_evaluate refuses (a stale dist2, a map with n_frames == 0, everything about the result), and particles that are
+ * not yet initialised. All memory of the layer is taken by cm_map_mcl_configure (two particle buffers, the weight table, the
+ * prefix sums, the field and its table, one bitmap and one list that serve the body cells and the free cells, the info words and
+ * their page-locked copy): no other call allocates. Sharpened: the particles are the layer's state, not a table of the map; they
+ * are readable (cm_map_mcl_copy) from the first init on, whatever happens to the map. The weight table and the info are stale
+ * from cm_map_mcl_configure and from every cm_map_integrate, cm_map_load, cm_map_cost_update, merge, init and predict until the
+ * next cm_map_mcl_update: cm_map_mcl_weights_copy and cm_map_mcl_device then refuse with CM_BAD_ARG and say since which call.
+ * cm_map_cost_configure and cm_map_configure, in either form, free the layer. It reads the map and the cost layer and writes
+ * buffers of its own only: no other layer's tables or staleness change. A NULL context leaves every output untouched. With
+ * CM_FLAG_PROFILE, cm_get_stage_times after an update lists mcl_clear, k_match_field, k_mcl_mark, k_mcl_compact, k_mcl_score,
+ * k_mcl_best, k_mcl_weights, k_mcl_spread, k_mcl_resample. Not modelled: the beam model's terms (z_short, z_max, z_rand),
+ * occlusion, adaptive (KLD) particle counts, random-particle injection, roll, pitch and z, weighting a cell by the number of
+ * its points. */
+#define CM_MCL_MAX_PARTICLES 65536
+#define CM_MCL_MAX_BEAMS 8192
+#define CM_MCL_MAX_RANGE_CELLS 1024
+#define CM_MCL_WEIGHT_ONE 65536
+#define CM_MCL_RESAMPLE_ALWAYS 1u
+typedef struct cm_mcl_params {         /* 40 bytes, no padding */
+    uint32_t n_particles;              /* 1 .. CM_MCL_MAX_PARTICLES */
+    uint32_t max_beams;                /* 1 .. CM_MCL_MAX_BEAMS */
+    uint32_t range_cells;              /* body cells beyond it are dropped; 1 .. CM_MCL_MAX_RANGE_CELLS */
+    float sigma, max_dist;             /* the field, exactly cm_match_params' */
+    float tau;                         /* temperature of the weights, in mean field bytes; finite, > 0 */
+    float resample_frac;               /* resample when n_eff < resample_frac * n_particles; finite, 0 .. 1 */
+    uint32_t flags;                    /* CM_MCL_RESAMPLE_ALWAYS or 0 */
+    uint64_t seed;
+} cm_mcl_params;
+typedef struct cm_mcl_particle {       /* 24 bytes */
+    float x, y;                        /* position in the map's world frame (m) */
+    uint32_t h;                        /* heading, a binary angle */
+    uint32_t parent;                   /* the particle of the last update it was copied from; its own index otherwise */
+    uint64_t acc;                      /* scores accumulated since it was initialised or resampled */
+} cm_mcl_particle;
+typedef struct cm_mcl_weight {         /* 8 bytes */
+    uint32_t score;                    /* S_p of the update */
+    uint32_t weight;                   /* W_p, 0 .. CM_MCL_WEIGHT_ONE */
+} cm_mcl_weight;
+typedef struct cm_mcl_info {           /* 176 bytes */
+    uint32_t n_particles, n_cells, stride, n_beams;
+    uint64_t gen;                      /* the gen of the update */
+    uint32_t resampled, best;
+    float best_x, best_y;              /* the best particle before resampling */
+    uint32_t best_h, _pad;
+    uint64_t sum_w, sum_w2;
+    int64_t sum_wqx, sum_wqy, sum_wc, sum_ws;
+    int64_t sum_wdxx, sum_wdyy, sum_wdxy;
+    double n_eff, mean_x, mean_y, mean_yaw;
+    double var_xx, var_yy, var_xy;
+} cm_mcl_info;
+/* Non-NULL parameters allocate the layer (no particles yet, gen = 0); NULL frees it. */
+CM_API int cm_map_mcl_configure(cm_ctx* ctx, const cm_mcl_params* p);
+/* Step 3. */
+CM_API int cm_map_mcl_init_pose(cm_ctx* ctx, float x0, float y0, float yaw0, float sd_x, float sd_y, float sd_yaw);
+/* Step 4, over the map's current image. */
+CM_API int cm_map_mcl_init_uniform(cm_ctx* ctx);
+/* Step 5. */
+CM_API int cm_map_mcl_predict(cm_ctx* ctx, float d_fwd, float d_left, float d_yaw, float sd_fwd, float sd_left, float sd_yaw);
+/* Steps 6 to 11 with the last frame. *out may be NULL. */
+CM_API int cm_map_mcl_update(cm_ctx* ctx, cm_mcl_info* out);
+/* Host copy of the n_particles particles after the last call; capacity in particles. Fewer: CM_CAPACITY (nothing is copied). */
+CM_API int cm_map_mcl_copy(cm_ctx* ctx, cm_mcl_particle* host_dst, uint64_t capacity);
+/* Host copy of the last update's weight table; capacity in entries. Fewer: CM_CAPACITY (nothing is copied; *info, which may be
+ * NULL, is still written). */
+CM_API int cm_map_mcl_weights_copy(cm_ctx* ctx, cm_mcl_weight* host_dst, uint64_t capacity, cm_mcl_info* info);
+/* Both in device memory owned by the context, valid until the next call of this layer or configure call of the map, the cost
+ * layer or this layer. Any of the three outputs may be NULL. */
+CM_API int cm_map_mcl_device(cm_ctx* ctx, const void** particles, const void** weights, cm_mcl_info* info);
+/* draw(p, i) of step 2 for p = first_p .. first_p + n_p - 1 into dst. A host function: no context, no GPU. CM_BAD_ARG: i >= 256,
+ * a NULL dst, first_p + n_p above 2^32 (nothing is written). */
+CM_API int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t n_p, uint32_t i, uint64_t* dst);
 
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
