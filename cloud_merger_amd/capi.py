@@ -56,6 +56,7 @@ SYMBOLS = [
     "cm_map_match_search_configure", "cm_map_match_search", "cm_map_match_search_result", "cm_map_match_search_level_copy",
     "cm_map_mcl_configure", "cm_map_mcl_init_pose", "cm_map_mcl_init_uniform", "cm_map_mcl_predict", "cm_map_mcl_update", "cm_map_mcl_copy",
     "cm_map_mcl_weights_copy", "cm_map_mcl_device", "cm_mcl_draws",
+    "cm_map_cast_configure", "cm_map_cast_evaluate", "cm_map_cast_evaluate_mcl", "cm_map_cast_copy", "cm_map_cast_device", "cm_cast_directions",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
     "cm_result_ndt_align", "cm_result_ndt_align_device", "cm_ndt_correspondences_copy",
@@ -459,6 +460,30 @@ MCL_WEIGHT_DTYPE = np.dtype([("score", "<u4"), ("weight", "<u4")])
 assert C.sizeof(MclParams) == 40 and MclParams.seed.offset == 32 and C.sizeof(MclInfo) == 176 and MclInfo.sum_w.offset == 48
 assert MclInfo.n_eff.offset == 120 and MCL_PARTICLE_DTYPE.itemsize == 24 and MCL_WEIGHT_DTYPE.itemsize == 8
 
+# the cast layer: expected ranges from many poses in the map, behind the cost layer (cm_map_cast_configure, cm_map_cast_evaluate)
+CAST_MAX_POSES = 65536
+CAST_MAX_BEARINGS = 4096
+CAST_MAX_RANGE_CELLS = 1024
+CAST_MAX_RAYS = 1 << 24
+CAST_PLAIN = 1
+CAST_MAX, CAST_HIT, CAST_OFF_MAP, CAST_NO_ORIGIN = 0, 1, 2, 3            # status values of a ray, not bits
+
+
+class CastParams(C.Structure):
+    """cm_cast_params (16 bytes): the most poses of an evaluate, the bearings per pose, the reach of a ray in cells, CAST_PLAIN or 0."""
+    _fields_ = [("max_poses", C.c_uint32), ("n_bearings", C.c_uint32), ("range_cells", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CastInfo(C.Structure):
+    """cm_cast_info (24 bytes): the poses and bearings of the last evaluate and its rays by status."""
+    _fields_ = [("n_poses", C.c_uint32), ("n_bearings", C.c_uint32), ("n_max", C.c_uint32), ("n_hit", C.c_uint32), ("n_off_map", C.c_uint32),
+                ("n_no_origin", C.c_uint32)]
+
+
+CAST_POSE_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("h", "<u4")])
+CAST_RAY_DTYPE = np.dtype([("k", "<u2"), ("status", "u1"), ("_pad", "u1"), ("jx", "<i2"), ("jy", "<i2")])
+assert C.sizeof(CastParams) == 16 and C.sizeof(CastInfo) == 24 and CAST_POSE_DTYPE.itemsize == 12 and CAST_RAY_DTYPE.itemsize == 8
+
 
 # normals and curvature of the result (cm_result_normals)
 NORMAL_MAX_K = 64
@@ -688,6 +713,12 @@ def load():
     L.cm_map_mcl_weights_copy.argtypes = [vp, vp, u64, C.POINTER(MclInfo)]
     L.cm_map_mcl_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(MclInfo)]
     L.cm_mcl_draws.argtypes = [u64, u64, u32, u32, u32, vp]
+    L.cm_map_cast_configure.argtypes = [vp, C.POINTER(CastParams), vp]
+    L.cm_map_cast_evaluate.argtypes = [vp, vp, u32, C.POINTER(CastInfo)]
+    L.cm_map_cast_evaluate_mcl.argtypes = [vp, C.POINTER(CastInfo)]
+    L.cm_map_cast_copy.argtypes = [vp, vp, u64, C.POINTER(CastInfo)]
+    L.cm_map_cast_device.argtypes = [vp, C.POINTER(vp), C.POINTER(CastInfo)]
+    L.cm_cast_directions.argtypes = [u32, vp, u64]
     L.cm_result_normals.argtypes = [vp, C.POINTER(NormalParams), vp, u64]
     L.cm_result_normals_device.argtypes = [vp, C.POINTER(NormalParams), C.POINTER(vp), C.POINTER(u64)]
     L.cm_result_align.argtypes = [vp, C.POINTER(AlignParams), vp, u64, C.POINTER(AlignResult)]
@@ -752,6 +783,20 @@ def mcl_draws(seed, gen, first_p, n_p, i):
     if st != OK and n_p:
         raise CloudMergeError(st, "cm_mcl_draws")
     return out
+
+
+def cast_directions(range_cells):
+    """(TRAJ_HEADINGS, 2) int16: the cast layer's direction table for range_cells, rint(range_cells * (cos, sin)) (cm_cast_directions)."""
+    out = np.empty((TRAJ_HEADINGS, 2), dtype=np.int16)
+    st = load().cm_cast_directions(int(range_cells), out.ctypes.data, out.shape[0])
+    if st != OK:
+        raise CloudMergeError(st, "cm_cast_directions")
+    return out
+
+
+def cast_heading(yaw):
+    """The binary angle of a yaw in radians: rint(yaw * 2^32 / (2 pi)) mod 2^32, the rollout layer's conversion."""
+    return int(np.rint(float(yaw) * (4294967296.0 / 6.283185307179586))) & 0xFFFFFFFF
 
 
 def status_string(status):
@@ -1172,6 +1217,7 @@ class CloudMerger:
             return
         p = self.map_params(cell, nx, ny, z_band, l_hit, l_miss, l_min, l_max, l_free, l_occ, max_range_cells)
         self._check(self._lib.cm_map_configure(self._ctx, C.byref(p)), "cm_map_configure")
+        self._map_cell = float(p.cell)                 # (the fp32 cell the library uses, for map_cast_ranges)
 
     def map_integrate(self, pose=None):
         """Integrates the last frame into the map: pose is the 3 x 4 matrix (fp32) that takes the vehicle frame at the frame's
@@ -1492,6 +1538,64 @@ class CloudMerger:
         parts, wts, info = C.c_void_p(), C.c_void_p(), MclInfo()
         self._check(self._lib.cm_map_mcl_device(self._ctx, C.byref(parts), C.byref(wts), C.byref(info)), "cm_map_mcl_device")
         return parts.value, wts.value, info
+
+    # ---- the cast layer: expected ranges from many poses in the map, behind the cost layer (cm_map_cast_configure / cm_map_cast_evaluate) ----
+    def map_cast_configure(self, max_poses=None, n_bearings=360, range_cells=256, plain=False, bearings=None):
+        """Allocates the cast layer behind the configured cost layer: at most max_poses poses per evaluate, n_bearings rays per
+        pose of at most range_cells cells; bearings are binary angles (a full turn is 2^32) added to a pose's heading, None
+        spaces them evenly. plain walks cell by cell through the image; otherwise the walk skips by the distance field, with
+        the same result. max_poses None frees the layer."""
+        if max_poses is None:
+            self._check(self._lib.cm_map_cast_configure(self._ctx, None, None), "cm_map_cast_configure")
+            return
+        b = None
+        if bearings is not None:
+            b = np.ascontiguousarray(np.asarray(bearings, dtype=np.uint64) & 0xFFFFFFFF, dtype=np.uint32).reshape(-1)
+            if b.shape[0] != int(n_bearings):
+                raise ValueError("bearings must hold n_bearings binary angles")
+        p = CastParams(int(max_poses), int(n_bearings), int(range_cells), CAST_PLAIN if plain else 0)
+        self._check(self._lib.cm_map_cast_configure(self._ctx, C.byref(p), b.ctypes.data if b is not None else None), "cm_map_cast_configure")
+        self._cast_cap = p.max_poses * p.n_bearings
+
+    def map_cast(self, poses):
+        """Casts n_bearings rays from every pose. poses: a CAST_POSE_DTYPE array, or (n, 3) rows of x, y (metres, the map's
+        world frame) and yaw (radians, converted by cast_heading). Returns the CastInfo."""
+        if isinstance(poses, np.ndarray) and poses.dtype == CAST_POSE_DTYPE:
+            q = np.ascontiguousarray(poses).reshape(-1)
+        else:
+            rows = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+            q = np.empty(rows.shape[0], dtype=CAST_POSE_DTYPE)
+            q["x"], q["y"] = rows[:, 0], rows[:, 1]
+            q["h"] = [cast_heading(v) for v in rows[:, 2]]
+        info = CastInfo()
+        self._check(self._lib.cm_map_cast_evaluate(self._ctx, q.ctypes.data if q.shape[0] else None, q.shape[0], C.byref(info)), "cm_map_cast_evaluate")
+        return info
+
+    def map_cast_particles(self):
+        """Casts from the localisation layer's current particles in place. Returns the CastInfo."""
+        info = CastInfo()
+        self._check(self._lib.cm_map_cast_evaluate_mcl(self._ctx, C.byref(info)), "cm_map_cast_evaluate_mcl")
+        return info
+
+    def map_cast_rays(self):
+        """((n_poses, n_bearings) CAST_RAY_DTYPE, CastInfo) of the last evaluate."""
+        info = CastInfo()
+        out = np.empty(getattr(self, "_cast_cap", 0), dtype=CAST_RAY_DTYPE)
+        self._check(self._lib.cm_map_cast_copy(self._ctx, out.ctypes.data, out.shape[0], C.byref(info)), "cm_map_cast_copy")
+        return out[: info.n_poses * info.n_bearings].reshape(info.n_poses, info.n_bearings), info
+
+    def map_cast_ranges(self, cell=None):
+        """((n_poses, n_bearings) float64 metric ranges cell * sqrt(jx^2 + jy^2), the rays, CastInfo) of the last evaluate; a ray
+        without an origin has range 0. cell None: the cell map_configure was given."""
+        rays, info = self.map_cast_rays()
+        cell = float(self._map_cell if cell is None else cell)
+        return cell * np.sqrt(rays["jx"].astype(np.float64) ** 2 + rays["jy"].astype(np.float64) ** 2), rays, info
+
+    def map_cast_device(self):
+        """(rays device pointer, CastInfo), owned by the context and valid until the next evaluate or configure call."""
+        rays, info = C.c_void_p(), CastInfo()
+        self._check(self._lib.cm_map_cast_device(self._ctx, C.byref(rays), C.byref(info)), "cm_map_cast_device")
+        return rays.value, info
 
     # ---- branch-and-bound scan matching over wide windows, behind the cost layer (cm_map_match_search_configure / cm_map_match_search) ----
     def map_match_search_configure(self, sigma=None, max_dist=0.5, n_a=0, a_stride=1, wx=0, wy=0, depth=0, max_nodes=1 << 16, max_cells=1 << 16,

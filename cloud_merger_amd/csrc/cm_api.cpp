@@ -1605,6 +1605,99 @@ int cm_map_mcl_device(cm_ctx* c, const void** particles, const void** weights, c
     return CM_OK;
 }
 
+static_assert(sizeof(cm_cast_params) == 16 && sizeof(cm_cast_pose) == 12 && offsetof(cm_cast_pose, h) == 8 && sizeof(cm_cast_ray) == 8 &&
+                  offsetof(cm_cast_ray, status) == 2 && offsetof(cm_cast_ray, jx) == 4 && sizeof(cm_cast_info) == 24 && offsetof(cm_cast_info, n_max) == 8,
+              "the cast layer's four structs");
+static_assert(sizeof(CmCastRayDev) == sizeof(cm_cast_ray) && offsetof(CmCastRayDev, jy) == offsetof(cm_cast_ray, jy) && sizeof(CmMclParticleDev) % 4 == 0 &&
+                  offsetof(CmMclParticleDev, x) == 0 && offsetof(CmMclParticleDev, y) == 4 && offsetof(CmMclParticleDev, h) == 8,
+              "the kernel writes cm_cast_ray and reads a particle's x, y, h as a pose's");
+static_assert(CM_CAST_MAX_POSES == CM_CAST_MAX_POSES_DEV && CM_CAST_MAX_BEARINGS == CM_CAST_MAX_BEARINGS_DEV && CM_CAST_MAX_RANGE_CELLS == CM_CAST_MAX_RANGE_DEV &&
+                  CM_CAST_MAX_RAYS == CM_CAST_MAX_RAYS_DEV && CM_CAST_DIRS == CM_TRAJ_HEADINGS && CM_CAST_NO_ORIGIN == 3 && CM_CAST_WORDS == 4 &&
+                  CM_MCL_MAX_PARTICLES <= CM_CAST_MAX_POSES,
+              "the kernels' constants; the count words are indexed by status");
+
+int cm_cast_directions(uint32_t range_cells, int16_t* dst, uint64_t capacity_pairs) {
+    if (!dst || range_cells < 1u || range_cells > CM_CAST_MAX_RANGE_CELLS) return CM_BAD_ARG;
+    if (capacity_pairs < CM_CAST_DIRS) return CM_CAPACITY;
+    cast_direction_table(range_cells, dst);
+    return CM_OK;
+}
+
+int cm_map_cast_configure(cm_ctx* c, const cm_cast_params* p, const uint32_t* bearings) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (p) {
+        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+        if (p->max_poses < 1u || p->max_poses > CM_CAST_MAX_POSES) return fail(c, CM_BAD_ARG, "max_poses must lie in 1..CM_CAST_MAX_POSES");
+        if (p->n_bearings < 1u || p->n_bearings > CM_CAST_MAX_BEARINGS) return fail(c, CM_BAD_ARG, "n_bearings must lie in 1..CM_CAST_MAX_BEARINGS");
+        if (p->range_cells < 1u || p->range_cells > CM_CAST_MAX_RANGE_CELLS) return fail(c, CM_BAD_ARG, "range_cells must lie in 1..CM_CAST_MAX_RANGE_CELLS");
+        if (static_cast<uint64_t>(p->max_poses) * p->n_bearings > CM_CAST_MAX_RAYS) return fail(c, CM_BAD_ARG, "max_poses * n_bearings is above CM_CAST_MAX_RAYS");
+        if (p->flags & ~CM_CAST_PLAIN) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    }
+    return map_cast_configure(c, p, bearings);
+}
+
+// The refusals every call on a configured cast layer shares.
+static int cast_check(cm_ctx* c, bool read) {
+    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
+    if (!c->cast_on) return fail(c, CM_BAD_ARG, "no cast layer (cm_map_cast_configure first)");
+    if (read && c->cast_stale) return fail(c, CM_BAD_ARG, c->cast_stale);
+    if (!read && !c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
+    return CM_OK;
+}
+
+int cm_map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n, cm_cast_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cast_check(c, false)) return e;
+    if (n < 1u || n > c->cast_params.max_poses) return fail(c, CM_BAD_ARG, "n must lie in 1..max_poses");
+    if (!host_poses) return fail(c, CM_BAD_ARG, "no poses");
+    if (const int e = map_cast_evaluate(c, host_poses, n)) return e;
+    if (out) *out = c->cast_info;
+    return CM_OK;
+}
+
+int cm_map_cast_evaluate_mcl(cm_ctx* c, cm_cast_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cast_check(c, false)) return e;
+    if (!c->mcl_on) return fail(c, CM_BAD_ARG, "no localisation layer (cm_map_mcl_configure first)");
+    if (!c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
+    if (c->mcl_params.n_particles > c->cast_params.max_poses) return fail(c, CM_BAD_ARG, "n_particles is above max_poses");
+    if (const int e = map_cast_evaluate(c, nullptr, c->mcl_params.n_particles)) return e;
+    if (out) *out = c->cast_info;
+    return CM_OK;
+}
+
+int cm_map_cast_copy(cm_ctx* c, cm_cast_ray* host_dst, uint64_t capacity, cm_cast_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cast_check(c, true)) return e;
+    if (info) *info = c->cast_info;
+    const uint64_t n = static_cast<uint64_t>(c->cast_info.n_poses) * c->cast_info.n_bearings;
+    if (n > capacity) return fail(c, CM_CAPACITY, "ray destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, c->cast_rays, n * sizeof(cm_cast_ray), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * sizeof(cm_cast_ray);
+    return CM_OK;
+}
+
+int cm_map_cast_device(cm_ctx* c, const void** rays, cm_cast_info* info) {
+    if (!c) return CM_BAD_ARG;
+    if (rays) *rays = nullptr;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = cast_check(c, true)) return e;
+    if (info) *info = c->cast_info;
+    if (rays) *rays = c->cast_rays;
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_match_search_params) == 40 && sizeof(cm_match_search_info) == 84 && offsetof(cm_match_search_info, scored) == 12 &&
                   offsetof(cm_match_search_info, live) == 44 && offsetof(cm_match_search_info, overflow_level) == 80, "the search layer's two structs");
 static_assert(CM_MATCH_SEARCH_MAX_SHIFT == CM_MSEARCH_MAX_SHIFT_DEV && CM_MATCH_SEARCH_MAX_DEPTH == CM_MSEARCH_MAX_DEPTH_DEV &&

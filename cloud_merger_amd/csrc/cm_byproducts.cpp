@@ -565,6 +565,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
     c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_integrate";
     c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_integrate";
+    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_integrate";
     return CM_OK;
 }
 
@@ -576,6 +577,7 @@ int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     if (const int e = map_match_configure(c, nullptr, 0)) return e;    // and so does the matching layer
     if (const int e = map_msearch_configure(c, nullptr, 0)) return e;  // and the search layer
     if (const int e = map_mcl_configure(c, nullptr, 0)) return e;      // and the localisation layer
+    if (const int e = map_cast_configure(c, nullptr, nullptr)) return e;   // and the cast layer
     c->cost_on = false;
     c->cost_fresh = false;
     if (!q) {
@@ -632,6 +634,8 @@ int map_cost_update(cm_ctx* c) {
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
     c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_cost_update";
     c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_cost_update";
+    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_cost_update";
+    c->cast_steps_fresh = false;                       // (the next evaluate rebuilds its skip table from the new dist2)
     return CM_OK;
 }
 
@@ -1312,6 +1316,98 @@ int map_mcl_update(cm_ctx* c) {
     return CM_OK;
 }
 
+// Step 3 of the cast layer: the rollout layer's heading table scaled by range_cells and rounded, ties to even.
+void cast_direction_table(uint32_t range_cells, int16_t* dst) {
+    const float* const t = traj_direction_table();
+    const double R = static_cast<double>(range_cells);
+    for (uint32_t i = 0; i < 2 * CM_TRAJ_HEADINGS; ++i) dst[i] = static_cast<int16_t>(std::rint(static_cast<double>(t[i]) * R));
+}
+
+// The cast layer's memory, all of it: the rays, the poses an evaluate uploads, the bearings and the direction table (both
+// uploaded here), the skip table, the count words and their page-locked copy. nullptr gives it back. The rays are stale until
+// the first evaluate.
+int map_cast_configure(cm_ctx* c, const cm_cast_params* q, const uint32_t* bearings) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->cast_on = false;
+    c->cast_steps_fresh = false;
+    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since cm_map_cast_configure";
+    std::memset(&c->cast_info, 0, sizeof c->cast_info);
+    if (!q) {
+        c->cast_rays.release();
+        c->cast_poses.release();
+        c->cast_bearings.release();
+        c->cast_dirs.release();
+        c->cast_steps.release();
+        c->cast_words.release();
+        c->cast_host.release();
+        return CM_OK;
+    }
+    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, nb = q->n_bearings;
+    if (!c->cast_rays.reserve(static_cast<size_t>(q->max_poses) * nb) || !c->cast_poses.reserve(3 * static_cast<size_t>(q->max_poses)) ||
+        !c->cast_bearings.reserve(nb) || !c->cast_dirs.reserve(CM_CAST_DIRS) || !c->cast_steps.reserve((n_cells + 3) / 4 * 4) ||
+        !c->cast_words.reserve(CM_CAST_WORDS) || !c->cast_host.reserve(CM_CAST_WORDS))
+        return fail(c, CM_HIP_ERROR, "cannot allocate the cast layer");
+    std::vector<uint32_t> b(nb);
+    for (size_t a = 0; a < nb; ++a) b[a] = bearings ? bearings[a] : static_cast<uint32_t>((static_cast<uint64_t>(a) << 32) / nb);
+    std::vector<int16_t> dirs(2 * CM_CAST_DIRS);
+    cast_direction_table(q->range_cells, dirs.data());
+    HIP_TRY(c, hipMemcpyAsync(c->cast_bearings, b.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->cast_dirs, dirs.data(), CM_CAST_DIRS * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->cast_params = *q;
+    c->cast_on = true;
+    return CM_OK;
+}
+
+// Steps 1 to 7 (cm_kernels_cast.hip; the semantics are in include/cloudmerge.h). One upload of the poses (none where they are
+// the particles), one clear of the counts, the skip table where dist2 has changed since it was built, the rays, then one copy
+// of the counts back and one wait. No allocation.
+int map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    const cm_cast_params& q = c->cast_params;
+    CmCastDev g;
+    g.inv = 1.0f / c->map_params.cell;
+    g.ax = c->map_info.anchor[0];
+    g.ay = c->map_info.anchor[1];
+    g.nx = c->map_info.nx;
+    g.ny = c->map_info.ny;
+    g.n_poses = n;
+    g.n_bearings = q.n_bearings;
+    g.pose_words = host_poses ? 3u : static_cast<uint32_t>(sizeof(CmMclParticleDev) / sizeof(uint32_t));
+    g.plain = (q.flags & CM_CAST_PLAIN) ? 1u : 0u;
+    const void* const poses = host_poses ? static_cast<const void*>(c->cast_poses) : static_cast<const void*>(c->mcl_parts[c->mcl_cur]);
+    hipStream_t st = c->stream;
+    c->cast_stale = "the rays are stale: the last evaluate of the cast layer failed";
+    c->prof_used = 0;
+    prof_mark(c, "cast_upload");
+    if (host_poses) HIP_TRY(c, hipMemcpyAsync(c->cast_poses, host_poses, static_cast<size_t>(n) * sizeof(cm_cast_pose), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->cast_words, 0, CM_CAST_WORDS * sizeof(uint32_t), st));
+    if (!g.plain && !c->cast_steps_fresh) {
+        prof_mark(c, "k_cast_steps");
+        cmk_cast_steps(st, c->cost_dist2, g.nx * g.ny, c->cast_steps);
+    }
+    prof_mark(c, "k_cast_rays");
+    cmk_cast_rays(st, c->map_image, c->cast_steps, g, poses, c->cast_bearings, c->cast_dirs, c->cast_rays, c->cast_words);
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->cast_host, c->cast_words, CM_CAST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    collect_stage_times(c);
+    if (!g.plain) c->cast_steps_fresh = true;
+    const uint32_t* const h = c->cast_host;
+    if (static_cast<uint64_t>(h[0]) + h[1] + h[2] + h[3] != static_cast<uint64_t>(n) * q.n_bearings)
+        return fail(c, CM_INTERNAL, "the status counts of the cast do not add up to its rays");
+    cm_cast_info& r = c->cast_info;
+    r.n_poses = n;
+    r.n_bearings = q.n_bearings;
+    r.n_max = h[CM_CAST_MAX];
+    r.n_hit = h[CM_CAST_HIT];
+    r.n_off_map = h[CM_CAST_OFF_MAP];
+    r.n_no_origin = h[CM_CAST_NO_ORIGIN];
+    c->cast_stale = nullptr;
+    return CM_OK;
+}
+
 // A recorded state table into the map: the table into the current state buffer, the image by step 8, the anchor; the layers
 // behind go stale exactly as after an integration, and the frame at rest counts as not yet integrated.
 int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]) {
@@ -1335,6 +1431,7 @@ int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]) {
     c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_load";
     c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_load";
     c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_load";
+    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_load";
     return CM_OK;
 }
 

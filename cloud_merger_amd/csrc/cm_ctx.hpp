@@ -387,6 +387,22 @@ struct cm_ctx {
     DevBuf<float> mcl_dirs;              // the heading table (2 * CM_TRAJ_HEADINGS floats)
     PinnedBuf<unsigned long long> mcl_host;     // CM_MCL_WORDS words read back
 
+    // Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses, configured by cm_map_cast_configure
+    // and evaluated by cm_map_cast_evaluate / _evaluate_mcl from map_info, map_image, cost_dist2 and, for the latter, mcl_parts.
+    // Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
+    bool cast_on = false;
+    const char* cast_stale = nullptr;    // why rays and info are not those of the current tables; nullptr: they are
+    bool cast_steps_fresh = false;       // cast_steps is that of the current dist2
+    cm_cast_params cast_params{};
+    cm_cast_info cast_info{};
+    DevBuf<CmCastRayDev> cast_rays;      // max_poses * n_bearings records
+    DevBuf<uint32_t> cast_poses;         // max_poses poses of three words, as an evaluate uploads them
+    DevBuf<uint32_t> cast_bearings;      // n_bearings binary angles
+    DevBuf<uint32_t> cast_dirs;          // CM_CAST_DIRS pairs of int16_t
+    DevBuf<unsigned char> cast_steps;    // nx * ny bytes: the skip table
+    DevBuf<uint32_t> cast_words;         // CM_CAST_WORDS status counts
+    PinnedBuf<uint32_t> cast_host;       // the counts read back
+
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
     SearchIndex nrm;
@@ -536,6 +552,13 @@ int map_mcl_init_pose(cm_ctx* c, const float v[6]);
 int map_mcl_init_uniform(cm_ctx* c);
 int map_mcl_predict(cm_ctx* c, const float v[6]);
 int map_mcl_update(cm_ctx* c);
+// The cast layer behind the cost layer. map_cast_configure: room for q's rays over the map's window, the bearings (nullptr:
+// evenly spaced) and the direction table uploaded (q nullptr: the buffers go). map_cast_evaluate runs a call that cm_api.cpp has
+// checked: n poses on the host, or, with host_poses nullptr, the localisation layer's n particles in place.
+// cast_direction_table: the CM_CAST_DIRS pairs of step 3 for range_cells into dst.
+void cast_direction_table(uint32_t range_cells, int16_t* dst);
+int map_cast_configure(cm_ctx* c, const cm_cast_params* q, const uint32_t* bearings);
+int map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n);
 // A recorded state table into the configured map (cm_map_load has checked it): state, image, anchor, staleness.
 int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]);
 // The search layer behind the cost layer. map_msearch_configure: room for q over the map's window, the field table at radius

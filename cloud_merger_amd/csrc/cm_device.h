@@ -556,3 +556,30 @@ struct CmMclMoveDev {
     float sc_a, sc_b, sc_yaw;
     unsigned long long base;
 };
+
+// Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses in the map. k_cast_rays gives one
+// lane one ray, CM_CAST_BLOCK threads per workgroup, the grid sized to the device with a stride over the rays, so that a wave
+// holds consecutive bearings of one pose; the direction table (CM_CAST_DIRS pairs of int16_t, 16 KiB) is staged in LDS.
+// k_cast_steps writes the skip table, one byte per window cell: 0 on an occupied cell, otherwise the number of steps a ray
+// may take from there, capped at CM_CAST_STEP_CAP. The layer's four count words on the device are indexed by status.
+#define CM_CAST_BLOCK 256
+#define CM_CAST_DIRS 4096
+#define CM_CAST_STEP_CAP 255u
+#define CM_CAST_MAX_POSES_DEV 65536u
+#define CM_CAST_MAX_BEARINGS_DEV 4096u
+#define CM_CAST_MAX_RANGE_DEV 1024u
+#define CM_CAST_MAX_RAYS_DEV (1u << 24)
+#define CM_CAST_WORDS 4
+struct CmCastDev {
+    float inv;                         // 1.0f / cell
+    int32_t ax, ay;                    // the map's anchor
+    uint32_t nx, ny;
+    uint32_t n_poses, n_bearings;
+    uint32_t pose_words;               // 32-bit words from one pose to the next: 3 (cm_cast_pose) or 6 (cm_mcl_particle)
+    uint32_t plain;                    // CM_CAST_PLAIN
+};
+struct CmCastRayDev {                  // cm_cast_ray
+    uint16_t k;
+    uint8_t status, pad;
+    int16_t jx, jy;
+};

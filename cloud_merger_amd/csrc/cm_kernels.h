@@ -321,6 +321,14 @@ void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* ds
 // The image of a state table (the map's step 8), for cm_map_load: (logodds, n_obs) per cell into one byte per cell.
 void cmk_map_image(hipStream_t s, const void* state, uint32_t n_cells, int l_free, int l_occ, void* image);
 
+// ---- cast layer behind the cost layer (cm_kernels_cast.hip) ---------------------------------------------------------------------------
+// steps: one byte per window cell, cmk_cast_steps writes it from dist2 (the skip table; not read under g.plain). poses: g.n_poses
+// records g.pose_words words apart, x, y and h in the first three. bearings: g.n_bearings binary angles. dirs: CM_CAST_DIRS pairs of
+// int16_t. rays: g.n_poses * g.n_bearings records of cm_cast_ray. words: the CM_CAST_WORDS status counts, zero before the launch.
+void cmk_cast_steps(hipStream_t s, const uint32_t* dist2, uint32_t n_cells, unsigned char* steps);
+void cmk_cast_rays(hipStream_t s, const void* image, const unsigned char* steps, const CmCastDev& g, const void* poses, const uint32_t* bearings,
+                   const void* dirs, void* rays, uint32_t* words);
+
 // ---- frontier layer behind the plan layer (cm_kernels_front.hip) -------------------------------------------------------------------
 // image, cost, pot: the map's image, the cost and the plan layer's tables. labels: a word per cell (parents, then roots, then
 // frontier numbers). size: a word per cell (a root's cell count, then its number). counts: g.n_blocks words. info:

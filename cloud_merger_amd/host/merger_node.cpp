@@ -291,6 +291,10 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             ok = read(is, sd[0], sd[1], sd[2]);
             for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(sd[k]) && sd[k] >= 0.0f && sd[k] <= 1024.0f;
         }
+        else if (key == "cast") ok = read_flag(is, &c.cast_enable);
+        else if (key == "cast_bearings") ok = read(is, c.cast_bearings) && c.cast_bearings >= 1u && c.cast_bearings <= CM_CAST_MAX_BEARINGS;
+        else if (key == "cast_range") ok = read(is, c.cast_range_cells) && c.cast_range_cells >= 1u && c.cast_range_cells <= CM_CAST_MAX_RANGE_CELLS;
+        else if (key == "cast_plain") ok = read_flag(is, &c.cast_plain);
         else if (key == "normals_k") ok = read(is, c.normals_k) && (c.normals_k == 0 || (c.normals_k >= 3 && c.normals_k <= CM_NORMAL_MAX_K));
         else if (key == "normals_viewpoint") {
             float* v = c.normals_viewpoint;
@@ -319,6 +323,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     if (c.grid_raycast && !(c.grid_cell > 0.0f)) { if (err) *err = "grid_raycast needs grid_cell > 0"; return false; }
     if (c.match_enable && c.match_search_enable) { if (err) *err = "match and match_search exclude each other"; return false; }
     if (c.mcl_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "mcl needs the cost layer (map and map_inflation)"; return false; }
+    if (c.cast_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "cast needs the cost layer (map and map_inflation)"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
     return true;
@@ -352,6 +357,10 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
     }
     if (cfg_.mcl_enable && !(cfg_.map_cell > 0.0f && cfg_.map_inflation_radius > 0.0f)) {
         error_ = "mcl needs the cost layer (map and map_inflation)";
+        return;
+    }
+    if (cfg_.cast_enable && !(cfg_.map_cell > 0.0f && cfg_.map_inflation_radius > 0.0f)) {
+        error_ = "cast needs the cost layer (map and map_inflation)";
         return;
     }
     uint32_t mask = 0;
@@ -396,6 +405,10 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                 const cm_mcl_params lp{cfg_.mcl_particles, cfg_.mcl_max_beams, cfg_.mcl_range_cells, cfg_.mcl_sigma, cfg_.mcl_max_dist, cfg_.mcl_tau,
                                        cfg_.mcl_resample_frac, cfg_.mcl_resample_always ? CM_MCL_RESAMPLE_ALWAYS : 0u, cfg_.mcl_seed};
                 if (cm_map_mcl_configure(ctx_, &lp) != CM_OK) refuse("cm_map_mcl_configure");
+            }
+            if (ctx_ && cfg_.cast_enable) {                        // the cast layer behind the cost layer: one pose, evenly spaced bearings
+                const cm_cast_params kp{1u, cfg_.cast_bearings, cfg_.cast_range_cells, cfg_.cast_plain ? CM_CAST_PLAIN : 0u};
+                if (cm_map_cast_configure(ctx_, &kp, nullptr) != CM_OK) refuse("cm_map_cast_configure");
             }
             if (ctx_ && cfg_.map_plan_neutral > 0u) {              // the plan layer behind the cost layer
                 const cm_plan_params pp{cfg_.map_plan_neutral, cfg_.map_plan_factor_q8, cfg_.map_plan_allow_unknown ? CM_PLAN_ALLOW_UNKNOWN : 0u,
@@ -657,6 +670,28 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
         map_dist2_.clear();
         set_error(cm_last_error(ctx_));
         return st;
+    }
+    // The virtual scan of the map behind the cost update: one pose, the one that was set (a match does not move it). A call the
+    // library refuses leaves the scan empty and says so.
+    cast_rays_.clear();
+    cast_info_ = cm_cast_info{};
+    if (cfg_.cast_enable && cfg_.map_inflation_radius > 0.0f) {
+        float set[12];
+        {
+            std::lock_guard<std::mutex> lk(pose_mu_);
+            std::memcpy(set, pose_, sizeof set);
+        }
+        const double yaw = std::atan2(static_cast<double>(set[4]), static_cast<double>(set[0]));
+        const cm_cast_pose cp{set[3], set[7], static_cast<uint32_t>(static_cast<int64_t>(std::rint(yaw * (4294967296.0 / 6.283185307179586))))};
+        cast_rays_.resize(cfg_.cast_bearings);
+        int cs = cm_map_cast_evaluate(ctx_, &cp, 1u, &cast_info_);
+        if (cs == CM_OK) cs = cm_map_cast_copy(ctx_, cast_rays_.data(), cast_rays_.size(), nullptr);
+        if (cs != CM_OK) {
+            cast_rays_.clear();
+            cast_info_ = cm_cast_info{};
+            set_error(cm_last_error(ctx_));
+            if (cs != CM_BAD_ARG) return cs;
+        }
     }
     // The plan behind the cost update: the potential to the goal, then the path from the vehicle cell. A goal or a vehicle
     // outside the window is the caller's to mend (the window has scrolled away from it): the frame stands, the plan is empty.

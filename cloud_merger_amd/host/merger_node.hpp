@@ -183,6 +183,14 @@ struct NodeConfig {
     bool mcl_init_uniform = false;                   // mcl_init uniform; otherwise around the pose with mcl_init_sd
     float mcl_init_sd[3] = {0.5f, 0.5f, 0.2f};       // sd_x, sd_y (metres), sd_yaw (radians)
     float mcl_noise[3] = {0.05f, 0.05f, 0.02f};      // sd_fwd, sd_left (metres), sd_yaw (radians) of every predict
+    // The cast layer (cm_map_cast_configure, cm_map_cast_evaluate): the virtual scan of the map. Off by default. On (it needs
+    // the cost layer; without one load_config refuses the file and the node does not start): after each frame's cost update
+    // the node casts cast_bearings evenly spaced rays of at most cast_range_cells cells from set_pose()'s pose (cast_rays(),
+    // cast_info()). cast_plain selects the cell-by-cell walk; the rays are the same.
+    bool cast_enable = false;
+    uint32_t cast_bearings = 360;
+    uint32_t cast_range_cells = 256;
+    bool cast_plain = false;
     // Normals and curvature of every published voxel cloud (cm_result_normals; pcl::NormalEstimation with setKSearch). Off by
     // default (normals_k 0). On: after the frame has been waited for the node asks for the table and keeps it until the next
     // frame (normals()). The viewpoint is in the base frame; PCL's default is the origin.
@@ -241,6 +249,8 @@ struct NodeConfig {
 //   mcl <0|1> | mcl_particles <n> | mcl_beams <max_beams> <range_cells> | mcl_field <sigma> <max_dist> | mcl_tau <tau> |
 //   mcl_resample <frac> <always 0|1> | mcl_seed <seed> | mcl_init <pose sd_x sd_y sd_yaw | uniform> | mcl_noise <sd_fwd sd_left sd_yaw>
 //   (the localisation layer behind the cost layer, which it needs: a file with mcl 1 and no map_inflation is refused)
+//   cast <0|1> | cast_bearings <n> | cast_range <cells> | cast_plain <0|1>
+//   (the cast layer behind the cost layer, which it needs: the virtual scan of the map from the set pose after every frame)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
 //   align_prev <0|1> | align_max_corr <metres> | align_normals_k <n> | align_max_iterations <n>   (the previous voxel cloud
 //   aligned to every new one: 3..64 neighbours for the normals, 0..64 iterations)
@@ -377,6 +387,10 @@ public:
     bool mcl_started() const { return mcl_started_; }
     const cm_mcl_info& mcl_info() const { return mcl_info_; }
     const std::vector<cm_mcl_particle>& mcl_particles() const { return mcl_particles_; }
+    // cast 1: the rays of the virtual scan behind the last frame's cost update (empty where the library refused the cast) and
+    // their counts by status.
+    const std::vector<cm_cast_ray>& cast_rays() const { return cast_rays_; }
+    const cm_cast_info& cast_info() const { return cast_info_; }
     // normals_k > 0: the normal and curvature of each voxel of the frame waited for last, in the order of the published cloud.
     const std::vector<cm_voxel_normal>& normals() const { return normals_; }
     // align_prev: the registration of the previous frame's published records against the frame waited for last; false while
@@ -462,6 +476,8 @@ private:
     float mcl_prev_[3] = {0.0f, 0.0f, 0.0f};         // x, y, yaw of the set pose at the last init or predict
     cm_mcl_info mcl_info_{};
     std::vector<cm_mcl_particle> mcl_particles_;
+    std::vector<cm_cast_ray> cast_rays_;
+    cm_cast_info cast_info_{};
     int map_of_frame(const cm_result& r);          // after cm_wait: cm_map_integrate and the two copies (the cost layer's update and its two) when the config asks for it
     std::vector<cm_voxel_normal> normals_;
     int normals_of_frame(const cm_result& r);      // after cm_wait: cm_result_normals when the config asks for it

@@ -1377,6 +1377,103 @@ CM_API int cm_map_mcl_device(cm_ctx* ctx, const void** particles, const void** w
  * a NULL dst, first_p + n_p above 2^32 (nothing is written). */
 CM_API int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t n_p, uint32_t i, uint64_t* dst);
 
+/* ---- the cast layer: expected ranges from many poses in the occupancy map (an extension) ----------------------------------
+ * Every other layer looks single cells up. This one answers what the map was built by ray casting to answer: from this pose,
+ * in this direction, how far is the first occupied cell? It serves a beam model, a virtual LaserScan of the map, visibility
+ * from a candidate pose and simulated scans. It is configured once behind the cost layer and evaluated on
+ * request for n poses x n_bearings rays. Everything after the origin cell is integer arithmetic: the rays and the info are bit
+ * for bit a function of the map's image, info and cell, the parameters, the bearings and the poses.
+ * Input: the map's image I as cm_map_occupancy_copy returns it, the map's info (anchor, nx, ny) and cell, the cost layer's
+ * fresh dist2 (it only lets the device skip: no output depends on it), the parameters, the bearings and per evaluation n poses.
+ *   1. Pose, cm_cast_pose (12 bytes): x, y (fp32) in the map's world frame and h, a binary angle, a full turn is 2^32. The
+ *      origin cell is step 1 of the map's semantics per axis (floorf(x * inv), the same existence test) minus the map's
+ *      anchor. An origin whose cell does not exist (NaN, +-inf, beyond +-2^30) or lies outside the window gives every ray of
+ *      that pose {status CM_CAST_NO_ORIGIN, k 0, jx 0, jy 0}.
+ *   2. Bearings. n_bearings binary angles b_a, taken at configure time; a NULL list means evenly spaced,
+ *      b_a = (uint32_t)(((uint64_t)a << 32) / n_bearings). Ray (p, a) has the heading H = h_p + b_a, wrapping; its direction
+ *      entry is e = ((H + 0x80000) >> 20) & 4095, the rollout layer's rule.
+ *   3. Direction table. 4096 pairs of int16_t, built once on the host from the CM_TRAJ_HEADINGS table (c_e, s_e) of
+ *      cm_traj_directions: E_e = (rint((double)c_e * (double)range_cells), rint((double)s_e * (double)range_cells)), ties to
+ *      even. cm_cast_directions returns it. With (dx, dy) = E_e, L = max(|dx|, |dy|). L >= 1 for every entry and every
+ *      range_cells >= 1: the table's angle th lies within pi / 4 of an axis, so the larger of |cos th| and |sin th| is at least
+ *      cos(pi / 4) = 0.7071..., its fp32 rounding is at least 0.70710677, the product with range_cells >= 1 is at least that
+ *      and rint of a value >= 0.5000...1 is at least 1. |c_e|, |s_e| <= 1 gives |dx|, |dy| <= range_cells: int16_t holds them.
+ *   4. Line: cm_result_grid_rays' step 5, unchanged. At step k the ray's cell is o + (rdiv(k * dx, L), rdiv(k * dy, L)) for
+ *      k = 0 .. L; unlike the map's rays the end cell (k = L) is included.
+ *   5. Walk. For k = 0, 1, .., L in order: a cell outside the window ends the ray with status CM_CAST_OFF_MAP, and step
+ *      k - 1 is reported (k >= 1 here: the origin is inside); else I(cell) == 100 ends it with status CM_CAST_HIT at step k;
+ *      I == -1 and I == 0 are both passed through. After step L without either the status is CM_CAST_MAX at step L. An
+ *      occupied origin cell is a HIT at k = 0.
+ *   6. Record, cm_cast_ray (8 bytes): k, the reported step; status; a zero byte; jx, jy, the reported step's cell minus the
+ *      origin cell. Ray (p, a) is entry p * n_bearings + a. The metric range is not part of the table
+ *      (cell * sqrt(jx^2 + jy^2)).
+ *   7. cm_cast_info: n_poses, n_bearings and the four status counts over all rays (integer sums).
+ * CM_CAST_PLAIN selects a device walk that does what steps 4 and 5 say, cell by cell, reading the image. Without it the
+ * device skips cells that dist2 proves free of an occupied cell (DESIGN.md §30 has the rule and its proof); the outputs are
+ * the same bytes either way.
+ * cm_map_cast_configure refuses with CM_BAD_ARG (cm_last_error says why): no configured cost layer; max_poses outside
+ * 1..CM_CAST_MAX_POSES, n_bearings outside 1..CM_CAST_MAX_BEARINGS, range_cells outside 1..CM_CAST_MAX_RANGE_CELLS;
+ * max_poses * n_bearings above CM_CAST_MAX_RAYS; unknown flag bits; a frame in flight. cm_map_cast_evaluate refuses: no layer; a
+ * stale or absent dist2 (no cm_map_cost_update since the last cm_map_integrate, cm_map_load or cm_map_cost_configure); n of 0
+ * or above max_poses; NULL poses; a frame in flight. cm_map_cast_evaluate_mcl casts from the localisation layer's current
+ * particles (x, y, h read from the 24-byte records in place; n = n_particles, refused above max_poses) and is refused without
+ * initialised particles; it changes nothing of that layer. A map with n_frames == 0 is allowed: every ray then ends MAX or
+ * OFF_MAP. All memory of the layer is taken by cm_map_cast_configure (the rays, the poses, the bearings, the direction table,
+ * one byte per window cell for the skips, the count words and their page-locked copy): no other call allocates. The rays and
+ * the info are stale from cm_map_cast_configure and from every cm_map_integrate, cm_map_load and cm_map_cost_update until the
+ * next evaluate: cm_map_cast_copy and cm_map_cast_device then refuse with CM_BAD_ARG and say since which call.
+ * cm_map_cost_configure and cm_map_configure, in either form, free the layer. It reads the map, the cost layer and the
+ * particles and writes buffers of its own only: no other layer's tables, staleness or timing change. A NULL context leaves
+ * every output untouched. With CM_FLAG_PROFILE, cm_get_stage_times after an evaluate lists cast_upload, k_cast_steps (only in
+ * the first evaluate after a cm_map_cost_update, and never under CM_CAST_PLAIN) and k_cast_rays. Not modelled: stopping at or
+ * counting unknown cells, sub-cell origins (a ray starts at its origin cell's centre, as the map's own rays do), 3-D casting,
+ * the use of the ranges inside cm_map_mcl_update. */
+#define CM_CAST_MAX_POSES 65536
+#define CM_CAST_MAX_BEARINGS 4096
+#define CM_CAST_MAX_RANGE_CELLS 1024
+#define CM_CAST_MAX_RAYS 16777216
+#define CM_CAST_PLAIN 1u
+#define CM_CAST_MAX 0                  /* status values, not bits */
+#define CM_CAST_HIT 1
+#define CM_CAST_OFF_MAP 2
+#define CM_CAST_NO_ORIGIN 3
+typedef struct cm_cast_params {        /* 16 bytes, no padding */
+    uint32_t max_poses;                /* 1 .. CM_CAST_MAX_POSES; max_poses * n_bearings <= CM_CAST_MAX_RAYS */
+    uint32_t n_bearings;               /* 1 .. CM_CAST_MAX_BEARINGS */
+    uint32_t range_cells;              /* the reach of a ray in cells; 1 .. CM_CAST_MAX_RANGE_CELLS */
+    uint32_t flags;                    /* CM_CAST_PLAIN or 0 */
+} cm_cast_params;
+typedef struct cm_cast_pose {          /* 12 bytes */
+    float x, y;                        /* position in the map's world frame (m) */
+    uint32_t h;                        /* heading, a binary angle */
+} cm_cast_pose;
+typedef struct cm_cast_ray {           /* 8 bytes, ray (p, a) is entry p * n_bearings + a */
+    uint16_t k;                        /* the reported step */
+    uint8_t status;                    /* CM_CAST_MAX, _HIT, _OFF_MAP or _NO_ORIGIN */
+    uint8_t _pad;                      /* zero */
+    int16_t jx, jy;                    /* the reported step's cell minus the origin cell */
+} cm_cast_ray;
+typedef struct cm_cast_info {          /* 24 bytes */
+    uint32_t n_poses, n_bearings;
+    uint32_t n_max, n_hit, n_off_map, n_no_origin;   /* rays by status; their sum is n_poses * n_bearings */
+} cm_cast_info;
+/* Non-NULL parameters allocate the layer and take the bearings (n_bearings of them, or NULL: evenly spaced); NULL parameters
+ * free it. */
+CM_API int cm_map_cast_configure(cm_ctx* ctx, const cm_cast_params* p, const uint32_t* bearings);
+/* Steps 1 to 7 for n poses. *out may be NULL. */
+CM_API int cm_map_cast_evaluate(cm_ctx* ctx, const cm_cast_pose* host_poses, uint32_t n, cm_cast_info* out);
+/* The same from the localisation layer's current particles. */
+CM_API int cm_map_cast_evaluate_mcl(cm_ctx* ctx, cm_cast_info* out);
+/* Host copy of the n_poses * n_bearings rays of the last evaluate; capacity in rays. Fewer: CM_CAPACITY (nothing is copied;
+ * *info, which may be NULL, is still written). */
+CM_API int cm_map_cast_copy(cm_ctx* ctx, cm_cast_ray* host_dst, uint64_t capacity, cm_cast_info* info);
+/* The same table in device memory owned by the context, valid until the next evaluate or configure call of the map, the cost
+ * layer or this layer. Either output may be NULL. */
+CM_API int cm_map_cast_device(cm_ctx* ctx, const void** rays, cm_cast_info* info);
+/* The direction table of step 3 for range_cells: 2 * 4096 int16_t. A host function: no context, no GPU. CM_BAD_ARG: a NULL
+ * dst, range_cells outside 1..CM_CAST_MAX_RANGE_CELLS; a capacity below 4096 pairs: CM_CAPACITY (nothing is written). */
+CM_API int cm_cast_directions(uint32_t range_cells, int16_t* dst, uint64_t capacity_pairs);
+
 /* ---- surface normals and curvature of the result (pcl::NormalEstimation, setKSearch; an extension) --------------------
  * One unit normal and one curvature per published point, estimated from its k nearest neighbours in the published cloud,
  * computed on request after a frame. Input: the n = n_out records of the last result, c_0 .. c_{n-1} in the
