@@ -626,6 +626,29 @@ int cm_merged_copy(cm_ctx* c, void* host_dst, uint64_t capacity, uint64_t* n_poi
     return copy_fused(c, c->frame_mask, host_dst, capacity, n_points, true);
 }
 
+// How a call hands n elements of `elem` bytes at src (HBM) to the caller: the capacity refusal with the call's own text, the
+// missing destination (after an empty result's CM_OK where the call answers an empty result without one), the copy, the wait.
+static int copy_out(cm_ctx* c, void* host_dst, const void* src, uint64_t n, size_t elem, uint64_t capacity, const char* too_small,
+                    bool empty_is_ok = false) {
+    if (n > capacity) return fail(c, CM_CAPACITY, too_small);
+    if (empty_is_ok && n == 0) return CM_OK;
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(host_dst, src, n * elem, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->bytes_d2h += n * elem;
+    return CM_OK;
+}
+
+// The same for a table the context keeps on the host (the cost table, the field table).
+static int table_out(cm_ctx* c, uint8_t* host_dst, const std::vector<unsigned char>& table, uint64_t capacity, uint64_t* n, const char* too_small) {
+    if (n) *n = table.size();
+    if (table.size() > capacity) return fail(c, CM_CAPACITY, too_small);
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    std::memcpy(host_dst, table.data(), table.size());
+    return CM_OK;
+}
+
 static_assert(sizeof(cm_voxel_cov) == 80 && sizeof(CmVoxelCovDev) == sizeof(cm_voxel_cov), "cm_voxel_cov is 80 bytes");
 static_assert(CM_COV_VALID == CM_COV_VALID_DEV && CM_COV_INFLATED == CM_COV_INFLATED_DEV, "flags mirror the header");
 
@@ -639,12 +662,7 @@ int cm_result_voxel_cov(cm_ctx* c, const cm_cov_params* p, cm_voxel_cov* host_ds
     if (c->result.n_out && !host_dst) return fail(c, CM_BAD_ARG, "no destination");
     e = voxel_cov(c, q);
     if (e != CM_OK) return e;
-    const uint64_t n = c->result.n_out;
-    if (n == 0) return CM_OK;
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->cov_entries, n * sizeof(cm_voxel_cov), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_voxel_cov);
-    return CM_OK;
+    return copy_out(c, host_dst, c->cov_entries, c->result.n_out, sizeof(cm_voxel_cov), capacity, "destination too small", true);
 }
 
 int cm_result_voxel_cov_device(cm_ctx* c, const cm_cov_params* p, const void** dev_ptr, uint64_t* n) {
@@ -781,12 +799,7 @@ int cm_result_grid_map(cm_ctx* c, const cm_grid_params* p, cm_grid_cell* host_ds
     e = grid_map(c, *p);
     if (e != CM_OK) return e;
     const uint64_t n = c->grid_n;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "grid destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->grid_cells, n * sizeof(cm_grid_cell), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_grid_cell);
-    return CM_OK;
+    return copy_out(c, host_dst, c->grid_cells, n, sizeof(cm_grid_cell), capacity_cells, "grid destination too small");
 }
 
 int cm_result_grid_map_device(cm_ctx* c, const cm_grid_params* p, const void** dev_ptr, uint64_t* n_cells) {
@@ -810,13 +823,7 @@ int cm_grid_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells,
     if (!c->grid_have) return fail(c, CM_BAD_ARG, "no grid map of the last result (cm_result_grid_map first)");
     const uint64_t n = c->grid_n;
     *n_cells = n;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "occupancy destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->grid_image, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n;
-    return CM_OK;
+    return copy_out(c, host_dst, c->grid_image, n, 1, capacity_cells, "occupancy destination too small");
 }
 
 static_assert(sizeof(cm_grid_ray_cell) == 8 && offsetof(cm_grid_ray_cell, n_end) == 4 && sizeof(cm_ray_params) == 8,
@@ -839,12 +846,7 @@ int cm_result_grid_rays(cm_ctx* c, const cm_grid_params* p, const cm_ray_params*
     e = grid_rays(c, *p, rr);
     if (e != CM_OK) return e;
     const uint64_t n = c->ray_n;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "ray destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ray_cells, n * sizeof(cm_grid_ray_cell), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_grid_ray_cell);
-    return CM_OK;
+    return copy_out(c, host_dst, c->ray_cells, n, sizeof(cm_grid_ray_cell), capacity_cells, "ray destination too small");
 }
 
 int cm_result_grid_rays_device(cm_ctx* c, const cm_grid_params* p, const cm_ray_params* r, const void** dev_ptr, uint64_t* n_cells) {
@@ -869,18 +871,39 @@ int cm_grid_ray_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_ce
     if (!c->ray_have) return fail(c, CM_BAD_ARG, "no rays of the last result (cm_result_grid_rays first)");
     const uint64_t n = c->ray_n;
     *n_cells = n;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "cleared occupancy destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->ray_image, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n;
-    return CM_OK;
+    return copy_out(c, host_dst, c->ray_image, n, 1, capacity_cells, "cleared occupancy destination too small");
 }
 
 static_assert(sizeof(cm_map_params) == 48 && offsetof(cm_map_params, max_range_cells) == 44 && sizeof(cm_map_cell) == 8 &&
                   offsetof(cm_map_cell, n_obs) == 4 && sizeof(cm_map_info) == 32 && offsetof(cm_map_info, n_frames) == 16,
               "cm_map_params is 48 bytes, cm_map_cell 8 (the kernels' two words), cm_map_info 32");
+
+// What every call on a layer of the map refuses first (cm_map_layers.hpp): a frame in flight, a missing ancestor, the missing
+// layer, and for a read a stale result. layer_fresh_check is the last part alone.
+static int layer_check(cm_ctx* c, int layer, bool read) {
+    const std::string why = layer_refusal(c->layers, c->pending, c->frame_serial, layer, read, c->map.info.n_frames != 0);
+    return why.empty() ? CM_OK : fail(c, CM_BAD_ARG, why);
+}
+static int layer_fresh_check(cm_ctx* c, int layer) {
+    const std::string why = layer_stale(c->layers, c->frame_serial, layer, c->map.info.n_frames != 0);
+    return why.empty() ? CM_OK : fail(c, CM_BAD_ARG, why);
+}
+// What a layer's configure call refuses first: a frame in flight and, where p is there, a missing ancestor.
+static int configure_check(cm_ctx* c, int layer, const void* p) {
+    const std::string why = layer_configure_refusal(c->layers, c->pending, layer, p == nullptr);
+    return why.empty() ? CM_OK : fail(c, CM_BAD_ARG, why);
+}
+// What the producers behind the cost layer refuse about its tables, in their own wording.
+static int cost_fresh_check(cm_ctx* c) { return c->layers[LAYER_COST].fresh() ? CM_OK : fail(c, CM_BAD_ARG, cost_stale_text()); }
+
+// What cm_map_integrate and the two matchers refuse about a pose; v: the vehicle's cell.
+static int pose_check(cm_ctx* c, const float pose[12], int v[2]) {
+    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    return CM_OK;
+}
 
 // The refusals of cm_map_configure about *p.
 static int map_params_check(cm_ctx* c, const cm_map_params* p) {
@@ -903,7 +926,7 @@ static int map_params_check(cm_ctx* c, const cm_map_params* p) {
 int cm_map_configure(cm_ctx* c, const cm_map_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_MAP, p)) return e;
     if (p)
         if (const int e = map_params_check(c, p)) return e;
     return map_configure(c, p);
@@ -913,79 +936,57 @@ int cm_map_integrate(cm_ctx* c, const float pose[12], cm_map_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = centroid_result_check(c)) return e;
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    if (!c->layers[LAYER_MAP].on) return fail(c, CM_BAD_ARG, LAYER_TABLE[LAYER_MAP].absent);
     int v[2];
-    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
-    if (c->map_serial == c->frame_serial) return fail(c, CM_BAD_ARG, "the last frame was already integrated");
+    if (const int e = pose_check(c, pose, v)) return e;
+    if (c->map.serial == c->frame_serial) return fail(c, CM_BAD_ARG, "the last frame was already integrated");
     if (const int e = map_integrate(c, pose, v)) return e;
-    if (out) *out = c->map_info;
-    return CM_OK;
-}
-
-// The refusals the three reads of the map share.
-static int map_read_check(cm_ctx* c) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
+    if (out) *out = c->map.info;
     return CM_OK;
 }
 
 int cm_map_copy(cm_ctx* c, cm_map_cell* host_dst, uint64_t capacity_cells, cm_map_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = map_read_check(c)) return e;
-    if (info) *info = c->map_info;
-    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "map destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->map_state[c->map_cur], n * sizeof(cm_map_cell), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_map_cell);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_MAP, true)) return e;
+    if (info) *info = c->map.info;
+    const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    return copy_out(c, host_dst, c->map.state[c->map.cur], n, sizeof(cm_map_cell), capacity_cells, "map destination too small");
 }
 
 int cm_map_device(cm_ctx* c, const void** dev_ptr, cm_map_info* info) {
     if (!c || !dev_ptr) return CM_BAD_ARG;
     *dev_ptr = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = map_read_check(c)) return e;
-    if (info) *info = c->map_info;
-    *dev_ptr = c->map_state[c->map_cur];
+    if (const int e = layer_check(c, LAYER_MAP, true)) return e;
+    if (info) *info = c->map.info;
+    *dev_ptr = c->map.state[c->map.cur];
     return CM_OK;
 }
 
 int cm_map_occupancy_copy(cm_ctx* c, int8_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = map_read_check(c)) return e;
-    if (info) *info = c->map_info;
-    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "map image destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->map_image, n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n;
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_MAP, true)) return e;
+    if (info) *info = c->map.info;
+    const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    return copy_out(c, host_dst, c->map.image, n, 1, capacity_cells, "map image destination too small");
 }
 
 int cm_map_load(cm_ctx* c, const cm_map_cell* host_src, uint64_t n_cells, const int32_t anchor[2], cm_map_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = map_read_check(c)) return e;
+    if (const int e = layer_check(c, LAYER_MAP, true)) return e;
     if (!host_src) return fail(c, CM_BAD_ARG, "no state table");
     if (!anchor) return fail(c, CM_BAD_ARG, "no anchor");
-    if (n_cells != static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny) return fail(c, CM_BAD_ARG, "n_cells is not nx * ny");
+    if (n_cells != static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny) return fail(c, CM_BAD_ARG, "n_cells is not nx * ny");
     for (int k = 0; k < 2; ++k)
         if (anchor[k] <= -(1 << 30) || anchor[k] >= (1 << 30)) return fail(c, CM_BAD_ARG, "the anchor lies 2^30 cells or more from the world origin");
     for (uint64_t i = 0; i < n_cells; ++i)
-        if (host_src[i].logodds < c->map_params.l_min || host_src[i].logodds > c->map_params.l_max)
+        if (host_src[i].logodds < c->map.params.l_min || host_src[i].logodds > c->map.params.l_max)
             return fail(c, CM_BAD_ARG, "a logodds lies outside [l_min, l_max]");
     if (const int e = map_load(c, host_src, anchor)) return e;
-    if (out) *out = c->map_info;
+    if (out) *out = c->map.info;
     return CM_OK;
 }
 
@@ -995,64 +996,46 @@ static_assert(CM_COST_MAX_AXIS == CM_COST_MAX_AXIS_DEV && CM_COST_MAX_RADIUS_CEL
 int cm_map_cost_configure(cm_ctx* c, const cm_cost_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_COST, p)) return e;
     uint32_t R = 0;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (const char* why = cm_cost_refusal(c->map_params.cell, p->inscribed_radius, p->inflation_radius, p->cost_scaling,
+        if (const char* why = cm_cost_refusal(c->map.params.cell, p->inscribed_radius, p->inflation_radius, p->cost_scaling,
                                               CM_COST_MAX_RADIUS_CELLS, &R))
             return fail(c, CM_BAD_ARG, why);
         if (p->flags & ~CM_COST_INFLATE_UNKNOWN) return fail(c, CM_BAD_ARG, "unknown flag bits");
-        if (c->map_info.nx > CM_COST_MAX_AXIS || c->map_info.ny > CM_COST_MAX_AXIS)
+        if (c->map.info.nx > CM_COST_MAX_AXIS || c->map.info.ny > CM_COST_MAX_AXIS)
             return fail(c, CM_BAD_ARG, "the map is wider or taller than CM_COST_MAX_AXIS cells");
     }
     return map_cost_configure(c, p, R);
 }
 
-// The refusals every call on a configured cost layer shares; the reads also refuse stale tables.
-static int cost_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (read && !c->cost_fresh)
-        return fail(c, CM_BAD_ARG, c->map_info.n_frames ? "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate"
-                                                        : "the cost tables are stale: no cm_map_cost_update since cm_map_cost_configure");
-    return CM_OK;
-}
-
 int cm_map_cost_update(cm_ctx* c, cm_map_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = cost_check(c, false)) return e;
+    if (const int e = layer_check(c, LAYER_COST, false)) return e;
     if (const int e = map_cost_update(c)) return e;
-    if (out) *out = c->map_info;
+    if (out) *out = c->map.info;
     return CM_OK;
 }
 
 // One of the two tables to the host: `bytes` per cell from src.
 static int cost_table_to_host(cm_ctx* c, void* host_dst, const void* src, size_t bytes, uint64_t capacity_cells, cm_map_info* info, const char* what) {
-    if (const int e = cost_check(c, true)) return e;
-    if (info) *info = c->map_info;
-    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, what);
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, src, n * bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * bytes;
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_COST, true)) return e;
+    if (info) *info = c->map.info;
+    const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    return copy_out(c, host_dst, src, n, bytes, capacity_cells, what);
 }
 
 int cm_map_cost_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    return cost_table_to_host(c, host_dst, c->cost_cells, 1, capacity_cells, info, "cost destination too small");
+    return cost_table_to_host(c, host_dst, c->cost.cells, 1, capacity_cells, info, "cost destination too small");
 }
 
 int cm_map_dist_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_map_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    return cost_table_to_host(c, host_dst, c->cost_dist2, sizeof(uint32_t), capacity_cells, info, "distance destination too small");
+    return cost_table_to_host(c, host_dst, c->cost.dist2, sizeof(uint32_t), capacity_cells, info, "distance destination too small");
 }
 
 int cm_map_cost_device(cm_ctx* c, const void** cost, const void** dist2, cm_map_info* info) {
@@ -1060,23 +1043,18 @@ int cm_map_cost_device(cm_ctx* c, const void** cost, const void** dist2, cm_map_
     if (cost) *cost = nullptr;
     if (dist2) *dist2 = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = cost_check(c, true)) return e;
-    if (info) *info = c->map_info;
-    if (cost) *cost = c->cost_cells;
-    if (dist2) *dist2 = c->cost_dist2;
+    if (const int e = layer_check(c, LAYER_COST, true)) return e;
+    if (info) *info = c->map.info;
+    if (cost) *cost = c->cost.cells;
+    if (dist2) *dist2 = c->cost.dist2;
     return CM_OK;
 }
 
 int cm_map_cost_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uint64_t* n) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = cost_check(c, false)) return e;
-    const uint64_t n_lut = c->cost_lut_host.size();
-    if (n) *n = n_lut;
-    if (n_lut > capacity) return fail(c, CM_CAPACITY, "cost table destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    std::memcpy(host_dst, c->cost_lut_host.data(), n_lut);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_COST, false)) return e;
+    return table_out(c, host_dst, c->cost.lut_host, capacity, n, "cost table destination too small");
 }
 
 static_assert(sizeof(cm_plan_params) == 16 && sizeof(cm_plan_info) == 16 && sizeof(cm_path_info) == 32, "the plan layer's three structs");
@@ -1086,14 +1064,12 @@ static_assert(CM_PATH_FOUND == CM_PLAN_PATH_FOUND_DEV && CM_PATH_UNREACHABLE == 
 int cm_map_plan_configure(cm_ctx* c, const cm_plan_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_PLAN, p)) return e;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
         if (p->neutral < 1u || p->neutral > 255u) return fail(c, CM_BAD_ARG, "neutral must lie in 1..255");
         if (p->cost_factor_q8 > 256u) return fail(c, CM_BAD_ARG, "cost_factor_q8 must lie in 0..256");
         if (p->flags & ~CM_PLAN_ALLOW_UNKNOWN) return fail(c, CM_BAD_ARG, "unknown flag bits");
-        const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+        const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
         if (p->max_path_cells < 1u || p->max_path_cells > n) return fail(c, CM_BAD_ARG, "max_path_cells must lie in 1..nx * ny");
         const uint64_t w_max = p->neutral + ((252u * p->cost_factor_q8) >> 8);
         if (7u * w_max * (n - 1u) > 0xFFFFFFFEull)
@@ -1102,72 +1078,50 @@ int cm_map_plan_configure(cm_ctx* c, const cm_plan_params* p) {
     return map_plan_configure(c, p);
 }
 
-// The refusals every call on a configured plan layer shares; the reads also refuse a stale potential.
-static int plan_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
-    if (read && c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
-    return CM_OK;
-}
-
 int cm_map_plan_update(cm_ctx* c, float gx, float gy, cm_plan_info* out, cm_map_info* map) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = plan_check(c, false)) return e;
-    if (const int e = cost_check(c, true)) return e;
+    if (const int e = layer_check(c, LAYER_PLAN, false)) return e;
+    if (const int e = layer_fresh_check(c, LAYER_COST)) return e;
     uint32_t goal[2];
     if (!map_window_cell(c, gx, gy, goal)) return fail(c, CM_BAD_ARG, "the goal is not finite or lies outside the map's window");
     if (const int e = map_plan_update(c, goal)) return e;
-    if (out) *out = c->plan_info;
-    if (map) *map = c->map_info;
+    if (out) *out = c->plan_layer.info;
+    if (map) *map = c->map.info;
     return CM_OK;
 }
 
 int cm_map_plan_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_plan_info* info, cm_map_info* map) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = plan_check(c, true)) return e;
-    if (info) *info = c->plan_info;
-    if (map) *map = c->map_info;
-    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "potential destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->plan_pot, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(uint32_t);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_PLAN, true)) return e;
+    if (info) *info = c->plan_layer.info;
+    if (map) *map = c->map.info;
+    const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    return copy_out(c, host_dst, c->plan_layer.pot, n, sizeof(uint32_t), capacity_cells, "potential destination too small");
 }
 
 int cm_map_plan_device(cm_ctx* c, const void** pot, cm_plan_info* info, cm_map_info* map) {
     if (!c) return CM_BAD_ARG;
     if (pot) *pot = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = plan_check(c, true)) return e;
-    if (info) *info = c->plan_info;
-    if (map) *map = c->map_info;
-    if (pot) *pot = c->plan_pot;
+    if (const int e = layer_check(c, LAYER_PLAN, true)) return e;
+    if (info) *info = c->plan_layer.info;
+    if (map) *map = c->map.info;
+    if (pot) *pot = c->plan_layer.pot;
     return CM_OK;
 }
 
 int cm_map_plan_path(cm_ctx* c, float sx, float sy, uint32_t* host_dst, uint64_t capacity, cm_path_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = plan_check(c, true)) return e;
+    if (const int e = layer_check(c, LAYER_PLAN, true)) return e;
     uint32_t start[2], head[CM_PLAN_PATH_HEAD];
     if (!map_window_cell(c, sx, sy, start)) return fail(c, CM_BAD_ARG, "the start is not finite or lies outside the map's window");
     if (const int e = map_plan_path(c, start, head)) return e;
     const uint64_t n = head[0];
-    if (info) *info = cm_path_info{{start[0], start[1]}, {c->plan_info.goal[0], c->plan_info.goal[1]}, head[0], head[1], head[2], 0u};
-    if (n > capacity) return fail(c, CM_CAPACITY, "path destination too small");
-    if (n == 0) return CM_OK;
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->plan_path + CM_PLAN_PATH_HEAD, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(uint32_t);
-    return CM_OK;
+    if (info) *info = cm_path_info{{start[0], start[1]}, {c->plan_layer.info.goal[0], c->plan_layer.info.goal[1]}, head[0], head[1], head[2], 0u};
+    return copy_out(c, host_dst, c->plan_layer.path + CM_PLAN_PATH_HEAD, n, sizeof(uint32_t), capacity, "path destination too small", true);
 }
 
 static_assert(sizeof(cm_traj_params) == 24 && sizeof(cm_traj_window) == 32 && sizeof(cm_traj_score) == 32 && sizeof(cm_traj_info) == 24,
@@ -1189,11 +1143,8 @@ int cm_traj_directions(float* cos_sin, uint64_t capacity_pairs) {
 int cm_map_traj_configure(cm_ctx* c, const cm_traj_params* p, const float* foot_xy, uint32_t n_foot) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_TRAJ, p)) return e;
     if (!p) return map_traj_configure(c, nullptr, nullptr, 0);
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
     if (p->nv < 1u || p->nw < 1u || static_cast<uint64_t>(p->nv) * p->nw > CM_TRAJ_MAX_SAMPLES)
         return fail(c, CM_BAD_ARG, "nv and nw must be at least 1 and nv * nw at most CM_TRAJ_MAX_SAMPLES");
     if (p->n_steps < 1u || p->n_steps > CM_TRAJ_MAX_STEPS) return fail(c, CM_BAD_ARG, "n_steps must lie in 1..CM_TRAJ_MAX_STEPS");
@@ -1205,22 +1156,11 @@ int cm_map_traj_configure(cm_ctx* c, const cm_traj_params* p, const float* foot_
     return map_traj_configure(c, p, foot_xy, n_foot);
 }
 
-// The refusals every call on a configured rollout layer shares; the reads also refuse stale scores.
-static int traj_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
-    if (!c->traj_on) return fail(c, CM_BAD_ARG, "no rollout layer (cm_map_traj_configure first)");
-    if (read && c->traj_stale) return fail(c, CM_BAD_ARG, c->traj_stale);
-    return CM_OK;
-}
-
 int cm_map_traj_evaluate(cm_ctx* c, const cm_traj_window* w, cm_traj_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = traj_check(c, false)) return e;
-    if (c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
+    if (const int e = layer_check(c, LAYER_TRAJ, false)) return e;
+    if (const int e = layer_fresh_check(c, LAYER_PLAN)) return e;
     if (!w) return fail(c, CM_BAD_ARG, "no window");
     for (const float v : {w->x, w->y, w->yaw, w->v_lo, w->v_hi, w->w_lo, w->w_hi, w->dt})
         if (!std::isfinite(v)) return fail(c, CM_BAD_ARG, "a window value is not finite");
@@ -1231,42 +1171,36 @@ int cm_map_traj_evaluate(cm_ctx* c, const cm_traj_window* w, cm_traj_info* out) 
     uint32_t start[2];
     if (!map_window_cell(c, w->x, w->y, start)) return fail(c, CM_BAD_ARG, "the start's cell does not exist or lies outside the map's window");
     // (traj_info holds the last command by value: a refusal below leaves the fresh scores and their info alone)
-    std::vector<float>& sv = c->traj_v;
-    std::vector<float>& sw = c->traj_w;
-    traj_samples(w->v_lo, w->v_hi, c->traj_params.nv, sv.data());
-    traj_samples(w->w_lo, w->w_hi, c->traj_params.nw, sw.data());
+    std::vector<float>& sv = c->traj.v;
+    std::vector<float>& sw = c->traj.w;
+    traj_samples(w->v_lo, w->v_hi, c->traj.params.nv, sv.data());
+    traj_samples(w->w_lo, w->w_hi, c->traj.params.nw, sw.data());
     for (const float v : sv)
         if (!std::isfinite(v) || !std::isfinite(static_cast<float>(v * w->dt))) return fail(c, CM_BAD_ARG, "a sample or its step length is not finite");
     for (const float wj : sw)
         if (!std::isfinite(wj) || std::fabs(static_cast<double>(wj) * static_cast<double>(w->dt)) >= 3.141592653589793)
             return fail(c, CM_BAD_ARG, "a turn of pi or more per step: |w_j * dt| must stay below pi");
     if (const int e = map_traj_evaluate(c, *w, start)) return e;
-    if (out) *out = c->traj_info;
+    if (out) *out = c->traj.info;
     return CM_OK;
 }
 
 int cm_map_traj_copy(cm_ctx* c, cm_traj_score* host_dst, uint64_t capacity, cm_traj_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = traj_check(c, true)) return e;
-    if (info) *info = c->traj_info;
-    const uint64_t n = static_cast<uint64_t>(c->traj_params.nv) * c->traj_params.nw;
-    if (n > capacity) return fail(c, CM_CAPACITY, "score destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->traj_scores, n * sizeof(cm_traj_score), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_traj_score);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_TRAJ, true)) return e;
+    if (info) *info = c->traj.info;
+    const uint64_t n = static_cast<uint64_t>(c->traj.params.nv) * c->traj.params.nw;
+    return copy_out(c, host_dst, c->traj.scores, n, sizeof(cm_traj_score), capacity, "score destination too small");
 }
 
 int cm_map_traj_device(cm_ctx* c, const void** scores, cm_traj_info* info) {
     if (!c) return CM_BAD_ARG;
     if (scores) *scores = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = traj_check(c, true)) return e;
-    if (info) *info = c->traj_info;
-    if (scores) *scores = c->traj_scores;
+    if (const int e = layer_check(c, LAYER_TRAJ, true)) return e;
+    if (info) *info = c->traj.info;
+    if (scores) *scores = c->traj.scores;
     return CM_OK;
 }
 
@@ -1281,69 +1215,42 @@ static_assert(CM_FRONTIER_NONE == CM_FRONT_NONE_DEV && CM_FRONTIER_MAX_TABLE == 
 int cm_map_frontier_configure(cm_ctx* c, const cm_frontier_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_FRONT, p)) return e;
     if (!p) return map_frontier_configure(c, nullptr);
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
     if (p->min_cells < 1u) return fail(c, CM_BAD_ARG, "min_cells must be at least 1");
     if (p->max_frontiers < 1u || p->max_frontiers > CM_FRONTIER_MAX_TABLE) return fail(c, CM_BAD_ARG, "max_frontiers must lie in 1..CM_FRONTIER_MAX_TABLE");
     if (p->max_cost > 252u) return fail(c, CM_BAD_ARG, "max_cost must lie in 0..252");
-    if (c->map_info.nx > 0xFFFFu || c->map_info.ny > 0xFFFFu) return fail(c, CM_BAD_ARG, "the window is too large for a 16-bit box");
+    if (c->map.info.nx > 0xFFFFu || c->map.info.ny > 0xFFFFu) return fail(c, CM_BAD_ARG, "the window is too large for a 16-bit box");
     return map_frontier_configure(c, p);
-}
-
-// The refusals every call on a configured frontier layer shares; the reads also refuse stale frontiers.
-static int front_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->plan_on) return fail(c, CM_BAD_ARG, "no plan layer (cm_map_plan_configure first)");
-    if (!c->front_on) return fail(c, CM_BAD_ARG, "no frontier layer (cm_map_frontier_configure first)");
-    if (read && c->front_stale) return fail(c, CM_BAD_ARG, c->front_stale);
-    return CM_OK;
 }
 
 int cm_map_frontier_update(cm_ctx* c, cm_frontier_info* out, cm_map_info* map) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = front_check(c, false)) return e;
-    if (c->plan_stale) return fail(c, CM_BAD_ARG, c->plan_stale);
+    if (const int e = layer_check(c, LAYER_FRONT, false)) return e;
+    if (const int e = layer_fresh_check(c, LAYER_PLAN)) return e;
     if (const int e = map_frontier_update(c)) return e;
-    if (out) *out = c->front_info;
-    if (map) *map = c->map_info;
+    if (out) *out = c->front.info;
+    if (map) *map = c->map.info;
     return CM_OK;
 }
 
 int cm_map_frontier_copy(cm_ctx* c, cm_frontier* host_dst, uint64_t capacity, cm_frontier_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = front_check(c, true)) return e;
-    if (info) *info = c->front_info;
-    const uint64_t n = c->front_info.n_written;
-    if (n > capacity) return fail(c, CM_CAPACITY, "frontier destination too small");
-    if (n == 0) return CM_OK;
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->front_table, n * sizeof(cm_frontier), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_frontier);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_FRONT, true)) return e;
+    if (info) *info = c->front.info;
+    const uint64_t n = c->front.info.n_written;
+    return copy_out(c, host_dst, c->front.table, n, sizeof(cm_frontier), capacity, "frontier destination too small", true);
 }
 
 int cm_map_frontier_labels_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity_cells, cm_frontier_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = front_check(c, true)) return e;
-    if (info) *info = c->front_info;
-    const uint64_t n = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    if (n > capacity_cells) return fail(c, CM_CAPACITY, "label destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->front_labels, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(uint32_t);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_FRONT, true)) return e;
+    if (info) *info = c->front.info;
+    const uint64_t n = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    return copy_out(c, host_dst, c->front.labels, n, sizeof(uint32_t), capacity_cells, "label destination too small");
 }
 
 int cm_map_frontier_device(cm_ctx* c, const void** labels, const void** table, cm_frontier_info* info) {
@@ -1351,10 +1258,10 @@ int cm_map_frontier_device(cm_ctx* c, const void** labels, const void** table, c
     if (labels) *labels = nullptr;
     if (table) *table = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = front_check(c, true)) return e;
-    if (info) *info = c->front_info;
-    if (labels) *labels = c->front_labels;
-    if (table) *table = c->front_table;
+    if (const int e = layer_check(c, LAYER_FRONT, true)) return e;
+    if (info) *info = c->front.info;
+    if (labels) *labels = c->front.labels;
+    if (table) *table = c->front.table;
     return CM_OK;
 }
 
@@ -1373,94 +1280,77 @@ int cm_match_table(float cell, float sigma, float max_dist, uint8_t* dst, uint64
     return CM_OK;
 }
 
+// What the two matchers' configure calls refuse in the same words: the field, then the angle candidates; the flag bits come
+// last in both (match_flags_check), behind the refusals each has of its own.
+static int match_field_check(cm_ctx* c, float sigma, float max_dist, uint32_t n_a, uint32_t a_stride, uint32_t* R) {
+    if (const char* why = cm_match_refusal(c->map.params.cell, sigma, max_dist, CM_MATCH_MAX_RADIUS_CELLS, R)) return fail(c, CM_BAD_ARG, why);
+    if (n_a > CM_MATCH_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_a exceeds CM_MATCH_MAX_ANGLES");
+    if (a_stride == 0u) return fail(c, CM_BAD_ARG, "a_stride must be at least 1");
+    if (static_cast<uint64_t>(n_a) * a_stride > 1024u) return fail(c, CM_BAD_ARG, "n_a * a_stride exceeds 1024 (a quarter turn)");
+    return CM_OK;
+}
+static int match_flags_check(cm_ctx* c, uint32_t flags) {
+    return (flags & ~CM_MATCH_SUBCELL) ? fail(c, CM_BAD_ARG, "unknown flag bits") : CM_OK;
+}
+
 int cm_map_match_configure(cm_ctx* c, const cm_match_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_MATCH, p)) return e;
     uint32_t R = 0;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
-        if (p->n_a > CM_MATCH_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_a exceeds CM_MATCH_MAX_ANGLES");
-        if (p->a_stride == 0u) return fail(c, CM_BAD_ARG, "a_stride must be at least 1");
-        if (static_cast<uint64_t>(p->n_a) * p->a_stride > 1024u) return fail(c, CM_BAD_ARG, "n_a * a_stride exceeds 1024 (a quarter turn)");
+        if (const int e = match_field_check(c, p->sigma, p->max_dist, p->n_a, p->a_stride, &R)) return e;
         if (p->wx > CM_MATCH_MAX_SHIFT || p->wy > CM_MATCH_MAX_SHIFT) return fail(c, CM_BAD_ARG, "wx or wy exceeds CM_MATCH_MAX_SHIFT");
         if ((2ull * p->n_a + 1u) * (2ull * p->wx + 1u) * (2ull * p->wy + 1u) > CM_MATCH_MAX_CANDIDATES)
             return fail(c, CM_BAD_ARG, "more than CM_MATCH_MAX_CANDIDATES candidates");
-        if (p->flags & ~CM_MATCH_SUBCELL) return fail(c, CM_BAD_ARG, "unknown flag bits");
+        if (const int e = match_flags_check(c, p->flags)) return e;
     }
     return map_match_configure(c, p, R);
-}
-
-// The refusals every call on a configured matching layer shares; the reads also refuse a stale volume.
-static int match_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->match_on) return fail(c, CM_BAD_ARG, "no matching layer (cm_map_match_configure first)");
-    if (read && c->match_stale) return fail(c, CM_BAD_ARG, c->match_stale);
-    if (read && c->match_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the match is stale: no cm_map_match_evaluate since the last merge");
-    return CM_OK;
 }
 
 int cm_map_match_evaluate(cm_ctx* c, const float pose[12], cm_match_result* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = match_check(c, false)) return e;
+    if (const int e = layer_check(c, LAYER_MATCH, false)) return e;
     if (const int e = centroid_result_check(c)) return e;
-    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
-    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
-    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    if (c->map.info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (const int e = cost_fresh_check(c)) return e;
     int v[2];
-    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    if (const int e = pose_check(c, pose, v)) return e;
     if (const int e = map_match_evaluate(c, pose)) return e;
-    if (out) *out = c->match_result;
+    if (out) *out = c->match.result;
     return CM_OK;
 }
 
 static uint64_t match_entries(const cm_ctx* c) {
-    const cm_match_params& q = c->match_params;
+    const cm_match_params& q = c->match.params;
     return (2ull * q.n_a + 1u) * (2ull * q.wx + 1u) * (2ull * q.wy + 1u);
 }
 
 int cm_map_match_copy(cm_ctx* c, uint32_t* host_dst, uint64_t capacity, cm_match_result* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = match_check(c, true)) return e;
-    if (out) *out = c->match_result;
+    if (const int e = layer_check(c, LAYER_MATCH, true)) return e;
+    if (out) *out = c->match.result;
     const uint64_t n = match_entries(c);
-    if (n > capacity) return fail(c, CM_CAPACITY, "score destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->match_vol, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(uint32_t);
-    return CM_OK;
+    return copy_out(c, host_dst, c->match.vol, n, sizeof(uint32_t), capacity, "score destination too small");
 }
 
 int cm_map_match_device(cm_ctx* c, const void** scores, cm_match_result* out) {
     if (!c) return CM_BAD_ARG;
     if (scores) *scores = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = match_check(c, true)) return e;
-    if (out) *out = c->match_result;
-    if (scores) *scores = c->match_vol;
+    if (const int e = layer_check(c, LAYER_MATCH, true)) return e;
+    if (out) *out = c->match.result;
+    if (scores) *scores = c->match.vol;
     return CM_OK;
 }
 
 int cm_map_match_table_copy(cm_ctx* c, uint8_t* host_dst, uint64_t capacity, uint64_t* n) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = match_check(c, false)) return e;
-    const uint64_t n_lut = c->match_lut_host.size();
-    if (n) *n = n_lut;
-    if (n_lut > capacity) return fail(c, CM_CAPACITY, "field table destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    std::memcpy(host_dst, c->match_lut_host.data(), n_lut);
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_MATCH, false)) return e;
+    return table_out(c, host_dst, c->match.lut_host, capacity, n, "field table destination too small");
 }
 
 static_assert(sizeof(cm_mcl_params) == 40 && offsetof(cm_mcl_params, seed) == 32 && sizeof(cm_mcl_particle) == 24 && sizeof(cm_mcl_weight) == 8 &&
@@ -1486,15 +1376,13 @@ int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t n_p, ui
 int cm_map_mcl_configure(cm_ctx* c, const cm_mcl_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_MCL, p)) return e;
     uint32_t R = 0;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
         if (p->n_particles < 1u || p->n_particles > CM_MCL_MAX_PARTICLES) return fail(c, CM_BAD_ARG, "n_particles must lie in 1..CM_MCL_MAX_PARTICLES");
         if (p->max_beams < 1u || p->max_beams > CM_MCL_MAX_BEAMS) return fail(c, CM_BAD_ARG, "max_beams must lie in 1..CM_MCL_MAX_BEAMS");
         if (p->range_cells < 1u || p->range_cells > CM_MCL_MAX_RANGE_CELLS) return fail(c, CM_BAD_ARG, "range_cells must lie in 1..CM_MCL_MAX_RANGE_CELLS");
-        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
+        if (const char* why = cm_match_refusal(c->map.params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
         if (!std::isfinite(p->tau) || !(p->tau > 0.0f)) return fail(c, CM_BAD_ARG, "tau must be finite and > 0");
         if (!std::isfinite(p->resample_frac) || !(p->resample_frac >= 0.0f && p->resample_frac <= 1.0f))
             return fail(c, CM_BAD_ARG, "resample_frac must be finite and lie in 0..1");
@@ -1503,16 +1391,16 @@ int cm_map_mcl_configure(cm_ctx* c, const cm_mcl_params* p) {
     return map_mcl_configure(c, p, R);
 }
 
-// The refusals every call on a configured localisation layer shares.
+static int particles_check(cm_ctx* c) {
+    return c->mcl.init ? CM_OK : fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
+}
+
+// The refusals every call on a configured localisation layer shares: the particles come before the stale weights.
 static int mcl_check(cm_ctx* c, bool need_particles, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->mcl_on) return fail(c, CM_BAD_ARG, "no localisation layer (cm_map_mcl_configure first)");
-    if (need_particles && !c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
-    if (read && c->mcl_stale) return fail(c, CM_BAD_ARG, c->mcl_stale);
-    if (read && c->mcl_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the weights are stale: no cm_map_mcl_update since the last merge");
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_MCL, false)) return e;
+    if (need_particles)
+        if (const int e = particles_check(c)) return e;
+    return read ? layer_fresh_check(c, LAYER_MCL) : CM_OK;
 }
 
 // A centre or a motion (x, y, yaw) and its three standard deviations: what init_pose and predict refuse about them.
@@ -1538,7 +1426,7 @@ int cm_map_mcl_init_uniform(cm_ctx* c) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = mcl_check(c, false, false)) return e;
-    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate or cm_map_load first)");
+    if (c->map.info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate or cm_map_load first)");
     return map_mcl_init_uniform(c);
 }
 
@@ -1556,11 +1444,11 @@ int cm_map_mcl_update(cm_ctx* c, cm_mcl_info* out) {
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = mcl_check(c, false, false)) return e;
     if (const int e = centroid_result_check(c)) return e;
-    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
-    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
-    if (!c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
+    if (c->map.info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (const int e = cost_fresh_check(c)) return e;
+    if (const int e = particles_check(c)) return e;
     if (const int e = map_mcl_update(c)) return e;
-    if (out) *out = c->mcl_info;
+    if (out) *out = c->mcl.info;
     return CM_OK;
 }
 
@@ -1568,29 +1456,17 @@ int cm_map_mcl_copy(cm_ctx* c, cm_mcl_particle* host_dst, uint64_t capacity) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = mcl_check(c, true, false)) return e;
-    const uint64_t n = c->mcl_params.n_particles;
-    if (n > capacity) return fail(c, CM_CAPACITY, "particle destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->mcl_parts[c->mcl_cur], n * sizeof(cm_mcl_particle), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_mcl_particle);
-    return CM_OK;
+    const uint64_t n = c->mcl.params.n_particles;
+    return copy_out(c, host_dst, c->mcl.parts[c->mcl.cur], n, sizeof(cm_mcl_particle), capacity, "particle destination too small");
 }
 
 int cm_map_mcl_weights_copy(cm_ctx* c, cm_mcl_weight* host_dst, uint64_t capacity, cm_mcl_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = mcl_check(c, true, true)) return e;
-    if (info) *info = c->mcl_info;
-    const uint64_t n = c->mcl_params.n_particles;
-    if (n > capacity) return fail(c, CM_CAPACITY, "weight destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->mcl_wts, n * sizeof(cm_mcl_weight), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_mcl_weight);
-    return CM_OK;
+    if (info) *info = c->mcl.info;
+    const uint64_t n = c->mcl.params.n_particles;
+    return copy_out(c, host_dst, c->mcl.wts, n, sizeof(cm_mcl_weight), capacity, "weight destination too small");
 }
 
 int cm_map_mcl_device(cm_ctx* c, const void** particles, const void** weights, cm_mcl_info* info) {
@@ -1599,9 +1475,9 @@ int cm_map_mcl_device(cm_ctx* c, const void** particles, const void** weights, c
     if (weights) *weights = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = mcl_check(c, true, true)) return e;
-    if (info) *info = c->mcl_info;
-    if (particles) *particles = c->mcl_parts[c->mcl_cur];
-    if (weights) *weights = c->mcl_wts;
+    if (info) *info = c->mcl.info;
+    if (particles) *particles = c->mcl.parts[c->mcl.cur];
+    if (weights) *weights = c->mcl.wts;
     return CM_OK;
 }
 
@@ -1626,10 +1502,8 @@ int cm_cast_directions(uint32_t range_cells, int16_t* dst, uint64_t capacity_pai
 int cm_map_cast_configure(cm_ctx* c, const cm_cast_params* p, const uint32_t* bearings) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_CAST, p)) return e;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
         if (p->max_poses < 1u || p->max_poses > CM_CAST_MAX_POSES) return fail(c, CM_BAD_ARG, "max_poses must lie in 1..CM_CAST_MAX_POSES");
         if (p->n_bearings < 1u || p->n_bearings > CM_CAST_MAX_BEARINGS) return fail(c, CM_BAD_ARG, "n_bearings must lie in 1..CM_CAST_MAX_BEARINGS");
         if (p->range_cells < 1u || p->range_cells > CM_CAST_MAX_RANGE_CELLS) return fail(c, CM_BAD_ARG, "range_cells must lie in 1..CM_CAST_MAX_RANGE_CELLS");
@@ -1639,25 +1513,20 @@ int cm_map_cast_configure(cm_ctx* c, const cm_cast_params* p, const uint32_t* be
     return map_cast_configure(c, p, bearings);
 }
 
-// The refusals every call on a configured cast layer shares.
+// The refusals every call on a configured cast layer shares: a read wants fresh rays, an evaluate a fresh cost table.
 static int cast_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->cast_on) return fail(c, CM_BAD_ARG, "no cast layer (cm_map_cast_configure first)");
-    if (read && c->cast_stale) return fail(c, CM_BAD_ARG, c->cast_stale);
-    if (!read && !c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
-    return CM_OK;
+    if (const int e = layer_check(c, LAYER_CAST, read)) return e;
+    return read ? CM_OK : cost_fresh_check(c);
 }
 
 int cm_map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n, cm_cast_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = cast_check(c, false)) return e;
-    if (n < 1u || n > c->cast_params.max_poses) return fail(c, CM_BAD_ARG, "n must lie in 1..max_poses");
+    if (n < 1u || n > c->cast.params.max_poses) return fail(c, CM_BAD_ARG, "n must lie in 1..max_poses");
     if (!host_poses) return fail(c, CM_BAD_ARG, "no poses");
     if (const int e = map_cast_evaluate(c, host_poses, n)) return e;
-    if (out) *out = c->cast_info;
+    if (out) *out = c->cast.info;
     return CM_OK;
 }
 
@@ -1665,11 +1534,11 @@ int cm_map_cast_evaluate_mcl(cm_ctx* c, cm_cast_info* out) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = cast_check(c, false)) return e;
-    if (!c->mcl_on) return fail(c, CM_BAD_ARG, "no localisation layer (cm_map_mcl_configure first)");
-    if (!c->mcl_init) return fail(c, CM_BAD_ARG, "the particles are not initialised (cm_map_mcl_init_pose or cm_map_mcl_init_uniform first)");
-    if (c->mcl_params.n_particles > c->cast_params.max_poses) return fail(c, CM_BAD_ARG, "n_particles is above max_poses");
-    if (const int e = map_cast_evaluate(c, nullptr, c->mcl_params.n_particles)) return e;
-    if (out) *out = c->cast_info;
+    if (!c->layers[LAYER_MCL].on) return fail(c, CM_BAD_ARG, LAYER_TABLE[LAYER_MCL].absent);
+    if (const int e = particles_check(c)) return e;
+    if (c->mcl.params.n_particles > c->cast.params.max_poses) return fail(c, CM_BAD_ARG, "n_particles is above max_poses");
+    if (const int e = map_cast_evaluate(c, nullptr, c->mcl.params.n_particles)) return e;
+    if (out) *out = c->cast.info;
     return CM_OK;
 }
 
@@ -1677,15 +1546,9 @@ int cm_map_cast_copy(cm_ctx* c, cm_cast_ray* host_dst, uint64_t capacity, cm_cas
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = cast_check(c, true)) return e;
-    if (info) *info = c->cast_info;
-    const uint64_t n = static_cast<uint64_t>(c->cast_info.n_poses) * c->cast_info.n_bearings;
-    if (n > capacity) return fail(c, CM_CAPACITY, "ray destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->cast_rays, n * sizeof(cm_cast_ray), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n * sizeof(cm_cast_ray);
-    return CM_OK;
+    if (info) *info = c->cast.info;
+    const uint64_t n = static_cast<uint64_t>(c->cast.info.n_poses) * c->cast.info.n_bearings;
+    return copy_out(c, host_dst, c->cast.rays, n, sizeof(cm_cast_ray), capacity, "ray destination too small");
 }
 
 int cm_map_cast_device(cm_ctx* c, const void** rays, cm_cast_info* info) {
@@ -1693,8 +1556,8 @@ int cm_map_cast_device(cm_ctx* c, const void** rays, cm_cast_info* info) {
     if (rays) *rays = nullptr;
     std::lock_guard<std::mutex> lk(c->merge_mu);
     if (const int e = cast_check(c, true)) return e;
-    if (info) *info = c->cast_info;
-    if (rays) *rays = c->cast_rays;
+    if (info) *info = c->cast.info;
+    if (rays) *rays = c->cast.rays;
     return CM_OK;
 }
 
@@ -1707,85 +1570,60 @@ static_assert(CM_MATCH_SEARCH_MAX_SHIFT == CM_MSEARCH_MAX_SHIFT_DEV && CM_MATCH_
 int cm_map_match_search_configure(cm_ctx* c, const cm_match_search_params* p) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
+    if (const int e = configure_check(c, LAYER_SEARCH, p)) return e;
     uint32_t R = 0;
     if (p) {
-        if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-        if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-        if (const char* why = cm_match_refusal(c->map_params.cell, p->sigma, p->max_dist, CM_MATCH_MAX_RADIUS_CELLS, &R)) return fail(c, CM_BAD_ARG, why);
-        if (p->n_a > CM_MATCH_MAX_ANGLES) return fail(c, CM_BAD_ARG, "n_a exceeds CM_MATCH_MAX_ANGLES");
-        if (p->a_stride == 0u) return fail(c, CM_BAD_ARG, "a_stride must be at least 1");
-        if (static_cast<uint64_t>(p->n_a) * p->a_stride > 1024u) return fail(c, CM_BAD_ARG, "n_a * a_stride exceeds 1024 (a quarter turn)");
+        if (const int e = match_field_check(c, p->sigma, p->max_dist, p->n_a, p->a_stride, &R)) return e;
         if (p->wx > CM_MATCH_SEARCH_MAX_SHIFT || p->wy > CM_MATCH_SEARCH_MAX_SHIFT) return fail(c, CM_BAD_ARG, "wx or wy exceeds CM_MATCH_SEARCH_MAX_SHIFT");
         if (p->depth > CM_MATCH_SEARCH_MAX_DEPTH) return fail(c, CM_BAD_ARG, "depth exceeds CM_MATCH_SEARCH_MAX_DEPTH");
         if (p->max_nodes == 0u || p->max_nodes > CM_MATCH_SEARCH_MAX_NODES) return fail(c, CM_BAD_ARG, "max_nodes must be 1 .. CM_MATCH_SEARCH_MAX_NODES");
         if (p->max_cells == 0u || p->max_cells > CM_MATCH_SEARCH_MAX_NODES) return fail(c, CM_BAD_ARG, "max_cells must be 1 .. CM_MATCH_SEARCH_MAX_NODES");
         const uint64_t rx = (2ull * p->wx + (1ull << p->depth)) >> p->depth, ry = (2ull * p->wy + (1ull << p->depth)) >> p->depth;
         if ((2ull * p->n_a + 1u) * rx * ry > p->max_nodes) return fail(c, CM_BAD_ARG, "more roots than max_nodes");
-        if (c->map_info.nx > 65535u || c->map_info.ny > 65535u) return fail(c, CM_BAD_ARG, "the map's window has more than 65535 cells along an axis");
-        if (p->flags & ~CM_MATCH_SUBCELL) return fail(c, CM_BAD_ARG, "unknown flag bits");
+        if (c->map.info.nx > 65535u || c->map.info.ny > 65535u) return fail(c, CM_BAD_ARG, "the map's window has more than 65535 cells along an axis");
+        if (const int e = match_flags_check(c, p->flags)) return e;
     }
     return map_msearch_configure(c, p, R);
-}
-
-// The refusals every call on a configured search layer shares; the reads also refuse a stale result.
-static int msearch_check(cm_ctx* c, bool read) {
-    if (c->pending) return fail(c, CM_BAD_ARG, "a frame is in flight (cm_wait first)");
-    if (!c->map_on) return fail(c, CM_BAD_ARG, "no occupancy map (cm_map_configure first)");
-    if (!c->cost_on) return fail(c, CM_BAD_ARG, "no cost layer (cm_map_cost_configure first)");
-    if (!c->msearch_on) return fail(c, CM_BAD_ARG, "no search layer (cm_map_match_search_configure first)");
-    if (read && c->msearch_stale) return fail(c, CM_BAD_ARG, c->msearch_stale);
-    if (read && c->msearch_serial != c->frame_serial) return fail(c, CM_BAD_ARG, "the search is stale: no cm_map_match_search since the last merge");
-    return CM_OK;
 }
 
 int cm_map_match_search(cm_ctx* c, const float pose[12], cm_match_result* out, cm_match_search_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = msearch_check(c, false)) return e;
+    if (const int e = layer_check(c, LAYER_SEARCH, false)) return e;
     if (const int e = centroid_result_check(c)) return e;
-    if (c->map_info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
-    if (!c->cost_fresh) return fail(c, CM_BAD_ARG, "the cost tables are stale: no cm_map_cost_update since the last cm_map_integrate");
-    if (!pose) return fail(c, CM_BAD_ARG, "no pose");
-    for (int k = 0; k < 12; ++k)
-        if (!std::isfinite(pose[k])) return fail(c, CM_BAD_ARG, "the pose must be finite");
+    if (c->map.info.n_frames == 0) return fail(c, CM_BAD_ARG, "the map holds no frame (cm_map_integrate first)");
+    if (const int e = cost_fresh_check(c)) return e;
     int v[2];
-    if (!map_vehicle_cell(c, pose, v)) return fail(c, CM_BAD_ARG, "the vehicle's cell does not exist (beyond 2^30 cells from the world origin)");
+    if (const int e = pose_check(c, pose, v)) return e;
     const int e = map_msearch_evaluate(c, pose);
-    if (e == CM_CAPACITY && info) *info = c->msearch_info;
+    if (e == CM_CAPACITY && info) *info = c->msearch.info;
     if (e) return e;
-    if (out) *out = c->msearch_result;
-    if (info) *info = c->msearch_info;
+    if (out) *out = c->msearch.result;
+    if (info) *info = c->msearch.info;
     return CM_OK;
 }
 
 int cm_map_match_search_result(cm_ctx* c, cm_match_result* out, cm_match_search_info* info) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = msearch_check(c, true)) return e;
-    if (out) *out = c->msearch_result;
-    if (info) *info = c->msearch_info;
+    if (const int e = layer_check(c, LAYER_SEARCH, true)) return e;
+    if (out) *out = c->msearch.result;
+    if (info) *info = c->msearch.info;
     return CM_OK;
 }
 
 int cm_map_match_search_level_copy(cm_ctx* c, uint32_t h, uint8_t* host_dst, uint64_t capacity, uint32_t dims[2]) {
     if (!c) return CM_BAD_ARG;
     std::lock_guard<std::mutex> lk(c->merge_mu);
-    if (const int e = msearch_check(c, true)) return e;
-    if (h > c->msearch_params.depth) return fail(c, CM_BAD_ARG, "no such level (h exceeds depth)");
-    const uint32_t pw = c->map_info.nx + (1u << h) - 1u, ph = c->map_info.ny + (1u << h) - 1u;
+    if (const int e = layer_check(c, LAYER_SEARCH, true)) return e;
+    if (h > c->msearch.params.depth) return fail(c, CM_BAD_ARG, "no such level (h exceeds depth)");
+    const uint32_t pw = c->map.info.nx + (1u << h) - 1u, ph = c->map.info.ny + (1u << h) - 1u;
     if (dims) {
         dims[0] = pw;
         dims[1] = ph;
     }
     const uint64_t n = static_cast<uint64_t>(pw) * ph;
-    if (n > capacity) return fail(c, CM_CAPACITY, "level destination too small");
-    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(host_dst, c->msearch_pyr + msearch_level_offset(c->map_info.nx, c->map_info.ny, h), n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->bytes_d2h += n;
-    return CM_OK;
+    return copy_out(c, host_dst, c->msearch.pyr + msearch_level_offset(c->map.info.nx, c->map.info.ny, h), n, 1, capacity, "level destination too small");
 }
 
 static_assert(sizeof(cm_voxel_normal) == 32 && sizeof(cm_normal_params) == 24, "cm_voxel_normal is 32 bytes, its parameters 24");

@@ -137,6 +137,38 @@ void collect_stage_times_by_name(cm_ctx* c) {
     }
 }
 
+// How a by-product call closes where it makes one host round trip at its end: the end mark, the launches' errors, at most
+// one copy of the call's info words into its page-locked buffer, the wait, the stage times.
+int finish_call(cm_ctx* c, void* host = nullptr, const void* dev = nullptr, size_t bytes = 0) {
+    prof_mark(c, "end");
+    HIP_TRY(c, hipGetLastError());
+    if (bytes) HIP_TRY(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    collect_stage_times(c);
+    return CM_OK;
+}
+
+// A map layer given back: its struct assigned afresh (the buffers go with the old value), its state off. layers_drop_below
+// walks the tree of cm_map_layers.hpp, so a configure call names no child.
+void layer_drop(cm_ctx* c, int l) {
+    switch (l) {
+        case LAYER_MAP: c->map = MapLayer{}; break;
+        case LAYER_COST: c->cost = CostLayer{}; break;
+        case LAYER_PLAN: c->plan_layer = PlanLayer{}; break;
+        case LAYER_TRAJ: c->traj = TrajLayer{}; break;
+        case LAYER_FRONT: c->front = FrontLayer{}; break;
+        case LAYER_MATCH: c->match = MatchLayer{}; break;
+        case LAYER_SEARCH: c->msearch = SearchLayer{}; break;
+        case LAYER_MCL: c->mcl = MclLayer{}; break;
+        case LAYER_CAST: c->cast = CastLayer{}; break;
+    }
+    layer_reset(c->layers, l);
+}
+void layers_drop_below(cm_ctx* c, int node) {
+    for (int l = LAYER_COUNT; l-- > 0;)
+        if (layer_below(l, node)) layer_drop(c, l);
+}
+
 // The bounds of the last result's centroids (k_cl_bounds into the six `words`, one host round trip): what a search grid is
 // laid over, and whose midpoint is a registration's pivot. The result holds at least one record.
 int result_bounds(cm_ctx* c, uint32_t* words, float mn[3], float mx[3]) {
@@ -405,10 +437,7 @@ int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r) {
     cmk_ray_cast(st, c->ray_bits, words, rd, n_sensors, c->ray_cells);
     prof_mark(c, "k_ray_finish");
     cmk_ray_finish(st, c->grid_cells, c->ray_cells, c->ray_image, static_cast<uint32_t>(n_cells), r.min_pass);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
+    if (const int e = finish_call(c)) return e;
     c->grid_have = true;
     c->ray_n = n_cells;
     c->ray_have = true;
@@ -438,47 +467,43 @@ float map_row(const float* m, const float* t) {
 // the scratch ray table, then cleared. nullptr gives it back.
 int map_configure(cm_ctx* c, const cm_map_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (const int e = map_cost_configure(c, nullptr, 0)) return e;     // the cost layer goes with the map it was sized for
-    c->map_on = false;
-    c->map_serial = 0;
-    c->map_cur = 0;
-    std::memset(&c->map_info, 0, sizeof c->map_info);
+    layers_drop_below(c, LAYER_MAP);                   // the layers go with the map they were sized for
     if (!q) {
-        c->map_state[0].release();
-        c->map_state[1].release();
-        c->map_image.release();
-        c->map_bits.release();
-        c->map_rays.release();
+        layer_drop(c, LAYER_MAP);
         return CM_OK;
     }
+    layer_reset(c->layers, LAYER_MAP);
+    c->map.serial = 0;
+    c->map.cur = 0;
+    std::memset(&c->map.info, 0, sizeof c->map.info);
     const uint64_t n_cells = static_cast<uint64_t>(q->nx) * q->ny;
     const size_t words = (n_cells + 31) / 32;
-    if (!c->map_state[0].reserve(n_cells * sizeof(cm_map_cell)) || !c->map_state[1].reserve(n_cells * sizeof(cm_map_cell)) ||
-        !c->map_image.reserve(n_cells) || !c->map_bits.reserve(2 * static_cast<size_t>(c->max_sensors) * words) ||
-        !c->map_rays.reserve(n_cells * sizeof(cm_grid_ray_cell)))
+    if (!c->map.state[0].reserve(n_cells * sizeof(cm_map_cell)) || !c->map.state[1].reserve(n_cells * sizeof(cm_map_cell)) ||
+        !c->map.image.reserve(n_cells) || !c->map.bits.reserve(2 * static_cast<size_t>(c->max_sensors) * words) ||
+        !c->map.rays.reserve(n_cells * sizeof(cm_grid_ray_cell)))
         return fail(c, CM_HIP_ERROR, "cannot allocate the occupancy map");
     hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemsetAsync(c->map_state[0], 0, n_cells * sizeof(cm_map_cell), st));
-    HIP_TRY(c, hipMemsetAsync(c->map_image, 0xFF, n_cells, st));
+    HIP_TRY(c, hipMemsetAsync(c->map.state[0], 0, n_cells * sizeof(cm_map_cell), st));
+    HIP_TRY(c, hipMemsetAsync(c->map.image, 0xFF, n_cells, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->map_params = *q;
-    c->map_info.nx = q->nx;
-    c->map_info.ny = q->ny;
-    c->map_on = true;
+    c->map.params = *q;
+    c->map.info.nx = q->nx;
+    c->map.info.ny = q->ny;
+    c->layers[LAYER_MAP].on = true;
     return CM_OK;
 }
 
 bool map_vehicle_cell(const cm_ctx* c, const float pose[12], int v[2]) {
-    const float inv = 1.0f / c->map_params.cell;
+    const float inv = 1.0f / c->map.params.cell;
     return map_world_axis(pose[3], inv, &v[0]) && map_world_axis(pose[7], inv, &v[1]);
 }
 
 bool map_window_cell(const cm_ctx* c, float x, float y, uint32_t cell[2]) {
-    const float inv = 1.0f / c->map_params.cell;
+    const float inv = 1.0f / c->map.params.cell;
     int g[2];
     if (!map_world_axis(x, inv, &g[0]) || !map_world_axis(y, inv, &g[1])) return false;
-    const int64_t ix = static_cast<int64_t>(g[0]) - c->map_info.anchor[0], iy = static_cast<int64_t>(g[1]) - c->map_info.anchor[1];
-    if (ix < 0 || ix >= static_cast<int64_t>(c->map_info.nx) || iy < 0 || iy >= static_cast<int64_t>(c->map_info.ny)) return false;
+    const int64_t ix = static_cast<int64_t>(g[0]) - c->map.info.anchor[0], iy = static_cast<int64_t>(g[1]) - c->map.info.anchor[1];
+    if (ix < 0 || ix >= static_cast<int64_t>(c->map.info.nx) || iy < 0 || iy >= static_cast<int64_t>(c->map.info.ny)) return false;
     cell[0] = static_cast<uint32_t>(ix);
     cell[1] = static_cast<uint32_t>(iy);
     return true;
@@ -490,7 +515,7 @@ bool map_window_cell(const cm_ctx* c, float x, float y, uint32_t cell[2]) {
 // E bitmaps, one pass over the cells that scrolls, updates and writes the image into the other state buffer; no host round
 // trip but the wait at the end, and no allocation: cm_map_configure made them all.
 int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
-    const cm_map_params& q = c->map_params;
+    const cm_map_params& q = c->map.params;
     const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
     const uint32_t words = static_cast<uint32_t>((n_cells + 31) / 32);
     const uint32_t n_sensors = c->frame.n_tiles ? c->frame.n_sensors : 0u;
@@ -524,8 +549,8 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     u.nx = q.nx;
     u.ny = q.ny;
     // the shift anchor_new - anchor_old: a window that shares no cell with the old one (or has no old one) carries nothing
-    const int64_t sx = static_cast<int64_t>(g.ax) - c->map_info.anchor[0], sy = static_cast<int64_t>(g.ay) - c->map_info.anchor[1];
-    const bool carry = c->map_info.n_frames != 0 && sx > -static_cast<int64_t>(q.nx) && sx < static_cast<int64_t>(q.nx) &&
+    const int64_t sx = static_cast<int64_t>(g.ax) - c->map.info.anchor[0], sy = static_cast<int64_t>(g.ay) - c->map.info.anchor[1];
+    const bool carry = c->map.info.n_frames != 0 && sx > -static_cast<int64_t>(q.nx) && sx < static_cast<int64_t>(q.nx) &&
                        sy > -static_cast<int64_t>(q.ny) && sy < static_cast<int64_t>(q.ny);
     u.carry = carry ? 1u : 0u;
     u.sx = carry ? static_cast<int32_t>(sx) : 0;
@@ -540,32 +565,22 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     hipStream_t st = c->stream;
     c->prof_used = 0;
     prof_mark(c, "map_clear");
-    if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->map_bits, 0, 2 * static_cast<size_t>(n_sensors) * words * 4, st));
-    HIP_TRY(c, hipMemsetAsync(c->map_rays, 0, n_cells * sizeof(cm_grid_ray_cell), st));
+    if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->map.bits, 0, 2 * static_cast<size_t>(n_sensors) * words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->map.rays, 0, n_cells * sizeof(cm_grid_ray_cell), st));
     prof_mark(c, "k_map_mark");
-    cmk_map_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->map_bits, words, n_sensors, c->frame.n_tiles);
+    cmk_map_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->map.bits, words, n_sensors, c->frame.n_tiles);
     prof_mark(c, "k_ray_cast");
-    cmk_ray_cast(st, c->map_bits, words, rd, n_sensors, c->map_rays);
+    cmk_ray_cast(st, c->map.bits, words, rd, n_sensors, c->map.rays);
     prof_mark(c, "k_map_update");
-    cmk_map_update(st, c->map_state[c->map_cur], c->map_state[c->map_cur ^ 1], c->map_rays, c->map_bits, words, u, c->map_image);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    c->map_cur ^= 1;
-    c->map_info.anchor[0] = g.ax;
-    c->map_info.anchor[1] = g.ay;
-    ++c->map_info.n_frames;
-    c->map_info.sensors_cast = cast;
-    c->map_serial = c->frame_serial;
-    c->cost_fresh = false;                             // the cost layer's tables are those of the image before this call
-    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_integrate";
-    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_integrate";
-    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_integrate";
-    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_integrate";
-    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_integrate";
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_integrate";
-    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_integrate";
+    cmk_map_update(st, c->map.state[c->map.cur], c->map.state[c->map.cur ^ 1], c->map.rays, c->map.bits, words, u, c->map.image);
+    if (const int e = finish_call(c)) return e;
+    c->map.cur ^= 1;
+    c->map.info.anchor[0] = g.ax;
+    c->map.info.anchor[1] = g.ay;
+    ++c->map.info.n_frames;
+    c->map.info.sensors_cast = cast;
+    c->map.serial = c->frame_serial;
+    layers_mark_below(c->layers, LAYER_MAP, SINCE_INTEGRATE);      // every layer's tables are those of the image before this call
     return CM_OK;
 }
 
@@ -573,33 +588,24 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
 // built here (cm_cost_table.hpp) and uploaded. nullptr gives it back. The tables are stale until the first update.
 int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (const int e = map_plan_configure(c, nullptr)) return e;        // the plan layer goes with the cost layer it reads
-    if (const int e = map_match_configure(c, nullptr, 0)) return e;    // and so does the matching layer
-    if (const int e = map_msearch_configure(c, nullptr, 0)) return e;  // and the search layer
-    if (const int e = map_mcl_configure(c, nullptr, 0)) return e;      // and the localisation layer
-    if (const int e = map_cast_configure(c, nullptr, nullptr)) return e;   // and the cast layer
-    c->cost_on = false;
-    c->cost_fresh = false;
+    layers_drop_below(c, LAYER_COST);                  // the layers that read the cost layer go with it
     if (!q) {
-        c->cost_cells.release();
-        c->cost_dist2.release();
-        c->cost_masks.release();
-        c->cost_lut.release();
-        c->cost_lut_host = std::vector<unsigned char>();
+        layer_drop(c, LAYER_COST);
         return CM_OK;
     }
-    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    const size_t words = static_cast<size_t>((c->map_info.ny + CM_COST_ROWS - 1) / CM_COST_ROWS) * c->map_info.nx;
+    layer_reset(c->layers, LAYER_COST);
+    const uint64_t n_cells = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    const size_t words = static_cast<size_t>((c->map.info.ny + CM_COST_ROWS - 1) / CM_COST_ROWS) * c->map.info.nx;
     const size_t n_lut = static_cast<size_t>(R) * R + 1;
-    if (!c->cost_cells.reserve(n_cells) || !c->cost_dist2.reserve(n_cells) || !c->cost_masks.reserve(2 * words) || !c->cost_lut.reserve(n_lut))
+    if (!c->cost.cells.reserve(n_cells) || !c->cost.dist2.reserve(n_cells) || !c->cost.masks.reserve(2 * words) || !c->cost.lut.reserve(n_lut))
         return fail(c, CM_HIP_ERROR, "cannot allocate the cost layer");
-    c->cost_lut_host.assign(n_lut, 0);
-    cm_cost_table(c->map_params.cell, q->inscribed_radius, q->inflation_radius, q->cost_scaling, R, c->cost_lut_host.data());
-    HIP_TRY(c, hipMemcpyAsync(c->cost_lut, c->cost_lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    c->cost.lut_host.assign(n_lut, 0);
+    cm_cost_table(c->map.params.cell, q->inscribed_radius, q->inflation_radius, q->cost_scaling, R, c->cost.lut_host.data());
+    HIP_TRY(c, hipMemcpyAsync(c->cost.lut, c->cost.lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->cost_params = *q;
-    c->cost_radius = R;
-    c->cost_on = true;
+    c->cost.params = *q;
+    c->cost.radius = R;
+    c->layers[LAYER_COST].on = true;
     return CM_OK;
 }
 
@@ -609,33 +615,24 @@ int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R) {
 int map_cost_update(cm_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     CmCostDev g;
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
-    g.r2 = c->cost_radius * c->cost_radius;
-    g.inflate_unknown = (c->cost_params.flags & CM_COST_INFLATE_UNKNOWN) ? 1u : 0u;
-    uint32_t* masks = c->cost_masks;
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
+    g.r2 = c->cost.radius * c->cost.radius;
+    g.inflate_unknown = (c->cost.params.flags & CM_COST_INFLATE_UNKNOWN) ? 1u : 0u;
+    uint32_t* masks = c->cost.masks;
     uint32_t* carry = masks + static_cast<size_t>((g.ny + CM_COST_ROWS - 1) / CM_COST_ROWS) * g.nx;
     hipStream_t st = c->stream;
     c->prof_used = 0;
     prof_mark(c, "k_cost_colmask");
-    cmk_cost_colmask(st, c->map_image, g, masks);
+    cmk_cost_colmask(st, c->map.image, g, masks);
     prof_mark(c, "k_cost_colcarry");
     cmk_cost_colcarry(st, masks, g, carry);
     prof_mark(c, "k_cost_rows");
-    cmk_cost_rows(st, c->map_image, masks, carry, c->cost_lut, g, c->cost_dist2, c->cost_cells);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    c->cost_fresh = true;
-    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_cost_update";
-    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_cost_update";
-    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_cost_update";
-    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_cost_update";
-    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_cost_update";
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_cost_update";
-    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_cost_update";
-    c->cast_steps_fresh = false;                       // (the next evaluate rebuilds its skip table from the new dist2)
+    cmk_cost_rows(st, c->map.image, masks, carry, c->cost.lut, g, c->cost.dist2, c->cost.cells);
+    if (const int e = finish_call(c)) return e;
+    layer_mark_fresh(c->layers, LAYER_COST, c->frame_serial);
+    layers_mark_below(c->layers, LAYER_COST, "the last cm_map_cost_update");
+    c->cast.steps_fresh = false;                       // (the next evaluate rebuilds its skip table from the new dist2)
     return CM_OK;
 }
 
@@ -644,25 +641,20 @@ int map_cost_update(cm_ctx* c) {
 // update.
 int map_plan_configure(cm_ctx* c, const cm_plan_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
-    if (const int e = map_traj_configure(c, nullptr, nullptr, 0)) return e;   // the rollout layer goes with the plan layer it reads
-    if (const int e = map_frontier_configure(c, nullptr)) return e;           // and so does the frontier layer
-    c->plan_on = false;
-    c->plan_stale = "the potential is stale: no cm_map_plan_update since cm_map_plan_configure";
-    std::memset(&c->plan_info, 0, sizeof c->plan_info);
+    layers_drop_below(c, LAYER_PLAN);                  // the two layers that read the potential go with it
     if (!q) {
-        c->plan_pot.release();
-        c->plan_words.release();
-        c->plan_path.release();
-        c->plan_host.release();
+        layer_drop(c, LAYER_PLAN);
         return CM_OK;
     }
-    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
-    const size_t n_tiles = static_cast<size_t>((c->map_info.nx + CM_PLAN_TILE - 1) / CM_PLAN_TILE) * ((c->map_info.ny + CM_PLAN_TILE - 1) / CM_PLAN_TILE);
-    if (!c->plan_pot.reserve(n_cells) || !c->plan_words.reserve(CM_PLAN_BATCH + 2 * n_tiles) ||
-        !c->plan_path.reserve(CM_PLAN_PATH_HEAD + static_cast<size_t>(q->max_path_cells)) || !c->plan_host.reserve(std::max(CM_PLAN_BATCH, CM_PLAN_PATH_HEAD)))
+    layer_reset(c->layers, LAYER_PLAN);
+    std::memset(&c->plan_layer.info, 0, sizeof c->plan_layer.info);
+    const uint64_t n_cells = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
+    const size_t n_tiles = static_cast<size_t>((c->map.info.nx + CM_PLAN_TILE - 1) / CM_PLAN_TILE) * ((c->map.info.ny + CM_PLAN_TILE - 1) / CM_PLAN_TILE);
+    if (!c->plan_layer.pot.reserve(n_cells) || !c->plan_layer.words.reserve(CM_PLAN_BATCH + 2 * n_tiles) ||
+        !c->plan_layer.path.reserve(CM_PLAN_PATH_HEAD + static_cast<size_t>(q->max_path_cells)) || !c->plan_layer.host.reserve(std::max(CM_PLAN_BATCH, CM_PLAN_PATH_HEAD)))
         return fail(c, CM_HIP_ERROR, "cannot allocate the plan layer");
-    c->plan_params = *q;
-    c->plan_on = true;
+    c->plan_layer.params = *q;
+    c->layers[LAYER_PLAN].on = true;
     return CM_OK;
 }
 
@@ -670,14 +662,14 @@ namespace {
 
 CmPlanDev plan_dev(const cm_ctx* c, const uint32_t goal[2]) {
     CmPlanDev g;
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
     g.tiles_x = (g.nx + CM_PLAN_TILE - 1) / CM_PLAN_TILE;
     g.tiles_y = (g.ny + CM_PLAN_TILE - 1) / CM_PLAN_TILE;
     g.goal = goal[0] + goal[1] * g.nx;
-    g.neutral = c->plan_params.neutral;
-    g.factor_q8 = c->plan_params.cost_factor_q8;
-    g.allow_unknown = (c->plan_params.flags & CM_PLAN_ALLOW_UNKNOWN) ? 1u : 0u;
+    g.neutral = c->plan_layer.params.neutral;
+    g.factor_q8 = c->plan_layer.params.cost_factor_q8;
+    g.allow_unknown = (c->plan_layer.params.flags & CM_PLAN_ALLOW_UNKNOWN) ? 1u : 0u;
     return g;
 }
 
@@ -694,15 +686,14 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
     const CmPlanDev g = plan_dev(c, goal);
     const size_t n_tiles = static_cast<size_t>(g.tiles_x) * g.tiles_y;
     const uint64_t bound = static_cast<uint64_t>(g.nx) * g.ny;
-    uint32_t* counters = c->plan_words;
+    uint32_t* counters = c->plan_layer.words;
     uint32_t* flags = counters + CM_PLAN_BATCH;
     hipStream_t st = c->stream;
-    c->plan_stale = "the potential is stale: the last cm_map_plan_update failed";
-    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_plan_update";
-    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_plan_update";
+    layer_mark_failed(c->layers, LAYER_PLAN);          // (until the fixed point is reached below)
+    layers_mark_below(c->layers, LAYER_PLAN, "the last cm_map_plan_update");
     c->prof_used = 0;
     prof_mark(c, "k_plan_init");
-    cmk_plan_init(st, g, c->plan_pot, flags);
+    cmk_plan_init(st, g, c->plan_layer.pot, flags);
     prof_mark(c, "k_plan_sweep");
     uint64_t launched = 0, n_sweeps = 0;
     while (!n_sweeps && launched < bound) {
@@ -710,12 +701,12 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
         HIP_TRY(c, hipMemsetAsync(counters, 0, CM_PLAN_BATCH * sizeof(uint32_t), st));
         for (uint32_t b = 0; b < batch; ++b) {
             const size_t cur = static_cast<size_t>((launched + b) & 1u) * n_tiles;
-            cmk_plan_sweep(st, c->cost_cells, g, c->plan_pot, flags + cur, flags + (n_tiles - cur), counters + b);
+            cmk_plan_sweep(st, c->cost.cells, g, c->plan_layer.pot, flags + cur, flags + (n_tiles - cur), counters + b);
         }
-        HIP_TRY(c, hipMemcpyAsync(c->plan_host, counters, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(c->plan_layer.host, counters, batch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(c, hipStreamSynchronize(st));
         for (uint32_t b = 0; b < batch && !n_sweeps; ++b)
-            if (c->plan_host[b] == 0u) n_sweeps = launched + b + 1;
+            if (c->plan_layer.host[b] == 0u) n_sweeps = launched + b + 1;
         launched += batch;
     }
     prof_mark(c, "end");
@@ -723,10 +714,10 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
     if (c->flags & CM_FLAG_PROFILE) HIP_TRY(c, hipStreamSynchronize(st));     // (the end mark only: the last batch was waited for)
     collect_stage_times(c);
     if (!n_sweeps) return fail(c, CM_INTERNAL, "the sweeps did not reach the fixed point within nx * ny launches");
-    c->plan_info.goal[0] = goal[0];
-    c->plan_info.goal[1] = goal[1];
-    c->plan_info.n_sweeps = static_cast<uint32_t>(n_sweeps);
-    c->plan_stale = nullptr;
+    c->plan_layer.info.goal[0] = goal[0];
+    c->plan_layer.info.goal[1] = goal[1];
+    c->plan_layer.info.n_sweeps = static_cast<uint32_t>(n_sweeps);
+    layer_mark_fresh(c->layers, LAYER_PLAN, c->frame_serial);
     return CM_OK;
 }
 
@@ -734,17 +725,13 @@ int map_plan_update(cm_ctx* c, const uint32_t goal[2]) {
 // and one wait here; cm_map_plan_path then copies the n_cells words the head announces and waits a second time.
 int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const CmPlanDev g = plan_dev(c, c->plan_info.goal);
+    const CmPlanDev g = plan_dev(c, c->plan_layer.info.goal);
     hipStream_t st = c->stream;
     c->prof_used = 0;
     prof_mark(c, "k_plan_path");
-    cmk_plan_path(st, c->cost_cells, c->plan_pot, g, start[0] + start[1] * g.nx, c->plan_params.max_path_cells, c->plan_path);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->plan_host, c->plan_path, CM_PLAN_PATH_HEAD * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    std::memcpy(head, c->plan_host, CM_PLAN_PATH_HEAD * sizeof(uint32_t));
+    cmk_plan_path(st, c->cost.cells, c->plan_layer.pot, g, start[0] + start[1] * g.nx, c->plan_layer.params.max_path_cells, c->plan_layer.path);
+    if (const int e = finish_call(c, c->plan_layer.host, c->plan_layer.path, CM_PLAN_PATH_HEAD * sizeof(uint32_t))) return e;
+    std::memcpy(head, c->plan_layer.host, CM_PLAN_PATH_HEAD * sizeof(uint32_t));
     if (head[1] == CM_PLAN_PATH_BROKEN_DEV) return fail(c, CM_INTERNAL, "the potential is not a fixed point: a reachable cell has no step");
     return CM_OK;
 }
@@ -754,25 +741,20 @@ int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]) {
 // layer is stale until the first update.
 int map_frontier_configure(cm_ctx* c, const cm_frontier_params* q) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->front_on = false;
-    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since cm_map_frontier_configure";
-    std::memset(&c->front_info, 0, sizeof c->front_info);
     if (!q) {
-        c->front_labels.release();
-        c->front_words.release();
-        c->front_table.release();
-        c->front_box.release();
-        c->front_host.release();
+        layer_drop(c, LAYER_FRONT);
         return CM_OK;
     }
-    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    layer_reset(c->layers, LAYER_FRONT);
+    std::memset(&c->front.info, 0, sizeof c->front.info);
+    const uint64_t n_cells = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
     const size_t n_blocks = static_cast<size_t>((n_cells + CM_FRONT_BLOCK - 1) / CM_FRONT_BLOCK);
-    if (!c->front_labels.reserve(n_cells) || !c->front_words.reserve(n_cells + n_blocks + CM_FRONT_INFO_WORDS) ||
-        !c->front_table.reserve(q->max_frontiers) || !c->front_box.reserve(4 * static_cast<size_t>(q->max_frontiers)) ||
-        !c->front_host.reserve(CM_FRONT_INFO_WORDS))
+    if (!c->front.labels.reserve(n_cells) || !c->front.words.reserve(n_cells + n_blocks + CM_FRONT_INFO_WORDS) ||
+        !c->front.table.reserve(q->max_frontiers) || !c->front.box.reserve(4 * static_cast<size_t>(q->max_frontiers)) ||
+        !c->front.host.reserve(CM_FRONT_INFO_WORDS))
         return fail(c, CM_HIP_ERROR, "cannot allocate the frontier layer");
-    c->front_params = *q;
-    c->front_on = true;
+    c->front.params = *q;
+    c->layers[LAYER_FRONT].on = true;
     return CM_OK;
 }
 
@@ -781,11 +763,11 @@ int map_frontier_configure(cm_ctx* c, const cm_frontier_params* q) {
 // wait. No loop on the host, and no allocation: cm_map_frontier_configure made them all.
 int map_frontier_update(cm_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_frontier_params& q = c->front_params;
-    const uint64_t n_cells = static_cast<uint64_t>(c->map_info.nx) * c->map_info.ny;
+    const cm_frontier_params& q = c->front.params;
+    const uint64_t n_cells = static_cast<uint64_t>(c->map.info.nx) * c->map.info.ny;
     CmFrontDev g;
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
     g.tiles_x = (g.nx + CM_FRONT_TILE - 1) / CM_FRONT_TILE;
     g.tiles_y = (g.ny + CM_FRONT_TILE - 1) / CM_FRONT_TILE;
     g.n_blocks = static_cast<uint32_t>((n_cells + CM_FRONT_BLOCK - 1) / CM_FRONT_BLOCK);
@@ -794,16 +776,16 @@ int map_frontier_update(cm_ctx* c) {
     g.max_cost = q.max_cost;
     g.pot_scale = q.pot_scale;
     g.gain_scale = q.gain_scale;
-    uint32_t* labels = c->front_labels;
-    uint32_t* size = c->front_words;
+    uint32_t* labels = c->front.labels;
+    uint32_t* size = c->front.words;
     uint32_t* counts = size + n_cells;
     uint32_t* info = counts + g.n_blocks;
     hipStream_t st = c->stream;
-    c->front_stale = "the frontiers are stale: the last cm_map_frontier_update failed";
+    layer_mark_failed(c->layers, LAYER_FRONT);
     c->prof_used = 0;
     HIP_TRY(c, hipMemsetAsync(info, 0, CM_FRONT_INFO_WORDS * sizeof(uint32_t), st));
     prof_mark(c, "k_front_local");
-    cmk_front_local(st, c->map_image, c->cost_cells, g, labels, size, info);
+    cmk_front_local(st, c->map.image, c->cost.cells, g, labels, size, info);
     prof_mark(c, "k_front_merge");
     cmk_front_merge(st, g, labels);
     prof_mark(c, "k_front_flatten");
@@ -813,25 +795,21 @@ int map_frontier_update(cm_ctx* c) {
     prof_mark(c, "k_front_scan");
     cmk_front_scan(st, g, counts, info);
     prof_mark(c, "k_front_number");
-    cmk_front_number(st, g, labels, size, counts, c->front_table, c->front_box);
+    cmk_front_number(st, g, labels, size, counts, c->front.table, c->front.box);
     prof_mark(c, "k_front_table");
-    cmk_front_table(st, g, c->plan_pot, labels, size, c->front_table, c->front_box);
+    cmk_front_table(st, g, c->plan_layer.pot, labels, size, c->front.table, c->front.box);
     prof_mark(c, "k_front_best");
-    cmk_front_best(st, g, c->front_table, c->front_box, info);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->front_host, info, CM_FRONT_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    const uint32_t* h = c->front_host;
-    c->front_info.n_frontier_cells = h[0];
-    c->front_info.n_components = h[1];
-    c->front_info.n_frontiers = h[2];
-    c->front_info.n_written = h[3];
-    c->front_info.best = h[4];
-    c->front_info._pad = 0u;
-    c->front_info.best_score = static_cast<int64_t>(static_cast<uint64_t>(h[6]) | (static_cast<uint64_t>(h[7]) << 32));
-    c->front_stale = nullptr;
+    cmk_front_best(st, g, c->front.table, c->front.box, info);
+    if (const int e = finish_call(c, c->front.host, info, CM_FRONT_INFO_WORDS * sizeof(uint32_t))) return e;
+    const uint32_t* h = c->front.host;
+    c->front.info.n_frontier_cells = h[0];
+    c->front.info.n_components = h[1];
+    c->front.info.n_frontiers = h[2];
+    c->front.info.n_written = h[3];
+    c->front.info.best = h[4];
+    c->front.info._pad = 0u;
+    c->front.info.best_score = static_cast<int64_t>(static_cast<uint64_t>(h[6]) | (static_cast<uint64_t>(h[7]) << 32));
+    layer_mark_fresh(c->layers, LAYER_FRONT, c->frame_serial);
     return CM_OK;
 }
 
@@ -869,33 +847,27 @@ void traj_samples(float lo, float hi, uint32_t n, float* out) {
 // The scores are stale until the first evaluate.
 int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->traj_on = false;
-    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since cm_map_traj_configure";
-    std::memset(&c->traj_info, 0, sizeof c->traj_info);
     if (!q) {
-        c->traj_scores.release();
-        c->traj_words.release();
-        c->traj_const.release();
-        c->traj_host.release();
-        c->traj_v = std::vector<float>();
-        c->traj_w = std::vector<float>();
+        layer_drop(c, LAYER_TRAJ);
         return CM_OK;
     }
+    layer_reset(c->layers, LAYER_TRAJ);
+    std::memset(&c->traj.info, 0, sizeof c->traj.info);
     const size_t n = static_cast<size_t>(q->nv) * q->nw, n_tab = static_cast<size_t>(q->nv) + q->nw;
     // (the page-locked words also stage the footprint for its upload below)
-    if (!c->traj_scores.reserve(n) || !c->traj_words.reserve(CM_TRAJ_INFO_WORDS + n_tab) || !c->traj_const.reserve(2 * CM_TRAJ_HEADINGS + 2 * static_cast<size_t>(n_foot)) ||
-        !c->traj_host.reserve(CM_TRAJ_INFO_WORDS + std::max(n_tab, 2 * static_cast<size_t>(n_foot))))
+    if (!c->traj.scores.reserve(n) || !c->traj.words.reserve(CM_TRAJ_INFO_WORDS + n_tab) || !c->traj.consts.reserve(2 * CM_TRAJ_HEADINGS + 2 * static_cast<size_t>(n_foot)) ||
+        !c->traj.host.reserve(CM_TRAJ_INFO_WORDS + std::max(n_tab, 2 * static_cast<size_t>(n_foot))))
         return fail(c, CM_HIP_ERROR, "cannot allocate the rollout layer");
-    c->traj_v.assign(q->nv, 0.0f);
-    c->traj_w.assign(q->nw, 0.0f);
-    std::memcpy(c->traj_host + CM_TRAJ_INFO_WORDS, foot_xy, 2 * static_cast<size_t>(n_foot) * sizeof(float));
-    HIP_TRY(c, hipMemcpyAsync(c->traj_const, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->traj_const + 2 * CM_TRAJ_HEADINGS, c->traj_host + CM_TRAJ_INFO_WORDS, 2 * static_cast<size_t>(n_foot) * sizeof(float),
+    c->traj.v.assign(q->nv, 0.0f);
+    c->traj.w.assign(q->nw, 0.0f);
+    std::memcpy(c->traj.host + CM_TRAJ_INFO_WORDS, foot_xy, 2 * static_cast<size_t>(n_foot) * sizeof(float));
+    HIP_TRY(c, hipMemcpyAsync(c->traj.consts, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->traj.consts + 2 * CM_TRAJ_HEADINGS, c->traj.host + CM_TRAJ_INFO_WORDS, 2 * static_cast<size_t>(n_foot) * sizeof(float),
                               hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->traj_params = *q;
-    c->traj_n_foot = n_foot;
-    c->traj_on = true;
+    c->traj.params = *q;
+    c->traj.n_foot = n_foot;
+    c->layers[LAYER_TRAJ].on = true;
     return CM_OK;
 }
 
@@ -905,57 +877,53 @@ int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy,
 // cm_map_traj_configure made them all.
 int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_traj_params& q = c->traj_params;
+    const cm_traj_params& q = c->traj.params;
     const double K = 4294967296.0 / 6.283185307179586;
     CmTrajDev g;
     g.x = w.x;
     g.y = w.y;
-    g.inv = 1.0f / c->map_params.cell;
-    g.ax = c->map_info.anchor[0];
-    g.ay = c->map_info.anchor[1];
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
+    g.inv = 1.0f / c->map.params.cell;
+    g.ax = c->map.info.anchor[0];
+    g.ay = c->map.info.anchor[1];
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
     g.h0 = static_cast<uint32_t>(static_cast<int64_t>(std::rint(static_cast<double>(w.yaw) * K)));
     g.nv = q.nv;
     g.nw = q.nw;
     g.n_steps = q.n_steps;
-    g.n_foot = c->traj_n_foot;
+    g.n_foot = c->traj.n_foot;
     g.occ_scale = q.occ_scale;
     g.goal_scale = q.goal_scale;
     g.allow_unknown = (q.flags & CM_TRAJ_ALLOW_UNKNOWN) ? 1u : 0u;
-    uint32_t* const up = c->traj_host + CM_TRAJ_INFO_WORDS;
+    uint32_t* const up = c->traj.host + CM_TRAJ_INFO_WORDS;
     for (uint32_t i = 0; i < q.nv; ++i) {
-        const float s = static_cast<float>(c->traj_v[i] * w.dt);
+        const float s = static_cast<float>(c->traj.v[i] * w.dt);
         std::memcpy(up + i, &s, sizeof s);
     }
     for (uint32_t j = 0; j < q.nw; ++j)
-        up[q.nv + j] = static_cast<uint32_t>(static_cast<int64_t>(std::rint((static_cast<double>(c->traj_w[j]) * static_cast<double>(w.dt)) * K)));
-    uint32_t* const info = c->traj_words;
+        up[q.nv + j] = static_cast<uint32_t>(static_cast<int64_t>(std::rint((static_cast<double>(c->traj.w[j]) * static_cast<double>(w.dt)) * K)));
+    uint32_t* const info = c->traj.words;
     uint32_t* const tab = info + CM_TRAJ_INFO_WORDS;
     const uint32_t n = q.nv * q.nw;
     hipStream_t st = c->stream;
-    c->traj_stale = "the scores are stale: the last cm_map_traj_evaluate failed";
+    layer_mark_failed(c->layers, LAYER_TRAJ);
     c->prof_used = 0;
     HIP_TRY(c, hipMemcpyAsync(tab, up, (static_cast<size_t>(q.nv) + q.nw) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     prof_mark(c, "k_traj_roll");
-    cmk_traj_roll(st, c->cost_cells, c->plan_pot, g, reinterpret_cast<const float*>(tab), tab + q.nv, c->traj_const, c->traj_const + 2 * CM_TRAJ_HEADINGS,
-                  c->traj_scores);
+    cmk_traj_roll(st, c->cost.cells, c->plan_layer.pot, g, reinterpret_cast<const float*>(tab), tab + q.nv, c->traj.consts, c->traj.consts + 2 * CM_TRAJ_HEADINGS,
+                  c->traj.scores);
     prof_mark(c, "k_traj_best");
-    cmk_traj_best(st, c->traj_scores, n, info);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->traj_host, info, CM_TRAJ_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    const uint32_t best = c->traj_host[0];
+    cmk_traj_best(st, c->traj.scores, n, info);
+    if (const int e = finish_call(c, c->traj.host, info, CM_TRAJ_INFO_WORDS * sizeof(uint32_t))) return e;
+    const uint32_t best = c->traj.host[0];
     if (best != CM_TRAJ_NONE && best >= n) return fail(c, CM_INTERNAL, "the best entry lies outside the table");
-    c->traj_info.best = best;
-    c->traj_info.n_valid = c->traj_host[1];
-    c->traj_info.best_v = best == CM_TRAJ_NONE ? 0.0f : c->traj_v[best / q.nw];
-    c->traj_info.best_w = best == CM_TRAJ_NONE ? 0.0f : c->traj_w[best % q.nw];
-    c->traj_info.start[0] = start[0];
-    c->traj_info.start[1] = start[1];
-    c->traj_stale = nullptr;
+    c->traj.info.best = best;
+    c->traj.info.n_valid = c->traj.host[1];
+    c->traj.info.best_v = best == CM_TRAJ_NONE ? 0.0f : c->traj.v[best / q.nw];
+    c->traj.info.best_w = best == CM_TRAJ_NONE ? 0.0f : c->traj.w[best % q.nw];
+    c->traj.info.start[0] = start[0];
+    c->traj.info.start[1] = start[1];
+    layer_mark_fresh(c->layers, LAYER_TRAJ, c->frame_serial);
     return CM_OK;
 }
 
@@ -964,31 +932,25 @@ int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2
 // an evaluate uploads from and reads back into. nullptr gives it back. Volume and result are stale until the first evaluate.
 int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->match_on = false;
-    c->match_stale = "the match is stale: no cm_map_match_evaluate since cm_map_match_configure";
-    std::memset(&c->match_result, 0, sizeof c->match_result);
     if (!q) {
-        c->match_field.release();
-        c->match_bits.release();
-        c->match_vol.release();
-        c->match_q.release();
-        c->match_host.release();
-        c->match_lut_host = std::vector<unsigned char>();
+        layer_drop(c, LAYER_MATCH);
         return CM_OK;
     }
-    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, words = (n_cells + 31) / 32;
+    layer_reset(c->layers, LAYER_MATCH);
+    std::memset(&c->match.result, 0, sizeof c->match.result);
+    const size_t n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny, words = (n_cells + 31) / 32;
     const size_t n_k = 2 * static_cast<size_t>(q->n_a) + 1, n_vol = n_k * (2 * static_cast<size_t>(q->wx) + 1) * (2 * static_cast<size_t>(q->wy) + 1);
     const size_t n_lut = static_cast<size_t>(R) * R + 1;
-    if (!c->match_field.reserve(n_cells + n_lut) || !c->match_bits.reserve(n_k * words) || !c->match_vol.reserve(n_vol + CM_MATCH_INFO_WORDS) ||
-        !c->match_q.reserve(6 * n_k) || !c->match_host.reserve(CM_MATCH_INFO_WORDS + 6 * n_k))
+    if (!c->match.field.reserve(n_cells + n_lut) || !c->match.bits.reserve(n_k * words) || !c->match.vol.reserve(n_vol + CM_MATCH_INFO_WORDS) ||
+        !c->match.q.reserve(6 * n_k) || !c->match.host.reserve(CM_MATCH_INFO_WORDS + 6 * n_k))
         return fail(c, CM_HIP_ERROR, "cannot allocate the matching layer");
-    c->match_lut_host.assign(n_lut, 0);
-    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, c->match_lut_host.data());
-    HIP_TRY(c, hipMemcpyAsync(c->match_field + n_cells, c->match_lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    c->match.lut_host.assign(n_lut, 0);
+    cm_match_table_build(c->map.params.cell, q->sigma, q->max_dist, R, c->match.lut_host.data());
+    HIP_TRY(c, hipMemcpyAsync(c->match.field + n_cells, c->match.lut_host.data(), n_lut, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->match_params = *q;
-    c->match_radius = R;
-    c->match_on = true;
+    c->match.params = *q;
+    c->match.radius = R;
+    c->layers[LAYER_MATCH].on = true;
     return CM_OK;
 }
 
@@ -998,28 +960,28 @@ int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R) {
 // them all.
 int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_match_params& q = c->match_params;
-    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny;
+    const cm_match_params& q = c->match.params;
+    const size_t n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny;
     CmMatchDev g;
     g.tx = pose[3];
     g.ty = pose[7];
-    g.inv = 1.0f / c->map_params.cell;
-    g.ax = c->map_info.anchor[0];
-    g.ay = c->map_info.anchor[1];
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
-    g.z_min = c->map_params.z_min;
-    g.z_max = c->map_params.z_max;
+    g.inv = 1.0f / c->map.params.cell;
+    g.ax = c->map.info.anchor[0];
+    g.ay = c->map.info.anchor[1];
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
+    g.z_min = c->map.params.z_min;
+    g.z_max = c->map.params.z_max;
     g.n_a = q.n_a;
     g.n_k = 2u * q.n_a + 1u;
     g.wx = q.wx;
     g.wy = q.wy;
     g.words = static_cast<uint32_t>((n_cells + 31) / 32);
-    g.r2 = c->match_radius * c->match_radius;
+    g.r2 = c->match.radius * c->match.radius;
     const uint32_t sx = 2u * q.wx + 1u, sy = 2u * q.wy + 1u;
     const size_t n_vol = static_cast<size_t>(g.n_k) * sx * sy;
     const float* const dirs = traj_direction_table();
-    float* const up = reinterpret_cast<float*>(c->match_host + CM_MATCH_INFO_WORDS);
+    float* const up = reinterpret_cast<float*>(c->match.host + CM_MATCH_INFO_WORDS);
     for (uint32_t kk = 0; kk < g.n_k; ++kk) {
         const int k = static_cast<int>(kk) - static_cast<int>(q.n_a);
         const uint32_t e = static_cast<uint32_t>(k * static_cast<int>(q.a_stride)) & (CM_TRAJ_HEADINGS - 1u);
@@ -1029,32 +991,28 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
             up[6 * kk + 3 + j] = static_cast<float>(static_cast<float>(sn * pose[j]) + static_cast<float>(cs * pose[4 + j]));
         }
     }
-    uint32_t* const info = c->match_vol + n_vol;
+    uint32_t* const info = c->match.vol + n_vol;
     const uint32_t n_tiles = c->frame.n_tiles;
     hipStream_t st = c->stream;
-    c->match_stale = "the match is stale: the last cm_map_match_evaluate failed";
+    layer_mark_failed(c->layers, LAYER_MATCH);
     c->prof_used = 0;
-    HIP_TRY(c, hipMemcpyAsync(c->match_q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->match.q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
     prof_mark(c, "match_clear");
-    HIP_TRY(c, hipMemsetAsync(c->match_bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
-    HIP_TRY(c, hipMemsetAsync(c->match_vol, 0, n_vol * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->match.bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->match.vol, 0, n_vol * 4, st));
     prof_mark(c, "k_match_field");
-    cmk_match_field(st, c->cost_dist2, c->match_field + n_cells, g.r2, static_cast<uint32_t>(n_cells), c->match_field);
+    cmk_match_field(st, c->cost.dist2, c->match.field + n_cells, g.r2, static_cast<uint32_t>(n_cells), c->match.field);
     prof_mark(c, "k_match_mark");
-    cmk_match_mark(st, c->d_frame, g, c->match_q, c->frame_mask, c->match_bits, n_tiles);
+    cmk_match_mark(st, c->d_frame, g, c->match.q, c->frame_mask, c->match.bits, n_tiles);
     prof_mark(c, "k_match_score");
-    cmk_match_score(st, c->match_field, c->match_bits, g, c->match_vol);
+    cmk_match_score(st, c->match.field, c->match.bits, g, c->match.vol);
     prof_mark(c, "k_match_best");
-    cmk_match_best(st, c->match_vol, c->match_bits, g, info);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->match_host, info, CM_MATCH_INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    const uint32_t* const h = c->match_host;
+    cmk_match_best(st, c->match.vol, c->match.bits, g, info);
+    if (const int e = finish_call(c, c->match.host, info, CM_MATCH_INFO_WORDS * sizeof(uint32_t))) return e;
+    const uint32_t* const h = c->match.host;
     const uint32_t best = h[0];
     if (best >= n_vol) return fail(c, CM_INTERNAL, "the best entry lies outside the volume");
-    cm_match_result& r = c->match_result;
+    cm_match_result& r = c->match.result;
     r.best = best;
     r.k = static_cast<int32_t>(best / (sx * sy)) - static_cast<int32_t>(q.n_a);
     r.j = static_cast<int32_t>((best / sx) % sy) - static_cast<int32_t>(q.wy);
@@ -1074,7 +1032,7 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     r.sub[0] = sub(r.i > -static_cast<int32_t>(q.wx) && r.i < static_cast<int32_t>(q.wx), h[3], h[4]);
     r.sub[1] = sub(r.j > -static_cast<int32_t>(q.wy) && r.j < static_cast<int32_t>(q.wy), h[5], h[6]);
     const uint32_t bk = best / (sx * sy);
-    const double cell = static_cast<double>(c->map_params.cell);
+    const double cell = static_cast<double>(c->map.params.cell);
     for (int j = 0; j < 3; ++j) {
         r.pose[j] = up[6 * bk + j];
         r.pose[4 + j] = up[6 * bk + 3 + j];
@@ -1082,8 +1040,7 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     r.pose[3] = static_cast<float>(pose[3] + static_cast<float>((static_cast<double>(r.i) + r.sub[0]) * cell));
     r.pose[7] = static_cast<float>(pose[7] + static_cast<float>((static_cast<double>(r.j) + r.sub[1]) * cell));
     for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
-    c->match_serial = c->frame_serial;
-    c->match_stale = nullptr;
+    layer_mark_fresh(c->layers, LAYER_MATCH, c->frame_serial);
     return CM_OK;
 }
 
@@ -1093,56 +1050,47 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
 // update reads back. nullptr gives it back. No particles, gen = 0, weights and info stale until the first update.
 int map_mcl_configure(cm_ctx* c, const cm_mcl_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->mcl_on = false;
-    c->mcl_init = false;
-    c->mcl_gen = 0;
-    c->mcl_cur = 0;
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since cm_map_mcl_configure";
-    std::memset(&c->mcl_info, 0, sizeof c->mcl_info);
     if (!q) {
-        c->mcl_parts[0].release();
-        c->mcl_parts[1].release();
-        c->mcl_wts.release();
-        c->mcl_cum.release();
-        c->mcl_field.release();
-        c->mcl_bits.release();
-        c->mcl_list.release();
-        c->mcl_dirs.release();
-        c->mcl_host.release();
+        layer_drop(c, LAYER_MCL);
         return CM_OK;
     }
-    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, side = 2 * static_cast<size_t>(q->range_cells) + 1;
+    layer_reset(c->layers, LAYER_MCL);
+    c->mcl.init = false;
+    c->mcl.gen = 0;
+    c->mcl.cur = 0;
+    std::memset(&c->mcl.info, 0, sizeof c->mcl.info);
+    const size_t n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny, side = 2 * static_cast<size_t>(q->range_cells) + 1;
     const size_t words = std::max((n_cells + 31) / 32, (side * side + 31) / 32);
     const size_t n_lut = static_cast<size_t>(R) * R + 1, n = q->n_particles;
-    if (!c->mcl_parts[0].reserve(n) || !c->mcl_parts[1].reserve(n) || !c->mcl_wts.reserve(n) || !c->mcl_cum.reserve(n + CM_MCL_WORDS) ||
-        !c->mcl_field.reserve(n_cells + n_lut) || !c->mcl_bits.reserve(words) ||
-        !c->mcl_list.reserve(CM_MCL_ONE_BLOCK + std::max(static_cast<size_t>(q->max_beams), n_cells)) || !c->mcl_dirs.reserve(2 * CM_TRAJ_HEADINGS) ||
-        !c->mcl_host.reserve(CM_MCL_WORDS))
+    if (!c->mcl.parts[0].reserve(n) || !c->mcl.parts[1].reserve(n) || !c->mcl.wts.reserve(n) || !c->mcl.cum.reserve(n + CM_MCL_WORDS) ||
+        !c->mcl.field.reserve(n_cells + n_lut) || !c->mcl.bits.reserve(words) ||
+        !c->mcl.list.reserve(CM_MCL_ONE_BLOCK + std::max(static_cast<size_t>(q->max_beams), n_cells)) || !c->mcl.dirs.reserve(2 * CM_TRAJ_HEADINGS) ||
+        !c->mcl.host.reserve(CM_MCL_WORDS))
         return fail(c, CM_HIP_ERROR, "cannot allocate the localisation layer");
     std::vector<unsigned char> lut(n_lut, 0);
-    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, lut.data());
-    HIP_TRY(c, hipMemcpyAsync(c->mcl_field + n_cells, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->mcl_dirs, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    cm_match_table_build(c->map.params.cell, q->sigma, q->max_dist, R, lut.data());
+    HIP_TRY(c, hipMemcpyAsync(c->mcl.field + n_cells, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->mcl.dirs, traj_direction_table(), 2 * CM_TRAJ_HEADINGS * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->mcl_params = *q;
-    c->mcl_radius = R;
-    c->mcl_on = true;
+    c->mcl.params = *q;
+    c->mcl.radius = R;
+    c->layers[LAYER_MCL].on = true;
     return CM_OK;
 }
 
 namespace {
 
 CmMclDev mcl_dev(const cm_ctx* c) {
-    const cm_mcl_params& q = c->mcl_params;
+    const cm_mcl_params& q = c->mcl.params;
     CmMclDev g;
-    g.inv = 1.0f / c->map_params.cell;
-    g.cell = c->map_params.cell;
-    g.ax = c->map_info.anchor[0];
-    g.ay = c->map_info.anchor[1];
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
-    g.z_min = c->map_params.z_min;
-    g.z_max = c->map_params.z_max;
+    g.inv = 1.0f / c->map.params.cell;
+    g.cell = c->map.params.cell;
+    g.ax = c->map.info.anchor[0];
+    g.ay = c->map.info.anchor[1];
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
+    g.z_min = c->map.params.z_min;
+    g.z_max = c->map.params.z_max;
     g.n = q.n_particles;
     g.max_beams = q.max_beams;
     g.range = q.range_cells;
@@ -1162,7 +1110,7 @@ CmMclMoveDev mcl_move(cm_ctx* c, const float v[6]) {
     m.sc_a = mcl_scale(v[3]);
     m.sc_b = mcl_scale(v[4]);
     m.sc_yaw = mcl_scale(v[5]);
-    m.base = cm_mcl_base(c->mcl_params.seed, c->mcl_gen++);
+    m.base = cm_mcl_base(c->mcl.params.seed, c->mcl.gen++);
     return m;
 }
 
@@ -1170,17 +1118,14 @@ CmMclMoveDev mcl_move(cm_ctx* c, const float v[6]) {
 
 int map_mcl_init_pose(cm_ctx* c, const float v[6]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->mcl_init = false;
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_init_pose";
-    c->mcl_cur = 0;
+    c->mcl.init = false;
+    layer_mark_stale(c->layers, LAYER_MCL, "the last cm_map_mcl_init_pose");
+    c->mcl.cur = 0;
     c->prof_used = 0;
     prof_mark(c, "k_mcl_init_pose");
-    cmk_mcl_init_pose(c->stream, mcl_move(c, v), c->mcl_params.n_particles, c->mcl_parts[0]);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    collect_stage_times(c);
-    c->mcl_init = true;
+    cmk_mcl_init_pose(c->stream, mcl_move(c, v), c->mcl.params.n_particles, c->mcl.parts[0]);
+    if (const int e = finish_call(c)) return e;
+    c->mcl.init = true;
     return CM_OK;
 }
 
@@ -1190,42 +1135,36 @@ int map_mcl_init_uniform(cm_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     const CmMclDev g = mcl_dev(c);
     const uint32_t n_cells = g.nx * g.ny, n_words = (n_cells + 31u) / 32u;
-    unsigned long long* const words = c->mcl_cum + g.n;
-    uint32_t* const counts = c->mcl_list;
-    uint32_t* const list = c->mcl_list + CM_MCL_ONE_BLOCK;
+    unsigned long long* const words = c->mcl.cum + g.n;
+    uint32_t* const counts = c->mcl.list;
+    uint32_t* const list = c->mcl.list + CM_MCL_ONE_BLOCK;
     hipStream_t st = c->stream;
     c->prof_used = 0;
     prof_mark(c, "k_mcl_free_bits");
-    cmk_mcl_free_bits(st, c->map_image, n_cells, c->mcl_bits);
+    cmk_mcl_free_bits(st, c->map.image, n_cells, c->mcl.bits);
     prof_mark(c, "k_mcl_compact");
-    cmk_mcl_compact(st, c->mcl_bits, n_words, n_cells, counts, list, words);
+    cmk_mcl_compact(st, c->mcl.bits, n_words, n_cells, counts, list, words);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->mcl_host, words, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(c->mcl.host, words, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    if (c->mcl_host[CM_MCL_W_NCELLS] == 0) return fail(c, CM_BAD_ARG, "the map's image holds no free cell");
-    c->mcl_init = false;
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_init_uniform";
-    c->mcl_cur = 0;
+    if (c->mcl.host[CM_MCL_W_NCELLS] == 0) return fail(c, CM_BAD_ARG, "the map's image holds no free cell");
+    c->mcl.init = false;
+    layer_mark_stale(c->layers, LAYER_MCL, "the last cm_map_mcl_init_uniform");
+    c->mcl.cur = 0;
     prof_mark(c, "k_mcl_init_uniform");
-    cmk_mcl_init_uniform(st, g, cm_mcl_base(c->mcl_params.seed, c->mcl_gen++), list, words, c->mcl_parts[0]);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    c->mcl_init = true;
+    cmk_mcl_init_uniform(st, g, cm_mcl_base(c->mcl.params.seed, c->mcl.gen++), list, words, c->mcl.parts[0]);
+    if (const int e = finish_call(c)) return e;
+    c->mcl.init = true;
     return CM_OK;
 }
 
 int map_mcl_predict(cm_ctx* c, const float v[6]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_mcl_predict";
+    layer_mark_stale(c->layers, LAYER_MCL, "the last cm_map_mcl_predict");
     c->prof_used = 0;
     prof_mark(c, "k_mcl_predict");
-    cmk_mcl_predict(c->stream, mcl_move(c, v), c->mcl_params.n_particles, c->mcl_dirs, c->mcl_parts[c->mcl_cur]);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    collect_stage_times(c);
+    cmk_mcl_predict(c->stream, mcl_move(c, v), c->mcl.params.n_particles, c->mcl.dirs, c->mcl.parts[c->mcl.cur]);
+    if (const int e = finish_call(c)) return e;
     return CM_OK;
 }
 
@@ -1235,52 +1174,48 @@ int map_mcl_predict(cm_ctx* c, const float v[6]) {
 // round trip. The host learns from the words whether the particles now live in the other buffer. No allocation.
 int map_mcl_update(cm_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_mcl_params& q = c->mcl_params;
+    const cm_mcl_params& q = c->mcl.params;
     const CmMclDev g = mcl_dev(c);
     const size_t n_cells = static_cast<size_t>(g.nx) * g.ny;
     const uint32_t body_words = static_cast<uint32_t>((static_cast<uint64_t>(g.side) * g.side + 31u) / 32u);
-    const uint32_t r2 = c->mcl_radius * c->mcl_radius;
-    unsigned long long* const words = c->mcl_cum + g.n;
-    uint32_t* const counts = c->mcl_list;
-    uint32_t* const list = c->mcl_list + CM_MCL_ONE_BLOCK;
-    CmMclParticleDev* const src = c->mcl_parts[c->mcl_cur];
-    CmMclParticleDev* const dst = c->mcl_parts[c->mcl_cur ^ 1];
-    const uint64_t gen = c->mcl_gen++;
+    const uint32_t r2 = c->mcl.radius * c->mcl.radius;
+    unsigned long long* const words = c->mcl.cum + g.n;
+    uint32_t* const counts = c->mcl.list;
+    uint32_t* const list = c->mcl.list + CM_MCL_ONE_BLOCK;
+    CmMclParticleDev* const src = c->mcl.parts[c->mcl.cur];
+    CmMclParticleDev* const dst = c->mcl.parts[c->mcl.cur ^ 1];
+    const uint64_t gen = c->mcl.gen++;
     const unsigned long long base = cm_mcl_base(q.seed, gen);
     const double beta = 1.0 / (255.0 * static_cast<double>(q.tau));
     const double thr = static_cast<double>(q.resample_frac) * static_cast<double>(q.n_particles);
     hipStream_t st = c->stream;
-    c->mcl_stale = "the weights are stale: the last cm_map_mcl_update failed";
+    layer_mark_failed(c->layers, LAYER_MCL);
     c->prof_used = 0;
     prof_mark(c, "mcl_clear");
-    HIP_TRY(c, hipMemsetAsync(c->mcl_bits, 0, static_cast<size_t>(body_words) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->mcl.bits, 0, static_cast<size_t>(body_words) * 4, st));
     HIP_TRY(c, hipMemsetAsync(words, 0, CM_MCL_WORDS * sizeof(unsigned long long), st));
     prof_mark(c, "k_match_field");
-    cmk_match_field(st, c->cost_dist2, c->mcl_field + n_cells, r2, static_cast<uint32_t>(n_cells), c->mcl_field);
+    cmk_match_field(st, c->cost.dist2, c->mcl.field + n_cells, r2, static_cast<uint32_t>(n_cells), c->mcl.field);
     prof_mark(c, "k_mcl_mark");
-    cmk_mcl_mark(st, c->d_frame, g, c->frame_mask, c->mcl_bits, c->frame.n_tiles);
+    cmk_mcl_mark(st, c->d_frame, g, c->frame_mask, c->mcl.bits, c->frame.n_tiles);
     prof_mark(c, "k_mcl_compact");
-    cmk_mcl_compact(st, c->mcl_bits, body_words, q.max_beams, counts, list, words);
+    cmk_mcl_compact(st, c->mcl.bits, body_words, q.max_beams, counts, list, words);
     prof_mark(c, "k_mcl_score");
-    cmk_mcl_score(st, c->mcl_field, g, list, words, c->mcl_dirs, src, c->mcl_wts);
+    cmk_mcl_score(st, c->mcl.field, g, list, words, c->mcl.dirs, src, c->mcl.wts);
     prof_mark(c, "k_mcl_best");
     cmk_mcl_best(st, src, g.n, words);
     prof_mark(c, "k_mcl_weights");
-    cmk_mcl_weights(st, src, g.n, beta, c->mcl_dirs, c->mcl_wts, words);
+    cmk_mcl_weights(st, src, g.n, beta, c->mcl.dirs, c->mcl.wts, words);
     prof_mark(c, "k_mcl_spread");
-    cmk_mcl_spread(st, src, g.n, c->mcl_wts, words);
+    cmk_mcl_spread(st, src, g.n, c->mcl.wts, words);
     prof_mark(c, "k_mcl_resample");
-    cmk_mcl_resample(st, src, dst, g.n, c->mcl_wts, c->mcl_cum, cm_mcl_splitmix64(base ^ (1ull << 63)), thr,
+    cmk_mcl_resample(st, src, dst, g.n, c->mcl.wts, c->mcl.cum, cm_mcl_splitmix64(base ^ (1ull << 63)), thr,
                      (q.flags & CM_MCL_RESAMPLE_ALWAYS) ? 1u : 0u, words);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->mcl_host, words, CM_MCL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    const unsigned long long* const h = c->mcl_host;
+    if (const int e = finish_call(c, c->mcl.host, words, CM_MCL_WORDS * sizeof(unsigned long long))) return e;
+    const unsigned long long* const h = c->mcl.host;
     if (h[CM_MCL_W_BEST] >= g.n || h[CM_MCL_W_SW] < CM_MCL_WEIGHT_ONE || h[CM_MCL_W_SW2] == 0) return fail(c, CM_INTERNAL, "the info words of the update are not a result");
-    if (h[CM_MCL_W_RESAMPLED]) c->mcl_cur ^= 1;
-    cm_mcl_info& r = c->mcl_info;
+    if (h[CM_MCL_W_RESAMPLED]) c->mcl.cur ^= 1;
+    cm_mcl_info& r = c->mcl.info;
     std::memset(&r, 0, sizeof r);
     r.n_particles = g.n;
     r.n_cells = static_cast<uint32_t>(h[CM_MCL_W_NCELLS]);
@@ -1311,8 +1246,7 @@ int map_mcl_update(cm_ctx* c) {
     r.var_xx = static_cast<double>(r.sum_wdxx) / den;
     r.var_yy = static_cast<double>(r.sum_wdyy) / den;
     r.var_xy = static_cast<double>(r.sum_wdxy) / den;
-    c->mcl_serial = c->frame_serial;
-    c->mcl_stale = nullptr;
+    layer_mark_fresh(c->layers, LAYER_MCL, c->frame_serial);
     return CM_OK;
 }
 
@@ -1328,34 +1262,27 @@ void cast_direction_table(uint32_t range_cells, int16_t* dst) {
 // the first evaluate.
 int map_cast_configure(cm_ctx* c, const cm_cast_params* q, const uint32_t* bearings) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->cast_on = false;
-    c->cast_steps_fresh = false;
-    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since cm_map_cast_configure";
-    std::memset(&c->cast_info, 0, sizeof c->cast_info);
     if (!q) {
-        c->cast_rays.release();
-        c->cast_poses.release();
-        c->cast_bearings.release();
-        c->cast_dirs.release();
-        c->cast_steps.release();
-        c->cast_words.release();
-        c->cast_host.release();
+        layer_drop(c, LAYER_CAST);
         return CM_OK;
     }
-    const size_t n_cells = static_cast<size_t>(c->map_info.nx) * c->map_info.ny, nb = q->n_bearings;
-    if (!c->cast_rays.reserve(static_cast<size_t>(q->max_poses) * nb) || !c->cast_poses.reserve(3 * static_cast<size_t>(q->max_poses)) ||
-        !c->cast_bearings.reserve(nb) || !c->cast_dirs.reserve(CM_CAST_DIRS) || !c->cast_steps.reserve((n_cells + 3) / 4 * 4) ||
-        !c->cast_words.reserve(CM_CAST_WORDS) || !c->cast_host.reserve(CM_CAST_WORDS))
+    layer_reset(c->layers, LAYER_CAST);
+    c->cast.steps_fresh = false;
+    std::memset(&c->cast.info, 0, sizeof c->cast.info);
+    const size_t n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny, nb = q->n_bearings;
+    if (!c->cast.rays.reserve(static_cast<size_t>(q->max_poses) * nb) || !c->cast.poses.reserve(3 * static_cast<size_t>(q->max_poses)) ||
+        !c->cast.bearings.reserve(nb) || !c->cast.dirs.reserve(CM_CAST_DIRS) || !c->cast.steps.reserve((n_cells + 3) / 4 * 4) ||
+        !c->cast.words.reserve(CM_CAST_WORDS) || !c->cast.host.reserve(CM_CAST_WORDS))
         return fail(c, CM_HIP_ERROR, "cannot allocate the cast layer");
     std::vector<uint32_t> b(nb);
     for (size_t a = 0; a < nb; ++a) b[a] = bearings ? bearings[a] : static_cast<uint32_t>((static_cast<uint64_t>(a) << 32) / nb);
     std::vector<int16_t> dirs(2 * CM_CAST_DIRS);
     cast_direction_table(q->range_cells, dirs.data());
-    HIP_TRY(c, hipMemcpyAsync(c->cast_bearings, b.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->cast_dirs, dirs.data(), CM_CAST_DIRS * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->cast.bearings, b.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->cast.dirs, dirs.data(), CM_CAST_DIRS * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->cast_params = *q;
-    c->cast_on = true;
+    c->cast.params = *q;
+    c->layers[LAYER_CAST].on = true;
     return CM_OK;
 }
 
@@ -1364,47 +1291,43 @@ int map_cast_configure(cm_ctx* c, const cm_cast_params* q, const uint32_t* beari
 // of the counts back and one wait. No allocation.
 int map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_cast_params& q = c->cast_params;
+    const cm_cast_params& q = c->cast.params;
     CmCastDev g;
-    g.inv = 1.0f / c->map_params.cell;
-    g.ax = c->map_info.anchor[0];
-    g.ay = c->map_info.anchor[1];
-    g.nx = c->map_info.nx;
-    g.ny = c->map_info.ny;
+    g.inv = 1.0f / c->map.params.cell;
+    g.ax = c->map.info.anchor[0];
+    g.ay = c->map.info.anchor[1];
+    g.nx = c->map.info.nx;
+    g.ny = c->map.info.ny;
     g.n_poses = n;
     g.n_bearings = q.n_bearings;
     g.pose_words = host_poses ? 3u : static_cast<uint32_t>(sizeof(CmMclParticleDev) / sizeof(uint32_t));
     g.plain = (q.flags & CM_CAST_PLAIN) ? 1u : 0u;
-    const void* const poses = host_poses ? static_cast<const void*>(c->cast_poses) : static_cast<const void*>(c->mcl_parts[c->mcl_cur]);
+    const void* const poses = host_poses ? static_cast<const void*>(c->cast.poses) : static_cast<const void*>(c->mcl.parts[c->mcl.cur]);
     hipStream_t st = c->stream;
-    c->cast_stale = "the rays are stale: the last evaluate of the cast layer failed";
+    layer_mark_failed(c->layers, LAYER_CAST);
     c->prof_used = 0;
     prof_mark(c, "cast_upload");
-    if (host_poses) HIP_TRY(c, hipMemcpyAsync(c->cast_poses, host_poses, static_cast<size_t>(n) * sizeof(cm_cast_pose), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->cast_words, 0, CM_CAST_WORDS * sizeof(uint32_t), st));
-    if (!g.plain && !c->cast_steps_fresh) {
+    if (host_poses) HIP_TRY(c, hipMemcpyAsync(c->cast.poses, host_poses, static_cast<size_t>(n) * sizeof(cm_cast_pose), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->cast.words, 0, CM_CAST_WORDS * sizeof(uint32_t), st));
+    if (!g.plain && !c->cast.steps_fresh) {
         prof_mark(c, "k_cast_steps");
-        cmk_cast_steps(st, c->cost_dist2, g.nx * g.ny, c->cast_steps);
+        cmk_cast_steps(st, c->cost.dist2, g.nx * g.ny, c->cast.steps);
     }
     prof_mark(c, "k_cast_rays");
-    cmk_cast_rays(st, c->map_image, c->cast_steps, g, poses, c->cast_bearings, c->cast_dirs, c->cast_rays, c->cast_words);
-    prof_mark(c, "end");
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->cast_host, c->cast_words, CM_CAST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    collect_stage_times(c);
-    if (!g.plain) c->cast_steps_fresh = true;
-    const uint32_t* const h = c->cast_host;
+    cmk_cast_rays(st, c->map.image, c->cast.steps, g, poses, c->cast.bearings, c->cast.dirs, c->cast.rays, c->cast.words);
+    if (const int e = finish_call(c, c->cast.host, c->cast.words, CM_CAST_WORDS * sizeof(uint32_t))) return e;
+    if (!g.plain) c->cast.steps_fresh = true;
+    const uint32_t* const h = c->cast.host;
     if (static_cast<uint64_t>(h[0]) + h[1] + h[2] + h[3] != static_cast<uint64_t>(n) * q.n_bearings)
         return fail(c, CM_INTERNAL, "the status counts of the cast do not add up to its rays");
-    cm_cast_info& r = c->cast_info;
+    cm_cast_info& r = c->cast.info;
     r.n_poses = n;
     r.n_bearings = q.n_bearings;
     r.n_max = h[CM_CAST_MAX];
     r.n_hit = h[CM_CAST_HIT];
     r.n_off_map = h[CM_CAST_OFF_MAP];
     r.n_no_origin = h[CM_CAST_NO_ORIGIN];
-    c->cast_stale = nullptr;
+    layer_mark_fresh(c->layers, LAYER_CAST, c->frame_serial);
     return CM_OK;
 }
 
@@ -1412,26 +1335,19 @@ int map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n) {
 // behind go stale exactly as after an integration, and the frame at rest counts as not yet integrated.
 int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_map_params& q = c->map_params;
+    const cm_map_params& q = c->map.params;
     const uint64_t n_cells = static_cast<uint64_t>(q.nx) * q.ny;
     hipStream_t st = c->stream;
-    HIP_TRY(c, hipMemcpyAsync(c->map_state[c->map_cur], src, n_cells * sizeof(cm_map_cell), hipMemcpyHostToDevice, st));
-    cmk_map_image(st, c->map_state[c->map_cur], static_cast<uint32_t>(n_cells), q.l_free, q.l_occ, c->map_image);
+    HIP_TRY(c, hipMemcpyAsync(c->map.state[c->map.cur], src, n_cells * sizeof(cm_map_cell), hipMemcpyHostToDevice, st));
+    cmk_map_image(st, c->map.state[c->map.cur], static_cast<uint32_t>(n_cells), q.l_free, q.l_occ, c->map.image);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(st));
-    c->map_info.anchor[0] = anchor[0];
-    c->map_info.anchor[1] = anchor[1];
-    c->map_info.n_frames = 1;
-    c->map_info.sensors_cast = 0;
-    c->map_serial = 0;
-    c->cost_fresh = false;
-    c->plan_stale = "the potential is stale: no cm_map_plan_update since the last cm_map_load";
-    c->traj_stale = "the scores are stale: no cm_map_traj_evaluate since the last cm_map_load";
-    c->front_stale = "the frontiers are stale: no cm_map_frontier_update since the last cm_map_load";
-    c->match_stale = "the match is stale: no cm_map_match_evaluate since the last cm_map_load";
-    c->msearch_stale = "the search is stale: no cm_map_match_search since the last cm_map_load";
-    c->mcl_stale = "the weights are stale: no cm_map_mcl_update since the last cm_map_load";
-    c->cast_stale = "the rays are stale: no cm_map_cast_evaluate since the last cm_map_load";
+    c->map.info.anchor[0] = anchor[0];
+    c->map.info.anchor[1] = anchor[1];
+    c->map.info.n_frames = 1;
+    c->map.info.sensors_cast = 0;
+    c->map.serial = 0;
+    layers_mark_below(c->layers, LAYER_MAP, "the last cm_map_load");
     return CM_OK;
 }
 
@@ -1470,44 +1386,38 @@ MSearchLayout msearch_layout(const cm_match_search_params& q, uint32_t n_roots) 
 // the candidates' matrices and the page-locked words. nullptr gives it back. Everything is stale until the first evaluate.
 int map_msearch_configure(cm_ctx* c, const cm_match_search_params* q, uint32_t R) {
     HIP_TRY(c, hipSetDevice(c->device));
-    c->msearch_on = false;
-    c->msearch_stale = "the search is stale: no cm_map_match_search since cm_map_match_search_configure";
-    std::memset(&c->msearch_result, 0, sizeof c->msearch_result);
-    std::memset(&c->msearch_info, 0, sizeof c->msearch_info);
     if (!q) {
-        c->msearch_pyr.release();
-        c->msearch_bits.release();
-        c->msearch_cells.release();
-        c->msearch_nodes.release();
-        c->msearch_q.release();
-        c->msearch_host.release();
+        layer_drop(c, LAYER_SEARCH);
         return CM_OK;
     }
-    const uint32_t nx = c->map_info.nx, ny = c->map_info.ny;
+    layer_reset(c->layers, LAYER_SEARCH);
+    std::memset(&c->msearch.result, 0, sizeof c->msearch.result);
+    std::memset(&c->msearch.info, 0, sizeof c->msearch.info);
+    const uint32_t nx = c->map.info.nx, ny = c->map.info.ny;
     const size_t n_cells = static_cast<size_t>(nx) * ny, words = (n_cells + 31) / 32;
     const size_t n_k = 2 * static_cast<size_t>(q->n_a) + 1, n_lut = static_cast<size_t>(R) * R + 1;
     const uint32_t rx = msearch_roots_along(q->wx, q->depth), ry = msearch_roots_along(q->wy, q->depth);
     const uint32_t n_roots = static_cast<uint32_t>(n_k) * rx * ry;
     const MSearchLayout l = msearch_layout(*q, n_roots);
     const size_t n_pyr = msearch_level_offset(nx, ny, q->depth + 1u);
-    if (!c->msearch_pyr.reserve(n_pyr + n_lut) || !c->msearch_bits.reserve(n_k * words) || !c->msearch_cells.reserve(n_k * q->max_cells + n_k) ||
-        !c->msearch_nodes.reserve(l.words + CM_MSEARCH_WORDS) || !c->msearch_q.reserve(6 * n_k) ||
-        !c->msearch_host.reserve(std::max(l.h_q + 6 * n_k, static_cast<size_t>(n_roots))))
+    if (!c->msearch.pyr.reserve(n_pyr + n_lut) || !c->msearch.bits.reserve(n_k * words) || !c->msearch.cells.reserve(n_k * q->max_cells + n_k) ||
+        !c->msearch.nodes.reserve(l.words + CM_MSEARCH_WORDS) || !c->msearch.q.reserve(6 * n_k) ||
+        !c->msearch.host.reserve(std::max(l.h_q + 6 * n_k, static_cast<size_t>(n_roots))))
         return fail(c, CM_HIP_ERROR, "cannot allocate the search layer");
     std::vector<unsigned char> lut(n_lut, 0);
-    cm_match_table_build(c->map_params.cell, q->sigma, q->max_dist, R, lut.data());
-    uint32_t* const roots = c->msearch_host;           // (the page-locked words are free until the first evaluate)
+    cm_match_table_build(c->map.params.cell, q->sigma, q->max_dist, R, lut.data());
+    uint32_t* const roots = c->msearch.host;           // (the page-locked words are free until the first evaluate)
     size_t r = 0;
     for (uint32_t kk = 0; kk < n_k; ++kk)
         for (uint32_t b = 0; b < ry; ++b)
             for (uint32_t a = 0; a < rx; ++a) roots[r++] = (kk << 24) | ((b << q->depth) << 12) | (a << q->depth);
-    HIP_TRY(c, hipMemcpyAsync(c->msearch_pyr + n_pyr, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->msearch_nodes + l.roots, roots, static_cast<size_t>(n_roots) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->msearch.pyr + n_pyr, lut.data(), n_lut, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->msearch.nodes + l.roots, roots, static_cast<size_t>(n_roots) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->msearch_params = *q;
-    c->msearch_radius = R;
-    c->msearch_n_roots = n_roots;
-    c->msearch_on = true;
+    c->msearch.params = *q;
+    c->msearch.radius = R;
+    c->msearch.n_roots = n_roots;
+    c->layers[LAYER_SEARCH].on = true;
     return CM_OK;
 }
 
@@ -1519,32 +1429,32 @@ int map_msearch_configure(cm_ctx* c, const cm_match_search_params* q, uint32_t R
 // one last copy; steps 7 and 8 on the host. No allocation: cm_map_match_search_configure made them all.
 int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     HIP_TRY(c, hipSetDevice(c->device));
-    const cm_match_search_params& q = c->msearch_params;
-    const uint32_t nx = c->map_info.nx, ny = c->map_info.ny, n_roots = c->msearch_n_roots;
+    const cm_match_search_params& q = c->msearch.params;
+    const uint32_t nx = c->map.info.nx, ny = c->map.info.ny, n_roots = c->msearch.n_roots;
     const size_t n_cells = static_cast<size_t>(nx) * ny;
     const MSearchLayout l = msearch_layout(q, n_roots);
     CmMatchDev g{};                                    // (for the exhaustive layer's mark kernel: no shifts)
     g.tx = pose[3];
     g.ty = pose[7];
-    g.inv = 1.0f / c->map_params.cell;
-    g.ax = c->map_info.anchor[0];
-    g.ay = c->map_info.anchor[1];
+    g.inv = 1.0f / c->map.params.cell;
+    g.ax = c->map.info.anchor[0];
+    g.ay = c->map.info.anchor[1];
     g.nx = nx;
     g.ny = ny;
-    g.z_min = c->map_params.z_min;
-    g.z_max = c->map_params.z_max;
+    g.z_min = c->map.params.z_min;
+    g.z_max = c->map.params.z_max;
     g.n_a = q.n_a;
     g.n_k = 2u * q.n_a + 1u;
     g.wx = 0;
     g.wy = 0;
     g.words = static_cast<uint32_t>((n_cells + 31) / 32);
-    g.r2 = c->msearch_radius * c->msearch_radius;
+    g.r2 = c->msearch.radius * c->msearch.radius;
     const CmMSearchDev m{nx, ny, g.n_k, q.n_a, q.wx, q.wy, q.max_cells};
     const float* const dirs = traj_direction_table();
-    uint32_t* const hw = c->msearch_host;              // the info words read back
-    uint32_t* const hcounts = c->msearch_host + l.h_counts;
-    uint32_t* const init = c->msearch_host + l.h_init;
-    float* const up = reinterpret_cast<float*>(c->msearch_host + l.h_q);
+    uint32_t* const hw = c->msearch.host;              // the info words read back
+    uint32_t* const hcounts = c->msearch.host + l.h_counts;
+    uint32_t* const init = c->msearch.host + l.h_init;
+    float* const up = reinterpret_cast<float*>(c->msearch.host + l.h_q);
     for (uint32_t kk = 0; kk < g.n_k; ++kk) {
         const int k = static_cast<int>(kk) - static_cast<int>(q.n_a);
         const uint32_t e = static_cast<uint32_t>(k * static_cast<int>(q.a_stride)) & (CM_TRAJ_HEADINGS - 1u);
@@ -1560,35 +1470,35 @@ int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     init[CM_MSEARCH_W_ONE] = 1u;
     init[CM_MSEARCH_W_FOUR] = 4u;
     init[CM_MSEARCH_W_NROOTS] = n_roots;
-    unsigned char* const pyr = c->msearch_pyr;
+    unsigned char* const pyr = c->msearch.pyr;
     const unsigned char* const lut = pyr + msearch_level_offset(nx, ny, q.depth + 1u);
     const auto level = [&](uint32_t h) { return pyr + msearch_level_offset(nx, ny, h); };
-    uint32_t* const cells = c->msearch_cells;
+    uint32_t* const cells = c->msearch.cells;
     uint32_t* const counts = cells + static_cast<size_t>(g.n_k) * q.max_cells;
-    uint32_t* const nodes = c->msearch_nodes;
+    uint32_t* const nodes = c->msearch.nodes;
     uint32_t* const words = nodes + l.words;
     uint32_t* const U = nodes + l.u;
     hipStream_t st = c->stream;
-    cm_match_search_info& info = c->msearch_info;
+    cm_match_search_info& info = c->msearch.info;
     std::memset(&info, 0, sizeof info);
     info.depth = q.depth;
     info.n_roots = n_roots;
     info.overflow_level = -1;
-    c->msearch_stale = "the search is stale: the last cm_map_match_search failed";
+    layer_mark_failed(c->layers, LAYER_SEARCH);
     c->prof_used = 0;
-    HIP_TRY(c, hipMemcpyAsync(c->msearch_q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->msearch.q, up, 6 * static_cast<size_t>(g.n_k) * sizeof(float), hipMemcpyHostToDevice, st));
     prof_mark(c, "msearch_clear");
     HIP_TRY(c, hipMemcpyAsync(words, init, CM_MSEARCH_WORDS * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemsetAsync(c->msearch_bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
+    HIP_TRY(c, hipMemsetAsync(c->msearch.bits, 0, static_cast<size_t>(g.n_k) * g.words * 4, st));
     HIP_TRY(c, hipMemsetAsync(counts, 0, static_cast<size_t>(g.n_k) * 4, st));
     prof_mark(c, "k_match_field");
-    cmk_match_field(st, c->cost_dist2, lut, g.r2, static_cast<uint32_t>(n_cells), pyr);
+    cmk_match_field(st, c->cost.dist2, lut, g.r2, static_cast<uint32_t>(n_cells), pyr);
     prof_mark(c, "k_msearch_pyramid");
     for (uint32_t h = 1; h <= q.depth; ++h) cmk_msearch_pyramid(st, level(h - 1u), level(h), nx, ny, h);
     prof_mark(c, "k_match_mark");
-    cmk_match_mark(st, c->d_frame, g, c->msearch_q, c->frame_mask, c->msearch_bits, c->frame.n_tiles);
+    cmk_match_mark(st, c->d_frame, g, c->msearch.q, c->frame_mask, c->msearch.bits, c->frame.n_tiles);
     prof_mark(c, "k_msearch_list");
-    cmk_msearch_list(st, c->msearch_bits, m, g.words, cells, counts);
+    cmk_msearch_list(st, c->msearch.bits, m, g.words, cells, counts);
     // A list's nodes times `splits` stripes of cells are the workgroups of a score launch: about 4096, no stripe under 1024
     // cells of room. More than one stripe adds into the scores, which are zero before: the info words' by their upload and by
     // k_msearch_pick, U by a clear.
@@ -1671,7 +1581,7 @@ int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     const uint32_t sx = 2u * q.wx + 1u, sy = 2u * q.wy + 1u;
     const uint32_t bk = node >> 24, bj = (node >> 12) & 4095u, bi = node & 4095u;
     if (bk >= g.n_k || bj >= sy || bi >= sx) return fail(c, CM_INTERNAL, "the best entry lies outside the range");
-    cm_match_result& r = c->msearch_result;
+    cm_match_result& r = c->msearch.result;
     r.best = (bk * sy + bj) * sx + bi;
     r.k = static_cast<int32_t>(bk) - static_cast<int32_t>(q.n_a);
     r.j = static_cast<int32_t>(bj) - static_cast<int32_t>(q.wy);
@@ -1691,7 +1601,7 @@ int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     const uint32_t* const nu = hw + CM_MSEARCH_W_NEIGH_U;
     r.sub[0] = sub(bi > 0u && bi + 1u < sx, nu[0], nu[1]);
     r.sub[1] = sub(bj > 0u && bj + 1u < sy, nu[2], nu[3]);
-    const double cell = static_cast<double>(c->map_params.cell);
+    const double cell = static_cast<double>(c->map.params.cell);
     for (int j = 0; j < 3; ++j) {
         r.pose[j] = up[6 * bk + j];
         r.pose[4 + j] = up[6 * bk + 3 + j];
@@ -1699,8 +1609,7 @@ int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     r.pose[3] = static_cast<float>(pose[3] + static_cast<float>((static_cast<double>(r.i) + r.sub[0]) * cell));
     r.pose[7] = static_cast<float>(pose[7] + static_cast<float>((static_cast<double>(r.j) + r.sub[1]) * cell));
     for (int j = 8; j < 12; ++j) r.pose[j] = pose[j];
-    c->msearch_serial = c->frame_serial;
-    c->msearch_stale = nullptr;
+    layer_mark_fresh(c->layers, LAYER_SEARCH, c->frame_serial);
     return CM_OK;
 }
 

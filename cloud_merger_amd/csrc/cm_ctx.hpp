@@ -27,6 +27,7 @@
 #include "cm_devbuf.hpp"
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_map_layers.hpp"
 #include "cm_route.hpp"
 
 // A cloud as a frame sees it: where its payload lies in HBM and how its points are laid out.
@@ -101,6 +102,140 @@ struct PoseFit {
     uint64_t n_src = 0;
     // Room for n_src records of corr_bytes each (what_state, what_table: the error texts of a failure).
     int reserve(cm_ctx* c, uint64_t n_src, size_t corr_bytes, const char* what_state, const char* what_table);
+};
+
+// Rolling log-odds occupancy map (cm_kernels_map.hip), configured by cm_map_configure and fed by cm_map_integrate after a
+// frame: the one by-product that survives merges (invalidate_result_tables leaves it alone). Buffers of its own — no frame
+// and no other by-product reads them —, all allocated by the configure call, so an integrate call allocates nothing.
+struct MapLayer {
+    cm_map_params params{};
+    DevBuf<void> state[2];           // cm_map_cell per window cell, twice: k_map_update reads one and writes the other
+    int cur = 0;                     // which of the two holds the map
+    DevBuf<void> image;              // the three-valued image: one byte per cell
+    DevBuf<uint32_t> bits;           // 2 * max_sensors bitmaps of ceil(cells / 32) words: the E bitmaps, then the H bitmaps
+    DevBuf<void> rays;               // k_ray_cast's scratch table: (n_pass, n_end) per cell
+    cm_map_info info{};              // anchor, size, integrations since the configure call, who cast in the last one
+    uint64_t serial = 0;             // the frame integrated last (0: none since the configure call)
+};
+
+// Cost layer over the occupancy map (cm_kernels_cost.hip), configured by cm_map_cost_configure behind the map and
+// recomputed by cm_map_cost_update from map.image. Buffers of its own, all allocated by the configure call; it lives and
+// goes with the map (map_configure frees it).
+struct CostLayer {
+    cm_cost_params params{};
+    uint32_t radius = 0;            // R: the table has R * R + 1 entries
+    DevBuf<unsigned char> cells;    // the inflated cost: one byte per cell
+    DevBuf<uint32_t> dist2;         // the squared distance: one word per cell
+    DevBuf<uint32_t> masks;         // the column pass: ceil(ny / CM_COST_ROWS) * nx obstacle words, then as many carry words
+    DevBuf<unsigned char> lut;      // the table in HBM
+    std::vector<unsigned char> lut_host;   // and as it was built
+};
+
+// Plan layer behind the cost layer (cm_kernels_plan.hip), configured by cm_map_plan_configure and recomputed by
+// cm_map_plan_update from cost.cells. Buffers of its own, all allocated by the configure call; it lives and goes with the
+// cost layer (map_cost_configure frees it).
+struct PlanLayer {
+    cm_plan_params params{};
+    cm_plan_info info{};
+    DevBuf<uint32_t> pot;           // the potential: one word per cell
+    DevBuf<uint32_t> words;         // CM_PLAN_BATCH sweep counters, then two tables of tile flags
+    DevBuf<uint32_t> path;          // CM_PLAN_PATH_HEAD words, then max_path_cells cells
+    PinnedBuf<uint32_t> host;       // what the host reads back: the counters of a batch, a path's head
+};
+
+// Rollout layer behind the plan layer (cm_kernels_traj.hip), configured by cm_map_traj_configure and evaluated by
+// cm_map_traj_evaluate from cost.cells and plan_layer.pot. Buffers of its own, all allocated by the configure call; it lives and
+// goes with the plan layer (map_plan_configure frees it).
+struct TrajLayer {
+    cm_traj_params params{};
+    uint32_t n_foot = 0;
+    cm_traj_info info{};
+    DevBuf<CmTrajScoreDev> scores;  // nv * nw records
+    DevBuf<uint32_t> words;         // CM_TRAJ_INFO_WORDS info words, then nv step lengths (fp32) and nw heading increments
+    DevBuf<float> consts;           // the heading table (2 * CM_TRAJ_HEADINGS floats), then the footprint (2 * n_foot)
+    PinnedBuf<uint32_t> host;       // CM_TRAJ_INFO_WORDS words read back, then the nv + nw words an evaluate uploads
+    std::vector<float> v, w;   // the samples of the last evaluate (nv and nw entries from the configure call on)
+};
+
+// Frontier layer behind the plan layer (cm_kernels_front.hip), configured by cm_map_frontier_configure and recomputed by
+// cm_map_frontier_update from map.image, cost.cells and plan_layer.pot. Buffers of its own, all allocated by the configure call;
+// it lives and goes with the plan layer (map_plan_configure frees it).
+struct FrontLayer {
+    cm_frontier_params params{};
+    cm_frontier_info info{};
+    DevBuf<uint32_t> labels;       // a word per cell: parents, then roots, then the frontier numbers
+    DevBuf<uint32_t> words;        // a size word per cell, the counts of the scan (one per CM_FRONT_BLOCK cells), CM_FRONT_INFO_WORDS info words
+    DevBuf<CmFrontEntryDev> table; // max_frontiers entries
+    DevBuf<uint32_t> box;          // four words per entry: the box while it is reduced
+    PinnedBuf<uint32_t> host;      // CM_FRONT_INFO_WORDS words read back
+};
+
+// Scan matching layer behind the cost layer (cm_kernels_match.hip), configured by cm_map_match_configure and evaluated by
+// cm_map_match_evaluate from the frame at rest, map.info and cost.dist2. Buffers of its own, all allocated by the
+// configure call; it lives and goes with the cost layer (map_cost_configure frees it).
+struct MatchLayer {
+    cm_match_params params{};
+    uint32_t radius = 0;           // R: the field table has R * R + 1 entries
+    cm_match_result result{};
+    DevBuf<unsigned char> field;   // nx * ny bytes L, then the field table
+    DevBuf<uint32_t> bits;         // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
+    DevBuf<uint32_t> vol;          // the volume, then CM_MATCH_INFO_WORDS info words
+    DevBuf<float> q;               // six floats per candidate
+    PinnedBuf<uint32_t> host;      // CM_MATCH_INFO_WORDS words read back, then the candidates' floats an evaluate uploads
+    std::vector<unsigned char> lut_host;
+};
+
+// Search layer behind the cost layer (cm_kernels_msearch.hip): branch-and-bound scan matching over wide windows,
+// configured by cm_map_match_search_configure and evaluated by cm_map_match_search from the same inputs as the layer
+// above. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer too.
+struct SearchLayer {
+    cm_match_search_params params{};
+    uint32_t radius = 0;         // R: the field table has R * R + 1 entries
+    uint32_t n_roots = 0;
+    cm_match_result result{};
+    cm_match_search_info info{};
+    DevBuf<unsigned char> pyr;   // levels 0 .. depth (level_offset), then the field table
+    DevBuf<uint32_t> bits;       // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
+    DevBuf<uint32_t> cells;      // 2 * n_a + 1 cell lists of max_cells words, then as many counts
+    DevBuf<uint32_t> nodes;      // the roots, two node lists of max_nodes words, the scores of max_nodes words, CM_MSEARCH_WORDS info words
+    DevBuf<float> q;             // six floats per candidate
+    PinnedBuf<uint32_t> host;    // CM_MSEARCH_WORDS words read back, 256 counts, CM_MSEARCH_WORDS words an evaluate uploads, then the candidates' floats
+};
+
+// Localisation layer behind the cost layer (cm_kernels_mcl.hip): a particle filter against the matching layer's field,
+// configured by cm_map_mcl_configure and driven by cm_map_mcl_init_* / _predict / _update from the frame at rest, map.info,
+// map.image and cost.dist2. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
+struct MclLayer {
+    bool init = false;               // the particles are initialised (an init call since the configure call)
+    uint64_t gen = 0;                // init, predict and update calls since the configure call
+    cm_mcl_params params{};
+    uint32_t radius = 0;             // R: the field table has R * R + 1 entries
+    cm_mcl_info info{};
+    DevBuf<CmMclParticleDev> parts[2];      // n_particles each: the resampling gathers from one into the other
+    int cur = 0;                     // which of the two holds the particles
+    DevBuf<CmMclWeightDev> wts;      // n_particles records
+    DevBuf<unsigned long long> cum;  // n_particles prefix sums, then CM_MCL_WORDS info words
+    DevBuf<unsigned char> field;     // nx * ny bytes L, then the field table
+    DevBuf<uint32_t> bits;           // one bitmap: the body cells ((2 range_cells + 1)^2 bits) or the free cells (nx * ny bits)
+    DevBuf<uint32_t> list;           // CM_MCL_ONE_BLOCK block counts, then max(max_beams, nx * ny) list entries
+    DevBuf<float> dirs;              // the heading table (2 * CM_TRAJ_HEADINGS floats)
+    PinnedBuf<unsigned long long> host;     // CM_MCL_WORDS words read back
+};
+
+// Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses, configured by cm_map_cast_configure
+// and evaluated by cm_map_cast_evaluate / _evaluate_mcl from map.info, map.image, cost.dist2 and, for the latter, mcl.parts.
+// Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
+struct CastLayer {
+    bool steps_fresh = false;       // steps is that of the current dist2
+    cm_cast_params params{};
+    cm_cast_info info{};
+    DevBuf<CmCastRayDev> rays;      // max_poses * n_bearings records
+    DevBuf<uint32_t> poses;         // max_poses poses of three words, as an evaluate uploads them
+    DevBuf<uint32_t> bearings;      // n_bearings binary angles
+    DevBuf<uint32_t> dirs;          // CM_CAST_DIRS pairs of int16_t
+    DevBuf<unsigned char> steps;    // nx * ny bytes: the skip table
+    DevBuf<uint32_t> words;         // CM_CAST_WORDS status counts
+    PinnedBuf<uint32_t> host;       // the counts read back
 };
 
 struct cm_ctx {
@@ -266,142 +401,20 @@ struct cm_ctx {
     uint64_t ray_n = 0;                  // cells of the last ray call
     bool ray_have = false;               // they hold the rays of the result at rest (cleared by a merge and by a grid call)
 
-    // Rolling log-odds occupancy map (cm_kernels_map.hip), configured by cm_map_configure and fed by cm_map_integrate after a
-    // frame: the one by-product that survives merges (invalidate_result_tables leaves it alone). Buffers of its own — no frame
-    // and no other by-product reads them —, all allocated by the configure call, so an integrate call allocates nothing.
-    bool map_on = false;                 // a map is configured
-    cm_map_params map_params{};
-    DevBuf<void> map_state[2];           // cm_map_cell per window cell, twice: k_map_update reads one and writes the other
-    int map_cur = 0;                     // which of the two holds the map
-    DevBuf<void> map_image;              // the three-valued image: one byte per cell
-    DevBuf<uint32_t> map_bits;           // 2 * max_sensors bitmaps of ceil(cells / 32) words: the E bitmaps, then the H bitmaps
-    DevBuf<void> map_rays;               // k_ray_cast's scratch table: (n_pass, n_end) per cell
-    cm_map_info map_info{};              // anchor, size, integrations since the configure call, who cast in the last one
+    // The occupancy map and the layers behind it (cm_map_layers.hpp has the tree): the one family of by-products that survives
+    // merges (invalidate_result_tables leaves it alone). `layers` says which of them are configured and whose result is stale;
+    // each struct holds one layer's parameters, result and buffers, so that giving a layer back is assigning a fresh struct.
     uint64_t frame_serial = 0;           // counts the frames enqueued (enqueue, merge_tables): the frame at rest is this one
-    uint64_t map_serial = 0;             // the frame integrated last (0: none since the configure call)
-
-    // Cost layer over the occupancy map (cm_kernels_cost.hip), configured by cm_map_cost_configure behind the map and
-    // recomputed by cm_map_cost_update from map_image. Buffers of its own, all allocated by the configure call; it lives and
-    // goes with the map (map_configure frees it).
-    bool cost_on = false;                // a cost layer is configured
-    bool cost_fresh = false;             // the two tables are those of the map's current image (cleared by map_integrate)
-    cm_cost_params cost_params{};
-    uint32_t cost_radius = 0;            // R: the table has R * R + 1 entries
-    DevBuf<unsigned char> cost_cells;    // the inflated cost: one byte per cell
-    DevBuf<uint32_t> cost_dist2;         // the squared distance: one word per cell
-    DevBuf<uint32_t> cost_masks;         // the column pass: ceil(ny / CM_COST_ROWS) * nx obstacle words, then as many carry words
-    DevBuf<unsigned char> cost_lut;      // the table in HBM
-    std::vector<unsigned char> cost_lut_host;   // and as it was built
-
-    // Plan layer behind the cost layer (cm_kernels_plan.hip), configured by cm_map_plan_configure and recomputed by
-    // cm_map_plan_update from cost_cells. Buffers of its own, all allocated by the configure call; it lives and goes with the
-    // cost layer (map_cost_configure frees it).
-    bool plan_on = false;                // a plan layer is configured
-    const char* plan_stale = nullptr;    // why pot is not that of the current cost table and a goal; nullptr: it is
-    cm_plan_params plan_params{};
-    cm_plan_info plan_info{};
-    DevBuf<uint32_t> plan_pot;           // the potential: one word per cell
-    DevBuf<uint32_t> plan_words;         // CM_PLAN_BATCH sweep counters, then two tables of tile flags
-    DevBuf<uint32_t> plan_path;          // CM_PLAN_PATH_HEAD words, then max_path_cells cells
-    PinnedBuf<uint32_t> plan_host;       // what the host reads back: the counters of a batch, a path's head
-
-    // Rollout layer behind the plan layer (cm_kernels_traj.hip), configured by cm_map_traj_configure and evaluated by
-    // cm_map_traj_evaluate from cost_cells and plan_pot. Buffers of its own, all allocated by the configure call; it lives and
-    // goes with the plan layer (map_plan_configure frees it).
-    bool traj_on = false;                // a rollout layer is configured
-    const char* traj_stale = nullptr;    // why the scores are not those of the current tables and a window; nullptr: they are
-    cm_traj_params traj_params{};
-    uint32_t traj_n_foot = 0;
-    cm_traj_info traj_info{};
-    DevBuf<CmTrajScoreDev> traj_scores;  // nv * nw records
-    DevBuf<uint32_t> traj_words;         // CM_TRAJ_INFO_WORDS info words, then nv step lengths (fp32) and nw heading increments
-    DevBuf<float> traj_const;            // the heading table (2 * CM_TRAJ_HEADINGS floats), then the footprint (2 * n_foot)
-    PinnedBuf<uint32_t> traj_host;       // CM_TRAJ_INFO_WORDS words read back, then the nv + nw words an evaluate uploads
-    std::vector<float> traj_v, traj_w;   // the samples of the last evaluate (nv and nw entries from the configure call on)
-
-    // Frontier layer behind the plan layer (cm_kernels_front.hip), configured by cm_map_frontier_configure and recomputed by
-    // cm_map_frontier_update from map_image, cost_cells and plan_pot. Buffers of its own, all allocated by the configure call;
-    // it lives and goes with the plan layer (map_plan_configure frees it).
-    bool front_on = false;               // a frontier layer is configured
-    const char* front_stale = nullptr;   // why labels and table are not those of the current tables; nullptr: they are
-    cm_frontier_params front_params{};
-    cm_frontier_info front_info{};
-    DevBuf<uint32_t> front_labels;       // a word per cell: parents, then roots, then the frontier numbers
-    DevBuf<uint32_t> front_words;        // a size word per cell, the counts of the scan (one per CM_FRONT_BLOCK cells), CM_FRONT_INFO_WORDS info words
-    DevBuf<CmFrontEntryDev> front_table; // max_frontiers entries
-    DevBuf<uint32_t> front_box;          // four words per entry: the box while it is reduced
-    PinnedBuf<uint32_t> front_host;      // CM_FRONT_INFO_WORDS words read back
-
-    // Scan matching layer behind the cost layer (cm_kernels_match.hip), configured by cm_map_match_configure and evaluated by
-    // cm_map_match_evaluate from the frame at rest, map_info and cost_dist2. Buffers of its own, all allocated by the
-    // configure call; it lives and goes with the cost layer (map_cost_configure frees it).
-    bool match_on = false;               // a matching layer is configured
-    const char* match_stale = nullptr;   // why volume and result are not those of the current tables and a prior; nullptr: they are
-    uint64_t match_serial = 0;           // the frame matched last: a merge since then makes them stale too
-    cm_match_params match_params{};
-    uint32_t match_radius = 0;           // R: the field table has R * R + 1 entries
-    cm_match_result match_result{};
-    DevBuf<unsigned char> match_field;   // nx * ny bytes L, then the field table
-    DevBuf<uint32_t> match_bits;         // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
-    DevBuf<uint32_t> match_vol;          // the volume, then CM_MATCH_INFO_WORDS info words
-    DevBuf<float> match_q;               // six floats per candidate
-    PinnedBuf<uint32_t> match_host;      // CM_MATCH_INFO_WORDS words read back, then the candidates' floats an evaluate uploads
-    std::vector<unsigned char> match_lut_host;
-
-    // Search layer behind the cost layer (cm_kernels_msearch.hip): branch-and-bound scan matching over wide windows,
-    // configured by cm_map_match_search_configure and evaluated by cm_map_match_search from the same inputs as the layer
-    // above. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer too.
-    bool msearch_on = false;
-    const char* msearch_stale = nullptr; // why result, info and pyramid are not those of the current tables and a prior; nullptr: they are
-    uint64_t msearch_serial = 0;         // the frame matched last
-    cm_match_search_params msearch_params{};
-    uint32_t msearch_radius = 0;         // R: the field table has R * R + 1 entries
-    uint32_t msearch_n_roots = 0;
-    cm_match_result msearch_result{};
-    cm_match_search_info msearch_info{};
-    DevBuf<unsigned char> msearch_pyr;   // levels 0 .. depth (msearch_level_offset), then the field table
-    DevBuf<uint32_t> msearch_bits;       // 2 * n_a + 1 bitmaps of (nx * ny + 31) / 32 words
-    DevBuf<uint32_t> msearch_cells;      // 2 * n_a + 1 cell lists of max_cells words, then as many counts
-    DevBuf<uint32_t> msearch_nodes;      // the roots, two node lists of max_nodes words, the scores of max_nodes words, CM_MSEARCH_WORDS info words
-    DevBuf<float> msearch_q;             // six floats per candidate
-    PinnedBuf<uint32_t> msearch_host;    // CM_MSEARCH_WORDS words read back, 256 counts, CM_MSEARCH_WORDS words an evaluate uploads, then the candidates' floats
-
-    // Localisation layer behind the cost layer (cm_kernels_mcl.hip): a particle filter against the matching layer's field,
-    // configured by cm_map_mcl_configure and driven by cm_map_mcl_init_* / _predict / _update from the frame at rest, map_info,
-    // map_image and cost_dist2. Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
-    bool mcl_on = false;
-    bool mcl_init = false;               // the particles are initialised (an init call since the configure call)
-    const char* mcl_stale = nullptr;     // why weights and info are not those of the current tables and particles; nullptr: they are
-    uint64_t mcl_serial = 0;             // the frame of the last update: a merge since then makes them stale too
-    uint64_t mcl_gen = 0;                // init, predict and update calls since the configure call
-    cm_mcl_params mcl_params{};
-    uint32_t mcl_radius = 0;             // R: the field table has R * R + 1 entries
-    cm_mcl_info mcl_info{};
-    DevBuf<CmMclParticleDev> mcl_parts[2];      // n_particles each: the resampling gathers from one into the other
-    int mcl_cur = 0;                     // which of the two holds the particles
-    DevBuf<CmMclWeightDev> mcl_wts;      // n_particles records
-    DevBuf<unsigned long long> mcl_cum;  // n_particles prefix sums, then CM_MCL_WORDS info words
-    DevBuf<unsigned char> mcl_field;     // nx * ny bytes L, then the field table
-    DevBuf<uint32_t> mcl_bits;           // one bitmap: the body cells ((2 range_cells + 1)^2 bits) or the free cells (nx * ny bits)
-    DevBuf<uint32_t> mcl_list;           // CM_MCL_ONE_BLOCK block counts, then max(max_beams, nx * ny) list entries
-    DevBuf<float> mcl_dirs;              // the heading table (2 * CM_TRAJ_HEADINGS floats)
-    PinnedBuf<unsigned long long> mcl_host;     // CM_MCL_WORDS words read back
-
-    // Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses, configured by cm_map_cast_configure
-    // and evaluated by cm_map_cast_evaluate / _evaluate_mcl from map_info, map_image, cost_dist2 and, for the latter, mcl_parts.
-    // Buffers of its own, all allocated by the configure call; it lives and goes with the cost layer.
-    bool cast_on = false;
-    const char* cast_stale = nullptr;    // why rays and info are not those of the current tables; nullptr: they are
-    bool cast_steps_fresh = false;       // cast_steps is that of the current dist2
-    cm_cast_params cast_params{};
-    cm_cast_info cast_info{};
-    DevBuf<CmCastRayDev> cast_rays;      // max_poses * n_bearings records
-    DevBuf<uint32_t> cast_poses;         // max_poses poses of three words, as an evaluate uploads them
-    DevBuf<uint32_t> cast_bearings;      // n_bearings binary angles
-    DevBuf<uint32_t> cast_dirs;          // CM_CAST_DIRS pairs of int16_t
-    DevBuf<unsigned char> cast_steps;    // nx * ny bytes: the skip table
-    DevBuf<uint32_t> cast_words;         // CM_CAST_WORDS status counts
-    PinnedBuf<uint32_t> cast_host;       // the counts read back
+    MapLayers layers;
+    MapLayer map;
+    CostLayer cost;
+    PlanLayer plan_layer;                // (`plan` is the frame's)
+    TrajLayer traj;
+    FrontLayer front;
+    MatchLayer match;
+    SearchLayer msearch;
+    MclLayer mcl;
+    CastLayer cast;
 
     // Normals and curvature of the result (cm_kernels_normals.hip), on request after a frame: buffers of its own, as the
     // cluster extraction's — no frame reads them — allocated by the first request and grown with the results. It reads `out`.
@@ -508,6 +521,12 @@ void box_direction_table(uint32_t n_angles, float* cos_sin);
 int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages = false);
 // The grid map at q and behind it the rays of the last frame at r (ray_cells and ray_image, ray_n = q.nx * q.ny cells).
 int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r);
+// The occupancy map and its layers (cm_map_layers.hpp has the tree, the refusals and the staleness rule; each layer's state is
+// one struct above). Every *_configure below works alike: the layers below the one at hand are given back (their structs
+// assigned afresh, which frees their buffers), then nullptr gives back the layer itself, and anything else reserves its
+// buffers — which allocates nothing where they fit —, uploads its tables and leaves the layer on and stale since this call.
+// Every producer marks its layer failed before it launches and fresh once its result is read back, and marks the layers
+// below stale where it changes what they read.
 // The occupancy map. map_configure: room for q's window, cleared (nullptr: the buffers go). map_vehicle_cell: the absolute
 // cell of the pose's translation at the configured cell size, false where it does not exist. map_integrate: the last frame
 // under `pose` into the map, whose window is then anchored around the vehicle cell v.
@@ -522,25 +541,25 @@ int map_cost_configure(cm_ctx* c, const cm_cost_params* q, uint32_t R);
 int map_cost_update(cm_ctx* c);
 // The plan layer behind the cost layer. map_plan_configure: room for the map's window and q's longest path (nullptr: the
 // buffers go). map_plan_update: pot for the goal's window cell. map_plan_path: the walk from the start's window cell into
-// plan_path; head receives its CM_PLAN_PATH_HEAD words.
+// plan_layer.path; head receives its CM_PLAN_PATH_HEAD words.
 int map_plan_configure(cm_ctx* c, const cm_plan_params* q);
 int map_plan_update(cm_ctx* c, const uint32_t goal[2]);
 int map_plan_path(cm_ctx* c, const uint32_t start[2], uint32_t head[4]);
 // The rollout layer behind the plan layer. traj_direction_table: the 2 * CM_TRAJ_HEADINGS floats of step 2 (built once).
 // traj_samples: the n samples of step 1 between lo and hi. map_traj_configure: room for q's samples and the footprint, which
-// is uploaded with the heading table (nullptr: the buffers go). map_traj_evaluate: the scores and traj_info for a window that
+// is uploaded with the heading table (nullptr: the buffers go). map_traj_evaluate: the scores and traj.info for a window that
 // cm_map_traj_evaluate has checked, from the start's window cell.
 const float* traj_direction_table();
 void traj_samples(float lo, float hi, uint32_t n, float* out);
 int map_traj_configure(cm_ctx* c, const cm_traj_params* q, const float* foot_xy, uint32_t n_foot);
 int map_traj_evaluate(cm_ctx* c, const cm_traj_window& w, const uint32_t start[2]);
 // The frontier layer behind the plan layer. map_frontier_configure: room for the map's window and q's table (nullptr: the
-// buffers go). map_frontier_update: labels, table and front_info of the current image, cost table and pot.
+// buffers go). map_frontier_update: labels, table and front.info of the current image, cost table and pot.
 int map_frontier_configure(cm_ctx* c, const cm_frontier_params* q);
 int map_frontier_update(cm_ctx* c);
 // The scan matching layer behind the cost layer. map_match_configure: room for q's candidates over the map's window and the
 // field table at radius R cells, which is built and uploaded (nullptr: the buffers go). map_match_evaluate: the volume and
-// match_result for a prior that cm_map_match_evaluate has checked.
+// match.result for a prior that cm_map_match_evaluate has checked.
 int map_match_configure(cm_ctx* c, const cm_match_params* q, uint32_t R);
 int map_match_evaluate(cm_ctx* c, const float pose[12]);
 // The localisation layer behind the cost layer. map_mcl_configure: room for q's particles and beams over the map's window and
@@ -562,9 +581,9 @@ int map_cast_evaluate(cm_ctx* c, const cm_cast_pose* host_poses, uint32_t n);
 // A recorded state table into the configured map (cm_map_load has checked it): state, image, anchor, staleness.
 int map_load(cm_ctx* c, const cm_map_cell* src, const int32_t anchor[2]);
 // The search layer behind the cost layer. map_msearch_configure: room for q over the map's window, the field table at radius
-// R cells built and uploaded, the roots built and uploaded (nullptr: the buffers go). map_msearch_evaluate: msearch_result and
-// msearch_info for a prior that cm_map_match_search has checked; CM_CAPACITY leaves the result stale and the info written.
-// msearch_level_offset: where level h starts in msearch_pyr.
+// R cells built and uploaded, the roots built and uploaded (nullptr: the buffers go). map_msearch_evaluate: msearch.result and
+// msearch.info for a prior that cm_map_match_search has checked; CM_CAPACITY leaves the result stale and the info written.
+// msearch_level_offset: where level h starts in msearch.pyr.
 int map_msearch_configure(cm_ctx* c, const cm_match_search_params* q, uint32_t R);
 int map_msearch_evaluate(cm_ctx* c, const float pose[12]);
 size_t msearch_level_offset(uint32_t nx, uint32_t ny, uint32_t h);

@@ -158,8 +158,61 @@ def case_growing_replaces_shrinking_keeps():
         assert total_two > total_one, "the two-tile result made the tables grow"
 
 
+# What each layer of the occupancy map allocates at tests/test_map_layer_texts.py's configuration (every DevBuf and PinnedBuf of
+# its struct in cm_ctx.hpp), recorded from the commit before the layer table (428edbf) with this case copied into its tree.
+LAYER_BUFFERS = dict(map=5, cost=4, plan=4, traj=4, front=5, match=5, search=6, mcl=9, cast=7)
+
+
+def case_map_layers_give_back_their_subtrees():
+    from tests import test_map_layer_texts as lt
+    with capi.CloudMerger(max_points_total=4096, max_sensors=1) as cm:
+        w = lt.Walk(cm)
+        w.frame()
+        base = allocations()[0]
+        took = {}
+        for layer in lt.LAYERS:
+            before = allocations()[0]
+            w.configure[layer]()
+            took[layer] = allocations()[0] - before
+        assert took == LAYER_BUFFERS
+        live_all, total = allocations()
+        # a producer call on every layer allocates nothing: the configure calls made every buffer
+        cm.map_integrate()
+        cm.map_cost_update()
+        cm.map_plan_update(*lt.HERE)
+        cm.map_path(*lt.HERE)
+        cm.map_traj_evaluate(lt.HERE[0], lt.HERE[1], 0.0)
+        cm.map_frontier_update()
+        cm.map_match(lt.POSE)
+        cm.map_match_search(lt.POSE)
+        cm.map_mcl_init_pose(lt.HERE[0], lt.HERE[1], 0.0)
+        cm.map_mcl_predict(0.0, 0.0, 0.0)
+        cm.map_mcl_update()
+        cm.map_mcl_init_uniform()
+        cm.map_mcl_update()
+        cm.map_cast([(lt.HERE[0], lt.HERE[1], 0.0)])
+        assert allocations() == (live_all, total), "a producer call allocated"
+        # a leaf layer configured again with the same parameters keeps its buffers
+        for layer in ("traj", "front", "match", "search", "mcl", "cast"):
+            w.configure[layer]()
+            assert allocations() == (live_all, total), layer
+        # a layer given back takes its subtree along, and nothing else
+        cm.map_plan_configure(None)
+        assert allocations()[0] == live_all - sum(took[k] for k in ("plan", "traj", "front"))
+        cm.map_cost_configure(None)
+        assert allocations()[0] == base + took["map"]
+        cm.map_configure(None)
+        assert allocations() == (base, total), "giving back allocates nothing and leaves nothing"
+        # ... and from the full tree in one call
+        for layer in lt.LAYERS:
+            w.configure[layer]()
+        assert allocations()[0] == live_all
+        cm.map_configure(None)
+        assert allocations()[0] == base
+
+
 CASES = {f.__name__[len("case_"):]: f for f in (case_destroy_returns_everything, case_steady_state_allocates_nothing,
-                                                case_growing_replaces_shrinking_keeps)}
+                                                case_growing_replaces_shrinking_keeps, case_map_layers_give_back_their_subtrees)}
 
 
 @pytest.mark.gpu
