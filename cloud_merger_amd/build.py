@@ -20,7 +20,7 @@ HOOKS_LIB_PATH = os.path.join(LIB_DIR, "libcloudmerge_hip_testhooks.so")
 SOURCES = ["cm_kernels.hip", "cm_kernels_v2.hip", "cm_kernels_v3.hip", "cm_kernels_v4.hip", "cm_kernels_ground.hip", "cm_kernels_motion.hip", "cm_kernels_cov.hip", "cm_kernels_sor.hip", "cm_kernels_cluster.hip", "cm_kernels_box.hip", "cm_kernels_grid.hip", "cm_kernels_rays.hip", "cm_kernels_map.hip", "cm_kernels_cost.hip", "cm_kernels_plan.hip", "cm_kernels_traj.hip", "cm_kernels_front.hip", "cm_kernels_match.hip", "cm_kernels_msearch.hip", "cm_kernels_mcl.hip", "cm_kernels_cast.hip",
            "cm_kernels_normals.hip", "cm_kernels_align.hip", "cm_kernels_ndt.hip",
            "cm_api.cpp", "cm_launch.cpp", "cm_byproducts.cpp", "cm_route.cpp"]
-HEADERS = ["cm_device.h", "cm_kernels.h", "cm_common.hpp", "cm_search.hpp", "cm_ctx.hpp", "cm_devbuf.hpp", "cm_route.hpp", "cm_sor_sum.hpp", "cm_align_solve.hpp", "cm_ndt_math.hpp", "cm_cost_table.hpp", "cm_match_table.hpp", "cm_mcl_math.hpp", "cm_cast_math.hpp", "cm_front_score.hpp", "cm_map_layers.hpp", "cloudmerge.map", os.path.join("..", "..", "include", "cloudmerge.h")]
+HEADERS = ["cm_device.h", "cm_kernels.h", "cm_common.hpp", "cm_search.hpp", "cm_ctx.hpp", "cm_devbuf.hpp", "cm_route.hpp", "cm_sor_sum.hpp", "cm_align_solve.hpp", "cm_ndt_math.hpp", "cm_cost_table.hpp", "cm_match_table.hpp", "cm_mcl_math.hpp", "cm_mcl_beam_table.hpp", "cm_cast_math.hpp", "cm_front_score.hpp", "cm_map_layers.hpp", "cloudmerge.map", os.path.join("..", "..", "include", "cloudmerge.h")]
 
 # -ffp-contract=off / -fno-fast-math: occupancy must match the reference bit for bit, so no FMA
 # contraction on the device or in the host-side quaternion/grid arithmetic (SURVEY.md §7 hard part 1).

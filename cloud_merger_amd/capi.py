@@ -55,7 +55,7 @@ SYMBOLS = [
     "cm_map_match_configure", "cm_map_match_evaluate", "cm_map_match_copy", "cm_map_match_device", "cm_map_match_table_copy", "cm_match_table",
     "cm_map_match_search_configure", "cm_map_match_search", "cm_map_match_search_result", "cm_map_match_search_level_copy",
     "cm_map_mcl_configure", "cm_map_mcl_init_pose", "cm_map_mcl_init_uniform", "cm_map_mcl_predict", "cm_map_mcl_update", "cm_map_mcl_copy",
-    "cm_map_mcl_weights_copy", "cm_map_mcl_device", "cm_mcl_draws",
+    "cm_map_mcl_weights_copy", "cm_map_mcl_device", "cm_mcl_draws", "cm_map_mcl_beam_configure", "cm_map_mcl_beam_info_copy", "cm_mcl_beam_table",
     "cm_map_cast_configure", "cm_map_cast_evaluate", "cm_map_cast_evaluate_mcl", "cm_map_cast_copy", "cm_map_cast_device", "cm_cast_directions",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
@@ -460,6 +460,28 @@ MCL_WEIGHT_DTYPE = np.dtype([("score", "<u4"), ("weight", "<u4")])
 assert C.sizeof(MclParams) == 40 and MclParams.seed.offset == 32 and C.sizeof(MclInfo) == 176 and MclInfo.sum_w.offset == 48
 assert MclInfo.n_eff.offset == 120 and MCL_PARTICLE_DTYPE.itemsize == 24 and MCL_WEIGHT_DTYPE.itemsize == 8
 
+# the beam model of the localisation layer: rays cast per beam (cm_map_mcl_beam_configure)
+MCL_BEAM_MAX_OVER = 64
+MCL_BEAM_MAX_D = 1450
+MCL_BEAM_PLAIN = 1
+
+
+class MclBeamParams(C.Structure):
+    """cm_mcl_beam_params (24 bytes): how many cells past its measured end a ray is followed, the hit term's sigma (metres), the
+    weights of the hit, short and random terms (their sum at most 1), MCL_BEAM_PLAIN or 0."""
+    _fields_ = [("over_cells", C.c_uint32), ("sigma", C.c_float), ("z_hit", C.c_float), ("z_short", C.c_float), ("z_rand", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class MclBeamInfo(C.Structure):
+    """cm_mcl_beam_info (56 bytes): the rays of the update (n_particles * n_beams) and how they ended: an occupied cell before,
+    at or after the measured end, none within reach, off the window, or not cast at all."""
+    _fields_ = [("n_rays", C.c_uint64), ("n_early", C.c_uint64), ("n_at", C.c_uint64), ("n_late", C.c_uint64), ("n_beyond", C.c_uint64),
+                ("n_off", C.c_uint64), ("n_skipped", C.c_uint64)]
+
+
+assert C.sizeof(MclBeamParams) == 24 and MclBeamParams.flags.offset == 20 and C.sizeof(MclBeamInfo) == 56
+
 # the cast layer: expected ranges from many poses in the map, behind the cost layer (cm_map_cast_configure, cm_map_cast_evaluate)
 CAST_MAX_POSES = 65536
 CAST_MAX_BEARINGS = 4096
@@ -713,6 +735,9 @@ def load():
     L.cm_map_mcl_weights_copy.argtypes = [vp, vp, u64, C.POINTER(MclInfo)]
     L.cm_map_mcl_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(MclInfo)]
     L.cm_mcl_draws.argtypes = [u64, u64, u32, u32, u32, vp]
+    L.cm_map_mcl_beam_configure.argtypes = [vp, C.POINTER(MclBeamParams)]
+    L.cm_map_mcl_beam_info_copy.argtypes = [vp, C.POINTER(MclBeamInfo)]
+    L.cm_mcl_beam_table.argtypes = [C.POINTER(MclBeamParams), C.c_float, vp, u64]
     L.cm_map_cast_configure.argtypes = [vp, C.POINTER(CastParams), vp]
     L.cm_map_cast_evaluate.argtypes = [vp, vp, u32, C.POINTER(CastInfo)]
     L.cm_map_cast_evaluate_mcl.argtypes = [vp, C.POINTER(CastInfo)]
@@ -782,6 +807,17 @@ def mcl_draws(seed, gen, first_p, n_p, i):
     st = load().cm_mcl_draws(int(seed) & (2**64 - 1), int(gen) & (2**64 - 1), int(first_p), int(n_p), int(i), out.ctypes.data if n_p else None)
     if st != OK and n_p:
         raise CloudMergeError(st, "cm_mcl_draws")
+    return out
+
+
+def mcl_beam_table(cell, over_cells=8, sigma=0.1, z_hit=0.75, z_short=0.125, z_rand=0.125, plain=False):
+    """(2 * over_cells + 3,) uint8: the beam model's table over a map of this cell (cm_mcl_beam_table): a hit at -over_cells ..
+    over_cells steps from the measured end, then no hit within reach, then off the window."""
+    p = MclBeamParams(int(over_cells), float(sigma), float(z_hit), float(z_short), float(z_rand), MCL_BEAM_PLAIN if plain else 0)
+    out = np.empty(2 * int(over_cells) + 3, dtype=np.uint8)
+    st = load().cm_mcl_beam_table(C.byref(p), float(cell), out.ctypes.data, out.shape[0])
+    if st != OK:
+        raise CloudMergeError(st, "cm_mcl_beam_table")
     return out
 
 
@@ -1538,6 +1574,23 @@ class CloudMerger:
         parts, wts, info = C.c_void_p(), C.c_void_p(), MclInfo()
         self._check(self._lib.cm_map_mcl_device(self._ctx, C.byref(parts), C.byref(wts), C.byref(info)), "cm_map_mcl_device")
         return parts.value, wts.value, info
+
+    def map_mcl_beam_configure(self, over_cells=8, sigma=0.1, z_hit=0.75, z_short=0.125, z_rand=0.125, plain=False):
+        """Switches the localisation layer's beam model on: an update then casts a ray from every particle towards every beam's
+        end cell and over_cells past it and scores where the first occupied cell lies (a Gaussian of sigma metres about the
+        end weighted z_hit, z_short for what lies behind the end, z_rand everywhere). plain walks cell by cell instead of
+        jumping. over_cells None goes back to the field score."""
+        if over_cells is None:
+            self._check(self._lib.cm_map_mcl_beam_configure(self._ctx, None), "cm_map_mcl_beam_configure")
+            return
+        p = MclBeamParams(int(over_cells), float(sigma), float(z_hit), float(z_short), float(z_rand), MCL_BEAM_PLAIN if plain else 0)
+        self._check(self._lib.cm_map_mcl_beam_configure(self._ctx, C.byref(p)), "cm_map_mcl_beam_configure")
+
+    def map_mcl_beam_info(self):
+        """The MclBeamInfo of the last update, which ran the beam model."""
+        info = MclBeamInfo()
+        self._check(self._lib.cm_map_mcl_beam_info_copy(self._ctx, C.byref(info)), "cm_map_mcl_beam_info_copy")
+        return info
 
     # ---- the cast layer: expected ranges from many poses in the map, behind the cost layer (cm_map_cast_configure / cm_map_cast_evaluate) ----
     def map_cast_configure(self, max_poses=None, n_bearings=360, range_cells=256, plain=False, bearings=None):

@@ -11,6 +11,8 @@
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 #include "cm_match_table.hpp"
+#include "cm_cast_math.hpp"
+#include "cm_mcl_beam_table.hpp"
 #include "cm_mcl_math.hpp"
 
 namespace {
@@ -372,6 +374,12 @@ int cm_create(cm_ctx** out, int device, const cm_limits* lim) {
     if (const char* bs = getenv("CM_BOX_SPLIT")) {
         const unsigned long v = std::strtoul(bs, nullptr, 10);
         if (v >= 1 && v < 0xFFFFFFFFul) c->box_split = static_cast<uint32_t>(v);
+    }
+    // CM_MCL_BEAM_WALKS=<1|2|4>: how many rays a lane of k_mcl_beam keeps in flight (a measurement's switch; the tables are
+    // the same bytes at every value)
+    if (const char* bw = getenv("CM_MCL_BEAM_WALKS")) {
+        const unsigned long v = std::strtoul(bw, nullptr, 10);
+        if (v == 1 || v == 2 || v == 4) c->mcl_beam_walks = static_cast<uint32_t>(v);
     }
     if (!ok) {
         delete c;
@@ -1478,6 +1486,36 @@ int cm_map_mcl_device(cm_ctx* c, const void** particles, const void** weights, c
     if (info) *info = c->mcl.info;
     if (particles) *particles = c->mcl.parts[c->mcl.cur];
     if (weights) *weights = c->mcl.wts;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_mcl_beam_params) == 24 && offsetof(cm_mcl_beam_params, flags) == 20 && sizeof(cm_mcl_beam_info) == 56 &&
+                  offsetof(cm_mcl_beam_info, n_skipped) == 48 && CM_MCL_BEAM_MAX_OVER == CM_MCL_BEAM_MAX_OVER_DEV && CM_MCL_BEAM_MAX_OVER == CM_CAST_MAX_OVER && CM_MCL_BEAM_MAX_D == CM_CAST_MAX_D,
+              "the beam model's two structs; the kernel's constant");
+
+int cm_mcl_beam_table(const cm_mcl_beam_params* p, float cell, uint8_t* dst, uint64_t capacity) {
+    if (!p || !dst || cm_mcl_beam_refusal(*p, cell)) return CM_BAD_ARG;
+    if (capacity < 2ull * p->over_cells + 3u) return CM_CAPACITY;
+    cm_mcl_beam_table_build(*p, cell, dst);
+    return CM_OK;
+}
+
+int cm_map_mcl_beam_configure(cm_ctx* c, const cm_mcl_beam_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = layer_check(c, LAYER_MCL, false)) return e;
+    if (p)
+        if (const char* why = cm_mcl_beam_refusal(*p, c->map.params.cell)) return fail(c, CM_BAD_ARG, why);
+    return map_mcl_beam_configure(c, p);
+}
+
+int cm_map_mcl_beam_info_copy(cm_ctx* c, cm_mcl_beam_info* out) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, true)) return e;
+    if (!c->mcl.beam_info_have) return fail(c, CM_BAD_ARG, "the last cm_map_mcl_update ran without the beam model (cm_map_mcl_beam_configure first)");
+    if (!out) return fail(c, CM_BAD_ARG, "no destination");
+    *out = c->mcl.beam_info;
     return CM_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "cm_cost_table.hpp"
 #include "cm_ctx.hpp"
 #include "cm_match_table.hpp"
+#include "cm_mcl_beam_table.hpp"
 #include "cm_mcl_math.hpp"
 #include "cm_search.hpp"
 
@@ -633,6 +634,7 @@ int map_cost_update(cm_ctx* c) {
     layer_mark_fresh(c->layers, LAYER_COST, c->frame_serial);
     layers_mark_below(c->layers, LAYER_COST, "the last cm_map_cost_update");
     c->cast.steps_fresh = false;                       // (the next evaluate rebuilds its skip table from the new dist2)
+    c->mcl.beam_steps_fresh = false;                   // (and so does the next update under the beam model)
     return CM_OK;
 }
 
@@ -1044,6 +1046,42 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     return CM_OK;
 }
 
+// The beam model given back: its four buffers and its state; the field score is the layer's again.
+static void mcl_beam_drop(cm_ctx* c) {
+    MclLayer& m = c->mcl;
+    m.beam_on = m.beam_steps_fresh = m.beam_info_have = false;
+    m.beam_params = cm_mcl_beam_params{};
+    m.beam_info = cm_mcl_beam_info{};
+    m.beam_steps.release();
+    m.beam_table.release();
+    m.beam_counts.release();
+    m.beam_host.release();
+}
+
+// The beam model's memory, all of it: one byte per window cell for the skips, the table (built here, cm_mcl_beam_table_build,
+// and uploaded), the count words and their page-locked copy. nullptr gives it back. The particles and gen stay; the weight
+// table and both infos are stale until the next update.
+int map_mcl_beam_configure(cm_ctx* c, const cm_mcl_beam_params* q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    mcl_beam_drop(c);
+    layer_mark_stale(c->layers, LAYER_MCL, "cm_map_mcl_beam_configure");
+    if (!q) return CM_OK;
+    MclLayer& m = c->mcl;
+    const size_t n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny, n_tab = 2 * static_cast<size_t>(q->over_cells) + 3;
+    if (!m.beam_steps.reserve((n_cells + 3) / 4 * 4) || !m.beam_table.reserve(n_tab) || !m.beam_counts.reserve(CM_MCL_BEAM_COUNTS) ||
+        !m.beam_host.reserve(CM_MCL_BEAM_COUNTS)) {
+        mcl_beam_drop(c);
+        return fail(c, CM_HIP_ERROR, "cannot allocate the beam model");
+    }
+    std::vector<unsigned char> tab(n_tab, 0);
+    cm_mcl_beam_table_build(*q, c->map.params.cell, tab.data());
+    HIP_TRY(c, hipMemcpyAsync(m.beam_table, tab.data(), n_tab, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    m.beam_params = *q;
+    m.beam_on = true;
+    return CM_OK;
+}
+
 // The localisation layer's memory, all of it: two particle buffers, the weight table, the prefix sums with the info words
 // behind them, the field with its table behind it (built here, cm_match_table.hpp, and uploaded), the one bitmap and the one
 // list (behind the block counts) that serve the body cells and the free cells, the heading table and the page-locked words an
@@ -1055,6 +1093,7 @@ int map_mcl_configure(cm_ctx* c, const cm_mcl_params* q, uint32_t R) {
         return CM_OK;
     }
     layer_reset(c->layers, LAYER_MCL);
+    mcl_beam_drop(c);
     c->mcl.init = false;
     c->mcl.gen = 0;
     c->mcl.cur = 0;
@@ -1200,8 +1239,25 @@ int map_mcl_update(cm_ctx* c) {
     cmk_mcl_mark(st, c->d_frame, g, c->frame_mask, c->mcl.bits, c->frame.n_tiles);
     prof_mark(c, "k_mcl_compact");
     cmk_mcl_compact(st, c->mcl.bits, body_words, q.max_beams, counts, list, words);
-    prof_mark(c, "k_mcl_score");
-    cmk_mcl_score(st, c->mcl.field, g, list, words, c->mcl.dirs, src, c->mcl.wts);
+    const bool beam = c->mcl.beam_on;
+    CmMclBeamDev bm;
+    bm.over = c->mcl.beam_params.over_cells;
+    bm.plain = (c->mcl.beam_params.flags & CM_MCL_BEAM_PLAIN) ? 1u : 0u;
+    bm.walks = c->mcl_beam_walks;
+    c->mcl.beam_info_have = false;
+    if (beam) {                                        // step 7 under the beam model: rays cast per beam
+        HIP_TRY(c, hipMemsetAsync(c->mcl.beam_counts, 0, CM_MCL_BEAM_COUNTS * sizeof(unsigned long long), st));
+        if (!bm.plain && !c->mcl.beam_steps_fresh) {
+            prof_mark(c, "k_mcl_steps");
+            cmk_cast_steps(st, c->cost.dist2, static_cast<uint32_t>(n_cells), c->mcl.beam_steps);
+        }
+        prof_mark(c, "k_mcl_beam");
+        cmk_mcl_beam(st, c->map.image, c->mcl.beam_steps, c->mcl.beam_table, g, bm, list, words, c->mcl.dirs, src, c->mcl.wts, c->mcl.beam_counts);
+        HIP_TRY(c, hipMemcpyAsync(c->mcl.beam_host, c->mcl.beam_counts, CM_MCL_BEAM_COUNTS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    } else {
+        prof_mark(c, "k_mcl_score");
+        cmk_mcl_score(st, c->mcl.field, g, list, words, c->mcl.dirs, src, c->mcl.wts);
+    }
     prof_mark(c, "k_mcl_best");
     cmk_mcl_best(st, src, g.n, words);
     prof_mark(c, "k_mcl_weights");
@@ -1214,6 +1270,19 @@ int map_mcl_update(cm_ctx* c) {
     if (const int e = finish_call(c, c->mcl.host, words, CM_MCL_WORDS * sizeof(unsigned long long))) return e;
     const unsigned long long* const h = c->mcl.host;
     if (h[CM_MCL_W_BEST] >= g.n || h[CM_MCL_W_SW] < CM_MCL_WEIGHT_ONE || h[CM_MCL_W_SW2] == 0) return fail(c, CM_INTERNAL, "the info words of the update are not a result");
+    if (beam) {
+        const unsigned long long* const b = c->mcl.beam_host;
+        cm_mcl_beam_info& bi = c->mcl.beam_info;
+        bi.n_rays = static_cast<uint64_t>(g.n) * std::min<uint64_t>(h[CM_MCL_W_NBEAMS], g.max_beams);
+        bi.n_early = b[0];
+        bi.n_at = b[1];
+        bi.n_late = b[2];
+        bi.n_beyond = b[3];
+        bi.n_off = b[4];
+        bi.n_skipped = b[5];
+        if (b[0] + b[1] + b[2] + b[3] + b[4] + b[5] != bi.n_rays) return fail(c, CM_INTERNAL, "the outcome counts of the beam model do not add up to its rays");
+        if (!bm.plain) c->mcl.beam_steps_fresh = true;
+    }
     if (h[CM_MCL_W_RESAMPLED]) c->mcl.cur ^= 1;
     cm_mcl_info& r = c->mcl.info;
     std::memset(&r, 0, sizeof r);
@@ -1246,6 +1315,7 @@ int map_mcl_update(cm_ctx* c) {
     r.var_xx = static_cast<double>(r.sum_wdxx) / den;
     r.var_yy = static_cast<double>(r.sum_wdyy) / den;
     r.var_xy = static_cast<double>(r.sum_wdxy) / den;
+    c->mcl.beam_info_have = beam;
     layer_mark_fresh(c->layers, LAYER_MCL, c->frame_serial);
     return CM_OK;
 }

@@ -220,6 +220,17 @@ struct MclLayer {
     DevBuf<uint32_t> list;           // CM_MCL_ONE_BLOCK block counts, then max(max_beams, nx * ny) list entries
     DevBuf<float> dirs;              // the heading table (2 * CM_TRAJ_HEADINGS floats)
     PinnedBuf<unsigned long long> host;     // CM_MCL_WORDS words read back
+    // The beam model (cm_map_mcl_beam_configure, k_mcl_beam): a second scoring mode, off by default. All of it allocated by
+    // that call; cm_map_mcl_configure and whatever frees the layer assign the struct afresh, which frees the mode with it.
+    bool beam_on = false;
+    bool beam_steps_fresh = false;   // beam_steps is that of the current dist2
+    bool beam_info_have = false;     // the last update ran the beam model: beam_info is its
+    cm_mcl_beam_params beam_params{};
+    cm_mcl_beam_info beam_info{};
+    DevBuf<unsigned char> beam_steps;       // nx * ny bytes: the skip table (cmk_cast_steps)
+    DevBuf<unsigned char> beam_table;       // 2 * over_cells + 3 bytes
+    DevBuf<unsigned long long> beam_counts; // CM_MCL_BEAM_COUNTS words
+    PinnedBuf<unsigned long long> beam_host;        // the counts read back
 };
 
 // Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses, configured by cm_map_cast_configure
@@ -380,6 +391,7 @@ struct cm_ctx {
     DevBuf<void> box_work;               // per listed chunk: (slot, chunk)
     DevBuf<double> box_sums;             // per listed chunk: CM_BOX_MAX_ANGLES sums
     uint32_t box_split = CM_BOX_SPLIT;   // (CM_BOX_SPLIT in the environment: the measurement of scripts/box_cost.py)
+    uint32_t mcl_beam_walks = CM_MCL_BEAM_WALKS;     // (CM_MCL_BEAM_WALKS in the environment: scripts/map_mcl_beam_cost.py)
 
     // 2-D grid map of the frame (cm_kernels_grid.hip), on request after a frame: it reads the frame's clouds in place (d_frame,
     // frame_mask, gmask) and writes a table and an image of its own — no frame reads them — allocated by the first request and
@@ -571,6 +583,9 @@ int map_mcl_init_pose(cm_ctx* c, const float v[6]);
 int map_mcl_init_uniform(cm_ctx* c);
 int map_mcl_predict(cm_ctx* c, const float v[6]);
 int map_mcl_update(cm_ctx* c);
+// The beam model of the localisation layer: its memory and table (nullptr: back to the field score); the weights and the
+// infos go stale, the particles and gen stay.
+int map_mcl_beam_configure(cm_ctx* c, const cm_mcl_beam_params* q);
 // The cast layer behind the cost layer. map_cast_configure: room for q's rays over the map's window, the bearings (nullptr:
 // evenly spaced) and the direction table uploaded (q nullptr: the buffers go). map_cast_evaluate runs a call that cm_api.cpp has
 // checked: n poses on the host, or, with host_poses nullptr, the localisation layer's n particles in place.

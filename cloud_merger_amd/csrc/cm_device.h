@@ -548,6 +548,17 @@ struct CmMclParticleDev {              // cm_mcl_particle
 struct CmMclWeightDev {                // cm_mcl_weight
     uint32_t score, weight;
 };
+// The beam model of the localisation layer (k_mcl_beam): a lane keeps CM_MCL_BEAM_WALKS rays in flight (1 and 4
+// are compiled too and chosen by the environment's CM_MCL_BEAM_WALKS, a measurement's switch: the same bytes at every value);
+// the CM_MCL_BEAM_COUNTS 64-bit outcome counts on the device, zero before an update, in cm_mcl_beam_info's order.
+#define CM_MCL_BEAM_WALKS 2
+#define CM_MCL_BEAM_COUNTS 6
+#define CM_MCL_BEAM_MAX_OVER_DEV 64u
+struct CmMclBeamDev {
+    uint32_t over;                     // over_cells
+    uint32_t plain;                    // CM_MCL_BEAM_PLAIN
+    uint32_t walks;                    // rays a lane keeps in flight: 1, 2 or 4
+};
 // What one init or predict call adds to a particle: the centre (init) or the motion (predict), the three noise scales sc and
 // the base of the call's draws.
 struct CmMclMoveDev {

@@ -312,6 +312,12 @@ void cmk_mcl_init_uniform(hipStream_t s, const CmMclDev& g, unsigned long long b
 void cmk_mcl_predict(hipStream_t s, const CmMclMoveDev& m, uint32_t n, const float* dirs, CmMclParticleDev* parts);
 void cmk_mcl_score(hipStream_t s, const unsigned char* field, const CmMclDev& g, const uint32_t* list, const unsigned long long* words,
                    const float* dirs, CmMclParticleDev* parts, CmMclWeightDev* wts);
+// The beam model's score in cmk_mcl_score's place: image, the map's image; steps, the skip bytes cmk_cast_steps wrote (not read
+// under bm.plain); table, the 2 * bm.over + 3 bytes of cm_mcl_beam_table on the device; counts, the CM_MCL_BEAM_COUNTS 64-bit
+// outcome counts, zero before the launch.
+void cmk_mcl_beam(hipStream_t s, const void* image, const unsigned char* steps, const unsigned char* table, const CmMclDev& g, const CmMclBeamDev& bm,
+                  const uint32_t* list, const unsigned long long* words, const float* dirs, CmMclParticleDev* parts, CmMclWeightDev* wts,
+                  unsigned long long* counts);
 void cmk_mcl_best(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, unsigned long long* words);
 void cmk_mcl_weights(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, double beta, const float* dirs, CmMclWeightDev* wts,
                      unsigned long long* words);

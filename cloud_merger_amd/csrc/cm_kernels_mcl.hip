@@ -23,6 +23,12 @@
 //                    cell). A lane takes beams lane, lane + 64, ... and issues the field loads of CM_MCL_BEAM_BATCH of them
 //                    before it adds any: the loads do not depend on one another. An integer wave reduction; lane 0 stores S_p
 //                    and the new acc_p by plain vector stores.
+//   k_mcl_beam       k_mcl_score's shape for the beam model: a beam is a ray on the map's integer line from the
+//                    particle's cell to the beam's end cell and over_cells past it, walked by cm_cast_math.hpp's reach forms (by
+//                    the skip bytes of cmk_cast_steps, or cell by cell through the image under CM_MCL_BEAM_PLAIN), and scored
+//                    at once by a table byte from LDS; two independent walks per lane in flight (one or four by a measurement's switch). The six outcome
+//                    counts are summed per lane, per wave by shuffles, per workgroup in LDS, then one 64-bit integer atomicAdd
+//                    per non-zero count and workgroup.
 //   k_mcl_best       one workgroup: the largest acc, ties to the lowest index; the best particle's x, y, h.
 //   k_mcl_weights    one thread per particle: W_p through cm_exp_neg (cm_ndt_math.hpp with the _rn macros), and the six sums
 //                    of step 9 combined per wave by shuffles and per workgroup in LDS before one 64-bit integer atomicAdd per
@@ -49,6 +55,10 @@
 #include "cm_ndt_math.hpp"
 #define CM_MCL_FN __device__ __forceinline__
 #include "cm_mcl_math.hpp"
+// the line and the walks of cm_cast_math.hpp, as cm_kernels_cast.hip sets them
+#define CM_CAST_FN __device__ __forceinline__
+#define CM_CAST_RCP(d) __builtin_amdgcn_rcpf(d)
+#include "cm_cast_math.hpp"
 
 namespace {
 
@@ -273,6 +283,118 @@ __global__ __launch_bounds__(CM_MCL_WAVES * 64) void k_mcl_score(const unsigned 
     }
 }
 
+// ---- the beam score ------------------------------------------------------------------------------------------------------------
+// Step 7 under the beam model (cm_map_mcl_beam_configure): k_mcl_score's shape, but every beam is a ray from the particle's
+// cell to the beam's end cell and bm.over steps past it, walked at once and turned into a table byte; no per-ray record.
+// Dynamic LDS: g.max_beams float2, then CM_MCL_WAVES * CM_MCL_BEAM_COUNTS count words, then the 2 * over + 3 table bytes.
+// A lane walks WALKS rays at a time (beams b, b + 64, ...): their byte loads do not depend on one another.
+template <int WALKS>
+__global__ __launch_bounds__(CM_MCL_WAVES * 64) void k_mcl_beam(const signed char* __restrict__ image, const unsigned char* __restrict__ steps,
+                                                                const unsigned char* __restrict__ table, CmMclDev g, CmMclBeamDev bm,
+                                                                const uint32_t* __restrict__ list, const u64* __restrict__ words,
+                                                                const float2* __restrict__ dirs, CmMclParticleDev* __restrict__ parts,
+                                                                CmMclWeightDev* __restrict__ wts, u64* __restrict__ counts) {
+    extern __shared__ __align__(16) unsigned char s_mem[];
+    float2* const s_beam = reinterpret_cast<float2*>(s_mem);
+    uint32_t(*const s_cnt)[CM_MCL_BEAM_COUNTS] = reinterpret_cast<uint32_t(*)[CM_MCL_BEAM_COUNTS]>(s_mem + static_cast<size_t>(g.max_beams) * sizeof(float2));
+    unsigned char* const s_tab = reinterpret_cast<unsigned char*>(s_cnt + CM_MCL_WAVES);
+    const uint32_t n_words = static_cast<uint32_t>(words[CM_MCL_W_NBEAMS]);
+    const uint32_t n_beams = n_words < g.max_beams ? n_words : g.max_beams;       // (it is at most max_beams: the room of s_beam)
+    const uint32_t E = bm.over;                        // (<= CM_CAST_MAX_OVER: the launcher looked)
+    for (uint32_t i = threadIdx.x; i < n_beams; i += CM_MCL_WAVES * 64) {
+        const uint32_t c = list[i];
+        const int bx = static_cast<int>(c % g.side) - static_cast<int>(g.range), by = static_cast<int>(c / g.side) - static_cast<int>(g.range);
+        s_beam[i] = make_float2(__fmul_rn(__fadd_rn(static_cast<float>(bx), 0.5f), g.cell), __fmul_rn(__fadd_rn(static_cast<float>(by), 0.5f), g.cell));
+    }
+    for (uint32_t i = threadIdx.x; i < 2u * E + 3u; i += CM_MCL_WAVES * 64) s_tab[i] = table[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6)));
+    uint32_t cnt[CM_MCL_BEAM_COUNTS] = {0u, 0u, 0u, 0u, 0u, 0u};       // early, at, late, beyond, off, skipped (a lane has below 2^23 rays)
+    for (uint32_t p = blockIdx.x * CM_MCL_WAVES + wave; p < g.n; p += gridDim.x * CM_MCL_WAVES) {
+        const CmMclParticleDev q = parts[p];
+        const float2 e = dirs[heading_entry(q.h)];
+        int px = 0, py = 0;
+        const bool there = world_axis(q.x, g.inv, &px) & world_axis(q.y, g.inv, &py);
+        // (|px| < 2^30 and |ax| < 2^30 + 2^21: the wrapped difference is below nx only where the true one is)
+        const uint32_t ox = static_cast<uint32_t>(px) - static_cast<uint32_t>(g.ax), oy = static_cast<uint32_t>(py) - static_cast<uint32_t>(g.ay);
+        const bool origin = there && ox < g.nx && oy < g.ny;
+        uint32_t sum = 0u;
+        for (uint32_t b0 = lane; b0 < n_beams; b0 += 64u * WALKS) {
+            CmCastLine ln[WALKS];
+            bool live[WALKS];
+            uint32_t out[WALKS];
+#pragma unroll
+            for (int k = 0; k < WALKS; ++k) {
+                const uint32_t b = b0 + 64u * static_cast<uint32_t>(k);
+                live[k] = false;
+                out[k] = 4u << 16;                     // no beam here
+                ln[k] = CmCastLine{1, 1, 0u, 1u, 0.5f, true};
+                if (b >= n_beams) continue;
+                out[k] = 3u << 16;                     // skipped
+                if (!origin) continue;
+                const float2 f = s_beam[b];
+                const float wx = __fsub_rn(__fadd_rn(q.x, __fmul_rn(e.x, f.x)), __fmul_rn(e.y, f.y));
+                const float wy = __fadd_rn(__fadd_rn(q.y, __fmul_rn(e.y, f.x)), __fmul_rn(e.x, f.y));
+                int gx = 0, gy = 0;
+                if (!(world_axis(wx, g.inv, &gx) & world_axis(wy, g.inv, &gy))) continue;
+                const long long dx = static_cast<long long>(gx) - static_cast<long long>(px), dy = static_cast<long long>(gy) - static_cast<long long>(py);
+                const long long adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
+                const long long L = adx > ady ? adx : ady;
+                if (L > static_cast<long long>(CM_CAST_MAX_D)) continue;          // (sharpened in the header: skipped)
+                if (L == 0) {                          // only the origin cell is looked at: a hit at 0 or beyond
+                    out[k] = image[oy * g.nx + ox] == 100 ? (1u << 16) : 0u;
+                    continue;
+                }
+                ln[k] = cm_cast_line(static_cast<int32_t>(dx), static_cast<int32_t>(dy));
+                live[k] = true;
+            }
+            if (bm.plain) cm_cast_reach_plain_n<WALKS>(ln, live, E, ox, oy, g.nx, g.ny, image, out);
+            else cm_cast_reach_skip_n<WALKS>(ln, live, E, ox, oy, g.nx, g.ny, steps, out);
+#pragma unroll
+            for (int k = 0; k < WALKS; ++k) {
+                const uint32_t status = out[k] >> 16;
+                if (status == 4u) continue;
+                if (status == 3u) {
+                    ++cnt[5];
+                    continue;
+                }
+                uint32_t idx;
+                if (status == 1u) {
+                    const int32_t d = static_cast<int32_t>(out[k] & 0xFFFFu) - static_cast<int32_t>(live[k] ? ln[k].L : 0u);
+                    const int32_t ee = d < -static_cast<int32_t>(E) ? -static_cast<int32_t>(E) : d;
+                    idx = static_cast<uint32_t>(ee + static_cast<int32_t>(E));
+                    cnt[0] += ee < 0;
+                    cnt[1] += ee == 0;
+                    cnt[2] += ee > 0;
+                } else if (status == 0u) {
+                    idx = 2u * E + 1u;
+                    ++cnt[3];
+                } else {
+                    idx = 2u * E + 2u;
+                    ++cnt[4];
+                }
+                sum += s_tab[idx];
+            }
+        }
+        sum = wave_sum(sum);
+        if (lane == 0u) {
+            wts[p].score = sum;
+            parts[p].acc = q.acc + sum;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CM_MCL_BEAM_COUNTS; ++k) cnt[k] = wave_sum(cnt[k]);       // (a wave has below 2^29 rays)
+    if (lane == 0u)
+        for (int k = 0; k < CM_MCL_BEAM_COUNTS; ++k) s_cnt[wave][k] = cnt[k];
+    __syncthreads();
+    if (threadIdx.x < CM_MCL_BEAM_COUNTS) {
+        u64 t = 0ull;
+        for (uint32_t w = 0; w < CM_MCL_WAVES; ++w) t += s_cnt[w][threadIdx.x];
+        if (t) atomicAdd(counts + threadIdx.x, t);     // (integers: the order cannot show)
+    }
+}
+
 __global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_best(const CmMclParticleDev* __restrict__ parts, uint32_t n, u64* __restrict__ words) {
     __shared__ u64 s_acc[CM_MCL_ONE_BLOCK / 64];
     __shared__ uint32_t s_index[CM_MCL_ONE_BLOCK / 64];
@@ -486,6 +608,18 @@ void cmk_mcl_score(hipStream_t s, const unsigned char* field, const CmMclDev& g,
     const size_t lds = static_cast<size_t>(g.max_beams) * sizeof(float2);          // (at most 64 KiB)
     hipLaunchKernelGGL(k_mcl_score, dim3(score_grid(g.n)), dim3(CM_MCL_WAVES * 64), lds, s, field, g, list, words, reinterpret_cast<const float2*>(dirs),
                        parts, wts);
+}
+
+void cmk_mcl_beam(hipStream_t s, const void* image, const unsigned char* steps, const unsigned char* table, const CmMclDev& g, const CmMclBeamDev& bm,
+                  const uint32_t* list, const unsigned long long* words, const float* dirs, CmMclParticleDev* parts, CmMclWeightDev* wts,
+                  unsigned long long* counts) {
+    if (!mcl_ok(g) || bm.over > CM_CAST_MAX_OVER) return;
+    const size_t lds = static_cast<size_t>(g.max_beams) * sizeof(float2) + CM_MCL_WAVES * CM_MCL_BEAM_COUNTS * sizeof(uint32_t) + ((2u * bm.over + 3u + 15u) & ~15u);
+    // (up to 64 KiB of beams and 240 bytes behind them: above the default limit of dynamic LDS, below the CU's 160 KiB)
+    const auto kernel = bm.walks == 1u ? k_mcl_beam<1> : bm.walks == 4u ? k_mcl_beam<4> : k_mcl_beam<2>;
+    if (lds > 65536u && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)) != hipSuccess) return;
+    hipLaunchKernelGGL(kernel, dim3(score_grid(g.n)), dim3(CM_MCL_WAVES * 64), lds, s, static_cast<const signed char*>(image), steps, table, g, bm, list, words,
+                       reinterpret_cast<const float2*>(dirs), parts, wts, counts);
 }
 
 void cmk_mcl_best(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, unsigned long long* words) {

@@ -291,6 +291,15 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
             ok = read(is, sd[0], sd[1], sd[2]);
             for (int k = 0; k < 3; ++k) ok = ok && std::isfinite(sd[k]) && sd[k] >= 0.0f && sd[k] <= 1024.0f;
         }
+        else if (key == "mcl_beam") ok = read_flag(is, &c.mcl_beam_enable);
+        else if (key == "mcl_beam_model") ok = read(is, c.mcl_beam_sigma, c.mcl_beam_over_cells) && std::isfinite(c.mcl_beam_sigma) && c.mcl_beam_sigma > 0.0f &&
+                                               c.mcl_beam_over_cells <= CM_MCL_BEAM_MAX_OVER;
+        else if (key == "mcl_beam_mix") {
+            float* z = c.mcl_beam_mix;
+            ok = read(is, z[0], z[1], z[2]) && std::isfinite(z[0]) && std::isfinite(z[1]) && std::isfinite(z[2]) && z[0] > 0.0f && z[1] >= 0.0f && z[2] >= 0.0f &&
+                 (static_cast<double>(z[0]) + static_cast<double>(z[1])) + static_cast<double>(z[2]) <= 1.0;
+        }
+        else if (key == "mcl_beam_plain") ok = read_flag(is, &c.mcl_beam_plain);
         else if (key == "cast") ok = read_flag(is, &c.cast_enable);
         else if (key == "cast_bearings") ok = read(is, c.cast_bearings) && c.cast_bearings >= 1u && c.cast_bearings <= CM_CAST_MAX_BEARINGS;
         else if (key == "cast_range") ok = read(is, c.cast_range_cells) && c.cast_range_cells >= 1u && c.cast_range_cells <= CM_CAST_MAX_RANGE_CELLS;
@@ -323,6 +332,7 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     if (c.grid_raycast && !(c.grid_cell > 0.0f)) { if (err) *err = "grid_raycast needs grid_cell > 0"; return false; }
     if (c.match_enable && c.match_search_enable) { if (err) *err = "match and match_search exclude each other"; return false; }
     if (c.mcl_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "mcl needs the cost layer (map and map_inflation)"; return false; }
+    if (c.mcl_beam_enable && !c.mcl_enable) { if (err) *err = "mcl_beam needs the localisation layer (mcl 1)"; return false; }
     if (c.cast_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "cast needs the cost layer (map and map_inflation)"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
@@ -405,6 +415,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                 const cm_mcl_params lp{cfg_.mcl_particles, cfg_.mcl_max_beams, cfg_.mcl_range_cells, cfg_.mcl_sigma, cfg_.mcl_max_dist, cfg_.mcl_tau,
                                        cfg_.mcl_resample_frac, cfg_.mcl_resample_always ? CM_MCL_RESAMPLE_ALWAYS : 0u, cfg_.mcl_seed};
                 if (cm_map_mcl_configure(ctx_, &lp) != CM_OK) refuse("cm_map_mcl_configure");
+                if (ctx_ && cfg_.mcl_beam_enable) {                // its beam model: rays cast per beam in the field score's place
+                    const cm_mcl_beam_params bp{cfg_.mcl_beam_over_cells, cfg_.mcl_beam_sigma, cfg_.mcl_beam_mix[0], cfg_.mcl_beam_mix[1], cfg_.mcl_beam_mix[2],
+                                                cfg_.mcl_beam_plain ? CM_MCL_BEAM_PLAIN : 0u};
+                    if (cm_map_mcl_beam_configure(ctx_, &bp) != CM_OK) refuse("cm_map_mcl_beam_configure");
+                }
             }
             if (ctx_ && cfg_.cast_enable) {                        // the cast layer behind the cost layer: one pose, evenly spaced bearings
                 const cm_cast_params kp{1u, cfg_.cast_bearings, cfg_.cast_range_cells, cfg_.cast_plain ? CM_CAST_PLAIN : 0u};
@@ -631,6 +646,7 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
             if (dyaw < -3.14159265f) dyaw += 6.28318531f;
             ls = cm_map_mcl_predict(ctx_, c * dx + s * dy, c * dy - s * dx, dyaw, cfg_.mcl_noise[0], cfg_.mcl_noise[1], cfg_.mcl_noise[2]);
             if (ls == CM_OK) ls = cm_map_mcl_update(ctx_, &mcl_info_);
+            if (ls == CM_OK && cfg_.mcl_beam_enable) ls = cm_map_mcl_beam_info_copy(ctx_, &mcl_beam_info_);
         }
         if (ls == CM_OK) {
             std::memcpy(mcl_prev_, now, sizeof now);

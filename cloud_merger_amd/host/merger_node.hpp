@@ -183,6 +183,13 @@ struct NodeConfig {
     bool mcl_init_uniform = false;                   // mcl_init uniform; otherwise around the pose with mcl_init_sd
     float mcl_init_sd[3] = {0.5f, 0.5f, 0.2f};       // sd_x, sd_y (metres), sd_yaw (radians)
     float mcl_noise[3] = {0.05f, 0.05f, 0.02f};      // sd_fwd, sd_left (metres), sd_yaw (radians) of every predict
+    // Its beam model (cm_map_mcl_beam_configure): an update casts a ray per particle and beam instead of looking the beam's end
+    // cell up in the field (mcl_beam_info()). Off by default; it needs mcl 1.
+    bool mcl_beam_enable = false;
+    float mcl_beam_sigma = 0.1f;                     // of the hit term (metres)
+    uint32_t mcl_beam_over_cells = 8;                // how far past its measured end a ray is followed
+    float mcl_beam_mix[3] = {0.75f, 0.125f, 0.125f}; // z_hit, z_short, z_rand
+    bool mcl_beam_plain = false;                     // walk cell by cell instead of jumping
     // The cast layer (cm_map_cast_configure, cm_map_cast_evaluate): the virtual scan of the map. Off by default. On (it needs
     // the cost layer; without one load_config refuses the file and the node does not start): after each frame's cost update
     // the node casts cast_bearings evenly spaced rays of at most cast_range_cells cells from set_pose()'s pose (cast_rays(),
@@ -249,6 +256,8 @@ struct NodeConfig {
 //   mcl <0|1> | mcl_particles <n> | mcl_beams <max_beams> <range_cells> | mcl_field <sigma> <max_dist> | mcl_tau <tau> |
 //   mcl_resample <frac> <always 0|1> | mcl_seed <seed> | mcl_init <pose sd_x sd_y sd_yaw | uniform> | mcl_noise <sd_fwd sd_left sd_yaw>
 //   (the localisation layer behind the cost layer, which it needs: a file with mcl 1 and no map_inflation is refused)
+//   mcl_beam <0|1> | mcl_beam_model <sigma> <over_cells> | mcl_beam_mix <z_hit> <z_short> <z_rand> | mcl_beam_plain <0|1>
+//   (the localisation layer's beam model; a file with mcl_beam 1 and no mcl 1 is refused)
 //   cast <0|1> | cast_bearings <n> | cast_range <cells> | cast_plain <0|1>
 //   (the cast layer behind the cost layer, which it needs: the virtual scan of the map from the set pose after every frame)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
@@ -386,6 +395,8 @@ public:
     // after the last call of the layer.
     bool mcl_started() const { return mcl_started_; }
     const cm_mcl_info& mcl_info() const { return mcl_info_; }
+    // mcl_beam 1: the outcome counts of the last update (zeros until the first).
+    const cm_mcl_beam_info& mcl_beam_info() const { return mcl_beam_info_; }
     const std::vector<cm_mcl_particle>& mcl_particles() const { return mcl_particles_; }
     // cast 1: the rays of the virtual scan behind the last frame's cost update (empty where the library refused the cast) and
     // their counts by status.
@@ -475,6 +486,7 @@ private:
     bool mcl_started_ = false;
     float mcl_prev_[3] = {0.0f, 0.0f, 0.0f};         // x, y, yaw of the set pose at the last init or predict
     cm_mcl_info mcl_info_{};
+    cm_mcl_beam_info mcl_beam_info_{};
     std::vector<cm_mcl_particle> mcl_particles_;
     std::vector<cm_cast_ray> cast_rays_;
     cm_cast_info cast_info_{};

@@ -1315,8 +1315,8 @@ CM_API int cm_map_frontier_device(cm_ctx* ctx, const void** labels, const void**
  * cm_map_cost_configure and cm_map_configure, in either form, free the layer. It reads the map and the cost layer and writes
  * buffers of its own only: no other layer's tables or staleness change. A NULL context leaves every output untouched. With
  * CM_FLAG_PROFILE, cm_get_stage_times after an update lists mcl_clear, k_match_field, k_mcl_mark, k_mcl_compact, k_mcl_score,
- * k_mcl_best, k_mcl_weights, k_mcl_spread, k_mcl_resample. Not modelled: the beam model's terms (z_short, z_max, z_rand),
- * occlusion, adaptive (KLD) particle counts, random-particle injection, roll, pitch and z, weighting a cell by the number of
+ * k_mcl_best, k_mcl_weights, k_mcl_spread, k_mcl_resample. The beam model's terms and occlusion are a mode of their own (the
+ * next section). Not modelled: adaptive (KLD) particle counts, random-particle injection, roll, pitch and z, weighting a cell by the number of
  * its points. */
 #define CM_MCL_MAX_PARTICLES 65536
 #define CM_MCL_MAX_BEAMS 8192
@@ -1377,6 +1377,79 @@ CM_API int cm_map_mcl_device(cm_ctx* ctx, const void** particles, const void** w
  * a NULL dst, first_p + n_p above 2^32 (nothing is written). */
 CM_API int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t n_p, uint32_t i, uint64_t* dst);
 
+/* ---- the beam model of the localisation layer: rays cast per beam (an extension) -------------------------------------------
+ * The field score of step 7 looks at a beam's end cell only: a pose whose beams end on a far wall after passing through a
+ * near one scores like the true pose. The beam model is a second scoring mode of the same layer (amcl's beam model with its
+ * hit, short and random terms). cm_map_mcl_beam_configure switches it on; it is off by default, and with it off
+ * every byte of the layer is what it is without this section. With it on, step 7 above is replaced by the steps below; steps
+ * 1 to 6 and 8 to 11 stay word for word. E = over_cells. Everything after the two cells is integer arithmetic: the weight
+ * table, both infos and the particles stay bit for bit a function of the inputs.
+ *   1. Origin cell. o is the map's step 1 of (x_p, y_p) minus the anchor. If it does not exist or lies outside the window,
+ *      every beam of p is `skipped` and S_p = 0.
+ *   2. End cell. (wx, wy) is computed exactly as in step 7 above, with the same rounded operations. g is its cell minus the
+ *      anchor. If it does not exist, the beam is `skipped` and adds 0. g may lie outside the window.
+ *   3. Line. (dx, dy) = g - o and L = max(|dx|, |dy|). The line is cm_result_grid_rays' step 5: the cell at step k is
+ *      o + (rdiv(k dx, L), rdiv(k dy, L)). It is followed for k = 0 .. L + E. With L = 0 only k = 0 (the origin cell) is looked
+ *      at. The bound on |dx|, |dy|: a beam's body cell has |b| <= range_cells, so |fx|, |fy| <= (range_cells + 0.5) cell; the
+ *      heading table's (c, s) are fp32 roundings of a cosine and a sine, c^2 + s^2 <= 1 + 2^-22, so the exact
+ *      |c fx - s fy| <= sqrt(2) (1 + 2^-23) (range_cells + 0.5) cell, 1448.87 cells at range_cells 1024, and likewise for y.
+ *      Two cells whose coordinates differ by t cells have indices that differ by less than t + 1. The roundings: with M the
+ *      largest |cell index| of the window, each of the two sums and each of the two products x * inv is off by at most
+ *      2^-24 (M + 1450) cells (the two inner products by 2^-24 * 1024.5 cells, which 1448.87 already leaves room for), in all
+ *      below 2^-22 (M + 1450). So |dx|, |dy| < 1449.87 + 2^-22 (M + 1450), which is at most 1450 = CM_MCL_BEAM_MAX_D whenever
+ *      2^-22 (M + 1450) <= 1.12: every window within 2^22 cells of the world origin (200 km at a 5 cm cell). Sharpened: a beam with |dx| or |dy| above
+ *      CM_MCL_BEAM_MAX_D, which only a window farther out can produce, is `skipped` and adds 0.
+ *   4. Walk, in order of k. A cell outside the window ends the ray as `off`. I == 100 ends it as a hit at k*; an occupied
+ *      origin cell is a hit at 0. -1 and 0 are passed through, as in the cast layer. No hit through L + E is `beyond`.
+ *   5. Outcome. A hit has e = max(k* - L, -E); it counts as `early` for e < 0, `at` for e == 0 and `late` for e > 0. The table
+ *      index is e + E for a hit, 2E + 1 for `beyond` and 2E + 2 for `off`. Sharpened: with L = 0 a free or unknown origin cell
+ *      is `beyond`, whatever E is, and an occupied one is `at`.
+ *   6. Table, 2E + 3 bytes, built once on the host in double, every operation rounded once, with cm_exp_neg of
+ *      cm_ndt_math.hpp, sc = (double)sigma / (double)cell and s2 = (2.0 * sc) * sc:
+ *      T[e + E] = rint(255 * min(1, (z_hit * cm_exp_neg((double)(e * e) / s2) + (e > 0 ? z_short : 0)) + z_rand)),
+ *      T[2E + 1] = rint(255 * (z_short + z_rand)), T[2E + 2] = rint(255 * z_rand); ties go to even. cm_mcl_beam_table returns
+ *      it.
+ *   7. Score. S_p is the sum of the table bytes over the beams, at most 8192 * 255; acc_p += S_p, as in step 7 above.
+ *   8. Counts, cm_mcl_beam_info: n_rays = n_particles * n_beams of the update and the six outcome counts over all
+ *      (p, beam), integer sums; the host checks that they add up to n_rays.
+ * CM_MCL_BEAM_PLAIN selects a device walk that does what step 4 says, cell by cell, reading the image. Without it the device
+ * skips cells that dist2 proves free of an occupied cell, by the cast layer's rule; the outputs are the same bytes either way.
+ * The mode does not need a configured cast layer.
+ * cm_map_mcl_beam_configure refuses with CM_BAD_ARG (cm_last_error says why): a frame in flight; no localisation layer (or
+ * no layer above it), in that layer's words; over_cells above CM_MCL_BEAM_MAX_OVER; sigma not finite and > 0; a z that is not
+ * finite, z_hit not > 0, z_short or z_rand below 0, a sum above 1 (in double, in the order written); unknown flag bits. A
+ * refused call changes nothing. An accepted call, with parameters or NULL, takes or gives back all the mode's memory (one byte
+ * per window cell for the skips, the table, the count words and their page-locked copy: no other call allocates), leaves the
+ * particles and gen alone (it is not one of the calls gen counts, so no draw changes) and makes the weight table and both infos
+ * stale "since cm_map_mcl_beam_configure" until the next cm_map_mcl_update. cm_map_mcl_configure in either form switches the
+ * mode off and frees it, and so does everything that frees the layer. cm_map_mcl_update refuses exactly what it refuses without
+ * the mode. cm_map_mcl_beam_info_copy refuses what cm_map_mcl_weights_copy refuses, and a last update that ran without the
+ * mode. A NULL context leaves every output untouched. With CM_FLAG_PROFILE the stage list of an update has k_mcl_beam in place
+ * of k_mcl_score, and k_mcl_steps in front of it only in the first beam update after a cm_map_cost_update (or after the
+ * configure call), never under CM_MCL_BEAM_PLAIN. Not modelled: a z_max term of its own (a ray without a hit takes the short
+ * and random terms), sub-cell ranges, unknown cells as obstacles, a per-beam weight. */
+#define CM_MCL_BEAM_MAX_OVER 64
+#define CM_MCL_BEAM_MAX_D 1450
+#define CM_MCL_BEAM_PLAIN 1u
+typedef struct cm_mcl_beam_params {    /* 24 bytes, no padding */
+    uint32_t over_cells;               /* E: how far past the measured end a ray is followed; 0 .. CM_MCL_BEAM_MAX_OVER */
+    float sigma;                       /* of the hit term, metres; finite, > 0 */
+    float z_hit, z_short, z_rand;      /* finite, each >= 0, z_hit > 0, their sum <= 1 */
+    uint32_t flags;                    /* CM_MCL_BEAM_PLAIN or 0 */
+} cm_mcl_beam_params;
+typedef struct cm_mcl_beam_info {      /* 56 bytes */
+    uint64_t n_rays;                   /* n_particles * n_beams of the update */
+    uint64_t n_early, n_at, n_late, n_beyond, n_off, n_skipped;   /* their sum is n_rays */
+} cm_mcl_beam_info;
+/* Non-NULL parameters switch the beam model on (or replace its parameters); NULL goes back to the field score. */
+CM_API int cm_map_mcl_beam_configure(cm_ctx* ctx, const cm_mcl_beam_params* p);
+/* The counts of the last update, which must have run the beam model. */
+CM_API int cm_map_mcl_beam_info_copy(cm_ctx* ctx, cm_mcl_beam_info* out);
+/* The table of step 6 for a map of this cell: 2 * over_cells + 3 bytes. A host function: no context, no GPU. CM_BAD_ARG: NULL
+ * p or dst, parameters cm_map_mcl_beam_configure refuses, a cell that is not finite and > 0; a smaller capacity: CM_CAPACITY
+ * (nothing is written). */
+CM_API int cm_mcl_beam_table(const cm_mcl_beam_params* p, float cell, uint8_t* dst, uint64_t capacity);
+
 /* ---- the cast layer: expected ranges from many poses in the occupancy map (an extension) ----------------------------------
  * Every other layer looks single cells up. This one answers what the map was built by ray casting to answer: from this pose,
  * in this direction, how far is the first occupied cell? It serves a beam model, a virtual LaserScan of the map, visibility
@@ -1426,8 +1499,9 @@ CM_API int cm_mcl_draws(uint64_t seed, uint64_t gen, uint32_t first_p, uint32_t 
  * particles and writes buffers of its own only: no other layer's tables, staleness or timing change. A NULL context leaves
  * every output untouched. With CM_FLAG_PROFILE, cm_get_stage_times after an evaluate lists cast_upload, k_cast_steps (only in
  * the first evaluate after a cm_map_cost_update, and never under CM_CAST_PLAIN) and k_cast_rays. Not modelled: stopping at or
- * counting unknown cells, sub-cell origins (a ray starts at its origin cell's centre, as the map's own rays do), 3-D casting,
- * the use of the ranges inside cm_map_mcl_update. */
+ * counting unknown cells, sub-cell origins (a ray starts at its origin cell's centre, as the map's own rays do), 3-D casting.
+ * cm_map_mcl_update does not read this layer's table: its beam model (cm_map_mcl_beam_configure) casts its own rays, from
+ * each particle towards each beam's end cell, with the same line and the same skip rule. */
 #define CM_CAST_MAX_POSES 65536
 #define CM_CAST_MAX_BEARINGS 4096
 #define CM_CAST_MAX_RANGE_CELLS 1024
