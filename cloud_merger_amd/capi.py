@@ -56,6 +56,7 @@ SYMBOLS = [
     "cm_map_match_search_configure", "cm_map_match_search", "cm_map_match_search_result", "cm_map_match_search_level_copy",
     "cm_map_mcl_configure", "cm_map_mcl_init_pose", "cm_map_mcl_init_uniform", "cm_map_mcl_predict", "cm_map_mcl_update", "cm_map_mcl_copy",
     "cm_map_mcl_weights_copy", "cm_map_mcl_device", "cm_mcl_draws", "cm_map_mcl_beam_configure", "cm_map_mcl_beam_info_copy", "cm_mcl_beam_table",
+    "cm_map_mcl_hyp_configure", "cm_map_mcl_hyp_copy", "cm_mcl_kld_bound",
     "cm_map_cast_configure", "cm_map_cast_evaluate", "cm_map_cast_evaluate_mcl", "cm_map_cast_copy", "cm_map_cast_device", "cm_cast_directions",
     "cm_result_normals", "cm_result_normals_device",
     "cm_result_align", "cm_result_align_device", "cm_align_correspondences_copy",
@@ -482,6 +483,39 @@ class MclBeamInfo(C.Structure):
 
 assert C.sizeof(MclBeamParams) == 24 and MclBeamParams.flags.offset == 20 and C.sizeof(MclBeamInfo) == 56
 
+# pose hypotheses and random-particle recovery of the localisation layer (cm_map_mcl_hyp_configure)
+MCL_HYP_MAX = 64
+MCL_NO_PARENT = 0xFFFFFFFF
+
+
+class MclHypParams(C.Structure):
+    """cm_mcl_hyp_params (40 bytes): the bin width in 1/1024 m and the bits of the heading bins, the most hypotheses reported,
+    the most particles one update may inject (0: none), the rates of the slow and the fast average of the score, the error and
+    the quantile of the KLD bound, flags and padding (0)."""
+    _fields_ = [("bin_q", C.c_uint32), ("heading_bits", C.c_uint32), ("max_hyp", C.c_uint32), ("inject_max", C.c_uint32), ("alpha_slow", C.c_float),
+                ("alpha_fast", C.c_float), ("kld_err", C.c_float), ("kld_z", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class MclHyp(C.Structure):
+    """cm_mcl_hyp (136 bytes): one connected component of the occupied bins: its smallest key, its particles and the heaviest
+    of them, the integer sums of the estimate over its particles, its share of the total weight and its mean and spread."""
+    _fields_ = [("label", C.c_uint64), ("n", C.c_uint32), ("top", C.c_uint32), ("sum_w", C.c_uint64), ("sum_wqx", C.c_int64), ("sum_wqy", C.c_int64),
+                ("sum_wc", C.c_int64), ("sum_ws", C.c_int64), ("sum_wdxx", C.c_int64), ("sum_wdyy", C.c_int64), ("sum_wdxy", C.c_int64),
+                ("share", C.c_double), ("mean_x", C.c_double), ("mean_y", C.c_double), ("mean_yaw", C.c_double), ("var_xx", C.c_double),
+                ("var_yy", C.c_double), ("var_xy", C.c_double)]
+
+
+class MclHypInfo(C.Structure):
+    """cm_mcl_hyp_info (72 bytes): the update's gen, the occupied bins, their components, the hypotheses reported, the KLD bound
+    for that many bins, the particles injected, the free cells they were drawn from, the sum of the scores, their average, its
+    slow and fast average and the share of the particles the recovery asked for."""
+    _fields_ = [("gen", C.c_uint64), ("n_bins", C.c_uint32), ("n_components", C.c_uint32), ("n_hyp", C.c_uint32), ("n_kld", C.c_uint32),
+                ("n_inject", C.c_uint32), ("n_free", C.c_uint32), ("sum_s", C.c_uint64), ("w_avg", C.c_double), ("w_slow", C.c_double),
+                ("w_fast", C.c_double), ("p_inject", C.c_double)]
+
+
+assert C.sizeof(MclHypParams) == 40 and C.sizeof(MclHyp) == 136 and MclHyp.share.offset == 80 and C.sizeof(MclHypInfo) == 72
+
 # the cast layer: expected ranges from many poses in the map, behind the cost layer (cm_map_cast_configure, cm_map_cast_evaluate)
 CAST_MAX_POSES = 65536
 CAST_MAX_BEARINGS = 4096
@@ -738,6 +772,9 @@ def load():
     L.cm_map_mcl_beam_configure.argtypes = [vp, C.POINTER(MclBeamParams)]
     L.cm_map_mcl_beam_info_copy.argtypes = [vp, C.POINTER(MclBeamInfo)]
     L.cm_mcl_beam_table.argtypes = [C.POINTER(MclBeamParams), C.c_float, vp, u64]
+    L.cm_map_mcl_hyp_configure.argtypes = [vp, C.POINTER(MclHypParams)]
+    L.cm_map_mcl_hyp_copy.argtypes = [vp, C.POINTER(MclHyp), u64, C.POINTER(MclHypInfo)]
+    L.cm_mcl_kld_bound.argtypes = [u32, C.c_float, C.c_float, C.POINTER(u32)]
     L.cm_map_cast_configure.argtypes = [vp, C.POINTER(CastParams), vp]
     L.cm_map_cast_evaluate.argtypes = [vp, vp, u32, C.POINTER(CastInfo)]
     L.cm_map_cast_evaluate_mcl.argtypes = [vp, C.POINTER(CastInfo)]
@@ -808,6 +845,16 @@ def mcl_draws(seed, gen, first_p, n_p, i):
     if st != OK and n_p:
         raise CloudMergeError(st, "cm_mcl_draws")
     return out
+
+
+def mcl_kld_bound(k, err=0.05, z=2.326):
+    """The KLD bound on the particle count for k occupied bins (cm_mcl_kld_bound): with probability given by the quantile z the
+    divergence between the sampled and the true belief stays below err."""
+    out = C.c_uint32()
+    st = load().cm_mcl_kld_bound(int(k), float(err), float(z), C.byref(out))
+    if st != OK:
+        raise CloudMergeError(st, "cm_mcl_kld_bound")
+    return out.value
 
 
 def mcl_beam_table(cell, over_cells=8, sigma=0.1, z_hit=0.75, z_short=0.125, z_rand=0.125, plain=False):
@@ -1585,6 +1632,25 @@ class CloudMerger:
             return
         p = MclBeamParams(int(over_cells), float(sigma), float(z_hit), float(z_short), float(z_rand), MCL_BEAM_PLAIN if plain else 0)
         self._check(self._lib.cm_map_mcl_beam_configure(self._ctx, C.byref(p)), "cm_map_mcl_beam_configure")
+
+    def map_mcl_hyp_configure(self, bin_m=0.5, heading_bits=5, max_hyp=8, inject_max=0, alpha_slow=0.05, alpha_fast=0.5, kld_err=0.05, kld_z=2.326):
+        """Switches the localisation layer's hypotheses on: every update then bins the particles (bin_m metres, 2^heading_bits
+        heading bins), reports the connected components of the occupied bins by weight (map_mcl_hypotheses) and, with
+        inject_max > 0, replaces up to that many particles by random ones while the fast average of the score lies below the
+        slow one. bin_m None switches the mode off."""
+        if bin_m is None:
+            self._check(self._lib.cm_map_mcl_hyp_configure(self._ctx, None), "cm_map_mcl_hyp_configure")
+            return
+        p = MclHypParams(int(round(float(bin_m) * 1024.0)), int(heading_bits), int(max_hyp), int(inject_max), float(alpha_slow), float(alpha_fast),
+                         float(kld_err), float(kld_z), 0, 0)
+        self._check(self._lib.cm_map_mcl_hyp_configure(self._ctx, C.byref(p)), "cm_map_mcl_hyp_configure")
+
+    def map_mcl_hypotheses(self):
+        """(list of MclHyp, MclHypInfo) of the last update, which ran the hypotheses: the heaviest component first."""
+        info = MclHypInfo()
+        buf = (MclHyp * MCL_HYP_MAX)()
+        self._check(self._lib.cm_map_mcl_hyp_copy(self._ctx, buf, MCL_HYP_MAX, C.byref(info)), "cm_map_mcl_hyp_copy")
+        return [buf[k] for k in range(info.n_hyp)], info
 
     def map_mcl_beam_info(self):
         """The MclBeamInfo of the last update, which ran the beam model."""

@@ -381,6 +381,10 @@ int cm_create(cm_ctx** out, int device, const cm_limits* lim) {
         const unsigned long v = std::strtoul(bw, nullptr, 10);
         if (v == 1 || v == 2 || v == 4) c->mcl_beam_walks = static_cast<uint32_t>(v);
     }
+    // CM_MCL_HYP_NO_AGG=1: the lanes of a wave send their own atomics in k_mcl_hyp_sums and k_mcl_hyp_spread (a measurement's
+    // switch; the hypotheses are the same bytes either way)
+    if (const char* na = getenv("CM_MCL_HYP_NO_AGG"))
+        if (na[0] == '1' && na[1] == 0) c->mcl_hyp_agg = 0;
     if (!ok) {
         delete c;
         return CM_HIP_ERROR;
@@ -1516,6 +1520,56 @@ int cm_map_mcl_beam_info_copy(cm_ctx* c, cm_mcl_beam_info* out) {
     if (!c->mcl.beam_info_have) return fail(c, CM_BAD_ARG, "the last cm_map_mcl_update ran without the beam model (cm_map_mcl_beam_configure first)");
     if (!out) return fail(c, CM_BAD_ARG, "no destination");
     *out = c->mcl.beam_info;
+    return CM_OK;
+}
+
+static_assert(sizeof(cm_mcl_hyp_params) == 40 && offsetof(cm_mcl_hyp_params, flags) == 32 && sizeof(cm_mcl_hyp) == 136 && offsetof(cm_mcl_hyp, sum_w) == 16 &&
+                  offsetof(cm_mcl_hyp, share) == 80 && sizeof(cm_mcl_hyp_info) == 72 && offsetof(cm_mcl_hyp_info, sum_s) == 32 &&
+                  CM_MCL_HYP_MAX == CM_MCL_HYP_MAX_DEV && sizeof(CmMclHypRecDev) == 88,
+              "the three structs of the hypotheses; the kernels' constant and record");
+
+int cm_mcl_kld_bound(uint32_t k, float err, float z, uint32_t* out) {
+    if (!out || !std::isfinite(err) || !(err > 0.0f && err <= 1.0f) || !std::isfinite(z) || !(z > 0.0f)) return CM_BAD_ARG;
+    if (k <= 1u) {
+        *out = 1u;
+        return CM_OK;
+    }
+    const double k1 = static_cast<double>(k - 1u);
+    const double a = 2.0 / (9.0 * k1);
+    const double b = (1.0 - a) + std::sqrt(a) * static_cast<double>(z);
+    const double n = std::ceil((k1 / (2.0 * static_cast<double>(err))) * ((b * b) * b));
+    *out = !(n <= 4294967295.0) ? 0xFFFFFFFFu : n < 1.0 ? 1u : static_cast<uint32_t>(n);
+    return CM_OK;
+}
+
+int cm_map_mcl_hyp_configure(cm_ctx* c, const cm_mcl_hyp_params* p) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = layer_check(c, LAYER_MCL, false)) return e;
+    if (p) {
+        if (p->bin_q < 64u || p->bin_q > 1048576u) return fail(c, CM_BAD_ARG, "bin_q must lie in 64..1048576");
+        if (p->heading_bits > 8u) return fail(c, CM_BAD_ARG, "heading_bits must lie in 0..8");
+        if (p->max_hyp < 1u || p->max_hyp > CM_MCL_HYP_MAX) return fail(c, CM_BAD_ARG, "max_hyp must lie in 1..CM_MCL_HYP_MAX");
+        if (p->inject_max > c->mcl.params.n_particles - 1u) return fail(c, CM_BAD_ARG, "inject_max is above n_particles - 1");
+        if (!std::isfinite(p->alpha_slow) || !std::isfinite(p->alpha_fast) || !(0.0f <= p->alpha_slow && p->alpha_slow <= p->alpha_fast && p->alpha_fast <= 1.0f))
+            return fail(c, CM_BAD_ARG, "the alphas must be finite with 0 <= alpha_slow <= alpha_fast <= 1");
+        if (!std::isfinite(p->kld_err) || !(p->kld_err > 0.0f && p->kld_err <= 1.0f)) return fail(c, CM_BAD_ARG, "kld_err must be finite and lie in 0 < kld_err <= 1");
+        if (!std::isfinite(p->kld_z) || !(p->kld_z > 0.0f)) return fail(c, CM_BAD_ARG, "kld_z must be finite and > 0");
+        if (p->flags || p->_pad) return fail(c, CM_BAD_ARG, "unknown flag bits");
+    }
+    return map_mcl_hyp_configure(c, p);
+}
+
+int cm_map_mcl_hyp_copy(cm_ctx* c, cm_mcl_hyp* host_dst, uint64_t capacity, cm_mcl_hyp_info* info) {
+    if (!c) return CM_BAD_ARG;
+    std::lock_guard<std::mutex> lk(c->merge_mu);
+    if (const int e = mcl_check(c, true, true)) return e;
+    if (!c->mcl.hyp_have) return fail(c, CM_BAD_ARG, "the last cm_map_mcl_update ran without the hypotheses (cm_map_mcl_hyp_configure first)");
+    if (info) *info = c->mcl.hyp_info;
+    const uint64_t n = c->mcl.hyp_out.size();
+    if (capacity < n) return fail(c, CM_CAPACITY, "hypothesis destination too small");
+    if (!host_dst) return fail(c, CM_BAD_ARG, "no destination");
+    std::memcpy(host_dst, c->mcl.hyp_out.data(), n * sizeof(cm_mcl_hyp));
     return CM_OK;
 }
 

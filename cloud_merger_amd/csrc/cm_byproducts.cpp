@@ -1082,6 +1082,51 @@ int map_mcl_beam_configure(cm_ctx* c, const cm_mcl_beam_params* q) {
     return CM_OK;
 }
 
+// The hypotheses mode given back: its buffers and its state.
+static void mcl_hyp_drop(cm_ctx* c) {
+    MclLayer& m = c->mcl;
+    m.hyp_on = m.hyp_have = false;
+    m.hyp_params = cm_mcl_hyp_params{};
+    m.hyp_info = cm_mcl_hyp_info{};
+    m.hyp_cap_bits = 0;
+    std::vector<cm_mcl_hyp>().swap(m.hyp_out);
+    m.hyp_keys.release();
+    m.hyp_slots.release();
+    m.hyp_rec.release();
+    m.hyp_words.release();
+    m.hyp_bits.release();
+    m.hyp_list.release();
+    m.hyp_host.release();
+}
+
+// The hypotheses mode's memory, all of it (MclLayer's hyp_* fields say what each holds). nullptr gives it back. The particles
+// and gen stay; the averages start at 0.0; the weight table, the infos and the hypotheses are stale until the next update.
+int map_mcl_hyp_configure(cm_ctx* c, const cm_mcl_hyp_params* q) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    mcl_hyp_drop(c);
+    layer_mark_stale(c->layers, LAYER_MCL, "cm_map_mcl_hyp_configure");
+    if (!q) return CM_OK;
+    MclLayer& m = c->mcl;
+    const size_t n = m.params.n_particles, n_cells = static_cast<size_t>(c->map.info.nx) * c->map.info.ny;
+    uint32_t cap_bits = 6;
+    while ((static_cast<size_t>(1) << cap_bits) < 4 * n) ++cap_bits;
+    const size_t cap = static_cast<size_t>(1) << cap_bits;
+    constexpr size_t rec_words = sizeof(CmMclHypRecDev) / sizeof(unsigned long long);
+    m.hyp_out.reserve(CM_MCL_HYP_MAX);
+    if (!m.hyp_keys.reserve(cap) || !m.hyp_slots.reserve(2 * cap + n) || !m.hyp_rec.reserve(n + CM_MCL_HYP_MAX) || !m.hyp_words.reserve(CM_MCL_HYP_WORDS) ||
+        !m.hyp_bits.reserve((n_cells + 31) / 32) || !m.hyp_list.reserve(CM_MCL_ONE_BLOCK + n_cells) ||
+        !m.hyp_host.reserve(CM_MCL_HYP_WORDS + CM_MCL_HYP_MAX * rec_words)) {
+        mcl_hyp_drop(c);
+        return fail(c, CM_HIP_ERROR, "cannot allocate the hypotheses of the localisation layer");
+    }
+    HIP_TRY(c, hipMemsetAsync(m.hyp_words, 0, CM_MCL_HYP_WORDS * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    m.hyp_cap_bits = cap_bits;
+    m.hyp_params = *q;
+    m.hyp_on = true;
+    return CM_OK;
+}
+
 // The localisation layer's memory, all of it: two particle buffers, the weight table, the prefix sums with the info words
 // behind them, the field with its table behind it (built here, cm_match_table.hpp, and uploaded), the one bitmap and the one
 // list (behind the block counts) that serve the body cells and the free cells, the heading table and the page-locked words an
@@ -1094,6 +1139,7 @@ int map_mcl_configure(cm_ctx* c, const cm_mcl_params* q, uint32_t R) {
     }
     layer_reset(c->layers, LAYER_MCL);
     mcl_beam_drop(c);
+    mcl_hyp_drop(c);
     c->mcl.init = false;
     c->mcl.gen = 0;
     c->mcl.cur = 0;
@@ -1153,6 +1199,13 @@ CmMclMoveDev mcl_move(cm_ctx* c, const float v[6]) {
     return m;
 }
 
+// R2: an init call puts the slow and the fast average of the hypotheses mode back to 0.0.
+int mcl_hyp_restart(cm_ctx* c) {
+    if (!c->mcl.hyp_on) return CM_OK;
+    HIP_TRY(c, hipMemsetAsync(c->mcl.hyp_words + CM_MCL_HW_STATE_SLOW, 0, 2 * sizeof(unsigned long long), c->stream));
+    return CM_OK;
+}
+
 }  // namespace
 
 int map_mcl_init_pose(cm_ctx* c, const float v[6]) {
@@ -1163,6 +1216,7 @@ int map_mcl_init_pose(cm_ctx* c, const float v[6]) {
     c->prof_used = 0;
     prof_mark(c, "k_mcl_init_pose");
     cmk_mcl_init_pose(c->stream, mcl_move(c, v), c->mcl.params.n_particles, c->mcl.parts[0]);
+    if (const int e = mcl_hyp_restart(c)) return e;
     if (const int e = finish_call(c)) return e;
     c->mcl.init = true;
     return CM_OK;
@@ -1192,6 +1246,7 @@ int map_mcl_init_uniform(cm_ctx* c) {
     c->mcl.cur = 0;
     prof_mark(c, "k_mcl_init_uniform");
     cmk_mcl_init_uniform(st, g, cm_mcl_base(c->mcl.params.seed, c->mcl.gen++), list, words, c->mcl.parts[0]);
+    if (const int e = mcl_hyp_restart(c)) return e;
     if (const int e = finish_call(c)) return e;
     c->mcl.init = true;
     return CM_OK;
@@ -1264,12 +1319,118 @@ int map_mcl_update(cm_ctx* c) {
     cmk_mcl_weights(st, src, g.n, beta, c->mcl.dirs, c->mcl.wts, words);
     prof_mark(c, "k_mcl_spread");
     cmk_mcl_spread(st, src, g.n, c->mcl.wts, words);
+    const bool hyp = c->mcl.hyp_on;
+    constexpr size_t hyp_rec_words = sizeof(CmMclHypRecDev) / sizeof(unsigned long long);
+    CmMclHypDev hy{};
+    c->mcl.hyp_have = false;
+    if (hyp) {                                         // the hypotheses over the particles as found, then R1 to R3
+        const cm_mcl_hyp_params& hp = c->mcl.hyp_params;
+        const size_t cap = static_cast<size_t>(1) << c->mcl.hyp_cap_bits;
+        hy.on = 1u;
+        hy.n = g.n;
+        hy.cap_bits = c->mcl.hyp_cap_bits;
+        hy.bin_q = hp.bin_q;
+        hy.heading_bits = hp.heading_bits;
+        hy.max_hyp = hp.max_hyp;
+        hy.inject_max = hp.inject_max;
+        hy.agg = c->mcl_hyp_agg;
+        hy.a_slow = static_cast<double>(hp.alpha_slow);
+        hy.a_fast = static_cast<double>(hp.alpha_fast);
+        hy.keys = c->mcl.hyp_keys;
+        hy.parent = c->mcl.hyp_slots;
+        hy.comp = c->mcl.hyp_slots + cap;
+        hy.slot = c->mcl.hyp_slots + 2 * cap;
+        hy.rec = c->mcl.hyp_rec;
+        hy.out = c->mcl.hyp_rec + g.n;
+        hy.words = c->mcl.hyp_words;
+        hy.free_list = c->mcl.hyp_list + CM_MCL_ONE_BLOCK;
+        prof_mark(c, "mcl_hyp_clear");
+        HIP_TRY(c, hipMemsetAsync(hy.keys, 0xFF, cap * sizeof(unsigned long long), st));
+        HIP_TRY(c, hipMemsetAsync(hy.words, 0, CM_MCL_HW_CLEARED * sizeof(unsigned long long), st));
+        prof_mark(c, "k_mcl_hyp_bins");
+        cmk_mcl_hyp_bins(st, src, hy);
+        prof_mark(c, "k_mcl_hyp_link");
+        cmk_mcl_hyp_link(st, hy);
+        prof_mark(c, "k_mcl_hyp_flatten");
+        cmk_mcl_hyp_flatten(st, hy);
+        prof_mark(c, "k_mcl_hyp_sums");
+        cmk_mcl_hyp_sums(st, src, c->mcl.wts, c->mcl.dirs, hy);
+        prof_mark(c, "k_mcl_hyp_spread");
+        cmk_mcl_hyp_spread(st, src, c->mcl.wts, hy);
+        prof_mark(c, "k_mcl_hyp_pick");
+        cmk_mcl_hyp_pick(st, hy);
+        if (hp.inject_max) {                           // the free cells of the current image, in the mode's own bitmap and list
+            const uint32_t cells = static_cast<uint32_t>(n_cells);
+            prof_mark(c, "k_mcl_free_bits");
+            cmk_mcl_free_bits(st, c->map.image, cells, c->mcl.hyp_bits);
+            prof_mark(c, "k_mcl_compact");
+            cmk_mcl_compact(st, c->mcl.hyp_bits, (cells + 31u) / 32u, cells, c->mcl.hyp_list, c->mcl.hyp_list + CM_MCL_ONE_BLOCK, hy.words);
+        }
+        prof_mark(c, "k_mcl_hyp_recover");
+        cmk_mcl_hyp_recover(st, hy, words);
+    }
     prof_mark(c, "k_mcl_resample");
-    cmk_mcl_resample(st, src, dst, g.n, c->mcl.wts, c->mcl.cum, cm_mcl_splitmix64(base ^ (1ull << 63)), thr,
-                     (q.flags & CM_MCL_RESAMPLE_ALWAYS) ? 1u : 0u, words);
+    cmk_mcl_resample(st, src, dst, g, c->mcl.wts, c->mcl.cum, base, cm_mcl_splitmix64(base ^ (1ull << 63)), thr,
+                     (q.flags & CM_MCL_RESAMPLE_ALWAYS) ? 1u : 0u, words, hy);
+    if (hyp) {
+        HIP_TRY(c, hipMemcpyAsync(c->mcl.hyp_host, hy.words, CM_MCL_HYP_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(c->mcl.hyp_host + CM_MCL_HYP_WORDS, hy.out, static_cast<size_t>(hy.max_hyp) * sizeof(CmMclHypRecDev), hipMemcpyDeviceToHost, st));
+    }
     if (const int e = finish_call(c, c->mcl.host, words, CM_MCL_WORDS * sizeof(unsigned long long))) return e;
     const unsigned long long* const h = c->mcl.host;
     if (h[CM_MCL_W_BEST] >= g.n || h[CM_MCL_W_SW] < CM_MCL_WEIGHT_ONE || h[CM_MCL_W_SW2] == 0) return fail(c, CM_INTERNAL, "the info words of the update are not a result");
+    if (hyp) {
+        const unsigned long long* const w = c->mcl.hyp_host;
+        const cm_mcl_hyp_params& hp = c->mcl.hyp_params;
+        const uint64_t n_hyp = w[CM_MCL_HW_NHYP];
+        if (w[CM_MCL_HW_NBINS] < 1 || w[CM_MCL_HW_NBINS] > g.n || w[CM_MCL_HW_NCOMP] < 1 || w[CM_MCL_HW_NCOMP] > w[CM_MCL_HW_NBINS] ||
+            n_hyp != std::min<uint64_t>(w[CM_MCL_HW_NCOMP], hp.max_hyp) || w[CM_MCL_HW_NINJECT] > hp.inject_max)
+            return fail(c, CM_INTERNAL, "the words of the hypotheses are not a result");
+        cm_mcl_hyp_info& hi = c->mcl.hyp_info;
+        std::memset(&hi, 0, sizeof hi);
+        hi.gen = gen;
+        hi.n_bins = static_cast<uint32_t>(w[CM_MCL_HW_NBINS]);
+        hi.n_components = static_cast<uint32_t>(w[CM_MCL_HW_NCOMP]);
+        hi.n_hyp = static_cast<uint32_t>(n_hyp);
+        (void)cm_mcl_kld_bound(hi.n_bins, hp.kld_err, hp.kld_z, &hi.n_kld);
+        hi.n_inject = static_cast<uint32_t>(w[CM_MCL_HW_NINJECT]);
+        hi.n_free = static_cast<uint32_t>(w[CM_MCL_HW_NFREE]);
+        hi.sum_s = w[CM_MCL_HW_SUMS];
+        std::memcpy(&hi.w_avg, w + CM_MCL_HW_WAVG, 8);
+        std::memcpy(&hi.w_slow, w + CM_MCL_HW_WSLOW, 8);
+        std::memcpy(&hi.w_fast, w + CM_MCL_HW_WFAST, 8);
+        std::memcpy(&hi.p_inject, w + CM_MCL_HW_PINJECT, 8);
+        const double total = static_cast<double>(h[CM_MCL_W_SW]);
+        c->mcl.hyp_out.clear();                        // (capacity CM_MCL_HYP_MAX since the configure call: no allocation)
+        for (uint64_t k = 0; k < n_hyp; ++k) {
+            CmMclHypRecDev d;
+            std::memcpy(&d, w + CM_MCL_HYP_WORDS + k * hyp_rec_words, sizeof d);
+            cm_mcl_hyp o;
+            std::memset(&o, 0, sizeof o);
+            o.label = d.label;
+            o.n = static_cast<uint32_t>(d.n);
+            o.top = ~static_cast<uint32_t>(d.top);
+            o.sum_w = d.sum_w;
+            o.sum_wqx = static_cast<int64_t>(d.sum_wqx);
+            o.sum_wqy = static_cast<int64_t>(d.sum_wqy);
+            o.sum_wc = static_cast<int64_t>(d.sum_wc);
+            o.sum_ws = static_cast<int64_t>(d.sum_ws);
+            o.sum_wdxx = static_cast<int64_t>(d.sum_wdxx);
+            o.sum_wdyy = static_cast<int64_t>(d.sum_wdyy);
+            o.sum_wdxy = static_cast<int64_t>(d.sum_wdxy);
+            if (d.sum_w) {
+                const double sw = static_cast<double>(o.sum_w), den = sw * 1048576.0;
+                o.share = sw / total;
+                o.mean_x = (static_cast<double>(o.sum_wqx) / sw) / 1024.0;
+                o.mean_y = (static_cast<double>(o.sum_wqy) / sw) / 1024.0;
+                o.mean_yaw = std::atan2(static_cast<double>(o.sum_ws), static_cast<double>(o.sum_wc));
+                o.var_xx = static_cast<double>(o.sum_wdxx) / den;
+                o.var_yy = static_cast<double>(o.sum_wdyy) / den;
+                o.var_xy = static_cast<double>(o.sum_wdxy) / den;
+            }
+            c->mcl.hyp_out.push_back(o);
+        }
+    }
     if (beam) {
         const unsigned long long* const b = c->mcl.beam_host;
         cm_mcl_beam_info& bi = c->mcl.beam_info;
@@ -1316,6 +1477,7 @@ int map_mcl_update(cm_ctx* c) {
     r.var_yy = static_cast<double>(r.sum_wdyy) / den;
     r.var_xy = static_cast<double>(r.sum_wdxy) / den;
     c->mcl.beam_info_have = beam;
+    c->mcl.hyp_have = hyp;
     layer_mark_fresh(c->layers, LAYER_MCL, c->frame_serial);
     return CM_OK;
 }

@@ -231,6 +231,21 @@ struct MclLayer {
     DevBuf<unsigned char> beam_table;       // 2 * over_cells + 3 bytes
     DevBuf<unsigned long long> beam_counts; // CM_MCL_BEAM_COUNTS words
     PinnedBuf<unsigned long long> beam_host;        // the counts read back
+    // The hypotheses and the recovery (cm_map_mcl_hyp_configure, k_mcl_hyp_*): a second mode, off by default, allocated and
+    // freed like the beam model.
+    bool hyp_on = false;
+    bool hyp_have = false;           // the last update ran the mode: hyp_info and hyp_out are its
+    cm_mcl_hyp_params hyp_params{};
+    cm_mcl_hyp_info hyp_info{};
+    uint32_t hyp_cap_bits = 0;       // the table of bins has 1 << hyp_cap_bits slots
+    std::vector<cm_mcl_hyp> hyp_out; // the hypotheses of the last update (reserved by the configure call)
+    DevBuf<unsigned long long> hyp_keys;    // cap keys
+    DevBuf<uint32_t> hyp_slots;      // cap parent words, cap component words, then n_particles slot words
+    DevBuf<CmMclHypRecDev> hyp_rec;  // n_particles records, then CM_MCL_HYP_MAX chosen ones
+    DevBuf<unsigned long long> hyp_words;   // CM_MCL_HYP_WORDS
+    DevBuf<uint32_t> hyp_bits;       // the free cells' bitmap (nx * ny bits)
+    DevBuf<uint32_t> hyp_list;       // CM_MCL_ONE_BLOCK block counts, then nx * ny list entries
+    PinnedBuf<unsigned long long> hyp_host; // CM_MCL_HYP_WORDS words, then the chosen records read back
 };
 
 // Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses, configured by cm_map_cast_configure
@@ -392,6 +407,7 @@ struct cm_ctx {
     DevBuf<double> box_sums;             // per listed chunk: CM_BOX_MAX_ANGLES sums
     uint32_t box_split = CM_BOX_SPLIT;   // (CM_BOX_SPLIT in the environment: the measurement of scripts/box_cost.py)
     uint32_t mcl_beam_walks = CM_MCL_BEAM_WALKS;     // (CM_MCL_BEAM_WALKS in the environment: scripts/map_mcl_beam_cost.py)
+    uint32_t mcl_hyp_agg = 1;        // (CM_MCL_HYP_NO_AGG=1 in the environment sets 0: scripts/map_mcl_hyp_cost.py)
 
     // 2-D grid map of the frame (cm_kernels_grid.hip), on request after a frame: it reads the frame's clouds in place (d_frame,
     // frame_mask, gmask) and writes a table and an image of its own — no frame reads them — allocated by the first request and
@@ -586,6 +602,8 @@ int map_mcl_update(cm_ctx* c);
 // The beam model of the localisation layer: its memory and table (nullptr: back to the field score); the weights and the
 // infos go stale, the particles and gen stay.
 int map_mcl_beam_configure(cm_ctx* c, const cm_mcl_beam_params* q);
+// The hypotheses mode: all its memory; nullptr gives it back. The averages start at 0.0.
+int map_mcl_hyp_configure(cm_ctx* c, const cm_mcl_hyp_params* q);
 // The cast layer behind the cost layer. map_cast_configure: room for q's rays over the map's window, the bearings (nullptr:
 // evenly spaced) and the direction table uploaded (q nullptr: the buffers go). map_cast_evaluate runs a call that cm_api.cpp has
 // checked: n poses on the host, or, with host_poses nullptr, the localisation layer's n particles in place.

@@ -567,6 +567,51 @@ struct CmMclMoveDev {
     float sc_a, sc_b, sc_yaw;
     unsigned long long base;
 };
+// The hypotheses and the recovery of the localisation layer (k_mcl_hyp_*). The bins of the particles live in an
+// open-addressing table of `cap` 64-bit keys (a power of two >= 4 n_particles, CM_MCL_HYP_EMPTY where free), with one parent
+// word and one component word per slot; a component's record is CmMclHypRecDev, n_particles of them at most. The mode's
+// CM_MCL_HYP_WORDS 64-bit words on the device: the first three are those of the ordered compaction of the free cells (where
+// cmk_mcl_compact and k_mcl_init_uniform expect them), then the counts, sum_s and the four doubles of the recovery as bit
+// patterns, all zero before an update; the last two are the slow and the fast average, which live from update to update.
+#define CM_MCL_HYP_MAX_DEV 64u
+#define CM_MCL_HYP_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define CM_MCL_HW_NFREE 0
+#define CM_MCL_HW_NBINS 3
+#define CM_MCL_HW_NCOMP 4
+#define CM_MCL_HW_NHYP 5
+#define CM_MCL_HW_SUMS 6
+#define CM_MCL_HW_WAVG 7
+#define CM_MCL_HW_WSLOW 8
+#define CM_MCL_HW_WFAST 9
+#define CM_MCL_HW_PINJECT 10
+#define CM_MCL_HW_NINJECT 11
+#define CM_MCL_HW_CLEARED 12           // words [0, 12) are zero before an update
+#define CM_MCL_HW_STATE_SLOW 12
+#define CM_MCL_HW_STATE_FAST 13
+#define CM_MCL_HYP_WORDS 16
+struct CmMclHypRecDev {                // the integer part of cm_mcl_hyp
+    unsigned long long label;
+    unsigned long long n;
+    unsigned long long sum_w, sum_wqx, sum_wqy, sum_wc, sum_ws;
+    unsigned long long top;            // W << 32 | ~p of the heaviest particle
+    unsigned long long sum_wdxx, sum_wdyy, sum_wdxy;
+};
+struct CmMclHypDev {
+    uint32_t on;                       // 0: the mode is off, nothing below is read
+    uint32_t n;                        // particles
+    uint32_t cap_bits;                 // the table has 1 << cap_bits slots
+    uint32_t bin_q, heading_bits, max_hyp, inject_max;
+    uint32_t agg;                      // lanes of a wave that share a component combine before the atomics (0: a measurement's switch)
+    double a_slow, a_fast;
+    unsigned long long* keys;          // cap keys
+    uint32_t* parent;                  // cap parent words
+    uint32_t* comp;                    // cap component numbers
+    uint32_t* slot;                    // n: the slot of every particle
+    CmMclHypRecDev* rec;               // n records
+    CmMclHypRecDev* out;               // CM_MCL_HYP_MAX_DEV records: the chosen ones in order
+    unsigned long long* words;         // CM_MCL_HYP_WORDS
+    const uint32_t* free_list;         // the free cells of the map's image in entry order (inject_max > 0)
+};
 
 // Cast layer behind the cost layer (cm_kernels_cast.hip): expected ranges from many poses in the map. k_cast_rays gives one
 // lane one ray, CM_CAST_BLOCK threads per workgroup, the grid sized to the device with a stride over the rays, so that a wave

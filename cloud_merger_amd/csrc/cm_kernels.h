@@ -322,8 +322,20 @@ void cmk_mcl_best(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, unsi
 void cmk_mcl_weights(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, double beta, const float* dirs, CmMclWeightDev* wts,
                      unsigned long long* words);
 void cmk_mcl_spread(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, const CmMclWeightDev* wts, unsigned long long* words);
-void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, uint32_t n, const CmMclWeightDev* wts, unsigned long long* cum,
-                      unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words);
+// base: the update's draw base; hy: the hypotheses mode (hy.on == 0: off, the step is the layer's own step 10).
+void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, const CmMclDev& g, const CmMclWeightDev* wts, unsigned long long* cum,
+                      unsigned long long base, unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words, const CmMclHypDev& hy);
+// The hypotheses mode (CmMclHypDev, cm_device.h), between cmk_mcl_spread and cmk_mcl_resample, over the particles and the
+// weights of the update. Before cmk_mcl_hyp_bins: hy.keys all CM_MCL_HYP_EMPTY and hy.words[0 .. CM_MCL_HW_CLEARED) zero. With
+// hy.inject_max > 0 the free cells' compaction goes into hy.words and hy.free_list before cmk_mcl_hyp_recover, which reads
+// n_beams from the layer's words. cmk_mcl_hyp_flatten is two launches: the roots' numbers, then every slot's.
+void cmk_mcl_hyp_bins(hipStream_t s, const CmMclParticleDev* parts, const CmMclHypDev& hy);
+void cmk_mcl_hyp_link(hipStream_t s, const CmMclHypDev& hy);
+void cmk_mcl_hyp_flatten(hipStream_t s, const CmMclHypDev& hy);
+void cmk_mcl_hyp_sums(hipStream_t s, const CmMclParticleDev* parts, const CmMclWeightDev* wts, const float* dirs, const CmMclHypDev& hy);
+void cmk_mcl_hyp_spread(hipStream_t s, const CmMclParticleDev* parts, const CmMclWeightDev* wts, const CmMclHypDev& hy);
+void cmk_mcl_hyp_pick(hipStream_t s, const CmMclHypDev& hy);
+void cmk_mcl_hyp_recover(hipStream_t s, const CmMclHypDev& hy, const unsigned long long* layer_words);
 // The image of a state table (the map's step 8), for cm_map_load: (logodds, n_obs) per cell into one byte per cell.
 void cmk_map_image(hipStream_t s, const void* state, uint32_t n_cells, int l_free, int l_occ, void* image);
 

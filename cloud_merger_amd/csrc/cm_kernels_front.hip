@@ -39,6 +39,7 @@
 
 #include "cm_device.h"
 #include "cm_kernels.h"
+#include "cm_search.hpp"
 #define CM_FRONT_FN __device__ __forceinline__
 #include "cm_front_score.hpp"
 
@@ -51,37 +52,11 @@ constexpr uint32_t kNoLabel = 0xFFFFu;                 // in LDS: no frontier ce
 static_assert(sizeof(CmFrontEntryDev) == 40, "cm_frontier is 40 bytes");
 static_assert(CM_FRONT_BLOCK == CM_FRONT_TILE * CM_FRONT_TILE && CM_FRONT_BLOCK % 64 == 0, "one thread per cell of a tile");
 
-__device__ __forceinline__ uint32_t front_load(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-
-// The root of c's tree. Every word of a frontier cell holds a cell of the same component that is not above it, a root holds
-// itself: the walk strictly decreases and ends.
-__device__ __forceinline__ uint32_t front_find(const uint32_t* parent, uint32_t c) {
-    uint32_t p = front_load(parent + c);
-    while (p != c) {
-        c = p;
-        p = front_load(parent + c);
-    }
-    return c;
-}
-
-// Unites the trees of a and b. The larger root's word falls to the smaller root; if the word was no root any more (another
-// thread hung it elsewhere in the meantime), what it held still has to meet the smaller root, and the larger of the two
-// cells in hand has strictly fallen.
-__device__ __forceinline__ void front_unite(uint32_t* parent, uint32_t a, uint32_t b) {
-    a = front_find(parent, a);
-    b = front_find(parent, b);
-    while (a != b) {
-        if (a < b) {
-            const uint32_t t = a;
-            a = b;
-            b = t;
-        }
-        const uint32_t old = atomicMin(parent + a, b);
-        if (old == a) break;
-        a = front_find(parent, old);
-        b = front_find(parent, b);
-    }
-}
+// The union-find on the label words (every word of a frontier cell holds a cell of the same component that is not above
+// it): cm_search.hpp's, which the localisation layer's hypotheses share.
+__device__ __forceinline__ uint32_t front_load(const uint32_t* p) { return cm_uf_load(p); }
+__device__ __forceinline__ uint32_t front_find(const uint32_t* parent, uint32_t c) { return cm_uf_find(parent, c); }
+__device__ __forceinline__ void front_unite(uint32_t* parent, uint32_t a, uint32_t b) { cm_uf_unite(parent, a, b); }
 
 __global__ __launch_bounds__(CM_FRONT_BLOCK) void k_front_local(const signed char* __restrict__ image, const unsigned char* __restrict__ cost,
                                                                 CmFrontDev g, uint32_t* __restrict__ labels, uint32_t* __restrict__ size,

@@ -37,7 +37,21 @@
 //   k_mcl_cum        one workgroup: the inclusive prefix sum of W in particle order, and the resampling decision, taken here
 //                    on the device from the sums: n_eff in double with the host's three operations.
 //   k_mcl_gather     one thread per new particle: a binary search in the prefix sums, the copy into the second buffer; without
-//                    resampling it sets the parents of the first.
+//                    resampling it sets the parents of the first. Under the hypotheses mode the last n_inject new particles are
+//                    k_mcl_init_uniform's body over the mode's free list instead.
+// The hypotheses mode (cm_map_mcl_hyp_configure), between k_mcl_spread and k_mcl_cum:
+//   k_mcl_hyp_bins   one lane per particle: its bin's 64-bit key goes into an open-addressing table by atomicCAS (at most a
+//                    quarter full); the lane that took a free slot makes it a root; the particle keeps its slot.
+//   k_mcl_hyp_link   one lane per slot: the 13 neighbour keys of one half-space are looked up and united with cm_search.hpp's
+//                    lock-free union-find (the frontier layer's), headings wrapping.
+//   k_mcl_hyp_roots, k_mcl_hyp_flatten   a root takes a component number (one atomic per workgroup) and clears its record;
+//                    then every slot takes its root's number and its key falls into the record's label (atomicMin).
+//   k_mcl_hyp_sums, k_mcl_hyp_spread   one lane per particle: the component's n, five weighted sums and top (one 64-bit
+//                    atomicMax of W << 32 | ~p), then the spread sums about its integer mean. Lanes of a wave that share a
+//                    component reduce among themselves and one lane sends the atomics (wave_by_component).
+//   k_mcl_hyp_pick   one workgroup: the first max_hyp records by (sum_w descending, label ascending).
+//   k_mcl_hyp_recover   one thread: the average score, its slow and fast averages and the injection count, in double with
+//                    every operation rounded on its own.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -202,11 +216,8 @@ __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_pose(CmMclMoveDev m, 
     parts[p] = q;
 }
 
-__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_uniform(CmMclDev g, u64 base, const uint32_t* __restrict__ list, const u64* __restrict__ words,
-                                                                   CmMclParticleDev* __restrict__ parts) {
-    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
-    if (p >= g.n) return;
-    const u64 n_free = words[CM_MCL_W_NCELLS];         // (>= 1: the host looked)
+// Step 4 for particle p over the n_free >= 1 free cells of list: its x, y, h, parent = p and acc = 0.
+__device__ __forceinline__ CmMclParticleDev uniform_particle(const CmMclDev& g, u64 base, uint32_t p, const uint32_t* __restrict__ list, u64 n_free) {
     const uint32_t c = list[__umul64hi(cm_mcl_draw(base, p, 0u), n_free)];
     const int ix = static_cast<int>(c % g.nx), iy = static_cast<int>(c / g.nx);
     const float ux = __fmul_rn(static_cast<float>(cm_mcl_draw(base, p, 1u) >> 40), 0x1p-24f);
@@ -217,7 +228,14 @@ __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_uniform(CmMclDev g, u
     q.h = static_cast<uint32_t>(cm_mcl_draw(base, p, 3u) >> 32);
     q.parent = p;
     q.acc = 0ull;
-    parts[p] = q;
+    return q;
+}
+
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_init_uniform(CmMclDev g, u64 base, const uint32_t* __restrict__ list, const u64* __restrict__ words,
+                                                                   CmMclParticleDev* __restrict__ parts) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (p >= g.n) return;
+    parts[p] = uniform_particle(g, base, p, list, words[CM_MCL_W_NCELLS]);      // (>= 1 free cell: the host looked)
 }
 
 __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_predict(CmMclMoveDev m, uint32_t n, const float2* __restrict__ dirs,
@@ -505,9 +523,305 @@ __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_spread(const CmMclParticle
     block_add<3>(v, words, slot);
 }
 
+// ---- the hypotheses and the recovery (cm_map_mcl_hyp_configure) -------------------------------------------------
+// Every output is a function of keys and integer sums: which slot a key lands in, which slot is a root and which number a
+// component gets depend on the order of arrival and show nowhere.
+__device__ __forceinline__ u64 wave_max(u64 v) {
+    for (int m = 1; m < 64; m <<= 1) {
+        const u64 o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+constexpr long long kHypOff = 1ll << 24;               // |bx|, |by| <= 2^24: |q| <= 2^30 and bin_q >= 64
+
+__device__ __forceinline__ u64 hyp_key(long long by, long long bx, uint32_t bh) {
+    return (static_cast<u64>(by + kHypOff) << 34) | (static_cast<u64>(bx + kHypOff) << 8) | bh;
+}
+__device__ __forceinline__ uint32_t hyp_hash(u64 key, uint32_t cap_bits) { return static_cast<uint32_t>((key * 0x9E3779B97F4A7C15ull) >> (64u - cap_bits)); }
+
+// H1: one lane per particle inserts its key; the lane whose compare-and-swap took a free slot makes it a tree of its own.
+// The table is at most a quarter full, so a probe always ends.
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_hyp_bins(const CmMclParticleDev* __restrict__ parts, CmMclHypDev hy) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    const uint32_t mask = (1u << hy.cap_bits) - 1u;
+    bool won = false;
+    if (p < hy.n) {
+        const CmMclParticleDev q = parts[p];
+        const long long bx = floor_div(quant_of(q.x), hy.bin_q), by = floor_div(quant_of(q.y), hy.bin_q);
+        const uint32_t bh = hy.heading_bits ? q.h >> (32u - hy.heading_bits) : 0u;
+        const u64 key = hyp_key(by, bx, bh);
+        uint32_t s = hyp_hash(key, hy.cap_bits);
+        for (;;) {
+            const u64 old = atomicCAS(hy.keys + s, CM_MCL_HYP_EMPTY, key);
+            if (old == CM_MCL_HYP_EMPTY) {
+                won = true;
+                hy.parent[s] = s;
+                break;
+            }
+            if (old == key) break;
+            s = (s + 1u) & mask;
+        }
+        hy.slot[p] = s;
+    }
+    const u64 m = __ballot(won);
+    if (m && (threadIdx.x & 63u) == 0u) atomicAdd(hy.words + CM_MCL_HW_NBINS, static_cast<u64>(__popcll(m)));
+}
+
+// H3: one lane per occupied slot looks up the 13 neighbour keys of one half-space ((dy, dx, dh) after (0, 0, 0) in that
+// order; the other half is covered from the neighbour's side) and unites. Headings wrap modulo 2^heading_bits.
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_hyp_link(CmMclHypDev hy) {
+    const uint32_t s = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    const uint32_t mask = (1u << hy.cap_bits) - 1u;
+    if (s > mask) return;
+    const u64 key = hy.keys[s];
+    if (key == CM_MCL_HYP_EMPTY) return;
+    const uint32_t hmask = (1u << hy.heading_bits) - 1u;
+    const uint32_t bh = static_cast<uint32_t>(key & 0xFFu);
+    const long long bx = static_cast<long long>((key >> 8) & 0x3FFFFFFull) - kHypOff, by = static_cast<long long>(key >> 34) - kHypOff;
+    for (int dy = 0; dy <= 1; ++dy)
+        for (int dx = -1; dx <= 1; ++dx)
+            for (int dh = -1; dh <= 1; ++dh) {
+                if (dy == 0 && (dx < 0 || (dx == 0 && dh <= 0))) continue;
+                const long long ny = by + dy, nx = bx + dx;
+                if (ny > kHypOff || nx > kHypOff || nx < -kHypOff) continue;   // (no particle has such a bin)
+                const u64 nkey = hyp_key(ny, nx, (bh + static_cast<uint32_t>(dh)) & hmask);
+                if (nkey == key) continue;
+                uint32_t t = hyp_hash(nkey, hy.cap_bits);
+                for (;;) {
+                    const u64 k = hy.keys[t];
+                    if (k == nkey) {
+                        cm_uf_unite(hy.parent, s, t);
+                        break;
+                    }
+                    if (k == CM_MCL_HYP_EMPTY) break;
+                    t = (t + 1u) & mask;
+                }
+            }
+}
+
+// One lane per slot: a root takes the next component number (one atomic per workgroup) and clears its record.
+__global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_hyp_roots(CmMclHypDev hy) {
+    __shared__ uint32_t s_w[CM_MCL_ONE_BLOCK / 64];
+    __shared__ uint32_t s_base;
+    const uint32_t s = blockIdx.x * CM_MCL_ONE_BLOCK + threadIdx.x;
+    const uint32_t mask = (1u << hy.cap_bits) - 1u;
+    const bool root = s <= mask && hy.keys[s] != CM_MCL_HYP_EMPTY && hy.parent[s] == s;
+    const uint32_t incl = block_scan<CM_MCL_ONE_BLOCK / 64>(root ? 1u : 0u, s_w);
+    if (threadIdx.x == CM_MCL_ONE_BLOCK - 1u) s_base = incl ? static_cast<uint32_t>(atomicAdd(hy.words + CM_MCL_HW_NCOMP, static_cast<u64>(incl))) : 0u;
+    __syncthreads();
+    if (!root) return;
+    const uint32_t c = s_base + incl - 1u;             // (< n: a component holds a particle)
+    hy.comp[s] = c;
+    CmMclHypRecDev r;
+    r.label = CM_MCL_HYP_EMPTY;
+    r.n = r.sum_w = r.sum_wqx = r.sum_wqy = r.sum_wc = r.sum_ws = r.top = r.sum_wdxx = r.sum_wdyy = r.sum_wdxy = 0ull;
+    hy.rec[c] = r;
+}
+
+// One lane per occupied slot: its root's number becomes its own, and its key falls into the component's label.
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_hyp_flatten(CmMclHypDev hy) {
+    const uint32_t s = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    if (s >= (1u << hy.cap_bits)) return;
+    const u64 key = hy.keys[s];
+    if (key == CM_MCL_HYP_EMPTY) return;
+    const uint32_t r = cm_uf_find(hy.parent, s);
+    const uint32_t c = hy.comp[r];                     // (written by k_mcl_hyp_roots; only roots are read here)
+    if (r != s) hy.comp[s] = c;
+    u64* const label = &hy.rec[c].label;
+    if (key < __hip_atomic_load(label, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(label, key);
+}
+
+// Lanes of a wave that share a component combine their K sums (and the largest `top`) before one of them calls issue(c,
+// sums, top): in a converged belief every particle adds to one record. Per round the first lane still waiting names the
+// component; a lane alone in its component issues its own values without a reduction. Every lane of the wave calls this.
+template <int K, class F>
+__device__ __forceinline__ void wave_by_component(bool active, uint32_t c, const u64 (&v)[K], u64 top, bool agg, F&& issue) {
+    if (!agg) {
+        if (active) issue(c, v, top);
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    u64 left = __ballot(active);
+    while (left) {                                     // (wave-uniform: at most one round per distinct component of the wave)
+        const uint32_t lead = static_cast<uint32_t>(__ffsll(static_cast<long long>(left))) - 1u;
+        const uint32_t c0 = static_cast<uint32_t>(__shfl(static_cast<int>(c), static_cast<int>(lead)));
+        const bool same = active && c == c0;
+        const u64 m = __ballot(same);
+        if (__popcll(m) == 1) {
+            if (lane == lead) issue(c, v, top);
+        } else {
+            u64 t[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) t[k] = wave_sum(same ? v[k] : 0ull);
+            const u64 tp = wave_max(same ? top : 0ull);
+            if (lane == lead) issue(c0, t, tp);
+        }
+        if (same) active = false;
+        left &= ~m;
+    }
+}
+
+// H4: one lane per particle; n, the five weighted sums and top of its component, and the sum of the scores (R1).
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_hyp_sums(const CmMclParticleDev* __restrict__ parts, const CmMclWeightDev* __restrict__ wts,
+                                                               const float2* __restrict__ dirs, CmMclHypDev hy) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    const bool in = p < hy.n;
+    u64 v[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, top = 0ull, score = 0ull;
+    uint32_t c = 0u;
+    if (in) {
+        const CmMclParticleDev q = parts[p];
+        const CmMclWeightDev w = wts[p];
+        const float2 e = dirs[heading_entry(q.h)];
+        const long long ci = static_cast<long long>(rintf(__fmul_rn(e.x, 32768.0f))), si = static_cast<long long>(rintf(__fmul_rn(e.y, 32768.0f)));
+        const long long sw = static_cast<long long>(w.weight);
+        c = hy.comp[hy.slot[p]];
+        v[0] = 1ull;
+        v[1] = w.weight;
+        v[2] = static_cast<u64>(sw * quant_of(q.x));   // (signed sums wrap as two's complement: the total is exact)
+        v[3] = static_cast<u64>(sw * quant_of(q.y));
+        v[4] = static_cast<u64>(sw * ci);
+        v[5] = static_cast<u64>(sw * si);
+        top = (static_cast<u64>(w.weight) << 32) | static_cast<u64>(~p);
+        score = w.score;
+    }
+    score = wave_sum(score);
+    if ((threadIdx.x & 63u) == 0u && score) atomicAdd(hy.words + CM_MCL_HW_SUMS, score);
+    CmMclHypRecDev* const rec = hy.rec;
+    wave_by_component<6>(in, c, v, top, hy.agg != 0u, [rec](uint32_t cc, const u64 (&t)[6], u64 tp) {
+        CmMclHypRecDev* const r = rec + cc;
+        atomicAdd(&r->n, t[0]);
+        if (t[1]) atomicAdd(&r->sum_w, t[1]);
+        if (t[2]) atomicAdd(&r->sum_wqx, t[2]);
+        if (t[3]) atomicAdd(&r->sum_wqy, t[3]);
+        if (t[4]) atomicAdd(&r->sum_wc, t[4]);
+        if (t[5]) atomicAdd(&r->sum_ws, t[5]);
+        atomicMax(&r->top, tp);
+    });
+}
+
+// H4's spread sums about the component's integer mean.
+__global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_hyp_spread(const CmMclParticleDev* __restrict__ parts, const CmMclWeightDev* __restrict__ wts,
+                                                                 CmMclHypDev hy) {
+    const uint32_t p = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
+    const bool in = p < hy.n;
+    u64 v[3] = {0ull, 0ull, 0ull};
+    uint32_t c = 0u;
+    bool any = false;
+    if (in) {
+        c = hy.comp[hy.slot[p]];
+        const long long w = wts[p].weight;
+        const u64 sum_w = hy.rec[c].sum_w;
+        if (w && sum_w) {                              // (a component of weight 0 has zero spread sums)
+            const long long mx = floor_div(static_cast<long long>(hy.rec[c].sum_wqx), sum_w), my = floor_div(static_cast<long long>(hy.rec[c].sum_wqy), sum_w);
+            const auto clamp16 = [](long long d) { return d < -32768 ? -32768ll : d > 32767 ? 32767ll : d; };
+            const long long dx = clamp16(quant_of(parts[p].x) - mx), dy = clamp16(quant_of(parts[p].y) - my);
+            v[0] = static_cast<u64>(w * dx * dx);
+            v[1] = static_cast<u64>(w * dy * dy);
+            v[2] = static_cast<u64>(w * dx * dy);
+            any = (v[0] | v[1] | v[2]) != 0ull;
+        }
+    }
+    CmMclHypRecDev* const rec = hy.rec;
+    wave_by_component<3>(any, c, v, 0ull, hy.agg != 0u, [rec](uint32_t cc, const u64 (&t)[3], u64) {
+        CmMclHypRecDev* const r = rec + cc;
+        if (t[0]) atomicAdd(&r->sum_wdxx, t[0]);
+        if (t[1]) atomicAdd(&r->sum_wdyy, t[1]);
+        if (t[2]) atomicAdd(&r->sum_wdxy, t[2]);
+    });
+}
+
+// H5: one workgroup picks the first min(n_components, max_hyp) records by sum_w descending, ties by label ascending (labels
+// are distinct: the order is total). A thread keeps the best record of its strip that comes after the last one chosen; per
+// round the workgroup reduces the threads' candidates and the thread that held the winner looks for its next.
+__global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_hyp_pick(CmMclHypDev hy) {
+    __shared__ u64 s_sw[CM_MCL_ONE_BLOCK / 64], s_label[CM_MCL_ONE_BLOCK / 64];
+    __shared__ uint32_t s_index[CM_MCL_ONE_BLOCK / 64];
+    __shared__ u64 s_win_sw, s_win_label;
+    __shared__ uint32_t s_win;
+    constexpr uint32_t kNoRec = 0xFFFFFFFFu;
+    const uint32_t n_comp = static_cast<uint32_t>(hy.words[CM_MCL_HW_NCOMP]);
+    const uint32_t n_hyp = n_comp < hy.max_hyp ? n_comp : hy.max_hyp;
+    const auto before = [](u64 sw_a, u64 label_a, u64 sw_b, u64 label_b) { return sw_a > sw_b || (sw_a == sw_b && label_a < label_b); };
+    u64 sw = 0ull, label = 0ull;
+    uint32_t index = kNoRec;
+    // the best of the strip that comes after (last_sw, last_label); first: everything counts
+    const auto rescan = [&](bool first, u64 last_sw, u64 last_label) {
+        index = kNoRec;
+        for (uint32_t i = threadIdx.x; i < n_comp; i += CM_MCL_ONE_BLOCK) {
+            const u64 a = hy.rec[i].sum_w, l = hy.rec[i].label;
+            if (!first && !before(last_sw, last_label, a, l)) continue;
+            if (index == kNoRec || before(a, l, sw, label)) {
+                sw = a;
+                label = l;
+                index = i;
+            }
+        }
+    };
+    rescan(true, 0ull, 0ull);
+    for (uint32_t r = 0; r < n_hyp; ++r) {
+        u64 bsw = sw, bl = label;
+        uint32_t bi = index;
+        const auto fold = [&](u64 osw, u64 ol, uint32_t oi) {
+            if (oi != kNoRec && (bi == kNoRec || before(osw, ol, bsw, bl))) {
+                bsw = osw;
+                bl = ol;
+                bi = oi;
+            }
+        };
+        for (int m = 1; m < 64; m <<= 1) fold(__shfl_xor(bsw, m), __shfl_xor(bl, m), static_cast<uint32_t>(__shfl_xor(static_cast<int>(bi), m)));
+        if ((threadIdx.x & 63u) == 0u) {
+            s_sw[threadIdx.x >> 6] = bsw;
+            s_label[threadIdx.x >> 6] = bl;
+            s_index[threadIdx.x >> 6] = bi;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0u) {
+            for (uint32_t w = 1; w < CM_MCL_ONE_BLOCK / 64; ++w) fold(s_sw[w], s_label[w], s_index[w]);
+            s_win = bi;                                // (r < n_comp: there is one)
+            s_win_sw = bsw;
+            s_win_label = bl;
+            if (bi != kNoRec) hy.out[r] = hy.rec[bi];
+        }
+        __syncthreads();
+        if (index != kNoRec && index == s_win) rescan(false, s_win_sw, s_win_label);
+        __syncthreads();                               // (s_win is read before the next round writes it)
+    }
+    if (threadIdx.x == 0u) hy.words[CM_MCL_HW_NHYP] = n_hyp;
+}
+
+// R1 to R3 by one thread, in double with every operation rounded on its own, as k_mcl_cum computes n_eff.
+__global__ void k_mcl_hyp_recover(CmMclHypDev hy, const u64* __restrict__ layer_words) {
+    if (threadIdx.x != 0u || blockIdx.x != 0u) return;
+    u64* const hw = hy.words;
+    const u64 n_beams = layer_words[CM_MCL_W_NBEAMS];
+    double slow = __builtin_bit_cast(double, hw[CM_MCL_HW_STATE_SLOW]), fast = __builtin_bit_cast(double, hw[CM_MCL_HW_STATE_FAST]);
+    double w_avg = 0.0, p = 0.0;
+    uint32_t n_inject = 0u;
+    if (n_beams) {
+        const double den = __dmul_rn(__dmul_rn(static_cast<double>(hy.n), __ull2double_rn(n_beams)), 255.0);
+        w_avg = __ddiv_rn(__ull2double_rn(hw[CM_MCL_HW_SUMS]), den);
+        slow = slow == 0.0 ? w_avg : __dadd_rn(slow, __dmul_rn(hy.a_slow, __dsub_rn(w_avg, slow)));
+        fast = fast == 0.0 ? w_avg : __dadd_rn(fast, __dmul_rn(hy.a_fast, __dsub_rn(w_avg, fast)));
+        if (slow > 0.0 && fast < slow) p = __dsub_rn(1.0, __ddiv_rn(fast, slow));
+        const uint32_t want = static_cast<uint32_t>(floor(__dmul_rn(p, static_cast<double>(hy.n))));       // (0 <= p <= 1: at most n)
+        n_inject = want < hy.inject_max ? want : hy.inject_max;
+        if (hw[CM_MCL_HW_NFREE] == 0ull) n_inject = 0u;                // (inject_max == 0 builds no list: n_free stays 0)
+    }
+    hw[CM_MCL_HW_STATE_SLOW] = __builtin_bit_cast(u64, slow);
+    hw[CM_MCL_HW_STATE_FAST] = __builtin_bit_cast(u64, fast);
+    hw[CM_MCL_HW_WAVG] = __builtin_bit_cast(u64, w_avg);
+    hw[CM_MCL_HW_WSLOW] = __builtin_bit_cast(u64, slow);
+    hw[CM_MCL_HW_WFAST] = __builtin_bit_cast(u64, fast);
+    hw[CM_MCL_HW_PINJECT] = __builtin_bit_cast(u64, p);
+    hw[CM_MCL_HW_NINJECT] = n_inject;
+}
+
 // ---- resampling ----------------------------------------------------------------------------------------------------------------
+// hyp_words: the words of the hypotheses mode, or nullptr with the mode off; an injection (R4) resamples whatever n_eff says.
 __global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_cum(const CmMclWeightDev* __restrict__ wts, uint32_t n, double thr, uint32_t always,
-                                                              u64* __restrict__ cum, u64* __restrict__ words) {
+                                                              u64* __restrict__ cum, u64* __restrict__ words, const u64* __restrict__ hyp_words) {
     __shared__ u64 s_w[CM_MCL_ONE_BLOCK / 64];
     const uint32_t per = (n + CM_MCL_ONE_BLOCK - 1u) / CM_MCL_ONE_BLOCK;
     const uint32_t lo = threadIdx.x * per < n ? threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
@@ -521,20 +835,31 @@ __global__ __launch_bounds__(CM_MCL_ONE_BLOCK) void k_mcl_cum(const CmMclWeightD
     if (threadIdx.x == 0u) {
         const double sw = __ull2double_rn(words[CM_MCL_W_SW]), sw2 = __ull2double_rn(words[CM_MCL_W_SW2]);
         const double n_eff = __ddiv_rn(__dmul_rn(sw, sw), sw2);
-        words[CM_MCL_W_RESAMPLED] = (always || n_eff < thr) ? 1ull : 0ull;
+        const bool inject = hyp_words && hyp_words[CM_MCL_HW_NINJECT] != 0ull;
+        words[CM_MCL_W_RESAMPLED] = (always || n_eff < thr || inject) ? 1ull : 0ull;
     }
 }
 
+// hy.on: the last n_inject new particles (R4) are step 4 over hy.free_list with the update's own draws; the others share T.
 __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_gather(CmMclParticleDev* __restrict__ src, CmMclParticleDev* __restrict__ dst, uint32_t n,
-                                                             const u64* __restrict__ cum, u64 r_draw, const u64* __restrict__ words) {
+                                                             const u64* __restrict__ cum, u64 r_draw, const u64* __restrict__ words, CmMclDev g,
+                                                             u64 base, CmMclHypDev hy) {
     const uint32_t j = blockIdx.x * CM_MCL_BLOCK + threadIdx.x;
     if (j >= n) return;
     if (!words[CM_MCL_W_RESAMPLED]) {
         src[j].parent = j;
         return;
     }
+    const uint32_t n_inject = hy.on ? static_cast<uint32_t>(hy.words[CM_MCL_HW_NINJECT]) : 0u;       // (<= inject_max <= n - 1)
+    const uint32_t m = n - n_inject;
+    if (j >= m) {
+        CmMclParticleDev o = uniform_particle(g, base, j, hy.free_list, hy.words[CM_MCL_HW_NFREE]);      // (n_free >= 1 where n_inject > 0)
+        o.parent = 0xFFFFFFFFu;
+        dst[j] = o;
+        return;
+    }
     const u64 T = words[CM_MCL_W_SW];
-    const u64 t = (static_cast<u64>(j) * T + __umul64hi(r_draw, T)) / n;          // (< T = cum[n - 1]: there is a p)
+    const u64 t = (static_cast<u64>(j) * T + __umul64hi(r_draw, T)) / m;          // (< T = cum[n - 1]: there is a p)
     uint32_t lo = 0u, hi = n - 1u;
     while (lo < hi) {                                  // the smallest p with cum[p] > t
         const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -553,6 +878,13 @@ __global__ __launch_bounds__(CM_MCL_BLOCK) void k_mcl_gather(CmMclParticleDev* _
 bool mcl_ok(const CmMclDev& g) {
     return g.nx >= 1 && g.ny >= 1 && static_cast<uint64_t>(g.nx) * g.ny <= (1u << 22) && g.n >= 1 && g.n <= CM_MCL_MAX_PARTICLES_DEV && g.max_beams >= 1 &&
            g.max_beams <= CM_MCL_MAX_BEAMS_DEV && g.range >= 1 && g.range <= CM_MCL_MAX_RANGE_DEV && g.side == 2u * g.range + 1u;
+}
+
+// The table holds four slots per particle at least (a probe ends), the records fit and an injection leaves a particle.
+bool hyp_ok(const CmMclHypDev& hy, uint32_t n) {
+    return hy.on && hy.n == n && n >= 1 && n <= CM_MCL_MAX_PARTICLES_DEV && hy.cap_bits >= 6 && hy.cap_bits <= 20 && (1ull << hy.cap_bits) >= 4ull * n &&
+           hy.bin_q >= 64 && hy.bin_q <= (1u << 20) && hy.heading_bits <= 8 && hy.max_hyp >= 1 && hy.max_hyp <= CM_MCL_HYP_MAX_DEV && hy.inject_max < n &&
+           hy.keys && hy.parent && hy.comp && hy.slot && hy.rec && hy.out && hy.words && (hy.inject_max == 0 || hy.free_list);
 }
 
 // Workgroups of k_mcl_score: enough to fill the device a few times over, never more than the particles need.
@@ -639,9 +971,47 @@ void cmk_mcl_spread(hipStream_t s, const CmMclParticleDev* parts, uint32_t n, co
     hipLaunchKernelGGL(k_mcl_spread, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, n, wts, words);
 }
 
-void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, uint32_t n, const CmMclWeightDev* wts, unsigned long long* cum,
-                      unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words) {
-    if (n == 0 || n > CM_MCL_MAX_PARTICLES_DEV) return;
-    hipLaunchKernelGGL(k_mcl_cum, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, wts, n, thr, always, cum, words);
-    hipLaunchKernelGGL(k_mcl_gather, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, src, dst, n, cum, r_draw, words);
+void cmk_mcl_resample(hipStream_t s, CmMclParticleDev* src, CmMclParticleDev* dst, const CmMclDev& g, const CmMclWeightDev* wts, unsigned long long* cum,
+                      unsigned long long base, unsigned long long r_draw, double thr, uint32_t always, unsigned long long* words, const CmMclHypDev& hy) {
+    const uint32_t n = g.n;
+    if (!mcl_ok(g) || (hy.on && !hyp_ok(hy, n))) return;
+    hipLaunchKernelGGL(k_mcl_cum, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, wts, n, thr, always, cum, words, hy.on ? hy.words : nullptr);
+    hipLaunchKernelGGL(k_mcl_gather, dim3((n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, src, dst, n, cum, r_draw, words, g, base, hy);
+}
+
+void cmk_mcl_hyp_bins(hipStream_t s, const CmMclParticleDev* parts, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_bins, dim3((hy.n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, hy);
+}
+
+void cmk_mcl_hyp_link(hipStream_t s, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_link, dim3(((1u << hy.cap_bits) + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, hy);
+}
+
+void cmk_mcl_hyp_flatten(hipStream_t s, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    const uint32_t cap = 1u << hy.cap_bits;
+    hipLaunchKernelGGL(k_mcl_hyp_roots, dim3((cap + CM_MCL_ONE_BLOCK - 1) / CM_MCL_ONE_BLOCK), dim3(CM_MCL_ONE_BLOCK), 0, s, hy);
+    hipLaunchKernelGGL(k_mcl_hyp_flatten, dim3((cap + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, hy);
+}
+
+void cmk_mcl_hyp_sums(hipStream_t s, const CmMclParticleDev* parts, const CmMclWeightDev* wts, const float* dirs, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_sums, dim3((hy.n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, wts, reinterpret_cast<const float2*>(dirs), hy);
+}
+
+void cmk_mcl_hyp_spread(hipStream_t s, const CmMclParticleDev* parts, const CmMclWeightDev* wts, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_spread, dim3((hy.n + CM_MCL_BLOCK - 1) / CM_MCL_BLOCK), dim3(CM_MCL_BLOCK), 0, s, parts, wts, hy);
+}
+
+void cmk_mcl_hyp_pick(hipStream_t s, const CmMclHypDev& hy) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_pick, dim3(1), dim3(CM_MCL_ONE_BLOCK), 0, s, hy);
+}
+
+void cmk_mcl_hyp_recover(hipStream_t s, const CmMclHypDev& hy, const unsigned long long* layer_words) {
+    if (!hyp_ok(hy, hy.n)) return;
+    hipLaunchKernelGGL(k_mcl_hyp_recover, dim3(1), dim3(64), 0, s, hy, layer_words);
 }

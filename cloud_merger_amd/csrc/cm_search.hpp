@@ -38,6 +38,37 @@ __device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
 __device__ __forceinline__ void min_into(uint32_t* p, uint32_t v) { if (v < ld_agent(p)) atomicMin(p, v); }
 __device__ __forceinline__ void max_into(uint32_t* p, uint32_t v) { if (v > ld_agent(p)) atomicMax(p, v); }
 
+// The lock-free union-find on 32-bit parent words that the frontier layer's merge and the localisation layer's hypotheses
+// share. Every word holds an element of the same tree that is not above it, a root holds itself: a walk strictly decreases
+// and ends. No thread waits on another.
+__device__ __forceinline__ uint32_t cm_uf_load(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ __forceinline__ uint32_t cm_uf_find(const uint32_t* parent, uint32_t c) {
+    uint32_t p = cm_uf_load(parent + c);
+    while (p != c) {
+        c = p;
+        p = cm_uf_load(parent + c);
+    }
+    return c;
+}
+// Unites the trees of a and b. The larger root's word falls to the smaller root; if the word was no root any more (another
+// thread hung it elsewhere in the meantime), what it held still has to meet the smaller root, and the larger of the two
+// elements in hand has strictly fallen.
+__device__ __forceinline__ void cm_uf_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+    a = cm_uf_find(parent, a);
+    b = cm_uf_find(parent, b);
+    while (a != b) {
+        if (a < b) {
+            const uint32_t t = a;
+            a = b;
+            b = t;
+        }
+        const uint32_t old = atomicMin(parent + a, b);
+        if (old == a) break;
+        a = cm_uf_find(parent, old);
+        b = cm_uf_find(parent, b);
+    }
+}
+
 // fp64, every operation rounded on its own whatever the contraction setting.
 __device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
 __device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }

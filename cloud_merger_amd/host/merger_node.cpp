@@ -300,6 +300,19 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
                  (static_cast<double>(z[0]) + static_cast<double>(z[1])) + static_cast<double>(z[2]) <= 1.0;
         }
         else if (key == "mcl_beam_plain") ok = read_flag(is, &c.mcl_beam_plain);
+        else if (key == "mcl_hyp") ok = read_flag(is, &c.mcl_hyp_enable);
+        else if (key == "mcl_hyp_bins") {
+            float bin_m = 0.0f;
+            ok = read(is, bin_m, c.mcl_hyp_heading_bits) && std::isfinite(bin_m) && bin_m >= 0.0625f && bin_m <= 1024.0f && c.mcl_hyp_heading_bits <= 8u;
+            if (ok) c.mcl_hyp_bin_q = static_cast<uint32_t>(std::lrint(static_cast<double>(bin_m) * 1024.0));
+        }
+        else if (key == "mcl_hyp_max") ok = read(is, c.mcl_hyp_max) && c.mcl_hyp_max >= 1u && c.mcl_hyp_max <= CM_MCL_HYP_MAX;
+        else if (key == "mcl_recovery") {
+            float* al = c.mcl_recovery_alpha;
+            ok = read(is, al[0], al[1], c.mcl_inject_max) && std::isfinite(al[0]) && std::isfinite(al[1]) && 0.0f <= al[0] && al[0] <= al[1] && al[1] <= 1.0f;
+        }
+        else if (key == "mcl_kld") ok = read(is, c.mcl_kld_err, c.mcl_kld_z) && std::isfinite(c.mcl_kld_err) && c.mcl_kld_err > 0.0f && c.mcl_kld_err <= 1.0f &&
+                                        std::isfinite(c.mcl_kld_z) && c.mcl_kld_z > 0.0f;
         else if (key == "cast") ok = read_flag(is, &c.cast_enable);
         else if (key == "cast_bearings") ok = read(is, c.cast_bearings) && c.cast_bearings >= 1u && c.cast_bearings <= CM_CAST_MAX_BEARINGS;
         else if (key == "cast_range") ok = read(is, c.cast_range_cells) && c.cast_range_cells >= 1u && c.cast_range_cells <= CM_CAST_MAX_RANGE_CELLS;
@@ -333,6 +346,8 @@ bool load_config(const std::string& path, NodeConfig* cfg, std::string* err) {
     if (c.match_enable && c.match_search_enable) { if (err) *err = "match and match_search exclude each other"; return false; }
     if (c.mcl_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "mcl needs the cost layer (map and map_inflation)"; return false; }
     if (c.mcl_beam_enable && !c.mcl_enable) { if (err) *err = "mcl_beam needs the localisation layer (mcl 1)"; return false; }
+    if (c.mcl_hyp_enable && !c.mcl_enable) { if (err) *err = "mcl_hyp needs the localisation layer (mcl 1)"; return false; }
+    if (c.mcl_hyp_enable && c.mcl_inject_max > c.mcl_particles - 1u) { if (err) *err = "mcl_recovery: inject_max is above mcl_particles - 1"; return false; }
     if (c.cast_enable && !(c.map_cell > 0.0f && c.map_inflation_radius > 0.0f)) { if (err) *err = "cast needs the cost layer (map and map_inflation)"; return false; }
     if (ground_z_from_crop) c.ground.z_keep_max = c.params.crop_max[2];     // (whichever of `crop` and `ground` came first)
     *cfg = c;
@@ -419,6 +434,11 @@ CloudMergerNode::CloudMergerNode(const NodeConfig& cfg)
                     const cm_mcl_beam_params bp{cfg_.mcl_beam_over_cells, cfg_.mcl_beam_sigma, cfg_.mcl_beam_mix[0], cfg_.mcl_beam_mix[1], cfg_.mcl_beam_mix[2],
                                                 cfg_.mcl_beam_plain ? CM_MCL_BEAM_PLAIN : 0u};
                     if (cm_map_mcl_beam_configure(ctx_, &bp) != CM_OK) refuse("cm_map_mcl_beam_configure");
+                }
+                if (ctx_ && cfg_.mcl_hyp_enable) {                 // its hypotheses and recovery
+                    const cm_mcl_hyp_params hp{cfg_.mcl_hyp_bin_q, cfg_.mcl_hyp_heading_bits, cfg_.mcl_hyp_max, cfg_.mcl_inject_max, cfg_.mcl_recovery_alpha[0],
+                                               cfg_.mcl_recovery_alpha[1], cfg_.mcl_kld_err, cfg_.mcl_kld_z, 0u, 0u};
+                    if (cm_map_mcl_hyp_configure(ctx_, &hp) != CM_OK) refuse("cm_map_mcl_hyp_configure");
                 }
             }
             if (ctx_ && cfg_.cast_enable) {                        // the cast layer behind the cost layer: one pose, evenly spaced bearings
@@ -647,6 +667,11 @@ int CloudMergerNode::map_of_frame(const cm_result& r) {
             ls = cm_map_mcl_predict(ctx_, c * dx + s * dy, c * dy - s * dx, dyaw, cfg_.mcl_noise[0], cfg_.mcl_noise[1], cfg_.mcl_noise[2]);
             if (ls == CM_OK) ls = cm_map_mcl_update(ctx_, &mcl_info_);
             if (ls == CM_OK && cfg_.mcl_beam_enable) ls = cm_map_mcl_beam_info_copy(ctx_, &mcl_beam_info_);
+            if (ls == CM_OK && cfg_.mcl_hyp_enable) {
+                mcl_hyp_.resize(CM_MCL_HYP_MAX);
+                ls = cm_map_mcl_hyp_copy(ctx_, mcl_hyp_.data(), mcl_hyp_.size(), &mcl_hyp_info_);
+                mcl_hyp_.resize(ls == CM_OK ? mcl_hyp_info_.n_hyp : 0u);
+            }
         }
         if (ls == CM_OK) {
             std::memcpy(mcl_prev_, now, sizeof now);

@@ -190,6 +190,16 @@ struct NodeConfig {
     uint32_t mcl_beam_over_cells = 8;                // how far past its measured end a ray is followed
     float mcl_beam_mix[3] = {0.75f, 0.125f, 0.125f}; // z_hit, z_short, z_rand
     bool mcl_beam_plain = false;                     // walk cell by cell instead of jumping
+    // Its hypotheses and recovery (cm_map_mcl_hyp_configure): every update reports the clusters of the belief (mcl_hypotheses(),
+    // mcl_hyp_info()) and may replace particles by random ones while the fast average of the score lies below the slow one.
+    // Off by default; it needs mcl 1.
+    bool mcl_hyp_enable = false;
+    uint32_t mcl_hyp_bin_q = 512;                    // bin width in 1/1024 m (mcl_hyp_bins takes metres)
+    uint32_t mcl_hyp_heading_bits = 5;
+    uint32_t mcl_hyp_max = 8;
+    float mcl_recovery_alpha[2] = {0.05f, 0.5f};     // alpha_slow, alpha_fast
+    uint32_t mcl_inject_max = 0;                     // most particles one update may inject; 0: no injection
+    float mcl_kld_err = 0.05f, mcl_kld_z = 2.326f;
     // The cast layer (cm_map_cast_configure, cm_map_cast_evaluate): the virtual scan of the map. Off by default. On (it needs
     // the cost layer; without one load_config refuses the file and the node does not start): after each frame's cost update
     // the node casts cast_bearings evenly spaced rays of at most cast_range_cells cells from set_pose()'s pose (cast_rays(),
@@ -258,6 +268,8 @@ struct NodeConfig {
 //   (the localisation layer behind the cost layer, which it needs: a file with mcl 1 and no map_inflation is refused)
 //   mcl_beam <0|1> | mcl_beam_model <sigma> <over_cells> | mcl_beam_mix <z_hit> <z_short> <z_rand> | mcl_beam_plain <0|1>
 //   (the localisation layer's beam model; a file with mcl_beam 1 and no mcl 1 is refused)
+//   mcl_hyp <0|1> | mcl_hyp_bins <bin_m> <heading_bits> | mcl_hyp_max <n> | mcl_recovery <alpha_slow> <alpha_fast> <inject_max> |
+//   mcl_kld <err> <z>   (its hypotheses and recovery; a file with mcl_hyp 1 and no mcl 1 is refused)
 //   cast <0|1> | cast_bearings <n> | cast_range <cells> | cast_plain <0|1>
 //   (the cast layer behind the cost layer, which it needs: the virtual scan of the map from the set pose after every frame)
 //   normals_k <n> | normals_viewpoint <x> <y> <z>   (normals of every voxel cloud from n neighbours, 3..64; 0: off)
@@ -397,6 +409,9 @@ public:
     const cm_mcl_info& mcl_info() const { return mcl_info_; }
     // mcl_beam 1: the outcome counts of the last update (zeros until the first).
     const cm_mcl_beam_info& mcl_beam_info() const { return mcl_beam_info_; }
+    // mcl_hyp 1: the hypotheses of the last update, the heaviest first, and their info (empty and zeros until the first).
+    const std::vector<cm_mcl_hyp>& mcl_hypotheses() const { return mcl_hyp_; }
+    const cm_mcl_hyp_info& mcl_hyp_info() const { return mcl_hyp_info_; }
     const std::vector<cm_mcl_particle>& mcl_particles() const { return mcl_particles_; }
     // cast 1: the rays of the virtual scan behind the last frame's cost update (empty where the library refused the cast) and
     // their counts by status.
@@ -487,6 +502,8 @@ private:
     float mcl_prev_[3] = {0.0f, 0.0f, 0.0f};         // x, y, yaw of the set pose at the last init or predict
     cm_mcl_info mcl_info_{};
     cm_mcl_beam_info mcl_beam_info_{};
+    std::vector<cm_mcl_hyp> mcl_hyp_;
+    cm_mcl_hyp_info mcl_hyp_info_{};
     std::vector<cm_mcl_particle> mcl_particles_;
     std::vector<cm_cast_ray> cast_rays_;
     cm_cast_info cast_info_{};

@@ -1316,8 +1316,8 @@ CM_API int cm_map_frontier_device(cm_ctx* ctx, const void** labels, const void**
  * buffers of its own only: no other layer's tables or staleness change. A NULL context leaves every output untouched. With
  * CM_FLAG_PROFILE, cm_get_stage_times after an update lists mcl_clear, k_match_field, k_mcl_mark, k_mcl_compact, k_mcl_score,
  * k_mcl_best, k_mcl_weights, k_mcl_spread, k_mcl_resample. The beam model's terms and occlusion are a mode of their own (the
- * next section). Not modelled: adaptive (KLD) particle counts, random-particle injection, roll, pitch and z, weighting a cell by the number of
- * its points. */
+ * next section), and so are pose hypotheses, the KLD bound and random-particle injection (the section after it). Not modelled: a
+ * particle count that changes between updates, roll, pitch and z, weighting a cell by the number of its points. */
 #define CM_MCL_MAX_PARTICLES 65536
 #define CM_MCL_MAX_BEAMS 8192
 #define CM_MCL_MAX_RANGE_CELLS 1024
@@ -1449,6 +1449,113 @@ CM_API int cm_map_mcl_beam_info_copy(cm_ctx* ctx, cm_mcl_beam_info* out);
  * p or dst, parameters cm_map_mcl_beam_configure refuses, a cell that is not finite and > 0; a smaller capacity: CM_CAPACITY
  * (nothing is written). */
 CM_API int cm_mcl_beam_table(const cm_mcl_beam_params* p, float cell, uint8_t* dst, uint64_t capacity);
+
+/* ---- pose hypotheses and random-particle recovery of the localisation layer (an extension) ----------------------------------
+ * cm_mcl_info reports one weighted mean over all particles. While the belief has two modes that mean lies between them, and
+ * after a kidnapping every particle scores equally badly, n_eff stays high and nothing is ever drawn elsewhere. This mode adds
+ * what amcl adds: the clusters of the belief (pf_cluster_stats), the KLD bound on the particle count, and the injection of
+ * random particles steered by a slow and a fast average of the score (recovery_alpha_slow / _fast).
+ * cm_map_mcl_hyp_configure switches it on; it is off by default, and with it off every byte, stage name and refusal of the
+ * layer is what it is without this section. With inject_max = 0 the particles, the weight table and cm_mcl_info are byte for
+ * byte those of the mode off. "Steps" are those of the localisation layer above. Everything is integer arithmetic on keys and
+ * sums except the few doubles named below, whose every operation is written out: the hypotheses and the info are bit for bit
+ * a function of the inputs.
+ * The hypotheses are computed in every update while the mode is on, over the particles as the update found them: acc after
+ * the score of step 7, W of step 8, before the resampling of step 10: the particles cm_mcl_info's estimate is defined over.
+ *   H1. Bins. With q of step 9 and floor division of integers (q = -1 lies in bin -1): bx = floor(q(x) / bin_q),
+ *       by = floor(q(y) / bin_q); bh = h >> (32 - heading_bits), and 0 when heading_bits = 0. |q| <= 2^30 and bin_q >= 64, so
+ *       |bx|, |by| <= 2^24. key = ((uint64_t)(by + 2^24) << 34) | ((uint64_t)(bx + 2^24) << 8) | bh: keys order bins by
+ *       (by, bx, bh).
+ *   H2. Occupied bins. n_bins is the number of distinct keys.
+ *   H3. Neighbours and components. Two occupied bins are neighbours when |by - by'| <= 1, |bx - bx'| <= 1 and bh - bh' is -1, 0
+ *       or 1 modulo 2^heading_bits: headings wrap (amcl's do not). With heading_bits = 0 or 1 every two heading bins are
+ *       neighbours. A component is a connected set of occupied bins; its label is its smallest key. n_components counts all
+ *       of them.
+ *   H4. Per component, over its particles, exact integers within the bounds of step 9 (a component is a subset of the
+ *       particles): n; sum_w, sum_wqx, sum_wqy, sum_wc, sum_ws with ci, si of step 9; top, the particle with the largest W,
+ *       ties to the lowest index. mq_x = floor(sum_wqx / sum_w), mq_y likewise; dq = clamp(q - mq, -32768, 32767) per axis;
+ *       sum_wdxx, sum_wdyy, sum_wdxy are the sums of W dq_x^2, W dq_y^2, W dq_x dq_y. A component with sum_w = 0 has mq = 0,
+ *       zero spread sums and 0.0 in every double of H5.
+ *   H5. Order and output. Components are ordered by sum_w descending, ties by label ascending. The first
+ *       n_hyp = min(n_components, max_hyp) become cm_mcl_hyp records. Their doubles are computed on the host from the
+ *       component's sums exactly as step 9 computes the global ones: mean_x = ((double)sum_wqx / (double)sum_w) / 1024.0,
+ *       mean_y likewise, mean_yaw = atan2((double)sum_ws, (double)sum_wc), var_xx = (double)sum_wdxx / ((double)sum_w *
+ *       1048576.0), var_yy and var_xy likewise. share = (double)sum_w / (double)(step 9's sum_w over all particles).
+ *   H6. KLD bound. n_kld = cm_mcl_kld_bound(n_bins, kld_err, kld_z), on the host in double, every operation rounded once: 1
+ *       for k <= 1; otherwise a = 2.0 / (9.0 * (double)(k - 1)), b = (1.0 - a) + sqrt(a) * (double)z,
+ *       n = ceil(((double)(k - 1) / (2.0 * (double)err)) * ((b * b) * b)), clamped to 1 .. 2^32 - 1 (a value that is not a
+ *       number gives 2^32 - 1). It is reported only.
+ * The recovery, in every update while the mode is on; inject_max bounds what it may do.
+ *   R1. Average score. sum_s = the sum of S_p over the particles, exact and below 2^38. With n_beams of cm_mcl_info: if
+ *       n_beams = 0 the two averages stay as they are, n_inject = 0 and w_avg and p_inject are reported as 0.0. Otherwise
+ *       w_avg = (double)sum_s / (((double)n_particles * (double)n_beams) * 255.0): both products are exact, the division is
+ *       rounded once.
+ *   R2. Slow and fast average. w_slow becomes w_avg when it is 0.0, otherwise w_slow + a_slow * (w_avg - w_slow): a
+ *       difference, a product and a sum, each rounded, nothing fused; a_slow = (double)alpha_slow. w_fast likewise with
+ *       alpha_fast. Both are 0.0 after cm_map_mcl_hyp_configure and after every cm_map_mcl_init_pose / _init_uniform that was
+ *       not refused.
+ *   R3. Injection count. p_inject = 1.0 - w_fast / w_slow when w_slow > 0 and w_fast < w_slow (the new values), else 0.0.
+ *       n_inject = min(inject_max, (uint32_t)floor(p_inject * (double)n_particles)), and 0 when the map's image has no free
+ *       cell. The averages are not reset after an injection (amcl's reset stops the injection after one round).
+ *       n_free is the number of free cells of the map's current image (step 4), and 0 when inject_max = 0: no list is built.
+ *   R4. Resampling happens iff step 10's condition holds or n_inject > 0. m = n_particles - n_inject (>= 1). New particle
+ *       j < m copies (x, y, h) of the smallest p with C_p > (j * T + r) / m, with T, r and C of step 10, parent = p, acc = 0:
+ *       with n_inject = 0 this is step 10 word for word. New particle j >= m is step 4 over the free cells of the map's
+ *       current image with draw(j, 0 .. 3) of this update's base (an update uses no draw(p, i) otherwise); its parent is
+ *       CM_MCL_NO_PARENT and its acc is 0. cm_mcl_info's resampled is 1 whenever resampling happened.
+ * cm_mcl_hyp_info: the gen of the update, n_bins, n_components, n_hyp, n_kld, n_inject, n_free, sum_s, w_avg, w_slow and
+ * w_fast after R2, p_inject.
+ * cm_map_mcl_hyp_configure refuses with CM_BAD_ARG (cm_last_error says why): a frame in flight; no localisation layer (or no
+ * layer above it), in that layer's words; bin_q outside 64 .. 1048576; heading_bits above 8; max_hyp outside
+ * 1 .. CM_MCL_HYP_MAX; inject_max above n_particles - 1; an alpha that is not finite or not 0 <= alpha_slow <= alpha_fast <= 1;
+ * kld_err not finite or outside 0 < kld_err <= 1; kld_z not finite and > 0; flags or _pad not 0. A refused call changes
+ * nothing. An accepted call, with parameters or NULL, takes or gives back all the mode's memory (the table of bins of
+ * a power of two >= 4 n_particles slots with a parent and a component word per slot, a slot word and a record per particle,
+ * the chosen records, the mode's words, a bitmap and a list of the free cells, and a page-locked copy of what an update reads
+ * back: no other call allocates), leaves the particles and gen alone (it is not one of the calls gen counts) and makes the
+ * weight table, the infos and the hypotheses stale "since cm_map_mcl_hyp_configure" until the next cm_map_mcl_update.
+ * cm_map_mcl_configure in either form switches the mode off and frees it, and so does everything that frees the layer. The
+ * mode and the beam model do not know of each other. cm_map_mcl_update refuses exactly what it refuses without the mode.
+ * cm_map_mcl_hyp_copy refuses what cm_map_mcl_weights_copy refuses, and a last update that ran without the mode; a capacity
+ * below n_hyp is CM_CAPACITY (nothing is copied; *info, which may be NULL, is still written). A NULL context leaves every
+ * output untouched. With CM_FLAG_PROFILE the stage list of an update has, between k_mcl_spread and k_mcl_resample:
+ * mcl_hyp_clear, k_mcl_hyp_bins, k_mcl_hyp_link, k_mcl_hyp_flatten, k_mcl_hyp_sums, k_mcl_hyp_spread, k_mcl_hyp_pick, then
+ * k_mcl_free_bits and k_mcl_compact only where inject_max > 0, then k_mcl_hyp_recover. Not modelled: a particle count that
+ * follows n_kld, amcl's reset of the averages, a cluster's heading spread. */
+#define CM_MCL_HYP_MAX 64
+#define CM_MCL_NO_PARENT 0xFFFFFFFFu
+typedef struct cm_mcl_hyp_params {     /* 40 bytes, no padding */
+    uint32_t bin_q;                    /* bin width in 1/1024 m; 64 .. 1048576 */
+    uint32_t heading_bits;             /* 2^heading_bits heading bins; 0 .. 8 */
+    uint32_t max_hyp;                  /* 1 .. CM_MCL_HYP_MAX */
+    uint32_t inject_max;               /* most particles one update may inject; 0: no injection; <= n_particles - 1 */
+    float alpha_slow, alpha_fast;      /* finite, 0 <= alpha_slow <= alpha_fast <= 1 */
+    float kld_err, kld_z;              /* finite, 0 < kld_err <= 1, kld_z > 0 */
+    uint32_t flags, _pad;              /* 0 */
+} cm_mcl_hyp_params;
+typedef struct cm_mcl_hyp {            /* 136 bytes */
+    uint64_t label;                    /* the smallest key of the component */
+    uint32_t n, top;                   /* its particles; the heaviest of them */
+    uint64_t sum_w;
+    int64_t sum_wqx, sum_wqy, sum_wc, sum_ws;
+    int64_t sum_wdxx, sum_wdyy, sum_wdxy;
+    double share, mean_x, mean_y, mean_yaw;
+    double var_xx, var_yy, var_xy;
+} cm_mcl_hyp;
+typedef struct cm_mcl_hyp_info {       /* 72 bytes */
+    uint64_t gen;                      /* the gen of the update */
+    uint32_t n_bins, n_components, n_hyp, n_kld, n_inject, n_free;
+    uint64_t sum_s;
+    double w_avg, w_slow, w_fast, p_inject;
+} cm_mcl_hyp_info;
+/* Non-NULL parameters switch the mode on (or replace its parameters; the averages start at 0.0); NULL switches it off and
+ * frees it. */
+CM_API int cm_map_mcl_hyp_configure(cm_ctx* ctx, const cm_mcl_hyp_params* p);
+/* The hypotheses of the last update, which must have run the mode, in the order of H5; capacity in records. */
+CM_API int cm_map_mcl_hyp_copy(cm_ctx* ctx, cm_mcl_hyp* host_dst, uint64_t capacity, cm_mcl_hyp_info* info);
+/* H6 for k bins. A host function: no context, no GPU. CM_BAD_ARG: a NULL out, err not finite or outside 0 < err <= 1, z not
+ * finite and > 0 (nothing is written). */
+CM_API int cm_mcl_kld_bound(uint32_t k, float err, float z, uint32_t* out);
 
 /* ---- the cast layer: expected ranges from many poses in the occupancy map (an extension) ----------------------------------
  * Every other layer looks single cells up. This one answers what the map was built by ray casting to answer: from this pose,
