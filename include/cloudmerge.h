@@ -308,6 +308,9 @@ CM_API int cm_ground_planes(cm_ctx* ctx, cm_ground_plane* planes, uint32_t capac
  * constant body twist xi = (v, w), dt = t - t_ref:
  *     q = M_s p,  c = w x q,  e = w x c,  k = w x v,  h = dt^2 / 2
  *     out = q + (dt (c + v) + h (e + k))      fp32, round-to-nearest, no contraction, in this order
+ * with dt = dt0_s + tau in fp32, dt0_s = (float)((double)(stamp_ns[s] - t_ref_ns) * 1e-9). The difference of the two
+ * stamps is taken modulo 2^64 and read as a signed 64-bit integer: stamps further apart than 2^63 ns wrap, they do not
+ * overflow. A uint32 tau is converted to fp32 (round-to-nearest-even, the whole unsigned range) and multiplied by 1e-9f.
  * It runs as one pre-pass (k_motion) over all clouds of the frame, before the transform's consumers: the voxel grid, the
  * outlier and ground stages, cm_merged_copy, the CM_GRID_OVERFLOW fallback and a redo inside cm_wait all see the
  * compensated points. A point with a non-finite coordinate or time stays non-finite and is dropped as before.

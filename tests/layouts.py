@@ -50,6 +50,21 @@ TIMED = {
 }
 ALL = {**LAYOUTS, **TIMED}
 NO_INTENSITY = tuple(k for k, v in ALL.items() if v.off[3] is None)
+# Layouts for the ego-motion tests alone (tests/motion_edge_frames.py), kept out of ALL: a plain 20-byte record with u32
+# nanoseconds behind the intensity, and the two fast layouts with a time field. PCL32 keeps it in the padding behind the
+# intensity; XYZI16 has no room: the intensity's four bytes are also read as the time (repack writes the intensity last, so
+# the caller passes the same bits for both).
+MOTION = {
+    "u32ns20": Layout(20, (0, 4, 8, 12), "GENERIC", (), (16, TIME_U32_NS)),
+    "pcl32_t20": Layout(32, (0, 4, 8, 16), "PCL32", (), (20, TIME_F32_S)),
+    "pcl32_t28": Layout(32, (0, 4, 8, 16), "PCL32", (), (28, TIME_U32_NS)),
+    "xyzi16_tf": Layout(16, (0, 4, 8, 12), "XYZI16", (), (12, TIME_F32_S)),
+    "xyzi16_tu": Layout(16, (0, 4, 8, 12), "XYZI16", (), (12, TIME_U32_NS)),
+}
+
+
+def layout(name) -> Layout:
+    return ALL[name] if name in ALL else MOTION[name]
 
 
 def _put(raw, off, values):
@@ -64,7 +79,7 @@ def repack(xyz, intensity, name, rng, tau=None, **kw) -> SensorCloud:
     """(n,3) float32 xyz and (n,) float32 intensity (None: zeros) as a SensorCloud in layout `name`; the float bits are
     copied, NaN payloads and signed zeros included. tau: per-point times for the time field (float32 seconds or uint32
     nanoseconds, per the layout's type); without it the field holds a decoy. kw: q_xyzw, t_xyz, is_dense."""
-    lay = ALL[name]
+    lay = layout(name)
     xyz = np.ascontiguousarray(xyz, dtype="<f4").reshape(-1, 3)
     n = len(xyz)
     raw = np.full((n, lay.step), 0xFF, np.uint8)

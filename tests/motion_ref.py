@@ -7,8 +7,20 @@ F = np.float32
 
 
 def dt0_s(stamp_ns, t_ref_ns):
-    """(float)((double)(stamp - t_ref) * 1e-9)"""
-    return F(float(int(stamp_ns) - int(t_ref_ns)) * 1e-9)
+    """(float)((double)(stamp - t_ref) * 1e-9), the difference taken modulo 2^64 and read as a signed 64-bit integer"""
+    d = (int(stamp_ns) - int(t_ref_ns)) & (2 ** 64 - 1)
+    return F(float(d - 2 ** 64 if d >= 2 ** 63 else d) * 1e-9)
+
+
+def valid(pts, crop_min=None, crop_max=None):
+    """point_valid of cm_common.hpp as a mask over (n, >= 3) points: every coordinate finite and, with a crop box, no
+    coordinate below its minimum or above its maximum."""
+    xyz = np.asarray(pts, F)[:, :3]
+    ok = np.isfinite(xyz).all(axis=1)
+    if crop_min is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= ~((xyz < np.asarray(crop_min, F)) | (xyz > np.asarray(crop_max, F))).any(axis=1)
+    return ok
 
 
 def cross(a, b):
@@ -41,12 +53,12 @@ def compensate(xyz, m, tau, dt0, v, w, intensity=None):
     v = tuple(F(a) for a in v)
     w = tuple(F(a) for a in w)
     k = cross(w, v)
-    dt = np.full(n, F(dt0), F) if tau is None else F(dt0) + np.asarray(tau, F)
-    h = F(0.5) * (dt * dt)
-    c = cross(w, q)
-    e = cross(w, c)
     out = np.empty((n, 4), F)
     with np.errstate(invalid="ignore", over="ignore"):       # (non-finite points stay non-finite, as on the device)
+        dt = np.full(n, F(dt0), F) if tau is None else F(dt0) + np.asarray(tau, F)
+        h = F(0.5) * (dt * dt)
+        c = cross(w, q)
+        e = cross(w, c)
         for a in range(3):
             out[:, a] = q[a] + ((dt * (c[a] + v[a])) + (h * (e[a] + k[a])))
     out[:, 3] = 0 if intensity is None else np.asarray(intensity, F)

@@ -23,6 +23,7 @@ from cloud_merger_amd.types import MergeParams, xyzi_cloud
 from tests import cost_ref as cr
 from tests import map_ref as mr
 from tests import match_ref as mf
+from tests import motion_edge_frames as ef
 from tests import test_grid_map as tg
 from tests import test_grid_rays as tr
 from tests import test_map_cost as tc
@@ -422,6 +423,70 @@ def test_with_ground_removal():
         vol, _ = cm.map_match_scores()
         assert vol.tobytes() == want_vol.tobytes() and same_result(result_dict(res), want)
         assert (res.k, res.i, res.j) == (0, -2, 1) and res.score == res.max_score
+
+
+# A moving vehicle: 7.2 m/s and a slow turn. Sensor 0's points carry a time over 0.1 s behind a stamp 50 ms after the
+# reference instant, sensor 1's are all at its stamp 80 ms before it: every point moves by 3 to 11 cells of 0.1 m.
+DESKEW = dict(v=(6.0, -4.0, 0.0), w=(0.0, 0.0, 0.05), t_ref=1_700_000_000_000_000_000, d_stamp=(50_000_000, -80_000_000), kinds=("velo22", "xyzi16"))
+
+
+def deskew_raws(parts):
+    """Per sensor the vehicle-frame points `parts` as a raw cloud under its translation (tests/motion_edge_frames.py's Cloud):
+    velo22 with float32 seconds at byte 18 for sensor 0, XYZI16 without a time field for sensor 1; and the two stamps."""
+    rng = np.random.default_rng(5)
+    raws = []
+    for s, p in enumerate(parts):
+        q = (np.asarray(p, np.float64) - np.asarray(TRANS[s], np.float64)).astype(F32)
+        tau = np.sort(rng.uniform(0.0, 0.1, len(q))).astype(F32) if s == 0 else None
+        raws.append(ef.Cloud(DESKEW["kinds"][s], q, tau, np.full(len(q), s, F32), t=TRANS[s], seed=s))
+    return raws, [DESKEW["t_ref"] + d for d in DESKEW["d_stamp"]]
+
+
+def run_deskewed(cm, raws, stamps, n_cap=4096):
+    """The frame of the raw clouds with compensation on. Returns the library's A and, per sensor, the numpy-compensated cloud
+    (tests/motion_ref.py) as XYZI16 with the identity transform: what a context without motion is fed."""
+    v, w, t_ref = DESKEW["v"], DESKEW["w"], DESKEW["t_ref"]
+    for s, r in enumerate(raws):
+        cm.set_transform(s, r.q, r.t)
+        cm.set_time_field(s, *r.time)
+        cm.submit(s, r.cloud)
+    cm.set_ego_motion(capi.make_motion(v, w, t_ref, stamps))
+    res = cm.merge_voxelize(tc.PARAMS)
+    assert res.status == capi.OK and res.path_flags & capi.PATH_MOTION
+    want = [r.compensated(cm.get_matrix(s), stamps[s], t_ref, v, w) for s, r in enumerate(raws)]
+    A = tg.host_clouds(cm, n_cap, False)[0]
+    assert A.tobytes() == np.concatenate(want).tobytes()
+    return A, [xyzi_cloud(c[:, :3], c[:, 3]) for c in want]
+
+
+def moved_by_cells(A, A0):
+    """The compensated cloud against the uncompensated one: (smallest, largest) displacement of a point in cells."""
+    assert A.shape == A0.shape and np.array_equal(A[:, 3], A0[:, 3])
+    d = np.hypot(A[:, 0] - A0[:, 0], A[:, 1] - A0[:, 1]) / CELL
+    return float(d.min()), float(d.max())
+
+
+@pytest.mark.gpu
+def test_with_deskew():
+    """k_match_mark reads the frame's clouds in place: under motion those are the compensated records of the pre-pass. The
+    identity scene's map, then its frame from a moving vehicle: the volume and the result are the restatement's on the
+    library's merged(), and the bytes a context without motion gives on the numpy-compensated clouds."""
+    sc = scene("deskew", BASE, q=dict(n_a=2, a_stride=16, wx=6, wy=5, flags=1))
+    raws, stamps = deskew_raws(parts_of(sc["map_cells"], sc["nx"], sc["ny"]))
+    with capi.CloudMerger(max_points_total=4096, max_sensors=2) as cm, capi.CloudMerger(max_points_total=4096, max_sensors=2) as plain:
+        build_map(cm, sc)
+        build_map(plain, sc)
+        A, comp = run_deskewed(cm, raws, stamps)
+        lo, hi = moved_by_cells(A, scan_of(sc)[1])
+        assert lo > 3.0 and hi < 12.0, (lo, hi)                        # the points did move, by several cells
+        vol, res = evaluate(cm, sc)
+        assert 0 < res.n_cells <= len(A)
+        tg.run_frame(plain, comp, tc.PARAMS)
+        assert tg.host_clouds(plain, 4096, False)[0].tobytes() == A.tobytes()
+        p_vol, p_res = evaluate(plain, sc)
+        assert vol.tobytes() == p_vol.tobytes() and bytes(res) == bytes(p_res)
+        unmoved = mf.match(scan_of(sc)[1], cm.map_cost()[1], sc["mq"], anchor_of(sc["nx"], sc["ny"]), sc["q"], prior_of(sc, TAB()), TAB())[0]
+        assert unmoved.tobytes() != vol.tobytes()                      # matching the raw clouds would show
 
 
 def small_stack(cm, nx=64, ny=48, cell=0.1, match=True):

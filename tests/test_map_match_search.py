@@ -351,6 +351,32 @@ def test_with_ground_removal():
         assert (res.k, res.i, res.j) == (0, -2, 1) and res.score == res.max_score
 
 
+@pytest.mark.gpu
+def test_with_deskew():
+    """tests/test_map_match.py's moving vehicle through the wide search: k_match_mark reads the compensated records in place.
+    Result, info and every level of the pyramid are the restatement's on the library's merged(), and the bytes of a context
+    without motion fed the numpy-compensated clouds."""
+    sc = tmm.scene("deskew", tmm.BASE, q=dict(n_a=2, a_stride=16, wx=20, wy=13, depth=3, max_nodes=1 << 16, max_cells=4096, flags=1))
+    raws, stamps = tmm.deskew_raws(tmm.parts_of(sc["map_cells"], sc["nx"], sc["ny"]))
+    with capi.CloudMerger(max_points_total=4096, max_sensors=2) as cm, capi.CloudMerger(max_points_total=4096, max_sensors=2) as plain:
+        tmm.build_map(cm, sc)
+        tmm.build_map(plain, sc)
+        A, comp = tmm.run_deskewed(cm, raws, stamps)
+        lo, hi = tmm.moved_by_cells(A, tmm.scan_of(sc)[1])
+        assert lo > 3.0 and hi < 12.0, (lo, hi)
+        res, info, (L, Q, D) = evaluate(cm, sc)
+        tg.run_frame(plain, comp, tc.PARAMS)
+        assert tg.host_clouds(plain, 4096, False)[0].tobytes() == A.tobytes()
+        p_res, p_info, _ = evaluate(plain, sc)
+        assert bytes(res) == bytes(p_res) and bytes(info) == bytes(p_info)
+        for h in range(search_q(sc)["depth"] + 1):
+            got = cm.map_match_search_level(h)
+            assert got.tobytes() == ms.level(L, h).tobytes() == plain.map_match_search_level(h).tobytes(), h
+        _, unmoved, _, _ = ms.match(tmm.scan_of(sc)[1], cm.map_cost()[1], sc["mq"], tmm.anchor_of(sc["nx"], sc["ny"]), search_q(sc), tmm.prior_of(sc, tmm.TAB()),
+                                    tmm.TAB())
+        assert not tmm.same_result(tmm.result_dict(res), unmoved)      # searching with the raw clouds would show
+
+
 def small_stack(cm, nx=64, ny=48, cell=0.1, search=True):
     tm.configure(cm, tc.map_q(cell, nx, ny))
     cm.map_cost_configure(0.35, 1.05, 3.0, True)

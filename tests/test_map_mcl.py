@@ -405,6 +405,42 @@ def test_particle_counts(room, n):
     p.update()
 
 
+def deskew_pair(make_pair, drive):
+    """The room's first scan from tests/test_map_match.py's moving vehicle, on a context with compensation on and on one
+    without, fed the numpy-compensated clouds: make_pair(cm) builds the lockstep pair (every call compares the library with
+    the restatement on the library's merged()), drive(pair) runs it and returns what the two contexts must share byte for byte."""
+    parts = split(body_points(scan_of(TRUTH0)))
+    raws, stamps = tmm.deskew_raws(parts)
+    out = []
+    with capi.CloudMerger(max_points_total=16384, max_sensors=2) as cm, capi.CloudMerger(max_points_total=16384, max_sensors=2) as plain:
+        build_room(cm)
+        build_room(plain)
+        A, comp = tmm.run_deskewed(cm, raws, stamps, n_cap=16384)
+        lo, hi = tmm.moved_by_cells(A, tmm.clouds_of(parts)[1])
+        assert lo > 3.0 and hi < 12.0, (lo, hi)                        # the points did move, by several cells
+        tg.run_frame(plain, comp, tc.PARAMS)
+        assert tg.host_clouds(plain, 16384, False)[0].tobytes() == A.tobytes()
+        for c in (cm, plain):
+            out.append(drive(make_pair(c)))
+    return out
+
+
+@pytest.mark.gpu
+def test_with_deskew():
+    """k_mcl_mark reads the frame's clouds in place: under motion the compensated records. Two updates with a predict between
+    them: particles, weights and info are the restatement's, and the same bytes with and without motion."""
+    def drive(p):
+        p.init_pose(TRUTH0[0] + 0.25, TRUTH0[1] - 0.2, TRUTH0[2] + 0.08, 0.3, 0.3, 0.1)
+        w1, i1, _ = p.update()
+        p.predict(0.1, 0.0, 0.05, 0.03, 0.03, 0.02)
+        w2, i2, _ = p.update()
+        assert i1.n_cells > 32 and i1.n_beams > 0
+        return w1.tobytes(), bytes(i1), w2.tobytes(), bytes(i2), p.particles().tobytes()
+
+    a, b = deskew_pair(lambda cm: Pair(cm, dict(TRACK_Q, seed=5)), drive)
+    assert a == b
+
+
 def some_body_cells(n, reach=40, seed=9):
     rng = np.random.default_rng(seed)
     cells = sorted(set(zip(rng.integers(-reach, reach + 1, 4 * n + 8).tolist(), rng.integers(-reach, reach + 1, 4 * n + 8).tolist())))

@@ -366,6 +366,28 @@ def test_particle_and_beam_counts(room, n, n_beams, over):
 
 
 @pytest.mark.gpu
+def test_with_deskew():
+    """The beams are the body cells of the frame's clouds, which under motion are the compensated records. Two updates with a
+    predict between them in both walks: weights, info, particles and the outcome counts are the restatement's on the library's
+    merged(), and the same bytes with and without motion."""
+    def drive(p):
+        p.init_pose(tml.TRUTH0[0] + 0.25, tml.TRUTH0[1] - 0.2, tml.TRUTH0[2] + 0.08, 0.3, 0.3, 0.1)
+        w1, i1, b1 = p.update()
+        p.predict(0.1, 0.0, 0.05, 0.03, 0.03, 0.02)
+        w2, i2, b2 = p.update()
+        assert i1.n_beams > 32 and b1["n_rays"] == i1.n_particles * i1.n_beams
+        return w1.tobytes(), bytes(i1), sorted(b1.items()), w2.tobytes(), bytes(i2), sorted(b2.items()), p.particles().tobytes()
+
+    q = tml.q_of(n_particles=300, max_beams=256, range_cells=64, seed=6)
+    walks = []
+    for plain_walk in (0, 1):
+        a, b = tml.deskew_pair(lambda cm: BeamPair(cm, q, b_of(over_cells=4, flags=plain_walk)), drive)
+        assert a == b
+        walks.append(a)
+    assert walks[0][0] == walks[1][0] and walks[0][3] == walks[1][3]      # the jump walk and the plain walk: the same weights
+
+
+@pytest.mark.gpu
 def test_the_two_walls_on_the_device(lab):
     lab_load(lab, two_walls(), WALLS_MQ, WALLS_ANCHOR)
     tml.frame(lab, tml.body_points(WALLS_BEAMS))
