@@ -1884,18 +1884,21 @@ int cm_local_bounds(cm_ctx* c, const cm_params* p, float min_xyz[3], float max_x
     for (int a = 0; a < 3; ++a)
         if (!(p->leaf[a] > 0.0f)) return fail(c, CM_BAD_ARG, "leaf must be > 0");
     std::vector<std::unique_lock<std::mutex>> locks;
-    const int bf = build_frame(c, p, false, locks);          // a peek: the clouds stay fresh
+    // a peek: the clouds stay fresh, and c->frame stays the last frame's. HBM holds the peek's descriptor afterwards, which
+    // frame_uploaded records: the merge that follows skips its upload when it builds the same one, and a by-product call
+    // that comes first puts c->frame back (frame_on_device).
+    CmFrameDev f;
+    const int bf = build_frame(c, p, &f, locks);
     if (bf != CM_OK) return bf;
     const float inf = std::numeric_limits<float>::infinity();
     for (int a = 0; a < 3; ++a) { min_xyz[a] = inf; max_xyz[a] = -inf; }
     if (n_valid) *n_valid = 0;
-    const CmFrameDev& f = c->frame;
     if (f.n_padded == 0) return CM_OK;
     cmk_setup(c->stream, f, c->d_frame, c->d_tiles);
     c->frame_uploaded = f;
     c->frame_uploaded_valid = true;
     uint64_t cnt = 0;
-    const int e = measure_bounds(c, min_xyz, max_xyz, &cnt);
+    const int e = measure_bounds(c, f.n_tiles, min_xyz, max_xyz, &cnt);
     if (e != CM_OK) return e;
     if (n_valid) *n_valid = cnt;
     return CM_OK;

@@ -73,6 +73,7 @@ int voxel_cov(cm_ctx* c, const cm_cov_params& q) {
     if (!ensure_merged(c)) return fail(c, CM_HIP_ERROR, "cannot allocate the fused cloud's buffer");
     hipStream_t st = c->stream;
     // the kept points in (sensor, point) order, as cm_merged_copy returns them
+    frame_on_device(c);
     cmk_merged(st, c->d_frame, c->cov_tile_counts, c->cov_words, c->merged, nt, c->frame_mask);
     // (voxel number, record index) pairs, sorted by voxel number: as many 8-bit passes as the numbers need
     const uint32_t passes = (key_width(n_out) + CM_RADIX_BITS - 1) / CM_RADIX_BITS;
@@ -387,6 +388,7 @@ int grid_map(cm_ctx* c, const cm_grid_params& q, bool more_stages) {
     HIP_TRY(c, hipMemsetAsync(c->grid_cells, 0, n_cells * sizeof(cm_grid_cell), st));
     prof_mark(c, "k_grid_bin");
     // (an empty frame has no tiles and, on a fresh context, no descriptor in HBM: nothing is launched)
+    frame_on_device(c);
     cmk_grid_bin(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->grid_cells, c->frame.n_tiles);
     prof_mark(c, "k_grid_finish");
     cmk_grid_finish(st, c->grid_cells, c->grid_image, static_cast<uint32_t>(n_cells), q.obstacle_height, q.min_points);
@@ -433,6 +435,7 @@ int grid_rays(cm_ctx* c, const cm_grid_params& q, const cm_ray_params& r) {
     if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->ray_bits, 0, static_cast<size_t>(n_sensors) * words * 4, st));
     HIP_TRY(c, hipMemsetAsync(c->ray_cells, 0, n_cells * sizeof(cm_grid_ray_cell), st));
     prof_mark(c, "k_ray_mark");
+    frame_on_device(c);
     cmk_ray_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->ray_bits, words, c->frame.n_tiles);
     prof_mark(c, "k_ray_cast");
     cmk_ray_cast(st, c->ray_bits, words, rd, n_sensors, c->ray_cells);
@@ -569,6 +572,7 @@ int map_integrate(cm_ctx* c, const float pose[12], const int v[2]) {
     if (n_sensors) HIP_TRY(c, hipMemsetAsync(c->map.bits, 0, 2 * static_cast<size_t>(n_sensors) * words * 4, st));
     HIP_TRY(c, hipMemsetAsync(c->map.rays, 0, n_cells * sizeof(cm_grid_ray_cell), st));
     prof_mark(c, "k_map_mark");
+    frame_on_device(c);
     cmk_map_mark(st, c->d_frame, g, c->frame_mask, c->frame_had_ground ? c->gmask : nullptr, c->map.bits, words, n_sensors, c->frame.n_tiles);
     prof_mark(c, "k_ray_cast");
     cmk_ray_cast(st, c->map.bits, words, rd, n_sensors, c->map.rays);
@@ -1005,6 +1009,7 @@ int map_match_evaluate(cm_ctx* c, const float pose[12]) {
     prof_mark(c, "k_match_field");
     cmk_match_field(st, c->cost.dist2, c->match.field + n_cells, g.r2, static_cast<uint32_t>(n_cells), c->match.field);
     prof_mark(c, "k_match_mark");
+    frame_on_device(c);
     cmk_match_mark(st, c->d_frame, g, c->match.q, c->frame_mask, c->match.bits, n_tiles);
     prof_mark(c, "k_match_score");
     cmk_match_score(st, c->match.field, c->match.bits, g, c->match.vol);
@@ -1291,6 +1296,7 @@ int map_mcl_update(cm_ctx* c) {
     prof_mark(c, "k_match_field");
     cmk_match_field(st, c->cost.dist2, c->mcl.field + n_cells, r2, static_cast<uint32_t>(n_cells), c->mcl.field);
     prof_mark(c, "k_mcl_mark");
+    frame_on_device(c);
     cmk_mcl_mark(st, c->d_frame, g, c->frame_mask, c->mcl.bits, c->frame.n_tiles);
     prof_mark(c, "k_mcl_compact");
     cmk_mcl_compact(st, c->mcl.bits, body_words, q.max_beams, counts, list, words);
@@ -1728,6 +1734,7 @@ int map_msearch_evaluate(cm_ctx* c, const float pose[12]) {
     prof_mark(c, "k_msearch_pyramid");
     for (uint32_t h = 1; h <= q.depth; ++h) cmk_msearch_pyramid(st, level(h - 1u), level(h), nx, ny, h);
     prof_mark(c, "k_match_mark");
+    frame_on_device(c);
     cmk_match_mark(st, c->d_frame, g, c->msearch.q, c->frame_mask, c->msearch.bits, c->frame.n_tiles);
     prof_mark(c, "k_msearch_list");
     cmk_msearch_list(st, c->msearch.bits, m, g.words, cells, counts);

@@ -513,13 +513,18 @@ inline bool ensure_cell_sort(cm_ctx* c) {
 }
 
 // cm_launch.cpp. Every one of them is called with merge_mu held.
-// Builds the frame descriptor in c->frame (consume: the frame takes the sensors' fresh clouds; false: a peek).
-int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::unique_lock<std::mutex>>& locks);
+// Builds the frame descriptor. peek == nullptr: in c->frame, and the frame takes the sensors' fresh clouds. Otherwise in *peek,
+// from the clouds the next frame would read, and nothing of the last frame changes. A refusal changes nothing either.
+int build_frame(cm_ctx* c, const cm_params* p, CmFrameDev* peek, std::vector<std::unique_lock<std::mutex>>& locks);
+// Uploads c->frame unless HBM holds it already (a peek leaves its own descriptor there). Every call that reads the last
+// frame's clouds through d_frame after the frame has finished starts with it; behind a frame it costs one memcmp.
+void frame_on_device(cm_ctx* c);
 // The frame's points that `mask` keeps (nullptr: every valid one) as 16-byte records in (sensor, point) order into `out`,
 // and their number (a host round trip). tile_counts: cap_tiles words.
 int fuse_points(cm_ctx* c, uint32_t* tile_counts, void* out, const unsigned char* mask, uint32_t* total);
-// k_minmax over the uploaded descriptor and a host round trip: the bounds of the frame's valid points and their count.
-int measure_bounds(cm_ctx* c, float mn[3], float mx[3], uint64_t* n_valid);
+// k_minmax over the uploaded descriptor, which has n_tiles tiles, and a host round trip: the bounds of its valid points and
+// their count.
+int measure_bounds(cm_ctx* c, uint32_t n_tiles, float mn[3], float mx[3], uint64_t* n_valid);
 // mode 0: the path (centroids). mode 1: partial table of per-voxel sums (fused cloud across GPUs); `bounds` (min xyz,
 // max xyz of the whole fused cloud) then fixes the grid unless the crop box does.
 int enqueue(cm_ctx* c, const cm_params* p, int mode = 0, const float* bounds = nullptr);

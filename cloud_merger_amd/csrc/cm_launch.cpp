@@ -63,6 +63,11 @@ int end_frame(cm_ctx* c) {
 
 }  // namespace
 
+void frame_on_device(cm_ctx* c) {
+    if (!c->frame.n_padded) return;                    // (an empty frame has no tiles: its readers launch nothing)
+    if (descriptor_changed(c)) cmk_setup(c->stream, c->frame, c->d_frame, c->d_tiles);
+}
+
 void radix_sort_pairs(cm_ctx* c, CmFrameState* st, const SortPairs& b, uint32_t n_pass, uint32_t nt, uint32_t n_slots,
                       bool lds_rank, uint32_t* tile_kept, const char* scatter_mark) {
     const uint32_t n_groups = (nt + CM_GROUP - 1) / CM_GROUP, gw = n_groups * CM_RADIX;
@@ -112,7 +117,7 @@ int bootstrap_box(cm_ctx* c) {
     if (descriptor_changed(c)) cmk_setup(c->stream, c->frame, c->d_frame, c->d_tiles);
     float mn[3], mx[3], leaf[3];
     uint64_t cnt = 0;
-    const int e = measure_bounds(c, mn, mx, &cnt);
+    const int e = measure_bounds(c, c->frame.n_tiles, mn, mx, &cnt);
     if (e != CM_OK) return e;
     c->route.pred.ok = false;
     if (cnt) {
@@ -440,8 +445,11 @@ void exact_grid(const CmFrameState& h, const float inv_leaf[3], cm_result& r) {
 
 }  // namespace
 
-// Builds the frame descriptor in c->frame.
-int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::unique_lock<std::mutex>>& locks) {
+// Builds the frame descriptor: in c->frame, or for a peek in *peek. It is assembled in a local and stored once nothing can
+// refuse the call any more: c->frame, c->n_in and c->n_sensors_used describe the last frame for as long as its result is
+// served (the by-product calls read its clouds through them), so neither a refusal nor a peek may touch them.
+int build_frame(cm_ctx* c, const cm_params* p, CmFrameDev* peek, std::vector<std::unique_lock<std::mutex>>& locks) {
+    const bool consume = peek == nullptr;
     for (uint32_t s = 0; s < c->max_sensors; ++s) locks.emplace_back(c->slots[s].mu);
 
     // Frame assembly policy (pc_preprocessing_main.cpp:134-157).
@@ -453,7 +461,7 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
     const uint32_t required = p->required_sensor_mask ? p->required_sensor_mask : have;
     if (have == 0 || (required & ~fresh) != 0) return CM_NOT_READY;
 
-    CmFrameDev& f = c->frame;
+    CmFrameDev f;
     std::memset(&f, 0, sizeof f);
     uint32_t base = 0, k = 0;
     uint64_t n_in = 0;
@@ -471,7 +479,7 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
         base = static_cast<uint32_t>(nb);
     }
     base = 0;
-    c->stats_n_sensors = 0;
+    if (consume) c->stats_n_sensors = 0;
     for (uint32_t s = 0; s < c->max_sensors; ++s) {
         Slot& sl = c->slots[s];
         if (!sl.has_data) continue;
@@ -555,22 +563,27 @@ int build_frame(cm_ctx* c, const cm_params* p, bool consume, std::vector<std::un
     }
     f.min_pts = p->min_points_per_voxel;
     f.downsample_all = p->downsample_all_data ? 1u : 0u;
+    if (!consume) {
+        *peek = f;
+        return CM_OK;
+    }
+    c->frame = f;
     c->n_in = n_in;
     c->n_sensors_used = k;
-    if (consume)
-        for (auto& sl : c->slots) sl.fresh = false;   // flag reset, :151-157
+    for (auto& sl : c->slots) sl.fresh = false;       // flag reset, :151-157
     return CM_OK;
 }
 
 int fuse_points(cm_ctx* c, uint32_t* tile_counts, void* out, const unsigned char* mask, uint32_t* total) {
+    frame_on_device(c);
     cmk_merged(c->stream, c->d_frame, tile_counts, c->merged_total, out, c->frame.n_tiles, mask);
     HIP_TRY(c, hipMemcpyAsync(total, c->merged_total, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return CM_OK;
 }
 
-int measure_bounds(cm_ctx* c, float mn[3], float mx[3], uint64_t* n_valid) {
-    const uint32_t n_partials = c->frame.n_tiles < CM_MINMAX_BLOCKS ? c->frame.n_tiles : CM_MINMAX_BLOCKS;
+int measure_bounds(cm_ctx* c, uint32_t n_tiles, float mn[3], float mx[3], uint64_t* n_valid) {
+    const uint32_t n_partials = n_tiles < CM_MINMAX_BLOCKS ? n_tiles : CM_MINMAX_BLOCKS;
     cmk_minmax(c->stream, c->d_frame, c->partials, n_partials, nullptr);
     std::vector<float> rec(static_cast<size_t>(n_partials) * 8);
     HIP_TRY(c, hipMemcpyAsync(rec.data(), c->partials, rec.size() * 4, hipMemcpyDeviceToHost, c->stream));
@@ -637,7 +650,7 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
 
     std::vector<std::unique_lock<std::mutex>> locks;
     c->prof_used = 0;                                // (k_motion, when compensation is on, is the frame's first stage)
-    const int bf = build_frame(c, p, true, locks);
+    const int bf = build_frame(c, p, nullptr, locks);
     if (bf != CM_OK) return bf;
     CmFrameDev& f = c->frame;
     if (mode == 1 && bounds) {
@@ -651,7 +664,7 @@ int enqueue(cm_ctx* c, const cm_params* p, int mode, const float* bounds) {
             if (descriptor_changed(c)) cmk_setup(c->stream, f, c->d_frame, c->d_tiles);
             float mn[3], mx[3];
             uint64_t cnt = 0;
-            const int e = measure_bounds(c, mn, mx, &cnt);
+            const int e = measure_bounds(c, f.n_tiles, mn, mx, &cnt);
             if (e != CM_OK) return e;
             if (cnt) sor_cell_m = sor_bounds_cell(sor_cell_m, mn, mx, &kb_o);
         }
