@@ -139,7 +139,10 @@ typedef struct cm_stage_times {
 /* Allocates the context, its stream and HBM work buffers on `device`. */
 CM_API int cm_create(cm_ctx** out, int device, const cm_limits* limits);
 CM_API int cm_destroy(cm_ctx* ctx);
-/* Run on a caller-owned hipStream_t (NULL: back to the context's own stream). */
+/* Run on a caller-owned hipStream_t (NULL: back to the context's own stream). A handle of 0 is NULL: it does NOT name the
+ * legacy default stream. torch.cuda.current_stream().cuda_stream is 0 on torch's default stream, so passing it selects the
+ * context's own stream, which is non-blocking and therefore not ordered behind the default stream: a caller on the default
+ * stream synchronises by hand (or creates a stream and passes that). Refused while a frame is in flight. */
 CM_API int cm_set_stream(cm_ctx* ctx, void* hip_stream);
 
 /* ---- static transforms: replaces tf::Transform(stf.getRotation(), stf.getOrigin()) (:320,:346,

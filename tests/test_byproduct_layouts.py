@@ -62,6 +62,12 @@ TILTS = [(0.0, 0.0), (0.02, -0.01), (0.0, 0.03), (-0.015, 0.0), (0.01, 0.01), (0
 NAN_PAYLOAD = 0x7FC00ABC
 # hand-placed world points outside the crop box, inside the grid, beside wall cells that are counted
 OUTSIDE = [(12.1, 1.0, 0.5), (-12.2, -2.0, 0.4), (3.0, 11.2, 0.6), (2.0, 2.0, 3.2)]
+COST_ARGS = (0.0, 1.0, 3.0, False)                     # cm_map_cost_configure's arguments
+
+
+def parameter_set(grid=GRID, mq=MQ, match=MATCH_Q, search=SEARCH_Q, mcl=MCL_Q, cost=COST_ARGS):
+    """What by_products() configures and restated() restates; the defaults are the module's constants."""
+    return dict(grid=grid, mq=mq, match=match, search=search, mcl=mcl, cost=cost)
 
 
 def pose_of(s):
@@ -141,9 +147,11 @@ def struct_bytes(s):
     return bytes(s)
 
 
-def by_products(cm, n_cap=N_CAP):
+def by_products(cm, n_cap=N_CAP, pset=None):
     """grid_map, grid_rays, map_configure + map_integrate, map_cost_update, map_match, map_match_search and a seeded
-    map_mcl_init_pose / predict / update on the context's last frame. Returns {name: bytes}."""
+    map_mcl_init_pose / predict / update on the context's last frame. Returns {name: bytes}. pset: a parameter_set()."""
+    pset = pset or parameter_set()
+    GRID, MQ, MATCH_Q, SEARCH_Q, MCL_Q = (pset[k] for k in ("grid", "mq", "match", "search", "mcl"))
     out = {}
     out["merged"] = cm.merged(n_cap).tobytes()
     out["grid"] = cm.grid_map(*GRID).tobytes()
@@ -156,7 +164,7 @@ def by_products(cm, n_cap=N_CAP):
     table, image, dev = tm.read_map(cm, info)
     assert dev.tobytes() == table.tobytes()
     out["map"], out["map_image"], out["map_info"] = table.tobytes(), image.tobytes(), repr(tm.info_tuple(info)).encode()
-    cm.map_cost_configure(0.0, 1.0, 3.0, False)
+    cm.map_cost_configure(*pset["cost"])
     cm.map_cost_update()
     cost, dist2, _ = cm.map_cost()
     out["cost"], out["dist2"] = cost.tobytes(), dist2.tobytes()
@@ -220,9 +228,12 @@ def TAB():
     return _tab[0]
 
 
-def restated(frame, dropped=None, guard=True):
+def restated(frame, dropped=None, guard=True, pset=None, counts=COUNTS):
     """{name: bytes} of by_products()' outputs that a restatement defines, from a frame_host frame alone. The vacuity guards are
-    conditions on this reference: they are checked here, before any device output is looked at."""
+    conditions on this reference: they are checked here, before any device output is looked at. pset: a parameter_set();
+    counts: the points per sensor the scene was made with."""
+    pset = pset or parameter_set()
+    GRID, MQ, MATCH_Q, SEARCH_Q, MCL_Q = (pset[k] for k in ("grid", "mq", "match", "search", "mcl"))
     A, tag = frame.A, frame.sensor
     NO_G = np.zeros((0, 4), F32)
     origin, cell, nx, ny, band, height, min_points = GRID
@@ -274,7 +285,7 @@ def restated(frame, dropped=None, guard=True):
         assert near >= 1, "no dropped point lies beside a counted cell"
         for s, d in enumerate(dropped):
             assert not set(d) & set(frame.index[tag == s].tolist()), f"sensor {s}: a hand-placed value was not dropped"
-            assert d == [] or (tag == s).sum() == COUNTS[s] - len(d)
+            assert d == [] or (tag == s).sum() == counts[s] - len(d)
     return want, structs
 
 
